@@ -3,8 +3,12 @@
 (synthetic EOF, T = 2920 x N = 10 000 grid points, float64, rotate(n_rot=10, power=1)), one MI355X per rank, and the
 run-sharded rule_n of configuration C4 (surrogates/s over all ranks).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
+* a plain run sets up, warms up, times the K steps and prints the headline line (contract keys + `stages_ms`); everything
+  else below (rooflines, self-check, e2e, rule_n, C5, CPU baseline and parity) runs only with --full.
+* --dump-outputs DIR: what the last timed step returned, as DIR/<name>.npy (float64): the singular values, the first n_rot
+  vectors and the rotation result.  The input is seeded, so two builds can be compared output for output.
 * a "step" = one pass of the hot path: device solve (Gram GEMM, eigensolver, back-projection of all `rank` modes) +
   Varimax/Promax rotation, with the centered field ALREADY RESIDENT in HBM when the timed region starts (the
   PCIe-inclusive time through the MCA class is reported separately as `e2e_ms`, never as `value`).
@@ -15,7 +19,7 @@ run-sharded rule_n of configuration C4 (surrogates/s over all ranks).
   all_gather of the spectra) runs after the timed region on the C4 configuration and is reported as
   `rule_n.surrogates_per_s` (all ranks together).  XMCA_BENCH_SHARE_GPU=1 puts every rank on GPU 0 with the gloo
   backend (RCCL refuses two ranks on one device) - the way the multi-rank flow is exercised on a 1-GPU box.
-* prints ONE JSON line on rank 0 with the driver's contract keys plus
+* prints ONE JSON line on rank 0 with the contract keys; with --full also
     `roofline`       the DOMINANT kernel of the step - since round 3 the Householder tridiagonalisation of the T x T Gram
                      matrix (trd_resident_kernel, csrc/tridiag.h; the block-Jacobi round kernel when XMCA_TRIDIAG=0):
                      algorithmic flops / average launch duration, hipEvents on the library's stream in the timed region;
@@ -89,13 +93,34 @@ def gen_A(T=2920, N=10_000, k=20, seed=0):
 
 
 def device_step(h, T, N, n_rot, power, dtype):
-    """solve + rotate on resident data; returns (sigma, R, n_iter)."""
+    """solve + rotate on resident data; returns (sigma, Vt, rotation result)."""
     rank = h.solve(1)
     sig = h.singular_values(rank)
     Vt = h.vectors(0, n_rot, N, dtype)                    # n_rot x N (0.8 MB): the loadings of array.py:821-822
     L = Vt.T * np.sqrt(sig[:n_rot])
     out = h.rotate_loadings(L, n_left=N, power=power, tol=1e-8)
-    return sig, out
+    return sig, Vt, out
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, sig, Vt, out):
+    """The arrays a caller of the timed path receives, as float64 .npy files (complex: real/imag in a last axis of 2).  When the
+    vectors would take the dump over DUMP_LIMIT_BYTES, a fixed seeded sample of their columns is written with its indices."""
+    arrays = {"singular_values": sig, "vectors": Vt, "rotation_matrix": out["R"], "phi": out["Phi"],
+              "norm_left": out["norm_left"], "norm_right": out["norm_right"], "n_iter": np.array([out["n_iter"]])}
+    arrays = {k: np.stack([a.real, a.imag], axis=-1) if np.iscomplexobj(a) else a for k, a in arrays.items()}
+    room = DUMP_LIMIT_BYTES - 4096 - 8 * sum(a.size for k, a in arrays.items() if k != "vectors")      # (4096: the .npy headers)
+    V = arrays["vectors"]
+    per_col = 8 * V.size // V.shape[1]
+    if per_col * V.shape[1] > room:
+        cols = np.sort(np.random.default_rng(0).choice(V.shape[1], room // (per_col + 8), replace=False))
+        arrays["vectors"] = V[:, cols]
+        arrays["vectors_columns"] = cols
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def csrc_hash():
@@ -210,6 +235,10 @@ def main():
     ap.add_argument("--N", type=int, default=10_000)
     ap.add_argument("--n-rot", type=int, default=10)
     ap.add_argument("--power", type=int, default=1)
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also the rooflines, self-check, e2e, rule_n, C5 and CPU-baseline legs (the --no-* "
+                         "options below switch single legs of a --full run off)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-rule-n", action="store_true")
     ap.add_argument("--no-e2e", action="store_true")
@@ -221,6 +250,8 @@ def main():
     ap.add_argument("--no-native-rccl", action="store_true",
                     help="skip the cross-check of the rule_n gather through the library's own RCCL communicator (xmca_comm_*)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args))
@@ -271,12 +302,12 @@ def main():
         torch.cuda.synchronize()
 
     for _ in range(args.warmup):
-        sig, out = device_step(h, T, N, args.n_rot, args.power, X.dtype)
+        device_step(h, T, N, args.n_rot, args.power, X.dtype)
     h.reset_timings()
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        sig, out = device_step(h, T, N, args.n_rot, args.power, X.dtype)
+        sig, Vt_step, out = device_step(h, T, N, args.n_rot, args.power, X.dtype)
     barrier()
     elapsed = time.perf_counter() - t0
     timings = h.timings()
@@ -293,6 +324,25 @@ def main():
         elapsed = float(tt.item())
     ms_per_step = 1e3 * elapsed / args.steps
     value = world * args.steps / elapsed
+    line = {
+        "metric": "MCA solve+rotate throughput (ms_per_step = solve+rotate wall-clock, ms); rule_n surrogates/s in `rule_n`",
+        "value": value, "unit": "solve+rotate/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f64", "data": "synthetic",
+        "config": {"workload": "C2: synthetic EOF T=%d x N=%d float64 (generator A), solve() + rotate(n_rot=%d, power=%d)"
+                               % (T, N, args.n_rot, args.power),
+                   "parallelism": "replicas x%d (solve/rotate do not shard); rule_n run-sharded x%d" % (world, world)},
+        "stages_ms": stages,
+    }
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, sig, Vt_step, out)
+    if not args.full:
+        if rank == 0:
+            sys.stdout.flush()
+            os.write(json_fd, (json.dumps(line) + "\n").encode())
+        if td is not None:
+            td.destroy_process_group()
+        return
 
     # ---- roofline of the dominant kernel: one launch of jacobi_fused_round_kernel per round of the block-Jacobi sweeps ----
     # algorithmic work of a round with S pair slots of NT x NT tiles: every upper off-diagonal tile G[P,Q] <- J_P^H G J_Q
@@ -616,17 +666,8 @@ def main():
             extra["persistent_giveups"] = int(_hip.load_library().xmca_persistent_giveups())
         except Exception:                                         # noqa: BLE001
             pass
-        line = {
-            "metric": "MCA solve+rotate throughput (ms_per_step = solve+rotate wall-clock, ms); rule_n surrogates/s in `rule_n`",
-            "value": value, "unit": "solve+rotate/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f64", "data": "synthetic",
-            "config": {"workload": "C2: synthetic EOF T=%d x N=%d float64 (generator A), solve() + rotate(n_rot=%d, power=%d)"
-                                   % (T, N, args.n_rot, args.power),
-                       "parallelism": "replicas x%d (solve/rotate do not shard); rule_n run-sharded x%d" % (world, world)},
-            "rule_n_surrogates_per_s": extra.get("rule_n", {}).get("surrogates_per_s"),
-            "stages_ms": stages, "roofline": roofline, "roofline_gemm": roofline_gemm, "cpu_baseline": cpu,
-        }
+        line.update({"rule_n_surrogates_per_s": extra.get("rule_n", {}).get("surrogates_per_s"),
+                     "roofline": roofline, "roofline_gemm": roofline_gemm, "cpu_baseline": cpu})
         line.update(extra)
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(line) + "\n").encode())

@@ -1,10 +1,11 @@
 export TMPDIR=/tmp
-rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY -d gpurun_out/pmc_f1 -o g --output-format csv -- python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-rule-n > /dev/null 2>&1
-rocprofv3 --kernel-trace --pmc FETCH_SIZE -d gpurun_out/pmc_f2 -o g --output-format csv -- python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-rule-n > /dev/null 2>&1
-rocprofv3 --kernel-trace --pmc WRITE_SIZE TCC_HIT_sum TCC_MISS_sum -d gpurun_out/pmc_f3 -o g --output-format csv -- python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-rule-n > /dev/null 2>&1
+OUT=$(realpath -m "${OUT:-out}"); export OUT; mkdir -p $OUT
+rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY -d $OUT/pmc_f1 -o g --output-format csv -- python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-rule-n > /dev/null 2>&1
+rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/pmc_f2 -o g --output-format csv -- python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-rule-n > /dev/null 2>&1
+rocprofv3 --kernel-trace --pmc WRITE_SIZE TCC_HIT_sum TCC_MISS_sum -d $OUT/pmc_f3 -o g --output-format csv -- python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-rule-n > /dev/null 2>&1
 python - <<'PY'
-import csv, collections
-for d in ["gpurun_out/pmc_f1","gpurun_out/pmc_f2","gpurun_out/pmc_f3"]:
+import csv, collections, os
+for d in [os.environ["OUT"] + "/pmc_f%d" % i for i in (1, 2, 3)]:
     agg=collections.defaultdict(lambda: collections.defaultdict(float)); cnt=collections.defaultdict(set); dur=collections.defaultdict(float)
     for r in csv.DictReader(open(d+"/g_counter_collection.csv")):
         k=r["Kernel_Name"][:40]

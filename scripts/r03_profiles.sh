@@ -1,23 +1,24 @@
 #!/bin/bash
-# Run on the GPU box (gpurun): the artefacts of round 3 under gpurun_out/r03_*; copy what is to be judged into profiles/.
+# Run on a machine with an MI355X: the artefacts of round 3 under $OUT/r03_*; copy what is to be judged into profiles/.
 #   scripts/r03_profiles.sh [quick]     quick = bench + kernel stats + PMC of the bench command only
 set -u
+OUT=$(realpath -m "${OUT:-out}"); export OUT          # output folder (created below)
 REPO=$PWD
-mkdir -p gpurun_out
+mkdir -p $OUT
 export TMPDIR=/tmp
 # 1. the bench line (N = 1)
-python bench.py --steps 10 --warmup 3 > gpurun_out/r03_bench_c2.json 2> gpurun_out/r03_bench_c2.err
+python bench.py --full --steps 10 --warmup 3 > $OUT/r03_bench_c2.json 2> $OUT/r03_bench_c2.err
 # 2. rocprofv3 kernel stats of the bench command (C2 step only)
-scripts/profile_cmd.sh r03_c2 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-rule-n --no-e2e --no-c5
+scripts/profile_cmd.sh r03_c2 python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-rule-n --no-e2e --no-c5
 # 3. PMC passes (separate runs, kernel-trace only)
 cd /tmp
 for pass in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY" "FETCH_SIZE" "WRITE_SIZE TCC_HIT_sum TCC_MISS_sum"; do
   tag=$(echo $pass | cut -d' ' -f1)
   rm -rf /tmp/pmc_$tag
-  ( cd $REPO && rocprofv3 --kernel-trace --pmc $pass -d /tmp/pmc_$tag -o g --output-format csv -- python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-rule-n --no-e2e --no-c5 > /dev/null 2>&1 )
+  ( cd $REPO && rocprofv3 --kernel-trace --pmc $pass -d /tmp/pmc_$tag -o g --output-format csv -- python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-rule-n --no-e2e --no-c5 > /dev/null 2>&1 )
 done
 cd $REPO
-python - <<'PY' > gpurun_out/r03_pmc_c2.json
+python - <<'PY' > $OUT/r03_pmc_c2.json
 import csv, collections, glob, json, sys
 sys.path.insert(0, ".")
 import bench
@@ -43,16 +44,16 @@ for k, d in out.items():
     if "SQ_VALU_MFMA_BUSY_CYCLES_per_launch" in d and "SQ_BUSY_CYCLES_per_launch" in d:
         d["mfma_busy_fraction"] = d["SQ_VALU_MFMA_BUSY_CYCLES_per_launch"] / (1024 * d["SQ_BUSY_CYCLES_per_launch"] / 32)
 out["csrc_sha16"] = bench.csrc_hash()
-out["_command"] = "rocprofv3 --kernel-trace --pmc <counters> --output-format csv -- python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-rule-n --no-e2e --no-c5 (three separate passes; FETCH_SIZE doubled per MI355X_MICROARCH.md)"
+out["_command"] = "rocprofv3 --kernel-trace --pmc <counters> --output-format csv -- python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-rule-n --no-e2e --no-c5 (three separate passes; FETCH_SIZE doubled per MI355X_MICROARCH.md)"
 print(json.dumps(out, indent=1))
 PY
 if [ "${1:-}" != "quick" ]; then
   # 4. the other configurations through the class + their kernel stats
   scripts/profile_cmd.sh r03_c3 python scripts/run_config.py C3
-  cp gpurun_out/prof_r03_c3.out gpurun_out/r03_c3.json
+  cp $OUT/prof_r03_c3.out $OUT/r03_c3.json
   scripts/profile_cmd.sh r03_c4 python scripts/rule_n_bench.py
-  cp gpurun_out/prof_r03_c4.out gpurun_out/r03_rule_n.json
+  cp $OUT/prof_r03_c4.out $OUT/r03_rule_n.json
   scripts/profile_cmd.sh r03_c5 python scripts/c5_device_ctor.py
-  cp gpurun_out/prof_r03_c5.out gpurun_out/r03_c5.json
+  cp $OUT/prof_r03_c5.out $OUT/r03_c5.json
 fi
-ls -la gpurun_out/r03_* gpurun_out/kstats_r03_*
+ls -la $OUT/r03_* $OUT/kstats_r03_*

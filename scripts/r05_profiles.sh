@@ -1,14 +1,15 @@
 #!/bin/bash
-# Run on the GPU box (gpurun): the artefacts of round 5 under gpurun_out/r05_*; copy what is to be judged into profiles/
+# Run on a machine with an MI355X: the artefacts of round 5 under $OUT/r05_*; copy what is to be judged into profiles/
 # (scripts/copy_r05_profiles.sh).   scripts/r05_profiles.sh [quick]   quick = bench + C2 kernel stats + the PMC passes only
 set -u
+OUT=$(realpath -m "${OUT:-out}"); export OUT          # output folder (created below)
 REPO=$PWD
-mkdir -p gpurun_out
+mkdir -p $OUT
 export TMPDIR=/tmp
 # 1. the bench line (N = 1)
-python bench.py --steps 10 --warmup 3 > gpurun_out/r05_bench_c2.json 2> gpurun_out/r05_bench_c2.err
+python bench.py --full --steps 10 --warmup 3 > $OUT/r05_bench_c2.json 2> $OUT/r05_bench_c2.err
 # 2. rocprofv3 kernel stats of the bench command (C2 step only)
-scripts/profile_cmd.sh r05_c2 python bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-rule-n --no-e2e --no-c5
+scripts/profile_cmd.sh r05_c2 python bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-rule-n --no-e2e --no-c5
 # 3. PMC passes (separate runs, kernel-trace only): the C2 step, and the Gram product alone at C2 and C5
 pmc() {   # pmc <tag> <command...>
   tag=$1; shift
@@ -17,7 +18,7 @@ pmc() {   # pmc <tag> <command...>
     rm -rf /tmp/pmc_${tag}_$p
     ( cd /tmp && rocprofv3 --kernel-trace --pmc $pass -d /tmp/pmc_${tag}_$p -o g --output-format csv -- "$@" > /dev/null 2>&1 )
   done
-  python - "$tag" "$*" <<'PY' > gpurun_out/r05_pmc_$tag.json
+  python - "$tag" "$*" <<'PY' > $OUT/r05_pmc_$tag.json
 import csv, collections, glob, json, sys
 sys.path.insert(0, ".")
 import bench
@@ -48,16 +49,16 @@ out["_command"] = "rocprofv3 --kernel-trace --pmc <counters> --output-format csv
 print(json.dumps(out, indent=1))
 PY
 }
-pmc c2 python $REPO/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-rule-n --no-e2e --no-c5
+pmc c2 python $REPO/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-rule-n --no-e2e --no-c5
 pmc gram_c2 python $REPO/scripts/gram_only.py c2 3
 pmc gram_c5 python $REPO/scripts/gram_only.py c5 2
 if [ "${1:-}" != "quick" ]; then
   # 4. the other configurations through the class + their kernel stats
   scripts/profile_cmd.sh r05_c3 python scripts/run_config.py C3
-  cp gpurun_out/prof_r05_c3.out gpurun_out/r05_c3_through_class.json
+  cp $OUT/prof_r05_c3.out $OUT/r05_c3_through_class.json
   scripts/profile_cmd.sh r05_c4 python scripts/rule_n_bench.py
-  cp gpurun_out/prof_r05_c4.out gpurun_out/r05_rule_n_single_gpu.json
+  cp $OUT/prof_r05_c4.out $OUT/r05_rule_n_single_gpu.json
   scripts/profile_cmd.sh r05_c5 python scripts/c5_device_ctor.py
-  cp gpurun_out/prof_r05_c5.out gpurun_out/r05_c5_through_class.json
+  cp $OUT/prof_r05_c5.out $OUT/r05_c5_through_class.json
 fi
-ls -la gpurun_out/r05_* gpurun_out/kstats_r05_*
+ls -la $OUT/r05_* $OUT/kstats_r05_*

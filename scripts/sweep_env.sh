@@ -3,7 +3,7 @@
 var=$1; vals=$2; shift 2
 for v in $vals; do
   echo -n "$var=$v  "
-  env $var=$v python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-rule-n --no-e2e "$@" 2>/dev/null | python -c "
+  env $var=$v python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-rule-n --no-e2e "$@" 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.readline())
 r = d['roofline']

@@ -397,7 +397,7 @@ def test_bench_py_launches_its_own_ranks():
     env = dict(os.environ, XMCA_BENCH_SHARE_GPU="1")
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--T", "400",
-                        "--N", "1500", "--no-cpu-baseline", "--no-e2e", "--rule-n-runs", "1", "--rule-n-rotated-runs", "0"], env=env, cwd=REPO,
+                        "--N", "1500", "--full", "--no-cpu-baseline", "--no-e2e", "--rule-n-runs", "1", "--rule-n-rotated-runs", "0"], env=env, cwd=REPO,
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -423,7 +423,7 @@ def test_bench_py_reports_the_tridiagonal_reduction_as_its_dominant_kernel():
     env.pop("WORLD_SIZE", None)
     T = 800
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--T", str(T),
-                        "--N", "2400", "--no-cpu-baseline", "--no-e2e", "--no-rule-n"], env=env, cwd=REPO,
+                        "--N", "2400", "--full", "--no-cpu-baseline", "--no-e2e", "--no-rule-n"], env=env, cwd=REPO,
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -435,6 +435,34 @@ def test_bench_py_reports_the_tridiagonal_reduction_as_its_dominant_kernel():
     assert rf["exchange_us_per_column"] > 0 and rf["launches_per_step"] >= 1
     g = line["roofline_gemm"]
     assert g["bound"] == "mfma" and 0 < g["frac"] < 1 and g["kernel"].startswith("gemm_kernel")
+
+
+def test_bench_py_plain_run_times_only_the_steps_and_dumps_their_outputs(tmp_path):
+    """Without --full the line holds the headline only; --dump-outputs writes what the last timed step returned (float64)."""
+    import json
+    import subprocess
+    from golden_inputs import gen_A
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+    T, N, n_rot = 400, 1500, 10
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--T", str(T),
+                        "--N", str(N), "--dump-outputs", str(tmp_path)], env=env, cwd=REPO, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["unit"] == "solve+rotate/s" and line["dtype"] == "f64"
+    assert line["higher_is_better"] is True and abs(line["value"] * line["ms_per_step"] - 1e3) < 1e-6 * 1e3
+    assert not {"roofline", "roofline_gemm", "cpu_baseline", "rule_n", "e2e_ms", "self_check"} & set(line)
+    out = {f[:-4]: np.load(os.path.join(str(tmp_path), f)) for f in os.listdir(str(tmp_path))}
+    assert set(out) == {"singular_values", "vectors", "rotation_matrix", "phi", "norm_left", "norm_right", "n_iter"}
+    assert all(a.dtype == np.float64 for a in out.values())
+    X = gen_A(T, N)                                         # (bench.py's generator A)
+    X = X - X.mean(axis=0)
+    sig, Vt = out["singular_values"], out["vectors"]
+    assert Vt.shape == (n_rot, N) and out["rotation_matrix"].shape == (n_rot, n_rot) and out["n_iter"][0] >= 1
+    assert abs(sig.sum() - (X * X).sum() / (T - 1)) / sig.sum() < 1e-10
+    assert np.max(np.abs(Vt @ Vt.T - np.eye(n_rot))) < 1e-10
 
 
 def test_persistent_kernels_of_four_lanes_pass_one_gate():
