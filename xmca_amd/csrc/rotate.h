@@ -2242,6 +2242,262 @@ __global__ __launch_bounds__(256) void varimax_persistent_kernel(const double* _
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Varimax on the fourth moments (real loadings, p <= ROT_MOMENT_PMAX).  With Z = A R the cubic term of G is
+//     G1_ij = sum_n a_ni z_nj^3 = sum_{k,l,m} M_iklm R_kj R_lj R_mj,      M_iklm = sum_n a_ni a_nk a_nl a_nm,
+// and M is symmetric in all four indices.  Over the P = p (p + 1) / 2 unordered pairs u = (l <= m):
+//     Q_nu = a_nl a_nm,   M'_uv = sum_n Q_nu Q_nv   (P x P),   S_uj = w_u R_lj R_mj   (w_u = 1 if l = m, else 2),
+//     Y = M' S   (P x p),    G1_ij = sum_k R_kj Y_(ik),j ,       G = G1 - (gamma / N) (A0 R) diag(c).
+// One pass over the loadings builds M' (rot_moment_kernel); after it an iteration costs ~2 P^2 p flops whatever N is,
+// so the whole loop runs in ONE workgroup with M' in registers (varimax_moment_kernel): no exchange between workgroups.
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int ROT_MOMENT_PMAX = 12;
+constexpr int ROT_MOMENT_PAIRS = ROT_MOMENT_PMAX * (ROT_MOMENT_PMAX + 1) / 2;    // 78
+constexpr int ROT_MOMENT_QROWS = (ROT_MOMENT_PAIRS + 3) / 4 * 4;                  // 80: Q padded to 4-row blocks
+__host__ __device__ static inline int rot_moment_pairs(int p) { return p * (p + 1) / 2; }
+__host__ __device__ static inline int rot_moment_blocks(int p) { return (rot_moment_pairs(p) + 3) / 4; }
+// M' is kept as the upper triangle of its 4 x 4 blocks: block (bu <= bv) at bu nb - bu (bu - 1) / 2 + bv - bu, 16 entries each
+__host__ __device__ static inline int rot_moment_entries(int p) {
+  const int nb = rot_moment_blocks(p);
+  return nb * (nb + 1) / 2 * 16;
+}
+// pair u -> (l, m), l <= m, in the order (0,0) (0,1) ... (0,p-1) (1,1) ...
+__device__ __forceinline__ void rot_moment_pair(int p, int u, int& l, int& m) {
+  l = 0;
+  while (u >= p - l) { u -= p - l; ++l; }
+  m = l + u;
+}
+
+// Per-workgroup partial of M' (fixed tiles per workgroup, fixed order): part[blockIdx.x * entries + e].
+// Thread t < nb (nb + 1) / 2 owns one 4 x 4 block of M' and adds, point by point, the products of the Q tile in LDS.
+__global__ __launch_bounds__(256) void rot_moment_kernel(const double* __restrict__ Ar, int64_t N, int p, double* __restrict__ part) {
+  __shared__ double As[ROT_MOMENT_PMAX][ROT_LDP];
+  __shared__ double Qs[ROT_MOMENT_QROWS][ROT_LDP];
+  __shared__ int pl[ROT_MOMENT_QROWS], pm[ROT_MOMENT_QROWS];
+  const int tid = threadIdx.x;
+  const int P = rot_moment_pairs(p), nb = rot_moment_blocks(p), nbp = nb * (nb + 1) / 2;
+  if (tid < P) rot_moment_pair(p, tid, pl[tid], pm[tid]);
+  int bu = 0, bv = 0;
+  if (tid < nbp) {
+    int r = tid;
+    while (r >= nb - bu) { r -= nb - bu; ++bu; }
+    bv = bu + r;
+  }
+  double acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) acc[i][k] = 0.0;
+  const int64_t nbatch = (N + ROT_PB - 1) / ROT_PB;
+  for (int64_t bt = blockIdx.x; bt < nbatch; bt += gridDim.x) {
+    const int64_t n0 = bt * ROT_PB;
+    __syncthreads();
+    for (int e = tid; e < p * ROT_PB; e += 256) {
+      const int j = e / ROT_PB, pt = e % ROT_PB;
+      const int64_t n = n0 + pt;
+      As[j][pt] = n < N ? Ar[(int64_t)j * N + n] : 0.0;
+    }
+    __syncthreads();
+    for (int e = tid; e < nb * 4 * ROT_PB; e += 256) {
+      const int u = e / ROT_PB, pt = e % ROT_PB;
+      Qs[u][pt] = u < P ? As[pl[u]][pt] * As[pm[u]][pt] : 0.0;
+    }
+    __syncthreads();
+    if (tid < nbp) {
+#pragma unroll 4
+      for (int pt = 0; pt < ROT_PB; ++pt) {
+        double qa[4], qb[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { qa[i] = Qs[4 * bu + i][pt]; qb[i] = Qs[4 * bv + i][pt]; }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int k = 0; k < 4; ++k) acc[i][k] = fma(qa[i], qb[k], acc[i][k]);
+      }
+    }
+  }
+  if (tid < nbp) {
+    double* dst = part + (int64_t)blockIdx.x * rot_moment_entries(p) + 16 * tid;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) dst[4 * i + k] = acc[i][k];
+  }
+}
+
+// M'_uv from the block layout of rot_moment_kernel (either triangle: the diagonal blocks hold both)
+__device__ __forceinline__ double rot_moment_at(const double* __restrict__ mom, int nb, int u, int v) {
+  if (u / 4 > v / 4) { const int t = u; u = v; v = t; }
+  const int bu = u / 4, bv = v / 4;
+  return mom[(bu * nb - bu * (bu - 1) / 2 + bv - bu) * 16 + (u % 4) * 4 + v % 4];
+}
+
+// The whole Varimax loop (real, p = PT <= 12) in one workgroup.  Y = M' S is formed in one of two ways:
+//   P <= 64 (p <= 10): Y^T = S^T M' by MFMA, wave w forms the columns u = 16 w ... 16 w + 15 with M' in the B operand
+//     registers and S^T formed from R in the A operand registers: no S step, no partial sums.
+//   P > 64 (p = 11, 12): thread t < NCH P holds the M' entries (u, c CK ... c CK + CK - 1), u = t % P, c = t / P, and forms
+//     that slice of row u of Y for every column; the NCH partial rows are added in order inside the G step.
+// The polar step is varimax_polar_wave16_full, as in the persistent kernel; R, c and the state block stay in LDS and go out
+// once behind the loop (as varimax_persistent_kernel).  Everything is sized at compile time (one instance per p): with
+// run-time trip counts the LDS loads of the Y and G steps could not be hoisted past the loop guards and every one of them paid
+// its full latency (3.2k + 5.5k cycles per iteration at p = 10).
+template <int PT>
+__global__ __launch_bounds__(256) void varimax_moment_kernel(const double* __restrict__ mom, int64_t N, const double* __restrict__ A0r,
+                                                             double* __restrict__ Rr, double* __restrict__ cvec, double* __restrict__ state,
+                                                             double tol, int max_iter, double gamma) {
+  constexpr int p = PT, pp = p * p, P = p * (p + 1) / 2;
+  constexpr bool COLS = P <= 64;
+  constexpr int NCH = COLS ? 1 : ((256 / P) < 8 ? (256 / P) : 8);   // slices of the contraction index of Y
+  constexpr int CK = COLS ? P : (P + NCH - 1) / NCH;                  // not COLS: M' entries per thread
+  constexpr int PC = p + (p & 1);                                     // not COLS: columns of S and Y (16-byte reads of an S row)
+  constexpr int KS = (P + 3) / 4;                                     // COLS: k-steps of the MFMA product
+  constexpr int SROWS = NCH * CK;                                     // rows of S (not COLS: P .. SROWS - 1 stay zero)
+  constexpr int SN = COLS ? 2 : SROWS * PC;                          // (COLS: no S in LDS)
+  constexpr int SE = (P * PC + 255) / 256;                            // S entries per thread
+  constexpr int NR = (p + 3) / 4;                                     // k-steps of the one-wave polar step
+  static_assert(p >= 2 && p <= ROT_MOMENT_PMAX && NCH * P <= 256, "");
+  __shared__ double Rl[pp], A0l[pp], Gl[pp], cl[p], stl[ROT_STATE_N];
+  __shared__ __attribute__((aligned(16))) double Sl[SN];
+  __shared__ double Yp[COLS ? p * P : NCH * P * PC];        // COLS: Y^T (rows j, pitch P); else the NCH partial rows of Y
+  __shared__ int pidx[pp];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int u = COLS ? lane : tid % P, c = COLS ? 0 : tid / P;
+  const bool yt = COLS ? lane < P : c < NCH;
+  for (int e = tid; e < pp; e += 256) { Rl[e] = Rr[e]; A0l[e] = A0r[e]; }
+  if (tid < p) cl[tid] = cvec[tid];
+  if (tid < ROT_STATE_N) stl[tid] = state[tid];
+  if (tid < P) {
+    int l, m;
+    rot_moment_pair(p, tid, l, m);
+    pidx[l * p + m] = tid;
+    pidx[m * p + l] = tid;
+  }
+  for (int e = tid; e < SN; e += 256) Sl[e] = 0.0;       // padding (never written below) stays zero
+  // M' in registers.  COLS: the B operands of the MFMA product, B[k][n] = M'(4 kk + k, 16 wave + n) with k = lane / 16,
+  // n = lane % 16; otherwise the slice (u, c CK + vv).
+  constexpr int MR = COLS ? KS : CK;
+  double mreg[MR];
+#pragma unroll
+  for (int vv = 0; vv < MR; ++vv) {
+    const int v = COLS ? 4 * vv + (lane >> 4) : c * CK + vv;
+    const int uu = COLS ? 16 * wave + (lane & 15) : u;
+    mreg[vv] = (COLS || yt) && v < P && uu < P ? rot_moment_at(mom, rot_moment_blocks(p), uu, v) : 0.0;
+  }
+  // what a thread reads in the S and G steps does not change from one iteration to the next: the addresses (and A0) are
+  // taken once.  S (not COLS): entries e = tid + 256 s of the P x PC matrix (u = e / PC, j = e % PC); G: entry (tid / p, tid % p).
+  int sa[SE], sb[SE], sd[SE];
+  double sw[SE];
+#pragma unroll
+  for (int s = 0; s < SE; ++s) {
+    const int e = tid + 256 * s, uu = e / PC, j = e % PC;
+    const bool live = e < P * PC && j < p;
+    int l = 0, m = 0;
+    if (live) rot_moment_pair(p, uu, l, m);
+    sa[s] = l * p + j;
+    sb[s] = m * p + j;
+    sw[s] = live ? (l == m ? 1.0 : 2.0) : 0.0;
+    sd[s] = e < P * PC ? e : -1;
+  }
+  // COLS: every wave multiplies the same S^T, so each forms its A operands itself from R (no S step, no barrier behind it):
+  // A[m][k] of k-step kk = S(4 kk + k, m) with m = lane % 16, k = lane / 16
+  constexpr int AK = COLS ? KS : 1;
+  int aa[AK], ab[AK];
+  double aw[AK];
+#pragma unroll
+  for (int kk = 0; kk < AK; ++kk) {
+    const int v = 4 * kk + (lane >> 4), j = lane & 15;
+    const bool live = v < P && j < p;
+    int l = 0, m = 0;
+    if (live) rot_moment_pair(p, v, l, m);
+    aa[kk] = l * p + (live ? j : 0);
+    ab[kk] = m * p + (live ? j : 0);
+    aw[kk] = live ? (l == m ? 1.0 : 2.0) : 0.0;
+  }
+  const double gn = gamma / (double)N;
+  __syncthreads();
+  const int gi = tid / p, gj = tid % p;
+  const bool gt = tid < pp;
+  int yoff[p];
+  double a0g[p];
+#pragma unroll
+  for (int k = 0; k < p; ++k) {
+    yoff[k] = gt ? (COLS ? gj * P + pidx[gi * p + k] : pidx[gi * p + k] * PC + gj) : 0;
+    a0g[k] = gt ? A0l[gi * p + k] : 0.0;
+  }
+  for (int it = 0; it < max_iter; ++it) {
+    if (stl[1] != 0.0 || stl[4] != 0.0) break;
+    ROT_STAMP(0);
+    // S_uj = w_u R_lj R_mj
+    if constexpr (!COLS) {
+#pragma unroll
+      for (int s = 0; s < SE; ++s)
+        if (sd[s] >= 0) Sl[sd[s]] = sw[s] * Rl[sa[s]] * Rl[sb[s]];
+      __syncthreads();
+    }
+    ROT_STAMP(1);
+    if constexpr (COLS) {
+      // Y^T = S^T M' (M' symmetric): wave w forms the 16 x 16 tile of rows j and columns u = 16 w + n by KS MFMAs
+      // (v_mfma_f64_16x16x4_f64; A = S^T formed from R, two accumulation chains added at the end).  LDS delivers two
+      // doubles per lane and MFMA; the VALU form read a double per FMA and was bound by the LDS bandwidth.
+      const d4_t zero = {0, 0, 0, 0};
+      d4_t acc0 = zero, acc1 = zero;
+#pragma unroll
+      for (int kk = 0; kk < KS; ++kk) {
+        const double sv = aw[kk] * Rl[aa[kk]] * Rl[ab[kk]];
+        if (kk & 1) acc1 = Mfma<double>::mma(sv, mreg[kk], acc1);
+        else acc0 = Mfma<double>::mma(sv, mreg[kk], acc0);
+      }
+      const int uu = 16 * wave + (lane & 15);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int j = Mfma<double>::row(lane, r);
+        if (j < p && uu < P) Yp[j * P + uu] = acc0[r] + acc1[r];
+      }
+    } else if (yt) {
+      // Y slice c of row u
+      double y[PC];
+#pragma unroll
+      for (int j = 0; j < PC; ++j) y[j] = 0.0;
+      const double* srow = Sl + c * CK * PC;
+#pragma unroll
+      for (int vv = 0; vv < CK; ++vv) {
+#pragma unroll
+        for (int j = 0; j < PC; j += 2) {
+          const double2 sv = *reinterpret_cast<const double2*>(srow + vv * PC + j);
+          y[j] = fma(mreg[vv], sv.x, y[j]);
+          y[j + 1] = fma(mreg[vv], sv.y, y[j + 1]);
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < PC; ++j) Yp[tid * PC + j] = y[j];
+    }
+    __syncthreads();
+    ROT_STAMP(2);
+    // G_ij = sum_k R_kj Y_(ik),j - (gamma / N) c_j (A0 R)_ij
+    if (gt) {
+      double g1 = 0.0, a = 0.0;
+#pragma unroll
+      for (int k = 0; k < p; ++k) {
+        double yk = 0.0;
+#pragma unroll
+        for (int cc = 0; cc < NCH; ++cc) yk += Yp[cc * P * PC + yoff[k]];
+        const double rk = Rl[k * p + gj];
+        g1 = fma(rk, yk, g1);
+        a = fma(a0g[k], rk, a);
+      }
+      Gl[tid] = g1 - gn * cl[gj] * a;
+    }
+    __syncthreads();
+    ROT_STAMP(3);
+    if (tid < 64) varimax_polar_wave16_full<false, NR>(Gl, nullptr, p, A0l, nullptr, Rl, nullptr, cl, stl, tol);
+    __syncthreads();
+    ROT_STAMP(4);
+  }
+  for (int e = tid; e < pp; e += 256) Rr[e] = Rl[e];
+  if (tid < p) cvec[tid] = cl[tid];
+  if (tid < ROT_STATE_N) state[tid] = stl[tid];
+}
+
 // B[n][k] = scale_n * sum_j a_j(n) M[j][k]   ->  N x p row-major (interleaved complex) for the host
 template <bool CPLX>
 __global__ void rot_apply_kernel(const double* __restrict__ Ar, const double* __restrict__ Ai, const double* __restrict__ h,

@@ -1296,6 +1296,7 @@ struct RotationDevice {
   DevBuf<unsigned int> counter;     // arrival ticket of the fused Varimax iteration kernel
   DevBuf<unsigned int> pflags;      // persistent Varimax kernel: epoch flag per workgroup
   DevBuf<double> ppart_r, ppart_i;  // ... and its double-buffered partials
+  DevBuf<double> mpart, mom;        // fourth-moment route (real, p <= ROT_MOMENT_PMAX): per-workgroup partials of M', M'
   int64_t N = 0, Nleft = 0;
   int p = 0;
   bool cplx = false;
@@ -1369,6 +1370,39 @@ class Rotator {
     if (!d.counter.get()) { d.counter.ensure(1); XMCA_HIP(hipMemsetAsync(d.counter.get(), 0, sizeof(unsigned int), st)); }
   }
 
+  // Varimax on the fourth moments (rotate.h, real loadings, p <= ROT_MOMENT_PMAX): one pass over the loadings builds the
+  // P x P pair moments M' (per-workgroup partials summed in a fixed order: the same bits on every run), then the whole loop
+  // runs in one workgroup from the R, c and state left by the initial step.  Writes R, c and the state block like
+  // varimax_persistent_kernel.
+  void moment_loop(RotationDevice& d, double tol, int max_iter) {
+    const int p = d.p, E = rot_moment_entries(p);
+    const int nm = pick_nwg(d.N, false, 512);
+    d.mpart.ensure((size_t)nm * E);
+    d.mom.ensure((size_t)E);
+    hipLaunchKernelGGL(rot_moment_kernel, dim3(nm), dim3(256), 0, st, d.A.r(), d.N, p, d.mpart.get());
+    XMCA_HIP(hipGetLastError());
+    hipLaunchKernelGGL(rot_reduce_partials_kernel, dim3(E), dim3(256), 0, st, d.mpart.get(), nullptr, nm, E, d.mom.get(), nullptr);
+    XMCA_HIP(hipGetLastError());
+    auto loop = [&](auto kern) {
+      hipLaunchKernelGGL(kern, dim3(1), dim3(256), 0, st, d.mom.get(), d.N, d.A0.r(), d.R.r(), d.cvec.get(), d.state.get(), tol, max_iter,
+                         gamma);
+    };
+    switch (p) {
+      case 2: loop(varimax_moment_kernel<2>); break;
+      case 3: loop(varimax_moment_kernel<3>); break;
+      case 4: loop(varimax_moment_kernel<4>); break;
+      case 5: loop(varimax_moment_kernel<5>); break;
+      case 6: loop(varimax_moment_kernel<6>); break;
+      case 7: loop(varimax_moment_kernel<7>); break;
+      case 8: loop(varimax_moment_kernel<8>); break;
+      case 9: loop(varimax_moment_kernel<9>); break;
+      case 10: loop(varimax_moment_kernel<10>); break;
+      case 11: loop(varimax_moment_kernel<11>); break;
+      default: loop(varimax_moment_kernel<12>); break;
+    }
+    XMCA_HIP(hipGetLastError());
+  }
+
   // runs Varimax + Promax on d.A / d.h (already normalised).  B_out (nullable): N x p rotated loadings for the host.
   template <bool CPLX>
   void run(RotationDevice& d, int power, double tol, int max_iter, RotateResult& res, double* B_out_dev, bool varimax_only) {
@@ -1406,7 +1440,15 @@ class Rotator {
     // replicates in flight), Varimax loops and tridiagonal reductions alike: the launch claims its CUs at the device's gate
     // (common.h PersistGate) and waits there for its turn - a reduction holds every CU for its ~20 ms, Varimax grids of
     // several lanes run side by side while they fit
-    const bool persist_ok = fused && persist_on && persist_smem <= 160 * 1024 && d.nwg <= 256 && d.nwg <= n_cus && max_iter > 0;
+    // real loadings with few modes: the fourth-moment route (one pass over the loadings, then the loop in one workgroup)
+    const bool moment = !CPLX && p <= ROT_MOMENT_PMAX;
+    const bool persist_ok = !moment && fused && persist_on && persist_smem <= 160 * 1024 && d.nwg <= 256 && d.nwg <= n_cus && max_iter > 0;
+    if (moment) {
+      moment_loop(d, tol, max_iter);
+      XMCA_HIP(hipMemcpyAsync(state, d.state.get(), sizeof(state), hipMemcpyDeviceToHost, st));
+      XMCA_HIP(hipStreamSynchronize(st));
+      launched = max_iter;
+    }
     if (persist_ok) {
       PersistGate::Claim claim(gate, d.nwg);           // given back at the end of this block: the stream has been synchronised by then
       // XMCA_VARIMAX_TEST_GIVEUP=k (tests): the persistent launch stops after k iterations, as if a workgroup had gone
@@ -1469,7 +1511,12 @@ class Rotator {
     }
     tm.end();
 #ifdef XMCA_ROT_PROF
-    {
+    if (moment) {
+      long long hs[16];
+      XMCA_HIP(hipMemcpyFromSymbol(hs, HIP_SYMBOL(rot_prof), sizeof(hs)));
+      std::fprintf(stderr, "[xmca varimax prof] moment route, last iteration: S %lld  Y = M'S %lld  G %lld  polar tail %lld (its %g)  total %lld cycles\n",
+                   hs[1] - hs[0], hs[2] - hs[1], hs[3] - hs[2], hs[4] - hs[3], state[5], hs[4] - hs[0]);
+    } else {
       long long hs[16];
       XMCA_HIP(hipMemcpyFromSymbol(hs, HIP_SYMBOL(rot_prof), sizeof(hs)));
       std::fprintf(stderr, "[xmca varimax prof] accum %lld  publish %lld  wait %lld  acquire %lld  reduce %lld  newton-schulz %lld (its %g)  tail %lld  total %lld cycles (nwg %d)\n",
