@@ -41,7 +41,7 @@ typedef struct xmca_handle xmca_handle;
 /* library / device management ------------------------------------------------------------------------- */
 const char* xmca_version(void);
 /* Number of this header's ABI (XMCA_ABI_VERSION): the binding refuses a library built from another revision. */
-#define XMCA_ABI_VERSION 9
+#define XMCA_ABI_VERSION 10
 int xmca_abi_version(void);
 int xmca_device_count(void);
 int xmca_create(int device, xmca_handle** out);
@@ -62,6 +62,20 @@ int xmca_set_field(xmca_handle* h, int side, const void* re, const void* im, int
  * Replaces scipy.signal.hilbert(field, axis=0) of array.py:464 for extend=False.
  * hilbert_col == NULL reverts to the real fields (a later solve on the same resident fields is a real one again). */
 int xmca_complexify(xmca_handle* h, const double* hilbert_col);
+
+/* Complexify with the fore/back-cast extension of solve(complexify=True, extend='exp', period=theta) on the device (ABI 10).
+ * Replaces the host path of xmca/array.py:378-472 (`_get_reg_coefs`, `_exp_forecast`, `_extend`, `_complexify`: regression and
+ * exponential forecast of every column, the 3T-long series, scipy.signal.hilbert, the trim to [T, 2T) and `remove_mean`).  For
+ * extend='exp' that procedure is one linear operator along time, the same for every column: X~ = X + i G X with
+ *   G[t][s] = col3[(t - s) mod 3T] - hbar[s] + sum_{k < rank} U[t][k] W[s][k]
+ * (xmca_amd/_hip.py extended_imag_parts derives it).  col3: 3T float64, the first column of the imaginary Hilbert
+ * operator at length 3T; hbar: T float64, the column means of its middle block; U, W: T x rank row-major float64 (rank <= 16).
+ * All host memory, O(T); the T x T operator is assembled on the device and X_im = G X formed by the solve (never the
+ * subspace formulation of xmca_complexify, which is exact for the circulant operator only) or by xmca_project.
+ * Float32 fields are promoted to float64 on the device first, as the reference extends in float64: the resident fields are
+ * float64 from then on (xmca_get_field returns float64; xmca_scale_field takes float64 factors).
+ * Undone by xmca_complexify(h, NULL) or the next xmca_set_field of the left field, like xmca_complexify. */
+int xmca_complexify_extended(xmca_handle* h, const double* col3, const double* hbar, const double* U, const double* W, int rank);
 
 /* MCA.solve numerical core (xmca/array.py:549-584): per-field SVD, kernel, kernel SVD, back-projection.
  *   n_fields  1 (EOF/PCA) or 2 (MCA)
@@ -88,7 +102,8 @@ int xmca_get_eofs(xmca_handle* h, int side, const double* W, int64_t m, int64_t 
 
 /* PC projection of MCA._get_U (xmca/array.py:648-674, the product `fields[k] @ V[k]`): U = X~ V with X~ the field of
  * `side` as solve() saw it - still resident on the device; the analytic signal X + i Ht X when complexify was
- * requested (the imaginary field plane is not needed: U = W + i Ht W with W = X V).
+ * requested (the imaginary field plane is not needed: U = W + i Ht W with W = X V); X + i G X after
+ * xmca_complexify_extended (the imaginary planes G X are formed first when the solve has not done so).
  *   V      N x m row-major, float64 (is_complex = 0) or interleaved complex128 (is_complex = 1), host memory
  *   U_out  T x m row-major float64, interleaved complex128 when *out_is_complex = 1 (model or V complex)
  * The scaling by 1/sqrt(sigma) and the rotation (array.py:391-393) stay with the caller (m x m work). */
@@ -139,6 +154,14 @@ int xmca_bootstrap_run(xmca_handle* h, const double* hilbert_col, const int64_t*
  * Does not touch the cumulative state of xmca_bootstrap_run. */
 int xmca_bootstrap_runs(xmca_handle* h, const double* hilbert_col, const int64_t* idx_left, const int64_t* idx_right, int64_t n_runs,
                         int rotated, int p, int power, double tol, double* spectra_out, int* kept_out, int64_t n_out);
+/* xmca_bootstrap_runs of a model solved with extend='exp' (ABI 10): every replicate is complexified with the operator G of
+ * xmca_complexify_extended (col3, hbar, U, W, rank for T = the T of xmca_bootstrap_begin) - the reference passes `extend` and
+ * `period` into every replicate's solve (xmca/array.py:1935-1947) and resampling rows keeps T, so G is the same for all of them.
+ * The fields must be float64 (the reference's replicates are: `_get_X(real=True)` of a complex128 signal); XMCA_ERR_INVALID
+ * otherwise. */
+int xmca_bootstrap_runs_extended(xmca_handle* h, const double* col3, const double* hbar, const double* U, const double* W, int rank,
+                                 const int64_t* idx_left, const int64_t* idx_right, int64_t n_runs, int rotated, int p, int power,
+                                 double tol, double* spectra_out, int* kept_out, int64_t n_out);
 int xmca_is_complex(xmca_handle* h);
 /* 1 when the singular vectors of `side` from the last xmca_solve are resident in float32: a real float32 field decomposed on
  * its dual side (N > T) keeps `_V` in the input's dtype as the reference does (xmca/array.py:584, the dtype of

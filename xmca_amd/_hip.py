@@ -34,6 +34,7 @@ SIGNATURES = {
     "xmca_last_error": (ctypes.c_char_p, [_vp]),
     "xmca_set_field": (_c_int, [_vp, _c_int, _vp, _vp, _c_i64, _c_i64, _c_int, _c_int]),
     "xmca_complexify": (_c_int, [_vp, _vp]),
+    "xmca_complexify_extended": (_c_int, [_vp, _vp, _vp, _vp, _vp, _c_int]),
     "xmca_solve": (_c_int, [_vp, _c_int, _c_i64, ctypes.POINTER(_c_i64)]),
     "xmca_get_singular_values": (_c_int, [_vp, _vp, _c_i64]),
     "xmca_get_vectors": (_c_int, [_vp, _c_int, _vp, _c_i64, _c_int]),
@@ -45,6 +46,8 @@ SIGNATURES = {
     "xmca_bootstrap_begin": (_c_int, [_vp, _c_int]),
     "xmca_bootstrap_run": (_c_int, [_vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_dbl, _vp, ctypes.POINTER(_c_int), _c_i64]),
     "xmca_bootstrap_runs": (_c_int, [_vp, _vp, _vp, _vp, _c_i64, _c_int, _c_int, _c_int, _c_dbl, _vp, _vp, _c_i64]),
+    "xmca_bootstrap_runs_extended": (_c_int, [_vp, _vp, _vp, _vp, _vp, _c_int, _vp, _vp, _c_i64, _c_int, _c_int, _c_int, _c_dbl, _vp, _vp,
+                                              _c_i64]),
     "xmca_correlate": (_c_int, [_vp, _c_int, _vp, _c_i64, _c_i64, _vp]),
     "xmca_project": (_c_int, [_vp, _c_int, _vp, _c_i64, _c_i64, _c_int, _vp, ctypes.POINTER(_c_int)]),
     "xmca_is_complex": (_c_int, [_vp]),
@@ -87,7 +90,7 @@ def library_path():
     return _build.LIB
 
 
-ABI_VERSION = 9          # bumped whenever a signature of include/xmca_hip.h changes; checked against xmca_abi_version()
+ABI_VERSION = 10         # bumped whenever a signature of include/xmca_hip.h changes; checked against xmca_abi_version()
 
 
 def load_library():
@@ -173,6 +176,64 @@ def hilbert_imag_operator(T):
     return np.ascontiguousarray(col[idx])
 
 
+def extended_imag_parts(T, period):
+    """O(T) parts of the imaginary operator G of the fore/back-cast analytic signal (extend='exp', xmca/array.py:378-472).
+
+    For `extend='exp'` the reference's `_complexify` is linear in the column and the same for every column: `_get_reg_coefs`
+    divides by the constant `mean(x)`, so the forecast of a series y is y[T-1] e + ymean (1 - e) + s (t + tc - tc e) with
+    e_t = exp(-(t + 1) / period), tc = (T - 1) / 2 and s = sum (t - tc) y_t / (T tc^2); the backcast is the same map of the
+    reversed series.  After `hilbert` of the 3T-long series, the trim to [T, 2T) and `remove_mean`, a centered field X becomes
+    X + i G X with
+
+        G = P (H3[T:2T, T:2T] + U W^T),   P = I - 1 1^T / T,
+
+    H3 the circulant imaginary operator of `hilbert` at length 3T and U W^T of rank 4: the extensions see a column only through
+    W^T y = (mean, s, y_0, y_{T-1}).  Returned (float64, nothing of size T x T):
+
+      col3   (3T,)   first column of H3: H3[T + t, T + s] = col3[(t - s) mod 3T]
+      hbar   (T,)    column means of the middle block, hbar[s] = mean_t col3[(t - s) mod 3T]
+      U      (T, 4)  P applied to the four images H3[T:2T, :] [backcast; 0; forecast] of the functionals
+      W      (T, 4)  the functionals
+
+    so that G[t, s] = col3[(t - s) mod 3T] - hbar[s] + sum_k U[t, k] W[s, k]."""
+    T = int(T)
+    if T < 2:
+        raise ValueError("extend='exp' needs at least 2 time steps")
+    period = float(period)
+    t = np.arange(T, dtype=np.float64)
+    tc = (T - 1) / 2.0
+    e = np.exp(-(t + 1.0) / period)
+    W = np.empty((T, 4))
+    W[:, 0] = 1.0 / T                               # ymean
+    W[:, 1] = (t - tc) / (T * tc * tc)              # slope s
+    W[:, 2] = 0.0
+    W[0, 2] = 1.0                                   # y_0 (last point of the reversed series)
+    W[:, 3] = 0.0
+    W[T - 1, 3] = 1.0                               # y_{T-1}
+    # coefficients of the four functionals in the forecast `post` (rows t) and the backcast `pre` (pre[t] = f_rev[T-1-t])
+    post = np.stack([1.0 - e, t + tc - tc * e, np.zeros(T), e], axis=1)
+    pre = np.stack([1.0 - e, -(t + tc - tc * e), e, np.zeros(T)], axis=1)[::-1]
+    col3 = hilbert_imag_column(3 * T)
+    h3 = np.zeros(3 * T)
+    if T % 2 == 0:                                  # 3T even
+        h3[0] = h3[3 * T // 2] = 1.0
+        h3[1:3 * T // 2] = 2.0
+    else:
+        h3[0] = 1.0
+        h3[1:(3 * T + 1) // 2] = 2.0
+    ext = np.zeros((3 * T, 4))
+    ext[:T] = pre
+    ext[2 * T:] = post
+    U = np.fft.ifft(np.fft.fft(ext, axis=0) * h3[:, None], axis=0).imag[T:2 * T]
+    U = np.ascontiguousarray(U - U.mean(axis=0))
+    # hbar[s] = (1/T) sum_{d = -s}^{T-1-s} col3[d mod 3T]: a sliding window over col3[-(T-1):] ++ col3[:T]
+    win = np.concatenate([col3[2 * T + 1:], col3[:T]])
+    cs = np.concatenate([[0.0], np.cumsum(win)])
+    s = np.arange(T)
+    hbar = (cs[2 * T - 1 - s] - cs[T - 1 - s]) / T
+    return np.ascontiguousarray(col3), np.ascontiguousarray(hbar), U, np.ascontiguousarray(W)
+
+
 class Handle:
     """One device + stream + workspace.  Not thread-safe."""
 
@@ -186,6 +247,7 @@ class Handle:
         if rc != 0:
             raise HipError(rc, "xmca_create(device=%d) failed" % device)
         self.device = device
+        self.field_dtype = None      # real dtype of the resident fields (float64 after complexify_extended of float32 fields)
         self._keep = []      # host / device buffers that must outlive the handle's use of them
 
     def close(self):
@@ -233,6 +295,7 @@ class Handle:
             re = np.ascontiguousarray(field)
             im = None
         self._check(self._lib.xmca_set_field(self._h, side, _ptr(re), _ptr(im), T, N, code, HOST))
+        self.field_dtype = np.dtype(np.float32 if code == XMCA_F32 else np.float64)
 
     def set_field_device(self, side, re_ptr, im_ptr, T, N, dtype):
         """Adopt device pointers (e.g. torch tensors' data_ptr()); the caller keeps them alive."""
@@ -240,11 +303,20 @@ class Handle:
         self.fields_owner = None
         self._check(self._lib.xmca_set_field(self._h, side, _vp(re_ptr), _vp(im_ptr) if im_ptr else None, T, N,
                                              _np_dtype_code(dtype), DEVICE))
+        self.field_dtype = np.dtype(np.float32 if _np_dtype_code(dtype) == XMCA_F32 else np.float64)
 
     def complexify(self, T):
         self.release_result()
         ht = hilbert_imag_column(T)
         self._check(self._lib.xmca_complexify(self._h, _ptr(ht)))
+
+    def complexify_extended(self, T, period):
+        """solve(complexify=True, extend='exp', period=period) on the resident fields: X~ = X + i G X with the operator of
+        `extended_imag_parts` (xmca_complexify_extended).  Float32 fields become float64 fields on the device."""
+        self.release_result()
+        col3, hbar, U, W = extended_imag_parts(T, period)
+        self._check(self._lib.xmca_complexify_extended(self._h, _ptr(col3), _ptr(hbar), _ptr(U), _ptr(W), U.shape[1]))
+        self.field_dtype = np.dtype(np.float64)
 
     def decomplexify(self):
         """Back to the real resident fields (undoes `complexify` for the next solve)."""
@@ -338,10 +410,12 @@ class Handle:
         self._check(self._lib.xmca_scale_field(self._h, side, _ptr(w), int(bool(divide))))
 
     def get_field(self, side, shape, dtype):
-        """Real plane of the resident field of `side` as a (T, N) array of `dtype` (the dtype it was set with)."""
-        out = np.empty(shape, dtype=dtype)
+        """Real plane of the resident field of `side` as a (T, N) array of `dtype` (the dtype it was set with; a float32 field
+        promoted by `complexify_extended` comes back exactly, through float64)."""
+        resident = self.field_dtype if self.field_dtype is not None else np.dtype(dtype)
+        out = np.empty(shape, dtype=resident)
         self._check(self._lib.xmca_get_field(self._h, side, _ptr(out)))
-        return out
+        return out.astype(dtype, copy=False)
 
     def bootstrap_begin(self, n_fields):
         """Working copies of the resident fields for `bootstrap_run` (MCA.bootstrapping on the device)."""
@@ -359,14 +433,21 @@ class Handle:
                                                  _ptr(out), ctypes.byref(kept), n_out))
         return out, bool(kept.value)
 
-    def bootstrap_runs(self, T, complexify, idx_left, idx_right, n_runs, rotated, p, power, tol, n_out):
+    def bootstrap_runs(self, T, complexify, idx_left, idx_right, n_runs, rotated, p, power, tol, n_out, extend_period=None):
         """All replicates in one call (several in flight on the device).  idx_*: (n_runs, T) COMPOSED row indices into the
-        fields as they were at `bootstrap_begin`, or None.  Returns (spectra[n_runs, n_out], kept[n_runs])."""
-        ht = hilbert_imag_column(T) if complexify else None
+        fields as they were at `bootstrap_begin`, or None.  `extend_period`: replicates of a complex model with extend='exp' and
+        this period (xmca_bootstrap_runs_extended; float64 fields).  Returns (spectra[n_runs, n_out], kept[n_runs])."""
         il = None if idx_left is None else np.ascontiguousarray(idx_left, dtype=np.int64).reshape(n_runs, T)
         ir = None if idx_right is None else np.ascontiguousarray(idx_right, dtype=np.int64).reshape(n_runs, T)
         out = np.zeros((n_runs, n_out), dtype=np.float64)
         kept = np.zeros(n_runs, dtype=np.int32)
+        if complexify and extend_period is not None:
+            col3, hbar, U, W = extended_imag_parts(T, extend_period)
+            self._check(self._lib.xmca_bootstrap_runs_extended(self._h, _ptr(col3), _ptr(hbar), _ptr(U), _ptr(W), U.shape[1], _ptr(il),
+                                                               _ptr(ir), n_runs, int(rotated), int(p), int(power), float(tol), _ptr(out),
+                                                               _ptr(kept), n_out))
+            return out, kept.astype(bool)
+        ht = hilbert_imag_column(T) if complexify else None
         self._check(self._lib.xmca_bootstrap_runs(self._h, _ptr(ht), _ptr(il), _ptr(ir), n_runs, int(rotated), int(p), int(power),
                                                   float(tol), _ptr(out), _ptr(kept), n_out))
         return out, kept.astype(bool)
@@ -431,6 +512,7 @@ class Handle:
         spectra = np.zeros((max(n, 0), n_out), dtype=np.float64)
         kept = np.zeros(max(n, 0), dtype=np.int32)
         ht = hilbert_imag_column(T) if complexify else None
+        self.field_dtype = None
         if n > 0:
             self._check(self._lib.xmca_rule_n(self._h, T, Nx, Ny if n_fields == 2 else 0, n_fields, _ptr(ht), int(rotated),
                                               int(p), int(power), float(tol), run_begin, run_end, int(seed),
@@ -442,6 +524,7 @@ class Handle:
         `comm`, see `Comm`); every rank gets all n_runs x n_out spectra and kept flags."""
         self.release_result()
         self.fields_owner = None
+        self.field_dtype = None
         spectra = np.zeros((max(n_runs, 0), n_out), dtype=np.float64)
         kept = np.zeros(max(n_runs, 0), dtype=np.int32)
         ht = hilbert_imag_column(T) if complexify else None

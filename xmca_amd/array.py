@@ -139,6 +139,7 @@ class MCA:
         self._fields_store = {}
         self._pending_hilbert = False
         self._device_hilbert = False
+        self._device_extend = None          # period of extend='exp' when the device applies the extended operator
         self._upload_serial = 0
         self._token = object()              # identity of this model as owner of a handle's resident fields (never reused, unlike id())
         self._shape = {}
@@ -187,10 +188,22 @@ class MCA:
         if self._store_is_raw:
             self._materialize_fields()
         if self._pending_hilbert:
-            from scipy.signal import hilbert
-            self._fields_store = {k: hilbert(f.real, axis=0) for k, f in self._fields_store.items()}
+            if getattr(self, '_device_extend', None) is not None:
+                self._fields_store = self._complexify(self._fields_store)     # the reference's own extension (array.py:429-472)
+            else:
+                from scipy.signal import hilbert
+                self._fields_store = {k: hilbert(f.real, axis=0) for k, f in self._fields_store.items()}
             self._pending_hilbert = False
         return self._fields_store
+
+    def _real_fields(self):
+        """Real parts of `_fields` without materialising a pending analytic signal on the host.  extend='exp': float64, as the
+        reference's real part of its complex128 signal (the imaginary part never enters the replicates of `bootstrapping`)."""
+        if not (self._pending_hilbert and getattr(self, '_device_extend', None) is not None):
+            return {k: x.real for k, x in self._get_X(original_scale=False).items()}
+        if self._store_is_raw:
+            self._materialize_fields()
+        return {k: np.array(f.real, dtype=np.float64) for k, f in self._fields_store.items()}
 
     @_fields.setter
     def _fields(self, value):
@@ -388,6 +401,8 @@ class MCA:
         cols = {}
         for k, w in factors.items():
             f = self._fields_store[k]
+            if getattr(dev, 'field_dtype', None) not in (None, np.dtype(f.dtype)):
+                return False                  # float32 fields promoted by an extend='exp' solve: the host path scales them
             w = np.asarray(w)
             if w.ndim > 2 or (w.ndim == 2 and w.shape[0] != 1) or np.iscomplexobj(w):
                 return False
@@ -485,8 +500,12 @@ class MCA:
             del self._V                                              # vectors of an earlier solve still on the device: not wanted
 
         dev = self._device()
-        if complexify and extend:
-            self._fields = self._complexify(self._fields)           # host path (nonlinear extension)
+        # extend='exp' is a fixed linear operator along time (`_hip.extended_imag_parts`): X_im = G X on the device, in float64
+        # like the reference; `_extend_on_host` (private) keeps the reference's host procedure for comparison
+        extend_exp = bool(complexify) and extend == 'exp' and not getattr(self, '_extend_on_host', False)
+        self._device_extend = period if extend_exp else None
+        if complexify and extend and not extend_exp:
+            self._fields = self._complexify(self._fields)           # host path (theta: nonlinear extension)
             self._device_hilbert = False
         elif self._store_is_raw:
             self._device_hilbert = bool(complexify)                  # centered real fields are resident already
@@ -494,7 +513,7 @@ class MCA:
         else:
             real = {k: self._fields[k].real if np.iscomplexobj(self._fields_store[k]) else self._fields_store[k]
                     for k in self._keys}
-            self._device_hilbert = bool(complexify)                  # X_im = Ht X on the device
+            self._device_hilbert = bool(complexify)                  # X_im = Ht X (or G X) on the device
             if complexify:
                 self._fields_store = real
                 self._pending_hilbert = True                         # host copy of the analytic signal: on first use
@@ -508,6 +527,8 @@ class MCA:
             raise np.linalg.LinAlgError('''SVD failed. NaN entries may be the problem.''') from err
 
         real_dtype = _real_dtype(next(iter(self._fields_store.values())).dtype)
+        if extend_exp:
+            real_dtype = np.float64                                  # float32 input is extended in float64 (complex128 result)
         singular_values = dev.singular_values(rank).astype(real_dtype, copy=False)
         # the vectors stay on the device until something reads them (233 MB at C2; pcs / eofs / rotate of a few modes
         # fetch just those modes); anything that would invalidate them on the handle makes this model fetch them first
@@ -585,10 +606,16 @@ class MCA:
 
     def _upload_fields(self, dev):
         """Makes the fields solve() works on resident on the device and records this model as their owner."""
+        T = self._n_observations['left']
+        extend = getattr(self, '_device_extend', None)
         if self._store_is_raw:
-            if self._owns_device_fields(dev):                   # device-preprocessed and still resident: nothing to send
-                if self._device_hilbert:
-                    dev.complexify(self._n_observations['left'])
+            # (float32 fields promoted by an earlier extend='exp' solve are resident as float64: a plain solve uploads them again)
+            same_dtype = getattr(dev, 'field_dtype', None) in (None, np.dtype(self._fields_store[self._keys[0]].dtype))
+            if self._owns_device_fields(dev) and (extend is not None or same_dtype):   # still resident: nothing to send
+                if extend is not None:
+                    dev.complexify_extended(T, extend)
+                elif self._device_hilbert:
+                    dev.complexify(T)
                 else:
                     dev.decomplexify()
                 return
@@ -597,7 +624,12 @@ class MCA:
         for side, k in enumerate(self._keys):
             dev.set_field(side, _device_ready(store[k]))
         if self._device_hilbert and not any(np.iscomplexobj(f) for f in store.values()):
-            dev.complexify(self._n_observations['left'])        # (a materialised host analytic signal goes up as it is)
+            # (a materialised host analytic signal goes up as it is); the extended operator, never the plain Hilbert one, for
+            # a model solved with extend='exp'
+            if extend is not None:
+                dev.complexify_extended(T, extend)
+            else:
+                dev.complexify(T)
         dev.fields_owner = self._owner_key()
 
     def _project_on_device(self, V):
@@ -986,8 +1018,9 @@ class MCA:
 
         The block indices are drawn on the host from numpy's global RNG exactly as the reference draws them
         (tools/array.py:91-138), the replicates themselves - cumulative row resampling, centering, solve, rotation,
-        variance - run on the device (`xmca_bootstrap_run`).  Column resampling (`axis=1`) and models with a
-        fore/back-cast extension keep the reference's host loop with one device solve per replicate.
+        variance - run on the device (`xmca_bootstrap_run`).  A model solved with extend='exp' runs there too, every replicate
+        complexified with the same extended operator in float64 (`xmca_bootstrap_runs_extended`).  Column resampling (`axis=1`)
+        and extend='theta' keep the reference's host loop with one device solve per replicate.
         """
         complexify = self._analysis['is_complex']
         extend = self._analysis['extend']
@@ -997,11 +1030,12 @@ class MCA:
         power = self._analysis['power']
         n_modes_max = self._get_min_mode(n_modes, rotated=True)
         var_surr = np.zeros([n_modes_max, n_runs])
-        on_device = axis == 0 and not extend and not getattr(self, '_bootstrap_on_host', False)
+        extend_exp = bool(complexify) and extend == 'exp' and getattr(self, '_device_extend', None) is not None
+        on_device = axis == 0 and (not extend or extend_exp) and not getattr(self, '_bootstrap_on_host', False)
         dev = self._device()
         n_obs = self._n_observations['left']
         for mode in range(n_modes):
-            X_surr = self._get_X(original_scale=False, real=True)
+            X_surr = self._real_fields() if extend_exp else self._get_X(original_scale=False, real=True)
             if strategy == 'iterative':
                 X_rec = self._reconstructed_X(mode=mode, original_scale=False)
                 for k in X_surr:
@@ -1033,7 +1067,8 @@ class MCA:
                 from . import dist
                 spec, kept = dist.sharded_bootstrap(dev, n_runs, T=n_obs, complexify=complexify, idx_left=composed if on_left else None,
                                                     idx_right=composed if on_right else None, rotated=is_rotated, p=n_rot,
-                                                    power=max(power, 1), tol=1e-8, n_out=n_out)
+                                                    power=max(power, 1), tol=1e-8, n_out=n_out,
+                                                    extend_period=period if extend_exp else None)
                 for run in range(n_runs):
                     if kept[run]:
                         var_surr[mode:, run] = spec[run, :n_modes_max - mode]
@@ -1056,6 +1091,7 @@ class MCA:
                                            block_size=block_size, replace=replace)
                     X_surr['left'], X_surr['right'] = both[:, :n_left], both[:, n_left:]
                 model = MCA(*list(X_surr.values()), handle=self._handle_override)
+                model._extend_on_host = getattr(self, '_extend_on_host', False)
                 model.solve(complexify=complexify, extend=extend, period=period)
                 if is_rotated:
                     try:

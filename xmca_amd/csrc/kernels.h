@@ -244,6 +244,24 @@ __global__ void circulant_kernel(const double* __restrict__ col, int T, TO* __re
   }
 }
 
+// T x T imaginary operator of the fore/back-cast analytic signal (extend='exp', xmca_amd/_hip.py extended_imag_parts):
+// G[t][s] = col3[(t - s) mod 3T] - hbar[s] + sum_k U[t][k] W[s][k] - the middle block of the 3T circulant Hilbert operator, the
+// rank-r images of the extensions (U, T x r row-major, already centered) and the row-mean removal of `remove_mean` (hbar: the
+// column means of the middle block).  Accumulated in float64, stored in the field's element type.
+template <typename TO>
+__global__ void extended_operator_kernel(const double* __restrict__ col3, const double* __restrict__ hbar, const double* __restrict__ U,
+                                         const double* __restrict__ W, int r, int T, TO* __restrict__ out) {
+  const int64_t n = (int64_t)T * T;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int t = (int)(i / T), s = (int)(i % T);
+    int64_t d = (int64_t)t - s;            // in (-T, T): col3 index d or 3T + d, both < 3T
+    if (d < 0) d += 3 * (int64_t)T;
+    double g = col3[d] - hbar[s];
+    for (int k = 0; k < r; ++k) g += U[(int64_t)t * r + k] * W[(int64_t)s * r + k];
+    out[i] = (TO)g;
+  }
+}
+
 // Orthonormal Fourier vectors of the frequencies kept by the analytic signal: Phi[t][f] = exp(2 pi i f t / T) / sqrt(T),
 // f = 0 .. m-1 (m = T/2 + 1 for even T, (T+1)/2 for odd T), and the Hilbert weights h_f of scipy.signal.hilbert
 // (1 for DC and Nyquist, 2 otherwise), so that hilbert(x) = Phi diag(h) Phi^H x.

@@ -12,6 +12,34 @@
 
 using namespace xmca;
 
+// The operator of a complexification X~ = X + i Op X along time (xmca_complexify / xmca_complexify_extended): the circulant
+// Hilbert operator of scipy.signal.hilbert (first column, T values) or the operator of the fore/back-cast analytic signal of
+// extend='exp' (xmca_amd/_hip.py extended_imag_parts: col3 of length 3T, hbar, U and W of T x r).  Host copies; the T x T matrix
+// is assembled on the device when it is needed (build_operator).
+struct ComplexOp {
+  enum Kind { CIRCULANT, EXTENDED } kind = CIRCULANT;
+  int64_t T = 0;
+  int r = 0;
+  std::vector<double> col, hbar, U, W;
+  static ComplexOp circulant(const double* col, int64_t T) {
+    ComplexOp op;
+    op.T = T;
+    op.col.assign(col, col + T);
+    return op;
+  }
+  static ComplexOp extended(const double* col3, const double* hbar, const double* U, const double* W, int r, int64_t T) {
+    ComplexOp op;
+    op.kind = EXTENDED;
+    op.T = T;
+    op.r = r;
+    op.col.assign(col3, col3 + 3 * T);
+    op.hbar.assign(hbar, hbar + T);
+    op.U.assign(U, U + T * r);
+    op.W.assign(W, W + T * r);
+    return op;
+  }
+};
+
 struct xmca_handle {
   ::xmca::DevPool pool;                   // first member: destroyed after every buffer below has gone back to it
   int device = 0;
@@ -27,8 +55,8 @@ struct xmca_handle {
   bool field_set[2] = {false, false};
   SolveResult res;
   bool solved = false;
-  bool hilbert_pending = false;          // complexify requested; carried out (or folded into the solve) lazily
-  std::vector<double> hilbert_col;
+  bool op_pending = false;               // complexify requested; carried out (or folded into the solve) lazily
+  ComplexOp op;                          // ... with this operator
   RotationDevice rot;
   // bootstrapping (xmca_bootstrap_begin / _run): cumulative resampled copies of the fields, a gather target and the
   // centered copies that are solved
@@ -154,17 +182,40 @@ void build_hilbert(xmca_handle* h, const double* col_host, int64_t T, DevBuf<TI>
   XMCA_HIP(hipStreamSynchronize(h->st));
 }
 
+// T x T operator of `op` in the field's element type: the circulant Hilbert operator, or the extended one (row means removed)
 template <typename TI>
-void complexify_impl(xmca_handle* h, const double* col_host) {
+void build_operator(xmca_handle* h, const ComplexOp& op, DevBuf<TI>& g) {
+  if (op.kind == ComplexOp::CIRCULANT) {
+    build_hilbert<TI>(h, op.col.data(), op.T, g);
+    return;
+  }
+  const int64_t T = op.T;
+  XMCA_CHECK((int64_t)op.col.size() == 3 * T && (int64_t)op.hbar.size() == T && (int64_t)op.U.size() == T * op.r &&
+                 (int64_t)op.W.size() == T * op.r,
+             XMCA_ERR_STATE, "extended operator: inconsistent parts");
+  DevBuf<double> col3, hbar, U, W;
+  XMCA_HIP(hipMemcpyAsync(col3.ensure((size_t)(3 * T)), op.col.data(), sizeof(double) * 3 * T, hipMemcpyHostToDevice, h->st));
+  XMCA_HIP(hipMemcpyAsync(hbar.ensure((size_t)T), op.hbar.data(), sizeof(double) * T, hipMemcpyHostToDevice, h->st));
+  XMCA_HIP(hipMemcpyAsync(U.ensure((size_t)(T * op.r) + 1), op.U.data(), sizeof(double) * T * op.r, hipMemcpyHostToDevice, h->st));
+  XMCA_HIP(hipMemcpyAsync(W.ensure((size_t)(T * op.r) + 1), op.W.data(), sizeof(double) * T * op.r, hipMemcpyHostToDevice, h->st));
+  hipLaunchKernelGGL((extended_operator_kernel<TI>), ew_grid(T * T), dim3(EW_BLOCK), 0, h->st, col3.get(), hbar.get(), U.get(), W.get(),
+                     op.r, (int)T, g.ensure((size_t)T * T));
+  XMCA_HIP(hipGetLastError());
+  XMCA_HIP(hipStreamSynchronize(h->st));
+}
+
+template <typename TI>
+void complexify_impl(xmca_handle* h, const ComplexOp& op) {
   FieldData<TI>* f = fields_of<TI>(h);
   const int64_t T = f[0].T;
+  XMCA_CHECK(op.T == T, XMCA_ERR_STATE, "complexify: the operator was made for another number of time steps");
   DevBuf<TI> htb;
-  build_hilbert<TI>(h, col_host, T, htb);
+  build_operator<TI>(h, op, htb);
   struct { const TI* r; } ht{htb.get()};
-  h->tm.begin("hilbert");
+  h->tm.begin(op.kind == ComplexOp::CIRCULANT ? "hilbert" : "hilbert_extended");
   for (int s = 0; s < 2; ++s) {
     if (!h->field_set[s]) continue;
-    GemmOpts o;   // X_im = Ht X   (T x T) (T x N)
+    GemmOpts o;   // X_im = Ht X (or G X)   (T x T) (T x N)
     TI* dst = f[s].im.ensure((size_t)T * f[s].N);
     gemm<TI, TI>(h->st, h->gws, ht.r, T, f[s].r(), f[s].N, dst, f[s].N, (int)T, (int)f[s].N, (int)T, o);
     f[s].has_im = true;
@@ -177,15 +228,16 @@ void complexify_impl(xmca_handle* h, const double* col_host) {
 template <typename TI>
 void solve_impl(xmca_handle* h, int n_fields, int64_t n_vec) {
   FieldData<TI>* f = fields_of<TI>(h);
-  if (h->hilbert_pending) {
+  if (h->op_pending) {
     static const bool analytic_on = [] { const char* e = std::getenv("XMCA_ANALYTIC"); return !(e && e[0] == '0'); }();
-    if (analytic_on && Solver<TI>::analytic_applicable(f, n_fields)) {
+    // the subspace formulation is exact for the Fourier-diagonal circulant operator only; the extended one is applied as a GEMM
+    if (h->op.kind == ComplexOp::CIRCULANT && analytic_on && Solver<TI>::analytic_applicable(f, n_fields)) {
       Solver<TI> s(h->st, h->gws, h->ews, h->tm);
       s.solve_analytic(f, n_fields, (int)n_vec, h->res);
       return;
     }
-    complexify_impl<TI>(h, h->hilbert_col.data());
-    h->hilbert_pending = false;
+    complexify_impl<TI>(h, h->op);
+    h->op_pending = false;
   }
   const bool cplx = f[0].has_im;
   if (n_fields == 2) XMCA_CHECK(f[1].has_im == cplx, XMCA_ERR_INVALID, "solve: both fields must be real or both complex");
@@ -261,7 +313,11 @@ void project_impl(xmca_handle* h, int side, const void* V, int64_t N, int64_t m,
   FieldData<TI>& f = fields_of<TI>(h)[side];
   XMCA_CHECK(f.N == N, XMCA_ERR_INVALID, "project: V has " + std::to_string(N) + " rows, the field has " + std::to_string(f.N) + " columns");
   const int64_t T = f.T;
-  const bool analytic = !f.has_im && h->hilbert_pending;       // imaginary plane implicit: X~ = X + i Ht X
+  if (h->op_pending && h->op.kind == ComplexOp::EXTENDED) {     // no implicit form: the imaginary planes G X are formed first
+    complexify_impl<TI>(h, h->op);
+    h->op_pending = false;
+  }
+  const bool analytic = !f.has_im && h->op_pending;            // imaginary plane implicit: X~ = X + i Ht X
   const bool f_cplx = f.has_im || analytic, cplx = f_cplx || v_cplx;
   // V -> planes in the field's element type (N x m, ld = m)
   const size_t nv = (size_t)N * m;
@@ -302,8 +358,8 @@ void project_impl(xmca_handle* h, int side, const void* V, int64_t N, int64_t m,
   DevBuf<double> ht;
   if (analytic) {
     // U = W + i Ht W:  Ur = Wr - Ht Wi,  Ui = Wi + Ht Wr
-    XMCA_CHECK((int64_t)h->hilbert_col.size() == T, XMCA_ERR_STATE, "project: the Hilbert column of the model is missing");
-    build_hilbert<double>(h, h->hilbert_col.data(), T, ht);
+    XMCA_CHECK(h->op.kind == ComplexOp::CIRCULANT && h->op.T == T, XMCA_ERR_STATE, "project: the Hilbert column of the model is missing");
+    build_hilbert<double>(h, h->op.col.data(), T, ht);
     XMCA_HIP(hipMemcpyAsync(ur.ensure(nu), wr.get(), sizeof(double) * nu, hipMemcpyDeviceToDevice, h->st));
     XMCA_HIP(hipMemcpyAsync(ui.ensure(nu), wi.get(), sizeof(double) * nu, hipMemcpyDeviceToDevice, h->st));
     GemmOpts o;
@@ -490,13 +546,15 @@ struct ReplicateRunner {
   RotationDevice rd;
   DevBuf<double> sigma_dev;
 
-  ReplicateRunner(xmca_handle* h_, int64_t T_, int64_t Nx, int64_t Ny, int n_fields_, const double* ht_host, int rotated_, int p_,
+  // op: the complexification of every replicate (nullptr: real); only the circulant Hilbert operator may take the analytic route
+  ReplicateRunner(xmca_handle* h_, int64_t T_, int64_t Nx, int64_t Ny, int n_fields_, const ComplexOp* op, int rotated_, int p_,
                   int power_, double tol_)
-      : h(h_), T(T_), Ns{Nx, Ny}, n_fields(n_fields_), rotated(rotated_), p(p_), power(power_), tol(tol_), cplx(ht_host != nullptr),
+      : h(h_), T(T_), Ns{Nx, Ny}, n_fields(n_fields_), rotated(rotated_), p(p_), power(power_), tol(tol_), cplx(op != nullptr),
         solver(h_->st, h_->gws, h_->ews, h_->tm), rot(h_->st, h_->tm, h_->gws, h_->ews) {
     static const bool analytic_on = [] { const char* e = std::getenv("XMCA_ANALYTIC"); return !(e && e[0] == '0'); }();
-    analytic = cplx && analytic_on && Nx > T && (n_fields == 1 || Ny > T);
-    if (cplx && !analytic) build_hilbert<TI>(h, ht_host, T, htb);
+    analytic = cplx && op->kind == ComplexOp::CIRCULANT && analytic_on && Nx > T && (n_fields == 1 || Ny > T);
+    if (cplx) XMCA_CHECK(op->T == T, XMCA_ERR_INVALID, "replicates: the operator was made for another number of time steps");
+    if (cplx && !analytic) build_operator<TI>(h, *op, htb);
   }
   int64_t rank() const { return std::min(T, n_fields == 2 ? std::min(Ns[0], Ns[1]) : Ns[0]); }
 
@@ -554,12 +612,12 @@ struct ReplicateRunner {
 // generator is keyed by (seed, run, side), so the spectra do not depend on the number of lanes.  XMCA_RULE_N_LANES
 // (default: 3 for eigenproblems of 2000 and more, 4 below; 1 = the plain loop).
 template <typename TI>
-void rule_n_lane(xmca_handle* h, int64_t T, int64_t Nx, int64_t Ny, int n_fields, const double* ht_host, int rotated, int p, int power,
+void rule_n_lane(xmca_handle* h, int64_t T, int64_t Nx, int64_t Ny, int n_fields, const ComplexOp* op, int rotated, int p, int power,
                  double tol, int64_t run_begin, int64_t run_end, int64_t first, int64_t stride, uint64_t seed, double* spectra, int* kept,
                  int64_t n_out) {
   FieldData<TI> f[2];
   const int64_t Ns[2] = {Nx, Ny};
-  ReplicateRunner<TI> runner(h, T, Nx, Ny, n_fields, ht_host, rotated, p, power, tol);
+  ReplicateRunner<TI> runner(h, T, Nx, Ny, n_fields, op, rotated, p, power, tol);
   XMCA_CHECK(n_out == (rotated ? (int64_t)p : runner.rank()), XMCA_ERR_INVALID, "rule_n: n_out must be rank (unrotated) or p (rotated)");
   for (int64_t run = run_begin + first; run < run_end; run += stride) {
     h->tm.begin("surrogate");
@@ -655,12 +713,15 @@ void rule_n_impl(xmca_handle* h, int64_t T, int64_t Nx, int64_t Ny, int n_fields
                  int64_t n_out) {
   const int64_t eig_n = std::min(T, n_fields == 2 ? std::min(Nx, Ny) : Nx);
   const int lanes = lanes_for(eig_n, run_end - run_begin);
+  ComplexOp hop;
+  if (ht_host) hop = ComplexOp::circulant(ht_host, T);
+  const ComplexOp* op = ht_host ? &hop : nullptr;
   if (lanes <= 1) {
-    rule_n_lane<TI>(h, T, Nx, Ny, n_fields, ht_host, rotated, p, power, tol, run_begin, run_end, 0, 1, seed, spectra, kept, n_out);
+    rule_n_lane<TI>(h, T, Nx, Ny, n_fields, op, rotated, p, power, tol, run_begin, run_end, 0, 1, seed, spectra, kept, n_out);
     return;
   }
   run_lanes(h, lanes, [&](xmca_handle* lh, int j) {
-    rule_n_lane<TI>(lh, T, Nx, Ny, n_fields, ht_host, rotated, p, power, tol, run_begin, run_end, j, lanes, seed, spectra, kept, n_out);
+    rule_n_lane<TI>(lh, T, Nx, Ny, n_fields, op, rotated, p, power, tol, run_begin, run_end, j, lanes, seed, spectra, kept, n_out);
   });
 }
 
@@ -719,7 +780,10 @@ void bootstrap_run_impl(xmca_handle* h, const double* ht_host, const int64_t* id
     XMCA_HIP(hipGetLastError());
   }
   h->tm.end();
-  ReplicateRunner<TI> runner(h, T, h->boot_N[0], n_fields == 2 ? h->boot_N[1] : 0, n_fields, ht_host, rotated, p, power, tol);
+  ComplexOp hop;
+  if (ht_host) hop = ComplexOp::circulant(ht_host, T);
+  ReplicateRunner<TI> runner(h, T, h->boot_N[0], n_fields == 2 ? h->boot_N[1] : 0, n_fields, ht_host ? &hop : nullptr, rotated, p, power,
+                             tol);
   XMCA_CHECK(n_out == (rotated ? (int64_t)p : runner.rank()), XMCA_ERR_INVALID, "bootstrap: n_out must be rank (unrotated) or p (rotated)");
   *kept = runner.run(f, spectrum, n_out);
 }
@@ -728,7 +792,7 @@ void bootstrap_run_impl(xmca_handle* h, const double* ht_host, const int64_t* id
 // gathered through the composed index of replicate r - the reference's cumulative resampling X <- X[idx_r] unrolled on
 // the host, c_r = c_{r-1}[idx_r] - so the replicates do not depend on each other on the device and can run in lanes.
 template <typename TI>
-void bootstrap_lane(xmca_handle* h, xmca_handle* src, const double* ht_host, const int64_t* idx_left, const int64_t* idx_right,
+void bootstrap_lane(xmca_handle* h, xmca_handle* src, const ComplexOp* op, const int64_t* idx_left, const int64_t* idx_right,
                     int64_t n_runs, int64_t first, int64_t stride, int rotated, int p, int power, double tol, double* spectra,
                     int* kept, int64_t n_out) {
   const int n_fields = src->boot_fields;
@@ -736,7 +800,7 @@ void bootstrap_lane(xmca_handle* h, xmca_handle* src, const double* ht_host, con
   const int64_t* idx_host[2] = {idx_left, idx_right};
   FieldData<TI> f[2];
   DevBuf<int64_t> idx_dev[2];
-  ReplicateRunner<TI> runner(h, T, src->boot_N[0], n_fields == 2 ? src->boot_N[1] : 0, n_fields, ht_host, rotated, p, power, tol);
+  ReplicateRunner<TI> runner(h, T, src->boot_N[0], n_fields == 2 ? src->boot_N[1] : 0, n_fields, op, rotated, p, power, tol);
   XMCA_CHECK(n_out == (rotated ? (int64_t)p : runner.rank()), XMCA_ERR_INVALID, "bootstrap: n_out must be rank (unrotated) or p (rotated)");
   for (int64_t run = first; run < n_runs; run += stride) {
     h->tm.begin("resample");
@@ -762,7 +826,7 @@ void bootstrap_lane(xmca_handle* h, xmca_handle* src, const double* ht_host, con
 }
 
 template <typename TI>
-void bootstrap_runs_impl(xmca_handle* h, const double* ht_host, const int64_t* idx_left, const int64_t* idx_right, int64_t n_runs,
+void bootstrap_runs_impl(xmca_handle* h, const ComplexOp* op, const int64_t* idx_left, const int64_t* idx_right, int64_t n_runs,
                          int rotated, int p, int power, double tol, double* spectra, int* kept, int64_t n_out) {
   const int n_fields = h->boot_fields;
   const int64_t T = h->boot_T;
@@ -773,11 +837,11 @@ void bootstrap_runs_impl(xmca_handle* h, const double* ht_host, const int64_t* i
   const int64_t eig_n = std::min(T, n_fields == 2 ? std::min(h->boot_N[0], h->boot_N[1]) : h->boot_N[0]);
   const int lanes = lanes_for(eig_n, n_runs);
   if (lanes <= 1) {
-    bootstrap_lane<TI>(h, h, ht_host, idx_left, idx_right, n_runs, 0, 1, rotated, p, power, tol, spectra, kept, n_out);
+    bootstrap_lane<TI>(h, h, op, idx_left, idx_right, n_runs, 0, 1, rotated, p, power, tol, spectra, kept, n_out);
     return;
   }
   run_lanes(h, lanes, [&](xmca_handle* lh, int j) {
-    bootstrap_lane<TI>(lh, h, ht_host, idx_left, idx_right, n_runs, j, lanes, rotated, p, power, tol, spectra, kept, n_out);
+    bootstrap_lane<TI>(lh, h, op, idx_left, idx_right, n_runs, j, lanes, rotated, p, power, tol, spectra, kept, n_out);
   });
 }
 
@@ -834,7 +898,7 @@ int xmca_set_field(xmca_handle* h, int side, const void* re, const void* im, int
   else set_field_impl<double>(h, side, re, im, T, N, location);
   h->field_set[side] = true;
   h->solved = false;
-  if (side == 0) h->hilbert_pending = false;
+  if (side == 0) h->op_pending = false;
   API_END(h)
 }
 
@@ -842,14 +906,46 @@ int xmca_complexify(xmca_handle* h, const double* hilbert_col) {
   API_BEGIN(h)
   XMCA_CHECK(h->field_set[0], XMCA_ERR_STATE, "complexify: set a field first");
   if (!hilbert_col) {            // back to the real fields (their real planes are untouched by a complex solve)
-    h->hilbert_pending = false;
+    h->op_pending = false;
     for (int s = 0; s < 2; ++s) { h->f32[s].has_im = false; h->f64[s].has_im = false; }
     h->solved = false;
     return XMCA_OK;
   }
   const int64_t T = h->dtype == XMCA_F32 ? h->f32[0].T : h->f64[0].T;
-  h->hilbert_col.assign(hilbert_col, hilbert_col + T);
-  h->hilbert_pending = true;      // xmca_solve decides: subspace formulation (no imaginary plane) or X_im = Ht X
+  h->op = ComplexOp::circulant(hilbert_col, T);
+  h->op_pending = true;           // xmca_solve decides: subspace formulation (no imaginary plane) or X_im = Ht X
+  h->solved = false;
+  API_END(h)
+}
+
+int xmca_complexify_extended(xmca_handle* h, const double* col3, const double* hbar, const double* U, const double* W, int rank) {
+  API_BEGIN(h)
+  XMCA_CHECK(h->field_set[0], XMCA_ERR_STATE, "complexify_extended: set a field first");
+  XMCA_CHECK(col3 && hbar && rank >= 0 && rank <= 16 && (rank == 0 || (U && W)), XMCA_ERR_INVALID,
+             "complexify_extended: need col3, hbar and T x rank U, W (rank <= 16)");
+  if (h->dtype == XMCA_F32) {
+    // the reference extends in float64 (the forecast of a float32 column is float64, array.py:394-410): the resident real
+    // float32 fields become float64 fields, exactly (every float32 is a float64)
+    for (int s = 0; s < 2; ++s) {
+      if (!h->field_set[s]) continue;
+      FieldData<float>& a = h->f32[s];
+      FieldData<double>& b = h->f64[s];
+      const int64_t n = a.T * a.N;
+      b.T = a.T; b.N = a.N; b.has_im = false; b.ext_re = nullptr; b.ext_im = nullptr;
+      hipLaunchKernelGGL((convert_kernel<float, double>), ew_grid(n), dim3(EW_BLOCK), 0, h->st, a.r(), b.re.ensure((size_t)n), n);
+      XMCA_HIP(hipGetLastError());
+    }
+    XMCA_HIP(hipStreamSynchronize(h->st));
+    for (int s = 0; s < 2; ++s) {
+      FieldData<float>& a = h->f32[s];
+      a.re.release(); a.im.release(); a.ext_re = nullptr; a.ext_im = nullptr; a.has_im = false;
+    }
+    h->dtype = XMCA_F64;
+  }
+  const int64_t T = h->f64[0].T;
+  XMCA_CHECK(T <= 46340, XMCA_ERR_UNSUPPORTED, "complexify_extended: T x T operator too large");
+  h->op = ComplexOp::extended(col3, hbar, U, W, rank, T);
+  h->op_pending = true;           // xmca_solve / xmca_project form X_im = G X (there is no subspace formulation of G)
   h->solved = false;
   API_END(h)
 }
@@ -996,10 +1092,32 @@ int xmca_bootstrap_runs(xmca_handle* h, const double* hilbert_col, const int64_t
   API_BEGIN(h)
   XMCA_CHECK(spectra_out && kept_out && n_out >= 1 && n_runs >= 0, XMCA_ERR_INVALID, "bootstrap: output buffers missing");
   XMCA_CHECK(!rotated || (p >= 2 && power >= 1), XMCA_ERR_INVALID, "bootstrap: rotation needs n_rot >= 2 and power >= 1");
+  XMCA_CHECK(h->boot_fields >= 1 && h->boot_T > 0, XMCA_ERR_STATE, "bootstrap: call xmca_bootstrap_begin first");
+  ComplexOp hop;
+  if (hilbert_col) hop = ComplexOp::circulant(hilbert_col, h->boot_T);
   if (h->dtype == XMCA_F32)
-    bootstrap_runs_impl<float>(h, hilbert_col, idx_left, idx_right, n_runs, rotated, p, power, tol, spectra_out, kept_out, n_out);
+    bootstrap_runs_impl<float>(h, hilbert_col ? &hop : nullptr, idx_left, idx_right, n_runs, rotated, p, power, tol, spectra_out, kept_out,
+                               n_out);
   else
-    bootstrap_runs_impl<double>(h, hilbert_col, idx_left, idx_right, n_runs, rotated, p, power, tol, spectra_out, kept_out, n_out);
+    bootstrap_runs_impl<double>(h, hilbert_col ? &hop : nullptr, idx_left, idx_right, n_runs, rotated, p, power, tol, spectra_out, kept_out,
+                                n_out);
+  h->tm.collect();
+  API_END(h)
+}
+
+int xmca_bootstrap_runs_extended(xmca_handle* h, const double* col3, const double* hbar, const double* U, const double* W, int rank,
+                                 const int64_t* idx_left, const int64_t* idx_right, int64_t n_runs, int rotated, int p, int power,
+                                 double tol, double* spectra_out, int* kept_out, int64_t n_out) {
+  API_BEGIN(h)
+  XMCA_CHECK(spectra_out && kept_out && n_out >= 1 && n_runs >= 0, XMCA_ERR_INVALID, "bootstrap: output buffers missing");
+  XMCA_CHECK(!rotated || (p >= 2 && power >= 1), XMCA_ERR_INVALID, "bootstrap: rotation needs n_rot >= 2 and power >= 1");
+  XMCA_CHECK(col3 && hbar && rank >= 0 && rank <= 16 && (rank == 0 || (U && W)), XMCA_ERR_INVALID,
+             "bootstrap: need col3, hbar and T x rank U, W (rank <= 16)");
+  XMCA_CHECK(h->boot_fields >= 1 && h->boot_T > 0, XMCA_ERR_STATE, "bootstrap: call xmca_bootstrap_begin first");
+  XMCA_CHECK(h->dtype == XMCA_F64, XMCA_ERR_INVALID, "bootstrap: the extended operator needs float64 fields (the reference's replicates are float64)");
+  XMCA_CHECK(h->boot_T <= 46340, XMCA_ERR_UNSUPPORTED, "bootstrap: T x T operator too large");
+  const ComplexOp op = ComplexOp::extended(col3, hbar, U, W, rank, h->boot_T);
+  bootstrap_runs_impl<double>(h, &op, idx_left, idx_right, n_runs, rotated, p, power, tol, spectra_out, kept_out, n_out);
   h->tm.collect();
   API_END(h)
 }

@@ -217,12 +217,13 @@ def broadcast_array(a, dev=None):
     return t.cpu().numpy()
 
 
-def sharded_bootstrap(dev, n_runs, *, T, complexify, idx_left, idx_right, rotated, p, power, tol, n_out):
+def sharded_bootstrap(dev, n_runs, *, T, complexify, idx_left, idx_right, rotated, p, power, tol, n_out, extend_period=None):
     """Bootstrap replicates sharded like the Rule-N runs (xmca/array.py:1935-1947 is the loop; the replicates are independent once
     the row indices are COMPOSED on the host): rank r runs the contiguous block [r*n/W, (r+1)*n/W) of replicates on its own GPU
     (which holds the same fields), ONE all_gather of (n_out + 1) float64 per replicate.  `idx_*`: (n_runs, T) composed row
     indices or None; rank 0's draws are used on every rank (they come from numpy's GLOBAL generator, which the ranks need not
-    share).  Returns (spectra [n_runs x n_out], kept [n_runs] bool) on every rank; any rank's failure raises on all of them."""
+    share).  `extend_period`: replicates of a complex model with extend='exp' (`_hip.Handle.bootstrap_runs`).  Returns (spectra
+    [n_runs x n_out], kept [n_runs] bool) on every rank; any rank's failure raises on all of them."""
     td = _dist()
     rank, world = rank_world()
     if td is not None:
@@ -235,8 +236,10 @@ def sharded_bootstrap(dev, n_runs, *, T, complexify, idx_left, idx_right, rotate
     spec = kept = None
     try:
         if end > begin:
+            ext = {} if extend_period is None else {"extend_period": extend_period}
             spec, kept = dev.bootstrap_runs(T, complexify, None if idx_left is None else idx_left[begin:end],
-                                            None if idx_right is None else idx_right[begin:end], end - begin, rotated, p, power, tol, n_out)
+                                            None if idx_right is None else idx_right[begin:end], end - begin, rotated, p, power, tol, n_out,
+                                            **ext)
         else:
             spec, kept = np.zeros((0, n_out)), np.zeros(0, dtype=bool)
     except Exception as err:                                      # noqa: BLE001  (reported on every rank by _gather_runs)
