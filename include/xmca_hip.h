@@ -114,14 +114,16 @@ int xmca_project(xmca_handle* h, int side, const void* V, int64_t N, int64_t m, 
  * correlation of tools/array.py:76-88): r[n][j] = corr(real part of field column n of `side`, Y[:, j]) on the resident
  * field - one tall GEMM X^T Y plus column moments instead of the reference's (N + m)^2 corrcoef matrix.
  *   Y      T x m row-major float64 (the real parts of the PCs), host memory
- *   r_out  N x m row-major float64
+ *   r_out  N x m row-major float64, clamped to [-1, 1] as np.corrcoef clips; NaN (a constant column) stays NaN
+ * The field is expected centered, as every caller has it: the one-pass variance loses about (mean / std)^2 eps otherwise.
  * p-values (scipy.stats.beta) stay with the caller. */
 int xmca_correlate(xmca_handle* h, int side, const double* Y, int64_t T, int64_t m, double* r_out);
 
 /* Constructor preprocessing on the device (xmca/array.py:199-215 `_set_field_means` / `_set_field_stds` / `_center`;
  * SURVEY 8f row 3): the field of `side` set with xmca_set_field (raw, uncentered) is centered in place, column by
  * column; mean_out / std_out (ddof = 0, float64 accumulation) get N values each and *n_nan_out the number of NaN
- * entries found - when it is not zero nothing was changed and the caller takes its own NaN-column path. */
+ * entries found.  Only the NaN-free columns are centered: a column holding a NaN is left as it is (mean and std NaN), and
+ * the caller takes its own NaN-column path when the count is not zero. */
 int xmca_center_field(xmca_handle* h, int side, double* mean_out, double* std_out, int64_t* n_nan_out);
 /* NaN-column handling of the constructor on the device (xmca/array.py:191-197 `_set_no_nan_idx`, `_remove_nan_cols`,
  * tools/array.py:27-62): keep_out[c] = 1 for every column of the resident raw field of `side` that holds no NaN

@@ -239,3 +239,33 @@ def test_plot_methods_exist_and_say_what_to_use_instead():
     for fn in (m.plot, m.save_plot):
         with pytest.raises(NotImplementedError, match="eofs"):
             fn(mode=1)
+
+
+@pytest.mark.parametrize("order", ["C", "F"])
+def test_eofs_never_return_the_models_own_vectors(order):
+    """unmasked fields and injected vectors: eofs() hands out a copy, so writing into it leaves the model as it was"""
+    from xmca_amd.array import MCA
+    fields = make_input("wide_both")
+    m = MCA(*fields)
+    r = 5
+    rng = np.random.default_rng(0)
+    m._V = {k: np.asarray(rng.standard_normal((f.shape[1], r)), order=order) for k, f in zip(m._keys, fields)}
+    m._analysis.update({'rank': r, 'n_rot': r})
+    V0 = {k: v.copy() for k, v in m._V.items()}
+    for n in (None, r, 1, 3):
+        e = m.eofs(n)
+        for k in m._keys:
+            assert not np.shares_memory(e[k], m._V[k]), (n, k)
+            assert np.array_equal(e[k], V0[k][:, :n]), (n, k)
+            e[k][...] = 7.0
+            assert np.array_equal(m._V[k], V0[k]), (n, k)
+
+
+def test_two_sided_p_of_r_an_ulp_beyond_one_is_zero():
+    from xmca_amd.array import _two_sided_p
+    p = _two_sided_p(np.array([1 + 2 ** -52, -1 - 2 ** -52, 1.0, np.nan]), 50)
+    assert np.array_equal(p, [0.0, 0.0, 0.0, np.nan], equal_nan=True)
+    r = np.linspace(-0.99, 0.99, 7)
+    import scipy.stats
+    ref = 2 * scipy.stats.beta(50 / 2 - 1, 50 / 2 - 1, loc=-1, scale=2).cdf(-np.abs(r))    # tools/array.py:86-88
+    assert np.allclose(_two_sided_p(r, 50), ref, rtol=1e-13, atol=0)

@@ -272,9 +272,13 @@ def test_bootstrapping_runs():
                                                 ("wide_both_f32", True, "1"), ("small_both", True, "1"), ("unit_left", False, "1")])
 def test_pcs_projection_matches_host_formula(name, cplx, analytic, monkeypatch):
     """pcs() = X~ V / sqrt(sigma) (array.py:391): the product runs on the fields resident on the device - real fields,
-    the implicit analytic signal of the subspace path (U = W + i Ht W), stored complex planes (general path), f32."""
+    the implicit analytic signal of the subspace path (U = W + i Ht W), stored complex planes (general path), f32.
+    The solver reads XMCA_ANALYTIC once per process, so the general path ("0") is reached by shape: a right field with no
+    more grid points than time steps makes `Solver::analytic_applicable` false."""
     monkeypatch.setenv("XMCA_ANALYTIC", analytic)
     fields = make_input(name)
+    if analytic == "0":
+        fields = (fields[0], np.ascontiguousarray(fields[1][:, :fields[1].shape[0] - 4]))
     m = MCA(*fields)
     m.solve(complexify=cplx)
     k = 12
@@ -814,3 +818,70 @@ def test_bootstrapping_and_rule_n_through_a_process_group_equal_the_plain_calls(
     assert r.returncode == 0, r.stderr[-3000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("EQUAL")][-1]
     assert line.split()[1] == "True" and line.split()[2] == "True", line
+
+
+# ----------------------------------------------------------------------------------------------
+# edge values of the correlation maps, ownership of eofs()
+# ----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("cplx", [False, True])
+def test_correlation_maps_of_a_single_point_field_stay_in_range(cplx):
+    """A (T, 1) left field: its PC is +-(the field) (real) and the homogeneous map is r = +-1 there.  The device correlation
+    sums the covariance and the variances in different orders, so |r| may land an ulp beyond 1 unless it is clamped; the
+    p-value of such an r (betainc of a negative argument) would be NaN where the reference reports 0."""
+    from xmca_amd.tools.array import pearsonr
+    rng = np.random.default_rng(1)
+    T = 120
+    pc = rng.standard_normal(T)
+    left = (3.0 * pc + 0.1 * rng.standard_normal(T))[:, None]
+    right = np.outer(pc, rng.standard_normal(150)) + 0.5 * rng.standard_normal((T, 150))
+    m = MCA(left, right)
+    m.solve(complexify=cplx)
+    X = m._get_X(real=True)
+    pcs = m.pcs()
+    other = {'left': 'right', 'right': 'left'}
+    for maps, pair in ((m.homogeneous_patterns(), {k: k for k in m._keys}), (m.heterogeneous_patterns(), other)):
+        rv, pv = maps
+        for k in m._keys:
+            r = rv[k].reshape(X[k].shape[1], -1)
+            p = pv[k].reshape(X[k].shape[1], -1)
+            assert not np.any(np.isnan(r)) and not np.any(np.isnan(p))       # no masked points here
+            assert np.all(np.abs(r) <= 1)
+            assert np.all(p[np.abs(r) == 1] == 0)
+            r_ref, p_ref = pearsonr(X[k], pcs[pair[k]].real)
+            assert np.max(np.abs(r - r_ref)) < 1e-10
+            assert np.max(np.abs(p - p_ref)) < 50 * 1e-10
+    if not cplx:
+        r = m.homogeneous_patterns()[0]['left'].reshape(-1)
+        assert np.all(np.abs(np.abs(r) - 1) < 1e-14)
+
+
+def _assert_eofs_are_copies(m, n=None):
+    """eofs(n) must not hand out the model's own vectors: writing into the result changes nothing the model returns later"""
+    e = m.eofs(n)
+    V0 = {k: np.array(m._V[k]) for k in m._keys}
+    pcs0 = m.pcs(n)
+    e0 = {k: np.array(v) for k, v in m.eofs(n).items()}
+    for k in m._keys:
+        assert not np.shares_memory(e[k], m._V[k]), k
+        e[k][...] = 7.0
+    for k in m._keys:
+        assert np.array_equal(np.asarray(m._V[k]), V0[k]), k
+        assert _rel(m.pcs(n)[k], pcs0[k]) < 1e-12, k
+        assert np.array_equal(m.eofs(n)[k], e0[k]), k
+
+
+@pytest.mark.parametrize("n", [None, 1, 3])
+def test_eofs_own_their_memory_in_every_route(n):
+    fields = make_input("small_both")
+    m = MCA(*fields)
+    m.solve()
+    assert set(m._V._pending) == set(m._keys)
+    _assert_eofs_are_copies(m, n)                           # device route (the vectors still resident)
+    m = MCA(*fields)
+    m.solve()
+    m._V.materialize()
+    _assert_eofs_are_copies(m, n)                           # host route: eofs(1) of F-ordered vectors is C-contiguous
+    m = MCA(*fields)
+    m.solve()
+    m._V = {k: np.ascontiguousarray(m._V[k]) for k in m._keys}
+    _assert_eofs_are_copies(m, n)                           # injected C-contiguous vectors

@@ -386,8 +386,8 @@ class Handle:
         return out.view(np.float64).reshape(-1)[:T * m].reshape(T, m).copy()
 
     def center_field(self, side, N):
-        """Centers the resident (raw) field of `side` in place.  Returns (mean[N], std[N], number of NaN entries); when
-        the last is not zero the field is unchanged."""
+        """Centers the resident (raw) field of `side` in place.  Returns (mean[N], std[N], number of NaN entries).  Only the
+        columns without NaN are centered; a column holding a NaN is left as it is, and its mean and std are NaN."""
         self.release_result()
         mean = np.empty(N, dtype=np.float64)
         std = np.empty(N, dtype=np.float64)

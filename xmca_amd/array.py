@@ -29,7 +29,9 @@ def _two_sided_p(r, n_obs):
     `homogeneous_patterns` costs on the host (18 of 21.7 ms at C2 for 10^5 values; it holds the GIL, so threads do not help)."""
     import scipy.special
     a = n_obs / 2 - 1
-    return 2 * scipy.special.betainc(a, a, (1.0 - np.abs(np.asarray(r, dtype=np.float64))) / 2)
+    # |r| an ulp above 1 (correlations summed in another order than the variances) is |r| = 1, p = 0; NaN stays NaN
+    x = np.clip((1.0 - np.abs(np.asarray(r, dtype=np.float64))) / 2, 0.0, 1.0)
+    return 2 * scipy.special.betainc(a, a, x)
 
 
 class _LazyVectors(dict):
@@ -716,13 +718,16 @@ class MCA:
 
     def _get_eofs(self, n=None, scaling='None', phase_shift=0, rotated=True):
         V = self._eofs_from_device(n, rotated)
+        fresh = V is not None                 # arrays of the device path are the caller's; `_get_V` may return views of `_V`
         if V is None:
             V = self._get_V(n, rotated=rotated)
         eofs = {}
         for k in self._keys:
             n_modes = V[k].shape[1]
-            if self._n_variables[k] == V[k].shape[0] and V[k].flags['C_CONTIGUOUS']:
+            if self._n_variables[k] == V[k].shape[0] and fresh and V[k].flags['C_CONTIGUOUS']:
                 full = V[k]                                                   # no masked points: the array is final as it is
+            elif self._n_variables[k] == V[k].shape[0]:
+                full = np.array(V[k], order='C')                              # (a copy: never the model's own vectors)
             else:
                 full = np.full((self._n_variables[k], n_modes), np.nan, dtype=V[k].dtype)
                 full[self._no_nan_index[k]] = V[k]                            # (N, n_modes), NaN at masked points

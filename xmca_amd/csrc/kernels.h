@@ -496,7 +496,9 @@ __global__ void column_moments_kernel(const T* __restrict__ x, int rows, int64_t
   sumsq[c] = q;
 }
 
-// Pearson correlation from the raw cross products: r[n][j] = (C[n][j] - sx[n] sy[j] / T) / sqrt((qx[n] - sx[n]^2 / T) (qy[j] - sy[j]^2 / T))
+// Pearson correlation from the raw cross products: r[n][j] = (C[n][j] - sx[n] sy[j] / T) / sqrt((qx[n] - sx[n]^2 / T) (qy[j] - sy[j]^2 / T)),
+// clamped to [-1, 1] as numpy.corrcoef clips: C (GEMM) and qx, qy (column moments) sum in different orders, so a perfectly
+// (anti-)correlated pair can land an ulp beyond 1.  The comparisons pass NaN through (fmin / fmax would not).
 __global__ void pearson_finish_kernel(double* __restrict__ C, int64_t N, int m, int T, const double* __restrict__ sx,
                                       const double* __restrict__ qx, const double* __restrict__ sy, const double* __restrict__ qy) {
   const int64_t total = N * m;
@@ -505,7 +507,8 @@ __global__ void pearson_finish_kernel(double* __restrict__ C, int64_t N, int m, 
     const int j = (int)(i % m);
     const double cov = C[i] - sx[n] * sy[j] / T;
     const double vx = qx[n] - sx[n] * sx[n] / T, vy = qy[j] - sy[j] * sy[j] / T;
-    C[i] = cov / sqrt(vx * vy);          // constant columns give NaN, like numpy.corrcoef
+    const double r = cov / sqrt(vx * vy);          // constant columns give NaN, like numpy.corrcoef
+    C[i] = r > 1.0 ? 1.0 : (r < -1.0 ? -1.0 : r);
   }
 }
 
