@@ -41,7 +41,7 @@ typedef struct xmca_handle xmca_handle;
 /* library / device management ------------------------------------------------------------------------- */
 const char* xmca_version(void);
 /* Number of this header's ABI (XMCA_ABI_VERSION): the binding refuses a library built from another revision. */
-#define XMCA_ABI_VERSION 10
+#define XMCA_ABI_VERSION 11
 int xmca_abi_version(void);
 int xmca_device_count(void);
 int xmca_create(int device, xmca_handle** out);
@@ -106,9 +106,36 @@ int xmca_get_eofs(xmca_handle* h, int side, const double* W, int64_t m, int64_t 
  * xmca_complexify_extended (the imaginary planes G X are formed first when the solve has not done so).
  *   V      N x m row-major, float64 (is_complex = 0) or interleaved complex128 (is_complex = 1), host memory
  *   U_out  T x m row-major float64, interleaved complex128 when *out_is_complex = 1 (model or V complex)
+ *   V == NULL (ABI 11): the first m vectors of the last solve, still resident on the device (N = their length, m <= the modes
+ *          back-projected); is_complex is then ignored
  * The scaling by 1/sqrt(sigma) and the rotation (array.py:391-393) stay with the caller (m x m work). */
 int xmca_project(xmca_handle* h, int side, const void* V, int64_t N, int64_t m, int is_complex, void* U_out,
                  int* out_is_complex);
+
+/* MCA.predict on new data (xmca/array.py:1299-1428, ABI 11): out (T_new x q) = (((X[:, keep] - mean) / std) V[:, :m]) W.
+ *   X         T_new x N_full row-major new data, host memory, element type `dtype` (the model's real field dtype)
+ *   keep_idx  N_keep increasing column indices (int64) of the grid points kept by the model; NULL: all N_full = N_keep columns
+ *   mean, std N_keep values of `dtype`; std == NULL: no division.  Subtraction and division run in `dtype`, the host's
+ *             `x -= mean; x /= std` bit for bit
+ *   V         N_keep x m host float64 / interleaved complex128 (v_is_complex), or NULL: the first m resident vectors of the last
+ *             solve of `side` (the product then runs in their precision: float32 vectors of a real float32 field stay float32)
+ *   W         m x q float64 / interleaved complex128 (w_is_complex) mixing matrix, host memory (the caller's 1/sqrt(sigma), inverse
+ *             rotation, mode order and selection)
+ *   out       T_new x q float64, interleaved complex128 when *out_is_complex = 1 (V or W complex)
+ * Rows are processed in blocks of bounded size.  The resident fields and vectors are not changed. */
+int xmca_predict(xmca_handle* h, int side, const void* X, int64_t T_new, int64_t N_full, int dtype, const int64_t* keep_idx,
+                 int64_t N_keep, const void* mean, const void* std, const void* V, int v_is_complex, const double* W, int64_t m,
+                 int64_t q, int w_is_complex, double* out, int* out_is_complex);
+
+/* MCA.reconstructed_fields / _reconstructed_X (xmca/array.py:1263-1292, ABI 11): out (T x N_full, float64, row-major).  Kept
+ * column keep_idx[c] = Re(B V[:, :m]^H)[:, c], times std[c] when std != NULL, plus mean[c] when mean != NULL; every other column
+ * NaN.  keep_idx == NULL with N_full == N_keep: the compact T x N_keep result.
+ *   B         T x m float64 / interleaved complex128 (b_is_complex) coefficients, host memory; m == 0: a zero product
+ *   V         N_keep x m host float64 / interleaved complex128 (v_is_complex), or NULL: the first m resident vectors of `side`
+ *   mean, std N_keep float64 values or NULL
+ * Rows are processed in blocks of bounded size.  The resident fields and vectors are not changed. */
+int xmca_reconstruct(xmca_handle* h, int side, const double* B, int64_t T, int64_t m, int b_is_complex, const void* V, int v_is_complex,
+                     const int64_t* keep_idx, int64_t N_keep, int64_t N_full, const double* mean, const double* std, double* out);
 
 /* Correlation maps of MCA.homogeneous_patterns / heterogeneous_patterns (xmca/array.py:1188-1261, the Pearson
  * correlation of tools/array.py:76-88): r[n][j] = corr(real part of field column n of `side`, Y[:, j]) on the resident

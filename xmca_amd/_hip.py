@@ -50,6 +50,9 @@ SIGNATURES = {
                                               _c_i64]),
     "xmca_correlate": (_c_int, [_vp, _c_int, _vp, _c_i64, _c_i64, _vp]),
     "xmca_project": (_c_int, [_vp, _c_int, _vp, _c_i64, _c_i64, _c_int, _vp, ctypes.POINTER(_c_int)]),
+    "xmca_predict": (_c_int, [_vp, _c_int, _vp, _c_i64, _c_i64, _c_int, _vp, _c_i64, _vp, _vp, _vp, _c_int, _vp, _c_i64, _c_i64, _c_int,
+                              _vp, ctypes.POINTER(_c_int)]),
+    "xmca_reconstruct": (_c_int, [_vp, _c_int, _vp, _c_i64, _c_i64, _c_int, _vp, _c_int, _vp, _c_i64, _c_i64, _vp, _vp, _vp]),
     "xmca_is_complex": (_c_int, [_vp]),
     "xmca_vectors_are_f32": (_c_int, [_vp, _c_int]),
     "xmca_persistent_giveups": (ctypes.c_longlong, []),
@@ -90,7 +93,7 @@ def library_path():
     return _build.LIB
 
 
-ABI_VERSION = 10         # bumped whenever a signature of include/xmca_hip.h changes; checked against xmca_abi_version()
+ABI_VERSION = 11         # bumped whenever a signature of include/xmca_hip.h changes; checked against xmca_abi_version()
 
 
 def load_library():
@@ -371,19 +374,79 @@ class Handle:
         self._check(self._lib.xmca_get_eofs(self._h, side, _ptr(W), m, q, int(w_cplx), _ptr(out), code))
         return out
 
-    def project(self, side, V, T):
+    def project(self, side, V, T, m=None, N=None):
         """U = X~ V (T x m) on the resident field of `side` (the analytic signal when the model is complex);
-        float64 / complex128.  MCA._get_U's `fields[k] @ V[k]` (array.py:391)."""
-        V = np.asarray(V)
-        cplx = np.iscomplexobj(V)
-        Vd = np.ascontiguousarray(V, dtype=np.complex128 if cplx else np.float64)
-        N, m = Vd.shape
+        float64 / complex128.  MCA._get_U's `fields[k] @ V[k]` (array.py:391).  V None: the first m vectors of the last solve,
+        still resident (N: their length)."""
+        if V is None:
+            Vd, cplx = None, False
+        else:
+            V = np.asarray(V)
+            cplx = np.iscomplexobj(V)
+            Vd = np.ascontiguousarray(V, dtype=np.complex128 if cplx else np.float64)
+            N, m = Vd.shape
         out = np.empty((T, m), dtype=np.complex128)          # large enough for either result type
         out_cplx = _c_int(0)
         self._check(self._lib.xmca_project(self._h, side, _ptr(Vd), N, m, int(cplx), _ptr(out), ctypes.byref(out_cplx)))
         if out_cplx.value:
             return out
         return out.view(np.float64).reshape(-1)[:T * m].reshape(T, m).copy()
+
+    @staticmethod
+    def _host_vectors(V):
+        if V is None:
+            return None, False
+        V = np.asarray(V)
+        cplx = np.iscomplexobj(V)
+        return np.ascontiguousarray(V, dtype=np.complex128 if cplx else np.float64), cplx
+
+    def predict(self, side, X, keep_idx, mean, std, V, W):
+        """((X[:, keep_idx] - mean) / std) V W (T' x q, float64 / complex128) on the device (xmca_predict): MCA.predict's product
+        without the vectors leaving the device.  X: T' x N_full real new data (its dtype is the ingest's: mean / std are cast to
+        it); keep_idx: kept columns or None; std None: no division; V: N' x m host vectors or None (the first m resident ones of
+        the last solve of `side`); W: m x q mix.  The resident fields and vectors stay as they are."""
+        X = np.ascontiguousarray(X)
+        code = _np_dtype_code(X.dtype)
+        if np.iscomplexobj(X) or X.ndim != 2:
+            raise TypeError("predict: X must be a real 2-D array")
+        T, N_full = X.shape
+        idx = None if keep_idx is None else np.ascontiguousarray(keep_idx, dtype=np.int64)
+        N = N_full if idx is None else idx.size
+        mean = np.ascontiguousarray(np.broadcast_to(mean, (N,)), dtype=X.dtype)
+        std = None if std is None else np.ascontiguousarray(np.broadcast_to(std, (N,)), dtype=X.dtype)
+        Vd, v_cplx = self._host_vectors(V)
+        w_cplx = np.iscomplexobj(W)
+        Wd = np.ascontiguousarray(W, dtype=np.complex128 if w_cplx else np.float64)
+        m, q = Wd.shape
+        if Vd is not None and Vd.shape != (N, m):
+            raise ValueError("predict: V must be N' x m = %d x %d, got %s" % (N, m, Vd.shape))
+        out = np.empty((T, q), dtype=np.complex128)
+        out_cplx = _c_int(0)
+        self._check(self._lib.xmca_predict(self._h, side, _ptr(X), T, N_full, code, _ptr(idx), N, _ptr(mean), _ptr(std), _ptr(Vd),
+                                           int(v_cplx), _ptr(Wd), m, q, int(w_cplx), _ptr(out), ctypes.byref(out_cplx)))
+        if out_cplx.value:
+            return out
+        return out.view(np.float64).reshape(-1)[:T * q].reshape(T, q).copy()
+
+    def reconstruct(self, side, B, V, N, keep_idx=None, N_full=None, mean=None, std=None):
+        """Re(B V^H) (* std + mean) on the device (xmca_reconstruct), T x N_full float64 with NaN at the columns not in keep_idx.
+        B: T x m coefficients; V: N x m host vectors or None (the first m resident ones of the last solve of `side`).  The
+        resident fields and vectors stay as they are."""
+        B = np.asarray(B)
+        b_cplx = np.iscomplexobj(B)
+        Bd = np.ascontiguousarray(B, dtype=np.complex128 if b_cplx else np.float64)
+        T, m = Bd.shape
+        Vd, v_cplx = self._host_vectors(V)
+        if Vd is not None and Vd.shape != (N, m):
+            raise ValueError("reconstruct: V must be N x m = %d x %d, got %s" % (N, m, Vd.shape))
+        idx = None if keep_idx is None else np.ascontiguousarray(keep_idx, dtype=np.int64)
+        N_full = N if N_full is None else N_full
+        mean = None if mean is None else np.ascontiguousarray(np.broadcast_to(mean, (N,)), dtype=np.float64)
+        std = None if std is None else np.ascontiguousarray(np.broadcast_to(std, (N,)), dtype=np.float64)
+        out = np.empty((T, N_full), dtype=np.float64)
+        self._check(self._lib.xmca_reconstruct(self._h, side, _ptr(Bd) if m else None, T, m, int(b_cplx), _ptr(Vd), int(v_cplx), _ptr(idx),
+                                               N, N_full, _ptr(mean), _ptr(std), _ptr(out)))
+        return out
 
     def center_field(self, side, N):
         """Centers the resident (raw) field of `side` in place.  Returns (mean[N], std[N], number of NaN entries).  Only the

@@ -7,6 +7,8 @@ Device side (libxmca_hip.so through `_hip.Handle`): the numerical core of
   * `solve`   xmca/array.py:549-584   (per-field SVD, kernel, kernel SVD, back-projection)
   * `rotate`  xmca/array.py:821-823 + xmca/tools/rotation.py (Varimax/Promax loop)
   * `rule_n`  xmca/array.py:1753-1765 (surrogate loop; run-sharded over ranks when torch.distributed is up)
+  * `predict` xmca/array.py:1299-1428 and `reconstructed_fields` :1263-1292 (products over the resident vectors; the host route
+    remains for other dtypes and models without device vectors)
 There is no numpy fallback for these three: without the library or a GPU they raise.
 """
 import cmath
@@ -32,6 +34,28 @@ def _two_sided_p(r, n_obs):
     # |r| an ulp above 1 (correlations summed in another order than the variances) is |r| = 1, p = 0; NaN stays NaN
     x = np.clip((1.0 - np.abs(np.asarray(r, dtype=np.float64))) / 2, 0.0, 1.0)
     return 2 * scipy.special.betainc(a, a, x)
+
+
+def _predict_mix(svals, R_inv_t, var_idx, n_rot, n):
+    """m x q mix of MCA.predict: pcs = x V[:, :m] W reproduces the reference's `(x @ V[:, :n_rot] / sqrt(s[:n_rot])) @ R` followed
+    by `[:, var_idx][:, :n]` (array.py:1299-1428) with W = diag(1 / sqrt(s[:n_rot])) R^-H[:, var_idx][:, :n], R^-H the
+    `rotation_matrix(inverse_transpose=True)`.  Trailing rows of W that are zero (modes no selected column mixes in, e.g. an
+    unrotated model asked for n < rank modes) are dropped, so m <= n_rot vectors enter the product."""
+    W = (R_inv_t / np.sqrt(svals[:n_rot])[:, None])[:, var_idx][:, :n]
+    used = np.flatnonzero(np.any(W != 0, axis=1))           # (a NaN row is used: it propagates as the reference's does)
+    return W[:used[-1] + 1] if used.size else W[:1]
+
+
+def _rotated_mix(svals, R, norm, var_idx, keep):
+    """m x q mix A of the rotated vectors: V_rot = V[:, :m] A with A = (diag(sqrt(s)) R / norm)[:, var_idx][:, keep], m = len(s)
+    (`_get_V`, array.py:615-646).  Used by the device EOFs and the reconstruction."""
+    return ((np.sqrt(svals)[:, None] * R) / norm)[:, var_idx][:, keep]
+
+
+def _reconstruct_coefficients(P, A):
+    """T x m coefficients B = P A^H of the reconstruction: (P @ V_rot^H).real = Re(B V[:, :m]^H) for V_rot = V[:, :m] A, with P the
+    PCs in 'eigen' scaling (array.py:1263-1292)."""
+    return P @ A.conj().T
 
 
 class _LazyVectors(dict):
@@ -645,6 +669,34 @@ class MCA:
             return {k: np.zeros((T, 0), dtype=V[k].dtype) for k in self._keys}
         return {k: dev.project(side, V[k], T) for side, k in enumerate(self._keys)}
 
+    def _vectors_resident(self):
+        """True while every vector of this model's last solve is still on the device only (nothing fetched, result held)."""
+        V = getattr(self, '_V', None)
+        return isinstance(V, _LazyVectors) and V._pending == set(self._keys) and self._device().holds_result_of(self)
+
+    def _resident_dtype(self):
+        """dtype the resident vectors have on the host (`_LazyVectors`): complex for a complex solve."""
+        dt = self._V._dtype
+        return np.result_type(dt, np.complex64) if self._analysis['is_complex'] else np.dtype(dt)
+
+    def _project_resident(self, max_mode):
+        """fields[k] @ V[k][:, :max_mode] of `_get_U` with the vectors still resident (xmca_project without V): nothing is fetched
+        or uploaded again.  (None, None) when they are not resident - the caller then takes `_get_V`."""
+        if not self._vectors_resident():
+            return None, None
+        dev = self._device()
+        if not self._owns_device_fields(dev):
+            self._upload_serial += 1
+            self._upload_fields(dev)              # (may release the result: checked again below)
+            if not self._vectors_resident():
+                return None, None
+        m = self._analysis['rank'] if max_mode is None else min(int(max_mode), self._analysis['rank'])
+        T = self._n_observations['left']
+        vdt = {k: self._resident_dtype() for k in self._keys}
+        if m < 1:
+            return {k: np.zeros((T, 0), dtype=vdt[k]) for k in self._keys}, vdt
+        return {k: dev.project(side, None, T, m, self._V._where[k][1]) for side, k in enumerate(self._keys)}, vdt
+
     def _get_U(self, n=None, rotated=True):
         keep = self._get_slice(n)
         mix = rotated and self._analysis['is_rotated']
@@ -655,12 +707,15 @@ class MCA:
             # the kept modes are projected instead - same numbers, no T x N x rank product for pcs(10), and the
             # null modes (sigma = 0 exactly on the device) cannot leak 0 * inf into the kept columns
             max_mode = keep.stop if keep.stop is not None else self._analysis['rank']
-        V = self._get_V(max_mode, rotated=False)
         sqrt_svals = np.sqrt(self._get_svals(max_mode))
-        XV = self._project_on_device(V)
+        XV, vdt = self._project_resident(max_mode)
+        if XV is None:
+            V = self._get_V(max_mode, rotated=False)
+            XV = self._project_on_device(V)
+            vdt = {k: V[k].dtype for k in self._keys}
         U = {}
         for k in self._keys:
-            U[k] = XV[k].astype(np.result_type(V[k].dtype, self._fields_store[k].dtype), copy=False) / sqrt_svals
+            U[k] = XV[k].astype(np.result_type(vdt[k], self._fields_store[k].dtype), copy=False) / sqrt_svals
             if mix:
                 R = self.rotation_matrix(inverse_transpose=True)
                 U[k] = (U[k] @ R)[:, self._var_idx]
@@ -687,12 +742,10 @@ class MCA:
         """(N' x q) array per field in its final memory layout, mixed on the device from the vectors still resident there
         (`xmca_get_eofs`), or None when they are not (then `_get_V`'s host path is taken).  Same numbers as `_get_V`:
         `(V sqrt(s)) @ R / norm`, columns ordered by explained variance, then the requested slice (array.py:615-646)."""
-        Vl = getattr(self, '_V', None)
-        if not (isinstance(Vl, _LazyVectors) and Vl._pending == set(self._keys)):
+        if not self._vectors_resident():
             return None                                   # (vectors already on the host - or injected by a test: no device needed)
+        Vl = self._V
         dev = self._device()
-        if not dev.holds_result_of(self):
-            return None
         rotated = rotated and self._analysis['is_rotated']
         max_mode = self._max_mode(n, rotated)
         max_mode = self._analysis['rank'] if max_mode is None else min(max_mode, self._analysis['rank'])
@@ -703,9 +756,8 @@ class MCA:
         for side, k in enumerate(self._keys):
             n_k = Vl._where[k][1]
             if rotated:
-                sqrt_svals = np.sqrt(self._get_svals(max_mode))
                 norm = self._get_norm(max_mode, sorted=False)
-                W = ((sqrt_svals[:, None] * self.rotation_matrix()) / norm[k])[:, self._var_idx][:, keep]
+                W = _rotated_mix(self._get_svals(max_mode), self.rotation_matrix(), norm[k], self._var_idx, keep)
                 out[k] = dev.eofs(side, n_k, max_mode, W, np.float64)
             else:
                 cols = range(max_mode)[keep]
@@ -913,7 +965,65 @@ class MCA:
         other = dict(zip(['left', 'right'], ['right', 'left']))
         return self._correlation_maps(n, phase_shift, other)
 
+    def _transform_vectors(self, k):
+        """(handle, vectors) for the device transforms of field k (xmca_predict / xmca_reconstruct): vectors None while they are
+        still resident from this model's solve, the host array once they were fetched (or truncated).  None - the host path - for
+        a model that was not solved by this package (`load_analysis`, injected vectors), a subclass with its own scaling and under
+        `_transform_on_host`."""
+        V = getattr(self, '_V', None)
+        if getattr(self, '_transform_on_host', False) or not isinstance(V, _LazyVectors):
+            return None
+        if type(self)._scale_X is not MCA._scale_X or type(self)._scale_X_inverse is not MCA._scale_X_inverse:
+            return None                   # a subclass scales differently (the xarray facade's coslat weights): its own host path
+        dev = self._device()
+        if k in V._pending:
+            return (dev, None) if dev.holds_result_of(self) else None
+        return dev, V[k]
+
+    def _reconstruct_on_device(self, mode, original_scale, full):
+        """`(pcs(mode, 'eigen') @ V_rot^H).real`, scaled back and (full) with the masked points re-inserted as NaN, as one product
+        over the vectors on the device per field (xmca_reconstruct): B = P A^H (T x m, `_reconstruct_coefficients`) is the only
+        host work.  Returns {k: T x N (full) or T x N'} or None when the host path has to run."""
+        route = {k: self._transform_vectors(k) for k in self._keys}
+        if any(r is None for r in route.values()):
+            return None
+        rotated = self._analysis['is_rotated']
+        keep = self._get_slice(mode)
+        max_mode = self._max_mode(mode, rotated)
+        max_mode = self._analysis['rank'] if max_mode is None else min(int(max_mode), self._analysis['rank'])
+        for dev, Vh in route.values():
+            if Vh is not None:
+                max_mode = min(max_mode, Vh.shape[1])
+        P = self._get_pcs(n=mode, scaling='eigen', rotated=True)
+        T = self._n_observations['left']
+        out = {}
+        for side, k in enumerate(self._keys):
+            dev, Vh = self._transform_vectors(k)          # (again: the projection above may have fetched the vectors)
+            vdt = self._resident_dtype() if Vh is None else Vh.dtype
+            if rotated:
+                A = _rotated_mix(self._get_svals(max_mode), self.rotation_matrix(), self._get_norm(max_mode, sorted=False)[k],
+                                 self._var_idx, keep)
+                vdt = np.result_type(vdt, np.float64)
+            else:
+                A = np.eye(max_mode)[:, keep]
+            B = _reconstruct_coefficients(P[k], A) if A.shape[1] else np.zeros((T, 0))
+            dtype = _real_dtype(np.result_type(P[k].dtype, vdt))            # the reference's (U @ V^H).real
+            n_keep = self._fields_store[k].shape[1]
+            mean = std = None
+            if original_scale:
+                mean = self._field_means[k]
+                std = self._field_stds[k] if self._analysis['is_normalized'] else None
+            mask = self._no_nan_index[k]
+            keep_idx = np.flatnonzero(mask) if (full and n_keep != mask.size) else None
+            X = dev.reconstruct(side, B, None if Vh is None else Vh[:, :B.shape[1]], n_keep, keep_idx=keep_idx,
+                                N_full=mask.size if keep_idx is not None else n_keep, mean=mean, std=std)
+            out[k] = X if full else X.astype(dtype, copy=False)
+        return out
+
     def _reconstructed_X(self, mode=None, original_scale=True):
+        rec = self._reconstruct_on_device(mode, original_scale, full=False)
+        if rec is not None:
+            return rec
         V = self._get_V(n=mode, rotated=True)
         U = self._get_pcs(n=mode, scaling='eigen', rotated=True)
         Xrec = {k: (U[k] @ V[k].conj().T).real for k in self._keys}
@@ -923,6 +1033,9 @@ class MCA:
 
     def reconstructed_fields(self, mode=None, original_scale=True):
         n_obs = self._n_observations['left']
+        rec = self._reconstruct_on_device(mode, original_scale, full=True)
+        if rec is not None:                  # final layout from the device: NaN at the masked points, float64
+            return {k: X.reshape((-1,) + self._fields_spatial_shape[k]) for k, X in rec.items()}
         out = {}
         for k, X in self._reconstructed_X(mode=mode, original_scale=original_scale).items():
             full = self._with_nan_columns(k, np.asarray(X, dtype=float), (n_obs,))
@@ -935,18 +1048,28 @@ class MCA:
     # predict (array.py:1299-1428)
     # ------------------------------------------------------------------------------------------
     def predict(self, left=None, right=None, n=None, scaling='None', phase_shift=0):
-        """Project new data on the singular vectors (rotated if the model is)."""
-        new = {k: d.copy() for k, d in zip(self._keys, [left, right]) if d is not None}
-        V = self._get_V(rotated=False)
-        sqrt_svals = np.sqrt(self._get_svals())
+        """Project new data on the singular vectors (rotated if the model is).  Real new data of the model's field dtype is
+        projected on the device (xmca_predict: the vectors stay there), anything else on the host as the reference does."""
+        given = {k: d for k, d in zip(self._keys, [left, right]) if d is not None}
+        on_device = all(isinstance(d, np.ndarray) and d.dtype == _real_dtype(self._fields_store[k].dtype)
+                        and self._transform_vectors(k) is not None for k, d in given.items())
+        if on_device:
+            V = None
+            svals = self._get_svals()
+        else:
+            given = {k: d.copy() for k, d in given.items()}
+            V = self._get_V(rotated=False)
+            sqrt_svals = np.sqrt(self._get_svals())
         R = self.rotation_matrix(inverse_transpose=True)
         n_rot = R.shape[0]
         if n is None:
             n = n_rot
         out = {}
-        for k, x in new.items():
+        for k, x in given.items():
             try:
-                x = x.reshape(x.shape[0], self._n_variables[k])[:, self._no_nan_index[k]]
+                x = x.reshape(x.shape[0], self._n_variables[k])
+                if not on_device:
+                    x = x[:, self._no_nan_index[k]]
             except ValueError as err:
                 if len(x.shape) != len(self._shape[k]):
                     msg = ('Error in {:} field. Dimension of new data ({:}) and the original field ({:}) do not match. '
@@ -957,14 +1080,17 @@ class MCA:
                 else:
                     msg = 'Dimension mismatch in {:} field.'.format(k)
                 raise ValueError(msg) from err
-            try:
-                x = self._scale_X({k: x})[k]
-            except ValueError as err:
-                msg = ('Error in {:} field. Spatial dimensions of new data {:} and the original field {:} '
-                       'do not match.').format(k, x.shape[1:], self._field_means[k].shape)
-                raise ValueError(msg) from err
-            pcs = (x @ V[k][:, :n_rot] / sqrt_svals[:n_rot]) @ R
-            pcs = pcs[:, self._var_idx][:, :n]
+            if on_device:
+                pcs = self._predict_on_device(k, x, svals, R, n_rot, n)
+            else:
+                try:
+                    x = self._scale_X({k: x})[k]
+                except ValueError as err:
+                    msg = ('Error in {:} field. Spatial dimensions of new data {:} and the original field {:} '
+                           'do not match.').format(k, x.shape[1:], self._field_means[k].shape)
+                    raise ValueError(msg) from err
+                pcs = (x @ V[k][:, :n_rot] / sqrt_svals[:n_rot]) @ R
+                pcs = pcs[:, self._var_idx][:, :n]
             if self._analysis['is_complex']:
                 pcs = pcs * cmath.rect(1, phase_shift)
             if scaling == 'None':
@@ -979,6 +1105,20 @@ class MCA:
                 raise ValueError(_SCALINGS_MSG.format(scaling))
             out[k] = pcs
         return out
+
+    def _predict_on_device(self, k, x, svals, R_inv_t, n_rot, n):
+        """`(x[:, kept] - mean) / std @ V[:, :n_rot] / sqrt(s) @ R^-H`, columns ordered and selected, for the raw T' x N new data x
+        of field k: one ingest + product on the device (xmca_predict) with the m x q mix of `_predict_mix`.  As `_scale_X` is called
+        with this field alone, it is divided by std whenever the model is normalized."""
+        W = _predict_mix(svals, R_inv_t, self._var_idx, n_rot, n)
+        if W.shape[1] == 0:
+            return np.zeros((x.shape[0], 0), dtype=np.result_type(W.dtype, self._resident_dtype()))
+        dev, Vh = self._transform_vectors(k)
+        mask = self._no_nan_index[k]
+        keep_idx = None if mask.all() else np.flatnonzero(mask)
+        std = self._field_stds[k] if self._analysis['is_normalized'] else None
+        side = self._keys.index(k)
+        return dev.predict(side, x, keep_idx, self._field_means[k], std, None if Vh is None else Vh[:, :W.shape[0]], W)
 
     # ------------------------------------------------------------------------------------------
     # significance (array.py:1716-1952)

@@ -469,6 +469,59 @@ __global__ void scale_columns_kernel(T* __restrict__ x, int rows, int64_t cols, 
   }
 }
 
+// New data of MCA.predict (xmca_predict): out[t][c] = (raw[t][idx[c]] - mean[c]) / std[c] for a rows x n_full row-major block, in
+// the element type TI of the data - numpy's `x -= mean; x /= std` bit for bit (a subtraction, then a correctly rounded division:
+// nothing to contract) - stored as the product's element type TP.  idx == nullptr: all columns (the contiguous case);
+// std == nullptr: no division.  Rows over blockIdx.y, columns over x: no index division per element.
+template <typename TI, typename TP>
+__global__ void ingest_columns_kernel(const TI* __restrict__ raw, int64_t n_full, const int64_t* __restrict__ idx, int rows,
+                                      int64_t cols, const TI* __restrict__ mean, const TI* __restrict__ stdv, TP* __restrict__ out) {
+  for (int t = blockIdx.y; t < rows; t += gridDim.y) {
+    const TI* src = raw + (int64_t)t * n_full;
+    TP* dst = out + (int64_t)t * cols;
+    for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < cols; c += (int64_t)gridDim.x * blockDim.x) {
+      TI v = src[idx ? idx[c] : c];
+      v = v - mean[c];
+      if (stdv) v = v / stdv[c];
+      dst[c] = (TP)v;
+    }
+  }
+}
+
+// Reconstruction epilogue (xmca_reconstruct): one pass from the compact rows x n_keep product C to the final rows x n_full
+// float64 layout.  Column j of the output is column col_of[j] of C (col_of == nullptr: j itself), or NaN where col_of[j] < 0;
+// kept values become C * std + mean like numpy's `x *= std; x += mean` (two roundings: not contracted), either factor optional.
+__global__ void reconstruct_epilogue_kernel(const double* __restrict__ C, int64_t n_keep, const int64_t* __restrict__ col_of, int rows,
+                                            int64_t n_full, const double* __restrict__ stdv, const double* __restrict__ mean,
+                                            double* __restrict__ out) {
+#pragma clang fp contract(off)
+  for (int t = blockIdx.y; t < rows; t += gridDim.y) {
+    const double* src = C + (int64_t)t * n_keep;
+    double* dst = out + (int64_t)t * n_full;
+    for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n_full; j += (int64_t)gridDim.x * blockDim.x) {
+      const int64_t c = col_of ? col_of[j] : j;
+      if (c < 0) {
+        dst[j] = __builtin_nan("");
+        continue;
+      }
+      double v = src[c];
+      if (stdv) v = v * stdv[c];
+      if (mean) v = v + mean[c];
+      dst[j] = v;
+    }
+  }
+}
+
+// 2-D grid of the two kernels above: columns in blocks of EW_BLOCK (at most 64 blocks), rows over y (at most 4096 at a time)
+static inline dim3 row_col_grid(int64_t rows, int64_t cols) {
+  int64_t bx = (cols + EW_BLOCK - 1) / EW_BLOCK;
+  if (bx > 64) bx = 64;
+  if (bx < 1) bx = 1;
+  int64_t by = rows < 4096 ? rows : 4096;
+  if (by < 1) by = 1;
+  return dim3((unsigned)bx, (unsigned)by);
+}
+
 // out[t][:] = in[idx[t]][:]   (row resampling of a rows x cols matrix)
 template <typename T>
 __global__ void gather_rows_kernel(const T* __restrict__ in, T* __restrict__ out, const int64_t* __restrict__ idx, int rows,

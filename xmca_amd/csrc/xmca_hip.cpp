@@ -319,15 +319,35 @@ void project_impl(xmca_handle* h, int side, const void* V, int64_t N, int64_t m,
   }
   const bool analytic = !f.has_im && h->op_pending;            // imaginary plane implicit: X~ = X + i Ht X
   const bool f_cplx = f.has_im || analytic, cplx = f_cplx || v_cplx;
-  // V -> planes in the field's element type (N x m, ld = m)
+  // V -> planes in the field's element type (N x m, ld = m): from the host, or (V == NULL) the first m resident vectors of the last
+  // solve transposed on the device - the same values as fetched, widened to float64 and uploaded again
   const size_t nv = (size_t)N * m;
   DevBuf<double> vh;
-  DevBuf<TI> vr, vi;
-  XMCA_HIP(hipMemcpyAsync(vh.ensure(nv * (v_cplx ? 2 : 1)), V, sizeof(double) * nv * (v_cplx ? 2 : 1), hipMemcpyHostToDevice, h->st));
-  if (v_cplx)
-    hipLaunchKernelGGL((split_complex_kernel<double, TI>), ew_grid((int64_t)nv), dim3(EW_BLOCK), 0, h->st, vh.get(), vr.ensure(nv), vi.ensure(nv), (int64_t)nv);
-  else
-    hipLaunchKernelGGL((convert_kernel<double, TI>), ew_grid((int64_t)nv), dim3(EW_BLOCK), 0, h->st, vh.get(), vr.ensure(nv), (int64_t)nv);
+  DevBuf<TI> vr, vi, vt;
+  if (V) {
+    XMCA_HIP(hipMemcpyAsync(vh.ensure(nv * (v_cplx ? 2 : 1)), V, sizeof(double) * nv * (v_cplx ? 2 : 1), hipMemcpyHostToDevice, h->st));
+    if (v_cplx)
+      hipLaunchKernelGGL((split_complex_kernel<double, TI>), ew_grid((int64_t)nv), dim3(EW_BLOCK), 0, h->st, vh.get(), vr.ensure(nv), vi.ensure(nv), (int64_t)nv);
+    else
+      hipLaunchKernelGGL((convert_kernel<double, TI>), ew_grid((int64_t)nv), dim3(EW_BLOCK), 0, h->st, vh.get(), vr.ensure(nv), (int64_t)nv);
+  } else {
+    const SolveResult& r = h->res;
+    v_cplx = r.cplx;
+    const dim3 grid((unsigned)ceil_div(N, 32), (unsigned)ceil_div(m, 32));
+    if (r.vt_f32[side]) {
+      hipLaunchKernelGGL((eof_transpose_kernel<float, TI>), grid, dim3(256), 0, h->st, r.Vt32[side].get(), (const float*)nullptr, r.ldv[side], N,
+                         (int)m, vr.ensure(nv));
+    } else if (!v_cplx) {
+      hipLaunchKernelGGL((eof_transpose_kernel<double, TI>), grid, dim3(256), 0, h->st, r.Vt[side].r(), (const double*)nullptr, r.ldv[side], N,
+                         (int)m, vr.ensure(nv));
+    } else {
+      hipLaunchKernelGGL((eof_transpose_kernel<double, TI>), grid, dim3(256), 0, h->st, r.Vt[side].r(), r.Vt[side].i(true), r.ldv[side], N,
+                         (int)m, vt.ensure(2 * nv));
+      XMCA_HIP(hipGetLastError());
+      hipLaunchKernelGGL((split_complex_kernel<TI, TI>), ew_grid((int64_t)nv), dim3(EW_BLOCK), 0, h->st, vt.get(), vr.ensure(nv), vi.ensure(nv),
+                         (int64_t)nv);
+    }
+  }
   XMCA_HIP(hipGetLastError());
   h->tm.begin("project");
   DevBuf<double> wr, wi, ur, ui;
@@ -380,6 +400,214 @@ void project_impl(xmca_handle* h, int side, const void* V, int64_t N, int64_t m,
   XMCA_HIP(hipMemcpyAsync(U_out, packed.get(), sizeof(double) * n_out, hipMemcpyDeviceToHost, h->st));
   XMCA_HIP(hipStreamSynchronize(h->st));
   *out_cplx = cplx ? 1 : 0;
+}
+
+// ---- forward / inverse transform of new data (xmca_predict, xmca_reconstruct) -------------------------------------------------
+// Rows of new data (predict) or of a reconstruction (reconstruct) are processed in blocks of at most this many bytes of T x N
+// data, so that neither a long new record nor a long reconstruction has to be resident at once.
+constexpr int64_t TRANSFORM_BLOCK_BYTES = (int64_t)128 << 20;
+
+int64_t transform_rows(int64_t T, int64_t row_bytes) {
+  const int64_t rows = TRANSFORM_BLOCK_BYTES / std::max<int64_t>(row_bytes, 1);
+  return std::max<int64_t>(1, std::min<int64_t>(T, rows));
+}
+
+// The m leading vectors of `side` as one operand of a product over grid points, in the product's element type TP: the resident
+// mode-major planes of the last solve (V == NULL; element (n, j) at j * ld + n) or a host N x m array uploaded as float64 planes
+// (element (n, j) at n * m + j).
+template <typename TP>
+struct VecOperand {
+  const TP* r = nullptr;
+  const TP* i = nullptr;        // nullptr: real vectors
+  int64_t ld = 0;
+  bool mode_major = true;
+  DevBuf<TP> hr, hi;
+};
+
+template <typename TP>
+void vec_operand(xmca_handle* h, int side, const void* V, int64_t N, int64_t m, bool v_cplx, VecOperand<TP>& op) {
+  if (!V) {
+    const SolveResult& r = h->res;
+    op.mode_major = true;
+    op.ld = r.ldv[side];
+    if constexpr (std::is_same<TP, float>::value) {
+      XMCA_CHECK(r.vt_f32[side], XMCA_ERR_STATE, "transform: the resident vectors are not float32");
+      op.r = r.Vt32[side].get();
+    } else {
+      XMCA_CHECK(!r.vt_f32[side], XMCA_ERR_STATE, "transform: the resident vectors are float32");
+      op.r = r.Vt[side].r();
+      op.i = r.Vt[side].i(r.cplx);
+    }
+    return;
+  }
+  const size_t nv = (size_t)N * m;
+  op.mode_major = false;
+  op.ld = m;
+  DevBuf<double> vh;
+  XMCA_HIP(hipMemcpyAsync(vh.ensure(nv * (v_cplx ? 2 : 1)), V, sizeof(double) * nv * (v_cplx ? 2 : 1), hipMemcpyHostToDevice, h->st));
+  if (v_cplx)
+    hipLaunchKernelGGL((split_complex_kernel<double, TP>), ew_grid((int64_t)nv), dim3(EW_BLOCK), 0, h->st, vh.get(), op.hr.ensure(nv),
+                       op.hi.ensure(nv), (int64_t)nv);
+  else
+    hipLaunchKernelGGL((convert_kernel<double, TP>), ew_grid((int64_t)nv), dim3(EW_BLOCK), 0, h->st, vh.get(), op.hr.ensure(nv), (int64_t)nv);
+  XMCA_HIP(hipGetLastError());
+  XMCA_HIP(hipStreamSynchronize(h->st));        // (vh goes back to the pool)
+  op.r = op.hr.get();
+  op.i = v_cplx ? op.hi.get() : nullptr;
+}
+
+// out (T_new x q) = (((X[:, keep] - mean) / std) V[:, :m]) W   (see xmca_predict).  TI: element type of the data (ingest
+// arithmetic), TP: element type of the vectors (product).
+template <typename TI, typename TP>
+void predict_impl(xmca_handle* h, int side, const TI* X, int64_t T, int64_t N_full, const int64_t* keep_idx, int64_t N, const TI* mean,
+                  const TI* stdv, const void* V, bool v_cplx, const double* W, int64_t m, int64_t q, bool w_cplx, double* out,
+                  int* out_cplx) {
+  VecOperand<TP> vo;
+  vec_operand<TP>(h, side, V, N, m, v_cplx, vo);
+  const bool vc = vo.i != nullptr, oc = vc || w_cplx;
+  DevBuf<int64_t> idx;
+  DevBuf<TI> mu, sd;
+  DevBuf<double> wh, wr, wi;
+  if (keep_idx) XMCA_HIP(hipMemcpyAsync(idx.ensure((size_t)N), keep_idx, sizeof(int64_t) * N, hipMemcpyHostToDevice, h->st));
+  XMCA_HIP(hipMemcpyAsync(mu.ensure((size_t)N), mean, sizeof(TI) * N, hipMemcpyHostToDevice, h->st));
+  if (stdv) XMCA_HIP(hipMemcpyAsync(sd.ensure((size_t)N), stdv, sizeof(TI) * N, hipMemcpyHostToDevice, h->st));
+  const size_t nw = (size_t)m * q;
+  XMCA_HIP(hipMemcpyAsync(wh.ensure(nw * (w_cplx ? 2 : 1)), W, sizeof(double) * nw * (w_cplx ? 2 : 1), hipMemcpyHostToDevice, h->st));
+  if (w_cplx) {
+    hipLaunchKernelGGL((split_complex_kernel<double, double>), ew_grid((int64_t)nw), dim3(EW_BLOCK), 0, h->st, wh.get(), wr.ensure(nw),
+                       wi.ensure(nw), (int64_t)nw);
+    XMCA_HIP(hipGetLastError());
+  }
+  const double* Wr = w_cplx ? wr.get() : wh.get();
+  const double* Wi = w_cplx ? wi.get() : nullptr;
+  const int64_t rows = transform_rows(T, N_full * (int64_t)sizeof(TI) + N * (int64_t)sizeof(TP));
+  DevBuf<TI> raw;
+  DevBuf<TP> xs;
+  DevBuf<double> yr, yi, o_r, o_i, packed;
+  raw.ensure((size_t)rows * N_full);
+  xs.ensure((size_t)rows * N);
+  yr.ensure((size_t)rows * m);
+  if (vc) yi.ensure((size_t)rows * m);
+  o_r.ensure((size_t)rows * q);
+  if (oc) { o_i.ensure((size_t)rows * q); packed.ensure((size_t)rows * q * 2); }
+  for (int64_t t0 = 0; t0 < T; t0 += rows) {
+    const int tb = (int)std::min<int64_t>(rows, T - t0);
+    XMCA_HIP(hipMemcpyAsync(raw.get(), X + t0 * N_full, sizeof(TI) * tb * N_full, hipMemcpyHostToDevice, h->st));
+    h->tm.begin("predict_ingest");
+    hipLaunchKernelGGL((ingest_columns_kernel<TI, TP>), row_col_grid(tb, N), dim3(EW_BLOCK), 0, h->st, raw.get(), N_full,
+                       keep_idx ? idx.get() : nullptr, tb, N, mu.get(), stdv ? sd.get() : nullptr, xs.get());
+    XMCA_HIP(hipGetLastError());
+    h->tm.end();
+    h->tm.begin("predict_gemm");
+    // Y = x V (tb x m): A = the ingested block, B(n, j) = V[:, j] at grid point n
+    GemmOpts o;
+    o.b_nfast = !vo.mode_major;
+    gemm<TP, double>(h->st, h->gws, xs.get(), N, vo.r, vo.ld, yr.get(), m, tb, (int)m, (int)N, o);
+    if (vc) gemm<TP, double>(h->st, h->gws, xs.get(), N, vo.i, vo.ld, yi.get(), m, tb, (int)m, (int)N, o);
+    // out = Y W (tb x q, K = m):  Or = Yr Wr - Yi Wi,  Oi = Yr Wi + Yi Wr
+    GemmOpts w;
+    gemm<double, double>(h->st, h->gws, yr.get(), m, Wr, q, o_r.get(), q, tb, (int)q, (int)m, w);
+    if (oc) {
+      if (Wi) gemm<double, double>(h->st, h->gws, yr.get(), m, Wi, q, o_i.get(), q, tb, (int)q, (int)m, w);
+      else XMCA_HIP(hipMemsetAsync(o_i.get(), 0, sizeof(double) * tb * q, h->st));
+      if (vc) {
+        GemmOpts acc;
+        acc.beta = 1.0;
+        gemm<double, double>(h->st, h->gws, yi.get(), m, Wr, q, o_i.get(), q, tb, (int)q, (int)m, acc);
+        if (Wi) {
+          acc.alpha = -1.0;
+          gemm<double, double>(h->st, h->gws, yi.get(), m, Wi, q, o_r.get(), q, tb, (int)q, (int)m, acc);
+        }
+      }
+    }
+    h->tm.end();
+    if (oc) {
+      hipLaunchKernelGGL((pack_rows_kernel<double>), ew_grid((int64_t)tb * q), dim3(EW_BLOCK), 0, h->st, o_r.get(), o_i.get(), q, tb, (int)q,
+                         packed.get(), 0);
+      XMCA_HIP(hipGetLastError());
+      XMCA_HIP(hipMemcpyAsync(out + 2 * t0 * q, packed.get(), sizeof(double) * 2 * tb * q, hipMemcpyDeviceToHost, h->st));
+    } else {
+      XMCA_HIP(hipMemcpyAsync(out + t0 * q, o_r.get(), sizeof(double) * tb * q, hipMemcpyDeviceToHost, h->st));
+    }
+    XMCA_HIP(hipStreamSynchronize(h->st));      // (the pageable source / destination of the next block)
+  }
+  *out_cplx = oc ? 1 : 0;
+}
+
+// out (T x N_full, float64) = Re(B V[:, :m]^H) * std + mean, NaN at the masked columns  (see xmca_reconstruct).  TP: element type of
+// the vectors (product).
+template <typename TP>
+void reconstruct_impl(xmca_handle* h, int side, const double* B, int64_t T, int64_t m, bool b_cplx, const void* V, bool v_cplx,
+                      const int64_t* keep_idx, int64_t N, int64_t N_full, const double* mean, const double* stdv, double* out) {
+  VecOperand<TP> vo;
+  if (m > 0) vec_operand<TP>(h, side, V, N, m, v_cplx, vo);
+  const bool both_cplx = b_cplx && vo.i != nullptr;        // Re((Br + i Bi)(Vr - i Vi)^T) = Br Vr^T + Bi Vi^T
+  DevBuf<int64_t> col_of;
+  DevBuf<double> mu, sd, bh, br, bi;
+  if (keep_idx) {
+    std::vector<int64_t> inv((size_t)N_full, -1);
+    for (int64_t c = 0; c < N; ++c) inv[(size_t)keep_idx[c]] = c;
+    XMCA_HIP(hipMemcpyAsync(col_of.ensure((size_t)N_full), inv.data(), sizeof(int64_t) * N_full, hipMemcpyHostToDevice, h->st));
+    XMCA_HIP(hipStreamSynchronize(h->st));      // (inv is a host temporary)
+  }
+  if (mean) XMCA_HIP(hipMemcpyAsync(mu.ensure((size_t)N), mean, sizeof(double) * N, hipMemcpyHostToDevice, h->st));
+  if (stdv) XMCA_HIP(hipMemcpyAsync(sd.ensure((size_t)N), stdv, sizeof(double) * N, hipMemcpyHostToDevice, h->st));
+  const size_t nb = (size_t)T * m;
+  DevBuf<TP> bpr, bpi;           // B in the product's element type
+  if (m > 0) {
+    XMCA_HIP(hipMemcpyAsync(bh.ensure(nb * (b_cplx ? 2 : 1)), B, sizeof(double) * nb * (b_cplx ? 2 : 1), hipMemcpyHostToDevice, h->st));
+    if (b_cplx)
+      hipLaunchKernelGGL((split_complex_kernel<double, TP>), ew_grid((int64_t)nb), dim3(EW_BLOCK), 0, h->st, bh.get(), bpr.ensure(nb),
+                         bpi.ensure(nb), (int64_t)nb);
+    else
+      hipLaunchKernelGGL((convert_kernel<double, TP>), ew_grid((int64_t)nb), dim3(EW_BLOCK), 0, h->st, bh.get(), bpr.ensure(nb), (int64_t)nb);
+    XMCA_HIP(hipGetLastError());
+  }
+  const int64_t rows = transform_rows(T, (N + N_full) * (int64_t)sizeof(double));
+  DevBuf<double> C, full;
+  C.ensure((size_t)rows * N);
+  full.ensure((size_t)rows * N_full);
+  for (int64_t t0 = 0; t0 < T; t0 += rows) {
+    const int tb = (int)std::min<int64_t>(rows, T - t0);
+    h->tm.begin("reconstruct_gemm");
+    if (m == 0) {
+      XMCA_HIP(hipMemsetAsync(C.get(), 0, sizeof(double) * tb * N, h->st));
+    } else {
+      // C = B V^T (tb x N, K = m): A = the rows of B, B(j, n) = V[n, j]
+      GemmOpts o;
+      o.b_nfast = vo.mode_major;
+      gemm<TP, double>(h->st, h->gws, bpr.get() + t0 * m, m, vo.r, vo.ld, C.get(), N, tb, (int)N, (int)m, o);
+      if (both_cplx) {
+        o.beta = 1.0;
+        gemm<TP, double>(h->st, h->gws, bpi.get() + t0 * m, m, vo.i, vo.ld, C.get(), N, tb, (int)N, (int)m, o);
+      }
+    }
+    h->tm.end();
+    h->tm.begin("reconstruct_epilogue");
+    hipLaunchKernelGGL(reconstruct_epilogue_kernel, row_col_grid(tb, N_full), dim3(EW_BLOCK), 0, h->st, C.get(), N,
+                       keep_idx ? col_of.get() : nullptr, tb, N_full, stdv ? sd.get() : nullptr, mean ? mu.get() : nullptr, full.get());
+    XMCA_HIP(hipGetLastError());
+    h->tm.end();
+    XMCA_HIP(hipMemcpyAsync(out + t0 * N_full, full.get(), sizeof(double) * tb * N_full, hipMemcpyDeviceToHost, h->st));
+    XMCA_HIP(hipStreamSynchronize(h->st));
+  }
+}
+
+// checks shared by xmca_predict / xmca_reconstruct: the vectors (resident or host), the kept columns
+void check_transform(xmca_handle* h, const char* what, int side, const void* V, int64_t m, const int64_t* keep_idx, int64_t N_keep,
+                     int64_t N_full) {
+  const std::string w(what);
+  XMCA_CHECK(side == 0 || side == 1, XMCA_ERR_INVALID, w + ": side must be 0 or 1");
+  XMCA_CHECK(N_keep >= 1 && N_full >= N_keep && m >= 0 && m <= INT32_MAX && N_full <= INT32_MAX, XMCA_ERR_INVALID, w + ": bad sizes");
+  XMCA_CHECK(keep_idx || N_keep == N_full, XMCA_ERR_INVALID, w + ": all columns are kept without keep_idx");
+  if (keep_idx) {
+    for (int64_t c = 0; c < N_keep; ++c)
+      XMCA_CHECK(keep_idx[c] >= 0 && keep_idx[c] < N_full && (c == 0 || keep_idx[c] > keep_idx[c - 1]), XMCA_ERR_INVALID,
+                 w + ": keep_idx must be increasing column indices below N_full");
+  }
+  if (!V && m > 0)
+    XMCA_CHECK(h->solved && m <= h->res.n_vec && h->res.ldv[side] == N_keep, XMCA_ERR_INVALID,
+               w + ": the resident vectors of the last solve do not have N_keep rows and m modes");
 }
 
 // r = corr(Re field columns, Y columns)  (see xmca_correlate)
@@ -1019,9 +1247,50 @@ int xmca_project(xmca_handle* h, int side, const void* V, int64_t N, int64_t m, 
   API_BEGIN(h)
   XMCA_CHECK(side == 0 || side == 1, XMCA_ERR_INVALID, "project: side must be 0 or 1");
   XMCA_CHECK(h->field_set[side], XMCA_ERR_STATE, "project: no field resident for this side");
-  XMCA_CHECK(V && U_out && out_is_complex && N >= 1 && m >= 1, XMCA_ERR_INVALID, "project: need an N x m matrix of vectors");
+  XMCA_CHECK(U_out && out_is_complex && N >= 1 && m >= 1, XMCA_ERR_INVALID, "project: need an N x m matrix of vectors");
+  if (!V)
+    XMCA_CHECK(h->solved && m <= h->res.n_vec && h->res.ldv[side] == N, XMCA_ERR_INVALID,
+               "project: the resident vectors of the last solve do not have N rows and m modes");
   if (h->dtype == XMCA_F32) project_impl<float>(h, side, V, N, m, is_complex != 0, U_out, out_is_complex);
   else project_impl<double>(h, side, V, N, m, is_complex != 0, U_out, out_is_complex);
+  API_END(h)
+}
+
+int xmca_predict(xmca_handle* h, int side, const void* X, int64_t T_new, int64_t N_full, int dtype, const int64_t* keep_idx,
+                 int64_t N_keep, const void* mean, const void* std, const void* V, int v_is_complex, const double* W, int64_t m,
+                 int64_t q, int w_is_complex, double* out, int* out_is_complex) {
+  API_BEGIN(h)
+  check_transform(h, "predict", side, V, m, keep_idx, N_keep, N_full);
+  XMCA_CHECK(X && mean && W && out && out_is_complex && T_new >= 1 && m >= 1 && q >= 1 && q <= INT32_MAX, XMCA_ERR_INVALID,
+             "predict: need new data, means, an m x q mix (m, q >= 1) and an output");
+  XMCA_CHECK(dtype == XMCA_F32 || dtype == XMCA_F64, XMCA_ERR_INVALID, "predict: dtype must be XMCA_F32 or XMCA_F64");
+  const bool vt32 = !V && h->res.vt_f32[side];
+  const bool vc = v_is_complex != 0, wc = w_is_complex != 0;
+  if (dtype == XMCA_F32) {
+    const float* x = static_cast<const float*>(X);
+    const float* mu = static_cast<const float*>(mean);
+    const float* sd = static_cast<const float*>(std);
+    if (vt32) predict_impl<float, float>(h, side, x, T_new, N_full, keep_idx, N_keep, mu, sd, V, vc, W, m, q, wc, out, out_is_complex);
+    else predict_impl<float, double>(h, side, x, T_new, N_full, keep_idx, N_keep, mu, sd, V, vc, W, m, q, wc, out, out_is_complex);
+  } else {
+    const double* x = static_cast<const double*>(X);
+    const double* mu = static_cast<const double*>(mean);
+    const double* sd = static_cast<const double*>(std);
+    if (vt32) predict_impl<double, float>(h, side, x, T_new, N_full, keep_idx, N_keep, mu, sd, V, vc, W, m, q, wc, out, out_is_complex);
+    else predict_impl<double, double>(h, side, x, T_new, N_full, keep_idx, N_keep, mu, sd, V, vc, W, m, q, wc, out, out_is_complex);
+  }
+  API_END(h)
+}
+
+int xmca_reconstruct(xmca_handle* h, int side, const double* B, int64_t T, int64_t m, int b_is_complex, const void* V, int v_is_complex,
+                     const int64_t* keep_idx, int64_t N_keep, int64_t N_full, const double* mean, const double* std, double* out) {
+  API_BEGIN(h)
+  check_transform(h, "reconstruct", side, V, m, keep_idx, N_keep, N_full);
+  XMCA_CHECK(out && T >= 1 && (B || m == 0), XMCA_ERR_INVALID, "reconstruct: need a T x m coefficient matrix and an output");
+  if (m > 0 && !V && h->res.vt_f32[side])
+    reconstruct_impl<float>(h, side, B, T, m, b_is_complex != 0, V, v_is_complex != 0, keep_idx, N_keep, N_full, mean, std, out);
+  else
+    reconstruct_impl<double>(h, side, B, T, m, b_is_complex != 0, V, v_is_complex != 0, keep_idx, N_keep, N_full, mean, std, out);
   API_END(h)
 }
 
