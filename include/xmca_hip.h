@@ -41,7 +41,7 @@ typedef struct xmca_handle xmca_handle;
 /* library / device management ------------------------------------------------------------------------- */
 const char* xmca_version(void);
 /* Number of this header's ABI (XMCA_ABI_VERSION): the binding refuses a library built from another revision. */
-#define XMCA_ABI_VERSION 11
+#define XMCA_ABI_VERSION 12
 int xmca_abi_version(void);
 int xmca_device_count(void);
 int xmca_create(int device, xmca_handle** out);
@@ -166,21 +166,16 @@ int xmca_get_field(xmca_handle* h, int side, void* out);
 
 /* MCA.bootstrapping (xmca/array.py:1813-1952): replicates on the device.
  * xmca_bootstrap_begin copies the real planes of the fields set with xmca_set_field (the caller's X_surr,
- * array.py:1925-1933) into working buffers.  Each xmca_bootstrap_run then
- *   resamples them along time, X <- X[idx, :] - cumulatively, like the reference's loop, which overwrites X_surr
- *   (idx_left / idx_right: T row indices drawn by the caller exactly as tools/array.py:91-138 does, or NULL when that
- *   side is not resampled),
- *   centers a copy (the MCA constructor, array.py:117), complexifies when hilbert_col != NULL, solves, rotates
- *   (rotated != 0: n_rot = p, power, tol) and returns the variance spectrum of `_get_variance` (array.py:755-779):
- *   `rank` singular values, or the p sorted norm products of the rotated model; *kept_out = 0 when Varimax failed. */
+ * array.py:1925-1933) into working buffers; they stay as they are until the next xmca_bootstrap_begin. */
 int xmca_bootstrap_begin(xmca_handle* h, int n_fields);
-int xmca_bootstrap_run(xmca_handle* h, const double* hilbert_col, const int64_t* idx_left, const int64_t* idx_right, int rotated,
-                       int p, int power, double tol, double* spectrum_out, int* kept_out, int64_t n_out);
 /* All replicates of one bootstrap in one call.  idx_left / idx_right: n_runs x T row indices INTO THE FIELDS AS THEY WERE AT
- * xmca_bootstrap_begin - the caller composes the reference's cumulative resampling, c_r = c_{r-1}[idx_r] (idx_r drawn exactly
- * as tools/array.py:91-138 does) - or NULL for a side that is not resampled.  The replicates are then independent on the
- * device and several are kept in flight (lanes, as in xmca_rule_n).  spectra_out: n_runs x n_out, kept_out: n_runs.
- * Does not touch the cumulative state of xmca_bootstrap_run. */
+ * xmca_bootstrap_begin - the caller composes the reference's cumulative resampling X <- X[idx_r, :] (its loop overwrites
+ * X_surr), c_r = c_{r-1}[idx_r] with idx_r drawn exactly as tools/array.py:91-138 does - or NULL for a side that is not
+ * resampled.  The replicates are then independent on the device and several are kept in flight (lanes, as in xmca_rule_n).
+ * Replicate r gathers the rows c_r of the working buffers, centers them (the MCA constructor, array.py:117), complexifies when
+ * hilbert_col != NULL, solves, rotates (rotated != 0: n_rot = p, power, tol) and contributes the variance spectrum of
+ * `_get_variance` (array.py:755-779): n_out = `rank` singular values, or the p sorted norm products of the rotated model.
+ * spectra_out: n_runs x n_out; kept_out: n_runs, 0 where Varimax failed. */
 int xmca_bootstrap_runs(xmca_handle* h, const double* hilbert_col, const int64_t* idx_left, const int64_t* idx_right, int64_t n_runs,
                         int rotated, int p, int power, double tol, double* spectra_out, int* kept_out, int64_t n_out);
 /* xmca_bootstrap_runs of a model solved with extend='exp' (ABI 10): every replicate is complexified with the operator G of

@@ -44,7 +44,6 @@ SIGNATURES = {
     "xmca_scale_field": (_c_int, [_vp, _c_int, _vp, _c_int]),
     "xmca_get_field": (_c_int, [_vp, _c_int, _vp]),
     "xmca_bootstrap_begin": (_c_int, [_vp, _c_int]),
-    "xmca_bootstrap_run": (_c_int, [_vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_dbl, _vp, ctypes.POINTER(_c_int), _c_i64]),
     "xmca_bootstrap_runs": (_c_int, [_vp, _vp, _vp, _vp, _c_i64, _c_int, _c_int, _c_int, _c_dbl, _vp, _vp, _c_i64]),
     "xmca_bootstrap_runs_extended": (_c_int, [_vp, _vp, _vp, _vp, _vp, _c_int, _vp, _vp, _c_i64, _c_int, _c_int, _c_int, _c_dbl, _vp, _vp,
                                               _c_i64]),
@@ -93,7 +92,7 @@ def library_path():
     return _build.LIB
 
 
-ABI_VERSION = 11         # bumped whenever a signature of include/xmca_hip.h changes; checked against xmca_abi_version()
+ABI_VERSION = 12         # bumped whenever a signature of include/xmca_hip.h changes; checked against xmca_abi_version()
 
 
 def load_library():
@@ -154,6 +153,30 @@ def _np_dtype_code(dt):
     if dt in (np.float64, np.complex128):
         return XMCA_F64
     raise TypeError("unsupported dtype %s (float32 / float64 / complex64 / complex128 only)" % dt)
+
+
+def _real_np(code):
+    return np.float32 if code == XMCA_F32 else np.float64
+
+
+def _cplx_np(code):
+    return np.complex64 if code == XMCA_F32 else np.complex128
+
+
+def _host_vectors(V):
+    """A maybe-complex host array as contiguous float64 / complex128 -> (array or None, is complex)."""
+    if V is None:
+        return None, False
+    V = np.asarray(V)
+    cplx = np.iscomplexobj(V)
+    return np.ascontiguousarray(V, dtype=np.complex128 if cplx else np.float64), cplx
+
+
+def _unpack(out, rows, cols, is_complex):
+    """The (rows, cols) result written into the complex128 buffer `out`: as it is, or its leading float64 values."""
+    if is_complex:
+        return out
+    return out.view(np.float64).reshape(-1)[:rows * cols].reshape(rows, cols).copy()
 
 
 def hilbert_imag_column(T):
@@ -298,7 +321,7 @@ class Handle:
             re = np.ascontiguousarray(field)
             im = None
         self._check(self._lib.xmca_set_field(self._h, side, _ptr(re), _ptr(im), T, N, code, HOST))
-        self.field_dtype = np.dtype(np.float32 if code == XMCA_F32 else np.float64)
+        self.field_dtype = np.dtype(_real_np(code))
 
     def set_field_device(self, side, re_ptr, im_ptr, T, N, dtype):
         """Adopt device pointers (e.g. torch tensors' data_ptr()); the caller keeps them alive."""
@@ -306,7 +329,7 @@ class Handle:
         self.fields_owner = None
         self._check(self._lib.xmca_set_field(self._h, side, _vp(re_ptr), _vp(im_ptr) if im_ptr else None, T, N,
                                              _np_dtype_code(dtype), DEVICE))
-        self.field_dtype = np.dtype(np.float32 if _np_dtype_code(dtype) == XMCA_F32 else np.float64)
+        self.field_dtype = np.dtype(_real_np(_np_dtype_code(dtype)))
 
     def complexify(self, T):
         self.release_result()
@@ -348,11 +371,7 @@ class Handle:
         """Returns Vt (n_modes x N); V = Vt.T."""
         cplx = bool(self._lib.xmca_is_complex(self._h))
         code = _np_dtype_code(dtype)
-        base = np.float32 if code == XMCA_F32 else np.float64
-        if cplx:
-            out = np.empty((n_modes, N), dtype=np.complex64 if code == XMCA_F32 else np.complex128)
-        else:
-            out = np.empty((n_modes, N), dtype=base)
+        out = np.empty((n_modes, N), dtype=_cplx_np(code) if cplx else _real_np(code))
         self._check(self._lib.xmca_get_vectors(self._h, side, _ptr(out), n_modes, code))
         return out
 
@@ -361,16 +380,12 @@ class Handle:
         first m vectors as they are (W None).  xmca_get_eofs: array.py:615-646 + :676-721 without an N x m pass on the host."""
         cplx = bool(self._lib.xmca_is_complex(self._h))
         code = _np_dtype_code(dtype)
-        w_cplx = W is not None and np.iscomplexobj(W)
+        W, w_cplx = _host_vectors(W)
         if W is not None:
-            W = np.ascontiguousarray(W, dtype=np.complex128 if w_cplx else np.float64)
             m, q = W.shape
         else:
             q = m
-        if cplx or w_cplx:
-            out = np.empty((N, q), dtype=np.complex64 if code == XMCA_F32 else np.complex128)
-        else:
-            out = np.empty((N, q), dtype=np.float32 if code == XMCA_F32 else np.float64)
+        out = np.empty((N, q), dtype=_cplx_np(code) if cplx or w_cplx else _real_np(code))
         self._check(self._lib.xmca_get_eofs(self._h, side, _ptr(W), m, q, int(w_cplx), _ptr(out), code))
         return out
 
@@ -378,27 +393,13 @@ class Handle:
         """U = X~ V (T x m) on the resident field of `side` (the analytic signal when the model is complex);
         float64 / complex128.  MCA._get_U's `fields[k] @ V[k]` (array.py:391).  V None: the first m vectors of the last solve,
         still resident (N: their length)."""
-        if V is None:
-            Vd, cplx = None, False
-        else:
-            V = np.asarray(V)
-            cplx = np.iscomplexobj(V)
-            Vd = np.ascontiguousarray(V, dtype=np.complex128 if cplx else np.float64)
+        Vd, cplx = _host_vectors(V)
+        if Vd is not None:
             N, m = Vd.shape
         out = np.empty((T, m), dtype=np.complex128)          # large enough for either result type
         out_cplx = _c_int(0)
         self._check(self._lib.xmca_project(self._h, side, _ptr(Vd), N, m, int(cplx), _ptr(out), ctypes.byref(out_cplx)))
-        if out_cplx.value:
-            return out
-        return out.view(np.float64).reshape(-1)[:T * m].reshape(T, m).copy()
-
-    @staticmethod
-    def _host_vectors(V):
-        if V is None:
-            return None, False
-        V = np.asarray(V)
-        cplx = np.iscomplexobj(V)
-        return np.ascontiguousarray(V, dtype=np.complex128 if cplx else np.float64), cplx
+        return _unpack(out, T, m, out_cplx.value)
 
     def predict(self, side, X, keep_idx, mean, std, V, W):
         """((X[:, keep_idx] - mean) / std) V W (T' x q, float64 / complex128) on the device (xmca_predict): MCA.predict's product
@@ -414,9 +415,8 @@ class Handle:
         N = N_full if idx is None else idx.size
         mean = np.ascontiguousarray(np.broadcast_to(mean, (N,)), dtype=X.dtype)
         std = None if std is None else np.ascontiguousarray(np.broadcast_to(std, (N,)), dtype=X.dtype)
-        Vd, v_cplx = self._host_vectors(V)
-        w_cplx = np.iscomplexobj(W)
-        Wd = np.ascontiguousarray(W, dtype=np.complex128 if w_cplx else np.float64)
+        Vd, v_cplx = _host_vectors(V)
+        Wd, w_cplx = _host_vectors(W)
         m, q = Wd.shape
         if Vd is not None and Vd.shape != (N, m):
             raise ValueError("predict: V must be N' x m = %d x %d, got %s" % (N, m, Vd.shape))
@@ -424,19 +424,15 @@ class Handle:
         out_cplx = _c_int(0)
         self._check(self._lib.xmca_predict(self._h, side, _ptr(X), T, N_full, code, _ptr(idx), N, _ptr(mean), _ptr(std), _ptr(Vd),
                                            int(v_cplx), _ptr(Wd), m, q, int(w_cplx), _ptr(out), ctypes.byref(out_cplx)))
-        if out_cplx.value:
-            return out
-        return out.view(np.float64).reshape(-1)[:T * q].reshape(T, q).copy()
+        return _unpack(out, T, q, out_cplx.value)
 
     def reconstruct(self, side, B, V, N, keep_idx=None, N_full=None, mean=None, std=None):
         """Re(B V^H) (* std + mean) on the device (xmca_reconstruct), T x N_full float64 with NaN at the columns not in keep_idx.
         B: T x m coefficients; V: N x m host vectors or None (the first m resident ones of the last solve of `side`).  The
         resident fields and vectors stay as they are."""
-        B = np.asarray(B)
-        b_cplx = np.iscomplexobj(B)
-        Bd = np.ascontiguousarray(B, dtype=np.complex128 if b_cplx else np.float64)
+        Bd, b_cplx = _host_vectors(B)
         T, m = Bd.shape
-        Vd, v_cplx = self._host_vectors(V)
+        Vd, v_cplx = _host_vectors(V)
         if Vd is not None and Vd.shape != (N, m):
             raise ValueError("reconstruct: V must be N x m = %d x %d, got %s" % (N, m, Vd.shape))
         idx = None if keep_idx is None else np.ascontiguousarray(keep_idx, dtype=np.int64)
@@ -481,20 +477,9 @@ class Handle:
         return out.astype(dtype, copy=False)
 
     def bootstrap_begin(self, n_fields):
-        """Working copies of the resident fields for `bootstrap_run` (MCA.bootstrapping on the device)."""
+        """Working copies of the resident fields for `bootstrap_runs` (MCA.bootstrapping on the device)."""
         self.release_result()
         self._check(self._lib.xmca_bootstrap_begin(self._h, n_fields))
-
-    def bootstrap_run(self, T, complexify, idx_left, idx_right, rotated, p, power, tol, n_out):
-        """One replicate: resample rows (cumulatively), center, solve (+ rotate).  Returns (spectrum[n_out], kept)."""
-        ht = hilbert_imag_column(T) if complexify else None
-        il = None if idx_left is None else np.ascontiguousarray(idx_left, dtype=np.int64)
-        ir = None if idx_right is None else np.ascontiguousarray(idx_right, dtype=np.int64)
-        out = np.zeros(n_out, dtype=np.float64)
-        kept = _c_int(0)
-        self._check(self._lib.xmca_bootstrap_run(self._h, _ptr(ht), _ptr(il), _ptr(ir), int(rotated), int(p), int(power), float(tol),
-                                                 _ptr(out), ctypes.byref(kept), n_out))
-        return out, bool(kept.value)
 
     def bootstrap_runs(self, T, complexify, idx_left, idx_right, n_runs, rotated, p, power, tol, n_out, extend_period=None):
         """All replicates in one call (several in flight on the device).  idx_*: (n_runs, T) COMPOSED row indices into the
@@ -526,11 +511,9 @@ class Handle:
 
     # ---- rotation -----------------------------------------------------------------------------
     def rotate_loadings(self, L, n_left, power=1, tol=1e-8, max_iter=1000, varimax_only=False, want_B=False, gamma=1.0):
-        L = np.asarray(L)
-        cplx = np.iscomplexobj(L)
-        Ld = np.ascontiguousarray(L, dtype=np.complex128 if cplx else np.float64)
+        Ld, cplx = _host_vectors(L)
         N, p = Ld.shape
-        cdt = np.complex128 if cplx else np.float64
+        cdt = Ld.dtype
         R = np.empty((p, p), dtype=cdt)
         Phi = np.empty((p, p), dtype=cdt)
         nl = np.zeros(p)
@@ -658,9 +641,7 @@ class Handle:
 
     def eigh(self, A, vectors=True):
         """Returns (lam descending, U) with A = U diag(lam) U^H; `vectors=False`: (lam, None), eigenvalues only."""
-        A = np.asarray(A)
-        cplx = np.iscomplexobj(A)
-        Ad = np.ascontiguousarray(A, dtype=np.complex128 if cplx else np.float64)
+        Ad, cplx = _host_vectors(A)
         n = Ad.shape[0]
         lam = np.empty(n)
         Zh = np.empty((n, n), dtype=Ad.dtype) if vectors else None
@@ -672,9 +653,7 @@ class Handle:
 
     def cholesky(self, A, rel_shift=0.0):
         """Returns (R upper triangular with R^H R = A + rel_shift max(diag A) I, ok)."""
-        A = np.asarray(A)
-        cplx = np.iscomplexobj(A)
-        Ad = np.ascontiguousarray(A, dtype=np.complex128 if cplx else np.float64)
+        Ad, cplx = _host_vectors(A)
         n = Ad.shape[0]
         R = np.empty((n, n), dtype=Ad.dtype)
         ok = _c_int(0)

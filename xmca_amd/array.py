@@ -1163,7 +1163,7 @@ class MCA:
 
         The block indices are drawn on the host from numpy's global RNG exactly as the reference draws them
         (tools/array.py:91-138), the replicates themselves - cumulative row resampling, centering, solve, rotation,
-        variance - run on the device (`xmca_bootstrap_run`).  A model solved with extend='exp' runs there too, every replicate
+        variance - run on the device (`xmca_bootstrap_runs`).  A model solved with extend='exp' runs there too, every replicate
         complexified with the same extended operator in float64 (`xmca_bootstrap_runs_extended`).  Column resampling (`axis=1`)
         and extend='theta' keep the reference's host loop with one device solve per replicate.
         """

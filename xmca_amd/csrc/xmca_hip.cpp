@@ -40,6 +40,14 @@ struct ComplexOp {
   }
 };
 
+// What the handle holds in the fields' element type: the resident fields and the working copies of a bootstrap
+// (xmca_bootstrap_begin).  xmca_handle::dtype says which of the two instances is live.
+template <typename TI>
+struct TypedState {
+  FieldData<TI> f[2];
+  DevBuf<TI> boot[2];
+};
+
 struct xmca_handle {
   ::xmca::DevPool pool;                   // first member: destroyed after every buffer below has gone back to it
   int device = 0;
@@ -49,44 +57,39 @@ struct xmca_handle {
   GemmWorkspace gws;
   EvdWorkspace ews;
   StageTimer tm;
-  int dtype = -1;
-  FieldData<float> f32[2];
-  FieldData<double> f64[2];
+  int dtype = -1;                         // XMCA_F32 / XMCA_F64: the live one of s32 / s64
+  TypedState<float> s32;
+  TypedState<double> s64;
   bool field_set[2] = {false, false};
   SolveResult res;
   bool solved = false;
   bool op_pending = false;               // complexify requested; carried out (or folded into the solve) lazily
   ComplexOp op;                          // ... with this operator
   RotationDevice rot;
-  // bootstrapping (xmca_bootstrap_begin / _run): cumulative resampled copies of the fields, a gather target and the
-  // centered copies that are solved
-  DevBuf<float> boot32[2], boot32_tmp;
-  DevBuf<double> boot64[2], boot64_tmp;
   DevBuf<int> center_nan;          // scratch of center_columns
   DevBuf<double> center_sum;
-  FieldData<float> bootf32[2];
-  FieldData<double> bootf64[2];
-  int64_t boot_T = 0, boot_N[2] = {0, 0};
+  int64_t boot_T = 0, boot_N[2] = {0, 0};      // shape of the working copies of xmca_bootstrap_begin
   int boot_fields = 0;
 };
 
+// End of an entry point's try block: the error goes to `obj` (a handle or a communicator), its code is returned
+#define XMCA_CATCH(obj)                                                \
+  catch (const ::xmca::Error& e) {                                     \
+    (obj)->err = e.what();                                             \
+    (void)hipGetLastError();                                           \
+    return e.code;                                                     \
+  }                                                                    \
+  catch (const std::exception& e) {                                    \
+    (obj)->err = std::string("unexpected: ") + e.what();               \
+    return XMCA_ERR_HIP;                                               \
+  }                                                                    \
+  return XMCA_OK;
 #define API_BEGIN(h)                                                   \
   if (!(h)) return XMCA_ERR_INVALID;                                   \
   try {                                                                \
     ::xmca::PoolScope _pool_scope(&(h)->pool);                         \
     XMCA_HIP(hipSetDevice((h)->device));
-#define API_END(h)                                                     \
-  }                                                                    \
-  catch (const ::xmca::Error& e) {                                     \
-    (h)->err = e.what();                                               \
-    (void)hipGetLastError();                                           \
-    return e.code;                                                     \
-  }                                                                    \
-  catch (const std::exception& e) {                                    \
-    (h)->err = std::string("unexpected: ") + e.what();                 \
-    return XMCA_ERR_HIP;                                               \
-  }                                                                    \
-  return XMCA_OK;
+#define API_END(h) } XMCA_CATCH(h)
 
 extern "C" {
 
@@ -149,15 +152,97 @@ const char* xmca_last_error(xmca_handle* h) { return h ? h->err.c_str() : "null 
 namespace {
 
 template <typename TI>
-FieldData<TI>* fields_of(xmca_handle* h);
-template <>
-FieldData<float>* fields_of<float>(xmca_handle* h) { return h->f32; }
-template <>
-FieldData<double>* fields_of<double>(xmca_handle* h) { return h->f64; }
+TypedState<TI>& typed(xmca_handle* h) {
+  if constexpr (std::is_same<TI, float>::value) return h->s32;
+  else return h->s64;
+}
+
+// The one dtype dispatch: f(float{}) or f(double{}) for a run-time XMCA_F32 / XMCA_F64 code; the callee takes its element
+// type from the tag, with_dtype(code, [&](auto t) { foo<decltype(t)>(...); })
+template <typename F>
+void with_dtype(int code, F&& f) {
+  if (code == XMCA_F32) f(float{});
+  else f(double{});
+}
+
+// ---- argument checks shared by the entry points (`what`: the entry point's prefix of the message) ---------------------------
+void check_side(const char* what, int side) {
+  XMCA_CHECK(side == 0 || side == 1, XMCA_ERR_INVALID, std::string(what) + ": side must be 0 or 1");
+}
+
+// rotation of every replicate (xmca_rule_n, xmca_bootstrap_runs*); `detail`: the entry point's own wording of the requirement
+void check_rotation_args(const char* what, const char* detail, int rotated, int p, int power) {
+  XMCA_CHECK(!rotated || (p >= 2 && power >= 1), XMCA_ERR_INVALID, std::string(what) + ": " + detail);
+}
+
+// the parts of the extended operator (xmca_complexify_extended, xmca_bootstrap_runs_extended)
+void check_extended_parts(const char* what, const double* col3, const double* hbar, const double* U, const double* W, int rank) {
+  XMCA_CHECK(col3 && hbar && rank >= 0 && rank <= 16 && (rank == 0 || (U && W)), XMCA_ERR_INVALID,
+             std::string(what) + ": need col3, hbar and T x rank U, W (rank <= 16)");
+}
+
+// ... and the bound on the T of its T x T assembly (46340^2 < 2^31)
+void check_operator_size(const char* what, int64_t T) {
+  XMCA_CHECK(T <= 46340, XMCA_ERR_UNSUPPORTED, std::string(what) + ": T x T operator too large");
+}
+
+void check_bootstrap_runs(const double* spectra_out, const int* kept_out, int64_t n_out, int64_t n_runs, int rotated,
+                          int p, int power) {
+  XMCA_CHECK(spectra_out && kept_out && n_out >= 1 && n_runs >= 0, XMCA_ERR_INVALID, "bootstrap: output buffers missing");
+  check_rotation_args("bootstrap", "rotation needs n_rot >= 2 and power >= 1", rotated, p, power);
+}
+
+// ---- host arrays <-> device planes --------------------------------------------------------------------------------------------
+// A host float64 array of n elements, interleaved complex when `cplx`, as device planes r / i (nullptr: real) of TP.  It is
+// uploaded into `stage` and split (complex) or converted (real) from there; convert_real = false (TP = double only) uses a real
+// array where it was uploaded, without a pass.  `stage` must not go back to the pool before the stream has passed the split /
+// conversion: the caller keeps the struct alive that long or synchronises first.
+template <typename TP>
+struct HostPlanes {
+  DevBuf<double> stage;
+  DevBuf<TP> re, im;
+  const TP* r = nullptr;
+  const TP* i = nullptr;
+};
+
+template <typename TP>
+void upload_planes(xmca_handle* h, const double* host, size_t n, bool cplx, HostPlanes<TP>& p, bool convert_real = true) {
+  const size_t n_host = n * (cplx ? 2 : 1);
+  XMCA_HIP(hipMemcpyAsync(p.stage.ensure(n_host), host, sizeof(double) * n_host, hipMemcpyHostToDevice, h->st));
+  p.i = nullptr;
+  if (cplx) {
+    hipLaunchKernelGGL((split_complex_kernel<double, TP>), ew_grid((int64_t)n), dim3(EW_BLOCK), 0, h->st, p.stage.get(), p.re.ensure(n),
+                       p.im.ensure(n), (int64_t)n);
+    p.r = p.re.get();
+    p.i = p.im.get();
+  } else if (convert_real) {
+    hipLaunchKernelGGL((convert_kernel<double, TP>), ew_grid((int64_t)n), dim3(EW_BLOCK), 0, h->st, p.stage.get(), p.re.ensure(n), (int64_t)n);
+    p.r = p.re.get();
+  } else if constexpr (std::is_same<TP, double>::value) {
+    p.r = p.stage.get();
+  }
+  XMCA_HIP(hipGetLastError());
+}
+
+// rows x cols device planes (row stride ld; im == nullptr: real) -> host array of TO, interleaved when complex, through `packed`
+// (rows * cols * (im ? 2 : 1) elements).  The caller synchronises the stream before `packed` goes back to the pool.
+template <typename TO>
+void pack_download(xmca_handle* h, const double* re, const double* im, int64_t ld, int rows, int cols, TO* packed, void* host) {
+  hipLaunchKernelGGL((pack_rows_kernel<TO>), ew_grid((int64_t)rows * cols), dim3(EW_BLOCK), 0, h->st, re, im, ld, rows, cols, packed, 0);
+  XMCA_HIP(hipGetLastError());
+  XMCA_HIP(hipMemcpyAsync(host, packed, sizeof(TO) * (size_t)rows * cols * (im ? 2 : 1), hipMemcpyDeviceToHost, h->st));
+}
+
+// number of time steps of the resident fields
+int64_t resident_T(xmca_handle* h) {
+  int64_t T = 0;
+  with_dtype(h->dtype, [&](auto t) { T = typed<decltype(t)>(h).f[0].T; });
+  return T;
+}
 
 template <typename TI>
 void set_field_impl(xmca_handle* h, int side, const void* re, const void* im, int64_t T, int64_t N, int location) {
-  FieldData<TI>& f = fields_of<TI>(h)[side];
+  FieldData<TI>& f = typed<TI>(h).f[side];
   const size_t n = (size_t)T * N;
   f.T = T; f.N = N;
   f.has_im = im != nullptr;
@@ -206,7 +291,7 @@ void build_operator(xmca_handle* h, const ComplexOp& op, DevBuf<TI>& g) {
 
 template <typename TI>
 void complexify_impl(xmca_handle* h, const ComplexOp& op) {
-  FieldData<TI>* f = fields_of<TI>(h);
+  FieldData<TI>* f = typed<TI>(h).f;
   const int64_t T = f[0].T;
   XMCA_CHECK(op.T == T, XMCA_ERR_STATE, "complexify: the operator was made for another number of time steps");
   DevBuf<TI> htb;
@@ -227,7 +312,7 @@ void complexify_impl(xmca_handle* h, const ComplexOp& op) {
 
 template <typename TI>
 void solve_impl(xmca_handle* h, int n_fields, int64_t n_vec) {
-  FieldData<TI>* f = fields_of<TI>(h);
+  FieldData<TI>* f = typed<TI>(h).f;
   if (h->op_pending) {
     static const bool analytic_on = [] { const char* e = std::getenv("XMCA_ANALYTIC"); return !(e && e[0] == '0'); }();
     // the subspace formulation is exact for the Fourier-diagonal circulant operator only; the extended one is applied as a GEMM
@@ -266,11 +351,7 @@ void get_vectors_impl(xmca_handle* h, int side, void* out, int64_t m) {
     return;
   }
   DevBuf<TO> tmp;
-  tmp.ensure(n_out);
-  hipLaunchKernelGGL((pack_rows_kernel<TO>), ew_grid((int64_t)m * N), dim3(EW_BLOCK), 0, h->st, r.Vt[side].r(), r.Vt[side].i(cplx), N,
-                     (int)m, (int)N, tmp.get(), 0);
-  XMCA_HIP(hipGetLastError());
-  XMCA_HIP(hipMemcpyAsync(out, tmp.get(), n_out * sizeof(TO), hipMemcpyDeviceToHost, h->st));
+  pack_download<TO>(h, r.Vt[side].r(), r.Vt[side].i(cplx), N, (int)m, (int)N, tmp.ensure(n_out), out);
   XMCA_HIP(hipStreamSynchronize(h->st));
 }
 
@@ -283,18 +364,14 @@ void get_eofs_impl(xmca_handle* h, int side, const double* W, int64_t m, int64_t
   const size_t n_out = (size_t)N * q * (o_cplx ? 2 : 1);
   DevBuf<TO> tmp;
   tmp.ensure(n_out);
-  DevBuf<double> wr, wi, wh;
+  HostPlanes<double> w;
   if (W) {
-    const size_t nw = (size_t)m * q;
-    XMCA_HIP(hipMemcpyAsync(wh.ensure(nw * (w_cplx ? 2 : 1)), W, sizeof(double) * nw * (w_cplx ? 2 : 1), hipMemcpyHostToDevice, h->st));
-    if (w_cplx) hipLaunchKernelGGL((split_complex_kernel<double, double>), ew_grid((int64_t)nw), dim3(EW_BLOCK), 0, h->st, wh.get(), wr.ensure(nw), wi.ensure(nw), (int64_t)nw);
-    const double* Wr = w_cplx ? wr.get() : wh.get();
-    const double* Wi = w_cplx ? wi.get() : nullptr;
+    upload_planes<double>(h, W, (size_t)m * q, w_cplx, w, false);
     const dim3 grid((unsigned)ceil_div(N, 256));
     if (r.vt_f32[side])
-      hipLaunchKernelGGL((eof_mix_kernel<float, TO>), grid, dim3(256), 0, h->st, r.Vt32[side].get(), (const float*)nullptr, N, N, (int)m, (int)q, Wr, Wi, tmp.get());
+      hipLaunchKernelGGL((eof_mix_kernel<float, TO>), grid, dim3(256), 0, h->st, r.Vt32[side].get(), (const float*)nullptr, N, N, (int)m, (int)q, w.r, w.i, tmp.get());
     else
-      hipLaunchKernelGGL((eof_mix_kernel<double, TO>), grid, dim3(256), 0, h->st, r.Vt[side].r(), r.Vt[side].i(v_cplx), N, N, (int)m, (int)q, Wr, Wi, tmp.get());
+      hipLaunchKernelGGL((eof_mix_kernel<double, TO>), grid, dim3(256), 0, h->st, r.Vt[side].r(), r.Vt[side].i(v_cplx), N, N, (int)m, (int)q, w.r, w.i, tmp.get());
   } else {
     const dim3 grid((unsigned)ceil_div(N, 32), (unsigned)ceil_div(q, 32));
     if (r.vt_f32[side])
@@ -310,7 +387,7 @@ void get_eofs_impl(xmca_handle* h, int side, const double* W, int64_t m, int64_t
 // U = X~ V on the resident field of `side` (see xmca_project)
 template <typename TI>
 void project_impl(xmca_handle* h, int side, const void* V, int64_t N, int64_t m, bool v_cplx, void* U_out, int* out_cplx) {
-  FieldData<TI>& f = fields_of<TI>(h)[side];
+  FieldData<TI>& f = typed<TI>(h).f[side];
   XMCA_CHECK(f.N == N, XMCA_ERR_INVALID, "project: V has " + std::to_string(N) + " rows, the field has " + std::to_string(f.N) + " columns");
   const int64_t T = f.T;
   if (h->op_pending && h->op.kind == ComplexOp::EXTENDED) {     // no implicit form: the imaginary planes G X are formed first
@@ -322,14 +399,12 @@ void project_impl(xmca_handle* h, int side, const void* V, int64_t N, int64_t m,
   // V -> planes in the field's element type (N x m, ld = m): from the host, or (V == NULL) the first m resident vectors of the last
   // solve transposed on the device - the same values as fetched, widened to float64 and uploaded again
   const size_t nv = (size_t)N * m;
-  DevBuf<double> vh;
-  DevBuf<TI> vr, vi, vt;
+  HostPlanes<TI> vp;
+  DevBuf<TI>& vr = vp.re;        // (the resident branch fills the same planes)
+  DevBuf<TI>& vi = vp.im;
+  DevBuf<TI> vt;
   if (V) {
-    XMCA_HIP(hipMemcpyAsync(vh.ensure(nv * (v_cplx ? 2 : 1)), V, sizeof(double) * nv * (v_cplx ? 2 : 1), hipMemcpyHostToDevice, h->st));
-    if (v_cplx)
-      hipLaunchKernelGGL((split_complex_kernel<double, TI>), ew_grid((int64_t)nv), dim3(EW_BLOCK), 0, h->st, vh.get(), vr.ensure(nv), vi.ensure(nv), (int64_t)nv);
-    else
-      hipLaunchKernelGGL((convert_kernel<double, TI>), ew_grid((int64_t)nv), dim3(EW_BLOCK), 0, h->st, vh.get(), vr.ensure(nv), (int64_t)nv);
+    upload_planes<TI>(h, static_cast<const double*>(V), nv, v_cplx, vp);
   } else {
     const SolveResult& r = h->res;
     v_cplx = r.cplx;
@@ -393,11 +468,7 @@ void project_impl(xmca_handle* h, int side, const void* V, int64_t N, int64_t m,
   }
   h->tm.end();
   DevBuf<double> packed;
-  const size_t n_out = nu * (cplx ? 2 : 1);
-  hipLaunchKernelGGL((pack_rows_kernel<double>), ew_grid((int64_t)nu), dim3(EW_BLOCK), 0, h->st, out_r, out_i, m, (int)T, (int)m,
-                     packed.ensure(n_out), 0);
-  XMCA_HIP(hipGetLastError());
-  XMCA_HIP(hipMemcpyAsync(U_out, packed.get(), sizeof(double) * n_out, hipMemcpyDeviceToHost, h->st));
+  pack_download<double>(h, out_r, out_i, m, (int)T, (int)m, packed.ensure(nu * (cplx ? 2 : 1)), U_out);
   XMCA_HIP(hipStreamSynchronize(h->st));
   *out_cplx = cplx ? 1 : 0;
 }
@@ -421,7 +492,7 @@ struct VecOperand {
   const TP* i = nullptr;        // nullptr: real vectors
   int64_t ld = 0;
   bool mode_major = true;
-  DevBuf<TP> hr, hi;
+  HostPlanes<TP> host;
 };
 
 template <typename TP>
@@ -440,20 +511,13 @@ void vec_operand(xmca_handle* h, int side, const void* V, int64_t N, int64_t m, 
     }
     return;
   }
-  const size_t nv = (size_t)N * m;
   op.mode_major = false;
   op.ld = m;
-  DevBuf<double> vh;
-  XMCA_HIP(hipMemcpyAsync(vh.ensure(nv * (v_cplx ? 2 : 1)), V, sizeof(double) * nv * (v_cplx ? 2 : 1), hipMemcpyHostToDevice, h->st));
-  if (v_cplx)
-    hipLaunchKernelGGL((split_complex_kernel<double, TP>), ew_grid((int64_t)nv), dim3(EW_BLOCK), 0, h->st, vh.get(), op.hr.ensure(nv),
-                       op.hi.ensure(nv), (int64_t)nv);
-  else
-    hipLaunchKernelGGL((convert_kernel<double, TP>), ew_grid((int64_t)nv), dim3(EW_BLOCK), 0, h->st, vh.get(), op.hr.ensure(nv), (int64_t)nv);
-  XMCA_HIP(hipGetLastError());
-  XMCA_HIP(hipStreamSynchronize(h->st));        // (vh goes back to the pool)
-  op.r = op.hr.get();
-  op.i = v_cplx ? op.hi.get() : nullptr;
+  upload_planes<TP>(h, static_cast<const double*>(V), (size_t)N * m, v_cplx, op.host);
+  XMCA_HIP(hipStreamSynchronize(h->st));        // (the staging buffer goes back to the pool)
+  op.host.stage.release();
+  op.r = op.host.r;
+  op.i = op.host.i;
 }
 
 // out (T_new x q) = (((X[:, keep] - mean) / std) V[:, :m]) W   (see xmca_predict).  TI: element type of the data (ingest
@@ -467,19 +531,13 @@ void predict_impl(xmca_handle* h, int side, const TI* X, int64_t T, int64_t N_fu
   const bool vc = vo.i != nullptr, oc = vc || w_cplx;
   DevBuf<int64_t> idx;
   DevBuf<TI> mu, sd;
-  DevBuf<double> wh, wr, wi;
+  HostPlanes<double> w;
   if (keep_idx) XMCA_HIP(hipMemcpyAsync(idx.ensure((size_t)N), keep_idx, sizeof(int64_t) * N, hipMemcpyHostToDevice, h->st));
   XMCA_HIP(hipMemcpyAsync(mu.ensure((size_t)N), mean, sizeof(TI) * N, hipMemcpyHostToDevice, h->st));
   if (stdv) XMCA_HIP(hipMemcpyAsync(sd.ensure((size_t)N), stdv, sizeof(TI) * N, hipMemcpyHostToDevice, h->st));
-  const size_t nw = (size_t)m * q;
-  XMCA_HIP(hipMemcpyAsync(wh.ensure(nw * (w_cplx ? 2 : 1)), W, sizeof(double) * nw * (w_cplx ? 2 : 1), hipMemcpyHostToDevice, h->st));
-  if (w_cplx) {
-    hipLaunchKernelGGL((split_complex_kernel<double, double>), ew_grid((int64_t)nw), dim3(EW_BLOCK), 0, h->st, wh.get(), wr.ensure(nw),
-                       wi.ensure(nw), (int64_t)nw);
-    XMCA_HIP(hipGetLastError());
-  }
-  const double* Wr = w_cplx ? wr.get() : wh.get();
-  const double* Wi = w_cplx ? wi.get() : nullptr;
+  upload_planes<double>(h, W, (size_t)m * q, w_cplx, w, false);
+  const double* Wr = w.r;
+  const double* Wi = w.i;
   const int64_t rows = transform_rows(T, N_full * (int64_t)sizeof(TI) + N * (int64_t)sizeof(TP));
   DevBuf<TI> raw;
   DevBuf<TP> xs;
@@ -522,11 +580,8 @@ void predict_impl(xmca_handle* h, int side, const TI* X, int64_t T, int64_t N_fu
     }
     h->tm.end();
     if (oc) {
-      hipLaunchKernelGGL((pack_rows_kernel<double>), ew_grid((int64_t)tb * q), dim3(EW_BLOCK), 0, h->st, o_r.get(), o_i.get(), q, tb, (int)q,
-                         packed.get(), 0);
-      XMCA_HIP(hipGetLastError());
-      XMCA_HIP(hipMemcpyAsync(out + 2 * t0 * q, packed.get(), sizeof(double) * 2 * tb * q, hipMemcpyDeviceToHost, h->st));
-    } else {
+      pack_download<double>(h, o_r.get(), o_i.get(), q, tb, (int)q, packed.get(), out + 2 * t0 * q);
+    } else {          // (a real result needs no packing pass)
       XMCA_HIP(hipMemcpyAsync(out + t0 * q, o_r.get(), sizeof(double) * tb * q, hipMemcpyDeviceToHost, h->st));
     }
     XMCA_HIP(hipStreamSynchronize(h->st));      // (the pageable source / destination of the next block)
@@ -543,7 +598,7 @@ void reconstruct_impl(xmca_handle* h, int side, const double* B, int64_t T, int6
   if (m > 0) vec_operand<TP>(h, side, V, N, m, v_cplx, vo);
   const bool both_cplx = b_cplx && vo.i != nullptr;        // Re((Br + i Bi)(Vr - i Vi)^T) = Br Vr^T + Bi Vi^T
   DevBuf<int64_t> col_of;
-  DevBuf<double> mu, sd, bh, br, bi;
+  DevBuf<double> mu, sd;
   if (keep_idx) {
     std::vector<int64_t> inv((size_t)N_full, -1);
     for (int64_t c = 0; c < N; ++c) inv[(size_t)keep_idx[c]] = c;
@@ -552,17 +607,8 @@ void reconstruct_impl(xmca_handle* h, int side, const double* B, int64_t T, int6
   }
   if (mean) XMCA_HIP(hipMemcpyAsync(mu.ensure((size_t)N), mean, sizeof(double) * N, hipMemcpyHostToDevice, h->st));
   if (stdv) XMCA_HIP(hipMemcpyAsync(sd.ensure((size_t)N), stdv, sizeof(double) * N, hipMemcpyHostToDevice, h->st));
-  const size_t nb = (size_t)T * m;
-  DevBuf<TP> bpr, bpi;           // B in the product's element type
-  if (m > 0) {
-    XMCA_HIP(hipMemcpyAsync(bh.ensure(nb * (b_cplx ? 2 : 1)), B, sizeof(double) * nb * (b_cplx ? 2 : 1), hipMemcpyHostToDevice, h->st));
-    if (b_cplx)
-      hipLaunchKernelGGL((split_complex_kernel<double, TP>), ew_grid((int64_t)nb), dim3(EW_BLOCK), 0, h->st, bh.get(), bpr.ensure(nb),
-                         bpi.ensure(nb), (int64_t)nb);
-    else
-      hipLaunchKernelGGL((convert_kernel<double, TP>), ew_grid((int64_t)nb), dim3(EW_BLOCK), 0, h->st, bh.get(), bpr.ensure(nb), (int64_t)nb);
-    XMCA_HIP(hipGetLastError());
-  }
+  HostPlanes<TP> bp;             // B in the product's element type
+  if (m > 0) upload_planes<TP>(h, B, (size_t)T * m, b_cplx, bp);
   const int64_t rows = transform_rows(T, (N + N_full) * (int64_t)sizeof(double));
   DevBuf<double> C, full;
   C.ensure((size_t)rows * N);
@@ -576,10 +622,10 @@ void reconstruct_impl(xmca_handle* h, int side, const double* B, int64_t T, int6
       // C = B V^T (tb x N, K = m): A = the rows of B, B(j, n) = V[n, j]
       GemmOpts o;
       o.b_nfast = vo.mode_major;
-      gemm<TP, double>(h->st, h->gws, bpr.get() + t0 * m, m, vo.r, vo.ld, C.get(), N, tb, (int)N, (int)m, o);
+      gemm<TP, double>(h->st, h->gws, bp.r + t0 * m, m, vo.r, vo.ld, C.get(), N, tb, (int)N, (int)m, o);
       if (both_cplx) {
         o.beta = 1.0;
-        gemm<TP, double>(h->st, h->gws, bpi.get() + t0 * m, m, vo.i, vo.ld, C.get(), N, tb, (int)N, (int)m, o);
+        gemm<TP, double>(h->st, h->gws, bp.i + t0 * m, m, vo.i, vo.ld, C.get(), N, tb, (int)N, (int)m, o);
       }
     }
     h->tm.end();
@@ -597,7 +643,7 @@ void reconstruct_impl(xmca_handle* h, int side, const double* B, int64_t T, int6
 void check_transform(xmca_handle* h, const char* what, int side, const void* V, int64_t m, const int64_t* keep_idx, int64_t N_keep,
                      int64_t N_full) {
   const std::string w(what);
-  XMCA_CHECK(side == 0 || side == 1, XMCA_ERR_INVALID, w + ": side must be 0 or 1");
+  check_side(what, side);
   XMCA_CHECK(N_keep >= 1 && N_full >= N_keep && m >= 0 && m <= INT32_MAX && N_full <= INT32_MAX, XMCA_ERR_INVALID, w + ": bad sizes");
   XMCA_CHECK(keep_idx || N_keep == N_full, XMCA_ERR_INVALID, w + ": all columns are kept without keep_idx");
   if (keep_idx) {
@@ -613,7 +659,7 @@ void check_transform(xmca_handle* h, const char* what, int side, const void* V, 
 // r = corr(Re field columns, Y columns)  (see xmca_correlate)
 template <typename TI>
 void correlate_impl(xmca_handle* h, int side, const double* Y, int64_t T, int64_t m, double* r_out) {
-  FieldData<TI>& f = fields_of<TI>(h)[side];
+  FieldData<TI>& f = typed<TI>(h).f[side];
   XMCA_CHECK(f.T == T, XMCA_ERR_INVALID, "correlate: Y has " + std::to_string(T) + " rows, the field has " + std::to_string(f.T));
   const int64_t N = f.N;
   DevBuf<double> yh, sx, qx, sy, qy, C;
@@ -656,7 +702,7 @@ void center_columns(xmca_handle* h, TI* x, int64_t T, int64_t N) {
 
 template <typename TI>
 void center_field_impl(xmca_handle* h, int side, double* mean_out, double* std_out, int64_t* n_nan_out) {
-  FieldData<TI>& f = fields_of<TI>(h)[side];
+  FieldData<TI>& f = typed<TI>(h).f[side];
   XMCA_CHECK(!f.has_im && !f.ext_re, XMCA_ERR_STATE, "center_field: needs a real field owned by the library");
   const int64_t N = f.N;
   DevBuf<double> mean, sd, part_sum, part_sq;
@@ -688,7 +734,7 @@ void center_field_impl(xmca_handle* h, int side, double* mean_out, double* std_o
 // keep_out[c] = 1 for columns without a NaN; the field is replaced by its kept columns (T x n_keep).
 template <typename TI>
 void compact_field_impl(xmca_handle* h, int side, int* keep_out, int64_t* n_keep_out) {
-  FieldData<TI>& f = fields_of<TI>(h)[side];
+  FieldData<TI>& f = typed<TI>(h).f[side];
   XMCA_CHECK(!f.has_im && !f.ext_re, XMCA_ERR_STATE, "compact_field: needs a real field owned by the library");
   const int64_t N = f.N;
   DevBuf<int> nans, part_nan;
@@ -725,7 +771,7 @@ void compact_field_impl(xmca_handle* h, int side, int* keep_out, int64_t* n_keep
 // apply_weights / normalize of the constructor stage (array.py:317-365) on the resident centered field: one factor per column
 template <typename TI>
 void scale_field_impl(xmca_handle* h, int side, const void* w_host, int divide) {
-  FieldData<TI>& f = fields_of<TI>(h)[side];
+  FieldData<TI>& f = typed<TI>(h).f[side];
   XMCA_CHECK(!f.has_im && !f.ext_re, XMCA_ERR_STATE, "scale_field: needs a real field owned by the library");
   DevBuf<TI> w;
   XMCA_HIP(hipMemcpyAsync(w.ensure((size_t)f.N), w_host, sizeof(TI) * (size_t)f.N, hipMemcpyHostToDevice, h->st));
@@ -758,6 +804,45 @@ void check_rot(const RotateResult& rr) {
              "Rotation process did not converge. Try decreasing the tolerance. Invalid NaN entries also might be a problem.");
 }
 
+// Promax of the first p modes of `res` where its vectors are (array.py:815-833): the loadings V sqrt(sigma) of both fields
+// stacked (array.py:818-822; Nl left rows, Nr right rows, 0 for a one-field result) are built in `d`, then rotated.
+void rotate_resident(xmca_handle* h, Rotator& rot, RotationDevice& d, DevBuf<double>& sigma_dev, const SolveResult& res, int64_t Nl,
+                     int64_t Nr, int p, int power, double tol, int max_iter, RotateResult& rr) {
+  const bool cplx = res.cplx;
+  rot.alloc(d, Nl + Nr, Nl, p, cplx);
+  XMCA_HIP(hipMemcpyAsync(sigma_dev.ensure((size_t)p), res.sigma.data(), sizeof(double) * p, hipMemcpyHostToDevice, h->st));
+  const CPlanes& Vl = res.Vt[0];
+  const CPlanes& Vr = res.Vt[Nr > 0 ? 1 : 0];
+  if (res.vt_f32[0]) {
+    // float32 model (one real field): the reference multiplies the float32 vectors by the float32 square roots of the float32
+    // singular values - a float32 product - and rotates that; the same roundings here, then float64 like the host path
+    XMCA_CHECK(!cplx && Nr == 0, XMCA_ERR_STATE, "rotate: float32-resident vectors are real and one-sided");
+    hipLaunchKernelGGL(rot_build_loadings_f32_kernel, ew_grid(Nl), dim3(EW_BLOCK), 0, h->st, res.Vt32[0].get(), Nl, Nl, sigma_dev.get(), p,
+                       d.A.r(), d.h.get());
+    rot.run<false>(d, power, tol, max_iter, rr, nullptr, false);
+  } else if (cplx) {
+    hipLaunchKernelGGL((rot_build_loadings_kernel<true>), ew_grid(Nl + Nr), dim3(EW_BLOCK), 0, h->st, Vl.r(), Vl.i(true), Nl, Nl,
+                       Vr.r(), Vr.i(true), Nr > 0 ? Nr : Nl, Nr, sigma_dev.get(), p, d.A.r(), d.A.i(true), d.h.get());
+    rot.run<true>(d, power, tol, max_iter, rr, nullptr, false);
+  } else {
+    hipLaunchKernelGGL((rot_build_loadings_kernel<false>), ew_grid(Nl + Nr), dim3(EW_BLOCK), 0, h->st, Vl.r(), (const double*)nullptr,
+                       Nl, Nl, Vr.r(), (const double*)nullptr, Nr > 0 ? Nr : Nl, Nr, sigma_dev.get(), p, d.A.r(), (double*)nullptr,
+                       d.h.get());
+    rot.run<false>(d, power, tol, max_iter, rr, nullptr, false);
+  }
+}
+
+// What every replicate of a rule_n / bootstrap call has in common: the shape of the fields, the complexification (op == nullptr:
+// real replicates) and the rotation (rotated != 0: n_rot = p, power, tol)
+struct ReplicateSpec {
+  int64_t T = 0, Nx = 0, Ny = 0;
+  int n_fields = 1;
+  const ComplexOp* op = nullptr;
+  int rotated = 0, p = 0, power = 1;
+  double tol = 0.0;
+  int64_t eig_n() const { return std::min(T, n_fields == 2 ? std::min(Nx, Ny) : Nx); }     // order of the eigenproblems = rank
+};
+
 // One surrogate / bootstrap replicate from centered real fields resident in `f` (re planes): complexify, solve, rotate,
 // variance spectrum (the body of the loops array.py:1753-1765 and :1935-1947).
 template <typename TI>
@@ -774,13 +859,13 @@ struct ReplicateRunner {
   RotationDevice rd;
   DevBuf<double> sigma_dev;
 
-  // op: the complexification of every replicate (nullptr: real); only the circulant Hilbert operator may take the analytic route
-  ReplicateRunner(xmca_handle* h_, int64_t T_, int64_t Nx, int64_t Ny, int n_fields_, const ComplexOp* op, int rotated_, int p_,
-                  int power_, double tol_)
-      : h(h_), T(T_), Ns{Nx, Ny}, n_fields(n_fields_), rotated(rotated_), p(p_), power(power_), tol(tol_), cplx(op != nullptr),
+  // only the circulant Hilbert operator may take the analytic route
+  ReplicateRunner(xmca_handle* h_, const ReplicateSpec& s)
+      : h(h_), T(s.T), Ns{s.Nx, s.Ny}, n_fields(s.n_fields), rotated(s.rotated), p(s.p), power(s.power), tol(s.tol), cplx(s.op != nullptr),
         solver(h_->st, h_->gws, h_->ews, h_->tm), rot(h_->st, h_->tm, h_->gws, h_->ews) {
+    const ComplexOp* op = s.op;
     static const bool analytic_on = [] { const char* e = std::getenv("XMCA_ANALYTIC"); return !(e && e[0] == '0'); }();
-    analytic = cplx && op->kind == ComplexOp::CIRCULANT && analytic_on && Nx > T && (n_fields == 1 || Ny > T);
+    analytic = cplx && op->kind == ComplexOp::CIRCULANT && analytic_on && s.Nx > T && (n_fields == 1 || s.Ny > T);
     if (cplx) XMCA_CHECK(op->T == T, XMCA_ERR_INVALID, "replicates: the operator was made for another number of time steps");
     if (cplx && !analytic) build_operator<TI>(h, *op, htb);
   }
@@ -803,23 +888,8 @@ struct ReplicateRunner {
       for (int64_t i = 0; i < n_out; ++i) out[i] = res.sigma[i];
       return 1;
     }
-    // rotate the first p modes (array.py:815-833)
-    const int64_t Nl = Ns[0], Nr = n_fields == 2 ? Ns[1] : 0;
-    rot.alloc(rd, Nl + Nr, Nl, p, cplx);
-    XMCA_HIP(hipMemcpyAsync(sigma_dev.ensure((size_t)p), res.sigma.data(), sizeof(double) * p, hipMemcpyHostToDevice, h->st));
-    const CPlanes& Vl = res.Vt[0];
-    const CPlanes& Vr = res.Vt[n_fields == 2 ? 1 : 0];
     RotateResult rr;
-    if (cplx) {
-      hipLaunchKernelGGL((rot_build_loadings_kernel<true>), ew_grid(Nl + Nr), dim3(EW_BLOCK), 0, h->st, Vl.r(), Vl.i(true), Nl, Nl,
-                         Vr.r(), Vr.i(true), Nr > 0 ? Nr : Nl, Nr, sigma_dev.get(), p, rd.A.r(), rd.A.i(true), rd.h.get());
-      rot.run<true>(rd, power, tol, 1000, rr, nullptr, false);
-    } else {
-      hipLaunchKernelGGL((rot_build_loadings_kernel<false>), ew_grid(Nl + Nr), dim3(EW_BLOCK), 0, h->st, Vl.r(), (const double*)nullptr,
-                         Nl, Nl, Vr.r(), (const double*)nullptr, Nr > 0 ? Nr : Nl, Nr, sigma_dev.get(), p, rd.A.r(), (double*)nullptr,
-                         rd.h.get());
-      rot.run<false>(rd, power, tol, 1000, rr, nullptr, false);
-    }
+    rotate_resident(h, rot, rd, sigma_dev, res, Ns[0], n_fields == 2 ? Ns[1] : 0, p, power, tol, 1000, rr);
     if (rr.nan || !rr.converged) {       // array.py:1762-1763: the run is silently dropped
       for (int64_t i = 0; i < n_out; ++i) out[i] = 0.0;
       return 0;
@@ -832,39 +902,44 @@ struct ReplicateRunner {
   }
 };
 
+// The replicates run = first, first + stride, ... < n_runs of one lane of a rule_n / bootstrap call (`what`).  fill(side, x, run)
+// queues the raw real field of `side` (T x N, row-major) into x on the lane's stream; the field is centered like the MCA
+// constructor does (array.py:117) and handed to the runner.  `stage` names the stage timer of that preparation.  sync_each_run:
+// the stream is synchronised after every replicate (a fill that uploads from a buffer it reuses for the next replicate), else
+// once when the lane has queued its last one.
+template <typename TI, typename Fill>
+void replicate_lane(xmca_handle* h, const char* what, const char* stage, const ReplicateSpec& spec, int64_t first, int64_t stride,
+                    int64_t n_runs, bool sync_each_run, double* spectra, int* kept, int64_t n_out, Fill&& fill) {
+  FieldData<TI> f[2];
+  const int64_t T = spec.T, Ns[2] = {spec.Nx, spec.Ny};
+  ReplicateRunner<TI> runner(h, spec);
+  XMCA_CHECK(n_out == (spec.rotated ? (int64_t)spec.p : runner.rank()), XMCA_ERR_INVALID,
+             std::string(what) + ": n_out must be rank (unrotated) or p (rotated)");
+  for (int64_t run = first; run < n_runs; run += stride) {
+    h->tm.begin(stage);
+    for (int s = 0; s < spec.n_fields; ++s) {
+      f[s].T = T; f[s].N = Ns[s]; f[s].has_im = false; f[s].ext_re = nullptr;
+      TI* x = f[s].re.ensure((size_t)(T * Ns[s]));
+      fill(s, x, run);
+      XMCA_HIP(hipGetLastError());
+      center_columns<TI>(h, x, T, Ns[s]);
+    }
+    h->tm.end();
+    kept[run] = runner.run(f, spectra + run * n_out, n_out);
+    if (sync_each_run) XMCA_HIP(hipStreamSynchronize(h->st));
+  }
+  if (!sync_each_run) XMCA_HIP(hipStreamSynchronize(h->st));
+}
+
 // Surrogates are independent: `lanes` of them are in flight at a time, each on its own stream with its own workspaces
 // and host thread (the solver synchronises its stream now and then, so a lane needs a thread of its own).  A round of
 // the eigensolver leaves the chip partly idle - its tile-solve chain and the tail of its updates - and a
 // second surrogate's kernels fill that: measured at C4 as two PROCESSES sharing the GPU +34 % surrogates/s
 // (profiles/r02_bench_shared_gpu_2ranks.json), now inside one process.  Lane j takes the runs j, j + lanes, ...; the
 // generator is keyed by (seed, run, side), so the spectra do not depend on the number of lanes.  XMCA_RULE_N_LANES
-// (default: 3 for eigenproblems of 2000 and more, 4 below; 1 = the plain loop).
-template <typename TI>
-void rule_n_lane(xmca_handle* h, int64_t T, int64_t Nx, int64_t Ny, int n_fields, const ComplexOp* op, int rotated, int p, int power,
-                 double tol, int64_t run_begin, int64_t run_end, int64_t first, int64_t stride, uint64_t seed, double* spectra, int* kept,
-                 int64_t n_out) {
-  FieldData<TI> f[2];
-  const int64_t Ns[2] = {Nx, Ny};
-  ReplicateRunner<TI> runner(h, T, Nx, Ny, n_fields, op, rotated, p, power, tol);
-  XMCA_CHECK(n_out == (rotated ? (int64_t)p : runner.rank()), XMCA_ERR_INVALID, "rule_n: n_out must be rank (unrotated) or p (rotated)");
-  for (int64_t run = run_begin + first; run < run_end; run += stride) {
-    h->tm.begin("surrogate");
-    for (int s = 0; s < n_fields; ++s) {
-      f[s].T = T; f[s].N = Ns[s]; f[s].has_im = false;
-      const int64_t n = T * Ns[s];
-      TI* x = f[s].re.ensure((size_t)n);
-      hipLaunchKernelGGL((philox_normal_kernel<TI>), ew_grid((n + 1) / 2), dim3(EW_BLOCK), 0, h->st, x, n, seed, (uint32_t)run,
-                         (uint32_t)s);
-      XMCA_HIP(hipGetLastError());
-      center_columns<TI>(h, x, T, Ns[s]);
-    }
-    h->tm.end();
-    kept[run - run_begin] = runner.run(f, spectra + (run - run_begin) * n_out, n_out);
-  }
-  XMCA_HIP(hipStreamSynchronize(h->st));
-}
-
-// number of replicates kept in flight (XMCA_RULE_N_LANES; measured in rule_n_impl's note above)
+// (default: 2 for eigenproblems of 2000 and more, 4 below; 1 = the plain loop).
+//
+// number of replicates kept in flight
 static int lanes_for(int64_t eig_n, int64_t n_runs) {
   // measured on MI355X (scripts/rule_n_bench.py, surrogates/s with 1 / 2 / 3 / 4 lanes): C4 8.0 / 10.6 / 10.4 / 10.4,
   // C2-shaped EOF 25.8 / 32.9 / 33.1 / 32.3, C1-shaped (eigenproblems of 675) 109 / 191 / 265 / 337
@@ -935,141 +1010,75 @@ void run_lanes(xmca_handle* h, int lanes, F&& lane_body) {
     if (e) std::rethrow_exception(e);
 }
 
-template <typename TI>
-void rule_n_impl(xmca_handle* h, int64_t T, int64_t Nx, int64_t Ny, int n_fields, const double* ht_host, int rotated, int p,
-                 int power, double tol, int64_t run_begin, int64_t run_end, uint64_t seed, double* spectra, int* kept,
-                 int64_t n_out) {
-  const int64_t eig_n = std::min(T, n_fields == 2 ? std::min(Nx, Ny) : Nx);
-  const int lanes = lanes_for(eig_n, run_end - run_begin);
-  ComplexOp hop;
-  if (ht_host) hop = ComplexOp::circulant(ht_host, T);
-  const ComplexOp* op = ht_host ? &hop : nullptr;
+// lane_body(lane handle, first, stride) runs the replicates first, first + stride, ... of a rule_n / bootstrap call: on the
+// caller's handle alone (the plain loop), or on as many concurrent lanes as lanes_for grants
+template <typename F>
+void run_replicates(xmca_handle* h, const ReplicateSpec& spec, int64_t n_runs, F&& lane_body) {
+  const int lanes = lanes_for(spec.eig_n(), n_runs);
   if (lanes <= 1) {
-    rule_n_lane<TI>(h, T, Nx, Ny, n_fields, op, rotated, p, power, tol, run_begin, run_end, 0, 1, seed, spectra, kept, n_out);
+    lane_body(h, (int64_t)0, (int64_t)1);
     return;
   }
-  run_lanes(h, lanes, [&](xmca_handle* lh, int j) {
-    rule_n_lane<TI>(lh, T, Nx, Ny, n_fields, op, rotated, p, power, tol, run_begin, run_end, j, lanes, seed, spectra, kept, n_out);
+  run_lanes(h, lanes, [&](xmca_handle* lh, int j) { lane_body(lh, (int64_t)j, (int64_t)lanes); });
+}
+
+// runs [run_begin, run_end) of xmca_rule_n: the fields of run r are N(0,1) surrogates keyed by (seed, r, side)
+template <typename TI>
+void rule_n_impl(xmca_handle* h, const ReplicateSpec& spec, int64_t run_begin, int64_t run_end, uint64_t seed, double* spectra, int* kept,
+                 int64_t n_out) {
+  const int64_t Ns[2] = {spec.Nx, spec.Ny};
+  run_replicates(h, spec, run_end - run_begin, [&](xmca_handle* lh, int64_t first, int64_t stride) {
+    replicate_lane<TI>(lh, "rule_n", "surrogate", spec, first, stride, run_end - run_begin, false, spectra, kept, n_out,
+                       [&](int s, TI* x, int64_t run) {
+                         const int64_t n = spec.T * Ns[s];
+                         hipLaunchKernelGGL((philox_normal_kernel<TI>), ew_grid((n + 1) / 2), dim3(EW_BLOCK), 0, lh->st, x, n, seed,
+                                            (uint32_t)(run_begin + run), (uint32_t)s);
+                       });
   });
 }
 
 // ---- bootstrapping: working copies on the device -----------------------------------------------------------------
-template <typename TI> DevBuf<TI>* boot_w(xmca_handle* h);
-template <> DevBuf<float>* boot_w<float>(xmca_handle* h) { return h->boot32; }
-template <> DevBuf<double>* boot_w<double>(xmca_handle* h) { return h->boot64; }
-template <typename TI> DevBuf<TI>& boot_tmp(xmca_handle* h);
-template <> DevBuf<float>& boot_tmp<float>(xmca_handle* h) { return h->boot32_tmp; }
-template <> DevBuf<double>& boot_tmp<double>(xmca_handle* h) { return h->boot64_tmp; }
-template <typename TI> FieldData<TI>* boot_f(xmca_handle* h);
-template <> FieldData<float>* boot_f<float>(xmca_handle* h) { return h->bootf32; }
-template <> FieldData<double>* boot_f<double>(xmca_handle* h) { return h->bootf64; }
-
 template <typename TI>
 void bootstrap_begin_impl(xmca_handle* h, int n_fields) {
-  FieldData<TI>* f = fields_of<TI>(h);
-  h->boot_T = f[0].T;
+  TypedState<TI>& ts = typed<TI>(h);
+  h->boot_T = ts.f[0].T;
   h->boot_fields = n_fields;
   for (int s = 0; s < n_fields; ++s) {
-    XMCA_CHECK(h->field_set[s] && f[s].T == h->boot_T, XMCA_ERR_STATE, "bootstrap: set the fields first (same number of time steps)");
-    h->boot_N[s] = f[s].N;
-    const size_t n = (size_t)f[s].T * f[s].N;
-    XMCA_HIP(hipMemcpyAsync(boot_w<TI>(h)[s].ensure(n), f[s].r(), sizeof(TI) * n, hipMemcpyDeviceToDevice, h->st));
+    XMCA_CHECK(h->field_set[s] && ts.f[s].T == h->boot_T, XMCA_ERR_STATE, "bootstrap: set the fields first (same number of time steps)");
+    h->boot_N[s] = ts.f[s].N;
+    const size_t n = (size_t)ts.f[s].T * ts.f[s].N;
+    XMCA_HIP(hipMemcpyAsync(ts.boot[s].ensure(n), ts.f[s].r(), sizeof(TI) * n, hipMemcpyDeviceToDevice, h->st));
   }
   XMCA_HIP(hipStreamSynchronize(h->st));
 }
 
-template <typename TI>
-void bootstrap_run_impl(xmca_handle* h, const double* ht_host, const int64_t* idx_left, const int64_t* idx_right, int rotated, int p,
-                        int power, double tol, double* spectrum, int* kept, int64_t n_out) {
-  const int n_fields = h->boot_fields;
-  const int64_t T = h->boot_T;
-  XMCA_CHECK(n_fields >= 1 && T > 0, XMCA_ERR_STATE, "bootstrap: call xmca_bootstrap_begin first");
-  const int64_t* idx_host[2] = {idx_left, idx_right};
-  FieldData<TI>* f = boot_f<TI>(h);
-  DevBuf<int64_t> idx_dev;
-  h->tm.begin("resample");
-  for (int s = 0; s < n_fields; ++s) {
-    const int64_t N = h->boot_N[s];
-    const size_t n = (size_t)T * N;
-    DevBuf<TI>& W = boot_w<TI>(h)[s];
-    if (idx_host[s]) {
-      for (int64_t t = 0; t < T; ++t) XMCA_CHECK(idx_host[s][t] >= 0 && idx_host[s][t] < T, XMCA_ERR_INVALID, "bootstrap: row index out of range");
-      XMCA_HIP(hipMemcpyAsync(idx_dev.ensure((size_t)T), idx_host[s], sizeof(int64_t) * T, hipMemcpyHostToDevice, h->st));
-      DevBuf<TI>& tmp = boot_tmp<TI>(h);
-      hipLaunchKernelGGL((gather_rows_kernel<TI>), ew_grid((int64_t)n, 4), dim3(EW_BLOCK), 0, h->st, W.get(), tmp.ensure(n), idx_dev.get(),
-                         (int)T, N);
-      XMCA_HIP(hipGetLastError());
-      XMCA_HIP(hipStreamSynchronize(h->st));      // idx_dev is reused for the other side
-      std::swap(W, tmp);                           // the resampling is cumulative (array.py:1935-1943 overwrite X_surr)
-    }
-    f[s].T = T; f[s].N = N; f[s].has_im = false; f[s].ext_re = nullptr;
-    XMCA_HIP(hipMemcpyAsync(f[s].re.ensure(n), W.get(), sizeof(TI) * n, hipMemcpyDeviceToDevice, h->st));
-    center_columns<TI>(h, f[s].re.get(), T, N);   // MCA(...) ctor, array.py:117
-    XMCA_HIP(hipGetLastError());
-  }
-  h->tm.end();
-  ComplexOp hop;
-  if (ht_host) hop = ComplexOp::circulant(ht_host, T);
-  ReplicateRunner<TI> runner(h, T, h->boot_N[0], n_fields == 2 ? h->boot_N[1] : 0, n_fields, ht_host ? &hop : nullptr, rotated, p, power,
-                             tol);
-  XMCA_CHECK(n_out == (rotated ? (int64_t)p : runner.rank()), XMCA_ERR_INVALID, "bootstrap: n_out must be rank (unrotated) or p (rotated)");
-  *kept = runner.run(f, spectrum, n_out);
-}
-
-// Replicates r = first, first + stride, ... of a bootstrap: rows of the ORIGINAL working copies (xmca_bootstrap_begin) are
-// gathered through the composed index of replicate r - the reference's cumulative resampling X <- X[idx_r] unrolled on
-// the host, c_r = c_{r-1}[idx_r] - so the replicates do not depend on each other on the device and can run in lanes.
-template <typename TI>
-void bootstrap_lane(xmca_handle* h, xmca_handle* src, const ComplexOp* op, const int64_t* idx_left, const int64_t* idx_right,
-                    int64_t n_runs, int64_t first, int64_t stride, int rotated, int p, int power, double tol, double* spectra,
-                    int* kept, int64_t n_out) {
-  const int n_fields = src->boot_fields;
-  const int64_t T = src->boot_T;
-  const int64_t* idx_host[2] = {idx_left, idx_right};
-  FieldData<TI> f[2];
-  DevBuf<int64_t> idx_dev[2];
-  ReplicateRunner<TI> runner(h, T, src->boot_N[0], n_fields == 2 ? src->boot_N[1] : 0, n_fields, op, rotated, p, power, tol);
-  XMCA_CHECK(n_out == (rotated ? (int64_t)p : runner.rank()), XMCA_ERR_INVALID, "bootstrap: n_out must be rank (unrotated) or p (rotated)");
-  for (int64_t run = first; run < n_runs; run += stride) {
-    h->tm.begin("resample");
-    for (int s = 0; s < n_fields; ++s) {
-      const int64_t N = src->boot_N[s];
-      const size_t n = (size_t)T * N;
-      const DevBuf<TI>& W = boot_w<TI>(src)[s];
-      f[s].T = T; f[s].N = N; f[s].has_im = false; f[s].ext_re = nullptr;
-      if (idx_host[s]) {
-        XMCA_HIP(hipMemcpyAsync(idx_dev[s].ensure((size_t)T), idx_host[s] + run * T, sizeof(int64_t) * T, hipMemcpyHostToDevice, h->st));
-        hipLaunchKernelGGL((gather_rows_kernel<TI>), ew_grid((int64_t)n, 4), dim3(EW_BLOCK), 0, h->st, W.get(), f[s].re.ensure(n),
-                           idx_dev[s].get(), (int)T, N);
-      } else {
-        XMCA_HIP(hipMemcpyAsync(f[s].re.ensure(n), W.get(), sizeof(TI) * n, hipMemcpyDeviceToDevice, h->st));
-      }
-      center_columns<TI>(h, f[s].re.get(), T, N);   // MCA(...) ctor, array.py:117
-      XMCA_HIP(hipGetLastError());
-    }
-    h->tm.end();
-    kept[run] = runner.run(f, spectra + run * n_out, n_out);
-    XMCA_HIP(hipStreamSynchronize(h->st));          // the index buffers are overwritten by the next replicate's upload
-  }
-}
-
+// The replicates of a bootstrap: rows of the ORIGINAL working copies (xmca_bootstrap_begin) are gathered through the composed
+// index of replicate r - the reference's cumulative resampling X <- X[idx_r] unrolled on the host, c_r = c_{r-1}[idx_r] - so
+// the replicates do not depend on each other on the device and can run in lanes.  A side without indices is copied as it is.
 template <typename TI>
 void bootstrap_runs_impl(xmca_handle* h, const ComplexOp* op, const int64_t* idx_left, const int64_t* idx_right, int64_t n_runs,
                          int rotated, int p, int power, double tol, double* spectra, int* kept, int64_t n_out) {
-  const int n_fields = h->boot_fields;
   const int64_t T = h->boot_T;
-  XMCA_CHECK(n_fields >= 1 && T > 0, XMCA_ERR_STATE, "bootstrap: call xmca_bootstrap_begin first");
-  for (const int64_t* idx : {idx_left, idx_right})
+  const int64_t* idx_host[2] = {idx_left, idx_right};
+  for (const int64_t* idx : idx_host)
     if (idx)
       for (int64_t i = 0; i < n_runs * T; ++i) XMCA_CHECK(idx[i] >= 0 && idx[i] < T, XMCA_ERR_INVALID, "bootstrap: row index out of range");
-  const int64_t eig_n = std::min(T, n_fields == 2 ? std::min(h->boot_N[0], h->boot_N[1]) : h->boot_N[0]);
-  const int lanes = lanes_for(eig_n, n_runs);
-  if (lanes <= 1) {
-    bootstrap_lane<TI>(h, h, op, idx_left, idx_right, n_runs, 0, 1, rotated, p, power, tol, spectra, kept, n_out);
-    return;
-  }
-  run_lanes(h, lanes, [&](xmca_handle* lh, int j) {
-    bootstrap_lane<TI>(lh, h, op, idx_left, idx_right, n_runs, j, lanes, rotated, p, power, tol, spectra, kept, n_out);
+  const ReplicateSpec spec{T, h->boot_N[0], h->boot_fields == 2 ? h->boot_N[1] : 0, h->boot_fields, op, rotated, p, power, tol};
+  const DevBuf<TI>* work = typed<TI>(h).boot;
+  run_replicates(h, spec, n_runs, [&](xmca_handle* lh, int64_t first, int64_t stride) {
+    DevBuf<int64_t> idx_dev[2];
+    // (synchronised after every replicate: the index buffers are overwritten by the next replicate's upload)
+    replicate_lane<TI>(lh, "bootstrap", "resample", spec, first, stride, n_runs, true, spectra, kept, n_out, [&](int s, TI* x, int64_t run) {
+      const int64_t N = h->boot_N[s];
+      const size_t n = (size_t)T * N;
+      if (idx_host[s]) {
+        XMCA_HIP(hipMemcpyAsync(idx_dev[s].ensure((size_t)T), idx_host[s] + run * T, sizeof(int64_t) * T, hipMemcpyHostToDevice, lh->st));
+        hipLaunchKernelGGL((gather_rows_kernel<TI>), ew_grid((int64_t)n, 4), dim3(EW_BLOCK), 0, lh->st, work[s].get(), x, idx_dev[s].get(),
+                           (int)T, N);
+      } else {
+        XMCA_HIP(hipMemcpyAsync(x, work[s].get(), sizeof(TI) * n, hipMemcpyDeviceToDevice, lh->st));
+      }
+    });
   });
 }
 
@@ -1111,7 +1120,7 @@ extern "C" {
 
 int xmca_set_field(xmca_handle* h, int side, const void* re, const void* im, int64_t T, int64_t N, int dtype, int location) {
   API_BEGIN(h)
-  XMCA_CHECK(side == 0 || side == 1, XMCA_ERR_INVALID, "set_field: side must be 0 or 1");
+  check_side("set_field", side);
   XMCA_CHECK(re && T >= 2 && N >= 1, XMCA_ERR_INVALID, "set_field: need a T x N field with T >= 2, N >= 1");
   XMCA_CHECK(dtype == XMCA_F32 || dtype == XMCA_F64, XMCA_ERR_INVALID, "set_field: dtype must be float32 or float64");
   XMCA_CHECK(T < (1 << 30) && N < (1ll << 31), XMCA_ERR_UNSUPPORTED, "set_field: dimension too large");
@@ -1119,11 +1128,9 @@ int xmca_set_field(xmca_handle* h, int side, const void* re, const void* im, int
   else {
     XMCA_CHECK(h->field_set[0], XMCA_ERR_STATE, "set_field: set the left field first");
     XMCA_CHECK(dtype == h->dtype, XMCA_ERR_INVALID, "set_field: both fields must have the same dtype");
-    const int64_t T0 = dtype == XMCA_F32 ? h->f32[0].T : h->f64[0].T;
-    XMCA_CHECK(T == T0, XMCA_ERR_INVALID, "set_field: time dimensions of the fields differ");
+    XMCA_CHECK(T == resident_T(h), XMCA_ERR_INVALID, "set_field: time dimensions of the fields differ");
   }
-  if (dtype == XMCA_F32) set_field_impl<float>(h, side, re, im, T, N, location);
-  else set_field_impl<double>(h, side, re, im, T, N, location);
+  with_dtype(dtype, [&](auto t) { set_field_impl<decltype(t)>(h, side, re, im, T, N, location); });
   h->field_set[side] = true;
   h->solved = false;
   if (side == 0) h->op_pending = false;
@@ -1135,12 +1142,11 @@ int xmca_complexify(xmca_handle* h, const double* hilbert_col) {
   XMCA_CHECK(h->field_set[0], XMCA_ERR_STATE, "complexify: set a field first");
   if (!hilbert_col) {            // back to the real fields (their real planes are untouched by a complex solve)
     h->op_pending = false;
-    for (int s = 0; s < 2; ++s) { h->f32[s].has_im = false; h->f64[s].has_im = false; }
+    for (int s = 0; s < 2; ++s) { h->s32.f[s].has_im = false; h->s64.f[s].has_im = false; }      // (both dtypes' fields)
     h->solved = false;
     return XMCA_OK;
   }
-  const int64_t T = h->dtype == XMCA_F32 ? h->f32[0].T : h->f64[0].T;
-  h->op = ComplexOp::circulant(hilbert_col, T);
+  h->op = ComplexOp::circulant(hilbert_col, resident_T(h));
   h->op_pending = true;           // xmca_solve decides: subspace formulation (no imaginary plane) or X_im = Ht X
   h->solved = false;
   API_END(h)
@@ -1149,15 +1155,14 @@ int xmca_complexify(xmca_handle* h, const double* hilbert_col) {
 int xmca_complexify_extended(xmca_handle* h, const double* col3, const double* hbar, const double* U, const double* W, int rank) {
   API_BEGIN(h)
   XMCA_CHECK(h->field_set[0], XMCA_ERR_STATE, "complexify_extended: set a field first");
-  XMCA_CHECK(col3 && hbar && rank >= 0 && rank <= 16 && (rank == 0 || (U && W)), XMCA_ERR_INVALID,
-             "complexify_extended: need col3, hbar and T x rank U, W (rank <= 16)");
-  if (h->dtype == XMCA_F32) {
+  check_extended_parts("complexify_extended", col3, hbar, U, W, rank);
+  if (h->dtype == XMCA_F32) {     // (not a dispatch: only float32 fields are moved, from typed<float> to typed<double>)
     // the reference extends in float64 (the forecast of a float32 column is float64, array.py:394-410): the resident real
     // float32 fields become float64 fields, exactly (every float32 is a float64)
     for (int s = 0; s < 2; ++s) {
       if (!h->field_set[s]) continue;
-      FieldData<float>& a = h->f32[s];
-      FieldData<double>& b = h->f64[s];
+      FieldData<float>& a = h->s32.f[s];
+      FieldData<double>& b = h->s64.f[s];
       const int64_t n = a.T * a.N;
       b.T = a.T; b.N = a.N; b.has_im = false; b.ext_re = nullptr; b.ext_im = nullptr;
       hipLaunchKernelGGL((convert_kernel<float, double>), ew_grid(n), dim3(EW_BLOCK), 0, h->st, a.r(), b.re.ensure((size_t)n), n);
@@ -1165,13 +1170,13 @@ int xmca_complexify_extended(xmca_handle* h, const double* col3, const double* h
     }
     XMCA_HIP(hipStreamSynchronize(h->st));
     for (int s = 0; s < 2; ++s) {
-      FieldData<float>& a = h->f32[s];
+      FieldData<float>& a = h->s32.f[s];
       a.re.release(); a.im.release(); a.ext_re = nullptr; a.ext_im = nullptr; a.has_im = false;
     }
     h->dtype = XMCA_F64;
   }
-  const int64_t T = h->f64[0].T;
-  XMCA_CHECK(T <= 46340, XMCA_ERR_UNSUPPORTED, "complexify_extended: T x T operator too large");
+  const int64_t T = h->s64.f[0].T;
+  check_operator_size("complexify_extended", T);
   h->op = ComplexOp::extended(col3, hbar, U, W, rank, T);
   h->op_pending = true;           // xmca_solve / xmca_project form X_im = G X (there is no subspace formulation of G)
   h->solved = false;
@@ -1183,8 +1188,7 @@ int xmca_solve(xmca_handle* h, int n_fields, int64_t n_vec, int64_t* rank_out) {
   XMCA_CHECK(n_fields == 1 || n_fields == 2, XMCA_ERR_INVALID, "solve: n_fields must be 1 or 2");
   XMCA_CHECK(h->field_set[0] && (n_fields == 1 || h->field_set[1]), XMCA_ERR_STATE, "solve: fields not set");
   h->solved = false;
-  if (h->dtype == XMCA_F32) solve_impl<float>(h, n_fields, n_vec);
-  else solve_impl<double>(h, n_fields, n_vec);
+  with_dtype(h->dtype, [&](auto t) { solve_impl<decltype(t)>(h, n_fields, n_vec); });
   if (n_fields == 1) h->res.ldv[1] = 0;      // (a one-field result has no right vectors: xmca_rotate_solved stacks by ldv)
   h->solved = true;
   if (rank_out) *rank_out = h->res.rank;
@@ -1221,38 +1225,33 @@ int xmca_get_solve_info(xmca_handle* h, int* info, int n) {
 int xmca_get_vectors(xmca_handle* h, int side, void* out, int64_t n_modes, int dtype) {
   API_BEGIN(h)
   XMCA_CHECK(h->solved, XMCA_ERR_STATE, "vectors requested before solve");
-  XMCA_CHECK(side == 0 || side == 1, XMCA_ERR_INVALID, "get_vectors: side must be 0 or 1");
+  check_side("get_vectors", side);
   XMCA_CHECK(out && n_modes >= 0 && n_modes <= h->res.n_vec && h->res.ldv[side] > 0, XMCA_ERR_INVALID,
              "get_vectors: more modes requested than were back-projected");
-  if (n_modes > 0) {
-    if (dtype == XMCA_F32) get_vectors_impl<float>(h, side, out, n_modes);
-    else get_vectors_impl<double>(h, side, out, n_modes);
-  }
+  if (n_modes > 0) with_dtype(dtype, [&](auto t) { get_vectors_impl<decltype(t)>(h, side, out, n_modes); });
   API_END(h)
 }
 
 int xmca_get_eofs(xmca_handle* h, int side, const double* W, int64_t m, int64_t q, int w_is_complex, void* out, int dtype) {
   API_BEGIN(h)
   XMCA_CHECK(h->solved, XMCA_ERR_STATE, "eofs requested before solve");
-  XMCA_CHECK(side == 0 || side == 1, XMCA_ERR_INVALID, "get_eofs: side must be 0 or 1");
+  check_side("get_eofs", side);
   XMCA_CHECK(out && q >= 1 && m >= 1 && m <= h->res.n_vec && (W || q == m) && h->res.ldv[side] > 0, XMCA_ERR_INVALID,
              "get_eofs: more modes requested than were back-projected, or a bad mixing matrix");
-  if (dtype == XMCA_F32) get_eofs_impl<float>(h, side, W, m, q, w_is_complex != 0, out);
-  else get_eofs_impl<double>(h, side, W, m, q, w_is_complex != 0, out);
+  with_dtype(dtype, [&](auto t) { get_eofs_impl<decltype(t)>(h, side, W, m, q, w_is_complex != 0, out); });
   API_END(h)
 }
 
 int xmca_project(xmca_handle* h, int side, const void* V, int64_t N, int64_t m, int is_complex, void* U_out,
                  int* out_is_complex) {
   API_BEGIN(h)
-  XMCA_CHECK(side == 0 || side == 1, XMCA_ERR_INVALID, "project: side must be 0 or 1");
+  check_side("project", side);
   XMCA_CHECK(h->field_set[side], XMCA_ERR_STATE, "project: no field resident for this side");
   XMCA_CHECK(U_out && out_is_complex && N >= 1 && m >= 1, XMCA_ERR_INVALID, "project: need an N x m matrix of vectors");
   if (!V)
     XMCA_CHECK(h->solved && m <= h->res.n_vec && h->res.ldv[side] == N, XMCA_ERR_INVALID,
                "project: the resident vectors of the last solve do not have N rows and m modes");
-  if (h->dtype == XMCA_F32) project_impl<float>(h, side, V, N, m, is_complex != 0, U_out, out_is_complex);
-  else project_impl<double>(h, side, V, N, m, is_complex != 0, U_out, out_is_complex);
+  with_dtype(h->dtype, [&](auto t) { project_impl<decltype(t)>(h, side, V, N, m, is_complex != 0, U_out, out_is_complex); });
   API_END(h)
 }
 
@@ -1266,19 +1265,14 @@ int xmca_predict(xmca_handle* h, int side, const void* X, int64_t T_new, int64_t
   XMCA_CHECK(dtype == XMCA_F32 || dtype == XMCA_F64, XMCA_ERR_INVALID, "predict: dtype must be XMCA_F32 or XMCA_F64");
   const bool vt32 = !V && h->res.vt_f32[side];
   const bool vc = v_is_complex != 0, wc = w_is_complex != 0;
-  if (dtype == XMCA_F32) {
-    const float* x = static_cast<const float*>(X);
-    const float* mu = static_cast<const float*>(mean);
-    const float* sd = static_cast<const float*>(std);
-    if (vt32) predict_impl<float, float>(h, side, x, T_new, N_full, keep_idx, N_keep, mu, sd, V, vc, W, m, q, wc, out, out_is_complex);
-    else predict_impl<float, double>(h, side, x, T_new, N_full, keep_idx, N_keep, mu, sd, V, vc, W, m, q, wc, out, out_is_complex);
-  } else {
-    const double* x = static_cast<const double*>(X);
-    const double* mu = static_cast<const double*>(mean);
-    const double* sd = static_cast<const double*>(std);
-    if (vt32) predict_impl<double, float>(h, side, x, T_new, N_full, keep_idx, N_keep, mu, sd, V, vc, W, m, q, wc, out, out_is_complex);
-    else predict_impl<double, double>(h, side, x, T_new, N_full, keep_idx, N_keep, mu, sd, V, vc, W, m, q, wc, out, out_is_complex);
-  }
+  // 2 x 2: the data's element type TI (the ingest arithmetic) x the resident vectors' element type TP (the product)
+  with_dtype(dtype, [&](auto ti) {
+    using TI = decltype(ti);
+    with_dtype(vt32 ? XMCA_F32 : XMCA_F64, [&](auto tp) {
+      predict_impl<TI, decltype(tp)>(h, side, static_cast<const TI*>(X), T_new, N_full, keep_idx, N_keep, static_cast<const TI*>(mean),
+                                     static_cast<const TI*>(std), V, vc, W, m, q, wc, out, out_is_complex);
+    });
+  });
   API_END(h)
 }
 
@@ -1287,38 +1281,35 @@ int xmca_reconstruct(xmca_handle* h, int side, const double* B, int64_t T, int64
   API_BEGIN(h)
   check_transform(h, "reconstruct", side, V, m, keep_idx, N_keep, N_full);
   XMCA_CHECK(out && T >= 1 && (B || m == 0), XMCA_ERR_INVALID, "reconstruct: need a T x m coefficient matrix and an output");
-  if (m > 0 && !V && h->res.vt_f32[side])
-    reconstruct_impl<float>(h, side, B, T, m, b_is_complex != 0, V, v_is_complex != 0, keep_idx, N_keep, N_full, mean, std, out);
-  else
-    reconstruct_impl<double>(h, side, B, T, m, b_is_complex != 0, V, v_is_complex != 0, keep_idx, N_keep, N_full, mean, std, out);
+  // the product runs in the element type of the resident vectors it reads (float64 for host vectors)
+  with_dtype(m > 0 && !V && h->res.vt_f32[side] ? XMCA_F32 : XMCA_F64, [&](auto tp) {
+    reconstruct_impl<decltype(tp)>(h, side, B, T, m, b_is_complex != 0, V, v_is_complex != 0, keep_idx, N_keep, N_full, mean, std, out);
+  });
   API_END(h)
 }
 
 int xmca_center_field(xmca_handle* h, int side, double* mean_out, double* std_out, int64_t* n_nan_out) {
   API_BEGIN(h)
-  XMCA_CHECK(side == 0 || side == 1, XMCA_ERR_INVALID, "center_field: side must be 0 or 1");
+  check_side("center_field", side);
   XMCA_CHECK(h->field_set[side] && mean_out && std_out && n_nan_out, XMCA_ERR_STATE, "center_field: set the field first");
-  if (h->dtype == XMCA_F32) center_field_impl<float>(h, side, mean_out, std_out, n_nan_out);
-  else center_field_impl<double>(h, side, mean_out, std_out, n_nan_out);
+  with_dtype(h->dtype, [&](auto t) { center_field_impl<decltype(t)>(h, side, mean_out, std_out, n_nan_out); });
   API_END(h)
 }
 
 int xmca_compact_field(xmca_handle* h, int side, int* keep_out, int64_t* n_keep_out) {
   API_BEGIN(h)
-  XMCA_CHECK(side == 0 || side == 1, XMCA_ERR_INVALID, "compact_field: side must be 0 or 1");
+  check_side("compact_field", side);
   XMCA_CHECK(h->field_set[side] && keep_out && n_keep_out, XMCA_ERR_STATE, "compact_field: set the field first");
-  if (h->dtype == XMCA_F32) compact_field_impl<float>(h, side, keep_out, n_keep_out);
-  else compact_field_impl<double>(h, side, keep_out, n_keep_out);
+  with_dtype(h->dtype, [&](auto t) { compact_field_impl<decltype(t)>(h, side, keep_out, n_keep_out); });
   h->solved = false;
   API_END(h)
 }
 
 int xmca_scale_field(xmca_handle* h, int side, const void* w, int divide) {
   API_BEGIN(h)
-  XMCA_CHECK(side == 0 || side == 1, XMCA_ERR_INVALID, "scale_field: side must be 0 or 1");
+  check_side("scale_field", side);
   XMCA_CHECK(h->field_set[side] && w, XMCA_ERR_STATE, "scale_field: set the field first");
-  if (h->dtype == XMCA_F32) scale_field_impl<float>(h, side, w, divide);
-  else scale_field_impl<double>(h, side, w, divide);
+  with_dtype(h->dtype, [&](auto t) { scale_field_impl<decltype(t)>(h, side, w, divide); });
   h->solved = false;
   API_END(h)
 }
@@ -1327,13 +1318,11 @@ int xmca_get_field(xmca_handle* h, int side, void* out) {
   API_BEGIN(h)
   XMCA_CHECK((side == 0 || side == 1) && out, XMCA_ERR_INVALID, "get_field: bad arguments");
   XMCA_CHECK(h->field_set[side], XMCA_ERR_STATE, "get_field: no field resident for this side");
-  if (h->dtype == XMCA_F32) {
-    FieldData<float>& f = h->f32[side];
-    XMCA_HIP(hipMemcpyAsync(out, f.r(), sizeof(float) * (size_t)f.T * f.N, hipMemcpyDeviceToHost, h->st));
-  } else {
-    FieldData<double>& f = h->f64[side];
-    XMCA_HIP(hipMemcpyAsync(out, f.r(), sizeof(double) * (size_t)f.T * f.N, hipMemcpyDeviceToHost, h->st));
-  }
+  with_dtype(h->dtype, [&](auto t) {
+    using TI = decltype(t);
+    const FieldData<TI>& f = typed<TI>(h).f[side];
+    XMCA_HIP(hipMemcpyAsync(out, f.r(), sizeof(TI) * (size_t)f.T * f.N, hipMemcpyDeviceToHost, h->st));
+  });
   XMCA_HIP(hipStreamSynchronize(h->st));
   API_END(h)
 }
@@ -1341,35 +1330,21 @@ int xmca_get_field(xmca_handle* h, int side, void* out) {
 int xmca_bootstrap_begin(xmca_handle* h, int n_fields) {
   API_BEGIN(h)
   XMCA_CHECK(n_fields == 1 || n_fields == 2, XMCA_ERR_INVALID, "bootstrap: n_fields must be 1 or 2");
-  if (h->dtype == XMCA_F32) bootstrap_begin_impl<float>(h, n_fields);
-  else bootstrap_begin_impl<double>(h, n_fields);
-  API_END(h)
-}
-
-int xmca_bootstrap_run(xmca_handle* h, const double* hilbert_col, const int64_t* idx_left, const int64_t* idx_right, int rotated,
-                       int p, int power, double tol, double* spectrum_out, int* kept_out, int64_t n_out) {
-  API_BEGIN(h)
-  XMCA_CHECK(spectrum_out && kept_out && n_out >= 1, XMCA_ERR_INVALID, "bootstrap: output buffers missing");
-  XMCA_CHECK(!rotated || (p >= 2 && power >= 1), XMCA_ERR_INVALID, "bootstrap: rotation needs n_rot >= 2 and power >= 1");
-  if (h->dtype == XMCA_F32) bootstrap_run_impl<float>(h, hilbert_col, idx_left, idx_right, rotated, p, power, tol, spectrum_out, kept_out, n_out);
-  else bootstrap_run_impl<double>(h, hilbert_col, idx_left, idx_right, rotated, p, power, tol, spectrum_out, kept_out, n_out);
+  with_dtype(h->dtype, [&](auto t) { bootstrap_begin_impl<decltype(t)>(h, n_fields); });
   API_END(h)
 }
 
 int xmca_bootstrap_runs(xmca_handle* h, const double* hilbert_col, const int64_t* idx_left, const int64_t* idx_right, int64_t n_runs,
                         int rotated, int p, int power, double tol, double* spectra_out, int* kept_out, int64_t n_out) {
   API_BEGIN(h)
-  XMCA_CHECK(spectra_out && kept_out && n_out >= 1 && n_runs >= 0, XMCA_ERR_INVALID, "bootstrap: output buffers missing");
-  XMCA_CHECK(!rotated || (p >= 2 && power >= 1), XMCA_ERR_INVALID, "bootstrap: rotation needs n_rot >= 2 and power >= 1");
+  check_bootstrap_runs(spectra_out, kept_out, n_out, n_runs, rotated, p, power);
   XMCA_CHECK(h->boot_fields >= 1 && h->boot_T > 0, XMCA_ERR_STATE, "bootstrap: call xmca_bootstrap_begin first");
   ComplexOp hop;
   if (hilbert_col) hop = ComplexOp::circulant(hilbert_col, h->boot_T);
-  if (h->dtype == XMCA_F32)
-    bootstrap_runs_impl<float>(h, hilbert_col ? &hop : nullptr, idx_left, idx_right, n_runs, rotated, p, power, tol, spectra_out, kept_out,
-                               n_out);
-  else
-    bootstrap_runs_impl<double>(h, hilbert_col ? &hop : nullptr, idx_left, idx_right, n_runs, rotated, p, power, tol, spectra_out, kept_out,
-                                n_out);
+  with_dtype(h->dtype, [&](auto t) {
+    bootstrap_runs_impl<decltype(t)>(h, hilbert_col ? &hop : nullptr, idx_left, idx_right, n_runs, rotated, p, power, tol, spectra_out,
+                                     kept_out, n_out);
+  });
   h->tm.collect();
   API_END(h)
 }
@@ -1378,13 +1353,11 @@ int xmca_bootstrap_runs_extended(xmca_handle* h, const double* col3, const doubl
                                  const int64_t* idx_left, const int64_t* idx_right, int64_t n_runs, int rotated, int p, int power,
                                  double tol, double* spectra_out, int* kept_out, int64_t n_out) {
   API_BEGIN(h)
-  XMCA_CHECK(spectra_out && kept_out && n_out >= 1 && n_runs >= 0, XMCA_ERR_INVALID, "bootstrap: output buffers missing");
-  XMCA_CHECK(!rotated || (p >= 2 && power >= 1), XMCA_ERR_INVALID, "bootstrap: rotation needs n_rot >= 2 and power >= 1");
-  XMCA_CHECK(col3 && hbar && rank >= 0 && rank <= 16 && (rank == 0 || (U && W)), XMCA_ERR_INVALID,
-             "bootstrap: need col3, hbar and T x rank U, W (rank <= 16)");
+  check_bootstrap_runs(spectra_out, kept_out, n_out, n_runs, rotated, p, power);
+  check_extended_parts("bootstrap", col3, hbar, U, W, rank);
   XMCA_CHECK(h->boot_fields >= 1 && h->boot_T > 0, XMCA_ERR_STATE, "bootstrap: call xmca_bootstrap_begin first");
   XMCA_CHECK(h->dtype == XMCA_F64, XMCA_ERR_INVALID, "bootstrap: the extended operator needs float64 fields (the reference's replicates are float64)");
-  XMCA_CHECK(h->boot_T <= 46340, XMCA_ERR_UNSUPPORTED, "bootstrap: T x T operator too large");
+  check_operator_size("bootstrap", h->boot_T);
   const ComplexOp op = ComplexOp::extended(col3, hbar, U, W, rank, h->boot_T);
   bootstrap_runs_impl<double>(h, &op, idx_left, idx_right, n_runs, rotated, p, power, tol, spectra_out, kept_out, n_out);
   h->tm.collect();
@@ -1393,11 +1366,10 @@ int xmca_bootstrap_runs_extended(xmca_handle* h, const double* col3, const doubl
 
 int xmca_correlate(xmca_handle* h, int side, const double* Y, int64_t T, int64_t m, double* r_out) {
   API_BEGIN(h)
-  XMCA_CHECK(side == 0 || side == 1, XMCA_ERR_INVALID, "correlate: side must be 0 or 1");
+  check_side("correlate", side);
   XMCA_CHECK(h->field_set[side], XMCA_ERR_STATE, "correlate: no field resident for this side");
   XMCA_CHECK(Y && r_out && T >= 2 && m >= 1, XMCA_ERR_INVALID, "correlate: need a T x m matrix");
-  if (h->dtype == XMCA_F32) correlate_impl<float>(h, side, Y, T, m, r_out);
-  else correlate_impl<double>(h, side, Y, T, m, r_out);
+  with_dtype(h->dtype, [&](auto t) { correlate_impl<decltype(t)>(h, side, Y, T, m, r_out); });
   API_END(h)
 }
 
@@ -1447,33 +1419,10 @@ int xmca_rotate_solved(xmca_handle* h, int p, int power, double tol, int max_ite
   const SolveResult& r = h->res;
   XMCA_CHECK(p <= r.n_vec && r.ldv[0] > 0, XMCA_ERR_INVALID, "rotate: more modes requested than were back-projected");
   const bool cplx = r.cplx;
-  const int64_t Nl = r.ldv[0], Nr = r.ldv[1] > 0 ? r.ldv[1] : 0;
   Rotator rot(h->st, h->tm, h->gws, h->ews);
-  RotationDevice& d = h->rot;
-  rot.alloc(d, Nl + Nr, Nl, p, cplx);
   DevBuf<double> sigma_dev;
-  XMCA_HIP(hipMemcpyAsync(sigma_dev.ensure((size_t)p), r.sigma.data(), sizeof(double) * p, hipMemcpyHostToDevice, h->st));
-  const CPlanes& Vl = r.Vt[0];
-  const CPlanes& Vr = r.Vt[Nr > 0 ? 1 : 0];
   RotateResult rr;
-  // loadings of both fields stacked, V sqrt(sigma) (array.py:818-822), built where the vectors are
-  if (r.vt_f32[0]) {
-    // float32 model (one real field): the reference multiplies the float32 vectors by the float32 square roots of the float32
-    // singular values - a float32 product - and rotates that; the same roundings here, then float64 like the host path
-    XMCA_CHECK(!cplx && Nr == 0, XMCA_ERR_STATE, "rotate: float32-resident vectors are real and one-sided");
-    hipLaunchKernelGGL(rot_build_loadings_f32_kernel, ew_grid(Nl), dim3(EW_BLOCK), 0, h->st, r.Vt32[0].get(), Nl, Nl, sigma_dev.get(), p, d.A.r(),
-                       d.h.get());
-    rot.run<false>(d, power, tol, max_iter, rr, nullptr, false);
-  } else if (cplx) {
-    hipLaunchKernelGGL((rot_build_loadings_kernel<true>), ew_grid(Nl + Nr), dim3(EW_BLOCK), 0, h->st, Vl.r(), Vl.i(true), Nl, Nl,
-                       Vr.r(), Vr.i(true), Nr > 0 ? Nr : Nl, Nr, sigma_dev.get(), p, d.A.r(), d.A.i(true), d.h.get());
-    rot.run<true>(d, power, tol, max_iter, rr, nullptr, false);
-  } else {
-    hipLaunchKernelGGL((rot_build_loadings_kernel<false>), ew_grid(Nl + Nr), dim3(EW_BLOCK), 0, h->st, Vl.r(), (const double*)nullptr,
-                       Nl, Nl, Vr.r(), (const double*)nullptr, Nr > 0 ? Nr : Nl, Nr, sigma_dev.get(), p, d.A.r(), (double*)nullptr,
-                       d.h.get());
-    rot.run<false>(d, power, tol, max_iter, rr, nullptr, false);
-  }
+  rotate_resident(h, rot, h->rot, sigma_dev, r, r.ldv[0], r.ldv[1] > 0 ? r.ldv[1] : 0, p, power, tol, max_iter, rr);
   h->tm.collect();
   if (iters_out) *iters_out = rr.iters;
   check_rot(rr);
@@ -1488,13 +1437,11 @@ int xmca_rule_n(xmca_handle* h, int64_t T, int64_t Nx, int64_t Ny, int n_fields,
   XMCA_CHECK(n_fields == 1 || n_fields == 2, XMCA_ERR_INVALID, "rule_n: n_fields must be 1 or 2");
   XMCA_CHECK(T >= 2 && Nx >= 1 && (n_fields == 1 || Ny >= 1), XMCA_ERR_INVALID, "rule_n: bad field shape");
   XMCA_CHECK(run_end >= run_begin && spectra_out && kept_out, XMCA_ERR_INVALID, "rule_n: bad run range / outputs");
-  XMCA_CHECK(!rotated || (p >= 2 && power >= 1), XMCA_ERR_INVALID, "rule_n: bad rotation parameters");
-  if (dtype == XMCA_F32)
-    rule_n_impl<float>(h, T, Nx, Ny, n_fields, hilbert_col, rotated, p, power, tol, run_begin, run_end, seed, spectra_out,
-                       kept_out, n_out);
-  else
-    rule_n_impl<double>(h, T, Nx, Ny, n_fields, hilbert_col, rotated, p, power, tol, run_begin, run_end, seed, spectra_out,
-                        kept_out, n_out);
+  check_rotation_args("rule_n", "bad rotation parameters", rotated, p, power);
+  ComplexOp hop;
+  if (hilbert_col) hop = ComplexOp::circulant(hilbert_col, T);
+  const ReplicateSpec spec{T, Nx, Ny, n_fields, hilbert_col ? &hop : nullptr, rotated, p, power, tol};
+  with_dtype(dtype, [&](auto t) { rule_n_impl<decltype(t)>(h, spec, run_begin, run_end, seed, spectra_out, kept_out, n_out); });
   h->tm.collect();
   API_END(h)
 }
@@ -1504,18 +1451,7 @@ int xmca_rule_n(xmca_handle* h, int64_t T, int64_t Nx, int64_t Ny, int n_fields,
   if (!(c)) return XMCA_ERR_INVALID;                                   \
   try {                                                                \
     XMCA_HIP(hipSetDevice((c)->device));
-#define COMM_END(c)                                                    \
-  }                                                                    \
-  catch (const ::xmca::Error& e) {                                     \
-    (c)->err = e.what();                                               \
-    (void)hipGetLastError();                                           \
-    return e.code;                                                     \
-  }                                                                    \
-  catch (const std::exception& e) {                                    \
-    (c)->err = std::string("unexpected: ") + e.what();                 \
-    return XMCA_ERR_HIP;                                               \
-  }                                                                    \
-  return XMCA_OK;
+#define COMM_END(c) } XMCA_CATCH(c)
 
 int xmca_comm_unique_id(void* id_out) {
   if (!id_out) return XMCA_ERR_INVALID;
@@ -1777,24 +1713,21 @@ int xmca_gemm(xmca_handle* h, const void* A, int64_t lda, int a_kfast, const voi
   API_BEGIN(h)
   XMCA_CHECK(A && B && C && M > 0 && N > 0 && K >= 0, XMCA_ERR_INVALID, "gemm: bad arguments");
   const size_t na = (size_t)(a_kfast ? M : K) * lda, nb = (size_t)(b_nfast ? K : N) * ldb;
-  const size_t es = dtype == XMCA_F32 ? 4 : 8;
-  DevBuf<char> Ad, Bd;
-  DevBuf<double> Cd;
-  XMCA_HIP(hipMemcpyAsync(Ad.ensure(na * es), A, na * es, hipMemcpyHostToDevice, h->st));
-  XMCA_HIP(hipMemcpyAsync(Bd.ensure(nb * es), B, nb * es, hipMemcpyHostToDevice, h->st));
-  Cd.ensure((size_t)M * N);
-  XMCA_HIP(hipMemsetAsync(Cd.get(), 0, sizeof(double) * (size_t)M * N, h->st));
   GemmOpts o;
   o.a_kfast = a_kfast != 0; o.b_nfast = b_nfast != 0; o.alpha = alpha; o.upper_only = upper_only != 0; o.mirror = mirror;
   o.force_splits = splits;
-  if (dtype == XMCA_F32)
-    gemm<float, double>(h->st, h->gws, reinterpret_cast<const float*>(Ad.get()), lda, reinterpret_cast<const float*>(Bd.get()), ldb,
-                        Cd.get(), N, M, N, K, o);
-  else
-    gemm<double, double>(h->st, h->gws, reinterpret_cast<const double*>(Ad.get()), lda, reinterpret_cast<const double*>(Bd.get()),
-                         ldb, Cd.get(), N, M, N, K, o);
-  XMCA_HIP(hipMemcpyAsync(C, Cd.get(), sizeof(double) * (size_t)M * N, hipMemcpyDeviceToHost, h->st));
-  XMCA_HIP(hipStreamSynchronize(h->st));
+  with_dtype(dtype, [&](auto t) {
+    using TI = decltype(t);
+    DevBuf<TI> Ad, Bd;
+    DevBuf<double> Cd;
+    XMCA_HIP(hipMemcpyAsync(Ad.ensure(na), A, na * sizeof(TI), hipMemcpyHostToDevice, h->st));
+    XMCA_HIP(hipMemcpyAsync(Bd.ensure(nb), B, nb * sizeof(TI), hipMemcpyHostToDevice, h->st));
+    Cd.ensure((size_t)M * N);
+    XMCA_HIP(hipMemsetAsync(Cd.get(), 0, sizeof(double) * (size_t)M * N, h->st));
+    gemm<TI, double>(h->st, h->gws, Ad.get(), lda, Bd.get(), ldb, Cd.get(), N, M, N, K, o);
+    XMCA_HIP(hipMemcpyAsync(C, Cd.get(), sizeof(double) * (size_t)M * N, hipMemcpyDeviceToHost, h->st));
+    XMCA_HIP(hipStreamSynchronize(h->st));
+  });
   API_END(h)
 }
 
@@ -1862,8 +1795,8 @@ int xmca_eigh(xmca_handle* h, const double* A, int n, int is_complex, double* la
 int xmca_bench_gram(xmca_handle* h, int side, int reps, double* avg_ms, double* kernel_ms, double* flops) {
   API_BEGIN(h)
   XMCA_CHECK((side == 0 || side == 1) && h->field_set[side] && reps >= 1, XMCA_ERR_STATE, "bench_gram: field not set");
-  int64_t T, N;
-  if (h->dtype == XMCA_F32) { T = h->f32[side].T; N = h->f32[side].N; } else { T = h->f64[side].T; N = h->f64[side].N; }
+  int64_t T = 0, N = 0;
+  with_dtype(h->dtype, [&](auto t) { T = typed<decltype(t)>(h).f[side].T; N = typed<decltype(t)>(h).f[side].N; });
   DevBuf<double> G;
   G.ensure((size_t)T * T);
   std::vector<hipEvent_t> ev(2 * (size_t)reps + 2);
@@ -1871,10 +1804,11 @@ int xmca_bench_gram(xmca_handle* h, int side, int reps, double* avg_ms, double* 
   auto run = [&](hipEvent_t b, hipEvent_t e) {
     GemmOpts o;
     o.b_nfast = false; o.upper_only = true; o.mirror = 1; o.ev_begin = b; o.ev_end = e;
-    if (h->dtype == XMCA_F32)
-      gemm<float, double>(h->st, h->gws, h->f32[side].r(), N, h->f32[side].r(), N, G.get(), T, (int)T, (int)T, (int)N, o);
-    else
-      gemm<double, double>(h->st, h->gws, h->f64[side].r(), N, h->f64[side].r(), N, G.get(), T, (int)T, (int)T, (int)N, o);
+    with_dtype(h->dtype, [&](auto t) {
+      using TI = decltype(t);
+      const TI* x = typed<TI>(h).f[side].r();
+      gemm<TI, double>(h->st, h->gws, x, N, x, N, G.get(), T, (int)T, (int)T, (int)N, o);
+    });
   };
   run(nullptr, nullptr);   // warm-up
   XMCA_HIP(hipStreamSynchronize(h->st));
@@ -1901,8 +1835,7 @@ int xmca_bench_gemm(xmca_handle* h, int M, int N, int K, int dtype, int a_kfast,
                     int reps, double* avg_ms) {
   API_BEGIN(h)
   XMCA_CHECK(M > 0 && N > 0 && K > 0 && reps > 0 && avg_ms, XMCA_ERR_INVALID, "bench_gemm: bad arguments");
-  if (dtype == XMCA_F32) bench_gemm_impl<float>(h, M, N, K, a_kfast, b_nfast, upper_only, splits, reps, avg_ms);
-  else bench_gemm_impl<double>(h, M, N, K, a_kfast, b_nfast, upper_only, splits, reps, avg_ms);
+  with_dtype(dtype, [&](auto t) { bench_gemm_impl<decltype(t)>(h, M, N, K, a_kfast, b_nfast, upper_only, splits, reps, avg_ms); });
   API_END(h)
 }
 
