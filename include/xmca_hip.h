@@ -41,7 +41,7 @@ typedef struct xmca_handle xmca_handle;
 /* library / device management ------------------------------------------------------------------------- */
 const char* xmca_version(void);
 /* Number of this header's ABI (XMCA_ABI_VERSION): the binding refuses a library built from another revision. */
-#define XMCA_ABI_VERSION 12
+#define XMCA_ABI_VERSION 13
 int xmca_abi_version(void);
 int xmca_device_count(void);
 int xmca_create(int device, xmca_handle** out);
@@ -145,6 +145,31 @@ int xmca_reconstruct(xmca_handle* h, int side, const double* B, int64_t T, int64
  * The field is expected centered, as every caller has it: the one-pass variance loses about (mean / std)^2 eps otherwise.
  * p-values (scipy.stats.beta) stay with the caller. */
 int xmca_correlate(xmca_handle* h, int side, const double* Y, int64_t T, int64_t m, double* r_out);
+
+/* Two-sided p-values of Pearson correlations of n_obs samples under the exact null distribution (ABI 13): the
+ * `2 * scipy.stats.beta(n/2 - 1, n/2 - 1, loc=-1, scale=2).cdf(-abs(r))` of tools/array.py:86-88,
+ * p = 2 I_x(a, a) with a = n_obs / 2 - 1 and x = (1 - |r|) / 2, the regularised incomplete beta function by its continued fraction,
+ * one value per lane in float64 (csrc/kernels.h pearson_two_sided_p; accuracy: DESIGN.md 2).
+ *   r      `count` float64 correlations, host memory;  p_out  `count` float64, host memory
+ *   n_obs  3 <= n_obs <= 1 000 000: XMCA_ERR_INVALID below (the distribution does not exist), XMCA_ERR_UNSUPPORTED above
+ * NaN stays NaN; |r| >= 1, an ulp beyond included, is exactly 0; p <= 1; values below the normal range go quietly to a denormal or 0.
+ * The resident fields and vectors are not changed. */
+int xmca_pearson_pvalues(xmca_handle* h, const double* r, int64_t count, int64_t n_obs, double* p_out);
+/* The constant of a call of the kernel above, -ln a - ln B(a, a) for a = n_obs / 2 - 1, computed once on the host and passed to
+ * every lane (no handle, no device: exported for the host tests).  XMCA_ERR_INVALID outside 3 <= n_obs <= 1 000 000. */
+int xmca_pvalue_log_norm(int64_t n_obs, double* out);
+
+/* MCA.homogeneous_patterns / heterogeneous_patterns of one field in their final layout (xmca/array.py:1188-1261, ABI 13): the
+ * correlations of xmca_correlate (the same launches), rounded to `r_dtype`, their p-values as xmca_pearson_pvalues with n_obs = T
+ * computed from the ROUNDED r - the reference's p belongs to the r it returns - and both maps scattered to N_full x m row-major
+ * with NaN at the masked grid points.
+ *   Y         T x m row-major float64 (the real parts of the PCs), host memory; 3 <= T <= 1 000 000 (errors as above)
+ *   keep_idx  N increasing row indices (int64) below N_full, N the columns of the resident field: the grid points the model kept;
+ *             NULL: N_full = N, no masked points
+ *   r_out     N_full x m of `r_dtype` (XMCA_F32 / XMCA_F64);  p_out  N_full x m float64;  host memory
+ * A constant column gives NaN in both maps.  The resident fields and vectors are not changed. */
+int xmca_correlation_maps(xmca_handle* h, int side, const double* Y, int64_t T, int64_t m, const int64_t* keep_idx, int64_t N_full,
+                          int r_dtype, void* r_out, double* p_out);
 
 /* Constructor preprocessing on the device (xmca/array.py:199-215 `_set_field_means` / `_set_field_stds` / `_center`;
  * SURVEY 8f row 3): the field of `side` set with xmca_set_field (raw, uncentered) is centered in place, column by

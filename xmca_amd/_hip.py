@@ -48,6 +48,9 @@ SIGNATURES = {
     "xmca_bootstrap_runs_extended": (_c_int, [_vp, _vp, _vp, _vp, _vp, _c_int, _vp, _vp, _c_i64, _c_int, _c_int, _c_int, _c_dbl, _vp, _vp,
                                               _c_i64]),
     "xmca_correlate": (_c_int, [_vp, _c_int, _vp, _c_i64, _c_i64, _vp]),
+    "xmca_pearson_pvalues": (_c_int, [_vp, _vp, _c_i64, _c_i64, _vp]),
+    "xmca_pvalue_log_norm": (_c_int, [_c_i64, _dp]),
+    "xmca_correlation_maps": (_c_int, [_vp, _c_int, _vp, _c_i64, _c_i64, _vp, _c_i64, _c_int, _vp, _vp]),
     "xmca_project": (_c_int, [_vp, _c_int, _vp, _c_i64, _c_i64, _c_int, _vp, ctypes.POINTER(_c_int)]),
     "xmca_predict": (_c_int, [_vp, _c_int, _vp, _c_i64, _c_i64, _c_int, _vp, _c_i64, _vp, _vp, _vp, _c_int, _vp, _c_i64, _c_i64, _c_int,
                               _vp, ctypes.POINTER(_c_int)]),
@@ -92,7 +95,8 @@ def library_path():
     return _build.LIB
 
 
-ABI_VERSION = 12         # bumped whenever a signature of include/xmca_hip.h changes; checked against xmca_abi_version()
+PVALUE_MAX_OBS = 1000000     # largest n_obs of xmca_pearson_pvalues / xmca_correlation_maps (csrc/kernels.h)
+ABI_VERSION = 13         # bumped whenever a signature of include/xmca_hip.h changes; checked against xmca_abi_version()
 
 
 def load_library():
@@ -122,6 +126,15 @@ def load_library():
                           "`python -m xmca_amd.build --force`" % (path, have, ABI_VERSION))
     _lib = lib
     return lib
+
+
+def pvalue_log_norm(n_obs):
+    """-ln a - ln B(a, a) for a = n_obs / 2 - 1: the per-call constant of the p-value kernel (xmca_pvalue_log_norm; no device)."""
+    out = _c_dbl(0)
+    rc = load_library().xmca_pvalue_log_norm(int(n_obs), ctypes.byref(out))
+    if rc != 0:
+        raise ValueError("pvalue_log_norm: n_obs must be between 3 and 1 000 000")
+    return out.value
 
 
 class HipError(RuntimeError):
@@ -508,6 +521,27 @@ class Handle:
         r = np.empty((N, m), dtype=np.float64)
         self._check(self._lib.xmca_correlate(self._h, side, _ptr(Yd), T, m, _ptr(r)))
         return r
+
+    def pearson_pvalues(self, r, n_obs):
+        """Two-sided p-values of the correlations `r` of n_obs samples on the device (xmca_pearson_pvalues): float64, the shape of
+        `r`; tools/array.py:86-88.  n_obs < 3 raises ValueError (the null distribution does not exist)."""
+        rd = np.ascontiguousarray(r, dtype=np.float64)
+        p = np.empty(rd.shape, dtype=np.float64)
+        self._check(self._lib.xmca_pearson_pvalues(self._h, _ptr(rd), rd.size, int(n_obs), _ptr(p)))
+        return p
+
+    def correlation_maps(self, side, Y, keep_idx, N_full, r_dtype):
+        """(r, p), both N_full x m in their final layout: correlations of the resident field `side` with the columns of Y (T x m)
+        in `r_dtype`, their two-sided p-values (float64, from the rounded r), NaN at the rows not in keep_idx (None: every row
+        is a column of the field).  xmca_correlation_maps."""
+        Yd = np.ascontiguousarray(np.asarray(Y).real, dtype=np.float64)
+        T, m = Yd.shape
+        idx = None if keep_idx is None else np.ascontiguousarray(keep_idx, dtype=np.int64)
+        code = _np_dtype_code(r_dtype)
+        r = np.empty((N_full, m), dtype=_real_np(code))
+        p = np.empty((N_full, m), dtype=np.float64)
+        self._check(self._lib.xmca_correlation_maps(self._h, side, _ptr(Yd), T, m, _ptr(idx), int(N_full), code, _ptr(r), _ptr(p)))
+        return r, p
 
     # ---- rotation -----------------------------------------------------------------------------
     def rotate_loadings(self, L, n_left, power=1, tol=1e-8, max_iter=1000, varimax_only=False, want_B=False, gamma=1.0):

@@ -936,26 +936,34 @@ class MCA:
     def _correlation_maps(self, n, phase_shift, pair):
         """Pearson correlation of every grid point (real part of the field) with the PCs and its p-value
         (array.py:1188-1261, tools/array.py:76-88).  The correlations are one tall GEMM over the field resident on the
-        device (`xmca_correlate`) instead of the reference's (N + m)^2 `np.corrcoef` matrix; p-values on the host."""
-        import scipy.stats
+        device instead of the reference's (N + m)^2 `np.corrcoef` matrix; the p-values and the final layout (masked grid
+        points as NaN, modes last) come from the device as well (`xmca_correlation_maps`).  Fewer than 3 observations (the null
+        distribution does not exist: every p is NaN) and `_patterns_on_host` take the host route: `xmca_correlate`, then
+        `_two_sided_p` and the re-layout in numpy."""
         pcs = self._get_pcs(n=n, phase_shift=phase_shift)
         dev = self._device()
         if not self._owns_device_fields(dev):
             self._upload_serial += 1
             self._upload_fields(dev)
         n_obs = self._n_observations['left']
+        on_host = n_obs < 3 or n_obs > _hip.PVALUE_MAX_OBS or getattr(self, '_patterns_on_host', False)
         rvals, pvals = {}, {}
         for side, k in enumerate(self._keys):
             try:
                 y = pcs[pair[k]].real
             except KeyError:
                 raise KeyError('Key not found. Two fields needed for heterogenous maps.')
-            r = dev.correlate(side, y, self._fields_store[k].shape[1])
-            r = r.astype(np.result_type(self._fields_store[k].real.dtype, y.dtype), copy=False)
-            p = _two_sided_p(r, n_obs)
-            for src, dst in ((r, rvals), (p, pvals)):
-                full = self._with_nan_columns(k, src.T, (src.shape[1],)).T
-                dst[k] = full.reshape(self._fields_spatial_shape[k] + (src.shape[1],))
+            r_dtype = np.result_type(self._fields_store[k].real.dtype, y.dtype)
+            if on_host:
+                r = dev.correlate(side, y, self._fields_store[k].shape[1]).astype(r_dtype, copy=False)
+                p = _two_sided_p(r, n_obs)
+                r, p = (self._with_nan_columns(k, src.T, (src.shape[1],)).T for src in (r, p))
+            else:
+                mask = self._no_nan_index[k]
+                keep_idx = None if self._fields_store[k].shape[1] == mask.size else np.flatnonzero(mask)
+                r, p = dev.correlation_maps(side, y, keep_idx, mask.size, r_dtype)
+            rvals[k] = r.reshape(self._fields_spatial_shape[k] + (r.shape[1],))
+            pvals[k] = p.reshape(self._fields_spatial_shape[k] + (p.shape[1],))
         return rvals, pvals
 
     def homogeneous_patterns(self, n=None, phase_shift=0):

@@ -565,6 +565,84 @@ __global__ void pearson_finish_kernel(double* __restrict__ C, int64_t N, int m, 
   }
 }
 
+// Two-sided p-value of a Pearson correlation r of n_obs samples under the exact null distribution (tools/array.py:86-88):
+// p = 2 I_x(a, a) with a = n_obs / 2 - 1 > 0 and x = (1 - |r|) / 2, the regularised incomplete beta function
+//   I_x(a, a) = exp(a (ln x + ln(1 - x)) - ln a - ln B(a, a)) / cf(x),
+// cf the continued fraction of I_x (DLMF 8.17.22) evaluated by the modified Lentz recurrence.  a = b puts x in [0, 1/2], the
+// side on which the fraction converges, so there is no reflection.  x is formed from 1 - |r| (exact for |r| >= 1/2), never from
+// 1 - r^2.  log_norm = -ln a - ln B(a, a) is the same for every value of a call and comes from the host (pvalue_log_norm).
+// NaN stays NaN, |r| >= 1 is exactly 0, the result never exceeds 1, a prefactor below the normal range goes quietly to a
+// denormal or 0.  The cap bounds the loop: a float64 run on the host needed at most 10 / 16 / 67 / 133 / 476 steps (at r near 0) for
+// n_obs = 3 / 61 / 2920 / 20 000 / 10^6, and the entry points refuse an n_obs beyond PVALUE_MAX_OBS.
+constexpr int PVALUE_MAX_STEPS = 1024;
+constexpr int64_t PVALUE_MAX_OBS = 1000000;
+__host__ __device__ inline double pearson_two_sided_p(const double r, const double a, const double log_norm) {
+  if (r != r) return r;
+  const double x = 0.5 * (1.0 - fabs(r));
+  if (!(x > 0.0)) return 0.0;
+  const double tiny = 1e-300, eps = 4.0 * 2.220446049250313e-16;
+  const double a2 = a + a;
+  double c = 1.0, d = 1.0 - a2 * x / (a + 1.0);
+  if (fabs(d) < tiny) d = tiny;
+  d = 1.0 / d;
+  double h = d;
+  for (int m = 1; m <= PVALUE_MAX_STEPS; ++m) {
+    const double am = a + 2.0 * m;
+    double t = m * (a - m) * x / ((am - 1.0) * am);           // even step
+    d = 1.0 + t * d;
+    c = 1.0 + t / c;
+    if (fabs(d) < tiny) d = tiny;
+    if (fabs(c) < tiny) c = tiny;
+    d = 1.0 / d;
+    h *= d * c;
+    t = -(a + m) * (a2 + m) * x / (am * (am + 1.0));          // odd step
+    d = 1.0 + t * d;
+    c = 1.0 + t / c;
+    if (fabs(d) < tiny) d = tiny;
+    if (fabs(c) < tiny) c = tiny;
+    d = 1.0 / d;
+    const double del = d * c;
+    h *= del;
+    if (fabs(del - 1.0) <= eps) break;
+  }
+  const double p = 2.0 * exp(a * (log(x) + log1p(-x)) + log_norm) * h;
+  return p > 1.0 ? 1.0 : p;
+}
+
+// -ln a - ln B(a, a) = ln Gamma(2a) - 2 ln Gamma(a) - ln a for a = n_obs / 2 - 1 (host).  The three terms are about a ln a each
+// and cancel to about 2 a ln 2, so they are taken in the host's extended precision and rounded once.
+static inline double pvalue_log_norm(int64_t n_obs) {
+  const long double a = (long double)n_obs / 2 - 1;
+  return (double)(lgammal(2 * a) - 2 * lgammal(a) - logl(a));
+}
+
+// p[i] = pearson_two_sided_p(r[i])  (xmca_pearson_pvalues): one value per lane, lanes that converge early idle
+__global__ void pearson_pvalues_kernel(const double* __restrict__ r, int64_t n, double a, double log_norm, double* __restrict__ p) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    p[i] = pearson_two_sided_p(r[i], a, log_norm);
+}
+
+// Final layout of the correlation maps (xmca_correlation_maps): row j of the n_full x m outputs is row row_of[j] of the compact
+// correlations C (row_of == nullptr: j itself), NaN in both maps where row_of[j] < 0.  r is rounded to the returned type TR and
+// p computed from the rounded value, as the host route computes p from the r it returns.
+template <typename TR>
+__global__ void correlation_maps_kernel(const double* __restrict__ C, const int64_t* __restrict__ row_of, int64_t n_full, int m, double a,
+                                        double log_norm, TR* __restrict__ r_out, double* __restrict__ p_out) {
+  const int64_t total = n_full * m;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t j = i / m;
+    const int64_t c = row_of ? row_of[j] : j;
+    if (c < 0) {
+      r_out[i] = (TR)__builtin_nan("");
+      p_out[i] = __builtin_nan("");
+      continue;
+    }
+    const TR r = (TR)C[c * m + (i - j * m)];
+    r_out[i] = r;
+    p_out[i] = pearson_two_sided_p((double)r, a, log_norm);
+  }
+}
+
 // ------------------------------------------------------------------------------------------------
 // Philox4x32-10 counter-based generator (Salmon et al. 2011) -> standard normals (Box-Muller).
 // counter = (element pair index lo, hi, run, side), key = seed: the stream of a surrogate depends only on

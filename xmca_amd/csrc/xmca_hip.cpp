@@ -240,6 +240,13 @@ int64_t resident_T(xmca_handle* h) {
   return T;
 }
 
+// number of columns of the resident field of `side`
+int64_t resident_N(xmca_handle* h, int side) {
+  int64_t N = 0;
+  with_dtype(h->dtype, [&](auto t) { N = typed<decltype(t)>(h).f[side].N; });
+  return N;
+}
+
 template <typename TI>
 void set_field_impl(xmca_handle* h, int side, const void* re, const void* im, int64_t T, int64_t N, int location) {
   FieldData<TI>& f = typed<TI>(h).f[side];
@@ -656,13 +663,15 @@ void check_transform(xmca_handle* h, const char* what, int side, const void* V, 
                w + ": the resident vectors of the last solve do not have N_keep rows and m modes");
 }
 
-// r = corr(Re field columns, Y columns)  (see xmca_correlate)
+// C (N x m, device) = corr(Re field columns, Y columns): column moments, the tall GEMM X^T Y and pearson_finish_kernel; shared by
+// xmca_correlate and xmca_correlation_maps.  `what`: the entry point's prefix of the message.
 template <typename TI>
-void correlate_impl(xmca_handle* h, int side, const double* Y, int64_t T, int64_t m, double* r_out) {
+void correlate_device(xmca_handle* h, const char* what, int side, const double* Y, int64_t T, int64_t m, DevBuf<double>& C) {
   FieldData<TI>& f = typed<TI>(h).f[side];
-  XMCA_CHECK(f.T == T, XMCA_ERR_INVALID, "correlate: Y has " + std::to_string(T) + " rows, the field has " + std::to_string(f.T));
+  XMCA_CHECK(f.T == T, XMCA_ERR_INVALID,
+             std::string(what) + ": Y has " + std::to_string(T) + " rows, the field has " + std::to_string(f.T));
   const int64_t N = f.N;
-  DevBuf<double> yh, sx, qx, sy, qy, C;
+  DevBuf<double> yh, sx, qx, sy, qy;
   DevBuf<TI> yt;
   const size_t ny = (size_t)T * m;
   XMCA_HIP(hipMemcpyAsync(yh.ensure(ny), Y, sizeof(double) * ny, hipMemcpyHostToDevice, h->st));
@@ -681,7 +690,55 @@ void correlate_impl(xmca_handle* h, int side, const double* Y, int64_t T, int64_
                      sy.get(), qy.get());
   XMCA_HIP(hipGetLastError());
   h->tm.end();
-  XMCA_HIP(hipMemcpyAsync(r_out, C.get(), sizeof(double) * (size_t)N * m, hipMemcpyDeviceToHost, h->st));
+  XMCA_HIP(hipStreamSynchronize(h->st));        // (Y is the caller's; the temporaries go back to the pool)
+}
+
+// r = corr(Re field columns, Y columns)  (see xmca_correlate)
+template <typename TI>
+void correlate_impl(xmca_handle* h, int side, const double* Y, int64_t T, int64_t m, double* r_out) {
+  DevBuf<double> C;
+  correlate_device<TI>(h, "correlate", side, Y, T, m, C);
+  XMCA_HIP(hipMemcpyAsync(r_out, C.get(), sizeof(double) * (size_t)typed<TI>(h).f[side].N * m, hipMemcpyDeviceToHost, h->st));
+  XMCA_HIP(hipStreamSynchronize(h->st));
+}
+
+// p = 2 I_x(a, a) of `count` host values  (see xmca_pearson_pvalues)
+void pearson_pvalues_impl(xmca_handle* h, const double* r, int64_t count, int64_t n_obs, double* p_out) {
+  DevBuf<double> rd, pd;
+  XMCA_HIP(hipMemcpyAsync(rd.ensure((size_t)count), r, sizeof(double) * count, hipMemcpyHostToDevice, h->st));
+  h->tm.begin("pvalues");
+  hipLaunchKernelGGL(pearson_pvalues_kernel, ew_grid(count), dim3(EW_BLOCK), 0, h->st, rd.get(), count, 0.5 * (double)n_obs - 1.0,
+                     pvalue_log_norm(n_obs), pd.ensure((size_t)count));
+  XMCA_HIP(hipGetLastError());
+  h->tm.end();
+  XMCA_HIP(hipMemcpyAsync(p_out, pd.get(), sizeof(double) * count, hipMemcpyDeviceToHost, h->st));
+  XMCA_HIP(hipStreamSynchronize(h->st));
+}
+
+// r (TR) and p (float64) of one field in their final N_full x m layout  (see xmca_correlation_maps)
+template <typename TI, typename TR>
+void correlation_maps_impl(xmca_handle* h, int side, const double* Y, int64_t T, int64_t m, const int64_t* keep_idx, int64_t N_full,
+                           TR* r_out, double* p_out) {
+  DevBuf<double> C, pd;
+  DevBuf<TR> rd;
+  DevBuf<int64_t> row_of;
+  correlate_device<TI>(h, "correlation_maps", side, Y, T, m, C);
+  const int64_t N = typed<TI>(h).f[side].N;
+  if (keep_idx) {
+    std::vector<int64_t> inv((size_t)N_full, -1);
+    for (int64_t c = 0; c < N; ++c) inv[(size_t)keep_idx[c]] = c;
+    XMCA_HIP(hipMemcpyAsync(row_of.ensure((size_t)N_full), inv.data(), sizeof(int64_t) * N_full, hipMemcpyHostToDevice, h->st));
+    XMCA_HIP(hipStreamSynchronize(h->st));      // (inv is a host temporary)
+  }
+  const size_t total = (size_t)N_full * m;
+  h->tm.begin("correlation_maps");
+  hipLaunchKernelGGL((correlation_maps_kernel<TR>), ew_grid((int64_t)total), dim3(EW_BLOCK), 0, h->st, C.get(),
+                     keep_idx ? row_of.get() : nullptr, N_full, (int)m, 0.5 * (double)T - 1.0, pvalue_log_norm(T), rd.ensure(total),
+                     pd.ensure(total));
+  XMCA_HIP(hipGetLastError());
+  h->tm.end();
+  XMCA_HIP(hipMemcpyAsync(r_out, rd.get(), sizeof(TR) * total, hipMemcpyDeviceToHost, h->st));
+  XMCA_HIP(hipMemcpyAsync(p_out, pd.get(), sizeof(double) * total, hipMemcpyDeviceToHost, h->st));
   XMCA_HIP(hipStreamSynchronize(h->st));
 }
 
@@ -1370,6 +1427,46 @@ int xmca_correlate(xmca_handle* h, int side, const double* Y, int64_t T, int64_t
   XMCA_CHECK(h->field_set[side], XMCA_ERR_STATE, "correlate: no field resident for this side");
   XMCA_CHECK(Y && r_out && T >= 2 && m >= 1, XMCA_ERR_INVALID, "correlate: need a T x m matrix");
   with_dtype(h->dtype, [&](auto t) { correlate_impl<decltype(t)>(h, side, Y, T, m, r_out); });
+  API_END(h)
+}
+
+int xmca_pvalue_log_norm(int64_t n_obs, double* out) {
+  if (!out || n_obs < 3 || n_obs > PVALUE_MAX_OBS) return XMCA_ERR_INVALID;
+  *out = pvalue_log_norm(n_obs);
+  return XMCA_OK;
+}
+
+int xmca_pearson_pvalues(xmca_handle* h, const double* r, int64_t count, int64_t n_obs, double* p_out) {
+  API_BEGIN(h)
+  XMCA_CHECK(n_obs >= 3, XMCA_ERR_INVALID, "pearson_pvalues: the null distribution needs n_obs >= 3");
+  XMCA_CHECK(n_obs <= PVALUE_MAX_OBS, XMCA_ERR_UNSUPPORTED, "pearson_pvalues: n_obs above " + std::to_string(PVALUE_MAX_OBS));
+  XMCA_CHECK(count >= 0 && (count == 0 || (r && p_out)), XMCA_ERR_INVALID, "pearson_pvalues: need `count` values and an output");
+  if (count > 0) pearson_pvalues_impl(h, r, count, n_obs, p_out);
+  API_END(h)
+}
+
+int xmca_correlation_maps(xmca_handle* h, int side, const double* Y, int64_t T, int64_t m, const int64_t* keep_idx, int64_t N_full,
+                          int r_dtype, void* r_out, double* p_out) {
+  API_BEGIN(h)
+  check_side("correlation_maps", side);
+  XMCA_CHECK(h->field_set[side], XMCA_ERR_STATE, "correlation_maps: no field resident for this side");
+  XMCA_CHECK(Y && r_out && p_out && m >= 1 && m <= INT32_MAX, XMCA_ERR_INVALID, "correlation_maps: need a T x m matrix and two outputs");
+  XMCA_CHECK(T >= 3, XMCA_ERR_INVALID, "correlation_maps: the null distribution needs T >= 3");
+  XMCA_CHECK(T <= PVALUE_MAX_OBS, XMCA_ERR_UNSUPPORTED, "correlation_maps: T above " + std::to_string(PVALUE_MAX_OBS));
+  XMCA_CHECK(r_dtype == XMCA_F32 || r_dtype == XMCA_F64, XMCA_ERR_INVALID, "correlation_maps: r_dtype must be XMCA_F32 or XMCA_F64");
+  const int64_t N = resident_N(h, side);
+  XMCA_CHECK(N_full >= N && N_full <= INT32_MAX && (keep_idx || N_full == N), XMCA_ERR_INVALID,
+             "correlation_maps: N_full must be the field's " + std::to_string(N) + " columns, or more with keep_idx");
+  if (keep_idx) {
+    for (int64_t c = 0; c < N; ++c)
+      XMCA_CHECK(keep_idx[c] >= 0 && keep_idx[c] < N_full && (c == 0 || keep_idx[c] > keep_idx[c - 1]), XMCA_ERR_INVALID,
+                 "correlation_maps: keep_idx must be increasing row indices below N_full, one per column of the field");
+  }
+  with_dtype(h->dtype, [&](auto t) {
+    with_dtype(r_dtype, [&](auto tr) {
+      correlation_maps_impl<decltype(t), decltype(tr)>(h, side, Y, T, m, keep_idx, N_full, static_cast<decltype(tr)*>(r_out), p_out);
+    });
+  });
   API_END(h)
 }
 
