@@ -83,7 +83,10 @@ int xmca_complexify_extended(xmca_handle* h, const double* col3, const double* h
  *             (two float64 fields: the re-solve of weak modes - deflation / weak-block refinement, DESIGN.md 1 - covers the
  *             modes that get vectors; with 0 <= n_vec < rank the singular values beyond n_vec are those of the single solve,
  *             accurate to ~5e-14 (sigma_1 / sigma_i)^2 relative)
- *   rank_out  min(T, Nx, Ny)  (array.py:597) */
+ *   rank_out  min(T, Nx, Ny)  (array.py:597)
+ * A one-field solve may return with the back-projection of the modes >= 256 still in flight on a second stream of the handle;
+ * every entry point that reads those modes, touches the fields or solves again waits for it first (and reports its failure),
+ * so callers see complete results in any call order.  XMCA_DEFER_BACKPROJECT=0: everything is finished before xmca_solve returns. */
 int xmca_solve(xmca_handle* h, int n_fields, int64_t n_vec, int64_t* rank_out);
 
 /* MCA._singular_values (array.py:590): all `rank` singular values of A^H B / (T-1), descending, float64. */

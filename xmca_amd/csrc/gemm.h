@@ -650,6 +650,9 @@ struct GemmOpts {
   bool upper_only = false;
   int mirror = 0;
   int force_splits = 0;  // 0 = heuristic
+  int plan_rows = 0;     // > 0: this launch computes a block of rows of a product with plan_rows rows (a multiple of the row tile
+                         // apart from the last block): the k-slices are cut as for the whole product, so every element gets the
+                         // bits the single launch gives it (Solver::back_project: head and deferred tail)
   const GemmTileList* tiles = nullptr;   // block-sparse: only these tiles, each over its own contraction range (no upper_only / mirror)
   hipEvent_t ev_begin = nullptr, ev_end = nullptr;   // optional: recorded around the MFMA kernel launch alone
 };
@@ -762,7 +765,8 @@ void gemm(hipStream_t st, GemmWorkspace& ws, const TI* A, int64_t lda, const TI*
   const int64_t tiles = list ? list->n : o.upper_only ? (int64_t)tm * (tm + 1) / 2 : (int64_t)tm * tn;
   const int klen = list ? list->klen : K;
   const int nkt = ceil_div(klen, BK);
-  int splits = o.force_splits > 0 ? o.force_splits : gemm_choose_splits(tiles, nkt, ws.cus());
+  const int64_t tiles_plan = (o.plan_rows > 0 && !list && !o.upper_only) ? (int64_t)ceil_div(o.plan_rows, GEMM_BM) * tn : tiles;
+  int splits = o.force_splits > 0 ? o.force_splits : gemm_choose_splits(tiles_plan, nkt, ws.cus());
   if (WIDE) splits = std::max(splits, ceil_div(K, GEMM_SLICE_PRODUCTS));
   const int* map_dev = nullptr;
   if (list) {

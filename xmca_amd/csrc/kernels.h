@@ -356,13 +356,16 @@ __global__ __launch_bounds__(256) void row_scale_chunk_kernel(T* __restrict__ re
 }
 // rows <- conj?(rows) / ||row||: one workgroup per row, or - few long rows - one per chunk of a row
 template <typename T>
-static inline void normalize_rows(hipStream_t st, T* re, T* im, int64_t ld, int rows, int cols, int conj, double* norms_out) {
+static inline void normalize_rows(hipStream_t st, T* re, T* im, int64_t ld, int rows, int cols, int conj, double* norms_out,
+                                  DevBuf<double>* part_keep = nullptr) {
+  // part_keep: where the partial sums of the chunked form live when `st` is not the stream of the calling thread's pool
   if (rows <= 0) return;
   const int chunks = ceil_div(cols, ROWN_CHUNK);
   if (rows >= 256 || chunks < 4) {
     hipLaunchKernelGGL((normalize_rows_kernel<T>), dim3(rows), dim3(256), 0, st, re, im, ld, cols, conj, norms_out);
   } else {
-    DevBuf<double> part;       // (returned to the stream's pool: the kernels queued here are ahead of its next user)
+    DevBuf<double> part_here;  // (returned to the stream's pool: the kernels queued here are ahead of its next user)
+    DevBuf<double>& part = part_keep ? *part_keep : part_here;
     part.ensure((size_t)rows * chunks);
     hipLaunchKernelGGL((row_sumsq_chunk_kernel<T>), dim3(chunks, rows), dim3(256), 0, st, (const T*)re, (const T*)im, ld, cols, part.get());
     hipLaunchKernelGGL((row_scale_chunk_kernel<T>), dim3(chunks, rows), dim3(256), 0, st, re, im, ld, cols, conj, (const double*)part.get(), norms_out);

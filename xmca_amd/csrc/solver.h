@@ -55,6 +55,11 @@ struct StageTimer {
     pending.clear();
   }
   void reset() { collect(); ms.clear(); order.clear(); }
+  void add(const std::string& name, double t) {      // time measured elsewhere (the deferred tail of the back-projection)
+    if (!enabled) return;
+    if (!ms.count(name)) order.push_back(name);
+    ms[name] += t;
+  }
 };
 
 // complex matrix as two f64 planes on the device (im.p == nullptr for real data)
@@ -120,6 +125,129 @@ struct SolveResult {
 };
 
 // ---------------------------------------------------------------------------------------------------
+// Deferred tail of the back-projection.  xmca_solve on one field finishes the first `head` modes and leaves
+// the product for the modes behind them in flight on a second stream: rotate(n_rot) reads the leading modes only, and its
+// Varimax loop is one workgroup that would otherwise run on an empty chip behind a GEMM it does not depend on.  Every entry
+// point of the C ABI joins first (xmca_hip.cpp join_tail) except the few that read no mode >= head.
+// The handle's pool is ordered by ONE stream: what the tail allocates (split-K slabs, tickets, tile maps, partial sums) is
+// its own, and the pool blocks it reads (eigenvector planes, their narrowed copies, the row scales) are kept here until the
+// join.
+// ---------------------------------------------------------------------------------------------------
+struct DeferredTail {
+  hipStream_t stream = nullptr;
+  hipEvent_t ev_fork = nullptr, ev_begin = nullptr, ev_done = nullptr;
+  GemmWorkspace gws;
+  DevBuf<double> part;                 // normalize_rows, chunked form
+  struct Kept { virtual ~Kept() = default; };
+  template <typename T>
+  struct KeptBuf : Kept {
+    DevBuf<T> b;
+    explicit KeptBuf(DevBuf<T>&& x) : b(std::move(x)) {}
+  };
+  std::vector<std::unique_ptr<Kept>> kept;
+  template <typename T>
+  void keep(DevBuf<T>& b) {
+    if (b.get()) kept.push_back(std::make_unique<KeptBuf<T>>(std::move(b)));
+  }
+  bool pending = false;
+  int head = 0;                        // modes [0, head) of the pending result are complete
+  int err_code = XMCA_OK;              // a failure while the tail was queued: thrown at the join
+  std::string err;
+  int calls = 0;
+
+  static bool enabled() {              // XMCA_DEFER_BACKPROJECT=0: the single launch
+    static const bool on = [] { const char* e = std::getenv("XMCA_DEFER_BACKPROJECT"); return !(e && e[0] == '0'); }();
+    return on;
+  }
+  // Rows of the head: two row tiles of the GEMM.  Anything up to one workgroup per CU costs the same time (256 rows x 10 000
+  // columns are 158 of 256), and the readers that do not join - the loadings of a rotation: at most ROT_MOMENT_PMAX = 12
+  // modes on the route that skips the join - need far fewer.  XMCA_DEFER_HEAD=<rows> (tests: small models), rounded up to tiles.
+  static int head_rows() {
+    static const int rows = [] {
+      const char* e = std::getenv("XMCA_DEFER_HEAD");
+      const int r = e ? std::atoi(e) : 256;
+      return std::max(1, ceil_div(r, GEMM_BM)) * GEMM_BM;
+    }();
+    return rows;
+  }
+  // Called once per xmca_solve, before anything is queued.  As for the eigensolver's second stream (TrdVecWorkspace::count_call):
+  // a stream costs ~10 ms to make, so the first solve of a handle stays serial, and it is made with every CU claimed at the
+  // gate of the persistent kernels.
+  void count_call() {
+    if (stream || !enabled() || in_surrogate_lanes() || ++calls < 2) return;
+    PersistGate& gate = persist_gate();
+    PersistGate::Claim alone(gate, gate.n_cus);
+    hipStream_t s = nullptr;
+    // The tail's stream leaves a few CUs alone: a CU mask on its queue with the last 16 bits clear.  The kernel driver deals the
+    // bits of a queue's mask round-robin to the XCDs (amdkfd, mqd_symmetrically_map_cu_mask: XCD x takes the bits x, x + 8, ...),
+    // so 16 bits are two CUs of each; the measurements fit (8 bits, one CU per XCD, do not suffice; 32 measure like 16).
+    // Without it the tail's workgroups hold every slot of the chip for ~0.6 ms each and the seven small kernels in front of the
+    // Varimax loop wait for slots one after the other (measured: 1.9 ms instead of 0.1 ms, and the loop's workgroup shares its
+    // CU's matrix pipe: 3.4 ms instead of 2.8 ms).  The price: a tail nobody overlaps with runs on 240 CUs.
+    // XMCA_DEFER_RESERVE_CUS=<n> (0: no mask).  A device whose CU count is not a multiple of 32 (partitioned, CU-masked from
+    // outside) gets no mask and keeps little of the gain: XMCA_TRACE=solve says which stream was made.
+    // The masked stream has default flags (the call takes none), the plain one is non-blocking: the masked one also orders
+    // against work on the legacy default stream of the process.  The library queues nothing there; a caller who does (torch's
+    // default stream) delays the tail by that work, no more.
+    static const int reserve = [] { const char* e = std::getenv("XMCA_DEFER_RESERVE_CUS"); return e ? std::atoi(e) : 16; }();
+    const int n_cus = gate.n_cus;
+    if (reserve > 0 && reserve < n_cus && n_cus % 32 == 0) {
+      std::vector<uint32_t> mask((size_t)n_cus / 32, 0xffffffffu);
+      for (int b = n_cus - reserve; b < n_cus; ++b) mask[(size_t)b / 32] &= ~(1u << (b % 32));
+      if (hipExtStreamCreateWithCUMask(&s, (uint32_t)mask.size(), mask.data()) != hipSuccess) { (void)hipGetLastError(); s = nullptr; }
+    }
+    const bool masked = s != nullptr;
+    if (!s) XMCA_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    if (xmca_trace("solve"))
+      std::fprintf(stderr, "[xmca solve] stream of the deferred back-projection: %s (%d CUs)\n",
+                   masked ? "CU mask, the last CUs left free" : "no CU mask", masked ? reserve : 0);
+    XMCA_HIP(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
+    XMCA_HIP(hipEventCreate(&ev_begin));
+    XMCA_HIP(hipEventCreate(&ev_done));
+    stream = s;
+  }
+  bool usable() const { return stream && enabled() && !pending && !in_surrogate_lanes(); }
+  // The tail's own device memory (not the pool's: xmca_pool_bytes does not count it); only with no tail pending (xmca_trim_pool)
+  void trim() {
+    gws.slabs.release();
+    gws.counters.release();
+    gws.counters_ready = 0;
+    part.release();
+  }
+  // Waits for the tail, gives back what it read and returns its device time (ms); throws what went wrong with it.
+  double join() {
+    if (!pending) return 0.0;
+    pending = false;
+    const hipError_t e = hipStreamSynchronize(stream);
+    float ms = 0.f;
+    if (e == hipSuccess && err_code == XMCA_OK) (void)hipEventElapsedTime(&ms, ev_begin, ev_done);
+    kept.clear();
+    if (err_code != XMCA_OK) {
+      const int code = err_code;
+      err_code = XMCA_OK;
+      throw Error(code, err);
+    }
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      throw Error(XMCA_ERR_HIP, std::string("deferred back-projection: ") + hipGetErrorString(e));
+    }
+    return (double)ms;
+  }
+  ~DeferredTail() {
+    if (!stream) return;
+    (void)hipStreamSynchronize(stream);
+    kept.clear();
+    (void)hipEventDestroy(ev_fork);
+    (void)hipEventDestroy(ev_begin);
+    (void)hipEventDestroy(ev_done);
+    (void)hipStreamDestroy(stream);
+  }
+  DeferredTail() = default;
+  DeferredTail(const DeferredTail&) = delete;
+  DeferredTail& operator=(const DeferredTail&) = delete;
+};
+
+// ---------------------------------------------------------------------------------------------------
 // solve
 // ---------------------------------------------------------------------------------------------------
 template <typename TI>
@@ -130,6 +258,7 @@ class Solver {
   EvdWorkspace& ews;
   StageTimer& tm;
   bool f32_vectors = false;    // xmca_solve on float32 fields: vectors of the one-field dual route stay float32 (SolveResult::Vt32)
+  DeferredTail* defer = nullptr;   // xmca_solve only: where the one-field dual route may leave the tail of its back-projection
   Solver(hipStream_t s, GemmWorkspace& g, EvdWorkspace& e, StageTimer& t) : st(s), gws(g), ews(e), tm(t) {}
 
   // per-field reduction: eigen-decomposition of the T x T Gram matrix when N > T
@@ -183,52 +312,95 @@ class Solver {
   // beyond n_known (null modes: their norm is rounding noise) are normalised by what they are.
   // `Vt32` (float32 fields, real): the result is written in float32 by the GEMM's epilogue - the reference's `_V` has the
   // input's dtype (array.py:584), and at C5 the float64 result is a 10 GB store against 5 GB.
+  // `tail` (the one-field route of xmca_solve, DeferredTail): only the leading modes are finished before this returns; the rest
+  // is queued on the tail's stream and joined by the next reader.  Both launches cut the contraction as the single launch
+  // does (GemmOpts::plan_rows) and every row is scaled / normalised on its own: the same bits either way.  `Ykeep`: the owner
+  // of Yr / Yi, which then has to outlive the caller's scope.
   void back_project(const FieldData<TI>& f, bool cplx, const double* Yr, const double* Yi, int m, CPlanes& Vt,
-                    const double* row_norm = nullptr, int n_known = 0, DevBuf<float>* Vt32 = nullptr) {
+                    const double* row_norm = nullptr, int n_known = 0, DevBuf<float>* Vt32 = nullptr, DeferredTail* tail = nullptr,
+                    CPlanes* Ykeep = nullptr) {
     const int T = (int)f.T;
     Narrow<TI> y;
     y.from(st, Yr, Yi, (int64_t)m * T);
     DevBuf<double> inv_dev;
     std::vector<double> inv_host;
     if (!row_norm) n_known = 0;
-    if constexpr (std::is_same<TI, float>::value) {
-      if (Vt32 && !cplx) {
-        Vt.re.release();                   // (the float64 planes of an earlier model are not part of this result)
-        Vt.im.release();
-        float* V = Vt32->ensure((size_t)m * f.N);
-        GemmOpts o;
-        o.a_kfast = true; o.b_nfast = true;
-        if (n_known > 0) {
-          inv_host.assign((size_t)m, 1.0);
-          for (int k = 0; k < n_known; ++k) inv_host[(size_t)k] = 1.0 / row_norm[k];
-          XMCA_HIP(hipMemcpyAsync(inv_dev.ensure((size_t)m), inv_host.data(), sizeof(double) * m, hipMemcpyHostToDevice, st));
-          o.row_scale = inv_dev.get();
-        }
-        gemm<float, float>(st, gws, y.r, T, f.r(), f.N, V, f.N, m, (int)f.N, T, o);
-        if (n_known < m)
-          normalize_rows<float>(st, V + (int64_t)n_known * f.N, nullptr, f.N, m - n_known, (int)f.N, 0, nullptr);
-        XMCA_HIP(hipGetLastError());
-        XMCA_HIP(hipStreamSynchronize(st));
-        return;
-      }
+    const bool v32 = std::is_same<TI, float>::value && Vt32 && !cplx;
+    float* V32 = nullptr;
+    if (v32) {
+      Vt.re.release();                   // (the float64 planes of an earlier model are not part of this result)
+      Vt.im.release();
+      V32 = Vt32->ensure((size_t)m * f.N);
+    } else {
+      Vt.ensure((size_t)m * f.N, cplx);
     }
-    Vt.ensure((size_t)m * f.N, cplx);
     if (n_known > 0) {
       inv_host.assign((size_t)m, 1.0);
       for (int k = 0; k < n_known; ++k) inv_host[(size_t)k] = 1.0 / row_norm[k];
       XMCA_HIP(hipMemcpyAsync(inv_dev.ensure((size_t)m), inv_host.data(), sizeof(double) * m, hipMemcpyHostToDevice, st));
-      // conj(Yh X~) = conj(Yh) conj(X~)
-      cgemm<TI>(st, gws, y.r, y.i, T, true, true, f.r(), f.i(), f.N, true, true, Vt.r(), Vt.i(cplx), f.N, m, (int)f.N, T, 1.0,
-                inv_dev.get(), nullptr, false);
-      if (n_known < m)
-        normalize_rows<double>(st, Vt.r() + (int64_t)n_known * f.N, cplx ? Vt.i(cplx) + (int64_t)n_known * f.N : nullptr, f.N, m - n_known,
-                               (int)f.N, 0, nullptr);
-    } else {
-      cgemm<TI>(st, gws, y.r, y.i, T, true, false, f.r(), f.i(), f.N, true, false, Vt.r(), Vt.i(cplx), f.N, m, (int)f.N, T, 1.0,
-                nullptr, nullptr, false);
-      normalize_rows<double>(st, Vt.r(), Vt.i(cplx), f.N, m, (int)f.N, 1, nullptr);
     }
-    XMCA_HIP(hipGetLastError());
+    // rows [r0, r1) of the product on stream `s`
+    auto rows = [&](hipStream_t s, GemmWorkspace& g, int r0, int r1, DevBuf<double>* part) {
+      const int nr = r1 - r0, N = (int)f.N;
+      const int64_t oy = (int64_t)r0 * T, ov = (int64_t)r0 * f.N;
+      const int n0 = std::max(n_known, r0);        // rows from here on are normalised by what they are
+      if (v32) {
+        if constexpr (std::is_same<TI, float>::value) {
+          GemmOpts o;
+          o.a_kfast = true; o.b_nfast = true;
+          o.plan_rows = m;
+          if (n_known > 0) o.row_scale = inv_dev.get() + r0;
+          gemm<float, float>(s, g, y.r + oy, T, f.r(), f.N, V32 + ov, f.N, nr, N, T, o);
+          if (n0 < r1) normalize_rows<float>(s, V32 + (int64_t)n0 * f.N, nullptr, f.N, r1 - n0, N, 0, nullptr, part);
+        }
+      } else if (n_known > 0) {
+        // conj(Yh X~) = conj(Yh) conj(X~)
+        cgemm<TI>(s, g, y.r + oy, y.i ? y.i + oy : nullptr, T, true, true, f.r(), f.i(), f.N, true, true, Vt.r() + ov,
+                  cplx ? Vt.i(cplx) + ov : nullptr, f.N, nr, N, T, 1.0, inv_dev.get() + r0, nullptr, false, 0.0, nullptr, m);
+        if (n0 < r1)
+          normalize_rows<double>(s, Vt.r() + (int64_t)n0 * f.N, cplx ? Vt.i(cplx) + (int64_t)n0 * f.N : nullptr, f.N, r1 - n0, N, 0, nullptr,
+                                 part);
+      } else {
+        cgemm<TI>(s, g, y.r + oy, y.i ? y.i + oy : nullptr, T, true, false, f.r(), f.i(), f.N, true, false, Vt.r() + ov,
+                  cplx ? Vt.i(cplx) + ov : nullptr, f.N, nr, N, T, 1.0, nullptr, nullptr, false, 0.0, nullptr, m);
+        normalize_rows<double>(s, Vt.r() + ov, cplx ? Vt.i(cplx) + ov : nullptr, f.N, nr, N, 1, nullptr, part);
+      }
+      XMCA_HIP(hipGetLastError());
+    };
+    // The head: as many leading modes as the readers that do not join may touch.  Deferring needs every head row to be scaled
+    // in the epilogue (n_known >= H: the rows normalised afterwards, and their number - which selects the form of
+    // normalize_rows - are then the single launch's), a tail at least as long as the head, and a field the handle owns (an
+    // adopted device pointer is the caller's to overwrite as soon as solve has returned).
+    int H = m;
+    if (tail && tail->usable() && !f.ext_re && !f.ext_im) {
+      const int h0 = DeferredTail::head_rows();
+      if (n_known >= h0 && m - h0 >= h0) H = h0;
+    }
+    rows(st, gws, 0, H, nullptr);
+    if (H < m) {
+      static const bool trace = xmca_trace("solve");
+      if (trace) std::fprintf(stderr, "[xmca solve] back-projection: modes [%d, %d) deferred to the second stream\n", H, m);
+      tail->head = H;
+      tail->pending = true;
+      try {
+        // (behind the head: forked in front of it, the tail's workgroups share the head's CUs and the rotation starts later - measured)
+        XMCA_HIP(hipEventRecord(tail->ev_fork, st));
+        PoolScope outside(nullptr);        // the handle's pool is ordered by `st` alone: nothing of the tail comes from it
+        XMCA_HIP(hipStreamWaitEvent(tail->stream, tail->ev_fork, 0));
+        XMCA_HIP(hipEventRecord(tail->ev_begin, tail->stream));
+        rows(tail->stream, tail->gws, H, m, &tail->part);
+        XMCA_HIP(hipEventRecord(tail->ev_done, tail->stream));
+      } catch (const Error& e) {           // surfaces where the tail is joined
+        (void)hipGetLastError();
+        tail->err_code = e.code;
+        tail->err = e.what();
+      }
+      // what the tail reads lives until the join (blocks of the handle's pool: they go back there behind the tail)
+      tail->keep(y.re);
+      tail->keep(y.im);
+      tail->keep(inv_dev);
+      if (Ykeep) { tail->keep(Ykeep->re); tail->keep(Ykeep->im); }
+    }
     XMCA_HIP(hipStreamSynchronize(st));   // `y` temporaries are released on return
   }
 
@@ -415,7 +587,7 @@ class Solver {
           while (known < m && Ra.lam[(size_t)known] > cut) { nrm[(size_t)known] = std::sqrt(Ra.lam[(size_t)known]); ++known; }
           const bool v32 = f32_vectors && std::is_same<TI, float>::value && !cplx;
           out.vt_f32[0] = v32;
-          back_project(A, cplx, Ra.Z.r(), Ra.Z.i(cplx), m, out.Vt[0], nrm.data(), known, v32 ? &out.Vt32[0] : nullptr);
+          back_project(A, cplx, Ra.Z.r(), Ra.Z.i(cplx), m, out.Vt[0], nrm.data(), known, v32 ? &out.Vt32[0] : nullptr, defer, &Ra.Z);
         }
         tm.end();
       } else {

@@ -63,6 +63,7 @@ struct xmca_handle {
   bool field_set[2] = {false, false};
   SolveResult res;
   bool solved = false;
+  DeferredTail tail;                     // modes >= tail.head of `res` may still be in flight (join_tail)
   bool op_pending = false;               // complexify requested; carried out (or folded into the solve) lazily
   ComplexOp op;                          // ... with this operator
   RotationDevice rot;
@@ -84,11 +85,29 @@ struct xmca_handle {
     return XMCA_ERR_HIP;                                               \
   }                                                                    \
   return XMCA_OK;
-#define API_BEGIN(h)                                                   \
+// xmca_solve may return with the back-projection of the modes >= tail.head in flight on the tail's stream (solver.h
+// DeferredTail).  Whoever reads those modes, changes what the tail reads (the fields) or starts the next solve waits here first;
+// a failure of the tail surfaces here, and the result is then no result.
+static void join_tail(xmca_handle* h) {
+  if (!h->tail.pending) return;
+  try {
+    h->tm.add("backproject", h->tail.join());
+  } catch (...) {
+    h->solved = false;
+    throw;
+  }
+}
+
+// Start of an entry point's try block.  API_BEGIN joins the deferred tail: an entry point joins unless it says otherwise.
+// API_BEGIN_NO_JOIN is for those that provably read no mode >= tail.head, no field and nothing the tail's stream touches.
+#define API_BEGIN_NO_JOIN(h)                                           \
   if (!(h)) return XMCA_ERR_INVALID;                                   \
   try {                                                                \
     ::xmca::PoolScope _pool_scope(&(h)->pool);                         \
     XMCA_HIP(hipSetDevice((h)->device));
+#define API_BEGIN(h)                                                   \
+  API_BEGIN_NO_JOIN(h)                                                 \
+    join_tail(h);
 #define API_END(h) } XMCA_CATCH(h)
 
 extern "C" {
@@ -139,6 +158,7 @@ void xmca_destroy(xmca_handle* h) {
   for (xmca_handle* lane : h->lanes) xmca_destroy(lane);
   h->lanes.clear();
   (void)hipSetDevice(h->device);
+  try { join_tail(h); } catch (...) {}
   (void)hipStreamSynchronize(h->st);
   try { h->tm.reset(); } catch (...) {}
   (void)hipStreamDestroy(h->st);
@@ -335,6 +355,10 @@ void solve_impl(xmca_handle* h, int n_fields, int64_t n_vec) {
   if (n_fields == 2) XMCA_CHECK(f[1].has_im == cplx, XMCA_ERR_INVALID, "solve: both fields must be real or both complex");
   Solver<TI> s(h->st, h->gws, h->ews, h->tm);
   s.f32_vectors = true;          // (only the one-field dual route of a real float32 field uses it)
+  if (n_fields == 1) {           // ... and only it may leave the tail of its back-projection in flight
+    h->tail.count_call();
+    s.defer = &h->tail;
+  }
   s.solve(f, n_fields, cplx, (int)n_vec, h->res);
 }
 
@@ -1254,7 +1278,7 @@ int xmca_solve(xmca_handle* h, int n_fields, int64_t n_vec, int64_t* rank_out) {
 }
 
 int xmca_get_singular_values(xmca_handle* h, double* out, int64_t n) {
-  API_BEGIN(h)
+  API_BEGIN_NO_JOIN(h)               // (host values, final when solve returned)
   XMCA_CHECK(h->solved, XMCA_ERR_STATE, "singular values requested before solve");
   XMCA_CHECK(out && n >= 0 && n <= h->res.rank, XMCA_ERR_INVALID, "get_singular_values: bad size");
   std::memcpy(out, h->res.sigma.data(), sizeof(double) * (size_t)n);
@@ -1280,7 +1304,8 @@ int xmca_get_solve_info(xmca_handle* h, int* info, int n) {
 }
 
 int xmca_get_vectors(xmca_handle* h, int side, void* out, int64_t n_modes, int dtype) {
-  API_BEGIN(h)
+  API_BEGIN_NO_JOIN(h)
+  if (n_modes > h->tail.head) join_tail(h);       // (the modes of the head were complete when solve returned)
   XMCA_CHECK(h->solved, XMCA_ERR_STATE, "vectors requested before solve");
   check_side("get_vectors", side);
   XMCA_CHECK(out && n_modes >= 0 && n_modes <= h->res.n_vec && h->res.ldv[side] > 0, XMCA_ERR_INVALID,
@@ -1473,7 +1498,11 @@ int xmca_correlation_maps(xmca_handle* h, int side, const double* Y, int64_t T, 
 int xmca_rotate_loadings(xmca_handle* h, const double* L, int64_t N, int64_t n_left, int p, int is_complex, int power,
                          double tol, int max_iter, int varimax_only, double gamma, double* B_out, double* R_out, double* Phi_out,
                          double* norm_left, double* norm_right, int* iters_out) {
-  API_BEGIN(h)
+  API_BEGIN_NO_JOIN(h)
+  // The loadings come from the host and the rotation reads nothing of the solve.  On the fourth-moment route (real, few modes) its
+  // loop is ONE workgroup: it runs beside the tail.  Every other route joins: a persistent grid, whose workgroups wait for each
+  // other, must not queue for CUs behind the tail's workgroups, and the GEMM-based route would share the chip with it for nothing.
+  if (is_complex != 0 || p > ROT_MOMENT_PMAX) join_tail(h);
   XMCA_CHECK(L && N >= 1 && p >= 2, XMCA_ERR_INVALID, "rotate: need N x p loadings with p >= 2");
   XMCA_CHECK(power >= 1, XMCA_ERR_INVALID, "rotate: `power` must be >= 1");
   XMCA_CHECK(n_left >= 0 && n_left <= N && max_iter >= 1, XMCA_ERR_INVALID, "rotate: bad n_left / max_iter");
@@ -1725,7 +1754,10 @@ int xmca_get_reduction_info(xmca_handle* h, char* out, int out_len) {
 
 int xmca_get_timings(xmca_handle* h, char* names, int names_len, double* ms, int max_n) {
   if (!h) return XMCA_ERR_INVALID;
-  try { h->tm.collect(); } catch (...) { return XMCA_ERR_HIP; }
+  try {                              // (the tail's time belongs to the step that queued it; its failure is the next reader's to report)
+    if (h->tail.pending && h->tail.err_code == XMCA_OK) { (void)hipSetDevice(h->device); join_tail(h); }
+    h->tm.collect();
+  } catch (...) { return XMCA_ERR_HIP; }
   std::string joined;
   int n = 0;
   for (const auto& name : h->tm.order) {
@@ -1759,7 +1791,10 @@ int xmca_get_timings(xmca_handle* h, char* names, int names_len, double* ms, int
 
 int xmca_reset_timings(xmca_handle* h) {
   if (!h) return XMCA_ERR_INVALID;
-  try { h->tm.reset(); } catch (...) { return XMCA_ERR_HIP; }
+  try {
+    if (h->tail.pending && h->tail.err_code == XMCA_OK) { (void)hipSetDevice(h->device); join_tail(h); }
+    h->tm.reset();
+  } catch (...) { return XMCA_ERR_HIP; }
   h->ews.w64.round_ms = 0.0;
   h->ews.w64.round_launches = 0;
   h->ews.trd.reduce_ms = 0.0;
@@ -1798,6 +1833,7 @@ int xmca_trim_pool(xmca_handle* h) {
   API_BEGIN(h)
   XMCA_HIP(hipStreamSynchronize(h->st));
   h->pool.trim();
+  h->tail.trim();                    // (joined above: split-K slabs and partial sums of the deferred back-projection)
   for (xmca_handle* lane : h->lanes) {
     XMCA_HIP(hipStreamSynchronize(lane->st));
     lane->pool.trim();
