@@ -407,7 +407,7 @@ def test_project_real_complex_and_implicit_analytic(h, dtype, T, N):
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("T,N", [(33, 1), (130, 1), (130, 100), (33, 33)])
 def test_project_after_solve_with_explicit_imaginary_planes(h, dtype, T, N):
-    """N <= T: `Solver::analytic_applicable` is false, so solve() forms X_im = Ht X on the device and project() uses the
+    """N <= T: `Solver::analytic_route` is false, so solve() forms X_im = Ht X on the device and project() uses the
     stored planes"""
     rng = np.random.default_rng(T + N)
     X = rng.standard_normal((T, N)).astype(dtype)

@@ -274,7 +274,7 @@ def test_pcs_projection_matches_host_formula(name, cplx, analytic, monkeypatch):
     """pcs() = X~ V / sqrt(sigma) (array.py:391): the product runs on the fields resident on the device - real fields,
     the implicit analytic signal of the subspace path (U = W + i Ht W), stored complex planes (general path), f32.
     The solver reads XMCA_ANALYTIC once per process, so the general path ("0") is reached by shape: a right field with no
-    more grid points than time steps makes `Solver::analytic_applicable` false."""
+    more grid points than time steps makes `Solver::analytic_route` false."""
     monkeypatch.setenv("XMCA_ANALYTIC", analytic)
     fields = make_input(name)
     if analytic == "0":

@@ -120,7 +120,7 @@ struct SolveResult {
   int64_t ldv[2] = {0, 0};
   bool cplx = false;
   bool weak_refined = false;          // the route refined its weak modes itself (Solver::refine_weak_block)
-  int consistent = 0;                 // leading modes whose sigma passed the route's own consistency check (solve_one_sided)
+  int consistent = 0;                 // leading modes whose sigma passed the route's own consistency check (guard_time_space)
   EvdInfo evd_info[3];
 };
 
@@ -261,14 +261,36 @@ class Solver {
   DeferredTail* defer = nullptr;   // xmca_solve only: where the one-field dual route may leave the tail of its back-projection
   Solver(hipStream_t s, GemmWorkspace& g, EvdWorkspace& e, StageTimer& t) : st(s), gws(g), ews(e), tm(t) {}
 
-  // per-field reduction: eigen-decomposition of the T x T Gram matrix when N > T
+  // per-field reduction: eigen-decomposition of the field's Gram matrix - T x T in time space (when N > T), m x m in the
+  // analytic frame
   struct Reduced {
     bool reduced = false;
-    int r = 0;                 // min(T, N)
-    CPlanes Z;                 // r x T : row i = conj(u_i)          (reduced only)
+    int r = 0;                 // min(T, N); the order of the Gram matrix when reduced
+    CPlanes Z;                 // r x r : row i = conj(eigenvector i): conj(u_i), conj(w_i) in the analytic frame (reduced only)
     DevBuf<double> s;          // r     : singular values of the field (reduced only)
     std::vector<double> lam;
   };
+
+  // The coordinates in which the small dense problem of a two-field model is posed: time space (n = T; X~ itself, real or
+  // complex) or the Fourier subspace of the analytic signal (n = m, complex; `an` set - see "Analytic-signal models" below).
+  // A frame says how a field's n x n Gram matrix is formed (gram) and how rows of frame coefficients become unit vectors in
+  // grid space (project); everything between the two is the same algebra (solve_wide_pair).
+  struct Analytic;
+  struct Frame {
+    int n;
+    bool cplx;
+    const Analytic* an;        // null: time space
+  };
+  void gram(const Frame& fr, const FieldData<TI>& f, CPlanes& G) {
+    if (fr.an) analytic_gram(f, *fr.an, G);
+    else gram(f, fr.cplx, G);
+  }
+  // rows [0, nv) of Vt = the normalised vectors of the coefficient rows E (nv x n); the analytic frame pads with zero rows up
+  // to rows_total (null modes), in time space nv == rows_total
+  void project(const Frame& fr, const FieldData<TI>& f, const CPlanes& E, int nv, int rows_total, CPlanes& Vt) {
+    if (fr.an) analytic_project(f, *fr.an, E.r(), E.im.get(), nv, rows_total, Vt);
+    else back_project(f, fr.cplx, E.r(), E.i(fr.cplx), nv, Vt);
+  }
 
   // G = X X^H (T x T, both triangles):  Gr = Xr Xr^T + Xi Xi^T ;  Gi = Xi Xr^T - Xr Xi^T
   void gram(const FieldData<TI>& f, bool cplx, CPlanes& G) {
@@ -281,26 +303,24 @@ class Solver {
   }
 
   void reduce_field(const FieldData<TI>& f, bool cplx, Reduced& R, CPlanes& G, EvdInfo* info, bool want_vectors = true) {
-    const int T = (int)f.T;
     R.reduced = f.N > f.T;
     R.r = (int)std::min(f.T, f.N);
     if (!R.reduced) return;
     gram(f, cplx, G);
-    reduce_field_gram(f, cplx, R, G, info, want_vectors);
+    reduce_gram(G, (int)f.T, cplx, R, info, want_vectors);
   }
-  // ... from the Gram matrix G of f (T x T)
-  void reduce_field_gram(const FieldData<TI>& f, bool cplx, Reduced& R, const CPlanes& G, EvdInfo* info, bool want_vectors = true) {
-    const int T = (int)f.T;
+  // ... from the Gram matrix G (n x n Hermitian) of the field, in either frame
+  void reduce_gram(const CPlanes& G, int n, bool cplx, Reduced& R, EvdInfo* info, bool want_vectors = true) {
     R.reduced = true;
-    R.r = T;
+    R.r = n;
     tm.begin("eigh");
-    if (want_vectors) R.Z.ensure((size_t)T * T, cplx);
-    R.s.ensure((size_t)T);
+    if (want_vectors) R.Z.ensure((size_t)n * n, cplx);
+    R.s.ensure((size_t)n);
     DevBuf<double> lam_dev;
-    lam_dev.ensure((size_t)T);
-    hermitian_evd(st, ews, G.r(), G.i(cplx), T, T, R.lam, lam_dev.get(), want_vectors ? R.Z.r() : nullptr,
-                  want_vectors ? R.Z.i(cplx) : nullptr, T, info);
-    hipLaunchKernelGGL(sqrt_clamp_kernel, dim3(ceil_div(T, 256)), dim3(256), 0, st, lam_dev.get(), R.s.get(), T, 1.0);
+    lam_dev.ensure((size_t)n);
+    hermitian_evd(st, ews, G.r(), G.i(cplx), n, n, R.lam, lam_dev.get(), want_vectors ? R.Z.r() : nullptr,
+                  want_vectors ? R.Z.i(cplx) : nullptr, n, info);
+    hipLaunchKernelGGL(sqrt_clamp_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, lam_dev.get(), R.s.get(), n, 1.0);
     XMCA_HIP(hipStreamSynchronize(st));
     tm.end();
   }
@@ -460,7 +480,7 @@ class Solver {
     if constexpr (!std::is_same<TI, double>::value) {
       return;
     } else {
-      static const double thr_plain = [] { const char* e = std::getenv("XMCA_DEFLATE_BELOW"); return e ? std::atof(e) : 1e-3; }();   // 0: off
+      const double thr_plain = deflate_below();
       const int n_vec = out.n_vec;
       if (thr_plain <= 0.0 || n_vec <= 1 || out.sigma.empty() || !(out.sigma[0] > 0.0)) return;
       const int T = (int)fields[0].T;
@@ -538,33 +558,12 @@ class Solver {
     const int T = (int)A.T;
     const double dof = (double)(T - 1);
     out.cplx = cplx;
-    Reduced Ra, Rb;
-    CPlanes G;
-    if (n_fields == 2 && n_vec_req == 0 && A.N > A.T && fields[1].N > fields[1].T && cholesky_enabled()) {
-      CPlanes Ga, Gb;
-      gram(A, cplx, Ga);
-      gram(fields[1], cplx, Gb);
-      if (values_by_cholesky(Ga, Gb, T, cplx, dof, out)) {
-        out.rank = T;
-        out.n_vec = 0;
-        out.ldv[0] = A.N;
-        out.ldv[1] = fields[1].N;
-        return;
-      }
-    }
-    static const bool one_sided_on = [] { const char* e = std::getenv("XMCA_ONE_SIDED"); return !(e && e[0] == '0'); }();
-    if (n_fields == 2 && one_sided_on && A.N > A.T && fields[1].N > fields[1].T) {
-      // two wide fields: the first one enters through a factor M, M^H M = G_a - its Cholesky factor when that passes the
-      // guards (factor_by_cholesky, solve_one_sided), else its eigen-factor
-      gram(A, cplx, G);
-      CPlanes Fm;
-      if (factor_by_cholesky(G, T, cplx, rows_sum_to_zero(G, T, cplx), Fm) &&
-          solve_one_sided(A, fields[1], cplx, Fm, nullptr, n_vec_req, out, G, true))
-        return;
-      reduce_field_gram(A, cplx, Ra, G, &out.evd_info[0], true);
-      solve_one_sided(A, fields[1], cplx, Ra.Z, Ra.s.get(), n_vec_req, out, G, false);
+    if (n_fields == 2 && A.N > A.T && fields[1].N > fields[1].T) {
+      solve_wide_pair(Frame{T, cplx, nullptr}, fields, n_vec_req, out);
       return;
     }
+    Reduced Ra, Rb;
+    CPlanes G;
     reduce_field(A, cplx, Ra, G, &out.evd_info[0], n_fields == 2 || n_vec_req != 0);
 
     if (n_fields == 1) {
@@ -616,9 +615,6 @@ class Solver {
         XMCA_HIP(hipMemcpyAsync(out.Vt[0].r(), Z.r(), sizeof(double) * (size_t)m * N, hipMemcpyDeviceToDevice, st));
         if (cplx) {
           XMCA_HIP(hipMemcpyAsync(out.Vt[0].im.get(), Z.im.get(), sizeof(double) * (size_t)m * N, hipMemcpyDeviceToDevice, st));
-          DevBuf<double> minus1;
-          // negate the imaginary plane: scale by -1 through the column-scale kernel with a 1-element trick is
-          // overkill; a dedicated lambda kernel keeps it simple
           negate(out.Vt[0].im.get(), (int64_t)m * N);
         }
         XMCA_HIP(hipStreamSynchronize(st));
@@ -626,29 +622,25 @@ class Solver {
       return;
     }
 
-    // ------------------------------- two fields ------------------------------------------------
+    // ------------------------------- two fields, at least one no wider than T ------------------
     const FieldData<TI>& B = fields[1];
     reduce_field(B, cplx, Rb, G, &out.evd_info[1]);
     const int ra = Ra.r, rb = Rb.r;
     const int rank = std::min(ra, rb);
     out.rank = rank;
 
-    // K = F_a^H F_b / dof   (ra x rb)
+    // K = F_a^H F_b / dof   (ra x rb), a narrow field being its own factor
     CPlanes K;
     K.ensure((size_t)ra * rb, cplx);
     tm.begin("kernel");
     {
       Narrow<TI> za, zb;
-      if (Ra.reduced && Rb.reduced) {
-        // K[i][j] = s_a,i s_b,j sum_t Za[i,t] conj(Zb[j,t]) / dof     (f64 x f64)
-        cgemm<double>(st, gws, Ra.Z.r(), Ra.Z.i(cplx), T, true, false, Rb.Z.r(), Rb.Z.i(cplx), T, false, true, K.r(), K.i(cplx), rb,
-                      ra, rb, T, 1.0 / dof, Ra.s.get(), Rb.s.get(), false);
-      } else if (Ra.reduced && !Rb.reduced) {
+      if (Ra.reduced) {
         // K = S_a Za X~b / dof
         za.from(st, Ra.Z.r(), Ra.Z.i(cplx), (int64_t)ra * T);
         cgemm<TI>(st, gws, za.r, za.i, T, true, false, B.r(), B.i(), B.N, true, false, K.r(), K.i(cplx), rb, ra, rb, T, 1.0 / dof,
                   Ra.s.get(), nullptr, false);
-      } else if (!Ra.reduced && Rb.reduced) {
+      } else if (Rb.reduced) {
         // K[n][j] = conj( sum_t X~a[t,n] Zb[j,t] ) s_b,j / dof
         zb.from(st, Rb.Z.r(), Rb.Z.i(cplx), (int64_t)rb * T);
         cgemm<TI>(st, gws, A.r(), A.i(), A.N, false, true, zb.r, zb.i, T, false, true, K.r(), K.i(cplx), rb, ra, rb, T, 1.0 / dof,
@@ -658,42 +650,13 @@ class Solver {
         cgemm<TI>(st, gws, A.r(), A.i(), A.N, false, true, B.r(), B.i(), B.N, true, false, K.r(), K.i(cplx), rb, ra, rb, T,
                   1.0 / dof, nullptr, nullptr, false);
       }
-      XMCA_HIP(hipStreamSynchronize(st));
+      XMCA_HIP(hipStreamSynchronize(st));     // za / zb are released
     }
     tm.end();
 
-    // SVD of K through the Hermitian EVD of the smaller Gram matrix
-    CPlanes H, Ph, Qh;
-    Ph.ensure((size_t)rank * ra, cplx);
-    Qh.ensure((size_t)rank * rb, cplx);
+    CPlanes Ph, Qh;
     std::vector<double> lam;
-    tm.begin("kernel_svd");
-    if (rb <= ra) {
-      H.ensure((size_t)rb * rb, cplx);
-      // H = K^H K
-      cgemm<double>(st, gws, K.r(), K.i(cplx), rb, false, true, K.r(), K.i(cplx), rb, true, false, H.r(), H.i(cplx), rb, rb, rb, ra,
-                    1.0, nullptr, nullptr, true);
-      hermitian_evd(st, ews, H.r(), H.i(cplx), rb, rb, lam, nullptr, Qh.r(), Qh.i(cplx), rb, &out.evd_info[2]);
-      // Ph = Qh K^H  (rows = conj(p_m)), then normalise rows
-      cgemm<double>(st, gws, Qh.r(), Qh.i(cplx), rb, true, false, K.r(), K.i(cplx), rb, false, true, Ph.r(), Ph.i(cplx), ra, rank, ra,
-                    rb, 1.0, nullptr, nullptr, false);
-      hipLaunchKernelGGL((normalize_rows_kernel<double>), dim3(rank), dim3(256), 0, st, Ph.r(), Ph.i(cplx), (int64_t)ra, ra, 0,
-                         (double*)nullptr);
-    } else {
-      H.ensure((size_t)ra * ra, cplx);
-      // H = K K^H
-      cgemm<double>(st, gws, K.r(), K.i(cplx), rb, true, false, K.r(), K.i(cplx), rb, false, true, H.r(), H.i(cplx), ra, ra, ra, rb,
-                    1.0, nullptr, nullptr, true);
-      hermitian_evd(st, ews, H.r(), H.i(cplx), ra, ra, lam, nullptr, Ph.r(), Ph.i(cplx), ra, &out.evd_info[2]);
-      // Qh = Ph K
-      cgemm<double>(st, gws, Ph.r(), Ph.i(cplx), ra, true, false, K.r(), K.i(cplx), rb, true, false, Qh.r(), Qh.i(cplx), rb, rank, rb,
-                    ra, 1.0, nullptr, nullptr, false);
-      hipLaunchKernelGGL((normalize_rows_kernel<double>), dim3(rank), dim3(256), 0, st, Qh.r(), Qh.i(cplx), (int64_t)rb, rb, 0,
-                         (double*)nullptr);
-    }
-    XMCA_HIP(hipGetLastError());
-    XMCA_HIP(hipStreamSynchronize(st));
-    tm.end();
+    kernel_svd(K, ra, rb, cplx, true, lam, Ph, Qh, &out.evd_info[2]);
     out.sigma.resize(rank);
     for (int i = 0; i < rank; ++i) out.sigma[i] = std::sqrt(std::max(lam[i], 0.0));
 
@@ -703,8 +666,8 @@ class Solver {
     out.ldv[1] = B.N;
     if (m == 0) return;
     tm.begin("backproject");
-    project_side(A, B, cplx, Ra, Rb, Ph, Qh, ra, rb, m, out.Vt[0]);   // V_left  from (F_b Q)
-    project_side(B, A, cplx, Rb, Ra, Qh, Ph, rb, ra, m, out.Vt[1]);   // V_right from (F_a P)
+    project_side(A, B, cplx, Ra.reduced, Ph, Qh, ra, rb, m, out.Vt[0]);   // V_left  from (F_b Q)
+    project_side(B, A, cplx, Rb.reduced, Qh, Ph, rb, ra, m, out.Vt[1]);   // V_right from (F_a P)
     tm.end();
   }
 
@@ -719,6 +682,15 @@ class Solver {
   static bool cholesky_enabled() {
     static const bool on = [] { const char* e = std::getenv("XMCA_CHOLESKY"); return !(e && e[0] == '0'); }();
     return on;
+  }
+  static bool one_sided_enabled() {    // XMCA_ONE_SIDED=0: both wide fields are decomposed (explicit K)
+    static const bool on = [] { const char* e = std::getenv("XMCA_ONE_SIDED"); return !(e && e[0] == '0'); }();
+    return on;
+  }
+  // XMCA_DEFLATE_BELOW: modes with vectors below this fraction of the top are refined (refine_weak_block, refine_by_deflation); 0: off
+  static double deflate_below() {
+    static const double thr = [] { const char* e = std::getenv("XMCA_DEFLATE_BELOW"); return e ? std::atof(e) : 1e-3; }();
+    return thr;
   }
   bool values_by_cholesky(CPlanes& Ga, CPlanes& Gb, int n, bool cplx, double dof, SolveResult& out) {
     tm.begin("cholesky");
@@ -746,109 +718,253 @@ class Solver {
     return true;
   }
 
+  // SVD of K (ra x rb) through the Hermitian EVD of the smaller Gram matrix: lam = sigma^2, descending, and with vectors the
+  // rows of Ph (rank x ra) = conj(p_m) and of Qh (rank x rb) = conj(q_m)
+  void kernel_svd(const CPlanes& K, int ra, int rb, bool cplx, bool want_vectors, std::vector<double>& lam, CPlanes& Ph, CPlanes& Qh,
+                  EvdInfo* info) {
+    const int rank = std::min(ra, rb);
+    CPlanes H;
+    tm.begin("kernel_svd");
+    if (want_vectors) {
+      Ph.ensure((size_t)rank * ra, cplx);
+      Qh.ensure((size_t)rank * rb, cplx);
+    }
+    if (rb <= ra) {
+      H.ensure((size_t)rb * rb, cplx);
+      // H = K^H K
+      cgemm<double>(st, gws, K.r(), K.i(cplx), rb, false, true, K.r(), K.i(cplx), rb, true, false, H.r(), H.i(cplx), rb, rb, rb, ra,
+                    1.0, nullptr, nullptr, true);
+      hermitian_evd(st, ews, H.r(), H.i(cplx), rb, rb, lam, nullptr, want_vectors ? Qh.r() : nullptr, want_vectors ? Qh.i(cplx) : nullptr,
+                    rb, info);
+      if (want_vectors) {
+        // Ph = Qh K^H  (rows = conj(p_m)), then normalise rows
+        cgemm<double>(st, gws, Qh.r(), Qh.i(cplx), rb, true, false, K.r(), K.i(cplx), rb, false, true, Ph.r(), Ph.i(cplx), ra, rank,
+                      ra, rb, 1.0, nullptr, nullptr, false);
+        hipLaunchKernelGGL((normalize_rows_kernel<double>), dim3(rank), dim3(256), 0, st, Ph.r(), Ph.i(cplx), (int64_t)ra, ra, 0,
+                           (double*)nullptr);
+      }
+    } else {
+      H.ensure((size_t)ra * ra, cplx);
+      // H = K K^H
+      cgemm<double>(st, gws, K.r(), K.i(cplx), rb, true, false, K.r(), K.i(cplx), rb, false, true, H.r(), H.i(cplx), ra, ra, ra, rb,
+                    1.0, nullptr, nullptr, true);
+      hermitian_evd(st, ews, H.r(), H.i(cplx), ra, ra, lam, nullptr, want_vectors ? Ph.r() : nullptr, want_vectors ? Ph.i(cplx) : nullptr,
+                    ra, info);
+      if (want_vectors) {
+        // Qh = Ph K
+        cgemm<double>(st, gws, Ph.r(), Ph.i(cplx), ra, true, false, K.r(), K.i(cplx), rb, true, false, Qh.r(), Qh.i(cplx), rb, rank,
+                      rb, ra, 1.0, nullptr, nullptr, false);
+        hipLaunchKernelGGL((normalize_rows_kernel<double>), dim3(rank), dim3(256), 0, st, Qh.r(), Qh.i(cplx), (int64_t)rb, rb, 0,
+                           (double*)nullptr);
+      }
+    }
+    XMCA_HIP(hipGetLastError());
+    XMCA_HIP(hipStreamSynchronize(st));
+    tm.end();
+  }
+
   // -------------------------------------------------------------------------------------------------------------
-  // Two fields, both wider than T: only ONE of them is decomposed.  With F_a = U_a S_a from G_a and the kernel
-  // K = F_a^H F_b / dof of the reference (array.py:553-566), K K^H = F_a^H (F_b F_b^H) F_a / dof^2 = F_a^H G_b F_a / dof^2:
-  // the Gram matrix of the second field enters as an operator and is never diagonalised (one T x T eigenproblem with
-  // vectors less per solve).  Left small singular vectors p_m and sigma_m^2 = eigenpairs of H = K K^H; in grid space
-  //   v_right,m ~ X~b^H (F_a p_m),    v_left,m ~ X~a^H (G_b F_a p_m) = dof C v_right,m     (rows normalised afterwards),
+  // Two fields that are both reduced in the frame: only ONE of them is decomposed.  With F_a = U_a S_a from G_a and the
+  // kernel K = F_a^H F_b / dof of the reference (array.py:553-566), K K^H = F_a^H (F_b F_b^H) F_a / dof^2 = F_a^H G_b F_a / dof^2:
+  // the Gram matrix of the second field enters as an operator and is never diagonalised (one eigenproblem with vectors less
+  // per solve).  Any factor M with M^H M = G_a serves (factor_by_cholesky): with H = M G_b M^H / dof^2 = P L P^H, q = M^H p
+  // solves G_a G_b q = sigma^2 dof^2 q whatever M is.  Left small singular vectors p_m and sigma_m^2 = eigenpairs of H; in grid space
+  //   v_right,m ~ X~b^H (M^H p_m),    v_left,m ~ X~a^H (G_b M^H p_m) = dof C v_right,m     (rows normalised afterwards),
   // which also fixes the shared phase gauge u^H C v = +sigma.
   // -------------------------------------------------------------------------------------------------------------
-  // Mf (T x T planes), ms (row scale or null): the factor M = diag(ms) Mf with M^H M = G_a (Ga).  guard: M is a Cholesky
-  // factor on probation - the Gram matrix of the left vectors is checked in time-space coordinates (Thl G_a Thl^H, as in
-  // solve_analytic) and `false` is returned, with nothing usable in `out`, when they are not orthogonal to 1e-6.
-  bool solve_one_sided(const FieldData<TI>& A, const FieldData<TI>& B, bool cplx, const CPlanes& Mf, const double* ms, int n_vec_req,
-                       SolveResult& out, const CPlanes& Ga, bool guard) {
-    const int T = (int)A.T, ra = T;
-    const double dof = (double)(T - 1);
-    const int rank = ra;                       // = T = min(T, Nx, Ny)
-    out.rank = rank;
-    CPlanes Gb, M1, H, Ph;
-    gram(B, cplx, Gb);
+  // Mf (n x n planes), ms (row scale or null): the factor M = diag(ms) Mf.  Writes sigma[0, n) and, for nv > 0, the frame
+  // coefficients of the leading nv modes: E_r[m] = conj(M^H p_m) = ((Ph diag(ms)) Mf)[m] (right vectors, metric G_b) and
+  // E_l = E_r G_b (left vectors, metric G_a; G_b Hermitian) - with their weak block refined (refine_weak_block: trusted down
+  // to 1e-5 sigma_1, on the 10-decade probe its absolute error is ~7e-12 sigma_1; what lies below is left to refine_by_deflation).
+  void one_sided_core(const CPlanes& Mf, const double* ms, const CPlanes& Ga, const CPlanes& Gb, int n, bool cplx, double dof, int nv,
+                      SolveResult& out, CPlanes& Er, CPlanes& El) {
+    CPlanes M1, H, Ph, Ws;
     tm.begin("kernel");
-    M1.ensure((size_t)ra * T, cplx);
-    H.ensure((size_t)ra * ra, cplx);
+    M1.ensure((size_t)n * n, cplx);
+    H.ensure((size_t)n * n, cplx);
     // M1 = M G_b ;  H = M1 M^H / dof^2
-    cgemm<double>(st, gws, Mf.r(), Mf.i(cplx), T, true, false, Gb.r(), Gb.i(cplx), T, true, false, M1.r(), M1.i(cplx), T, ra, T, T,
-                  1.0, ms, nullptr, false);
-    cgemm<double>(st, gws, M1.r(), M1.i(cplx), T, true, false, Mf.r(), Mf.i(cplx), T, false, true, H.r(), H.i(cplx), ra, ra, ra, T,
+    cgemm<double>(st, gws, Mf.r(), Mf.i(cplx), n, true, false, Gb.r(), Gb.i(cplx), n, true, false, M1.r(), M1.i(cplx), n, n, n, n, 1.0,
+                  ms, nullptr, false);
+    cgemm<double>(st, gws, M1.r(), M1.i(cplx), n, true, false, Mf.r(), Mf.i(cplx), n, false, true, H.r(), H.i(cplx), n, n, n, n,
                   1.0 / (dof * dof), nullptr, ms, true);
     tm.end();
-    const int m = n_vec_req < 0 ? rank : std::min(n_vec_req, rank);
     std::vector<double> lam;
     tm.begin("kernel_svd");
-    if (m > 0) Ph.ensure((size_t)ra * ra, cplx);
-    hermitian_evd(st, ews, H.r(), H.i(cplx), ra, ra, lam, nullptr, m > 0 ? Ph.r() : nullptr, m > 0 ? Ph.i(cplx) : nullptr, ra,
+    if (nv > 0) Ph.ensure((size_t)n * n, cplx);
+    hermitian_evd(st, ews, H.r(), H.i(cplx), n, n, lam, nullptr, nv > 0 ? Ph.r() : nullptr, nv > 0 ? Ph.i(cplx) : nullptr, n,
                   &out.evd_info[2]);
     XMCA_HIP(hipStreamSynchronize(st));
     tm.end();
-    out.sigma.resize(rank);
-    for (int i = 0; i < rank; ++i) out.sigma[i] = std::sqrt(std::max(lam[i], 0.0));
-    out.n_vec = m;
-    out.ldv[0] = A.N;
-    out.ldv[1] = B.N;
-    if (m == 0) return true;
+    for (int i = 0; i < n; ++i) out.sigma[i] = std::sqrt(std::max(lam[i], 0.0));
+    if (nv == 0) return;
     tm.begin("backproject");
-    // Th_a[m][t] = conj((M^H p_m)[t]) = ((Ph diag(ms)) Mf)[m][t] ;  Th_l = Th_a G_b  (G_b Hermitian)
-    CPlanes Ws, Tha, Thl;
-    Ws.ensure((size_t)m * ra, cplx);
-    Tha.ensure((size_t)m * T, cplx);
-    Thl.ensure((size_t)m * T, cplx);
-    XMCA_HIP(hipMemcpyAsync(Ws.r(), Ph.r(), sizeof(double) * (size_t)m * ra, hipMemcpyDeviceToDevice, st));
-    if (cplx) XMCA_HIP(hipMemcpyAsync(Ws.im.get(), Ph.im.get(), sizeof(double) * (size_t)m * ra, hipMemcpyDeviceToDevice, st));
-    if (ms)
-      hipLaunchKernelGGL(scale_kernel, ew_grid((int64_t)m * ra), dim3(EW_BLOCK), 0, st, Ws.r(), Ws.i(cplx), (int64_t)ra, m, ra, ms, 0, 0);
-    cgemm<double>(st, gws, Ws.r(), Ws.i(cplx), ra, true, false, Mf.r(), Mf.i(cplx), T, true, false, Tha.r(), Tha.i(cplx), T, m, T, ra,
-                  1.0, nullptr, nullptr, false);
-    cgemm<double>(st, gws, Tha.r(), Tha.i(cplx), T, true, false, Gb.r(), Gb.i(cplx), T, true, false, Thl.r(), Thl.i(cplx), T, m, T, T, 1.0,
+    Ws.ensure((size_t)nv * n, cplx);
+    Er.ensure((size_t)nv * n, cplx);
+    El.ensure((size_t)nv * n, cplx);
+    XMCA_HIP(hipMemcpyAsync(Ws.r(), Ph.r(), sizeof(double) * (size_t)nv * n, hipMemcpyDeviceToDevice, st));
+    if (cplx) XMCA_HIP(hipMemcpyAsync(Ws.im.get(), Ph.im.get(), sizeof(double) * (size_t)nv * n, hipMemcpyDeviceToDevice, st));
+    if (ms) hipLaunchKernelGGL(scale_kernel, ew_grid((int64_t)nv * n), dim3(EW_BLOCK), 0, st, Ws.r(), Ws.i(cplx), (int64_t)n, nv, n, ms, 0, 0);
+    cgemm<double>(st, gws, Ws.r(), Ws.i(cplx), n, true, false, Mf.r(), Mf.i(cplx), n, true, false, Er.r(), Er.i(cplx), n, nv, n, n, 1.0,
                   nullptr, nullptr, false);
-    XMCA_HIP(hipStreamSynchronize(st));
+    cgemm<double>(st, gws, Er.r(), Er.i(cplx), n, true, false, Gb.r(), Gb.i(cplx), n, true, false, El.r(), El.i(cplx), n, nv, n, n, 1.0,
+                  nullptr, nullptr, false);
+    XMCA_HIP(hipStreamSynchronize(st));       // Ph, Ws are released on return
     tm.end();
-    // weak block of H from the rows of Tha / Thl and projection of the weak rows against the strong ones, as in the analytic
-    // route (time-space coordinates: metrics G_a, G_b).  In this route it is trusted down to 1e-5 sigma_1 (on the 10-decade
-    // probe its absolute error is ~7e-12 sigma_1); what lies below is left to refine_by_deflation.
-    refine_weak_block(Tha, Thl, m, T, dof, out, cplx, &Ga, &Gb);
-    out.consistent = 0;
-    if (m > 1) {
-      // C = Thl G_a Thl^H (two products, 10 ms at T = 5000).  Off the diagonal: the Gram matrix of the left vectors (guard of
-      // the Cholesky factor).  On the diagonal: with g = G_b q, g^H G_a g = mu g^H q = mu^2 for an eigenpair of G_a G_b, a
-      // Rayleigh quotient of the pencil (G_b G_a G_b, G_b) that uses G_a itself and not its factor - second order in the
-      // vector's error, so C_ii / mu_i^2 - 1 shows what the factor's absolute error eps lambda_a1 did to sigma_i^2.  The
-      // leading modes that agree to 1e-6 need no second solve (refine_by_deflation): for fields whose weak modes are noise
-      // against noise that is all of them (real C3: down to 1e-8 sigma_1), for variance spectra graded over 10 decades it
-      // stops where the weak block stops being good.
-      tm.begin("orthogonality_check");
-      int n_check = 0;                                     // null modes carry arbitrary vectors
-      while (n_check < m && out.sigma[n_check] > 1e-9 * out.sigma[0]) ++n_check;
-      std::vector<double> cdiag, crow;
-      const double worst = coherence(Thl, Ga, m, T, n_check, cplx, &cdiag, &crow);
-      tm.end();
-      int ok = 0;
-      double worst_c = 0.0;
-      for (; ok < m; ++ok) {
-        const double mu = out.sigma[ok] * out.sigma[ok] * dof * dof;
-        if (!(out.sigma[ok] > 1e-11 * out.sigma[0])) break;
-        const double dev = std::fabs(cdiag[ok] / (mu * mu) - 1.0);
-        if (!(dev < 1e-6) || !(crow[ok] < 1e-6)) break;       // ... and its left vector must be orthogonal to the stronger ones
-        worst_c = std::max(worst_c, dev);
-      }
-      out.consistent = ok;
-      static const bool trace = xmca_trace("solve");
-      if (trace)
-        std::fprintf(stderr, "[xmca solve] one-sided (time space): left-vector coherence %.3e over %d modes; sigma consistent (%.1e) for the "
-                             "leading %d of %d modes, sigma there %.2e sigma_1\n", worst, n_check, worst_c, ok, m,
-                     ok > 0 ? out.sigma[ok - 1] / out.sigma[0] : 1.0);
-      // (guard of the Cholesky factor: over the modes that will be kept from this solve - what lies behind them is solved again)
-      double worst_kept = 0.0;
-      for (int i = 0; i < ok; ++i) worst_kept = std::max(worst_kept, crow[i]);
-      if (guard && !((ok == n_check ? worst : worst_kept) < 1e-6)) return false;
-      if (guard && ok < std::min(n_check, 2)) return false;
+    refine_weak_block(Er, El, nv, n, dof, out, cplx, Ga, Gb);
+  }
+
+  // The guards of a one-sided solve check the Gram matrix of the left vectors, C = E_l G_a E_l^H (two small products; null
+  // modes carry arbitrary vectors and are left out), and say whether a Cholesky factor on probation may stay.  The two frames
+  // ask DIFFERENT questions on purpose.  Time space: besides the factor it decides, mode by mode, what refine_by_deflation has
+  // to solve again (`consistent`), for either factor.  Analytic frame: nothing is solved again (its weak block is measured
+  // accurate as it is), so only the Cholesky factor is checked, on the worst pair alone.
+  int non_null_modes(const SolveResult& out, int nv) const {
+    int n_check = 0;
+    while (n_check < nv && out.sigma[n_check] > 1e-9 * out.sigma[0]) ++n_check;
+    return n_check;
+  }
+  // Time space.  Off the diagonal of C: the orthogonality of the left vectors.  On the diagonal: with g = G_b q,
+  // g^H G_a g = mu g^H q = mu^2 for an eigenpair of G_a G_b, a Rayleigh quotient of the pencil (G_b G_a G_b, G_b) that uses G_a
+  // itself and not its factor - second order in the vector's error, so C_ii / mu_i^2 - 1 shows what the factor's absolute
+  // error eps lambda_a1 did to sigma_i^2 (C: 10 ms at T = 5000).  The leading modes that agree to 1e-6 need no second solve: for
+  // fields whose weak modes are noise against noise that is all of them (real C3: down to 1e-8 sigma_1), for variance spectra
+  // graded over 10 decades it stops where the weak block stops being good.
+  bool guard_time_space(const CPlanes& El, const CPlanes& Ga, int nv, int n, bool cplx, double dof, bool on_probation, SolveResult& out) {
+    tm.begin("orthogonality_check");
+    const int n_check = non_null_modes(out, nv);
+    std::vector<double> cdiag, crow;
+    const double worst = coherence(El, Ga, nv, n, n_check, cplx, &cdiag, &crow);
+    tm.end();
+    int ok = 0;
+    double worst_c = 0.0;
+    for (; ok < nv; ++ok) {
+      const double mu = out.sigma[ok] * out.sigma[ok] * dof * dof;
+      if (!(out.sigma[ok] > 1e-11 * out.sigma[0])) break;
+      const double dev = std::fabs(cdiag[ok] / (mu * mu) - 1.0);
+      if (!(dev < 1e-6) || !(crow[ok] < 1e-6)) break;       // ... and its left vector must be orthogonal to the stronger ones
+      worst_c = std::max(worst_c, dev);
     }
+    out.consistent = ok;
+    static const bool trace = xmca_trace("solve");
+    if (trace)
+      std::fprintf(stderr, "[xmca solve] one-sided (time space): left-vector coherence %.3e over %d modes; sigma consistent (%.1e) for the "
+                           "leading %d of %d modes, sigma there %.2e sigma_1\n", worst, n_check, worst_c, ok, nv,
+                   ok > 0 ? out.sigma[ok - 1] / out.sigma[0] : 1.0);
+    if (!on_probation) return true;
+    // (the Cholesky factor: over the modes that will be kept from this solve - what lies behind them is solved again)
+    double worst_kept = 0.0;
+    for (int i = 0; i < ok; ++i) worst_kept = std::max(worst_kept, crow[i]);
+    return (ok == n_check ? worst : worst_kept) < 1e-6 && ok >= std::min(n_check, 2);
+  }
+  // Analytic frame.  On spectra graded over many decades E_l = E_r Gy_b cancels down to the weak rows and the Cholesky factor -
+  // unlike the eigen-factor, whose weak rows are small numbers to begin with - leaves u_weak with a component along the
+  // strong modes that project_out_rows has to remove (2e-8 left on the 10-decade probe, 4e-8 at C3 - the leading modes among
+  // themselves, the same with either factor).  Above 1e-6 the factor is not trusted: decompose the field.
+  bool guard_analytic(const CPlanes& El, const CPlanes& Ga, int nv, int n, bool on_probation, const SolveResult& out) {
+    if (!on_probation) return true;
+    tm.begin("orthogonality_check");
+    const int n_check = non_null_modes(out, nv);
+    const double worst = coherence(El, Ga, nv, n, n_check, true);
+    tm.end();
+    static const bool trace = xmca_trace("solve");
+    if (trace) std::fprintf(stderr, "[xmca solve] Cholesky factor: left-vector coherence %.3e over %d modes\n", worst, n_check);
+    return worst < 1e-6;
+  }
+
+  // One-sided solve with the factor M = diag(ms) Mf of G_a: core, guard, projection into grid space.  on_probation: M is a
+  // Cholesky factor, and `false` is returned, with nothing usable in `out`, when the guard refuses it.
+  bool solve_one_sided(const Frame& fr, const FieldData<TI>& A, const FieldData<TI>& B, const CPlanes& Mf, const double* ms,
+                       const CPlanes& Ga, const CPlanes& Gb, int nv, int n_vec, double dof, bool on_probation, SolveResult& out) {
+    CPlanes Er, El;
+    one_sided_core(Mf, ms, Ga, Gb, fr.n, fr.cplx, dof, nv, out, Er, El);
+    if (nv == 0) return true;
+    if (nv > 1 && !(fr.an ? guard_analytic(El, Ga, nv, fr.n, on_probation, out)
+                          : guard_time_space(El, Ga, nv, fr.n, fr.cplx, dof, on_probation, out)))
+      return false;
     tm.begin("backproject");
-    back_project(B, cplx, Tha.r(), Tha.i(cplx), m, out.Vt[1]);
-    back_project(A, cplx, Thl.r(), Thl.i(cplx), m, out.Vt[0]);
+    project(fr, B, Er, nv, n_vec, out.Vt[1]);
+    project(fr, A, El, nv, n_vec, out.Vt[0]);
     tm.end();
     return true;
+  }
+
+  // E = (W diag(s)) Z for the leading nv rows of W: frame coefficients of the modes whose small singular vectors are the rows
+  // of W, through the factor conj(F[t][j]) = Z[j][t] s_j of the OTHER field R
+  void rows_through_factor(const CPlanes& W, const Reduced& R, int nv, int n, bool cplx, CPlanes& E) {
+    CPlanes Ws;
+    Ws.ensure((size_t)nv * n, cplx);
+    E.ensure((size_t)nv * n, cplx);
+    XMCA_HIP(hipMemcpyAsync(Ws.r(), W.r(), sizeof(double) * (size_t)nv * n, hipMemcpyDeviceToDevice, st));
+    if (cplx) XMCA_HIP(hipMemcpyAsync(Ws.im.get(), W.im.get(), sizeof(double) * (size_t)nv * n, hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(scale_kernel, ew_grid((int64_t)nv * n), dim3(EW_BLOCK), 0, st, Ws.r(), Ws.i(cplx), (int64_t)n, nv, n, R.s.get(), 0, 0);
+    cgemm<double>(st, gws, Ws.r(), Ws.i(cplx), n, true, false, R.Z.r(), R.Z.i(cplx), n, true, false, E.r(), E.i(cplx), n, nv, n, n, 1.0,
+                  nullptr, nullptr, false);
+    XMCA_HIP(hipStreamSynchronize(st));       // Ws is released on return
+  }
+
+  // Two fields, both reduced in the frame `fr` (time space: both wider than T).  In either frame the model has rank T =
+  // min(T, N) as the reference reports it (array.py:597) and T singular values; the analytic frame resolves n = m of them and
+  // sigma[m, T), like the vector rows [m, n_vec), stay exact zeros.
+  void solve_wide_pair(const Frame& fr, const FieldData<TI>* fields, int n_vec_req, SolveResult& out) {
+    const FieldData<TI>& A = fields[0];
+    const FieldData<TI>& B = fields[1];
+    const int T = (int)A.T, n = fr.n;
+    const bool cplx = fr.cplx;
+    const double dof = (double)(T - 1);
+    const int n_vec = n_vec_req < 0 ? T : std::min(n_vec_req, T);
+    const int nv = std::min(n_vec, n);              // modes that can be non-null
+    out.rank = T;
+    out.n_vec = n_vec;
+    out.sigma.assign(T, 0.0);
+    out.ldv[0] = A.N;
+    out.ldv[1] = B.N;
+    out.consistent = 0;
+    CPlanes Ga, Gb;
+    if (n_vec == 0 && cholesky_enabled()) {
+      gram(fr, A, Ga);
+      gram(fr, B, Gb);
+      if (values_by_cholesky(Ga, Gb, n, cplx, dof, out)) return;    // (overwrites Ga)
+    }
+    Reduced Ra, Rb;
+    if (one_sided_enabled()) {
+      // the first field enters through a factor of G_a: the Cholesky factor when that passes factor_by_cholesky and the guard -
+      // no field is diagonalised at all - else the eigen-factor S_a Z_a
+      CPlanes Fm;
+      gram(fr, A, Ga);
+      const bool by_chol = factor_by_cholesky(Ga, n, cplx, !fr.an && rows_sum_to_zero(Ga, n, cplx), Fm);
+      if (!by_chol) reduce_gram(Ga, n, cplx, Ra, &out.evd_info[0]);
+      gram(fr, B, Gb);
+      if (by_chol) {
+        if (solve_one_sided(fr, A, B, Fm, nullptr, Ga, Gb, nv, n_vec, dof, true, out)) return;
+        reduce_gram(Ga, n, cplx, Ra, &out.evd_info[0]);
+      }
+      solve_one_sided(fr, A, B, Ra.Z, Ra.s.get(), Ga, Gb, nv, n_vec, dof, false, out);
+      return;
+    }
+    // XMCA_ONE_SIDED=0: both fields decomposed, K = S_a Z_a Z_b^H S_b / dof  (n x n)
+    gram(fr, A, Ga);
+    reduce_gram(Ga, n, cplx, Ra, &out.evd_info[0]);
+    gram(fr, B, Gb);
+    reduce_gram(Gb, n, cplx, Rb, &out.evd_info[1]);
+    CPlanes K, Ph, Qh;
+    K.ensure((size_t)n * n, cplx);
+    tm.begin("kernel");
+    cgemm<double>(st, gws, Ra.Z.r(), Ra.Z.i(cplx), n, true, false, Rb.Z.r(), Rb.Z.i(cplx), n, false, true, K.r(), K.i(cplx), n, n, n, n,
+                  1.0 / dof, Ra.s.get(), Rb.s.get(), false);
+    tm.end();
+    std::vector<double> lam;
+    // (time space has always taken the vectors here, also for n_vec = 0; the values-only eigensolver rounds differently)
+    const bool want_vectors = n_vec > 0 || !fr.an;
+    kernel_svd(K, n, n, cplx, want_vectors, lam, Ph, Qh, &out.evd_info[2]);
+    for (int i = 0; i < n; ++i) out.sigma[i] = std::sqrt(std::max(lam[i], 0.0));
+    if (n_vec == 0) return;
+    tm.begin("backproject");
+    CPlanes E;
+    rows_through_factor(Qh, Rb, nv, n, cplx, E);    // V_left  from (F_b Q)
+    project(fr, A, E, nv, n_vec, out.Vt[0]);
+    rows_through_factor(Ph, Ra, nv, n, cplx, E);    // V_right from (F_a P)
+    project(fr, B, E, nv, n_vec, out.Vt[1]);
+    tm.end();
   }
 
   // largest |C_ij| / sqrt(C_ii C_jj) over the leading n_check rows of C = E G E^H (E: nv x n rows, G: n x n metric)
@@ -915,11 +1031,6 @@ class Solver {
     CPlanes Phi;            // T x m
     DevBuf<double> h;       // m Hilbert weights
   };
-  struct AReduced {
-    CPlanes Wh;             // m x m, row i = conj(w_i): eigenvectors of Gy
-    DevBuf<double> s;       // m
-    std::vector<double> lam;
-  };
 
   void analytic_basis(int T, Analytic& an) {
     an.m = (T % 2 == 0) ? T / 2 + 1 : (T + 1) / 2;
@@ -949,9 +1060,8 @@ class Solver {
     // Gy[k][l] = h_k h_l / T  sum_s sum_t exp(-2 pi i k s / T) G[s][t] exp(+2 pi i l t / T): a 2-D DFT of G of which the
     // m x m corner is kept (fft.h: T transforms along the rows, m along the columns, each in the LDS of one workgroup) when T
     // factors into 2, 3, 5, 7 and fits; otherwise two products with the explicit Fourier vectors: P1 = G Phi, Gy = D (Phi^H P1) D
-    constexpr bool fft_on = true;   // (the DFT-by-GEMM form was a run-time switch until round 4)
     FftPlan plan;
-    if (fft_on && fft_plan(T, plan)) {
+    if (fft_plan(T, plan)) {
       fft_batch(st, plan, T, G.get(), nullptr, T, 1, +1.0, P1.r(), P1.im.get(), m, 1, m, nullptr, nullptr, 1.0);
       fft_batch(st, plan, m, P1.r(), P1.im.get(), 1, m, -1.0, Gy.r(), Gy.im.get(), 1, m, m, an.h.get(), an.h.get(), 1.0 / (double)T);
       hipLaunchKernelGGL(hermitize_kernel, ew_grid((int64_t)m * m), dim3(EW_BLOCK), 0, st, Gy.r(), Gy.im.get(), m);
@@ -966,23 +1076,10 @@ class Solver {
     XMCA_HIP(hipStreamSynchronize(st));     // G, P1 are released on return
   }
 
-  void reduce_analytic(const FieldData<TI>& f, const Analytic& an, AReduced& R, EvdInfo* info, bool want_vectors) {
+  void reduce_analytic(const FieldData<TI>& f, const Analytic& an, Reduced& R, EvdInfo* info, bool want_vectors) {
     CPlanes Gy;
     analytic_gram(f, an, Gy);
-    reduce_analytic_gram(Gy, an, R, info, want_vectors);
-  }
-  void reduce_analytic_gram(const CPlanes& Gy, const Analytic& an, AReduced& R, EvdInfo* info, bool want_vectors) {
-    const int m = an.m;
-    tm.begin("eigh");
-    if (want_vectors) R.Wh.ensure((size_t)m * m, true);
-    R.s.ensure((size_t)m);
-    DevBuf<double> lam_dev;
-    lam_dev.ensure((size_t)m);
-    hermitian_evd(st, ews, Gy.r(), Gy.im.get(), m, m, R.lam, lam_dev.get(), want_vectors ? R.Wh.r() : nullptr,
-                  want_vectors ? R.Wh.im.get() : nullptr, m, info);
-    hipLaunchKernelGGL(sqrt_clamp_kernel, dim3(ceil_div(m, 256)), dim3(256), 0, st, lam_dev.get(), R.s.get(), m, 1.0);
-    XMCA_HIP(hipStreamSynchronize(st));
-    tm.end();
+    reduce_gram(Gy, an.m, true, R, info, want_vectors);
   }
 
   // Vt[i][:] = normalised  sum_t b_i[t] X[t][:]  with  b_i = Phi D conj(E[i][:])  for i < nv; rows nv..rows_total-1 are zero
@@ -997,9 +1094,8 @@ class Solver {
     Bt.ensure((size_t)nv * T, true);
     // Bt[i][t] = sum_k h_k conj(E[i][k]) exp(2 pi i k t / T) / sqrt(T)      (nv x T): nv zero-padded DFTs of length T, or
     // Bt = conj(E D) Phi^T as a product with the explicit Fourier vectors
-    constexpr bool fft_on = true;   // (the DFT-by-GEMM form was a run-time switch until round 4)
     FftPlan plan;
-    if (fft_on && fft_plan(T, plan)) {
+    if (fft_plan(T, plan)) {
       fft_batch(st, plan, nv, Er, Ei, m, 1, +1.0, Bt.r(), Bt.im.get(), T, 1, T, nullptr, nullptr, 1.0 / std::sqrt((double)T), m, true,
                 an.h.get());
     } else {
@@ -1020,12 +1116,13 @@ class Solver {
     XMCA_HIP(hipStreamSynchronize(st));
   }
 
-  // Weak modes of the analytic two-field model (the counterpart of refine_by_deflation in the Fourier subspace).
-  // H = M Gy_b M^H / dof^2 is formed with an absolute error of ~50 eps lambda_1: its eigenvalues below ~1e-3 sigma_1 lose
+  // Weak modes of a one-sided solve (one_sided_core; the counterpart of refine_by_deflation inside the small problem, in
+  // either frame - the figures below were measured in the analytic one).  H = M G_b M^H / dof^2 is formed with an absolute
+  // error of ~50 eps lambda_1: its eigenvalues below ~1e-3 sigma_1 lose
   // digits like (sigma_1 / sigma_m)^2 (measured at BASELINE configs[2], sigma_1 / sigma_2500 = 9e4: 49 of the 2500
   // singular values beyond 1e-5 of the reference's, median 7e-7 over the noise floor; near-degenerate weak vectors mixed
   // at 1e-2) while its eigenVECTORS still split the strong from the weak part cleanly.  The rows of Er (= p_i^H M) and
-  // El (= Er Gy_b) below the 1e-3 line give the weak block of H without passing through lambda_1:
+  // El (= Er G_b) below the 1e-3 line give the weak block of H without passing through lambda_1:
   //     H_w[i][j] = p_i^H H p_j = El_i Er_j^H / dof^2        (norm sigma_{ns+1}^2, error eps sigma_1 sigma_w)
   // and its eigen-decomposition H_w = Z^H L Z - a nearly diagonal matrix, two or three Jacobi sweeps - replaces sigma and
   // rotates the weak rows: Er_w <- Z Er_w, El_w <- Z El_w.  Up to three levels, as in refine_by_deflation; same switch.
@@ -1060,12 +1157,12 @@ class Solver {
     XMCA_HIP(hipStreamSynchronize(st));       // temporaries
   }
 
-  // Ga / Gb: metrics of the left / right coefficient rows (Gy_a, Gy_b) for the projection above, or null
-  void refine_weak_block(CPlanes& Er, CPlanes& El, int nv, int m, double dof, SolveResult& out, bool cplx = true,
-                         const CPlanes* Ga = nullptr, const CPlanes* Gb = nullptr) {
+  // Ga / Gb: metrics of the left / right coefficient rows for the projection above
+  void refine_weak_block(CPlanes& Er, CPlanes& El, int nv, int m, double dof, SolveResult& out, bool cplx, const CPlanes& Ga,
+                         const CPlanes& Gb) {
     out.weak_refined = false;
     if constexpr (std::is_same<TI, float>::value) return;        // float32 fields: sigma is resolved to 6e-8 sigma_1 at best
-    static const double thr = [] { const char* e = std::getenv("XMCA_DEFLATE_BELOW"); return e ? std::atof(e) : 1e-3; }();   // 0: off
+    const double thr = deflate_below();
     if (thr <= 0.0 || nv <= 1 || !(out.sigma[0] > 0.0)) return;
     int done = 0;
     for (int level = 0; level < 3; ++level) {
@@ -1097,10 +1194,8 @@ class Solver {
         if (cplx) XMCA_HIP(hipMemcpyAsync(im, Tmp.im.get(), sizeof(double) * (size_t)nw * m, hipMemcpyDeviceToDevice, st));
       }
       XMCA_HIP(hipStreamSynchronize(st));
-      if (Ga && Gb) {
-        project_out_rows(Er, *Gb, done, ns, nv, m, cplx);
-        project_out_rows(El, *Ga, done, ns, nv, m, cplx);
-      }
+      project_out_rows(Er, Gb, done, ns, nv, m, cplx);
+      project_out_rows(El, Ga, done, ns, nv, m, cplx);
       tm.end();
       for (int j = 0; j < nw; ++j) out.sigma[ns + j] = std::sqrt(std::max(lam[j], 0.0));
       done = ns;
@@ -1108,15 +1203,16 @@ class Solver {
     out.weak_refined = true;
   }
 
-  static bool analytic_applicable(const FieldData<TI>* fields, int n_fields) {
-    for (int k = 0; k < n_fields; ++k)
-      if (fields[k].N <= fields[k].T || fields[k].has_im) return false;
-    return true;
+  // Whether a complexified model is solved in the analytic frame: the subspace formulation is exact for the Fourier-diagonal
+  // circulant Hilbert operator only (the extended one is applied as a GEMM), and it needs real fields that are all wider
+  // than T.  XMCA_ANALYTIC=0: never (the imaginary planes are formed and the model takes the time-space routes).
+  static bool analytic_route(bool circulant, int64_t T, int64_t Nx, int64_t Ny, int n_fields, bool has_im) {
+    static const bool on = [] { const char* e = std::getenv("XMCA_ANALYTIC"); return !(e && e[0] == '0'); }();
+    return on && circulant && !has_im && Nx > T && (n_fields == 1 || Ny > T);
   }
 
   // M with M^H M = G (n x n Hermitian, positive semi-definite) as the UNSHIFTED Cholesky factor - the cheap replacement of
-  // the eigen-factor S W^H of the field that the one-sided routes decompose.  Any factor serves them: with H = M G_b M^H / dof^2
-  // = P L P^H, q = M^H p solves G_a G_b q = sigma^2 dof^2 q, and the singular vectors are X~b^H q and X~a^H G_b q, whatever M is.
+  // the eigen-factor S Z of the field that the one-sided solve decomposes (any factor serves it: one_sided_core).
   // Both factors are exact for a matrix eps |G| away from G; what the eigen-factor has on top is the eigensolver's handling
   // of graded spectra (LR step), so a factor whose pivots span more than `1e8` (variances) is refused and the caller
   // decomposes the field as before.  No shift (a ridge delta moves sigma_i^2 by delta / lambda_a,i, relative): the one null
@@ -1184,164 +1280,27 @@ class Solver {
     out.Vt32[1].release();
     const FieldData<TI>& A = fields[0];
     const int T = (int)A.T;
-    const double dof = (double)(T - 1);
     Analytic an;
     analytic_basis(T, an);
     const int m = an.m;
     out.cplx = true;
     out.weak_refined = false;
     for (EvdInfo& e : out.evd_info) e = EvdInfo();
+    const Frame fr{m, true, &an};
+    if (n_fields == 2) {
+      solve_wide_pair(fr, fields, n_vec_req, out);
+      return;
+    }
     out.rank = T;                                   // min(T, N) as the reference reports it (array.py:597)
     const int n_vec = n_vec_req < 0 ? T : std::min(n_vec_req, T);
-    const int nv = std::min(n_vec, m);              // modes that can be non-null
     out.n_vec = n_vec;
-    out.sigma.assign(T, 0.0);
-    AReduced Ra, Rb;
-    if (n_fields == 2 && n_vec == 0 && cholesky_enabled()) {
-      CPlanes Gya, Gyb;
-      analytic_gram(A, an, Gya);
-      analytic_gram(fields[1], an, Gyb);
-      if (values_by_cholesky(Gya, Gyb, m, true, dof, out)) {      // sigma[m..T) stay exact zeros
-        out.ldv[0] = A.N;
-        out.ldv[1] = fields[1].N;
-        return;
-      }
-    }
-    static const bool one_sided_on = [] { const char* e = std::getenv("XMCA_ONE_SIDED"); return !(e && e[0] == '0'); }();
-    CPlanes Fm, Gya;                   // factor of Gy_a used by the one-sided route: Cholesky (Fm) or eigen (Ra.s, Ra.Wh)
-    bool by_chol = false;
-    if (n_fields == 2 && one_sided_on) {
-      analytic_gram(A, an, Gya);
-      by_chol = factor_by_cholesky(Gya, m, true, false, Fm);
-      if (!by_chol) reduce_analytic_gram(Gya, an, Ra, &out.evd_info[0], true);
-    } else {
-      reduce_analytic(A, an, Ra, &out.evd_info[0], n_fields == 2 || n_vec != 0);
-    }
-    if (n_fields == 1) {
-      for (int i = 0; i < m; ++i) out.sigma[i] = std::max(Ra.lam[i], 0.0) / dof;
-      out.ldv[0] = A.N;
-      tm.begin("backproject");
-      if (n_vec > 0) analytic_project(A, an, Ra.Wh.r(), Ra.Wh.im.get(), nv, n_vec, out.Vt[0]);
-      tm.end();
-      return;
-    }
-    const FieldData<TI>& B = fields[1];
-    if (one_sided_on) {
-      // second field as an operator (see solve_one_sided): H = M Gy_b M^H / dof^2 with M^H M = Gy_a - the Cholesky factor
-      // (factor_by_cholesky: no eigen-decomposition of the first field at all) or the eigen-factor S_a Wh_a
-      CPlanes Gyb;
-      analytic_gram(B, an, Gyb);
-      out.ldv[0] = A.N;
-      out.ldv[1] = B.N;
-      // returns false when the Cholesky factor turned out not to be good enough (left vectors not orthogonal: see below)
-      auto with_factor = [&](const CPlanes& Mf, const double* ms, bool guard) -> bool {
-        CPlanes M1, H, Ph;
-        tm.begin("kernel");
-        M1.ensure((size_t)m * m, true);
-        H.ensure((size_t)m * m, true);
-        cgemm<double>(st, gws, Mf.r(), Mf.im.get(), m, true, false, Gyb.r(), Gyb.im.get(), m, true, false, M1.r(), M1.im.get(), m, m, m,
-                      m, 1.0, ms, nullptr, false);
-        cgemm<double>(st, gws, M1.r(), M1.im.get(), m, true, false, Mf.r(), Mf.im.get(), m, false, true, H.r(), H.im.get(), m, m, m, m,
-                      1.0 / (dof * dof), nullptr, ms, true);
-        tm.end();
-        std::vector<double> lam;
-        tm.begin("kernel_svd");
-        if (n_vec > 0) Ph.ensure((size_t)m * m, true);
-        hermitian_evd(st, ews, H.r(), H.im.get(), m, m, lam, nullptr, n_vec > 0 ? Ph.r() : nullptr, n_vec > 0 ? Ph.im.get() : nullptr, m,
-                      &out.evd_info[2]);
-        XMCA_HIP(hipStreamSynchronize(st));
-        tm.end();
-        for (int i = 0; i < m; ++i) out.sigma[i] = std::sqrt(std::max(lam[i], 0.0));
-        if (n_vec == 0) return true;
-        tm.begin("backproject");
-        // E_right = Ph M (rows = conj of the subspace coefficients of q_m = M^H p_m),  E_left = E_right Gy_b
-        CPlanes Ws, Er, El;
-        Ws.ensure((size_t)nv * m, true);
-        Er.ensure((size_t)nv * m, true);
-        El.ensure((size_t)nv * m, true);
-        XMCA_HIP(hipMemcpyAsync(Ws.r(), Ph.r(), sizeof(double) * (size_t)nv * m, hipMemcpyDeviceToDevice, st));
-        XMCA_HIP(hipMemcpyAsync(Ws.im.get(), Ph.im.get(), sizeof(double) * (size_t)nv * m, hipMemcpyDeviceToDevice, st));
-        if (ms)
-          hipLaunchKernelGGL(scale_kernel, ew_grid((int64_t)nv * m), dim3(EW_BLOCK), 0, st, Ws.r(), Ws.im.get(), (int64_t)m, nv, m, ms, 0, 0);
-        cgemm<double>(st, gws, Ws.r(), Ws.im.get(), m, true, false, Mf.r(), Mf.im.get(), m, true, false, Er.r(), Er.im.get(), m, nv, m,
-                      m, 1.0, nullptr, nullptr, false);
-        cgemm<double>(st, gws, Er.r(), Er.im.get(), m, true, false, Gyb.r(), Gyb.im.get(), m, true, false, El.r(), El.im.get(), m, nv, m, m,
-                      1.0, nullptr, nullptr, false);
-        tm.end();
-        refine_weak_block(Er, El, nv, m, dof, out, true, &Gya, &Gyb);
-        if (guard && nv > 1) {
-          // The left vectors are u_i ~ X~a^H g_i with g_i = E_left,i^H: their Gram matrix is E_l Gy_a E_l^H (nv x nv, two small
-          // products).  On spectra graded over many decades E_l = E_r Gy_b cancels down to the weak rows and the Cholesky
-          // factor - unlike the eigen-factor, whose weak rows are small numbers to begin with - leaves u_weak with a component
-          // along the strong modes that project_out_rows has to remove (2e-8 left on the 10-decade probe, 4e-8 at C3 - the leading
-          // modes among themselves, the same with either factor).  Above 1e-6 the factor is not trusted: decompose the field.
-          tm.begin("orthogonality_check");
-          int n_check = 0;                                     // null modes carry arbitrary vectors
-          while (n_check < nv && out.sigma[n_check] > 1e-9 * out.sigma[0]) ++n_check;
-          const double worst = coherence(El, Gya, nv, m, n_check, true);
-          tm.end();
-          static const bool trace = xmca_trace("solve");
-          if (trace) std::fprintf(stderr, "[xmca solve] Cholesky factor: left-vector coherence %.3e over %d modes\n", worst, n_check);
-          if (!(worst < 1e-6)) return false;
-        }
-        tm.begin("backproject");
-        analytic_project(B, an, Er.r(), Er.im.get(), nv, n_vec, out.Vt[1]);
-        analytic_project(A, an, El.r(), El.im.get(), nv, n_vec, out.Vt[0]);
-        tm.end();
-        return true;
-      };
-      if (by_chol && with_factor(Fm, nullptr, true)) return;
-      if (by_chol) reduce_analytic_gram(Gya, an, Ra, &out.evd_info[0], true);
-      with_factor(Ra.Wh, Ra.s.get(), false);
-      return;
-    }
-    reduce_analytic(B, an, Rb, &out.evd_info[1], true);
-    // K = S_a Wh_a Wh_b^H S_b / dof   (m x m)
-    CPlanes K, H, Ph, Qh;
-    K.ensure((size_t)m * m, true);
-    tm.begin("kernel");
-    cgemm<double>(st, gws, Ra.Wh.r(), Ra.Wh.im.get(), m, true, false, Rb.Wh.r(), Rb.Wh.im.get(), m, false, true, K.r(), K.im.get(), m, m, m,
-                  m, 1.0 / dof, Ra.s.get(), Rb.s.get(), false);
-    tm.end();
-    tm.begin("kernel_svd");
-    H.ensure((size_t)m * m, true);
-    std::vector<double> lam;
-    cgemm<double>(st, gws, K.r(), K.im.get(), m, false, true, K.r(), K.im.get(), m, true, false, H.r(), H.im.get(), m, m, m, m, 1.0,
-                  nullptr, nullptr, true);
-    if (n_vec > 0) {
-      Qh.ensure((size_t)m * m, true);
-      Ph.ensure((size_t)m * m, true);
-      hermitian_evd(st, ews, H.r(), H.im.get(), m, m, lam, nullptr, Qh.r(), Qh.im.get(), m, &out.evd_info[2]);
-      cgemm<double>(st, gws, Qh.r(), Qh.im.get(), m, true, false, K.r(), K.im.get(), m, false, true, Ph.r(), Ph.im.get(), m, m, m, m, 1.0,
-                    nullptr, nullptr, false);
-      hipLaunchKernelGGL((normalize_rows_kernel<double>), dim3(m), dim3(256), 0, st, Ph.r(), Ph.im.get(), (int64_t)m, m, 0,
-                         (double*)nullptr);
-      XMCA_HIP(hipGetLastError());
-    } else {
-      hermitian_evd(st, ews, H.r(), H.im.get(), m, m, lam, nullptr, nullptr, nullptr, m, &out.evd_info[2]);
-    }
-    XMCA_HIP(hipStreamSynchronize(st));
-    tm.end();
-    for (int i = 0; i < m; ++i) out.sigma[i] = std::sqrt(std::max(lam[i], 0.0));
+    out.sigma.assign(T, 0.0);                       // sigma[m, T) stay exact zeros
+    Reduced Ra;
+    reduce_analytic(A, an, Ra, &out.evd_info[0], n_vec != 0);
+    for (int i = 0; i < m; ++i) out.sigma[i] = std::max(Ra.lam[i], 0.0) / (double)(T - 1);
     out.ldv[0] = A.N;
-    out.ldv[1] = B.N;
-    if (n_vec == 0) return;
     tm.begin("backproject");
-    // E_left = (Qh diag(s_b)) Wh_b ,  E_right = (Ph diag(s_a)) Wh_a   (first nv rows)
-    auto side = [&](const FieldData<TI>& self, const CPlanes& Wsmall, const AReduced& other, CPlanes& Vt) {
-      CPlanes Ws, E;
-      Ws.ensure((size_t)nv * m, true);
-      E.ensure((size_t)nv * m, true);
-      XMCA_HIP(hipMemcpyAsync(Ws.r(), Wsmall.r(), sizeof(double) * (size_t)nv * m, hipMemcpyDeviceToDevice, st));
-      XMCA_HIP(hipMemcpyAsync(Ws.im.get(), Wsmall.im.get(), sizeof(double) * (size_t)nv * m, hipMemcpyDeviceToDevice, st));
-      hipLaunchKernelGGL(scale_kernel, ew_grid((int64_t)nv * m), dim3(EW_BLOCK), 0, st, Ws.r(), Ws.im.get(), (int64_t)m, nv, m,
-                         other.s.get(), 0, 0);
-      cgemm<double>(st, gws, Ws.r(), Ws.im.get(), m, true, false, other.Wh.r(), other.Wh.im.get(), m, true, false, E.r(), E.im.get(), m,
-                    nv, m, m, 1.0, nullptr, nullptr, false);
-      analytic_project(self, an, E.r(), E.im.get(), nv, n_vec, Vt);
-    };
-    side(A, Qh, Rb, out.Vt[0]);
-    side(B, Ph, Ra, out.Vt[1]);
+    if (n_vec > 0) project(fr, A, Ra.Z, std::min(n_vec, m), n_vec, out.Vt[0]);
     tm.end();
   }
 
@@ -1356,13 +1315,14 @@ class Solver {
     XMCA_HIP(hipStreamSynchronize(st));
   }
 
-  // singular vectors of `self` in grid space.
+  // singular vectors of `self` in grid space when at least one field is no wider than T (solve_core).
   //   self unreduced : V = own small singular vectors  -> Vt = conj(Oh)
-  //   self reduced   : V ~ X~self^H (F_other w_m)  with w the OTHER side's small singular vectors (Wh rows = conj(w_m))
-  void project_side(const FieldData<TI>& self, const FieldData<TI>& other, bool cplx, const Reduced& Rs, const Reduced& Ro,
-                    const CPlanes& Oh, const CPlanes& Wh, int r_self, int r_other, int m, CPlanes& Vt) {
+  //   self reduced   : V ~ X~self^H (X~other w_m)  with w the OTHER side's small singular vectors (Wh rows = conj(w_m)); the other
+  //                    field is then the narrow one and its own factor
+  void project_side(const FieldData<TI>& self, const FieldData<TI>& other, bool cplx, bool self_reduced, const CPlanes& Oh,
+                    const CPlanes& Wh, int r_self, int r_other, int m, CPlanes& Vt) {
     const int T = (int)self.T;
-    if (!Rs.reduced) {
+    if (!self_reduced) {
       Vt.ensure((size_t)m * r_self, cplx);
       XMCA_HIP(hipMemcpyAsync(Vt.r(), Oh.r(), sizeof(double) * (size_t)m * r_self, hipMemcpyDeviceToDevice, st));
       if (cplx) {
@@ -1372,27 +1332,15 @@ class Solver {
       XMCA_HIP(hipStreamSynchronize(st));
       return;
     }
-    // Th[m][t] = sum_j Wh[m][j] conj(F_other[t][j])
+    // Th[m][t] = sum_j Wh[m][j] conj(X~other[t][j])
     CPlanes Th;
     Th.ensure((size_t)m * T, cplx);
-    if (Ro.reduced) {
-      // conj(F_o[t][j]) = Z_o[j][t] s_j  ->  Th = (Wh diag(s_o)) Z_o
-      CPlanes Ws;
-      Ws.ensure((size_t)m * r_other, cplx);
-      XMCA_HIP(hipMemcpyAsync(Ws.r(), Wh.r(), sizeof(double) * (size_t)m * r_other, hipMemcpyDeviceToDevice, st));
-      if (cplx) XMCA_HIP(hipMemcpyAsync(Ws.im.get(), Wh.im.get(), sizeof(double) * (size_t)m * r_other, hipMemcpyDeviceToDevice, st));
-      hipLaunchKernelGGL(scale_kernel, ew_grid((int64_t)m * r_other), dim3(EW_BLOCK), 0, st, Ws.r(), Ws.i(cplx), (int64_t)r_other, m,
-                         r_other, Ro.s.get(), 0, 0);
-      cgemm<double>(st, gws, Ws.r(), Ws.i(cplx), r_other, true, false, Ro.Z.r(), Ro.Z.i(cplx), T, true, false, Th.r(), Th.i(cplx), T,
-                    m, T, r_other, 1.0, nullptr, nullptr, false);
-      XMCA_HIP(hipStreamSynchronize(st));
-    } else {
-      // conj(F_o[t][j]) = conj(X~o[t][j])
+    {
       Narrow<TI> w;
       w.from(st, Wh.r(), Wh.i(cplx), (int64_t)m * r_other);
       cgemm<TI>(st, gws, w.r, w.i, r_other, true, false, other.r(), other.i(), other.N, false, true, Th.r(), Th.i(cplx), T, m, T,
                 r_other, 1.0, nullptr, nullptr, false);
-      XMCA_HIP(hipStreamSynchronize(st));
+      XMCA_HIP(hipStreamSynchronize(st));     // `w` is released
     }
     back_project(self, cplx, Th.r(), Th.i(cplx), m, Vt);
   }

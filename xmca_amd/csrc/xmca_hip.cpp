@@ -341,9 +341,8 @@ template <typename TI>
 void solve_impl(xmca_handle* h, int n_fields, int64_t n_vec) {
   FieldData<TI>* f = typed<TI>(h).f;
   if (h->op_pending) {
-    static const bool analytic_on = [] { const char* e = std::getenv("XMCA_ANALYTIC"); return !(e && e[0] == '0'); }();
-    // the subspace formulation is exact for the Fourier-diagonal circulant operator only; the extended one is applied as a GEMM
-    if (h->op.kind == ComplexOp::CIRCULANT && analytic_on && Solver<TI>::analytic_applicable(f, n_fields)) {
+    if (Solver<TI>::analytic_route(h->op.kind == ComplexOp::CIRCULANT, f[0].T, f[0].N, n_fields == 2 ? f[1].N : 0, n_fields,
+                                   f[0].has_im || (n_fields == 2 && f[1].has_im))) {
       Solver<TI> s(h->st, h->gws, h->ews, h->tm);
       s.solve_analytic(f, n_fields, (int)n_vec, h->res);
       return;
@@ -940,13 +939,11 @@ struct ReplicateRunner {
   RotationDevice rd;
   DevBuf<double> sigma_dev;
 
-  // only the circulant Hilbert operator may take the analytic route
   ReplicateRunner(xmca_handle* h_, const ReplicateSpec& s)
       : h(h_), T(s.T), Ns{s.Nx, s.Ny}, n_fields(s.n_fields), rotated(s.rotated), p(s.p), power(s.power), tol(s.tol), cplx(s.op != nullptr),
         solver(h_->st, h_->gws, h_->ews, h_->tm), rot(h_->st, h_->tm, h_->gws, h_->ews) {
     const ComplexOp* op = s.op;
-    static const bool analytic_on = [] { const char* e = std::getenv("XMCA_ANALYTIC"); return !(e && e[0] == '0'); }();
-    analytic = cplx && op->kind == ComplexOp::CIRCULANT && analytic_on && s.Nx > T && (n_fields == 1 || s.Ny > T);
+    analytic = cplx && Solver<TI>::analytic_route(op->kind == ComplexOp::CIRCULANT, T, s.Nx, s.Ny, n_fields, false);
     if (cplx) XMCA_CHECK(op->T == T, XMCA_ERR_INVALID, "replicates: the operator was made for another number of time steps");
     if (cplx && !analytic) build_operator<TI>(h, *op, htb);
   }
