@@ -3,14 +3,16 @@
 // Loadings live as planes in mode-major order:  A[j][n]  (p modes x N grid points, ld = N), so a wave reads
 // 64 consecutive grid points of one mode per instruction.
 //
-// One Varimax iteration (xmca/tools/rotation.py:52-64) = two launches, no host round trip:
-//   varimax_accum_kernel : a SINGLE pass over the loadings:  z = a_n R,  w = |z|^2 z - z c/n,  G += a_n^H w
+// One Varimax iteration (xmca/tools/rotation.py:52-64), no host round trip:
+//   rot_accum_body<0>    : a SINGLE pass over the loadings:  z = a_n R,  w = |z|^2 z - z c/n,  G += a_n^H w
 //                          (column sums c_k = sum_n |z_nk|^2 are obtained without a pass over N as
 //                          diag(R^H (A^H A) R)); per-workgroup partial G's.
-//   varimax_step_kernel  : one workgroup: reduce partials, one-sided Jacobi SVD of the p x p matrix
-//                          (16-lane groups, one column pair each), R = U V^H, d = sum(s), the reference's
-//                          stopping rule |d - d_old| / d < tol, iteration counter, next c.
-// After convergence (or NaN) both kernels turn into no-ops, so the host can enqueue iterations in batches
+//   the step             : sum of the partials in a fixed order, R = unitary polar factor of G (Newton-Schulz),
+//                          d = Re tr(R^H G), the reference's stopping rule |d - d_old| / d < tol, iteration
+//                          counter, next c.
+// varimax_init_kernel sets R = I, c and the state block; the loop is varimax_persistent_kernel (one launch),
+// varimax_iter_kernel (one launch per iteration) or, on the fourth moments, varimax_moment_kernel (one workgroup).
+// After convergence (or NaN) varimax_iter_kernel turns into a no-op, so the host can enqueue iterations in batches
 // and look at the state block only once per batch; the stop iteration is decided on the device.
 #pragma once
 #include "common.h"
@@ -23,7 +25,8 @@ constexpr int ROT_PMAX = 64;     // max number of rotated modes
 constexpr int ROT_PB = 64;       // grid points per batch inside a workgroup
 constexpr int ROT_LDP = ROT_PB + 1;
 
-// state block (doubles): [0]=iter [1]=converged [2]=d [3]=d_old [4]=nan_flag [5]=svd_sweeps(last)
+// state block (doubles): [0]=iter [1]=converged [2]=d [3]=d_old [4]=nan_flag (2: the persistent kernel gave up)
+// [5]=Newton-Schulz iterations of the last polar step [6]=its lower bound for the next one
 constexpr int ROT_STATE_N = 8;
 
 // the same for the float32-resident vectors of a real one-field float32 model: L = float(V) * float(sqrt(float(sigma))), a
@@ -183,7 +186,8 @@ __global__ void rot_point_scale_kernel(double* __restrict__ Xr, double* __restri
 }
 
 // Generic single-pass accumulation over grid points (one p x p result per launch).
-//   MODE 0 (Varimax step): Z = A R ;  W = |Z|^2 Z - Z c / N ;             out = A^H W
+//   MODE 0 (Varimax step): Z = A R ;  W = |Z|^2 Z - gamma Z c / N ;       out = A^H W   (gamma in the `power` argument; only
+//                          as the body of varimax_iter_kernel / varimax_persistent_kernel: no rot_accum_kernel<.., 0, 0>)
 //   MODE 1 (Gram)        : out = A^H A
 //   MODE 2 (Promax fit)  : B = h (A R); h2 = |B_n|; X = B / h2; Xn = X / colmax; Y = Xn |Xn|^(power-1)
 //                          SEL 0: X^H X   SEL 1: X^H Y   SEL 2: sum_{n<Nleft} h2^2 x^H x   SEL 3: same over n>=Nleft
@@ -462,261 +466,20 @@ __device__ void rot_colsums(const double* Rr, const double* Ri, const double* A0
   }
 }
 
-// One workgroup (256 threads): G = sum partials ; SVD by one-sided Jacobi ; R = U V^H ; d ; stop rule ; next c.
+// One workgroup (256 threads) in front of every Varimax loop: R = I, c from A0 (= diag(R^H A0 R)), state reset.
 template <bool CPLX>
-__global__ __launch_bounds__(256) void varimax_step_kernel(const double* __restrict__ part_r, const double* __restrict__ part_i,
-                                                           int nwg, int p, const double* __restrict__ A0r,
-                                                           const double* __restrict__ A0i, double* __restrict__ Rr,
-                                                           double* __restrict__ Ri, double* __restrict__ Wr,
-                                                           double* __restrict__ Wi, double* __restrict__ cvec,
-                                                           double* __restrict__ state, double tol, int init_only) {
-  constexpr int LD = ROT_PMAX + 1;
-  __shared__ double Gr[ROT_PMAX][LD], Gi[CPLX ? ROT_PMAX : 1][CPLX ? LD : 1];
-  __shared__ double Vr[ROT_PMAX][LD], Vi[CPLX ? ROT_PMAX : 1][CPLX ? LD : 1];
-  __shared__ double sig[ROT_PMAX];
-  __shared__ double red2r[256], red2i[CPLX ? 256 : 1];
-  __shared__ int flag;
+__global__ __launch_bounds__(256) void varimax_init_kernel(int p, const double* __restrict__ A0r, const double* __restrict__ A0i,
+                                                           double* __restrict__ Rr, double* __restrict__ Ri, double* __restrict__ cvec,
+                                                           double* __restrict__ state) {
   const int tid = threadIdx.x;
-  if (init_only) {
-    // R = I, c from A0, state reset
-    for (int e = tid; e < p * p; e += 256) {
-      Rr[e] = Wr[e] = (e / p == e % p) ? 1.0 : 0.0;
-      if (CPLX) Ri[e] = Wi[e] = 0.0;
-    }
-    __syncthreads();
-    __threadfence_block();
-    rot_colsums<CPLX>(Rr, Ri, A0r, A0i, p, cvec, tid, 256);
-    if (tid < ROT_STATE_N) state[tid] = 0.0;
-    return;
-  }
-  if (state[1] != 0.0 || state[4] != 0.0) return;
-
-  // G = sum of the per-workgroup partials: 256 / p^2 thread slices per entry, combined in a fixed order
-  const int pp = p * p;
-  const int nsl = pp <= 128 ? 256 / pp : 1;
-  if (nsl > 1) {
-    const int sl = tid / pp, e = tid % pp;
-    if (sl < nsl) {
-      double sr = 0.0, si = 0.0;
-      for (int w = sl; w < nwg; w += nsl) {
-        sr += part_r[(int64_t)w * pp + e];
-        if (CPLX) si += part_i[(int64_t)w * pp + e];
-      }
-      red2r[tid] = sr;
-      if (CPLX) red2i[tid] = si;
-    }
-    __syncthreads();
-  }
   for (int e = tid; e < p * p; e += 256) {
-    double sr = 0.0, si = 0.0;
-    if (nsl > 1) {
-      for (int sl = 0; sl < nsl; ++sl) {
-        sr += red2r[sl * pp + e];
-        if (CPLX) si += red2i[sl * pp + e];
-      }
-    } else {
-      for (int w = 0; w < nwg; ++w) {
-        sr += part_r[(int64_t)w * pp + e];
-        if (CPLX) si += part_i[(int64_t)w * pp + e];
-      }
-    }
-    const int j = e / p, k = e % p;
-    // warm start: V <- right singular vectors of the previous iteration (G changes slowly, so G V_prev is already
-    // nearly column-orthogonal and the Jacobi sweeps below converge in one or two passes); G is staged in V's
-    // place for the product and swapped in afterwards.
-    Vr[j][k] = sr;
-    if constexpr (CPLX) Vi[j][k] = si;
+    Rr[e] = (e / p == e % p) ? 1.0 : 0.0;
+    if (CPLX) Ri[e] = 0.0;
   }
   __syncthreads();
-  for (int e = tid; e < p * p; e += 256) {
-    const int j = e / p, k = e % p;
-    double ar = 0.0, ai = 0.0;
-    for (int m = 0; m < p; ++m) {
-      const double gr = Vr[j][m], wr = Wr[m * p + k];
-      ar += gr * wr;
-      if constexpr (CPLX) {
-        const double gi = Vi[j][m], wi = Wi[m * p + k];
-        ar -= gi * wi;
-        ai += gr * wi + gi * wr;
-      }
-    }
-    Gr[j][k] = ar;
-    if constexpr (CPLX) Gi[j][k] = ai;
-  }
-  __syncthreads();
-  for (int e = tid; e < p * p; e += 256) {
-    const int j = e / p, k = e % p;
-    Vr[j][k] = Wr[e];
-    if constexpr (CPLX) Vi[j][k] = Wi[e];
-  }
-  __syncthreads();
-
-  // one-sided Jacobi: orthogonalise the columns of G (G V = U S).  16-lane groups own one column pair each.
-  const int pe = (p + 1) & ~1;             // even number of players (last one is a dummy when p is odd)
-  const int npairs = pe / 2;
-  const int grp = tid >> 4, gl = tid & 15;
-  int sweeps = 0;
-  for (int sweep = 0; sweep < 60; ++sweep) {
-    if (tid == 0) flag = 0;
-    __syncthreads();
-    for (int step = 0; step < pe - 1; ++step) {
-      for (int pr = grp; pr < npairs; pr += 16) {
-        int a, b;
-        if (pr == 0) { a = pe - 1; b = step; }
-        else { a = (step + pr) % (pe - 1); b = (step - pr + (pe - 1)) % (pe - 1); }
-        const int ca = min(a, b), cb = max(a, b);
-        if (cb >= p) continue;   // dummy player
-        double al = 0.0, be = 0.0, gr = 0.0, gi = 0.0;
-        for (int i = gl; i < p; i += 16) {
-          const double xr = Gr[i][ca], yr = Gr[i][cb];
-          al += xr * xr; be += yr * yr; gr += xr * yr;
-          if constexpr (CPLX) {
-            const double xi = Gi[i][ca], yi = Gi[i][cb];
-            al += xi * xi; be += yi * yi;
-            gr += xi * yi;                 // conj(x) y = (xr - i xi)(yr + i yi)
-            gi += xr * yi - xi * yr;
-          }
-        }
-        for (int o = 8; o > 0; o >>= 1) {
-          al += __shfl_xor(al, o); be += __shfl_xor(be, o); gr += __shfl_xor(gr, o); gi += __shfl_xor(gi, o);
-        }
-        const double g2 = gr * gr + gi * gi;
-        if (g2 > 0.0 && g2 > 1e-29 * al * be) {
-          // same rotation as in jacobi.h: t = sign(d) 2|g| / (|d| + sqrt(d^2 + 4|g|^2)), one sqrt + one reciprocal
-          const double dd = be - al;
-          const double w = (dd >= 0.0 ? 2.0 : -2.0) / (fabs(dd) + sqrt(dd * dd + 4.0 * g2));
-          const double c = 1.0 / sqrt(1.0 + w * w * g2);
-          const double sr = w * c * gr, si = w * c * gi;
-          if (gl == 0) flag = 1;
-          for (int i = gl; i < p; i += 16) {
-            // new_a = c x - conj(sg) y ; new_b = sg x + c y
-            {
-              const double xr = Gr[i][ca], yr = Gr[i][cb];
-              if constexpr (!CPLX) {
-                Gr[i][ca] = c * xr - sr * yr; Gr[i][cb] = sr * xr + c * yr;
-              } else {
-                const double xi = Gi[i][ca], yi = Gi[i][cb];
-                Gr[i][ca] = c * xr - (sr * yr + si * yi); Gi[i][ca] = c * xi - (sr * yi - si * yr);
-                Gr[i][cb] = (sr * xr - si * xi) + c * yr; Gi[i][cb] = (sr * xi + si * xr) + c * yi;
-              }
-            }
-            {
-              const double xr = Vr[i][ca], yr = Vr[i][cb];
-              if constexpr (!CPLX) {
-                Vr[i][ca] = c * xr - sr * yr; Vr[i][cb] = sr * xr + c * yr;
-              } else {
-                const double xi = Vi[i][ca], yi = Vi[i][cb];
-                Vr[i][ca] = c * xr - (sr * yr + si * yi); Vi[i][ca] = c * xi - (sr * yi - si * yr);
-                Vr[i][cb] = (sr * xr - si * xi) + c * yr; Vi[i][cb] = (sr * xi + si * xr) + c * yi;
-              }
-            }
-          }
-        }
-      }
-      __syncthreads();
-    }
-    ++sweeps;
-    const int f = flag;
-    __syncthreads();
-    if (!f) break;
-  }
-
-  // singular values = column norms; U = G / s
-  for (int k = tid; k < p; k += 256) {
-    double acc = 0.0;
-    for (int i = 0; i < p; ++i) {
-      acc += Gr[i][k] * Gr[i][k];
-      if constexpr (CPLX) acc += Gi[i][k] * Gi[i][k];
-    }
-    sig[k] = sqrt(acc);
-  }
-  __syncthreads();
-  // R[j][k] = sum_m U[j][m] conj(V[k][m]) = sum_m G[j][m]/s_m * conj(V[k][m])
-  double rr_loc[ROT_PMAX * ROT_PMAX / 256], ri_loc[ROT_PMAX * ROT_PMAX / 256];
-  {
-    int slot = 0;
-    for (int e = tid; e < p * p; e += 256, ++slot) {
-      const int j = e / p, k = e % p;
-      double rr = 0.0, ri = 0.0;
-      for (int m = 0; m < p; ++m) {
-        const double inv = 1.0 / sig[m];
-        const double ur = Gr[j][m] * inv, vr = Vr[k][m];
-        rr += ur * vr;
-        if constexpr (CPLX) {
-          const double ui = Gi[j][m] * inv, vi = Vi[k][m];
-          rr += ui * vi;              // (ur + i ui)(vr - i vi)
-          ri += ui * vr - ur * vi;
-        }
-      }
-      Rr[e] = rr;
-      Wr[e] = Vr[j][k];
-      if (CPLX) { Ri[e] = ri; Wi[e] = Vi[j][k]; }
-#pragma unroll
-      for (int sl = 0; sl < ROT_PMAX * ROT_PMAX / 256; ++sl)
-        if (sl == slot) { rr_loc[sl] = rr; ri_loc[sl] = ri; }
-    }
-  }
-  __syncthreads();
-  // next column sums c_k = Re sum_j conj(R[j][k]) (A0 R)[j][k]: stage R in G's place and A0 in V's place
-  {
-    int slot = 0;
-    for (int e = tid; e < p * p; e += 256, ++slot) {
-      const int j = e / p, k = e % p;
-#pragma unroll
-      for (int sl = 0; sl < ROT_PMAX * ROT_PMAX / 256; ++sl)
-        if (sl == slot) { Gr[j][k] = rr_loc[sl]; if constexpr (CPLX) Gi[j][k] = ri_loc[sl]; }
-      Vr[j][k] = A0r[e];
-      if constexpr (CPLX) Vi[j][k] = A0i[e];
-    }
-  }
-  __syncthreads();
-  {
-    int slot = 0;
-    for (int e = tid; e < p * p; e += 256, ++slot) {
-      const int j = e / p, k = e % p;
-      double tr = 0.0, ti = 0.0;
-      for (int l = 0; l < p; ++l) {
-        const double ar = Vr[j][l], r_ = Gr[l][k];
-        tr += ar * r_;
-        if constexpr (CPLX) {
-          const double ai = Vi[j][l], ri_ = Gi[l][k];
-          tr -= ai * ri_;
-          ti += ar * ri_ + ai * r_;
-        }
-      }
-      double prod = Gr[j][k] * tr;
-      if constexpr (CPLX) prod += Gi[j][k] * ti;
-#pragma unroll
-      for (int sl = 0; sl < ROT_PMAX * ROT_PMAX / 256; ++sl)
-        if (sl == slot) rr_loc[sl] = prod;
-    }
-  }
-  __syncthreads();
-  {
-    int slot = 0;
-    for (int e = tid; e < p * p; e += 256, ++slot) {
-#pragma unroll
-      for (int sl = 0; sl < ROT_PMAX * ROT_PMAX / 256; ++sl)
-        if (sl == slot) Vr[e / p][e % p] = rr_loc[sl];
-    }
-  }
-  __syncthreads();
-  for (int k = tid; k < p; k += 256) {
-    double acc = 0.0;
-    for (int j = 0; j < p; ++j) acc += Vr[j][k];
-    cvec[k] = acc;
-  }
-  if (tid == 0) {
-    double d = 0.0;
-    for (int k = 0; k < p; ++k) d += sig[k];
-    const double d_old = state[2];
-    state[3] = d_old;
-    state[2] = d;
-    state[0] += 1.0;
-    state[5] = (double)sweeps;
-    if (!(d == d)) state[4] = 1.0;                          // NaN (e.g. a zero row in the loadings)
-    else if (fabs(d - d_old) / d < tol) state[1] = 1.0;     // rotation.py:62
-  }
+  __threadfence_block();
+  rot_colsums<CPLX>(Rr, Ri, A0r, A0i, p, cvec, tid, 256);
+  if (tid < ROT_STATE_N) state[tid] = 0.0;
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -1409,19 +1409,31 @@ struct RotateResult {
   double last_d = 0.0;
 };
 
-// Device state of one rotation problem: normalised loadings A (p x N planes), h, R, ...
+// Device state of one rotation problem, by the route that owns each buffer (RotRoute below)
 struct RotationDevice {
-  CPlanes A, R, A0, acc, W;   // W: right singular vectors of the previous Varimax step (warm start)
-  DevBuf<double> h, cvec, state, part_r, part_i, colmax;
-  DevBuf<unsigned int> counter;     // arrival ticket of the fused Varimax iteration kernel
-  DevBuf<unsigned int> pflags;      // persistent Varimax kernel: epoch flag per workgroup
+  CPlanes A, R, acc;                // every route: normalised loadings A (p x N planes), the rotation R, the p x p matrix of apply()
+  DevBuf<double> h;                 // ... and the row norms of the loadings
+  // fused routes: Gram matrix A0 = A^H A, column sums c and state block of the loop; the one-pass accumulation kernels (Gram,
+  // column maxima, Promax fits) sum their per-workgroup partials into A0 / acc
+  CPlanes A0;
+  DevBuf<double> cvec, state, part_r, part_i, colmax;
+  DevBuf<double> mpart, mom;        // fourth-moment route: per-workgroup partials of M', M'
+  DevBuf<unsigned int> pflags;      // persistent loop: epoch flag per workgroup
   DevBuf<double> ppart_r, ppart_i;  // ... and its double-buffered partials
-  DevBuf<double> mpart, mom;        // fourth-moment route (real, p <= ROT_MOMENT_PMAX): per-workgroup partials of M', M'
+  DevBuf<unsigned int> counter;     // per-iteration launches (part_r / part_i too): arrival ticket of varimax_iter_kernel
   int64_t N = 0, Nleft = 0;
   int p = 0;
   bool cplx = false;
   int nwg = 0;            // grid of the Varimax kernels (persistent: one workgroup per CU at most)
   int nacc = 0;           // grid of the one-pass accumulation kernels (Gram, column maxima, Promax fits): sized by N
+};
+
+// The loop Rotator::run takes for a problem
+enum class RotRoute {
+  Generic,        // more modes than the fused kernels hold: GEMMs and a Hermitian EVD per iteration (run_generic)
+  Moment,         // real loadings, p <= ROT_MOMENT_PMAX: fourth moments in one pass, then the loop in ONE workgroup
+  Persistent,     // the whole loop in one launch on a resident grid; hands over to PerIteration when a workgroup never arrives
+  PerIteration,   // one launch per iteration, enqueued in batches
 };
 
 class Rotator {
@@ -1434,6 +1446,22 @@ class Rotator {
   Rotator(hipStream_t s, StageTimer& t) : st(s), tm(t) {}
   Rotator(hipStream_t s, StageTimer& t, GemmWorkspace& g, EvdWorkspace& e) : st(s), tm(t), gws(&g), ews(&e) {}
   static bool fused_fits(int p, bool cplx) { return p <= rot_max_modes(cplx); }
+  static bool persist_enabled() {     // XMCA_VARIMAX_PERSIST=0: one launch per iteration where the persistent loop would run
+    static const bool on = [] { const char* e = std::getenv("XMCA_VARIMAX_PERSIST"); return !(e && e[0] == '0'); }();
+    return on;
+  }
+  static bool trace_enabled() { static const bool on = xmca_trace("rot"); return on; }      // XMCA_TRACE=rot, read once per process
+  // the Varimax loop is a single workgroup, which can run beside other work (xmca_rotate_loadings: no join of the deferred tail)
+  static bool single_workgroup_loop(int p, bool cplx) { return !cplx && p <= ROT_MOMENT_PMAX; }
+  // The persistent loop spins on every workgroup of its grid: all of them must be co-resident, one per CU (a partitioned /
+  // CU-masked device has fewer CUs than the 128-workgroup cap -> per-iteration launches instead), and the LDS must hold both
+  // scratch areas.
+  static RotRoute route(int p, bool cplx, int nwg, int n_cus, int max_iter) {
+    if (!fused_fits(p, cplx)) return RotRoute::Generic;
+    if (single_workgroup_loop(p, cplx)) return RotRoute::Moment;
+    const bool persistent = persist_enabled() && rot_persistent_smem(p, cplx) <= 160 * 1024 && nwg <= 256 && nwg <= n_cus && max_iter > 0;
+    return persistent ? RotRoute::Persistent : RotRoute::PerIteration;
+  }
 
   // `wide`: many modes (p^2 x planes >= 512 doubles per partial) - the accumulation dominates an iteration and the partials are
   // summed in two stages whose cost does not grow with the grid (varimax_persistent_kernel): up to one workgroup per CU.
@@ -1452,19 +1480,20 @@ class Rotator {
     return (int)std::max<int64_t>(1, (nb + per - 1) / per);
   }
 
+  // one pass over the loadings on d.nacc workgroups (MODE 1: Gram, 2: Promax fit, 3: column maxima), partials summed into out
   template <bool CPLX, int MODE, int SEL>
   void accum(RotationDevice& d, double power, double* out_r, double* out_i) {
+    static_assert(MODE >= 1 && MODE <= 3, "MODE 0 is the body of the Varimax kernels, not a launch");
     const size_t smem = rot_accum_smem(d.p, CPLX);
     auto kern = rot_accum_kernel<CPLX, MODE, SEL>;
     XMCA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    const int grid = MODE == 0 ? d.nwg : d.nacc;       // (MODE 0: the partials go to the step kernel, which adds up d.nwg of them)
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, st, d.A.r(), d.A.i(CPLX), d.h.get(), d.N, d.Nleft, d.p, d.R.r(),
+    hipLaunchKernelGGL(kern, dim3(d.nacc), dim3(256), smem, st, d.A.r(), d.A.i(CPLX), d.h.get(), d.N, d.Nleft, d.p, d.R.r(),
                        d.R.i(CPLX), d.cvec.get(), d.colmax.get(), power, d.state.get(), d.part_r.get(),
                        CPLX ? d.part_i.get() : nullptr, reinterpret_cast<unsigned long long*>(d.colmax.get()));
     XMCA_HIP(hipGetLastError());
-    if (MODE != 0 && MODE != 3) {
+    if (MODE != 3) {
       hipLaunchKernelGGL(rot_reduce_partials_kernel, dim3(d.p * d.p), dim3(256), 0, st, d.part_r.get(),
-                         CPLX ? d.part_i.get() : nullptr, grid, d.p * d.p, out_r, CPLX ? out_i : nullptr);
+                         CPLX ? d.part_i.get() : nullptr, d.nacc, d.p * d.p, out_r, CPLX ? out_i : nullptr);
       XMCA_HIP(hipGetLastError());
     }
   }
@@ -1480,7 +1509,6 @@ class Rotator {
     d.h.ensure((size_t)N);
     d.R.ensure((size_t)p * p, cplx);
     d.A0.ensure((size_t)p * p, cplx);
-    d.W.ensure((size_t)p * p, cplx);
     d.acc.ensure((size_t)p * p, cplx);
     d.cvec.ensure((size_t)p);
     d.state.ensure(ROT_STATE_N);
@@ -1488,6 +1516,21 @@ class Rotator {
     if (cplx) d.part_i.ensure((size_t)std::max(d.nwg, d.nacc) * p * p);
     d.colmax.ensure((size_t)p);
     if (!d.counter.get()) { d.counter.ensure(1); XMCA_HIP(hipMemsetAsync(d.counter.get(), 0, sizeof(unsigned int), st)); }
+  }
+
+  void read_state(RotationDevice& d, double* state) {      // state block of the loop -> host (synchronises the stream)
+    XMCA_HIP(hipMemcpyAsync(state, d.state.get(), sizeof(double) * ROT_STATE_N, hipMemcpyDeviceToHost, st));
+    XMCA_HIP(hipStreamSynchronize(st));
+  }
+  SmallMat fetch(const CPlanes& M, int p, bool cplx) {     // p x p planes on the device -> host (synchronises the stream)
+    const size_t pp = (size_t)p * p;
+    std::vector<double> r(pp), i(pp, 0.0);
+    XMCA_HIP(hipMemcpyAsync(r.data(), M.r(), sizeof(double) * pp, hipMemcpyDeviceToHost, st));
+    if (cplx) XMCA_HIP(hipMemcpyAsync(i.data(), M.im.get(), sizeof(double) * pp, hipMemcpyDeviceToHost, st));
+    XMCA_HIP(hipStreamSynchronize(st));
+    SmallMat out(p);
+    for (size_t e = 0; e < pp; ++e) out.a[e] = cd(r[e], i[e]);
+    return out;
   }
 
   // Varimax on the fourth moments (rotate.h, real loadings, p <= ROT_MOMENT_PMAX): one pass over the loadings builds the
@@ -1503,194 +1546,168 @@ class Rotator {
     XMCA_HIP(hipGetLastError());
     hipLaunchKernelGGL(rot_reduce_partials_kernel, dim3(E), dim3(256), 0, st, d.mpart.get(), nullptr, nm, E, d.mom.get(), nullptr);
     XMCA_HIP(hipGetLastError());
-    auto loop = [&](auto kern) {
-      hipLaunchKernelGGL(kern, dim3(1), dim3(256), 0, st, d.mom.get(), d.N, d.A0.r(), d.R.r(), d.cvec.get(), d.state.get(), tol, max_iter,
-                         gamma);
-    };
-    switch (p) {
-      case 2: loop(varimax_moment_kernel<2>); break;
-      case 3: loop(varimax_moment_kernel<3>); break;
-      case 4: loop(varimax_moment_kernel<4>); break;
-      case 5: loop(varimax_moment_kernel<5>); break;
-      case 6: loop(varimax_moment_kernel<6>); break;
-      case 7: loop(varimax_moment_kernel<7>); break;
-      case 8: loop(varimax_moment_kernel<8>); break;
-      case 9: loop(varimax_moment_kernel<9>); break;
-      case 10: loop(varimax_moment_kernel<10>); break;
-      case 11: loop(varimax_moment_kernel<11>); break;
-      default: loop(varimax_moment_kernel<12>); break;
-    }
+    static constexpr decltype(&varimax_moment_kernel<2>) loop[ROT_MOMENT_PMAX - 1] = {     // one instance per p = 2 .. ROT_MOMENT_PMAX
+        varimax_moment_kernel<2>, varimax_moment_kernel<3>, varimax_moment_kernel<4>,  varimax_moment_kernel<5>,  varimax_moment_kernel<6>, varimax_moment_kernel<7>,
+        varimax_moment_kernel<8>, varimax_moment_kernel<9>, varimax_moment_kernel<10>, varimax_moment_kernel<11>, varimax_moment_kernel<12>};
+    hipLaunchKernelGGL(loop[p - 2], dim3(1), dim3(256), 0, st, d.mom.get(), d.N, d.A0.r(), d.R.r(), d.cvec.get(), d.state.get(), tol, max_iter,
+                       gamma);
     XMCA_HIP(hipGetLastError());
   }
 
-  // runs Varimax + Promax on d.A / d.h (already normalised).  B_out (nullable): N x p rotated loadings for the host.
+  // LDS of one iteration's scratch: the accumulation and the polar step use the same area one after the other
+  static size_t iter_smem(int p, bool cplx) { return std::max(rot_accum_smem(p, cplx), rot_polar_smem(p, cplx)); }
+
+  // The whole loop in one launch: the workgroups exchange their partial G through epoch-tagged buffers.  The grid must be
+  // resident, and so must the persistent grids of the OTHER surrogate lanes of this process (rule_n / bootstrap keep several
+  // replicates in flight), Varimax loops and tridiagonal reductions alike: the launch claims its CUs at the device's gate
+  // (common.h PersistGate) and waits there for its turn - a reduction holds every CU for its ~20 ms, Varimax grids of several
+  // lanes run side by side while they fit.  Returns the number of iterations completed: max_iter, or fewer when a workgroup
+  // never arrived - the state block then holds the last completed iteration and per_iteration_loop goes on from there.
   template <bool CPLX>
-  void run(RotationDevice& d, int power, double tol, int max_iter, RotateResult& res, double* B_out_dev, bool varimax_only) {
+  int persistent_loop(RotationDevice& d, double tol, int max_iter, double* state) {
     const int p = d.p;
-    res.p = p; res.cplx = CPLX;
-    if (!fused_fits(p, CPLX)) { run_generic<CPLX>(d, power, tol, max_iter, res, B_out_dev, varimax_only); return; }
-    tm.begin("varimax");
-    accum<CPLX, 1, 0>(d, 1.0, d.A0.r(), d.A0.i(CPLX));
-    hipLaunchKernelGGL((varimax_step_kernel<CPLX>), dim3(1), dim3(256), 0, st, d.part_r.get(), CPLX ? d.part_i.get() : nullptr, d.nwg,
-                       p, d.A0.r(), d.A0.i(CPLX), d.R.r(), d.R.i(CPLX), d.W.r(), d.W.i(CPLX), d.cvec.get(), d.state.get(), tol, 1);
+    size_t smem = rot_persistent_smem(p, CPLX);
+    const int tiles_per_wg = (int)(((d.N + ROT_PB - 1) / ROT_PB + d.nwg - 1) / d.nwg);
+    const bool resident = smem + rot_resident_smem(p, CPLX, tiles_per_wg) <= 160 * 1024;     // the A tiles stay in LDS
+    if (resident) smem += rot_resident_smem(p, CPLX, tiles_per_wg);
+    PersistGate::Claim claim(persist_gate(), d.nwg);           // given back on return: the stream has been synchronised by then
+    // XMCA_VARIMAX_TEST_GIVEUP=k (tests): the persistent launch stops after k iterations, as if a workgroup had gone
+    // missing there, and the per-iteration launches take over - the hand-over must not change R or the stop iteration.
+    // Read per call, like XMCA_ROT_TWO_STAGE below: the tests change both inside one process.
+    const char* tg = std::getenv("XMCA_VARIMAX_TEST_GIVEUP");
+    const int persist_iters = (tg && std::atoi(tg) > 0) ? std::min(std::atoi(tg), max_iter) : max_iter;
+    d.pflags.ensure((size_t)2 * d.nwg);                        // partial published / chunk of the sum published
+    d.ppart_r.ensure((size_t)2 * d.nwg * p * p + 4 * (size_t)p * p);   // ... + the summed G (two parities, two planes)
+    if (CPLX) d.ppart_i.ensure((size_t)2 * d.nwg * p * p);
+    XMCA_HIP(hipMemsetAsync(d.pflags.get(), 0, sizeof(unsigned int) * 2 * d.nwg, st));
+    // two-stage sum of the partials when every workgroup would otherwise read more than ~32k doubles (XMCA_ROT_TWO_STAGE=0 / 1 forces)
+    const char* ts = std::getenv("XMCA_ROT_TWO_STAGE");
+    const bool two_stage = ts ? ts[0] != '0' : ((size_t)d.nwg * p * p * (CPLX ? 2 : 1) > 32768 || (long_grid(d.N) && d.nwg > 128));
+    constexpr int rot_poll_delay = 0;     // (a delayed first poll, the lever of the tridiagonal reduction, has no measurable effect here)
+    XMCA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(varimax_persistent_kernel<CPLX>),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    hipLaunchKernelGGL((varimax_persistent_kernel<CPLX>), dim3(d.nwg), dim3(256), smem, st, d.A.r(), d.A.i(CPLX), d.h.get(),
+                       d.N, p, d.A0.r(), d.A0.i(CPLX), d.R.r(), d.R.i(CPLX), d.cvec.get(), d.state.get(), d.ppart_r.get(),
+                       CPLX ? d.ppart_i.get() : nullptr, d.pflags.get(), tol, persist_iters, iter_smem(p, CPLX) / sizeof(double),
+                       resident ? tiles_per_wg : 0, gamma, rot_poll_delay,
+                       two_stage ? d.ppart_r.get() + (size_t)2 * d.nwg * p * p : nullptr);
     XMCA_HIP(hipGetLastError());
-    double state[ROT_STATE_N] = {0};
-    int launched = 0;
-    // default: one launch per iteration (partial G + last-arriving workgroup finishes the step with a Newton-Schulz
-    // polar factor); XMCA_VARIMAX_FUSED=0 selects the two-launch variant with the Jacobi SVD.
-    static const bool fused_on = [] { const char* e = std::getenv("XMCA_VARIMAX_FUSED"); return !(e && e[0] == '0'); }();
-    const bool fused = fused_on;
-    const size_t fused_smem = std::max(rot_accum_smem(p, CPLX), rot_polar_smem(p, CPLX));
-    if (fused)
-      XMCA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(varimax_iter_kernel<CPLX>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)fused_smem));
-    // XMCA_VARIMAX_PERSIST (default on): the whole loop in one launch, workgroups exchange their partial G through
-    // epoch-tagged buffers.  Needs a resident grid (<= 1 workgroup per CU) and the LDS for both scratch areas.
-    static const bool persist_on = [] { const char* e = std::getenv("XMCA_VARIMAX_PERSIST"); return !(e && e[0] == '0'); }();
-    const size_t work_bytes = std::max(rot_accum_smem(p, CPLX), rot_polar_smem(p, CPLX));
-    size_t persist_smem = rot_persistent_smem(p, CPLX);
-    int tiles_per_wg = (int)(((d.N + ROT_PB - 1) / ROT_PB + d.nwg - 1) / d.nwg);
-    bool resident = persist_smem + rot_resident_smem(p, CPLX, tiles_per_wg) <= 160 * 1024;
-    if (resident) persist_smem += rot_resident_smem(p, CPLX, tiles_per_wg);
-    // the epoch exchange spins on every workgroup of the grid: all of them must be co-resident, one per CU (a
-    // partitioned / CU-masked device has fewer CUs than the 128-workgroup cap -> per-iteration launches instead)
-    PersistGate& gate = persist_gate();
-    const int n_cus = gate.n_cus;
-    // ... and so must the persistent grids of the OTHER surrogate lanes of this process (rule_n / bootstrap keep several
-    // replicates in flight), Varimax loops and tridiagonal reductions alike: the launch claims its CUs at the device's gate
-    // (common.h PersistGate) and waits there for its turn - a reduction holds every CU for its ~20 ms, Varimax grids of
-    // several lanes run side by side while they fit
-    // real loadings with few modes: the fourth-moment route (one pass over the loadings, then the loop in one workgroup)
-    const bool moment = !CPLX && p <= ROT_MOMENT_PMAX;
-    const bool persist_ok = !moment && fused && persist_on && persist_smem <= 160 * 1024 && d.nwg <= 256 && d.nwg <= n_cus && max_iter > 0;
-    if (moment) {
-      moment_loop(d, tol, max_iter);
-      XMCA_HIP(hipMemcpyAsync(state, d.state.get(), sizeof(state), hipMemcpyDeviceToHost, st));
-      XMCA_HIP(hipStreamSynchronize(st));
-      launched = max_iter;
-    }
-    if (persist_ok) {
-      PersistGate::Claim claim(gate, d.nwg);           // given back at the end of this block: the stream has been synchronised by then
-      // XMCA_VARIMAX_TEST_GIVEUP=k (tests): the persistent launch stops after k iterations, as if a workgroup had gone
-      // missing there, and the per-iteration launches take over - the hand-over must not change R or the stop iteration
-      const char* tg = std::getenv("XMCA_VARIMAX_TEST_GIVEUP");
-      const int persist_iters = (tg && std::atoi(tg) > 0) ? std::min(std::atoi(tg), max_iter) : max_iter;
-      d.pflags.ensure((size_t)2 * d.nwg);                        // partial published / chunk of the sum published
-      d.ppart_r.ensure((size_t)2 * d.nwg * p * p + 4 * (size_t)p * p);   // ... + the summed G (two parities, two planes)
-      if (CPLX) d.ppart_i.ensure((size_t)2 * d.nwg * p * p);
-      XMCA_HIP(hipMemsetAsync(d.pflags.get(), 0, sizeof(unsigned int) * 2 * d.nwg, st));
-      // two-stage sum of the partials when every workgroup would otherwise read more than ~32k doubles (XMCA_ROT_TWO_STAGE=0 / 1 forces)
-      const bool rot_two_stage = [&] { const char* e = std::getenv("XMCA_ROT_TWO_STAGE"); return e ? e[0] != '0' : ((size_t)d.nwg * p * p * (CPLX ? 2 : 1) > 32768 || (long_grid(d.N) && d.nwg > 128)); }();
-      constexpr int rot_poll_delay = 0;     // (a delayed first poll, the lever of the tridiagonal reduction, has no measurable effect here)
-      XMCA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(varimax_persistent_kernel<CPLX>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)persist_smem));
-      hipLaunchKernelGGL((varimax_persistent_kernel<CPLX>), dim3(d.nwg), dim3(256), persist_smem, st, d.A.r(), d.A.i(CPLX), d.h.get(),
-                         d.N, p, d.A0.r(), d.A0.i(CPLX), d.R.r(), d.R.i(CPLX), d.cvec.get(), d.state.get(), d.ppart_r.get(),
-                         CPLX ? d.ppart_i.get() : nullptr, d.pflags.get(), tol, persist_iters, work_bytes / sizeof(double),
-                         resident ? tiles_per_wg : 0, gamma, rot_poll_delay,
-                         rot_two_stage ? d.ppart_r.get() + (size_t)2 * d.nwg * p * p : nullptr);
-      XMCA_HIP(hipGetLastError());
-      XMCA_HIP(hipMemcpyAsync(state, d.state.get(), sizeof(state), hipMemcpyDeviceToHost, st));
-      XMCA_HIP(hipStreamSynchronize(st));
-      if (state[4] == 2.0 || (persist_iters < max_iter && state[1] == 0.0 && state[4] == 0.0)) {
-        // a workgroup never arrived (grid not resident: another process holds CUs).  Workgroup 0 has written the R, c
-        // and iteration state of the last completed iteration: clear the flag and let the per-iteration launches below
-        // finish the loop from there.
-        ++persist_giveups();
-        if (xmca_trace("giveup")) std::fprintf(stderr, "xmca: varimax_persistent_kernel (%d workgroups) gave up after %d iterations\n", d.nwg, (int)state[0]);
-        state[4] = 0.0;
-        XMCA_HIP(hipMemcpyAsync(d.state.get(), state, sizeof(state), hipMemcpyHostToDevice, st));
-        XMCA_HIP(hipStreamSynchronize(st));
-        launched = (int)state[0];
-      } else {
-        launched = max_iter;
-      }
-    }
-    while (launched < max_iter) {
+    read_state(d, state);
+    const bool gave_up = state[4] == 2.0 || (persist_iters < max_iter && state[1] == 0.0 && state[4] == 0.0);
+    if (!gave_up) return max_iter;
+    // a workgroup never arrived (grid not resident: another process holds CUs).  Workgroup 0 has written the R, c and iteration
+    // state of the last completed iteration: clear the flag for the per-iteration launches
+    ++persist_giveups();
+    if (xmca_trace("giveup")) std::fprintf(stderr, "xmca: varimax_persistent_kernel (%d workgroups) gave up after %d iterations\n", d.nwg, (int)state[0]);
+    state[4] = 0.0;
+    XMCA_HIP(hipMemcpyAsync(d.state.get(), state, sizeof(double) * ROT_STATE_N, hipMemcpyHostToDevice, st));
+    XMCA_HIP(hipStreamSynchronize(st));
+    return (int)state[0];
+  }
+
+  // One launch per iteration (partial G + the last-arriving workgroup finishes the step), from iteration `from`: batches of 32,
+  // the state block read back after each - the kernel is a no-op once the loop has converged or met a NaN.
+  template <bool CPLX>
+  void per_iteration_loop(RotationDevice& d, double tol, int max_iter, int from, double* state) {
+    const int p = d.p;
+    const size_t smem = iter_smem(p, CPLX);
+    XMCA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(varimax_iter_kernel<CPLX>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    for (int launched = from; launched < max_iter;) {
       const int batch = std::min(32, max_iter - launched);
-      for (int b = 0; b < batch; ++b) {
-        if (fused) {
-          hipLaunchKernelGGL((varimax_iter_kernel<CPLX>), dim3(d.nwg), dim3(256), fused_smem, st, d.A.r(), d.A.i(CPLX), d.h.get(), d.N,
-                             p, d.A0.r(), d.A0.i(CPLX), d.R.r(), d.R.i(CPLX), d.cvec.get(), d.state.get(), d.part_r.get(),
-                             CPLX ? d.part_i.get() : nullptr, d.counter.get(), tol, gamma);
-        } else {
-          accum<CPLX, 0, 0>(d, gamma, nullptr, nullptr);      // (MODE 0 carries gamma in the `power` slot)
-          hipLaunchKernelGGL((varimax_step_kernel<CPLX>), dim3(1), dim3(256), 0, st, d.part_r.get(), CPLX ? d.part_i.get() : nullptr,
-                             d.nwg, p, d.A0.r(), d.A0.i(CPLX), d.R.r(), d.R.i(CPLX), d.W.r(), d.W.i(CPLX), d.cvec.get(), d.state.get(), tol, 0);
-        }
-      }
+      for (int b = 0; b < batch; ++b)
+        hipLaunchKernelGGL((varimax_iter_kernel<CPLX>), dim3(d.nwg), dim3(256), smem, st, d.A.r(), d.A.i(CPLX), d.h.get(), d.N, p,
+                           d.A0.r(), d.A0.i(CPLX), d.R.r(), d.R.i(CPLX), d.cvec.get(), d.state.get(), d.part_r.get(),
+                           CPLX ? d.part_i.get() : nullptr, d.counter.get(), tol, gamma);
       XMCA_HIP(hipGetLastError());
       launched += batch;
-      XMCA_HIP(hipMemcpyAsync(state, d.state.get(), sizeof(state), hipMemcpyDeviceToHost, st));
-      XMCA_HIP(hipStreamSynchronize(st));
-      static const bool trace = xmca_trace("rot");
-      if (trace)
+      read_state(d, state);
+      if (trace_enabled())
         std::fprintf(stderr, "[xmca varimax] p=%d N=%lld cplx=%d launched=%d iter=%g conv=%g d=%.12g polar_its=%g nan=%g\n", p,
                      (long long)d.N, (int)CPLX, launched, state[0], state[1], state[2], state[5], state[4]);
       if (state[1] != 0.0 || state[4] != 0.0) break;
     }
-    tm.end();
+  }
+
+  // -DXMCA_ROT_PROF: cycle stamps of the last iteration (rotate.h ROT_STAMP)
+  void print_phase_stamps([[maybe_unused]] const RotationDevice& d, [[maybe_unused]] RotRoute r, [[maybe_unused]] const double* state) {
 #ifdef XMCA_ROT_PROF
-    if (moment) {
-      long long hs[16];
-      XMCA_HIP(hipMemcpyFromSymbol(hs, HIP_SYMBOL(rot_prof), sizeof(hs)));
+    long long hs[16];
+    XMCA_HIP(hipMemcpyFromSymbol(hs, HIP_SYMBOL(rot_prof), sizeof(hs)));
+    if (r == RotRoute::Moment) {
       std::fprintf(stderr, "[xmca varimax prof] moment route, last iteration: S %lld  Y = M'S %lld  G %lld  polar tail %lld (its %g)  total %lld cycles\n",
                    hs[1] - hs[0], hs[2] - hs[1], hs[3] - hs[2], hs[4] - hs[3], state[5], hs[4] - hs[0]);
-    } else {
-      long long hs[16];
-      XMCA_HIP(hipMemcpyFromSymbol(hs, HIP_SYMBOL(rot_prof), sizeof(hs)));
-      std::fprintf(stderr, "[xmca varimax prof] accum %lld  publish %lld  wait %lld  acquire %lld  reduce %lld  newton-schulz %lld (its %g)  tail %lld  total %lld cycles (nwg %d)\n",
-                   hs[1] - hs[0], hs[6] - hs[1], hs[7] - hs[6], hs[2] - hs[7], hs[3] - hs[2], hs[4] - hs[3], state[5], hs[5] - hs[4], hs[5] - hs[0], d.nwg);
-      std::fprintf(stderr, "[xmca varimax prof] NS iteration 1: T tiles %lld  barrier %lld  flags %lld  Y tiles %lld  barrier %lld\n", hs[9] - hs[8],
-                   hs[10] - hs[9], hs[11] - hs[10], hs[12] - hs[11], hs[13] - hs[12]);
-      std::fprintf(stderr, "[xmca varimax prof] NS iteration 1: T products %lld  T epilogue %lld  Y products %lld  Y epilogue %lld\n", hs[14] - hs[8],
-                   hs[9] - hs[14], hs[15] - hs[11], hs[12] - hs[15]);
+      return;
     }
+    std::fprintf(stderr, "[xmca varimax prof] accum %lld  publish %lld  wait %lld  acquire %lld  reduce %lld  newton-schulz %lld (its %g)  tail %lld  total %lld cycles (nwg %d)\n",
+                 hs[1] - hs[0], hs[6] - hs[1], hs[7] - hs[6], hs[2] - hs[7], hs[3] - hs[2], hs[4] - hs[3], state[5], hs[5] - hs[4], hs[5] - hs[0], d.nwg);
+    std::fprintf(stderr, "[xmca varimax prof] NS iteration 1: T tiles %lld  barrier %lld  flags %lld  Y tiles %lld  barrier %lld\n", hs[9] - hs[8],
+                 hs[10] - hs[9], hs[11] - hs[10], hs[12] - hs[11], hs[13] - hs[12]);
+    std::fprintf(stderr, "[xmca varimax prof] NS iteration 1: T products %lld  T epilogue %lld  Y products %lld  Y epilogue %lld\n", hs[14] - hs[8],
+                 hs[9] - hs[14], hs[15] - hs[11], hs[12] - hs[15]);
 #endif
+  }
+
+  // runs Varimax + Promax on d.A / d.h (already normalised).  B_out (nullable): N x p rotated loadings for the host.
+  void run(RotationDevice& d, int power, double tol, int max_iter, RotateResult& res, double* B_out_dev, bool varimax_only) {
+    if (d.cplx) run<true>(d, power, tol, max_iter, res, B_out_dev, varimax_only);
+    else run<false>(d, power, tol, max_iter, res, B_out_dev, varimax_only);
+  }
+  template <bool CPLX>
+  void run(RotationDevice& d, int power, double tol, int max_iter, RotateResult& res, double* B_out_dev, bool varimax_only) {
+    const int p = d.p;
+    res.p = p; res.cplx = CPLX;
+    const RotRoute r = route(p, CPLX, d.nwg, persist_gate().n_cus, max_iter);
+    if (r == RotRoute::Generic) { run_generic<CPLX>(d, power, tol, max_iter, res, B_out_dev, varimax_only); return; }
+    tm.begin("varimax");
+    accum<CPLX, 1, 0>(d, 1.0, d.A0.r(), d.A0.i(CPLX));
+    hipLaunchKernelGGL((varimax_init_kernel<CPLX>), dim3(1), dim3(256), 0, st, p, d.A0.r(), d.A0.i(CPLX), d.R.r(), d.R.i(CPLX), d.cvec.get(),
+                       d.state.get());
+    XMCA_HIP(hipGetLastError());
+    double state[ROT_STATE_N] = {0};
+    int done = 0;      // iterations the persistent loop completed before it handed over
+    switch (r) {
+      case RotRoute::Moment: moment_loop(d, tol, max_iter); read_state(d, state); break;
+      case RotRoute::Persistent: done = persistent_loop<CPLX>(d, tol, max_iter, state); [[fallthrough]];
+      case RotRoute::PerIteration: per_iteration_loop<CPLX>(d, tol, max_iter, done, state); break;
+      case RotRoute::Generic: break;      // (returned above)
+    }
+    tm.end();
+    print_phase_stamps(d, r, state);
     res.iters = (int)state[0];
     res.converged = state[1] != 0.0;
     res.nan = state[4] != 0.0;
     res.last_d = state[2];
+    finish(d, res, B_out_dev, varimax_only, [&](SmallMat& XX, SmallMat& XP, SmallMat& SL, SmallMat& SR) {
+      // column maxima of X = rownormalised(B),  B = h (A R), then one pass per sum
+      XMCA_HIP(hipMemsetAsync(d.colmax.get(), 0, sizeof(double) * p, st));
+      accum<CPLX, 3, 0>(d, (double)power, nullptr, nullptr);
+      accum<CPLX, 2, 0>(d, (double)power, d.acc.r(), d.acc.i(CPLX)); XX = fetch(d.acc, p, CPLX);
+      accum<CPLX, 2, 1>(d, (double)power, d.acc.r(), d.acc.i(CPLX)); XP = fetch(d.acc, p, CPLX);
+      accum<CPLX, 2, 2>(d, (double)power, d.acc.r(), d.acc.i(CPLX)); SL = fetch(d.acc, p, CPLX);
+      accum<CPLX, 2, 3>(d, (double)power, d.acc.r(), d.acc.i(CPLX)); SR = fetch(d.acc, p, CPLX);
+    });
+  }
+
+  // What every route does with its result: nothing unless the loop converged; the converged R alone for `varimax_only`; else
+  // Promax from the four p x p sums X^H X, X^H P, S_left, S_right, which `promax_sums` forms in the route's own way.
+  template <typename Sums>
+  void finish(RotationDevice& d, RotateResult& res, double* B_out_dev, bool varimax_only, Sums&& promax_sums) {
     if (!res.converged) return;
-
-    std::vector<double> Rr((size_t)p * p), Ri((size_t)p * p, 0.0);
-    XMCA_HIP(hipMemcpyAsync(Rr.data(), d.R.r(), sizeof(double) * p * p, hipMemcpyDeviceToHost, st));
-    if (CPLX) XMCA_HIP(hipMemcpyAsync(Ri.data(), d.R.im.get(), sizeof(double) * p * p, hipMemcpyDeviceToHost, st));
-    XMCA_HIP(hipStreamSynchronize(st));
-    SmallMat Rv(p);
-    for (int e = 0; e < p * p; ++e) Rv.a[e] = cd(Rr[e], Ri[e]);
-
+    const SmallMat Rv = fetch(d.R, d.p, d.cplx);
     if (varimax_only) {
       res.R = Rv.a;
-      res.Phi = SmallMat::eye(p).a;
-      if (B_out_dev) apply<CPLX>(d, Rv, B_out_dev);
+      res.Phi = SmallMat::eye(d.p).a;
+      if (B_out_dev) apply(d, Rv, B_out_dev);
       return;
     }
-
     tm.begin("promax");
-    // column maxima of X = rownormalised(B),  B = h (A R)
-    XMCA_HIP(hipMemsetAsync(d.colmax.get(), 0, sizeof(double) * p, st));
-    accum<CPLX, 3, 0>(d, (double)power, nullptr, nullptr);
-    auto fetch = [&](SmallMat& M) {
-      std::vector<double> r((size_t)p * p), i((size_t)p * p, 0.0);
-      XMCA_HIP(hipMemcpyAsync(r.data(), d.acc.r(), sizeof(double) * p * p, hipMemcpyDeviceToHost, st));
-      if (CPLX) XMCA_HIP(hipMemcpyAsync(i.data(), d.acc.im.get(), sizeof(double) * p * p, hipMemcpyDeviceToHost, st));
-      XMCA_HIP(hipStreamSynchronize(st));
-      M = SmallMat(p);
-      for (int e = 0; e < p * p; ++e) M.a[e] = cd(r[e], i[e]);
-    };
     SmallMat XX, XP, SL, SR;
-    accum<CPLX, 2, 0>(d, (double)power, d.acc.r(), d.acc.i(CPLX)); fetch(XX);
-    accum<CPLX, 2, 1>(d, (double)power, d.acc.r(), d.acc.i(CPLX)); fetch(XP);
-    accum<CPLX, 2, 2>(d, (double)power, d.acc.r(), d.acc.i(CPLX)); fetch(SL);
-    accum<CPLX, 2, 3>(d, (double)power, d.acc.r(), d.acc.i(CPLX)); fetch(SR);
+    promax_sums(XX, XP, SL, SR);
     tm.end();
-
-    finish_promax<CPLX>(d, Rv, XX, XP, SL, SR, res, B_out_dev);
+    finish_promax(d, Rv, XX, XP, SL, SR, res, B_out_dev);
   }
 
   // p x p tail of Promax on the host (rotation.py:128-147) from the four p x p sums of the N-sized passes
-  template <bool CPLX>
   void finish_promax(RotationDevice& d, const SmallMat& Rv, const SmallMat& XX, const SmallMat& XP, const SmallMat& SL, const SmallMat& SR,
                      RotateResult& res, double* B_out_dev) {
     const int p = d.p;
@@ -1717,7 +1734,7 @@ class Rotator {
       res.norm_left[k] = std::sqrt(std::max(nl(k, k).real(), 0.0));
       res.norm_right[k] = std::sqrt(std::max(nr(k, k).real(), 0.0));
     }
-    if (B_out_dev) apply<CPLX>(d, Rf, B_out_dev);
+    if (B_out_dev) apply(d, Rf, B_out_dev);
   }
 
   // -------------------------------------------------------------------------------------------------------------
@@ -1794,61 +1811,36 @@ class Rotator {
     }
     tm.end();
     res.last_d = dsum;
-    if (!res.converged) return;
-
-    std::vector<double> Rr(pp), Ri(pp, 0.0);
-    XMCA_HIP(hipMemcpyAsync(Rr.data(), d.R.r(), sizeof(double) * pp, hipMemcpyDeviceToHost, st));
-    if (CPLX) XMCA_HIP(hipMemcpyAsync(Ri.data(), d.R.im.get(), sizeof(double) * pp, hipMemcpyDeviceToHost, st));
-    XMCA_HIP(hipStreamSynchronize(st));
-    SmallMat Rv(p);
-    for (size_t e = 0; e < pp; ++e) Rv.a[e] = cd(Rr[e], Ri[e]);
-    if (varimax_only) {
-      res.R = Rv.a;
-      res.Phi = SmallMat::eye(p).a;
-      if (B_out_dev) apply<CPLX>(d, Rv, B_out_dev);
-      return;
-    }
-    tm.begin("promax");
-    // X = row-normalised (A R), B = h (A R) per grid point (rotation.py:115-117), target P (:121-124), then the four sums
-    CPlanes Bs, Pt, C;
-    Bs.ensure((size_t)p * N, CPLX); Pt.ensure((size_t)p * N, CPLX); C.ensure(pp, CPLX);
-    rotate_A(Zt);
-    XMCA_HIP(hipMemcpyAsync(Bs.r(), Zt.r(), sizeof(double) * (size_t)p * N, hipMemcpyDeviceToDevice, st));
-    if (CPLX) XMCA_HIP(hipMemcpyAsync(Bs.im.get(), Zt.im.get(), sizeof(double) * (size_t)p * N, hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL(rot_point_scale_kernel, ew_grid(N), dim3(EW_BLOCK), 0, st, Bs.r(), Bs.i(CPLX), N, p, d.h.get(), 0);
-    hipLaunchKernelGGL(rot_point_scale_kernel, ew_grid(N), dim3(EW_BLOCK), 0, st, Zt.r(), Zt.i(CPLX), N, p, (const double*)nullptr, 1);
-    hipLaunchKernelGGL(rot_row_reduce_kernel, dim3(p), dim3(256), 0, st, Zt.r(), Zt.i(CPLX), N, 1, cvec.get());
-    hipLaunchKernelGGL(rot_target_kernel, ew_grid((int64_t)p * N), dim3(EW_BLOCK), 0, st, Zt.r(), Zt.i(CPLX), N, p, cvec.get(), (double)power,
-                       Pt.r(), Pt.i(CPLX));
-    XMCA_HIP(hipGetLastError());
-    auto fetch = [&](SmallMat& M) {
-      std::vector<double> r(pp), i(pp, 0.0);
-      XMCA_HIP(hipMemcpyAsync(r.data(), C.r(), sizeof(double) * pp, hipMemcpyDeviceToHost, st));
-      if (CPLX) XMCA_HIP(hipMemcpyAsync(i.data(), C.im.get(), sizeof(double) * pp, hipMemcpyDeviceToHost, st));
-      XMCA_HIP(hipStreamSynchronize(st));
-      M = SmallMat(p);
-      for (size_t e = 0; e < pp; ++e) M.a[e] = cd(r[e], i[e]);
-    };
-    SmallMat XX, XP, SL, SR;
-    gram(Zt, Zt, 0, N, C); fetch(XX);
-    gram(Zt, Pt, 0, N, C); fetch(XP);
-    SL = SmallMat(p); SR = SmallMat(p);
-    if (d.Nleft > 0) { gram(Bs, Bs, 0, d.Nleft, C); fetch(SL); }
-    if (d.Nleft < N) { gram(Bs, Bs, d.Nleft, N, C); fetch(SR); }
-    tm.end();
-    finish_promax<CPLX>(d, Rv, XX, XP, SL, SR, res, B_out_dev);
+    finish(d, res, B_out_dev, varimax_only, [&](SmallMat& XX, SmallMat& XP, SmallMat& SL, SmallMat& SR) {
+      // X = row-normalised (A R), B = h (A R) per grid point (rotation.py:115-117), target P (:121-124), then the four sums
+      CPlanes Bs, Pt, C;
+      Bs.ensure((size_t)p * N, CPLX); Pt.ensure((size_t)p * N, CPLX); C.ensure(pp, CPLX);
+      rotate_A(Zt);
+      XMCA_HIP(hipMemcpyAsync(Bs.r(), Zt.r(), sizeof(double) * (size_t)p * N, hipMemcpyDeviceToDevice, st));
+      if (CPLX) XMCA_HIP(hipMemcpyAsync(Bs.im.get(), Zt.im.get(), sizeof(double) * (size_t)p * N, hipMemcpyDeviceToDevice, st));
+      hipLaunchKernelGGL(rot_point_scale_kernel, ew_grid(N), dim3(EW_BLOCK), 0, st, Bs.r(), Bs.i(CPLX), N, p, d.h.get(), 0);
+      hipLaunchKernelGGL(rot_point_scale_kernel, ew_grid(N), dim3(EW_BLOCK), 0, st, Zt.r(), Zt.i(CPLX), N, p, (const double*)nullptr, 1);
+      hipLaunchKernelGGL(rot_row_reduce_kernel, dim3(p), dim3(256), 0, st, Zt.r(), Zt.i(CPLX), N, 1, cvec.get());
+      hipLaunchKernelGGL(rot_target_kernel, ew_grid((int64_t)p * N), dim3(EW_BLOCK), 0, st, Zt.r(), Zt.i(CPLX), N, p, cvec.get(), (double)power,
+                         Pt.r(), Pt.i(CPLX));
+      XMCA_HIP(hipGetLastError());
+      gram(Zt, Zt, 0, N, C); XX = fetch(C, p, CPLX);
+      gram(Zt, Pt, 0, N, C); XP = fetch(C, p, CPLX);
+      SL = SmallMat(p); SR = SmallMat(p);
+      if (d.Nleft > 0) { gram(Bs, Bs, 0, d.Nleft, C); SL = fetch(C, p, CPLX); }
+      if (d.Nleft < N) { gram(Bs, Bs, d.Nleft, N, C); SR = fetch(C, p, CPLX); }
+    });
   }
 
   // B = h (A M)  -> N x p row-major (interleaved complex) on the device
-  template <bool CPLX>
   void apply(RotationDevice& d, const SmallMat& M, double* B_out_dev) {
     const int p = d.p;
     std::vector<double> mr((size_t)p * p), mi((size_t)p * p);
     for (int e = 0; e < p * p; ++e) { mr[e] = M.a[e].real(); mi[e] = M.a[e].imag(); }
     XMCA_HIP(hipMemcpyAsync(d.acc.r(), mr.data(), sizeof(double) * p * p, hipMemcpyHostToDevice, st));
-    if (CPLX) XMCA_HIP(hipMemcpyAsync(d.acc.im.get(), mi.data(), sizeof(double) * p * p, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL((rot_apply_kernel<CPLX>), ew_grid(d.N), dim3(EW_BLOCK), 0, st, d.A.r(), d.A.i(CPLX), d.h.get(), d.N, p,
-                       d.acc.r(), d.acc.i(CPLX), B_out_dev);
+    if (d.cplx) XMCA_HIP(hipMemcpyAsync(d.acc.im.get(), mi.data(), sizeof(double) * p * p, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(d.cplx ? rot_apply_kernel<true> : rot_apply_kernel<false>, ew_grid(d.N), dim3(EW_BLOCK), 0, st, d.A.r(), d.A.i(d.cplx),
+                       d.h.get(), d.N, p, d.acc.r(), d.acc.i(d.cplx), B_out_dev);
     XMCA_HIP(hipGetLastError());
     XMCA_HIP(hipStreamSynchronize(st));
   }

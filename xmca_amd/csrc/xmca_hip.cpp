@@ -899,17 +899,15 @@ void rotate_resident(xmca_handle* h, Rotator& rot, RotationDevice& d, DevBuf<dou
     XMCA_CHECK(!cplx && Nr == 0, XMCA_ERR_STATE, "rotate: float32-resident vectors are real and one-sided");
     hipLaunchKernelGGL(rot_build_loadings_f32_kernel, ew_grid(Nl), dim3(EW_BLOCK), 0, h->st, res.Vt32[0].get(), Nl, Nl, sigma_dev.get(), p,
                        d.A.r(), d.h.get());
-    rot.run<false>(d, power, tol, max_iter, rr, nullptr, false);
   } else if (cplx) {
     hipLaunchKernelGGL((rot_build_loadings_kernel<true>), ew_grid(Nl + Nr), dim3(EW_BLOCK), 0, h->st, Vl.r(), Vl.i(true), Nl, Nl,
                        Vr.r(), Vr.i(true), Nr > 0 ? Nr : Nl, Nr, sigma_dev.get(), p, d.A.r(), d.A.i(true), d.h.get());
-    rot.run<true>(d, power, tol, max_iter, rr, nullptr, false);
   } else {
     hipLaunchKernelGGL((rot_build_loadings_kernel<false>), ew_grid(Nl + Nr), dim3(EW_BLOCK), 0, h->st, Vl.r(), (const double*)nullptr,
                        Nl, Nl, Vr.r(), (const double*)nullptr, Nr > 0 ? Nr : Nl, Nr, sigma_dev.get(), p, d.A.r(), (double*)nullptr,
                        d.h.get());
-    rot.run<false>(d, power, tol, max_iter, rr, nullptr, false);
   }
+  rot.run(d, power, tol, max_iter, rr, nullptr, false);
 }
 
 // What every replicate of a rule_n / bootstrap call has in common: the shape of the fields, the complexification (op == nullptr:
@@ -1499,7 +1497,7 @@ int xmca_rotate_loadings(xmca_handle* h, const double* L, int64_t N, int64_t n_l
   // The loadings come from the host and the rotation reads nothing of the solve.  On the fourth-moment route (real, few modes) its
   // loop is ONE workgroup: it runs beside the tail.  Every other route joins: a persistent grid, whose workgroups wait for each
   // other, must not queue for CUs behind the tail's workgroups, and the GEMM-based route would share the chip with it for nothing.
-  if (is_complex != 0 || p > ROT_MOMENT_PMAX) join_tail(h);
+  if (!Rotator::single_workgroup_loop(p, is_complex != 0)) join_tail(h);
   XMCA_CHECK(L && N >= 1 && p >= 2, XMCA_ERR_INVALID, "rotate: need N x p loadings with p >= 2");
   XMCA_CHECK(power >= 1, XMCA_ERR_INVALID, "rotate: `power` must be >= 1");
   XMCA_CHECK(n_left >= 0 && n_left <= N && max_iter >= 1, XMCA_ERR_INVALID, "rotate: bad n_left / max_iter");
@@ -1516,12 +1514,11 @@ int xmca_rotate_loadings(xmca_handle* h, const double* L, int64_t N, int64_t n_l
   if (cplx) {
     hipLaunchKernelGGL((rot_import_loadings_kernel<true>), ew_grid(N), dim3(EW_BLOCK), 0, h->st, Ld.get(), N, p, d.A.r(), d.A.i(true),
                        d.h.get());
-    rot.run<true>(d, power, tol, max_iter, rr, B_out ? Bd.get() : nullptr, varimax_only != 0);
   } else {
     hipLaunchKernelGGL((rot_import_loadings_kernel<false>), ew_grid(N), dim3(EW_BLOCK), 0, h->st, Ld.get(), N, p, d.A.r(),
                        (double*)nullptr, d.h.get());
-    rot.run<false>(d, power, tol, max_iter, rr, B_out ? Bd.get() : nullptr, varimax_only != 0);
   }
+  rot.run(d, power, tol, max_iter, rr, B_out ? Bd.get() : nullptr, varimax_only != 0);
   h->tm.collect();
   if (iters_out) *iters_out = rr.iters;
   check_rot(rr);
