@@ -41,7 +41,7 @@ typedef struct xmca_handle xmca_handle;
 /* library / device management ------------------------------------------------------------------------- */
 const char* xmca_version(void);
 /* Number of this header's ABI (XMCA_ABI_VERSION): the binding refuses a library built from another revision. */
-#define XMCA_ABI_VERSION 13
+#define XMCA_ABI_VERSION 14
 int xmca_abi_version(void);
 int xmca_device_count(void);
 int xmca_create(int device, xmca_handle** out);
@@ -214,6 +214,20 @@ int xmca_bootstrap_runs(xmca_handle* h, const double* hilbert_col, const int64_t
 int xmca_bootstrap_runs_extended(xmca_handle* h, const double* col3, const double* hbar, const double* U, const double* W, int rank,
                                  const int64_t* idx_left, const int64_t* idx_right, int64_t n_runs, int rotated, int p, int power,
                                  double tol, double* spectra_out, int* kept_out, int64_t n_out);
+/* Column resampling, `bootstrapping(axis=1)` (ABI 14): the two entries above with column indices in place of row indices.
+ * cols_left: n_runs x Nl, cols_right: n_runs x Nr composed indices INTO THE COLUMNS OF [left | right] AS THE FIELDS WERE AT
+ * xmca_bootstrap_begin, 0 <= index < Nl + Nr (< Nl with one field; XMCA_ERR_INVALID otherwise, before anything is launched) -
+ * the reference resamples the concatenation of both fields with one draw when both sides are resampled and splits it again at
+ * Nl (array.py:1921-1928), so a column of either replicate field may come from either working copy; with one side resampled its
+ * indices stay inside that side's range (left: c, right: Nl + c).  NULL: the side is copied as it is.  T, Nl and Nr do not
+ * change, so the complexification (hilbert_col, or the parts of the extended operator) is the one of the row entries; every
+ * replicate is centered again like the MCA constructor does.  Errors and outputs as for the row entries. */
+int xmca_bootstrap_runs_columns(xmca_handle* h, const double* hilbert_col, const int64_t* cols_left, const int64_t* cols_right,
+                                int64_t n_runs, int rotated, int p, int power, double tol, double* spectra_out, int* kept_out,
+                                int64_t n_out);
+int xmca_bootstrap_runs_columns_extended(xmca_handle* h, const double* col3, const double* hbar, const double* U, const double* W,
+                                         int rank, const int64_t* cols_left, const int64_t* cols_right, int64_t n_runs, int rotated,
+                                         int p, int power, double tol, double* spectra_out, int* kept_out, int64_t n_out);
 int xmca_is_complex(xmca_handle* h);
 /* 1 when the singular vectors of `side` from the last xmca_solve are resident in float32: a real float32 field decomposed on
  * its dual side (N > T) keeps `_V` in the input's dtype as the reference does (xmca/array.py:584, the dtype of

@@ -47,6 +47,9 @@ SIGNATURES = {
     "xmca_bootstrap_runs": (_c_int, [_vp, _vp, _vp, _vp, _c_i64, _c_int, _c_int, _c_int, _c_dbl, _vp, _vp, _c_i64]),
     "xmca_bootstrap_runs_extended": (_c_int, [_vp, _vp, _vp, _vp, _vp, _c_int, _vp, _vp, _c_i64, _c_int, _c_int, _c_int, _c_dbl, _vp, _vp,
                                               _c_i64]),
+    "xmca_bootstrap_runs_columns": (_c_int, [_vp, _vp, _vp, _vp, _c_i64, _c_int, _c_int, _c_int, _c_dbl, _vp, _vp, _c_i64]),
+    "xmca_bootstrap_runs_columns_extended": (_c_int, [_vp, _vp, _vp, _vp, _vp, _c_int, _vp, _vp, _c_i64, _c_int, _c_int, _c_int, _c_dbl,
+                                                      _vp, _vp, _c_i64]),
     "xmca_correlate": (_c_int, [_vp, _c_int, _vp, _c_i64, _c_i64, _vp]),
     "xmca_pearson_pvalues": (_c_int, [_vp, _vp, _c_i64, _c_i64, _vp]),
     "xmca_pvalue_log_norm": (_c_int, [_c_i64, _dp]),
@@ -96,7 +99,7 @@ def library_path():
 
 
 PVALUE_MAX_OBS = 1000000     # largest n_obs of xmca_pearson_pvalues / xmca_correlation_maps (csrc/kernels.h)
-ABI_VERSION = 13         # bumped whenever a signature of include/xmca_hip.h changes; checked against xmca_abi_version()
+ABI_VERSION = 14         # bumped whenever a signature of include/xmca_hip.h changes; checked against xmca_abi_version()
 
 
 def load_library():
@@ -494,23 +497,30 @@ class Handle:
         self.release_result()
         self._check(self._lib.xmca_bootstrap_begin(self._h, n_fields))
 
-    def bootstrap_runs(self, T, complexify, idx_left, idx_right, n_runs, rotated, p, power, tol, n_out, extend_period=None):
-        """All replicates in one call (several in flight on the device).  idx_*: (n_runs, T) COMPOSED row indices into the
-        fields as they were at `bootstrap_begin`, or None.  `extend_period`: replicates of a complex model with extend='exp' and
-        this period (xmca_bootstrap_runs_extended; float64 fields).  Returns (spectra[n_runs, n_out], kept[n_runs])."""
-        il = None if idx_left is None else np.ascontiguousarray(idx_left, dtype=np.int64).reshape(n_runs, T)
-        ir = None if idx_right is None else np.ascontiguousarray(idx_right, dtype=np.int64).reshape(n_runs, T)
+    def bootstrap_runs(self, T, complexify, idx_left, idx_right, n_runs, rotated, p, power, tol, n_out, extend_period=None, axis=0):
+        """All replicates in one call (several in flight on the device).  idx_*: COMPOSED indices into the fields as they were at
+        `bootstrap_begin`, or None - axis=0: (n_runs, T) row indices; axis=1: (n_runs, Nl) / (n_runs, Nr) column indices into
+        [left | right] (xmca_bootstrap_runs_columns*).  `extend_period`: replicates of a complex model with extend='exp' and
+        this period (xmca_bootstrap_runs*_extended; float64 fields).  Returns (spectra[n_runs, n_out], kept[n_runs])."""
+        if axis not in (0, 1):
+            raise ValueError('{:} not a valid axis. either 0 or 1.'.format(axis))
+        il = None if idx_left is None else np.ascontiguousarray(idx_left, dtype=np.int64).reshape(n_runs, -1)
+        ir = None if idx_right is None else np.ascontiguousarray(idx_right, dtype=np.int64).reshape(n_runs, -1)
+        if axis == 0 and any(i is not None and i.shape[1] != T for i in (il, ir)):
+            raise ValueError("bootstrap_runs: row indices must be n_runs x T")
         out = np.zeros((n_runs, n_out), dtype=np.float64)
         kept = np.zeros(n_runs, dtype=np.int32)
+        columns = "_columns" if axis == 1 else ""
         if complexify and extend_period is not None:
             col3, hbar, U, W = extended_imag_parts(T, extend_period)
-            self._check(self._lib.xmca_bootstrap_runs_extended(self._h, _ptr(col3), _ptr(hbar), _ptr(U), _ptr(W), U.shape[1], _ptr(il),
-                                                               _ptr(ir), n_runs, int(rotated), int(p), int(power), float(tol), _ptr(out),
-                                                               _ptr(kept), n_out))
+            run = getattr(self._lib, "xmca_bootstrap_runs%s_extended" % columns)
+            self._check(run(self._h, _ptr(col3), _ptr(hbar), _ptr(U), _ptr(W), U.shape[1], _ptr(il), _ptr(ir), n_runs, int(rotated),
+                            int(p), int(power), float(tol), _ptr(out), _ptr(kept), n_out))
             return out, kept.astype(bool)
         ht = hilbert_imag_column(T) if complexify else None
-        self._check(self._lib.xmca_bootstrap_runs(self._h, _ptr(ht), _ptr(il), _ptr(ir), n_runs, int(rotated), int(p), int(power),
-                                                  float(tol), _ptr(out), _ptr(kept), n_out))
+        run = getattr(self._lib, "xmca_bootstrap_runs" + columns)
+        self._check(run(self._h, _ptr(ht), _ptr(il), _ptr(ir), n_runs, int(rotated), int(p), int(power), float(tol), _ptr(out),
+                        _ptr(kept), n_out))
         return out, kept.astype(bool)
 
     def correlate(self, side, Y, N):

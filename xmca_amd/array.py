@@ -1170,10 +1170,12 @@ class MCA:
         """Monte Carlo (moving-block) bootstrap / permutation of the model (array.py:1813-1952).
 
         The block indices are drawn on the host from numpy's global RNG exactly as the reference draws them
-        (tools/array.py:91-138), the replicates themselves - cumulative row resampling, centering, solve, rotation,
-        variance - run on the device (`xmca_bootstrap_runs`).  A model solved with extend='exp' runs there too, every replicate
-        complexified with the same extended operator in float64 (`xmca_bootstrap_runs_extended`).  Column resampling (`axis=1`)
-        and extend='theta' keep the reference's host loop with one device solve per replicate.
+        (tools/array.py:91-138) and composed over the replicates (`compose_bootstrap_indices`); the replicates themselves -
+        cumulative resampling of rows (`axis=0`) or of columns (`axis=1`; of the concatenation [left | right] when both sides are
+        resampled), centering, solve, rotation, variance - run on the device (`xmca_bootstrap_runs`, `xmca_bootstrap_runs_columns`).
+        A model solved with extend='exp' runs there too, every replicate complexified with the same extended operator in float64
+        (`xmca_bootstrap_runs_extended`, `xmca_bootstrap_runs_columns_extended`).  Only extend='theta' keeps the reference's host
+        loop with one device solve per replicate.
         """
         complexify = self._analysis['is_complex']
         extend = self._analysis['extend']
@@ -1184,7 +1186,7 @@ class MCA:
         n_modes_max = self._get_min_mode(n_modes, rotated=True)
         var_surr = np.zeros([n_modes_max, n_runs])
         extend_exp = bool(complexify) and extend == 'exp' and getattr(self, '_device_extend', None) is not None
-        on_device = axis == 0 and (not extend or extend_exp) and not getattr(self, '_bootstrap_on_host', False)
+        on_device = (not extend or extend_exp) and not getattr(self, '_bootstrap_on_host', False)
         dev = self._device()
         n_obs = self._n_observations['left']
         for mode in range(n_modes):
@@ -1194,34 +1196,19 @@ class MCA:
                 for k in X_surr:
                     X_surr[k] -= X_rec[k]
             if on_device:
-                if on_right and 'right' not in X_surr:
-                    raise ValueError('No bootstrapping possible. There is no right field. Set `on_right=False`.')
-                if n_obs % block_size:
-                    raise ValueError('Length of data array ({:}) must be a multiple of block size {:}'.format(n_obs, block_size))
+                widths = [X_surr[k].shape[1] for k in self._keys]
+                # (the reference's errors, before any device work)
+                idx_left, idx_right = compose_bootstrap_indices(n_runs, axis, n_obs, widths, on_left, on_right, block_size, replace)
                 for side, k in enumerate(self._keys):
                     dev.set_field(side, _device_ready(np.ascontiguousarray(X_surr[k])))
                 dev.bootstrap_begin(len(self._keys))
-                n_blocks = n_obs // block_size
-                rank = min([n_obs] + [X_surr[k].shape[1] for k in self._keys])
+                rank = min([n_obs] + widths)
                 n_out = n_rot if is_rotated else rank
-                # the reference resamples cumulatively (X_surr is overwritten, array.py:1935-1943): replicate r sees the rows
-                # c_r = c_{r-1}[idx_r] of the original field.  The draws are made here in the reference's order, composed, and
-                # the device runs all replicates in one call, several at a time.
-                cum = np.arange(n_obs)
-                composed = np.empty((n_runs, n_obs), dtype=np.int64)
-                for run in range(n_runs):
-                    if on_left or on_right:
-                        # one draw per replicate, like tools/array.py:136 (both sides share it when both are resampled)
-                        pick = np.random.choice(n_blocks, size=n_blocks, replace=replace)
-                        rows = (pick[:, None] * block_size + np.arange(block_size)[None, :]).reshape(-1)
-                        cum = cum[rows]
-                    composed[run] = cum
                 # (replicates are independent once composed: sharded over the ranks of a torch.distributed job like the Rule-N runs)
                 from . import dist
-                spec, kept = dist.sharded_bootstrap(dev, n_runs, T=n_obs, complexify=complexify, idx_left=composed if on_left else None,
-                                                    idx_right=composed if on_right else None, rotated=is_rotated, p=n_rot,
-                                                    power=max(power, 1), tol=1e-8, n_out=n_out,
-                                                    extend_period=period if extend_exp else None)
+                spec, kept = dist.sharded_bootstrap(dev, n_runs, T=n_obs, complexify=complexify, idx_left=idx_left, idx_right=idx_right,
+                                                    rotated=is_rotated, p=n_rot, power=max(power, 1), tol=1e-8, n_out=n_out,
+                                                    extend_period=period if extend_exp else None, **({'axis': 1} if axis == 1 else {}))
                 for run in range(n_runs):
                     if kept[run]:
                         var_surr[mode:, run] = spec[run, :n_modes_max - mode]
@@ -1364,6 +1351,56 @@ class MCA:
         """Print the analysis meta information."""
         import yaml
         print(yaml.dump({k: str(v) for k, v in self._analysis.items()}, sort_keys=False, default_flow_style=False))
+
+
+def compose_bootstrap_indices(n_runs, axis, n_obs, widths, on_left, on_right, block_size=1, replace=True):
+    """The resampling of `bootstrapping` as indices: (idx_left, idx_right), each (n_runs, length) int64 or None for a side that
+    is not resampled, for fields of n_obs rows and widths = [Nl] or [Nl, Nr] columns.  No device is involved.
+
+    Per replicate one `np.random.choice(n_blocks, size=n_blocks, replace=replace)` is drawn from numpy's global generator, exactly as
+    tools/array.py:132 does, and expanded from blocks to rows / columns.  The reference resamples cumulatively (X_surr is
+    overwritten, array.py:1902-1928), so replicate r sees c_r = c_{r-1}[idx_r] of the original fields: the composed c_r are
+    returned.  axis=0: row indices < n_obs, the same for both sides when both are resampled.  axis=1: column indices into
+    [left | right] - a left-only draw lives in [0, Nl), a right-only draw in Nl + [0, Nr), and with both sides the concatenation
+    of Nl + Nr columns is resampled with one draw (blocks may straddle the seam) and split again at Nl, so either side may
+    receive columns of the other.  Raises the reference's ValueErrors (no right field, length not a multiple of block_size,
+    invalid axis)."""
+    n_fields = len(widths)
+    if axis == 0:
+        if on_right and n_fields < 2:
+            raise ValueError('No bootstrapping possible. There is no right field. Set `on_right=False`.')
+        length, offset = n_obs, 0
+    else:
+        if not (on_left or on_right):
+            return None, None
+        if on_right and not on_left and n_fields < 2:
+            raise ValueError('No bootstrapping possible. There is no right field. Set `on_right=False`.')
+        if axis != 1:
+            raise ValueError('{:} not a valid axis. either 0 or 1.'.format(axis))
+        if on_left and on_right:
+            length, offset = sum(widths), 0
+        elif on_left:
+            length, offset = widths[0], 0
+        else:
+            length, offset = widths[1], widths[0]
+    if length % block_size:
+        raise ValueError('Length of data array ({:}) must be a multiple of block size {:}'.format(length, block_size))
+    n_blocks = length // block_size
+    cum = np.arange(length)
+    composed = np.empty((n_runs, length), dtype=np.int64)
+    for run in range(n_runs):
+        if on_left or on_right:
+            # one draw per replicate, like tools/array.py:132 (both sides share it when both are resampled)
+            pick = np.random.choice(n_blocks, size=n_blocks, replace=replace)
+            cum = cum[(pick[:, None] * block_size + np.arange(block_size)[None, :]).reshape(-1)]
+        composed[run] = cum
+    if axis == 0:
+        return (composed if on_left else None), (composed if on_right else None)
+    composed += offset
+    if on_left and on_right:
+        n_left = widths[0]
+        return np.ascontiguousarray(composed[:, :n_left]), (np.ascontiguousarray(composed[:, n_left:]) if n_fields == 2 else None)
+    return (composed, None) if on_left else (None, composed)
 
 
 def _gpu_visible():

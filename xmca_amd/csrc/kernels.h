@@ -536,6 +536,53 @@ __global__ void gather_rows_kernel(const T* __restrict__ in, T* __restrict__ out
   }
 }
 
+// out[t][j] = src(c[j])[t][local(c[j])] for t < rows, j < n_out: column resampling.  c = idx[j] indexes the columns of the virtual
+// concatenation [left | right] of two row-major matrices with `rows` rows (right == nullptr, n_right == 0: left alone), so a
+// column of `out` comes from either of them, each with its own leading dimension.  A workgroup owns a strip of GATHER_COLS_BLOCK
+// output columns: every thread reads its index ONCE and resolves it to a column pointer and a stride, then walks a tile of
+// GATHER_COLS_ROWS rows with them (blockIdx.y, grid-stride over the tiles) - stores are coalesced along j, loads are scattered
+// inside one source row, GATHER_COLS_UNROLL of them in flight per thread, and the address of the next row is one add.  The
+// workgroups of one row tile (consecutive blockIdx.x, dispatched together) read the same 32 source rows, 2.5 MB at 10 000 float64
+// columns: the part of a cache line one strip does not use is found in L2 by the strip that does.
+constexpr int GATHER_COLS_BLOCK = 256;
+constexpr int GATHER_COLS_ROWS = 32;
+constexpr int GATHER_COLS_UNROLL = 8;
+template <typename T>
+__global__ void __launch_bounds__(GATHER_COLS_BLOCK)
+gather_concat_columns_kernel(const T* __restrict__ left, int64_t n_left, const T* __restrict__ right, int64_t n_right,
+                             const int64_t* __restrict__ idx, T* __restrict__ out, int64_t n_out, int rows) {
+  const int64_t j = (int64_t)blockIdx.x * GATHER_COLS_BLOCK + threadIdx.x;
+  if (j >= n_out) return;
+  const int64_t c = idx[j];
+  const bool from_left = c < n_left;
+  const int64_t ld = from_left ? n_left : n_right;
+  const T* const col = from_left ? left + c : right + (c - n_left);
+  for (int t0 = (int)blockIdx.y * GATHER_COLS_ROWS; t0 < rows; t0 += (int)gridDim.y * GATHER_COLS_ROWS) {
+    const int t1 = t0 + GATHER_COLS_ROWS < rows ? t0 + GATHER_COLS_ROWS : rows;
+    const T* s = col + (int64_t)t0 * ld;
+    T* d = out + (int64_t)t0 * n_out + j;
+    int t = t0;
+    for (; t + GATHER_COLS_UNROLL <= t1; t += GATHER_COLS_UNROLL) {
+      T v[GATHER_COLS_UNROLL];
+#pragma unroll
+      for (int u = 0; u < GATHER_COLS_UNROLL; ++u) v[u] = s[(int64_t)u * ld];
+#pragma unroll
+      for (int u = 0; u < GATHER_COLS_UNROLL; ++u) d[(int64_t)u * n_out] = v[u];
+      s += (int64_t)GATHER_COLS_UNROLL * ld;
+      d += (int64_t)GATHER_COLS_UNROLL * n_out;
+    }
+    for (; t < t1; ++t, s += ld, d += n_out) *d = *s;
+  }
+}
+
+// grid of gather_concat_columns_kernel: one strip of columns per x, the row tiles over y (at most 65535 at a time)
+static inline dim3 gather_cols_grid(int64_t rows, int64_t n_out) {
+  int64_t by = (rows + GATHER_COLS_ROWS - 1) / GATHER_COLS_ROWS;
+  if (by > 65535) by = 65535;
+  if (by < 1) by = 1;
+  return dim3((unsigned)((n_out + GATHER_COLS_BLOCK - 1) / GATHER_COLS_BLOCK), (unsigned)by);
+}
+
 // column sums and sums of squares of a rows x cols matrix (one thread per column, coalesced over columns)
 template <typename T>
 __global__ void column_moments_kernel(const T* __restrict__ x, int rows, int64_t cols, double* __restrict__ sum,

@@ -659,6 +659,15 @@ class Solver {
     kernel_svd(K, ra, rb, cplx, true, lam, Ph, Qh, &out.evd_info[2]);
     out.sigma.resize(rank);
     for (int i = 0; i < rank; ++i) out.sigma[i] = std::sqrt(std::max(lam[i], 0.0));
+    if (n_vec_req == 0 && rank > 0) {
+      // Values only (replicates): nothing refines the tail afterwards (refine_by_deflation needs vectors).  lam = sigma^2 comes
+      // from the Gram matrix of K, whose rounding noise is (ra + rb) eps lam_1: an eigenvalue below it says nothing, and its
+      // square root would turn an exactly rank-deficient kernel - columns duplicated by a column bootstrap, where the reference's
+      // SVD of K returns 1e-16 sigma_1 - into values of 1e-8 sigma_1.  Such a value is reported as what it stands for, zero.
+      const double floor = (double)(ra + rb) * 2.220446049250313e-16 * std::max(lam[0], 0.0);
+      for (int i = 0; i < rank; ++i)
+        if (lam[i] <= floor) out.sigma[i] = 0.0;
+    }
 
     const int m = n_vec_req < 0 ? rank : std::min(n_vec_req, rank);
     out.n_vec = m;

@@ -1128,18 +1128,25 @@ void bootstrap_begin_impl(xmca_handle* h, int n_fields) {
   XMCA_HIP(hipStreamSynchronize(h->st));
 }
 
-// The replicates of a bootstrap: rows of the ORIGINAL working copies (xmca_bootstrap_begin) are gathered through the composed
-// index of replicate r - the reference's cumulative resampling X <- X[idx_r] unrolled on the host, c_r = c_{r-1}[idx_r] - so
-// the replicates do not depend on each other on the device and can run in lanes.  A side without indices is copied as it is.
+// The replicates of a bootstrap: rows (axis 0) or columns (axis 1) of the ORIGINAL working copies (xmca_bootstrap_begin) are
+// gathered through the composed index of replicate r - the reference's cumulative resampling X <- X[idx_r] unrolled on the host,
+// c_r = c_{r-1}[idx_r] - so the replicates do not depend on each other on the device and can run in lanes.  Row indices address
+// the T rows of a side's own copy; column indices address the columns of [left | right], Nl + Nr of them (the reference
+// resamples the concatenation when both sides are, tools/array.py:91-138 through array.py:1921-1928), N[side] per replicate.
+// A side without indices is copied as it is.
 template <typename TI>
-void bootstrap_runs_impl(xmca_handle* h, const ComplexOp* op, const int64_t* idx_left, const int64_t* idx_right, int64_t n_runs,
+void bootstrap_runs_impl(xmca_handle* h, const ComplexOp* op, int axis, const int64_t* idx_left, const int64_t* idx_right, int64_t n_runs,
                          int rotated, int p, int power, double tol, double* spectra, int* kept, int64_t n_out) {
   const int64_t T = h->boot_T;
+  const int64_t Nl = h->boot_N[0], Nr = h->boot_fields == 2 ? h->boot_N[1] : 0;
   const int64_t* idx_host[2] = {idx_left, idx_right};
-  for (const int64_t* idx : idx_host)
-    if (idx)
-      for (int64_t i = 0; i < n_runs * T; ++i) XMCA_CHECK(idx[i] >= 0 && idx[i] < T, XMCA_ERR_INVALID, "bootstrap: row index out of range");
-  const ReplicateSpec spec{T, h->boot_N[0], h->boot_fields == 2 ? h->boot_N[1] : 0, h->boot_fields, op, rotated, p, power, tol};
+  const int64_t idx_len[2] = {axis == 0 ? T : Nl, axis == 0 ? T : Nr}, bound = axis == 0 ? T : Nl + Nr;
+  for (int s = 0; s < 2; ++s)
+    if (idx_host[s])
+      for (int64_t i = 0; i < n_runs * idx_len[s]; ++i)
+        XMCA_CHECK(idx_host[s][i] >= 0 && idx_host[s][i] < bound, XMCA_ERR_INVALID,
+                   axis == 0 ? "bootstrap: row index out of range" : "bootstrap: column index out of range");
+  const ReplicateSpec spec{T, Nl, Nr, h->boot_fields, op, rotated, p, power, tol};
   const DevBuf<TI>* work = typed<TI>(h).boot;
   run_replicates(h, spec, n_runs, [&](xmca_handle* lh, int64_t first, int64_t stride) {
     DevBuf<int64_t> idx_dev[2];
@@ -1147,15 +1154,48 @@ void bootstrap_runs_impl(xmca_handle* h, const ComplexOp* op, const int64_t* idx
     replicate_lane<TI>(lh, "bootstrap", "resample", spec, first, stride, n_runs, true, spectra, kept, n_out, [&](int s, TI* x, int64_t run) {
       const int64_t N = h->boot_N[s];
       const size_t n = (size_t)T * N;
-      if (idx_host[s]) {
-        XMCA_HIP(hipMemcpyAsync(idx_dev[s].ensure((size_t)T), idx_host[s] + run * T, sizeof(int64_t) * T, hipMemcpyHostToDevice, lh->st));
+      if (!idx_host[s]) {
+        XMCA_HIP(hipMemcpyAsync(x, work[s].get(), sizeof(TI) * n, hipMemcpyDeviceToDevice, lh->st));
+        return;
+      }
+      const int64_t len = idx_len[s];
+      XMCA_HIP(hipMemcpyAsync(idx_dev[s].ensure((size_t)len), idx_host[s] + run * len, sizeof(int64_t) * len, hipMemcpyHostToDevice, lh->st));
+      if (axis == 0)
         hipLaunchKernelGGL((gather_rows_kernel<TI>), ew_grid((int64_t)n, 4), dim3(EW_BLOCK), 0, lh->st, work[s].get(), x, idx_dev[s].get(),
                            (int)T, N);
-      } else {
-        XMCA_HIP(hipMemcpyAsync(x, work[s].get(), sizeof(TI) * n, hipMemcpyDeviceToDevice, lh->st));
-      }
+      else
+        hipLaunchKernelGGL((gather_concat_columns_kernel<TI>), gather_cols_grid(T, N), dim3(GATHER_COLS_BLOCK), 0, lh->st, work[0].get(), Nl,
+                           Nr > 0 ? work[1].get() : (const TI*)nullptr, Nr, idx_dev[s].get(), x, N, (int)T);
     });
   });
+}
+
+// xmca_bootstrap_runs / xmca_bootstrap_runs_columns (axis 0 / 1): replicates complexified with the Hilbert transform, or real
+void bootstrap_runs_entry(xmca_handle* h, int axis, const double* hilbert_col, const int64_t* idx_left, const int64_t* idx_right,
+                          int64_t n_runs, int rotated, int p, int power, double tol, double* spectra_out, int* kept_out, int64_t n_out) {
+  check_bootstrap_runs(spectra_out, kept_out, n_out, n_runs, rotated, p, power);
+  XMCA_CHECK(h->boot_fields >= 1 && h->boot_T > 0, XMCA_ERR_STATE, "bootstrap: call xmca_bootstrap_begin first");
+  ComplexOp hop;
+  if (hilbert_col) hop = ComplexOp::circulant(hilbert_col, h->boot_T);
+  with_dtype(h->dtype, [&](auto t) {
+    bootstrap_runs_impl<decltype(t)>(h, hilbert_col ? &hop : nullptr, axis, idx_left, idx_right, n_runs, rotated, p, power, tol, spectra_out,
+                                     kept_out, n_out);
+  });
+  h->tm.collect();
+}
+
+// xmca_bootstrap_runs_extended / xmca_bootstrap_runs_columns_extended: replicates complexified with the extended operator
+void bootstrap_runs_extended_entry(xmca_handle* h, int axis, const double* col3, const double* hbar, const double* U, const double* W,
+                                   int rank, const int64_t* idx_left, const int64_t* idx_right, int64_t n_runs, int rotated, int p,
+                                   int power, double tol, double* spectra_out, int* kept_out, int64_t n_out) {
+  check_bootstrap_runs(spectra_out, kept_out, n_out, n_runs, rotated, p, power);
+  check_extended_parts("bootstrap", col3, hbar, U, W, rank);
+  XMCA_CHECK(h->boot_fields >= 1 && h->boot_T > 0, XMCA_ERR_STATE, "bootstrap: call xmca_bootstrap_begin first");
+  XMCA_CHECK(h->dtype == XMCA_F64, XMCA_ERR_INVALID, "bootstrap: the extended operator needs float64 fields (the reference's replicates are float64)");
+  check_operator_size("bootstrap", h->boot_T);
+  const ComplexOp op = ComplexOp::extended(col3, hbar, U, W, rank, h->boot_T);
+  bootstrap_runs_impl<double>(h, &op, axis, idx_left, idx_right, n_runs, rotated, p, power, tol, spectra_out, kept_out, n_out);
+  h->tm.collect();
 }
 
 }  // namespace
@@ -1414,15 +1454,7 @@ int xmca_bootstrap_begin(xmca_handle* h, int n_fields) {
 int xmca_bootstrap_runs(xmca_handle* h, const double* hilbert_col, const int64_t* idx_left, const int64_t* idx_right, int64_t n_runs,
                         int rotated, int p, int power, double tol, double* spectra_out, int* kept_out, int64_t n_out) {
   API_BEGIN(h)
-  check_bootstrap_runs(spectra_out, kept_out, n_out, n_runs, rotated, p, power);
-  XMCA_CHECK(h->boot_fields >= 1 && h->boot_T > 0, XMCA_ERR_STATE, "bootstrap: call xmca_bootstrap_begin first");
-  ComplexOp hop;
-  if (hilbert_col) hop = ComplexOp::circulant(hilbert_col, h->boot_T);
-  with_dtype(h->dtype, [&](auto t) {
-    bootstrap_runs_impl<decltype(t)>(h, hilbert_col ? &hop : nullptr, idx_left, idx_right, n_runs, rotated, p, power, tol, spectra_out,
-                                     kept_out, n_out);
-  });
-  h->tm.collect();
+  bootstrap_runs_entry(h, 0, hilbert_col, idx_left, idx_right, n_runs, rotated, p, power, tol, spectra_out, kept_out, n_out);
   API_END(h)
 }
 
@@ -1430,14 +1462,25 @@ int xmca_bootstrap_runs_extended(xmca_handle* h, const double* col3, const doubl
                                  const int64_t* idx_left, const int64_t* idx_right, int64_t n_runs, int rotated, int p, int power,
                                  double tol, double* spectra_out, int* kept_out, int64_t n_out) {
   API_BEGIN(h)
-  check_bootstrap_runs(spectra_out, kept_out, n_out, n_runs, rotated, p, power);
-  check_extended_parts("bootstrap", col3, hbar, U, W, rank);
-  XMCA_CHECK(h->boot_fields >= 1 && h->boot_T > 0, XMCA_ERR_STATE, "bootstrap: call xmca_bootstrap_begin first");
-  XMCA_CHECK(h->dtype == XMCA_F64, XMCA_ERR_INVALID, "bootstrap: the extended operator needs float64 fields (the reference's replicates are float64)");
-  check_operator_size("bootstrap", h->boot_T);
-  const ComplexOp op = ComplexOp::extended(col3, hbar, U, W, rank, h->boot_T);
-  bootstrap_runs_impl<double>(h, &op, idx_left, idx_right, n_runs, rotated, p, power, tol, spectra_out, kept_out, n_out);
-  h->tm.collect();
+  bootstrap_runs_extended_entry(h, 0, col3, hbar, U, W, rank, idx_left, idx_right, n_runs, rotated, p, power, tol, spectra_out, kept_out,
+                                n_out);
+  API_END(h)
+}
+
+int xmca_bootstrap_runs_columns(xmca_handle* h, const double* hilbert_col, const int64_t* cols_left, const int64_t* cols_right,
+                                int64_t n_runs, int rotated, int p, int power, double tol, double* spectra_out, int* kept_out,
+                                int64_t n_out) {
+  API_BEGIN(h)
+  bootstrap_runs_entry(h, 1, hilbert_col, cols_left, cols_right, n_runs, rotated, p, power, tol, spectra_out, kept_out, n_out);
+  API_END(h)
+}
+
+int xmca_bootstrap_runs_columns_extended(xmca_handle* h, const double* col3, const double* hbar, const double* U, const double* W,
+                                         int rank, const int64_t* cols_left, const int64_t* cols_right, int64_t n_runs, int rotated,
+                                         int p, int power, double tol, double* spectra_out, int* kept_out, int64_t n_out) {
+  API_BEGIN(h)
+  bootstrap_runs_extended_entry(h, 1, col3, hbar, U, W, rank, cols_left, cols_right, n_runs, rotated, p, power, tol, spectra_out,
+                                kept_out, n_out);
   API_END(h)
 }
 
