@@ -92,8 +92,9 @@ def solve(fields, complexify=False):
 # ----------------------------------------------------------------------------
 # Varimax / Promax (xmca/tools/rotation.py:15-78, :84-149)
 # ----------------------------------------------------------------------------
-def varimax(A, gamma=1.0, max_iter=1000, tol=1e-8):
-    """Kaiser-normalised Varimax.  Returns (B, R, n_iter).
+def varimax(A, gamma=1.0, max_iter=1000, tol=1e-8, ratios=None):
+    """Kaiser-normalised Varimax.  Returns (B, R, n_iter).  `ratios` (a list, optional) receives ``|d-d_old|/d`` of every
+    iteration: what the stopping rule compared with `tol` (tests that assert the iteration count check its margin).
 
     rotation.py:46-48 row normalisation; :52-64 loop
     ``Z=AR; G=A^H(Z^2 conj(Z) - gamma/n Z diag(colsum|Z|^2)); R=U V^H; d=sum(s)``
@@ -116,6 +117,8 @@ def varimax(A, gamma=1.0, max_iter=1000, tol=1e-8):
         R = u @ vh
         d = np.sum(s)
         n_iter = it + 1
+        if ratios is not None:
+            ratios.append(float(abs(d - d_prev) / d))
         if abs(d - d_prev) / d < tol:
             break
     else:

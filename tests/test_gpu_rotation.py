@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from golden_inputs import GOLDEN_DIR, make_input
+from oracle.promax_edges import wide_loadings as _wide_loadings      # many-mode inputs, shared with test_gpu_promax_edges.py
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-7
@@ -70,21 +71,6 @@ def test_zero_row_is_linalg_error(hip):
     A[7] = 0.0           # Kaiser normalisation divides by the row norm -> NaN, as in the reference
     with pytest.raises(np.linalg.LinAlgError):
         hip.rotate_loadings(A, n_left=A.shape[0])
-
-
-def _wide_loadings(n, p, cplx, seed):
-    rng = np.random.default_rng(seed)
-    L = 0.15 * rng.standard_normal((n, p))
-    w = n // p
-    for j in range(p):
-        L[j * w:(j + 1) * w, j] += np.hanning(w) * (3.0 - 0.05 * j)
-    if cplx:
-        L = L * np.exp(1j * rng.uniform(0, 2 * np.pi, (n, 1)) * 0.3) + 0.05j * rng.standard_normal((n, p))
-        M = rng.standard_normal((p, p)) + 1j * rng.standard_normal((p, p))
-    else:
-        M = rng.standard_normal((p, p))
-    Q, _ = np.linalg.qr(M)
-    return L @ Q
 
 
 @pytest.mark.parametrize("n,p,cplx,seed", [(900, 17, False, 55), (600, 20, False, 51), (480, 24, True, 52),
