@@ -103,6 +103,33 @@ int xmca_get_vectors(xmca_handle* h, int side, void* out, int64_t n_modes, int d
  * the first q = m vectors as they are.  The output is complex (interleaved) when the model or W is; dtype: float32 / float64. */
 int xmca_get_eofs(xmca_handle* h, int side, const double* W, int64_t m, int64_t q, int w_is_complex, void* out, int dtype);
 
+/* Spatial maps in their final layout: MCA.eofs() with a scaling, a phase shift or masked grid points, spatial_amplitude() and
+ * spatial_phase() (xmca/array.py:690-712, :1090-1093, :1122; an entry point added to ABI 14 - no existing signature changes).  The
+ * compact values z[n][c] = (sum_{mm < m} V[n][mm] W[mm][c]) * col_factor[c] of the N' grid points of `side` are those of xmca_get_eofs
+ * (W, m, q, w_is_complex as there; W == NULL: the first q = m vectors), times a per-column factor.
+ *   col_factor  q float64 values, interleaved complex when factor_is_complex, host memory (the 'eigen' norms, the phase shift
+ *               e^{i phi}), or NULL
+ *   keep_idx    N' increasing row indices (int64) below N_full: the grid points the model kept, as in xmca_correlation_maps; every other
+ *               row of `out` is NaN (both planes of a complex output).  NULL: N_full = N', no masked points
+ *   kind        XMCA_MAP_EOF: z, complex (interleaved) when the model, W or the factor is;  XMCA_MAP_AMPLITUDE: sqrt(re^2 + im^2), real;
+ *               XMCA_MAP_PHASE: atan2(im, re), real (a real model has im = +0: 0 or pi)
+ *   scaling     XMCA_SCALE_NONE;  XMCA_SCALE_MAX: column c is divided by its largest |Re z| (EOF) or amplitude (AMPLITUDE) over the N'
+ *               points;  XMCA_SCALE_STD (EOF only): by the population standard deviation (ddof 0) of Re z.  Any other combination is
+ *               XMCA_ERR_INVALID.  The division is plain IEEE: a zero column gives inf / NaN as numpy does
+ *   out         N_full x q of `dtype` (XMCA_F32 / XMCA_F64 components), host memory
+ *   stat_out    NULL, or q float64 divisors (written when scaling is not NONE)
+ * The statistics are float64 sums merged in a fixed order (no atomics): two calls give the same bits.  With scaling NONE and no factor
+ * the kept rows are bit for bit those of xmca_get_eofs.  The resident fields, vectors and rotation state are not changed. */
+#define XMCA_MAP_EOF 0
+#define XMCA_MAP_AMPLITUDE 1
+#define XMCA_MAP_PHASE 2
+#define XMCA_SCALE_NONE 0
+#define XMCA_SCALE_MAX 1
+#define XMCA_SCALE_STD 2
+int xmca_get_maps(xmca_handle* h, int side, const double* W, int64_t m, int64_t q, int w_is_complex, const double* col_factor,
+                  int factor_is_complex, const int64_t* keep_idx, int64_t N_full, int kind, int scaling, void* out, int dtype,
+                  double* stat_out);
+
 /* PC projection of MCA._get_U (xmca/array.py:648-674, the product `fields[k] @ V[k]`): U = X~ V with X~ the field of
  * `side` as solve() saw it - still resident on the device; the analytic signal X + i Ht X when complexify was
  * requested (the imaginary field plane is not needed: U = W + i Ht W with W = X V); X + i G X after

@@ -39,6 +39,7 @@ SIGNATURES = {
     "xmca_get_singular_values": (_c_int, [_vp, _vp, _c_i64]),
     "xmca_get_vectors": (_c_int, [_vp, _c_int, _vp, _c_i64, _c_int]),
     "xmca_get_eofs": (_c_int, [_vp, _c_int, _vp, _c_i64, _c_i64, _c_int, _vp, _c_int]),
+    "xmca_get_maps": (_c_int, [_vp, _c_int, _vp, _c_i64, _c_i64, _c_int, _vp, _c_int, _vp, _c_i64, _c_int, _c_int, _vp, _c_int, _vp]),
     "xmca_center_field": (_c_int, [_vp, _c_int, _vp, _vp, ctypes.POINTER(_c_i64)]),
     "xmca_compact_field": (_c_int, [_vp, _c_int, _vp, ctypes.POINTER(_c_i64)]),
     "xmca_scale_field": (_c_int, [_vp, _c_int, _vp, _c_int]),
@@ -98,7 +99,9 @@ def library_path():
     return _build.LIB
 
 
-PVALUE_MAX_OBS = 1000000     # largest n_obs of xmca_pearson_pvalues / xmca_correlation_maps (csrc/kernels.h)
+MAP_EOF, MAP_AMPLITUDE, MAP_PHASE = 0, 1, 2          # `kind` of xmca_get_maps
+SCALE_NONE, SCALE_MAX, SCALE_STD = 0, 1, 2           # ... and its `scaling`
+PVALUE_MAX_OBS = 1000000    # largest n_obs of xmca_pearson_pvalues / xmca_correlation_maps (csrc/kernels.h)
 ABI_VERSION = 14         # bumped whenever a signature of include/xmca_hip.h changes; checked against xmca_abi_version()
 
 
@@ -404,6 +407,31 @@ class Handle:
         out = np.empty((N, q), dtype=_cplx_np(code) if cplx or w_cplx else _real_np(code))
         self._check(self._lib.xmca_get_eofs(self._h, side, _ptr(W), m, q, int(w_cplx), _ptr(out), code))
         return out
+
+    def maps(self, side, N, m, W, col_factor, keep_idx, N_full, kind, scaling, dtype, want_stats=False):
+        """(N_full x q) spatial map of `side` in its final layout (xmca_get_maps): the values of `eofs(side, N, m, W, dtype)` times the
+        q per-column factors `col_factor` (None: as they are), as EOFs, amplitudes or phases (`kind`: MAP_*), every column divided
+        by its largest value or its standard deviation over the N kept points (`scaling`: SCALE_*), NaN at the rows not in keep_idx
+        (None: N_full = N).  `dtype`: float32 / float64 components of the result.  want_stats: (map, the q float64 divisors)."""
+        cplx = bool(self._lib.xmca_is_complex(self._h))
+        code = _np_dtype_code(dtype)
+        W, w_cplx = _host_vectors(W)
+        if W is not None:
+            m, q = W.shape
+        else:
+            q = m
+        f, f_cplx = _host_vectors(col_factor)
+        if f is not None and f.shape != (q,):
+            raise ValueError("maps: col_factor must hold one value per column (%d), got shape %s" % (q, f.shape))
+        idx = None if keep_idx is None else np.ascontiguousarray(keep_idx, dtype=np.int64)
+        if idx is not None and idx.shape != (N,):
+            raise ValueError("maps: keep_idx must hold one row index per kept point (%d), got shape %s" % (N, idx.shape))
+        o_cplx = kind == MAP_EOF and (cplx or w_cplx or f_cplx)
+        out = np.empty((int(N_full), q), dtype=_cplx_np(code) if o_cplx else _real_np(code))
+        stats = np.full(q, np.nan) if want_stats else None
+        self._check(self._lib.xmca_get_maps(self._h, side, _ptr(W), m, q, int(w_cplx), _ptr(f), int(f_cplx), _ptr(idx), int(N_full),
+                                            int(kind), int(scaling), _ptr(out), code, _ptr(stats)))
+        return (out, stats) if want_stats else out
 
     def project(self, side, V, T, m=None, N=None):
         """U = X~ V (T x m) on the resident field of `side` (the analytic signal when the model is complex);

@@ -22,6 +22,8 @@ from . import __version__, _hip
 from .tools.array import (block_bootstrap, get_nan_cols, has_nan_time_steps, pearsonr, remove_mean, remove_nan_cols)
 
 _SCALINGS_MSG = ('The scaling option {:} is not valid. Please choose one of the following: None, eigen, std, max')
+# `scaling` of the spatial getters -> the divisor `xmca_get_maps` computes ('eigen' is a per-column factor, not a divisor)
+_MAP_SCALINGS = {'None': _hip.SCALE_NONE, 'eigen': _hip.SCALE_NONE, 'max': _hip.SCALE_MAX, 'std': _hip.SCALE_STD}
 
 
 def _two_sided_p(r, n_obs):
@@ -742,10 +744,19 @@ class MCA:
         """(N' x q) array per field in its final memory layout, mixed on the device from the vectors still resident there
         (`xmca_get_eofs`), or None when they are not (then `_get_V`'s host path is taken).  Same numbers as `_get_V`:
         `(V sqrt(s)) @ R / norm`, columns ordered by explained variance, then the requested slice (array.py:615-646)."""
-        if not self._vectors_resident():
+        mix = self._eof_mix(n, rotated)
+        if mix is None:
             return None                                   # (vectors already on the host - or injected by a test: no device needed)
-        Vl = self._V
         dev = self._device()
+        return {k: dev.eofs(side, n_k, m, W, dtype) for k, (side, n_k, m, W, dtype) in mix.items()}
+
+    def _eof_mix(self, n, rotated):
+        """Arguments of `xmca_get_eofs` / `xmca_get_maps` per field - (side, N', m, W, component dtype): the resident vectors
+        V[:, :m], the m x q mix W (None: the first q = m vectors as they are) - or None when the vectors are not resident or the
+        selection is empty."""
+        if not self._vectors_resident():
+            return None
+        Vl = self._V
         rotated = rotated and self._analysis['is_rotated']
         max_mode = self._max_mode(n, rotated)
         max_mode = self._analysis['rank'] if max_mode is None else min(max_mode, self._analysis['rank'])
@@ -758,17 +769,67 @@ class MCA:
             if rotated:
                 norm = self._get_norm(max_mode, sorted=False)
                 W = _rotated_mix(self._get_svals(max_mode), self.rotation_matrix(), norm[k], self._var_idx, keep)
-                out[k] = dev.eofs(side, n_k, max_mode, W, np.float64)
+                out[k] = (side, n_k, max_mode, W, np.float64)
             else:
                 cols = range(max_mode)[keep]
                 if cols.start == 0 and cols.step == 1:
-                    out[k] = dev.eofs(side, n_k, len(cols), None, Vl._dtype)
+                    out[k] = (side, n_k, len(cols), None, Vl._dtype)
                 else:
-                    W = np.eye(max_mode)[:, keep]
-                    out[k] = dev.eofs(side, n_k, max_mode, W, Vl._dtype)
+                    out[k] = (side, n_k, max_mode, np.eye(max_mode)[:, keep], Vl._dtype)
+        return out
+
+    def _maps_from_device(self, n, rotated, kind, scaling='None', phase_shift=0):
+        """eofs() / spatial_amplitude() / spatial_phase() of every field in their final (space..., modes) arrays from the device
+        (`xmca_get_maps`): phase shift and 'eigen' norms as per-column factors, 'max' / 'std' divisors, amplitude or phase and the
+        NaN rows of the masked grid points, without a pass over N x q on the host.  The dtype of each result is worked out here with
+        the promotions the numpy code below performs, and passed down.  None when the vectors are not resident, the selection is
+        empty, `_maps_on_host` is set or a float32 / complex64 result is to be scaled by 'std': the caller then runs the numpy code."""
+        if getattr(self, '_maps_on_host', False) or scaling not in _MAP_SCALINGS:
+            return None
+        mix = self._eof_mix(n, rotated)
+        if mix is None:
+            return None
+        dev = self._device()
+        cplx = self._analysis['is_complex']
+        shift = cmath.rect(1, phase_shift) if cplx and phase_shift != 0 else None
+        plan = {}
+        for k, (side, n_k, m, W, dtype) in mix.items():
+            q = m if W is None else W.shape[1]
+            dt = np.result_type(dtype, np.complex64) if cplx or np.iscomplexobj(W) else np.dtype(dtype)
+            factor = None
+            if shift is not None:
+                dt = (np.zeros(0, dtype=dt) * shift).dtype
+                factor = np.full(q, shift)
+            if scaling == 'eigen':
+                norm = self._get_norm(q, sorted=True)[k]
+                if norm.shape != (q,):
+                    return None                           # (the numpy code raises numpy's own broadcasting error)
+                dt = np.result_type(dt, norm.dtype)
+                factor = norm if factor is None else factor * norm
+            if scaling == 'std' and dt in (np.float32, np.complex64):
+                # the reference's divisor of a float32 result is `np.nanstd` in float32: it adds the N' squares one after the other
+                # in float32 and is off by 3e-5 at N' = 4e4, fifteen times the 2e-6 this class holds float32 results to against the
+                # reference's arithmetic - the device's float64 sums would not be that number, so the numpy code keeps this case
+                return None
+            if kind != _hip.MAP_EOF:
+                dt = np.zeros(0, dtype=dt).real.dtype
+            plain = kind == _hip.MAP_EOF and factor is None and scaling == 'None' and self._n_variables[k] == n_k
+            plan[k] = (side, n_k, m, W, dtype, factor, dt, plain)
+        out = {}
+        for k, (side, n_k, m, W, dtype, factor, dt, plain) in plan.items():
+            if plain:
+                full = dev.eofs(side, n_k, m, W, dtype)   # no mask, no scaling, no phase shift: `xmca_get_eofs` as it is
+            else:
+                masked = self._n_variables[k] != n_k
+                full = dev.maps(side, n_k, m, W, factor, np.flatnonzero(self._no_nan_index[k]) if masked else None,
+                                self._n_variables[k], kind, _MAP_SCALINGS[scaling], dt)
+            out[k] = full.reshape(self._fields_spatial_shape[k] + (full.shape[1],))
         return out
 
     def _get_eofs(self, n=None, scaling='None', phase_shift=0, rotated=True):
+        eofs = self._maps_from_device(n, rotated, _hip.MAP_EOF, scaling, phase_shift)
+        if eofs is not None:
+            return eofs
         V = self._eofs_from_device(n, rotated)
         fresh = V is not None                 # arrays of the device path are the caller's; `_get_V` may return views of `_V`
         if V is None:
@@ -910,6 +971,9 @@ class MCA:
         return self._get_eofs(n, scaling, phase_shift, rotated)
 
     def spatial_amplitude(self, n=None, scaling='None', rotated=True):
+        out = self._maps_from_device(n, rotated, _hip.MAP_AMPLITUDE, 'max' if scaling == 'max' else 'None')
+        if out is not None:
+            return out
         out = {}
         for k, eof in self.eofs(n, scaling='None', rotated=rotated).items():
             out[k] = np.sqrt(eof * eof.conjugate()).real
@@ -918,6 +982,9 @@ class MCA:
         return out
 
     def spatial_phase(self, n=None, phase_shift=0, rotated=True):
+        out = self._maps_from_device(n, rotated, _hip.MAP_PHASE, 'None', phase_shift)
+        if out is not None:
+            return out
         return {k: np.arctan2(e.imag, e.real).real
                 for k, e in self.eofs(n, phase_shift=phase_shift, rotated=rotated).items()}
 

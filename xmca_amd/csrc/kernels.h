@@ -694,6 +694,158 @@ __global__ void correlation_maps_kernel(const double* __restrict__ C, const int6
 }
 
 // ------------------------------------------------------------------------------------------------
+// Spatial maps in their final layout (xmca_get_maps): scaled / masked EOFs, amplitude and phase maps from the compact n x q values
+// C that eof_mix_kernel / eof_transpose_kernel leave on the device (float64 whatever the output type - the statistics are those of
+// the unrounded values, and a value that is only rounded at the end has the bits xmca_get_eofs returns; interleaved when `cc`).
+// ------------------------------------------------------------------------------------------------
+constexpr int MAP_EOF = 0, MAP_AMPLITUDE = 1, MAP_PHASE = 2;       // XMCA_MAP_* of the header
+constexpr int STAT_MAX_RE = 0, STAT_MAX_AMP = 1, STAT_STD = 2;     // what a column is divided by
+constexpr int MAP_STAT_BLOCKS = 1024;                              // most partials per column
+
+// z = C[idx] * f: the per-column factor (fr, fi) is applied only when there is one (`hf`), so that values without a factor pass
+// bit for bit; a real value with a real factor keeps im = +0 (atan2 then gives 0 or pi, as numpy does for a real array)
+__device__ __forceinline__ void map_value(const double* __restrict__ C, bool cc, int64_t idx, bool hf, bool fc, double fr, double fi,
+                                          double& re, double& im) {
+  double vr, vi = 0.0;
+  if (cc) { vr = C[2 * idx]; vi = C[2 * idx + 1]; }
+  else vr = C[idx];
+  if (!hf) { re = vr; im = vi; }
+  else if (fc) { re = vr * fr - vi * fi; im = vr * fi + vi * fr; }
+  else { re = vr * fr; im = cc ? vi * fr : 0.0; }
+}
+
+// (count, mean, M2) of two disjoint samples -> of their union (Chan, Golub & LeVeque 1983); an empty side changes nothing
+__device__ __forceinline__ void moments_merge(double& na, double& ma, double& qa, double nb, double mb, double qb) {
+  const double n = na + nb;
+  if (nb == 0.0) return;
+  const double d = mb - ma, w = nb / n;
+  ma += d * w;
+  qa += qb + d * d * na * w;
+  na = n;
+}
+
+// Partials of the column statistics: workgroup b reduces the rows b * 256 + t + k * 256 * gridDim.x of every column to ONE partial -
+// the largest |Re z| or |z|, or the (count, mean, M2) of Re z - in part[(b * q + c) * NP .. + NP), NP = 3 for STAT_STD and 1
+// otherwise.  One row per lane, 8 columns at a time in registers (the row's values lie side by side); every column is reduced over
+// the 64 lanes of a wave by shuffles, then over the four waves through LDS.  No atomics: the same bits every call.  The moments are Welford's recurrence per lane and Chan's merge from there on, never E[x^2] - E[x]^2.
+template <int STAT>
+__global__ __launch_bounds__(256) void map_column_partials_kernel(const double* __restrict__ C, int cc, int64_t n, int q,
+                                                                 const double* __restrict__ fr, const double* __restrict__ fi,
+                                                                 double* __restrict__ part) {
+  constexpr int NP = STAT == STAT_STD ? 3 : 1;
+  __shared__ double red[4][8][NP];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const bool hf = fr != nullptr, fc = fi != nullptr;
+  for (int c0 = 0; c0 < q; c0 += 8) {
+    double a0[8], a1[8], a2[8], pr[8], pi[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int c = c0 + u < q ? c0 + u : q - 1;
+      a0[u] = a1[u] = a2[u] = 0.0;
+      pr[u] = hf ? fr[c] : 1.0;
+      pi[u] = fc ? fi[c] : 0.0;
+    }
+    for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < n; r += (int64_t)gridDim.x * 256) {
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int c = c0 + u < q ? c0 + u : q - 1;
+        double re, im;
+        map_value(C, cc != 0, r * q + c, hf, fc, pr[u], pi[u], re, im);
+        if constexpr (STAT == STAT_STD) {
+          a0[u] += 1.0;
+          const double d = re - a1[u];
+          a1[u] += d / a0[u];
+          a2[u] += d * (re - a1[u]);
+        } else if constexpr (STAT == STAT_MAX_AMP) {
+          a0[u] = fmax(a0[u], sqrt(re * re + im * im));
+        } else {
+          a0[u] = fmax(a0[u], fabs(re));
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+#pragma unroll
+      for (int s = 32; s >= 1; s >>= 1) {
+        if constexpr (STAT == STAT_STD) {
+          const double nb = __shfl_xor(a0[u], s, 64), mb = __shfl_xor(a1[u], s, 64), qb = __shfl_xor(a2[u], s, 64);
+          // (both lanes of a pair merge the same two samples, the lower lane's first, so they agree bit for bit)
+          if (lane & s) {
+            double nn = nb, mm = mb, qq = qb;
+            moments_merge(nn, mm, qq, a0[u], a1[u], a2[u]);
+            a0[u] = nn; a1[u] = mm; a2[u] = qq;
+          } else {
+            moments_merge(a0[u], a1[u], a2[u], nb, mb, qb);
+          }
+        } else {
+          a0[u] = fmax(a0[u], __shfl_xor(a0[u], s, 64));
+        }
+      }
+      if (lane == 0) {
+        red[wave][u][0] = a0[u];
+        if constexpr (STAT == STAT_STD) { red[wave][u][1] = a1[u]; red[wave][u][2] = a2[u]; }
+      }
+    }
+    __syncthreads();
+    if (threadIdx.x < 8 && c0 + (int)threadIdx.x < q) {
+      const int u = threadIdx.x;
+      double* o = part + ((int64_t)blockIdx.x * q + c0 + u) * NP;
+      if constexpr (STAT == STAT_STD) {
+        double nn = red[0][u][0], mm = red[0][u][1], qq = red[0][u][2];
+        for (int w = 1; w < 4; ++w) moments_merge(nn, mm, qq, red[w][u][0], red[w][u][1], red[w][u][2]);
+        o[0] = nn; o[1] = mm; o[2] = qq;
+      } else {
+        o[0] = fmax(fmax(red[0][u][0], red[1][u][0]), fmax(red[2][u][0], red[3][u][0]));
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// ... and their merge, in the order of the workgroups: div[c] = the maximum, or the population standard deviation sqrt(M2 / count)
+template <int STAT>
+__global__ void map_column_finish_kernel(const double* __restrict__ part, int blocks, int q, double* __restrict__ div) {
+  constexpr int NP = STAT == STAT_STD ? 3 : 1;
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= q) return;
+  double nn = part[(int64_t)c * NP], mm = 0.0, qq = 0.0;
+  if constexpr (STAT == STAT_STD) { mm = part[(int64_t)c * NP + 1]; qq = part[(int64_t)c * NP + 2]; }
+  for (int b = 1; b < blocks; ++b) {
+    const double* p = part + ((int64_t)b * q + c) * NP;
+    if constexpr (STAT == STAT_STD) moments_merge(nn, mm, qq, p[0], p[1], p[2]);
+    else nn = fmax(nn, p[0]);
+  }
+  div[c] = STAT == STAT_STD ? sqrt(qq / nn) : nn;
+}
+
+// Final layout: row j of the n_full x q output is row row_of[j] of C (row_of == nullptr: j itself) times the factor of its column,
+// as value (MAP_EOF; interleaved complex when `oc`), sqrt(re^2 + im^2) or atan2(im, re), divided by div[c] (nullptr: as it is; a
+// plain IEEE division, a zero column gives inf / NaN as on the host) and rounded to TO; NaN - in both planes - where row_of[j] < 0.
+template <typename TO>
+__global__ void map_finish_kernel(const double* __restrict__ C, int cc, const int64_t* __restrict__ row_of, int64_t n_full, int q,
+                                  const double* __restrict__ fr, const double* __restrict__ fi, const double* __restrict__ div,
+                                  int kind, int oc, TO* __restrict__ out) {
+  const int64_t total = n_full * q;
+  const bool hf = fr != nullptr, fc = fi != nullptr;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t j = i / q;
+    const int c = (int)(i - j * q);
+    const int64_t r = row_of ? row_of[j] : j;
+    double re, im;
+    if (r < 0) {
+      re = im = __builtin_nan("");
+    } else {
+      map_value(C, cc != 0, r * q + c, hf, fc, hf ? fr[c] : 1.0, fc ? fi[c] : 0.0, re, im);
+      if (kind == MAP_AMPLITUDE) re = sqrt(re * re + im * im);
+      else if (kind == MAP_PHASE) re = atan2(im, re);
+      if (div) { const double d = div[c]; re /= d; im /= d; }
+    }
+    if (oc) { out[2 * i] = (TO)re; out[2 * i + 1] = (TO)im; }
+    else out[i] = (TO)re;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Philox4x32-10 counter-based generator (Salmon et al. 2011) -> standard normals (Box-Muller).
 // counter = (element pair index lo, hi, run, side), key = seed: the stream of a surrogate depends only on
 // (seed, run, side), never on which GPU generates it.

@@ -386,15 +386,15 @@ void get_vectors_impl(xmca_handle* h, int side, void* out, int64_t m) {
 }
 
 // EOFs of `side` in the reference's final layout (see xmca_get_eofs): N x q, mixed on the device from the resident mode-major vectors
+// ... into `tmp` on the device (N x q, interleaved when the model or W is complex); `w` holds the uploaded W until the caller has
+// synchronised the stream
 template <typename TO>
-void get_eofs_impl(xmca_handle* h, int side, const double* W, int64_t m, int64_t q, bool w_cplx, void* out) {
+void eofs_compact(xmca_handle* h, int side, const double* W, int64_t m, int64_t q, bool w_cplx, HostPlanes<double>& w, DevBuf<TO>& tmp) {
   const SolveResult& r = h->res;
   const int64_t N = r.ldv[side];
   const bool v_cplx = r.cplx, o_cplx = v_cplx || (W && w_cplx);
   const size_t n_out = (size_t)N * q * (o_cplx ? 2 : 1);
-  DevBuf<TO> tmp;
   tmp.ensure(n_out);
-  HostPlanes<double> w;
   if (W) {
     upload_planes<double>(h, W, (size_t)m * q, w_cplx, w, false);
     const dim3 grid((unsigned)ceil_div(N, 256));
@@ -410,7 +410,67 @@ void get_eofs_impl(xmca_handle* h, int side, const double* W, int64_t m, int64_t
       hipLaunchKernelGGL((eof_transpose_kernel<double, TO>), grid, dim3(256), 0, h->st, r.Vt[side].r(), r.Vt[side].i(v_cplx), N, N, (int)q, tmp.get());
   }
   XMCA_HIP(hipGetLastError());
+}
+
+template <typename TO>
+void get_eofs_impl(xmca_handle* h, int side, const double* W, int64_t m, int64_t q, bool w_cplx, void* out) {
+  const bool o_cplx = h->res.cplx || (W && w_cplx);
+  const size_t n_out = (size_t)h->res.ldv[side] * q * (o_cplx ? 2 : 1);
+  DevBuf<TO> tmp;
+  HostPlanes<double> w;
+  eofs_compact<TO>(h, side, W, m, q, w_cplx, w, tmp);
   XMCA_HIP(hipMemcpyAsync(out, tmp.get(), n_out * sizeof(TO), hipMemcpyDeviceToHost, h->st));
+  XMCA_HIP(hipStreamSynchronize(h->st));
+}
+
+// Spatial maps of `side` in their final N_full x q layout (see xmca_get_maps): the compact EOFs as above, the divisors of the
+// columns (partials per workgroup, merged in a fixed order), then one pass that applies factor, divisor, amplitude / phase and the
+// mask.  The compact values are read twice, the output is written once.
+template <typename TO>
+void get_maps_impl(xmca_handle* h, int side, const double* W, int64_t m, int64_t q, bool w_cplx, const double* col_factor, bool f_cplx,
+                   const int64_t* keep_idx, int64_t N_full, int kind, int scaling, void* out, double* stat_out) {
+  const int64_t N = h->res.ldv[side];
+  const bool c_cplx = h->res.cplx || (W && w_cplx);
+  const bool o_cplx = kind == MAP_EOF && (c_cplx || (col_factor && f_cplx));
+  DevBuf<double> tmp, part, div;      // (the compact values stay float64: rounded once, at the end)
+  DevBuf<TO> fin;
+  DevBuf<int64_t> row_of;
+  HostPlanes<double> w, f;
+  eofs_compact<double>(h, side, W, m, q, w_cplx, w, tmp);
+  if (col_factor) upload_planes<double>(h, col_factor, (size_t)q, f_cplx, f, false);
+  if (keep_idx) {
+    std::vector<int64_t> inv((size_t)N_full, -1);
+    for (int64_t c = 0; c < N; ++c) inv[(size_t)keep_idx[c]] = c;
+    XMCA_HIP(hipMemcpyAsync(row_of.ensure((size_t)N_full), inv.data(), sizeof(int64_t) * N_full, hipMemcpyHostToDevice, h->st));
+    XMCA_HIP(hipStreamSynchronize(h->st));      // (inv is a host temporary)
+  }
+  h->tm.begin("maps");
+  if (scaling != XMCA_SCALE_NONE) {
+    const int blocks = (int)std::min<int64_t>(ceil_div(N, (int64_t)256), MAP_STAT_BLOCKS);
+    const int np = scaling == XMCA_SCALE_STD ? 3 : 1;
+    part.ensure((size_t)blocks * q * np);
+    div.ensure((size_t)q);
+    const dim3 fgrid((unsigned)ceil_div(q, (int64_t)256));
+    auto stats = [&](auto stat) {
+      constexpr int STAT = decltype(stat)::value;
+      hipLaunchKernelGGL((map_column_partials_kernel<STAT>), dim3((unsigned)blocks), dim3(256), 0, h->st, tmp.get(), (int)c_cplx, N, (int)q,
+                         f.r, f.i, part.get());
+      hipLaunchKernelGGL((map_column_finish_kernel<STAT>), fgrid, dim3(256), 0, h->st, part.get(), blocks, (int)q, div.get());
+    };
+    if (scaling == XMCA_SCALE_STD) stats(std::integral_constant<int, STAT_STD>{});
+    else if (kind == MAP_AMPLITUDE) stats(std::integral_constant<int, STAT_MAX_AMP>{});
+    else stats(std::integral_constant<int, STAT_MAX_RE>{});
+    XMCA_HIP(hipGetLastError());
+  }
+  const size_t total = (size_t)N_full * q;
+  hipLaunchKernelGGL((map_finish_kernel<TO>), ew_grid((int64_t)total), dim3(EW_BLOCK), 0, h->st, tmp.get(), (int)c_cplx,
+                     keep_idx ? row_of.get() : nullptr, N_full, (int)q, f.r, f.i, scaling != XMCA_SCALE_NONE ? div.get() : nullptr, kind,
+                     (int)o_cplx, fin.ensure(total * (o_cplx ? 2 : 1)));
+  XMCA_HIP(hipGetLastError());
+  h->tm.end();
+  if (stat_out && scaling != XMCA_SCALE_NONE)
+    XMCA_HIP(hipMemcpyAsync(stat_out, div.get(), sizeof(double) * q, hipMemcpyDeviceToHost, h->st));
+  XMCA_HIP(hipMemcpyAsync(out, fin.get(), sizeof(TO) * total * (o_cplx ? 2 : 1), hipMemcpyDeviceToHost, h->st));
   XMCA_HIP(hipStreamSynchronize(h->st));
 }
 
@@ -1356,6 +1416,34 @@ int xmca_get_eofs(xmca_handle* h, int side, const double* W, int64_t m, int64_t 
   XMCA_CHECK(out && q >= 1 && m >= 1 && m <= h->res.n_vec && (W || q == m) && h->res.ldv[side] > 0, XMCA_ERR_INVALID,
              "get_eofs: more modes requested than were back-projected, or a bad mixing matrix");
   with_dtype(dtype, [&](auto t) { get_eofs_impl<decltype(t)>(h, side, W, m, q, w_is_complex != 0, out); });
+  API_END(h)
+}
+
+int xmca_get_maps(xmca_handle* h, int side, const double* W, int64_t m, int64_t q, int w_is_complex, const double* col_factor,
+                  int factor_is_complex, const int64_t* keep_idx, int64_t N_full, int kind, int scaling, void* out, int dtype,
+                  double* stat_out) {
+  API_BEGIN(h)
+  XMCA_CHECK(h->solved, XMCA_ERR_STATE, "maps requested before solve");
+  check_side("get_maps", side);
+  XMCA_CHECK(out && q >= 1 && q <= INT32_MAX && m >= 1 && m <= h->res.n_vec && (W || q == m) && h->res.ldv[side] > 0, XMCA_ERR_INVALID,
+             "get_maps: more modes requested than were back-projected, or a bad mixing matrix");
+  XMCA_CHECK(dtype == XMCA_F32 || dtype == XMCA_F64, XMCA_ERR_INVALID, "get_maps: dtype must be XMCA_F32 or XMCA_F64");
+  XMCA_CHECK((kind == XMCA_MAP_EOF && (scaling == XMCA_SCALE_NONE || scaling == XMCA_SCALE_MAX || scaling == XMCA_SCALE_STD)) ||
+                 (kind == XMCA_MAP_AMPLITUDE && (scaling == XMCA_SCALE_NONE || scaling == XMCA_SCALE_MAX)) ||
+                 (kind == XMCA_MAP_PHASE && scaling == XMCA_SCALE_NONE),
+             XMCA_ERR_INVALID, "get_maps: EOFs scale by NONE / MAX / STD, amplitudes by NONE / MAX, phases not at all");
+  const int64_t N = h->res.ldv[side];
+  XMCA_CHECK(N_full >= N && N_full <= INT32_MAX && (keep_idx || N_full == N), XMCA_ERR_INVALID,
+             "get_maps: N_full must be the vectors' " + std::to_string(N) + " rows, or more with keep_idx");
+  if (keep_idx) {
+    for (int64_t c = 0; c < N; ++c)
+      XMCA_CHECK(keep_idx[c] >= 0 && keep_idx[c] < N_full && (c == 0 || keep_idx[c] > keep_idx[c - 1]), XMCA_ERR_INVALID,
+                 "get_maps: keep_idx must be increasing row indices below N_full, one per row of the vectors");
+  }
+  with_dtype(dtype, [&](auto t) {
+    get_maps_impl<decltype(t)>(h, side, W, m, q, w_is_complex != 0, col_factor, factor_is_complex != 0, keep_idx, N_full, kind, scaling,
+                               out, stat_out);
+  });
   API_END(h)
 }
 
