@@ -362,6 +362,13 @@ int xmca_trim_pool(xmca_handle* h);
  * b_nfast: B(k,n) = B[k*ldb + n] else B[n*ldb + k];  dtype of A and B; upper_only/mirror as in gemm.h. */
 int xmca_gemm(xmca_handle* h, const void* A, int64_t lda, int a_kfast, const void* B, int64_t ldb, int b_nfast, double* C,
               int M, int N, int K, int dtype, double alpha, int upper_only, int mirror, int splits);
+/* The same product with the epilogue options of gemm.h:  C = alpha * row_scale[m] * col_scale[n] * op(A) op(B) + beta * C.
+ * C (host, M rows of ldc >= N elements, c_dtype XMCA_F32 / XMCA_F64) goes to the device as it is, is read only when
+ * beta != 0, and comes back whole, the ldc - N padding elements of every row included; row_scale (M) and col_scale (N)
+ * are host float64 arrays or NULL. */
+int xmca_gemm_ex(xmca_handle* h, const void* A, int64_t lda, int a_kfast, const void* B, int64_t ldb, int b_nfast, void* C,
+                 int64_t ldc, int c_dtype, int M, int N, int K, int dtype, double alpha, double beta, const double* row_scale,
+                 const double* col_scale, int upper_only, int mirror, int splits);
 /* Hermitian eigendecomposition of an n x n host matrix (interleaved complex when is_complex):
  * lam (n, descending) and Zh (n x n, row i = conj(u_i); NULL: eigenvalues only); info (4 ints): sweeps, tile, slots,
  * bit 0: Cholesky LR step taken, bit 1: solved by tridiagonalisation (csrc/tridiag.h; then no sweeps).  The device time of the

@@ -86,6 +86,8 @@ SIGNATURES = {
     "xmca_trim_pool": (_c_int, [_vp]),
     "xmca_gemm": (_c_int, [_vp, _vp, _c_i64, _c_int, _vp, _c_i64, _c_int, _vp, _c_int, _c_int, _c_int, _c_int, _c_dbl,
                            _c_int, _c_int, _c_int]),
+    "xmca_gemm_ex": (_c_int, [_vp, _vp, _c_i64, _c_int, _vp, _c_i64, _c_int, _vp, _c_i64, _c_int, _c_int, _c_int, _c_int, _c_int,
+                              _c_dbl, _c_dbl, _vp, _vp, _c_int, _c_int, _c_int]),
     "xmca_eigh": (_c_int, [_vp, _vp, _c_int, _c_int, _vp, _vp, _vp]),
     "xmca_cholesky": (_c_int, [_vp, _vp, _c_int, _c_int, _c_dbl, _vp, ctypes.POINTER(_c_int)]),
     "xmca_bench_gram": (_c_int, [_vp, _c_int, _c_int, _dp, _dp, _dp]),
@@ -697,18 +699,60 @@ class Handle:
         self._check(self._lib.xmca_trim_pool(self._h))
 
     # ---- kernel-level entry points --------------------------------------------------------------
-    def gemm(self, A, B, a_kfast=True, b_nfast=True, alpha=1.0, upper_only=False, mirror=0, splits=0):
-        """C = alpha * op(A) op(B); A: (M,K) if a_kfast else (K,M); B: (K,N) if b_nfast else (N,K)."""
-        A = np.ascontiguousarray(A)
-        B = np.ascontiguousarray(B, dtype=A.dtype)
-        code = _np_dtype_code(A.dtype)
+    @staticmethod
+    def _gemm_operand(X, ld, dtype=None):
+        """One operand of gemm / gemm_ex and its leading dimension.  Without `ld`: a contiguous copy, ld = its width.  With
+        `ld`: X is the view buf[:, :width] of a C-contiguous (rows, ld) array - rows `ld` elements apart, and all
+        rows * ld elements behind its first one exist, since the entry point uploads that many."""
+        if ld is None:
+            X = np.ascontiguousarray(X, dtype=dtype)
+            return X, X.shape[1]
+        ld = int(ld)
+        root = X
+        while isinstance(root.base, np.ndarray):
+            root = root.base
+        rows, width = X.shape
+        it = X.itemsize
+        ok = (X.ndim == 2 and (dtype is None or X.dtype == dtype) and ld >= width and X.strides[1] == it
+              and (rows == 1 or X.strides[0] == ld * it) and root.flags.c_contiguous
+              and X.ctypes.data + rows * ld * it <= root.ctypes.data + root.nbytes)
+        if not ok:
+            raise ValueError("gemm: with a leading dimension the operand must be buf[:, :width] of a contiguous (rows, ld) array")
+        return X, ld
+
+    def _gemm_shapes(self, A, B, a_kfast, b_nfast, lda, ldb):
+        A, lda = self._gemm_operand(A, lda)
+        B, ldb = self._gemm_operand(B, ldb, A.dtype)
         M, K = A.shape if a_kfast else A.shape[::-1]
         Kb, N = B.shape if b_nfast else B.shape[::-1]
         if K != Kb:
             raise ValueError("gemm: inner dimensions differ")
+        return A, B, M, N, K, lda, ldb, _np_dtype_code(A.dtype)
+
+    def gemm(self, A, B, a_kfast=True, b_nfast=True, alpha=1.0, upper_only=False, mirror=0, splits=0, lda=None, ldb=None):
+        """C = alpha * op(A) op(B); A: (M,K) if a_kfast else (K,M); B: (K,N) if b_nfast else (N,K).  `lda` / `ldb`: rows
+        of the operand that many elements apart (see _gemm_operand); default: its width."""
+        A, B, M, N, K, lda, ldb, code = self._gemm_shapes(A, B, a_kfast, b_nfast, lda, ldb)
         C = np.zeros((M, N), dtype=np.float64)
-        self._check(self._lib.xmca_gemm(self._h, _ptr(A), A.shape[1], int(a_kfast), _ptr(B), B.shape[1], int(b_nfast),
+        self._check(self._lib.xmca_gemm(self._h, _ptr(A), lda, int(a_kfast), _ptr(B), ldb, int(b_nfast),
                                         _ptr(C), M, N, K, code, float(alpha), int(upper_only), int(mirror), int(splits)))
+        return C
+
+    def gemm_ex(self, A, B, C, a_kfast=True, b_nfast=True, alpha=1.0, beta=0.0, row_scale=None, col_scale=None, upper_only=False,
+                mirror=0, splits=0, lda=None, ldb=None):
+        """alpha * row_scale[:, None] * col_scale[None, :] * op(A) op(B) + beta * C, returned in a copy of C: float64 or
+        float32, (M, ldc) with ldc >= N - the columns from N on come back as they went in (xmca_gemm_ex)."""
+        A, B, M, N, K, lda, ldb, code = self._gemm_shapes(A, B, a_kfast, b_nfast, lda, ldb)
+        C = np.array(C, order="C", copy=True)
+        if C.ndim != 2 or C.shape[0] != M or C.shape[1] < N:
+            raise ValueError("gemm_ex: C must be (M, ldc) with ldc >= N")
+        rs = None if row_scale is None else np.ascontiguousarray(row_scale, dtype=np.float64)
+        cs = None if col_scale is None else np.ascontiguousarray(col_scale, dtype=np.float64)
+        if (rs is not None and rs.shape != (M,)) or (cs is not None and cs.shape != (N,)):
+            raise ValueError("gemm_ex: row_scale has M and col_scale N elements")
+        self._check(self._lib.xmca_gemm_ex(self._h, _ptr(A), lda, int(a_kfast), _ptr(B), ldb, int(b_nfast), _ptr(C), C.shape[1],
+                                           _np_dtype_code(C.dtype), M, N, K, code, float(alpha), float(beta), _ptr(rs), _ptr(cs),
+                                           int(upper_only), int(mirror), int(splits)))
         return C
 
     def eigh(self, A, vectors=True):

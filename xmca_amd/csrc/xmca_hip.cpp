@@ -1989,6 +1989,43 @@ int xmca_gemm(xmca_handle* h, const void* A, int64_t lda, int a_kfast, const voi
   API_END(h)
 }
 
+int xmca_gemm_ex(xmca_handle* h, const void* A, int64_t lda, int a_kfast, const void* B, int64_t ldb, int b_nfast, void* C,
+                 int64_t ldc, int c_dtype, int M, int N, int K, int dtype, double alpha, double beta, const double* row_scale,
+                 const double* col_scale, int upper_only, int mirror, int splits) {
+  API_BEGIN(h)
+  XMCA_CHECK(A && B && C && M > 0 && N > 0 && K >= 0 && ldc >= N, XMCA_ERR_INVALID, "gemm_ex: bad arguments");
+  XMCA_CHECK(lda >= (a_kfast ? K : M) && ldb >= (b_nfast ? N : K), XMCA_ERR_INVALID, "gemm_ex: leading dimension below the extent");
+  const size_t na = (size_t)(a_kfast ? M : K) * lda, nb = (size_t)(b_nfast ? K : N) * ldb, nc = (size_t)M * ldc;
+  DevBuf<double> rs, cs;
+  GemmOpts o;
+  o.a_kfast = a_kfast != 0; o.b_nfast = b_nfast != 0; o.alpha = alpha; o.beta = beta; o.upper_only = upper_only != 0; o.mirror = mirror;
+  o.force_splits = splits;
+  if (row_scale) {
+    XMCA_HIP(hipMemcpyAsync(rs.ensure(M), row_scale, sizeof(double) * M, hipMemcpyHostToDevice, h->st));
+    o.row_scale = rs.get();
+  }
+  if (col_scale) {
+    XMCA_HIP(hipMemcpyAsync(cs.ensure(N), col_scale, sizeof(double) * N, hipMemcpyHostToDevice, h->st));
+    o.col_scale = cs.get();
+  }
+  with_dtype(dtype, [&](auto ti) {
+    using TI = decltype(ti);
+    with_dtype(c_dtype, [&](auto to) {
+      using TO = decltype(to);
+      DevBuf<TI> Ad, Bd;
+      DevBuf<TO> Cd;
+      XMCA_HIP(hipMemcpyAsync(Ad.ensure(na), A, na * sizeof(TI), hipMemcpyHostToDevice, h->st));
+      XMCA_HIP(hipMemcpyAsync(Bd.ensure(nb), B, nb * sizeof(TI), hipMemcpyHostToDevice, h->st));
+      // C goes up whatever beta is: the padding of its rows and, with beta = 0, what it held before must come back as they were / unread
+      XMCA_HIP(hipMemcpyAsync(Cd.ensure(nc), C, nc * sizeof(TO), hipMemcpyHostToDevice, h->st));
+      gemm<TI, TO>(h->st, h->gws, Ad.get(), lda, Bd.get(), ldb, Cd.get(), ldc, M, N, K, o);
+      XMCA_HIP(hipMemcpyAsync(C, Cd.get(), nc * sizeof(TO), hipMemcpyDeviceToHost, h->st));
+      XMCA_HIP(hipStreamSynchronize(h->st));
+    });
+  });
+  API_END(h)
+}
+
 int xmca_cholesky(xmca_handle* h, const double* A, int n, int is_complex, double rel_shift, double* R, int* ok) {
   API_BEGIN(h)
   XMCA_CHECK(A && R && ok && n >= 1, XMCA_ERR_INVALID, "cholesky: bad arguments");
