@@ -41,7 +41,7 @@ typedef struct xmca_handle xmca_handle;
 /* library / device management ------------------------------------------------------------------------- */
 const char* xmca_version(void);
 /* Number of this header's ABI (XMCA_ABI_VERSION): the binding refuses a library built from another revision. */
-#define XMCA_ABI_VERSION 14
+#define XMCA_ABI_VERSION 15
 int xmca_abi_version(void);
 int xmca_device_count(void);
 int xmca_create(int device, xmca_handle** out);
@@ -378,6 +378,20 @@ int xmca_eigh(xmca_handle* h, const double* A, int n, int is_complex, double* la
  * triangular, row-major, same element layout) with R^H R = A + rel_shift * max(diag A) * I; *ok = 0 when a pivot was
  * not positive.  (The device routine behind the values-only two-field solve; exported for the kernel tests.) */
 int xmca_cholesky(xmca_handle* h, const double* A, int n, int is_complex, double rel_shift, double* R, int* ok);
+/* The same factorisation on the trailing block A[first:, first:] of a host buffer of n rows of lda >= n elements (interleaved
+ * complex when is_complex), posed the way the one-sided solves pose it: base advanced by first * (lda + 1) elements, size
+ * n - first, leading dimension lda.  The buffer goes to the device as it is and comes back whole in R (n x lda), so the
+ * caller sees what was written outside the block.  (Kernel tests only.) */
+int xmca_cholesky_ex(xmca_handle* h, const double* A, int n, int64_t lda, int first, int is_complex, double rel_shift, double* R, int* ok);
+/* The batched DFT of csrc/fft.h with every argument of fft_batch, host in / host out (kernel tests only):
+ *   out[b*out_bs + k*out_es] = sa[k] sb[b] scale * sum_{t < n_in} x[b][t] exp(sign 2 pi i k t / n),  b < batch, k < n_keep,
+ * x[b][t] = in[b*in_bs + t*in_es], or sin[t] * conj(in[...]) with conj_in (sin alone scales without conjugating).  in_im, sin
+ * (n_in), sa (n_keep) and sb (batch) may be NULL.  in_re / in_im hold in_count elements, out_re / out_im out_count: the outputs
+ * go to the device before the launch and come back whole, so untouched elements return as they went in.  1 <= n_in, n_keep <= n;
+ * a request with an input or output index outside its buffer returns XMCA_ERR_INVALID before anything is launched. */
+int xmca_fft_ex(xmca_handle* h, const double* in_re, const double* in_im, int64_t in_count, int64_t in_bs, int64_t in_es, int n_in,
+                int conj_in, const double* sin, int batch, int n, int sign, double* out_re, double* out_im, int64_t out_count,
+                int64_t out_bs, int64_t out_es, int n_keep, const double* sa, const double* sb, double scale);
 /* Time `reps` Gram products G = X X^T of the resident field `side` with hipEvents on the library's stream;
  * avg_ms = mean duration of one product (all launches it needs), kernel_ms = mean duration of the MFMA
  * kernel launches alone, flops = useful flops of one product, T (T+1) N. */

@@ -1,5 +1,5 @@
 """CPU: the plumbing of `bootstrapping(axis=1)` that needs no device - the two column entry points in the header, the binding
-table and the built library (ABI 14), and the index composition `compose_bootstrap_indices` against `block_bootstrap(axis=1)`
+table and the built library (added at ABI 14; the number is 15 since the kernel-test entries), and the index composition `compose_bootstrap_indices` against `block_bootstrap(axis=1)`
 applied cumulatively the way the reference's loop applies it (xmca/array.py:1902-1928)."""
 import os
 import re
@@ -17,10 +17,10 @@ NEW = ("xmca_bootstrap_runs_columns", "xmca_bootstrap_runs_columns_extended")
 def test_column_entries_are_declared_bound_and_exported_at_abi_14():
     from xmca_amd import _hip
     header = open(os.path.join(REPO, "include", "xmca_hip.h")).read()
-    assert int(re.search(r"#define XMCA_ABI_VERSION (\d+)", header).group(1)) == 14
-    assert _hip.ABI_VERSION == 14
+    assert int(re.search(r"#define XMCA_ABI_VERSION (\d+)", header).group(1)) == 15
+    assert _hip.ABI_VERSION == 15
     lib = _hip.load_library()
-    assert lib.xmca_abi_version() == 14
+    assert lib.xmca_abi_version() == 15
     code = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
     for name, row in zip(NEW, ("xmca_bootstrap_runs", "xmca_bootstrap_runs_extended")):
         assert re.search(r"\bint %s\s*\(" % name, code), name

@@ -34,8 +34,8 @@ def test_maps_entry_point_is_declared_exported_and_bound():
 def test_abi_number_is_unchanged_by_the_added_entry_point():
     from xmca_amd import _hip
     d = re.search(r"#define\s+XMCA_ABI_VERSION\s+(\d+)", _header())
-    assert d and int(d.group(1)) == 14
-    assert _hip.ABI_VERSION == 14 and _hip.load_library().xmca_abi_version() == 14
+    assert d and int(d.group(1)) == 15
+    assert _hip.ABI_VERSION == 15 and _hip.load_library().xmca_abi_version() == 15
 
 
 class _StubDevice:

@@ -90,6 +90,9 @@ SIGNATURES = {
                               _c_dbl, _c_dbl, _vp, _vp, _c_int, _c_int, _c_int]),
     "xmca_eigh": (_c_int, [_vp, _vp, _c_int, _c_int, _vp, _vp, _vp]),
     "xmca_cholesky": (_c_int, [_vp, _vp, _c_int, _c_int, _c_dbl, _vp, ctypes.POINTER(_c_int)]),
+    "xmca_cholesky_ex": (_c_int, [_vp, _vp, _c_int, _c_i64, _c_int, _c_int, _c_dbl, _vp, ctypes.POINTER(_c_int)]),
+    "xmca_fft_ex": (_c_int, [_vp, _vp, _vp, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _vp, _c_int, _c_int, _c_int, _vp, _vp, _c_i64,
+                             _c_i64, _c_i64, _c_int, _vp, _vp, _c_dbl]),
     "xmca_bench_gram": (_c_int, [_vp, _c_int, _c_int, _dp, _dp, _dp]),
     "xmca_bench_gemm": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _dp]),
 }
@@ -104,7 +107,7 @@ def library_path():
 MAP_EOF, MAP_AMPLITUDE, MAP_PHASE = 0, 1, 2          # `kind` of xmca_get_maps
 SCALE_NONE, SCALE_MAX, SCALE_STD = 0, 1, 2           # ... and its `scaling`
 PVALUE_MAX_OBS = 1000000    # largest n_obs of xmca_pearson_pvalues / xmca_correlation_maps (csrc/kernels.h)
-ABI_VERSION = 14         # bumped whenever a signature of include/xmca_hip.h changes; checked against xmca_abi_version()
+ABI_VERSION = 15         # bumped whenever a signature of include/xmca_hip.h changes; checked against xmca_abi_version()
 
 
 def load_library():
@@ -775,6 +778,52 @@ class Handle:
         ok = _c_int(0)
         self._check(self._lib.xmca_cholesky(self._h, _ptr(Ad), n, int(cplx), float(rel_shift), _ptr(R), ctypes.byref(ok)))
         return R, bool(ok.value)
+
+    def cholesky_ex(self, A, first=0, lda=None, rel_shift=0.0):
+        """The factorisation of the trailing block A[first:n, first:n] inside a buffer of n rows of lda >= n elements, posed
+        as the one-sided solves pose it (xmca_cholesky_ex).  A: (n, n), padded here to (n, lda) with NaN, or (n, lda) as it
+        is.  Returns (the whole buffer as it comes back, ok): the block holds R, everything else what it held before."""
+        Ad, cplx = _host_vectors(A)
+        n = Ad.shape[0]
+        lda = Ad.shape[1] if lda is None else int(lda)
+        if Ad.ndim != 2 or lda < n or Ad.shape[1] not in (n, lda):
+            raise ValueError("cholesky_ex: A must be (n, n) or (n, lda) with lda >= n")
+        if Ad.shape[1] != lda:
+            buf = np.full((n, lda), np.nan, dtype=Ad.dtype)
+            buf[:, :n] = Ad
+            Ad = buf
+        R = np.empty_like(Ad)
+        ok = _c_int(0)
+        self._check(self._lib.xmca_cholesky_ex(self._h, _ptr(Ad), n, lda, int(first), int(cplx), float(rel_shift), _ptr(R),
+                                               ctypes.byref(ok)))
+        return R, bool(ok.value)
+
+    def fft_ex(self, in_re, in_im, batch, n, out_re, out_im, sign=-1, in_bs=None, in_es=1, n_in=None, conj_in=False, sin=None,
+               out_bs=None, out_es=1, n_keep=None, sa=None, sb=None, scale=1.0):
+        """fft_batch of csrc/fft.h with every argument (xmca_fft_ex): element (b, t) of the input at in_re[b*in_bs + t*in_es]
+        of the flattened buffers, element (b, k) of the output at out[b*out_bs + k*out_es]; out_re / out_im are the buffers as
+        they are before the call.  Returns copies of them (same shapes) with the n_keep outputs of every transform written."""
+        n_in = n if n_in is None else int(n_in)
+        n_keep = n if n_keep is None else int(n_keep)
+        in_bs = n_in if in_bs is None else int(in_bs)
+        out_bs = n_keep if out_bs is None else int(out_bs)
+        ir = np.ascontiguousarray(in_re, dtype=np.float64)
+        ii = None if in_im is None else np.ascontiguousarray(in_im, dtype=np.float64)
+        if ii is not None and ii.size != ir.size:
+            raise ValueError("fft_ex: in_re and in_im differ in size")
+        outr = np.array(out_re, dtype=np.float64, order="C", copy=True)
+        outi = np.array(out_im, dtype=np.float64, order="C", copy=True)
+        if outr.size != outi.size:
+            raise ValueError("fft_ex: out_re and out_im differ in size")
+        fs = None if sin is None else np.ascontiguousarray(sin, dtype=np.float64)
+        fa = None if sa is None else np.ascontiguousarray(sa, dtype=np.float64)
+        fb = None if sb is None else np.ascontiguousarray(sb, dtype=np.float64)
+        if ((fs is not None and fs.size != n_in) or (fa is not None and fa.size != n_keep) or (fb is not None and fb.size != batch)):
+            raise ValueError("fft_ex: sin has n_in, sa n_keep and sb batch elements")
+        self._check(self._lib.xmca_fft_ex(self._h, _ptr(ir), _ptr(ii), ir.size, in_bs, int(in_es), n_in, int(bool(conj_in)), _ptr(fs),
+                                          int(batch), int(n), int(sign), _ptr(outr), _ptr(outi), outr.size, out_bs, int(out_es),
+                                          n_keep, _ptr(fa), _ptr(fb), float(scale)))
+        return outr, outi
 
     def bench_gemm(self, M, N, K, dtype, a_kfast=True, b_nfast=True, upper_only=False, splits=0, reps=5):
         """ms per product C = op(A) op(B) on device-resident random operands."""

@@ -2051,6 +2051,72 @@ int xmca_cholesky(xmca_handle* h, const double* A, int n, int is_complex, double
   API_END(h)
 }
 
+int xmca_cholesky_ex(xmca_handle* h, const double* A, int n, int64_t lda, int first, int is_complex, double rel_shift, double* R, int* ok) {
+  API_BEGIN(h)
+  XMCA_CHECK(A && R && ok && n >= 1 && lda >= n && first >= 0 && first < n, XMCA_ERR_INVALID, "cholesky_ex: bad arguments");
+  const bool cplx = is_complex != 0;
+  const size_t cnt = (size_t)n * (size_t)lda, no = cnt * (cplx ? 2 : 1);
+  DevBuf<double> raw, rout;
+  CPlanes Ap;
+  Ap.ensure(cnt, cplx);
+  if (cplx) {
+    XMCA_HIP(hipMemcpyAsync(raw.ensure(2 * cnt), A, sizeof(double) * 2 * cnt, hipMemcpyHostToDevice, h->st));
+    hipLaunchKernelGGL((split_complex_kernel<double, double>), ew_grid((int64_t)cnt), dim3(EW_BLOCK), 0, h->st, raw.get(), Ap.r(),
+                       Ap.im.get(), (int64_t)cnt);
+  } else {
+    XMCA_HIP(hipMemcpyAsync(Ap.r(), A, sizeof(double) * cnt, hipMemcpyHostToDevice, h->st));
+  }
+  // the trailing block behind row / column `first`, the way factor_by_cholesky (solver.h) poses it: base + first * (lda + 1), ld = lda
+  const size_t off = (size_t)first * (size_t)(lda + 1);
+  *ok = cholesky_upper(h->st, h->gws, Ap.r() + off, cplx ? Ap.im.get() + off : nullptr, n - first, lda, rel_shift) ? 1 : 0;
+  hipLaunchKernelGGL((pack_rows_kernel<double>), ew_grid((int64_t)cnt), dim3(EW_BLOCK), 0, h->st, Ap.r(), Ap.i(cplx), lda, n, (int)lda,
+                     rout.ensure(no), 0);
+  XMCA_HIP(hipGetLastError());
+  XMCA_HIP(hipMemcpyAsync(R, rout.get(), sizeof(double) * no, hipMemcpyDeviceToHost, h->st));
+  XMCA_HIP(hipStreamSynchronize(h->st));
+  API_END(h)
+}
+
+int xmca_fft_ex(xmca_handle* h, const double* in_re, const double* in_im, int64_t in_count, int64_t in_bs, int64_t in_es, int n_in,
+                int conj_in, const double* sin_, int batch, int n, int sign, double* out_re, double* out_im, int64_t out_count,
+                int64_t out_bs, int64_t out_es, int n_keep, const double* sa, const double* sb, double scale) {
+  API_BEGIN(h)
+  XMCA_CHECK(in_re && out_re && out_im && batch >= 1 && n >= 2 && (sign == 1 || sign == -1) && in_count >= 1 && out_count >= 1,
+             XMCA_ERR_INVALID, "fft_ex: bad arguments");
+  XMCA_CHECK(n_in >= 1 && n_in <= n && n_keep >= 1 && n_keep <= n, XMCA_ERR_INVALID, "fft_ex: n_in and n_keep lie in [1, n]");
+  // an index b * bs + t * es is linear in (b, t): its extremes are at the corners of [0, batch) x [0, count)
+  auto inside = [&](int64_t bs, int64_t es, int len, int64_t count) {
+    const int64_t lim = (int64_t)1 << 30;      // (products with a 31-bit index stay inside int64)
+    if (bs <= -lim || bs >= lim || es <= -lim || es >= lim) return false;
+    for (int64_t b : {(int64_t)0, (int64_t)batch - 1})
+      for (int64_t t : {(int64_t)0, (int64_t)len - 1}) {
+        const int64_t i = b * bs + t * es;
+        if (i < 0 || i >= count) return false;
+      }
+    return true;
+  };
+  XMCA_CHECK(inside(in_bs, in_es, n_in, in_count), XMCA_ERR_INVALID, "fft_ex: an input index lies outside the input");
+  XMCA_CHECK(inside(out_bs, out_es, n_keep, out_count), XMCA_ERR_INVALID, "fft_ex: an output index lies outside the output");
+  FftPlan plan;
+  XMCA_CHECK(fft_plan(n, plan), XMCA_ERR_UNSUPPORTED, "fft_ex: length must factor into 2, 3, 5, 7 and be at most 5120");
+  const size_t ni = (size_t)in_count, nout = (size_t)out_count;
+  DevBuf<double> ir, ii, orr, oi, fs, fa, fb;
+  XMCA_HIP(hipMemcpyAsync(ir.ensure(ni), in_re, sizeof(double) * ni, hipMemcpyHostToDevice, h->st));
+  if (in_im) XMCA_HIP(hipMemcpyAsync(ii.ensure(ni), in_im, sizeof(double) * ni, hipMemcpyHostToDevice, h->st));
+  if (sin_) XMCA_HIP(hipMemcpyAsync(fs.ensure((size_t)n_in), sin_, sizeof(double) * n_in, hipMemcpyHostToDevice, h->st));
+  if (sa) XMCA_HIP(hipMemcpyAsync(fa.ensure((size_t)n_keep), sa, sizeof(double) * n_keep, hipMemcpyHostToDevice, h->st));
+  if (sb) XMCA_HIP(hipMemcpyAsync(fb.ensure((size_t)batch), sb, sizeof(double) * batch, hipMemcpyHostToDevice, h->st));
+  // the outputs go up first: what the kernel must not touch comes back as it went in
+  XMCA_HIP(hipMemcpyAsync(orr.ensure(nout), out_re, sizeof(double) * nout, hipMemcpyHostToDevice, h->st));
+  XMCA_HIP(hipMemcpyAsync(oi.ensure(nout), out_im, sizeof(double) * nout, hipMemcpyHostToDevice, h->st));
+  fft_batch(h->st, plan, batch, ir.get(), in_im ? ii.get() : nullptr, in_bs, in_es, (double)sign, orr.get(), oi.get(), out_bs, out_es, n_keep,
+            sa ? fa.get() : nullptr, sb ? fb.get() : nullptr, scale, n_in, conj_in != 0, sin_ ? fs.get() : nullptr);
+  XMCA_HIP(hipMemcpyAsync(out_re, orr.get(), sizeof(double) * nout, hipMemcpyDeviceToHost, h->st));
+  XMCA_HIP(hipMemcpyAsync(out_im, oi.get(), sizeof(double) * nout, hipMemcpyDeviceToHost, h->st));
+  XMCA_HIP(hipStreamSynchronize(h->st));
+  API_END(h)
+}
+
 int xmca_eigh(xmca_handle* h, const double* A, int n, int is_complex, double* lam, double* Zh, int* info) {
   API_BEGIN(h)
   XMCA_CHECK(A && n >= 1 && lam, XMCA_ERR_INVALID, "eigh: bad arguments");
