@@ -167,6 +167,26 @@ int xmca_predict(xmca_handle* h, int side, const void* X, int64_t T_new, int64_t
 int xmca_reconstruct(xmca_handle* h, int side, const double* B, int64_t T, int64_t m, int b_is_complex, const void* V, int v_is_complex,
                      const int64_t* keep_idx, int64_t N_keep, int64_t N_full, const double* mean, const double* std, double* out);
 
+/* xmca_predict with per-grid-point weights - the `data *= coslat weights` of xMCA._scale_X (xmca/xarray.py:97-108; an entry point
+ * added to ABI 15 - no existing signature changes): out = (((X[:, keep] - mean) / std * weight) V[:, :m]) W.
+ *   weight    N_keep float64 values, host memory, applied after `- mean`, `/ std`: the product is formed in double and rounded to
+ *             `dtype`, numpy's in-place `x *= w` for a float64 w bit for bit (a plain multiply for XMCA_F64).  NULL: xmca_predict,
+ *             to the bit
+ * Every other argument as in xmca_predict. */
+int xmca_predict_weighted(xmca_handle* h, int side, const void* X, int64_t T_new, int64_t N_full, int dtype, const int64_t* keep_idx,
+                          int64_t N_keep, const void* mean, const void* std, const void* V, int v_is_complex, const double* W, int64_t m,
+                          int64_t q, int w_is_complex, double* out, int* out_is_complex, const double* weight);
+
+/* xmca_reconstruct with the weights taken out again - the `field /= coslat weights` of xMCA._scale_X_inverse (xmca/xarray.py:110-126;
+ * an entry point added to ABI 15 - no existing signature changes): kept column keep_idx[c] = Re(B V[:, :m]^H)[:, c] / inv_weight[c],
+ * then `* std[c]` and `+ mean[c]` as in xmca_reconstruct.
+ *   inv_weight  N_keep float64 values, host memory.  The division is IEEE, never a multiplication by a reciprocal: a weight of 0
+ *               gives inf / NaN as numpy does.  NULL: xmca_reconstruct, to the bit
+ * Every other argument as in xmca_reconstruct. */
+int xmca_reconstruct_weighted(xmca_handle* h, int side, const double* B, int64_t T, int64_t m, int b_is_complex, const void* V,
+                              int v_is_complex, const int64_t* keep_idx, int64_t N_keep, int64_t N_full, const double* mean,
+                              const double* std, double* out, const double* inv_weight);
+
 /* Correlation maps of MCA.homogeneous_patterns / heterogeneous_patterns (xmca/array.py:1188-1261, the Pearson
  * correlation of tools/array.py:76-88): r[n][j] = corr(real part of field column n of `side`, Y[:, j]) on the resident
  * field - one tall GEMM X^T Y plus column moments instead of the reference's (N + m)^2 corrcoef matrix.

@@ -59,6 +59,9 @@ SIGNATURES = {
     "xmca_predict": (_c_int, [_vp, _c_int, _vp, _c_i64, _c_i64, _c_int, _vp, _c_i64, _vp, _vp, _vp, _c_int, _vp, _c_i64, _c_i64, _c_int,
                               _vp, ctypes.POINTER(_c_int)]),
     "xmca_reconstruct": (_c_int, [_vp, _c_int, _vp, _c_i64, _c_i64, _c_int, _vp, _c_int, _vp, _c_i64, _c_i64, _vp, _vp, _vp]),
+    "xmca_predict_weighted": (_c_int, [_vp, _c_int, _vp, _c_i64, _c_i64, _c_int, _vp, _c_i64, _vp, _vp, _vp, _c_int, _vp, _c_i64, _c_i64,
+                                       _c_int, _vp, ctypes.POINTER(_c_int), _vp]),
+    "xmca_reconstruct_weighted": (_c_int, [_vp, _c_int, _vp, _c_i64, _c_i64, _c_int, _vp, _c_int, _vp, _c_i64, _c_i64, _vp, _vp, _vp, _vp]),
     "xmca_is_complex": (_c_int, [_vp]),
     "xmca_vectors_are_f32": (_c_int, [_vp, _c_int]),
     "xmca_persistent_giveups": (ctypes.c_longlong, []),
@@ -194,6 +197,14 @@ def _host_vectors(V):
     V = np.asarray(V)
     cplx = np.iscomplexobj(V)
     return np.ascontiguousarray(V, dtype=np.complex128 if cplx else np.float64), cplx
+
+
+def _column_weights(what, w, N):
+    """Per-column weights of the weighted transforms as N contiguous float64 values (the device reads exactly N)."""
+    w = np.asarray(w)
+    if np.iscomplexobj(w) or w.shape != (N,):
+        raise ValueError("%s: the weights must be %d real values, one per kept column, got shape %s" % (what, N, w.shape))
+    return np.ascontiguousarray(w, dtype=np.float64)
 
 
 def _unpack(out, rows, cols, is_complex):
@@ -450,11 +461,12 @@ class Handle:
         self._check(self._lib.xmca_project(self._h, side, _ptr(Vd), N, m, int(cplx), _ptr(out), ctypes.byref(out_cplx)))
         return _unpack(out, T, m, out_cplx.value)
 
-    def predict(self, side, X, keep_idx, mean, std, V, W):
+    def predict(self, side, X, keep_idx, mean, std, V, W, weight=None):
         """((X[:, keep_idx] - mean) / std) V W (T' x q, float64 / complex128) on the device (xmca_predict): MCA.predict's product
         without the vectors leaving the device.  X: T' x N_full real new data (its dtype is the ingest's: mean / std are cast to
         it); keep_idx: kept columns or None; std None: no division; V: N' x m host vectors or None (the first m resident ones of
-        the last solve of `side`); W: m x q mix.  The resident fields and vectors stay as they are."""
+        the last solve of `side`); W: m x q mix.  weight: N' float64 factors applied after the division, numpy's in-place
+        `x *= weight` (xmca_predict_weighted), or None.  The resident fields and vectors stay as they are."""
         X = np.ascontiguousarray(X)
         code = _np_dtype_code(X.dtype)
         if np.iscomplexobj(X) or X.ndim != 2:
@@ -471,14 +483,20 @@ class Handle:
             raise ValueError("predict: V must be N' x m = %d x %d, got %s" % (N, m, Vd.shape))
         out = np.empty((T, q), dtype=np.complex128)
         out_cplx = _c_int(0)
-        self._check(self._lib.xmca_predict(self._h, side, _ptr(X), T, N_full, code, _ptr(idx), N, _ptr(mean), _ptr(std), _ptr(Vd),
-                                           int(v_cplx), _ptr(Wd), m, q, int(w_cplx), _ptr(out), ctypes.byref(out_cplx)))
+        args = (self._h, side, _ptr(X), T, N_full, code, _ptr(idx), N, _ptr(mean), _ptr(std), _ptr(Vd), int(v_cplx), _ptr(Wd), m, q,
+                int(w_cplx), _ptr(out), ctypes.byref(out_cplx))
+        if weight is None:
+            self._check(self._lib.xmca_predict(*args))
+        else:
+            weight = _column_weights("predict", weight, N)
+            self._check(self._lib.xmca_predict_weighted(*args, _ptr(weight)))
         return _unpack(out, T, q, out_cplx.value)
 
-    def reconstruct(self, side, B, V, N, keep_idx=None, N_full=None, mean=None, std=None):
+    def reconstruct(self, side, B, V, N, keep_idx=None, N_full=None, mean=None, std=None, inv_weight=None):
         """Re(B V^H) (* std + mean) on the device (xmca_reconstruct), T x N_full float64 with NaN at the columns not in keep_idx.
-        B: T x m coefficients; V: N x m host vectors or None (the first m resident ones of the last solve of `side`).  The
-        resident fields and vectors stay as they are."""
+        B: T x m coefficients; V: N x m host vectors or None (the first m resident ones of the last solve of `side`).
+        inv_weight: N float64 factors the product is divided by first, numpy's `x /= inv_weight` (xmca_reconstruct_weighted), or
+        None.  The resident fields and vectors stay as they are."""
         Bd, b_cplx = _host_vectors(B)
         T, m = Bd.shape
         Vd, v_cplx = _host_vectors(V)
@@ -489,8 +507,13 @@ class Handle:
         mean = None if mean is None else np.ascontiguousarray(np.broadcast_to(mean, (N,)), dtype=np.float64)
         std = None if std is None else np.ascontiguousarray(np.broadcast_to(std, (N,)), dtype=np.float64)
         out = np.empty((T, N_full), dtype=np.float64)
-        self._check(self._lib.xmca_reconstruct(self._h, side, _ptr(Bd) if m else None, T, m, int(b_cplx), _ptr(Vd), int(v_cplx), _ptr(idx),
-                                               N, N_full, _ptr(mean), _ptr(std), _ptr(out)))
+        args = (self._h, side, _ptr(Bd) if m else None, T, m, int(b_cplx), _ptr(Vd), int(v_cplx), _ptr(idx), N, N_full, _ptr(mean),
+                _ptr(std), _ptr(out))
+        if inv_weight is None:
+            self._check(self._lib.xmca_reconstruct(*args))
+        else:
+            inv_weight = _column_weights("reconstruct", inv_weight, N)
+            self._check(self._lib.xmca_reconstruct_weighted(*args, _ptr(inv_weight)))
         return out
 
     def center_field(self, side, N):

@@ -926,7 +926,7 @@ class MCA:
         try:
             R = self._rotation_matrix
         except AttributeError:
-            R = np.eye(len(self.singular_values()))
+            R = np.eye(len(self._get_svals()))         # (not the public getter: the facade's returns a DataArray)
         if inverse_transpose and self._analysis['power'] > 1:
             R = np.linalg.pinv(R).conjugate().T
         return R
@@ -937,7 +937,7 @@ class MCA:
             idx = self._var_idx
             return self._correlation_matrix[idx, :][:, idx]
         except AttributeError:
-            return np.eye(len(self.singular_values()))
+            return np.eye(len(self._get_svals()))
 
     # ------------------------------------------------------------------------------------------
     # public getters (array.py:898-1297)
@@ -1043,17 +1043,26 @@ class MCA:
     def _transform_vectors(self, k):
         """(handle, vectors) for the device transforms of field k (xmca_predict / xmca_reconstruct): vectors None while they are
         still resident from this model's solve, the host array once they were fetched (or truncated).  None - the host path - for
-        a model that was not solved by this package (`load_analysis`, injected vectors), a subclass with its own scaling and under
-        `_transform_on_host`."""
+        a model that was not solved by this package (`load_analysis`, injected vectors), a subclass with its own scaling that does
+        not state it through `_device_column_weights`, and under `_transform_on_host`."""
         V = getattr(self, '_V', None)
         if getattr(self, '_transform_on_host', False) or not isinstance(V, _LazyVectors):
             return None
-        if type(self)._scale_X is not MCA._scale_X or type(self)._scale_X_inverse is not MCA._scale_X_inverse:
-            return None                   # a subclass scales differently (the xarray facade's coslat weights): its own host path
+        cls = type(self)
+        if ((cls._scale_X is not MCA._scale_X or cls._scale_X_inverse is not MCA._scale_X_inverse)
+                and cls._device_column_weights is MCA._device_column_weights):
+            return None                   # a subclass scales differently and does not say how: its own host path
         dev = self._device()
         if k in V._pending:
             return (dev, None) if dev.holds_result_of(self) else None
         return dev, V[k]
+
+    def _device_column_weights(self, k):
+        """What a subclass's `_scale_X` / `_scale_X_inverse` do beyond `- mean`, `/ std` to field k, for the device transforms:
+        `(forward, inverse)`, two (N',) float64 arrays - `_scale_X` multiplies by `forward` last, `_scale_X_inverse` divides by
+        `inverse` first - or None (nothing, the array class).  A subclass that overrides the scaling methods without overriding
+        this hook keeps the host route (`_transform_vectors`)."""
+        return None
 
     def _reconstruct_on_device(self, mode, original_scale, full):
         """`(pcs(mode, 'eigen') @ V_rot^H).real`, scaled back and (full) with the masked points re-inserted as NaN, as one product
@@ -1084,14 +1093,16 @@ class MCA:
             B = _reconstruct_coefficients(P[k], A) if A.shape[1] else np.zeros((T, 0))
             dtype = _real_dtype(np.result_type(P[k].dtype, vdt))            # the reference's (U @ V^H).real
             n_keep = self._fields_store[k].shape[1]
-            mean = std = None
+            mean = std = inv_weight = None
             if original_scale:
                 mean = self._field_means[k]
                 std = self._field_stds[k] if self._analysis['is_normalized'] else None
+                weights = self._device_column_weights(k)
+                inv_weight = None if weights is None else weights[1]
             mask = self._no_nan_index[k]
             keep_idx = np.flatnonzero(mask) if (full and n_keep != mask.size) else None
             X = dev.reconstruct(side, B, None if Vh is None else Vh[:, :B.shape[1]], n_keep, keep_idx=keep_idx,
-                                N_full=mask.size if keep_idx is not None else n_keep, mean=mean, std=std)
+                                N_full=mask.size if keep_idx is not None else n_keep, mean=mean, std=std, inv_weight=inv_weight)
             out[k] = X if full else X.astype(dtype, copy=False)
         return out
 
@@ -1184,7 +1195,8 @@ class MCA:
     def _predict_on_device(self, k, x, svals, R_inv_t, n_rot, n):
         """`(x[:, kept] - mean) / std @ V[:, :n_rot] / sqrt(s) @ R^-H`, columns ordered and selected, for the raw T' x N new data x
         of field k: one ingest + product on the device (xmca_predict) with the m x q mix of `_predict_mix`.  As `_scale_X` is called
-        with this field alone, it is divided by std whenever the model is normalized."""
+        with this field alone, it is divided by std whenever the model is normalized; a subclass's column weights
+        (`_device_column_weights`) come last."""
         W = _predict_mix(svals, R_inv_t, self._var_idx, n_rot, n)
         if W.shape[1] == 0:
             return np.zeros((x.shape[0], 0), dtype=np.result_type(W.dtype, self._resident_dtype()))
@@ -1193,7 +1205,9 @@ class MCA:
         keep_idx = None if mask.all() else np.flatnonzero(mask)
         std = self._field_stds[k] if self._analysis['is_normalized'] else None
         side = self._keys.index(k)
-        return dev.predict(side, x, keep_idx, self._field_means[k], std, None if Vh is None else Vh[:, :W.shape[0]], W)
+        weights = self._device_column_weights(k)
+        return dev.predict(side, x, keep_idx, self._field_means[k], std, None if Vh is None else Vh[:, :W.shape[0]], W,
+                           weight=None if weights is None else weights[0])
 
     # ------------------------------------------------------------------------------------------
     # significance (array.py:1716-1952)

@@ -475,10 +475,13 @@ __global__ void scale_columns_kernel(T* __restrict__ x, int rows, int64_t cols, 
 // New data of MCA.predict (xmca_predict): out[t][c] = (raw[t][idx[c]] - mean[c]) / std[c] for a rows x n_full row-major block, in
 // the element type TI of the data - numpy's `x -= mean; x /= std` bit for bit (a subtraction, then a correctly rounded division:
 // nothing to contract) - stored as the product's element type TP.  idx == nullptr: all columns (the contiguous case);
-// std == nullptr: no division.  Rows over blockIdx.y, columns over x: no index division per element.
+// std == nullptr: no division.  weight (float64, one per kept column) != nullptr: the value is then multiplied by weight[c] in
+// double and rounded back to TI - numpy's in-place `x *= w` for a float64 w (a plain multiply for TI = double); the vector is
+// re-read per row and stays in L2.  Rows over blockIdx.y, columns over x: no index division per element.
 template <typename TI, typename TP>
 __global__ void ingest_columns_kernel(const TI* __restrict__ raw, int64_t n_full, const int64_t* __restrict__ idx, int rows,
-                                      int64_t cols, const TI* __restrict__ mean, const TI* __restrict__ stdv, TP* __restrict__ out) {
+                                      int64_t cols, const TI* __restrict__ mean, const TI* __restrict__ stdv,
+                                      const double* __restrict__ weight, TP* __restrict__ out) {
   for (int t = blockIdx.y; t < rows; t += gridDim.y) {
     const TI* src = raw + (int64_t)t * n_full;
     TP* dst = out + (int64_t)t * cols;
@@ -486,6 +489,7 @@ __global__ void ingest_columns_kernel(const TI* __restrict__ raw, int64_t n_full
       TI v = src[idx ? idx[c] : c];
       v = v - mean[c];
       if (stdv) v = v / stdv[c];
+      if (weight) v = (TI)((double)v * weight[c]);
       dst[c] = (TP)v;
     }
   }
@@ -494,9 +498,10 @@ __global__ void ingest_columns_kernel(const TI* __restrict__ raw, int64_t n_full
 // Reconstruction epilogue (xmca_reconstruct): one pass from the compact rows x n_keep product C to the final rows x n_full
 // float64 layout.  Column j of the output is column col_of[j] of C (col_of == nullptr: j itself), or NaN where col_of[j] < 0;
 // kept values become C * std + mean like numpy's `x *= std; x += mean` (two roundings: not contracted), either factor optional.
+// inv_weight != nullptr: C / inv_weight[c] first, numpy's `x /= w` (an IEEE division, never a reciprocal multiply).
 __global__ void reconstruct_epilogue_kernel(const double* __restrict__ C, int64_t n_keep, const int64_t* __restrict__ col_of, int rows,
-                                            int64_t n_full, const double* __restrict__ stdv, const double* __restrict__ mean,
-                                            double* __restrict__ out) {
+                                            int64_t n_full, const double* __restrict__ inv_weight, const double* __restrict__ stdv,
+                                            const double* __restrict__ mean, double* __restrict__ out) {
 #pragma clang fp contract(off)
   for (int t = blockIdx.y; t < rows; t += gridDim.y) {
     const double* src = C + (int64_t)t * n_keep;
@@ -508,6 +513,7 @@ __global__ void reconstruct_epilogue_kernel(const double* __restrict__ C, int64_
         continue;
       }
       double v = src[c];
+      if (inv_weight) v = v / inv_weight[c];
       if (stdv) v = v * stdv[c];
       if (mean) v = v + mean[c];
       dst[j] = v;

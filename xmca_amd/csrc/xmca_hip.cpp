@@ -610,21 +610,23 @@ void vec_operand(xmca_handle* h, int side, const void* V, int64_t N, int64_t m, 
   op.i = op.host.i;
 }
 
-// out (T_new x q) = (((X[:, keep] - mean) / std) V[:, :m]) W   (see xmca_predict).  TI: element type of the data (ingest
-// arithmetic), TP: element type of the vectors (product).
+// out (T_new x q) = (((X[:, keep] - mean) / std * weight) V[:, :m]) W   (see xmca_predict, xmca_predict_weighted).  TI: element type
+// of the data (ingest arithmetic), TP: element type of the vectors (product).
 template <typename TI, typename TP>
 void predict_impl(xmca_handle* h, int side, const TI* X, int64_t T, int64_t N_full, const int64_t* keep_idx, int64_t N, const TI* mean,
-                  const TI* stdv, const void* V, bool v_cplx, const double* W, int64_t m, int64_t q, bool w_cplx, double* out,
-                  int* out_cplx) {
+                  const TI* stdv, const double* weight, const void* V, bool v_cplx, const double* W, int64_t m, int64_t q, bool w_cplx,
+                  double* out, int* out_cplx) {
   VecOperand<TP> vo;
   vec_operand<TP>(h, side, V, N, m, v_cplx, vo);
   const bool vc = vo.i != nullptr, oc = vc || w_cplx;
   DevBuf<int64_t> idx;
   DevBuf<TI> mu, sd;
+  DevBuf<double> wt;
   HostPlanes<double> w;
   if (keep_idx) XMCA_HIP(hipMemcpyAsync(idx.ensure((size_t)N), keep_idx, sizeof(int64_t) * N, hipMemcpyHostToDevice, h->st));
   XMCA_HIP(hipMemcpyAsync(mu.ensure((size_t)N), mean, sizeof(TI) * N, hipMemcpyHostToDevice, h->st));
   if (stdv) XMCA_HIP(hipMemcpyAsync(sd.ensure((size_t)N), stdv, sizeof(TI) * N, hipMemcpyHostToDevice, h->st));
+  if (weight) XMCA_HIP(hipMemcpyAsync(wt.ensure((size_t)N), weight, sizeof(double) * N, hipMemcpyHostToDevice, h->st));
   upload_planes<double>(h, W, (size_t)m * q, w_cplx, w, false);
   const double* Wr = w.r;
   const double* Wi = w.i;
@@ -643,7 +645,8 @@ void predict_impl(xmca_handle* h, int side, const TI* X, int64_t T, int64_t N_fu
     XMCA_HIP(hipMemcpyAsync(raw.get(), X + t0 * N_full, sizeof(TI) * tb * N_full, hipMemcpyHostToDevice, h->st));
     h->tm.begin("predict_ingest");
     hipLaunchKernelGGL((ingest_columns_kernel<TI, TP>), row_col_grid(tb, N), dim3(EW_BLOCK), 0, h->st, raw.get(), N_full,
-                       keep_idx ? idx.get() : nullptr, tb, N, mu.get(), stdv ? sd.get() : nullptr, xs.get());
+                       keep_idx ? idx.get() : nullptr, tb, N, mu.get(), stdv ? sd.get() : nullptr, weight ? wt.get() : nullptr,
+                       xs.get());
     XMCA_HIP(hipGetLastError());
     h->tm.end();
     h->tm.begin("predict_gemm");
@@ -679,16 +682,17 @@ void predict_impl(xmca_handle* h, int side, const TI* X, int64_t T, int64_t N_fu
   *out_cplx = oc ? 1 : 0;
 }
 
-// out (T x N_full, float64) = Re(B V[:, :m]^H) * std + mean, NaN at the masked columns  (see xmca_reconstruct).  TP: element type of
-// the vectors (product).
+// out (T x N_full, float64) = Re(B V[:, :m]^H) / inv_weight * std + mean, NaN at the masked columns  (see xmca_reconstruct,
+// xmca_reconstruct_weighted).  TP: element type of the vectors (product).
 template <typename TP>
 void reconstruct_impl(xmca_handle* h, int side, const double* B, int64_t T, int64_t m, bool b_cplx, const void* V, bool v_cplx,
-                      const int64_t* keep_idx, int64_t N, int64_t N_full, const double* mean, const double* stdv, double* out) {
+                      const int64_t* keep_idx, int64_t N, int64_t N_full, const double* mean, const double* stdv,
+                      const double* inv_weight, double* out) {
   VecOperand<TP> vo;
   if (m > 0) vec_operand<TP>(h, side, V, N, m, v_cplx, vo);
   const bool both_cplx = b_cplx && vo.i != nullptr;        // Re((Br + i Bi)(Vr - i Vi)^T) = Br Vr^T + Bi Vi^T
   DevBuf<int64_t> col_of;
-  DevBuf<double> mu, sd;
+  DevBuf<double> mu, sd, iw;
   if (keep_idx) {
     std::vector<int64_t> inv((size_t)N_full, -1);
     for (int64_t c = 0; c < N; ++c) inv[(size_t)keep_idx[c]] = c;
@@ -697,6 +701,7 @@ void reconstruct_impl(xmca_handle* h, int side, const double* B, int64_t T, int6
   }
   if (mean) XMCA_HIP(hipMemcpyAsync(mu.ensure((size_t)N), mean, sizeof(double) * N, hipMemcpyHostToDevice, h->st));
   if (stdv) XMCA_HIP(hipMemcpyAsync(sd.ensure((size_t)N), stdv, sizeof(double) * N, hipMemcpyHostToDevice, h->st));
+  if (inv_weight) XMCA_HIP(hipMemcpyAsync(iw.ensure((size_t)N), inv_weight, sizeof(double) * N, hipMemcpyHostToDevice, h->st));
   HostPlanes<TP> bp;             // B in the product's element type
   if (m > 0) upload_planes<TP>(h, B, (size_t)T * m, b_cplx, bp);
   const int64_t rows = transform_rows(T, (N + N_full) * (int64_t)sizeof(double));
@@ -721,7 +726,8 @@ void reconstruct_impl(xmca_handle* h, int side, const double* B, int64_t T, int6
     h->tm.end();
     h->tm.begin("reconstruct_epilogue");
     hipLaunchKernelGGL(reconstruct_epilogue_kernel, row_col_grid(tb, N_full), dim3(EW_BLOCK), 0, h->st, C.get(), N,
-                       keep_idx ? col_of.get() : nullptr, tb, N_full, stdv ? sd.get() : nullptr, mean ? mu.get() : nullptr, full.get());
+                       keep_idx ? col_of.get() : nullptr, tb, N_full, inv_weight ? iw.get() : nullptr, stdv ? sd.get() : nullptr,
+                       mean ? mu.get() : nullptr, full.get());
     XMCA_HIP(hipGetLastError());
     h->tm.end();
     XMCA_HIP(hipMemcpyAsync(out + t0 * N_full, full.get(), sizeof(double) * tb * N_full, hipMemcpyDeviceToHost, h->st));
@@ -1463,6 +1469,13 @@ int xmca_project(xmca_handle* h, int side, const void* V, int64_t N, int64_t m, 
 int xmca_predict(xmca_handle* h, int side, const void* X, int64_t T_new, int64_t N_full, int dtype, const int64_t* keep_idx,
                  int64_t N_keep, const void* mean, const void* std, const void* V, int v_is_complex, const double* W, int64_t m,
                  int64_t q, int w_is_complex, double* out, int* out_is_complex) {
+  return xmca_predict_weighted(h, side, X, T_new, N_full, dtype, keep_idx, N_keep, mean, std, V, v_is_complex, W, m, q, w_is_complex, out,
+                               out_is_complex, nullptr);
+}
+
+int xmca_predict_weighted(xmca_handle* h, int side, const void* X, int64_t T_new, int64_t N_full, int dtype, const int64_t* keep_idx,
+                          int64_t N_keep, const void* mean, const void* std, const void* V, int v_is_complex, const double* W, int64_t m,
+                          int64_t q, int w_is_complex, double* out, int* out_is_complex, const double* weight) {
   API_BEGIN(h)
   check_transform(h, "predict", side, V, m, keep_idx, N_keep, N_full);
   XMCA_CHECK(X && mean && W && out && out_is_complex && T_new >= 1 && m >= 1 && q >= 1 && q <= INT32_MAX, XMCA_ERR_INVALID,
@@ -1475,7 +1488,7 @@ int xmca_predict(xmca_handle* h, int side, const void* X, int64_t T_new, int64_t
     using TI = decltype(ti);
     with_dtype(vt32 ? XMCA_F32 : XMCA_F64, [&](auto tp) {
       predict_impl<TI, decltype(tp)>(h, side, static_cast<const TI*>(X), T_new, N_full, keep_idx, N_keep, static_cast<const TI*>(mean),
-                                     static_cast<const TI*>(std), V, vc, W, m, q, wc, out, out_is_complex);
+                                     static_cast<const TI*>(std), weight, V, vc, W, m, q, wc, out, out_is_complex);
     });
   });
   API_END(h)
@@ -1483,12 +1496,19 @@ int xmca_predict(xmca_handle* h, int side, const void* X, int64_t T_new, int64_t
 
 int xmca_reconstruct(xmca_handle* h, int side, const double* B, int64_t T, int64_t m, int b_is_complex, const void* V, int v_is_complex,
                      const int64_t* keep_idx, int64_t N_keep, int64_t N_full, const double* mean, const double* std, double* out) {
+  return xmca_reconstruct_weighted(h, side, B, T, m, b_is_complex, V, v_is_complex, keep_idx, N_keep, N_full, mean, std, out, nullptr);
+}
+
+int xmca_reconstruct_weighted(xmca_handle* h, int side, const double* B, int64_t T, int64_t m, int b_is_complex, const void* V,
+                              int v_is_complex, const int64_t* keep_idx, int64_t N_keep, int64_t N_full, const double* mean,
+                              const double* std, double* out, const double* inv_weight) {
   API_BEGIN(h)
   check_transform(h, "reconstruct", side, V, m, keep_idx, N_keep, N_full);
   XMCA_CHECK(out && T >= 1 && (B || m == 0), XMCA_ERR_INVALID, "reconstruct: need a T x m coefficient matrix and an output");
   // the product runs in the element type of the resident vectors it reads (float64 for host vectors)
   with_dtype(m > 0 && !V && h->res.vt_f32[side] ? XMCA_F32 : XMCA_F64, [&](auto tp) {
-    reconstruct_impl<decltype(tp)>(h, side, B, T, m, b_is_complex != 0, V, v_is_complex != 0, keep_idx, N_keep, N_full, mean, std, out);
+    reconstruct_impl<decltype(tp)>(h, side, B, T, m, b_is_complex != 0, V, v_is_complex != 0, keep_idx, N_keep, N_full, mean, std, inv_weight,
+                                   out);
   });
   API_END(h)
 }

@@ -64,8 +64,56 @@ class xMCA(MCA):
             field += self._field_means[k]
         return data_dict
 
+    def _device_column_weights(self, k):
+        """The coslat weights of `_scale_X` / `_scale_X_inverse` for the device transforms (see `MCA._device_column_weights`).
+        Weights given through `apply_weights` are, as in the reference, part of neither."""
+        if not self._analysis['is_coslat_corrected']:
+            return None
+        w = self._coslat_weights(k)
+        return w, w
+
+    def _column_factor(self, k, weight):
+        """The factor a time-independent `weight` puts on every kept grid point of field k: `(ones * weight)` over one time step of
+        the field's dims / coords - xarray's own `*`, so the broadcasting is the library's - flattened, at the kept points.  None
+        when the weight has the field's time dimension, when the product is not of the field's spatial shape (a foreign dimension,
+        a mismatch) or for an unknown key: the host route then computes, or raises, as the reference does."""
+        xr = _xr()
+        if k not in self._field_dims or k not in self._fields_store:
+            return None
+        dims = self._field_dims[k]
+        time_dim = dims[0]
+        if time_dim in getattr(weight, 'dims', ()):
+            return None
+        coords = self._field_coords[k]
+        one_step = {d: (np.asarray(getattr(coords[d], 'values', coords[d]))[:1] if d == time_dim else coords[d])
+                    for d in dims if d in coords}
+        shape = (1,) + tuple(self._fields_spatial_shape[k])
+        ones = xr.DataArray(np.ones(shape, dtype=self._fields_store[k].dtype), dims=dims, coords=one_step)
+        try:
+            product = np.asarray((ones * weight).data)
+        except Exception:
+            return None
+        if product.shape != shape:
+            return None
+        return product.reshape(-1)[self._no_nan_index[k]]
+
+    def _apply_weights_on_device(self, weights):
+        """Time-independent weights on a field that is still resident on the device: one multiply per element there, the host's own
+        operation to the bit (`MCA._scale_on_device`, which refuses what it cannot do that way).  False: nothing was changed."""
+        if not self._store_is_raw:
+            return False
+        factors = {k: 1 for k in self._keys}
+        for k, weight in weights.items():
+            factor = self._column_factor(k, weight)
+            if factor is None or factor.dtype != self._fields_store[k].dtype:
+                return False
+            factors[k] = factor
+        return self._scale_on_device(factors, divide=False)
+
     def apply_weights(self, **weights):
         """Weights as DataArrays broadcastable against the fields (keys `left` / `right`)."""
+        if self._apply_weights_on_device(weights):
+            return
         fields = self.fields()
         store = self._fields
         for k, weight in weights.items():
