@@ -56,6 +56,24 @@ const char* xmca_last_error(xmca_handle* h);
  *             (they must stay valid until the next xmca_set_field / xmca_destroy). */
 int xmca_set_field(xmca_handle* h, int side, const void* re, const void* im, int64_t T, int64_t N, int dtype, int location);
 
+/* xmca_set_field for a real field that already lives on the handle's GPU, in any two-stride layout (an entry point added to ABI 15 -
+ * no existing signature changes): element (t, n) of the T x N field is re[t * stride_t + n * stride_n], strides in elements, not
+ * negative.  The field is COPIED into the library's own buffer as a contiguous row-major T x N array, so xmca_compact_field,
+ * xmca_center_field, xmca_scale_field and the solve work as after a host upload; the caller's memory is never written and is not
+ * referenced after the call returns (the handle's stream is synchronised).  Checks and state changes are those of xmca_set_field.
+ * The copy kernel is chosen from the strides (xmca_ingest_regime): XMCA_INGEST_ROWS for stride_n == 1 - contiguous rows stride_t
+ * apart, moved 16 bytes per lane where source and destination row are both 16-byte aligned, element by element otherwise (a column
+ * slice of a wider array);  XMCA_INGEST_TRANSPOSE for stride_t == 1 - time is the fast axis, as in a (space, time) array handed
+ * over transposed: 64 x 64 tiles through LDS, both sides coalesced;  XMCA_INGEST_GATHER for anything else (steps along both
+ * axes).  A dimension of one element counts as contiguous.  The caller orders its own work on `re` before the call. */
+#define XMCA_INGEST_ROWS 0
+#define XMCA_INGEST_TRANSPOSE 1
+#define XMCA_INGEST_GATHER 2
+int xmca_set_field_strided(xmca_handle* h, int side, const void* re, int64_t T, int64_t N, int64_t stride_t, int64_t stride_n, int dtype);
+/* The regime xmca_set_field_strided takes for a T x N view (no handle, no device); XMCA_ERR_INVALID for a negative stride or an
+ * empty view. */
+int xmca_ingest_regime(int64_t T, int64_t N, int64_t stride_t, int64_t stride_n);
+
 /* Hilbert complexify on the device: X_im = Ht * X_re for every field set so far.  Ht (T x T) is the imaginary
  * part of the analytic-signal operator, imag(scipy.signal.hilbert(eye(T), axis=0)); it is circulant, so the
  * caller passes only its first column `hilbert_col` (T float64, host): Ht[t][s] = hilbert_col[(t - s) mod T].
@@ -130,6 +148,15 @@ int xmca_get_maps(xmca_handle* h, int side, const double* W, int64_t m, int64_t 
                   int factor_is_complex, const int64_t* keep_idx, int64_t N_full, int kind, int scaling, void* out, int dtype,
                   double* stat_out);
 
+/* xmca_get_maps with the memory space of `out` as an argument (an entry point added to ABI 15 - no existing signature changes).
+ *   out_location  XMCA_HOST: xmca_get_maps, to the bit.  XMCA_DEVICE: `out` is memory of the handle's GPU holding N_full x q
+ *                 values of `dtype` (interleaved complex as above - torch's complex layout); the finishing kernel writes it
+ *                 directly, nothing crosses to the host.  stat_out stays host memory.
+ * The handle's stream is synchronised before the call returns; the caller orders its own work on `out` before the call. */
+int xmca_get_maps_to(xmca_handle* h, int side, const double* W, int64_t m, int64_t q, int w_is_complex, const double* col_factor,
+                     int factor_is_complex, const int64_t* keep_idx, int64_t N_full, int kind, int scaling, void* out, int dtype,
+                     double* stat_out, int out_location);
+
 /* PC projection of MCA._get_U (xmca/array.py:648-674, the product `fields[k] @ V[k]`): U = X~ V with X~ the field of
  * `side` as solve() saw it - still resident on the device; the analytic signal X + i Ht X when complexify was
  * requested (the imaginary field plane is not needed: U = W + i Ht W with W = X V); X + i G X after
@@ -187,6 +214,26 @@ int xmca_reconstruct_weighted(xmca_handle* h, int side, const double* B, int64_t
                               int v_is_complex, const int64_t* keep_idx, int64_t N_keep, int64_t N_full, const double* mean,
                               const double* std, double* out, const double* inv_weight);
 
+/* xmca_predict_weighted for new data in either memory space (an entry point added to ABI 15 - no existing signature changes).
+ *   x_location  XMCA_HOST: X is contiguous host memory (stride_t = N_full, stride_n = 1): xmca_predict_weighted, to the bit.
+ *               XMCA_DEVICE: X is memory of the handle's GPU, element (t, n) at X[t * stride_t + n * stride_n] (strides in
+ *               elements, not negative).  It is not staged: with stride_n == 1 the ingest reads the rows in place with their
+ *               pitch, any other view is made contiguous block by block with the kernels of xmca_set_field_strided.  X is
+ *               never written.
+ * `out` stays host memory (T_new x q).  Every other argument as in xmca_predict_weighted. */
+int xmca_predict_strided(xmca_handle* h, int side, const void* X, int64_t T_new, int64_t N_full, int64_t stride_t, int64_t stride_n,
+                         int x_location, int dtype, const int64_t* keep_idx, int64_t N_keep, const void* mean, const void* std,
+                         const void* V, int v_is_complex, const double* W, int64_t m, int64_t q, int w_is_complex, double* out,
+                         int* out_is_complex, const double* weight);
+
+/* xmca_reconstruct_weighted with the memory space of `out` as an argument (an entry point added to ABI 15 - no existing signature
+ * changes).  out_location XMCA_HOST: xmca_reconstruct_weighted, to the bit.  XMCA_DEVICE: `out` is memory of the handle's GPU
+ * (T x N_full float64); the epilogue of every row block writes its rows of `out` directly.  The handle's stream is synchronised
+ * before the call returns. */
+int xmca_reconstruct_to(xmca_handle* h, int side, const double* B, int64_t T, int64_t m, int b_is_complex, const void* V,
+                        int v_is_complex, const int64_t* keep_idx, int64_t N_keep, int64_t N_full, const double* mean,
+                        const double* std, double* out, const double* inv_weight, int out_location);
+
 /* Correlation maps of MCA.homogeneous_patterns / heterogeneous_patterns (xmca/array.py:1188-1261, the Pearson
  * correlation of tools/array.py:76-88): r[n][j] = corr(real part of field column n of `side`, Y[:, j]) on the resident
  * field - one tall GEMM X^T Y plus column moments instead of the reference's (N + m)^2 corrcoef matrix.
@@ -220,6 +267,13 @@ int xmca_pvalue_log_norm(int64_t n_obs, double* out);
  * A constant column gives NaN in both maps.  The resident fields and vectors are not changed. */
 int xmca_correlation_maps(xmca_handle* h, int side, const double* Y, int64_t T, int64_t m, const int64_t* keep_idx, int64_t N_full,
                           int r_dtype, void* r_out, double* p_out);
+
+/* xmca_correlation_maps with the memory space of both outputs as an argument (an entry point added to ABI 15 - no existing
+ * signature changes).  out_location XMCA_HOST: xmca_correlation_maps, to the bit.  XMCA_DEVICE: r_out and p_out are memory of the
+ * handle's GPU, written directly by the final kernel.  Y stays host memory.  The handle's stream is synchronised before the call
+ * returns. */
+int xmca_correlation_maps_to(xmca_handle* h, int side, const double* Y, int64_t T, int64_t m, const int64_t* keep_idx, int64_t N_full,
+                             int r_dtype, void* r_out, double* p_out, int out_location);
 
 /* Constructor preprocessing on the device (xmca/array.py:199-215 `_set_field_means` / `_set_field_stds` / `_center`;
  * SURVEY 8f row 3): the field of `side` set with xmca_set_field (raw, uncentered) is centered in place, column by

@@ -33,6 +33,8 @@ SIGNATURES = {
     "xmca_destroy": (None, [_vp]),
     "xmca_last_error": (ctypes.c_char_p, [_vp]),
     "xmca_set_field": (_c_int, [_vp, _c_int, _vp, _vp, _c_i64, _c_i64, _c_int, _c_int]),
+    "xmca_set_field_strided": (_c_int, [_vp, _c_int, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_int]),
+    "xmca_ingest_regime": (_c_int, [_c_i64, _c_i64, _c_i64, _c_i64]),
     "xmca_complexify": (_c_int, [_vp, _vp]),
     "xmca_complexify_extended": (_c_int, [_vp, _vp, _vp, _vp, _vp, _c_int]),
     "xmca_solve": (_c_int, [_vp, _c_int, _c_i64, ctypes.POINTER(_c_i64)]),
@@ -40,6 +42,8 @@ SIGNATURES = {
     "xmca_get_vectors": (_c_int, [_vp, _c_int, _vp, _c_i64, _c_int]),
     "xmca_get_eofs": (_c_int, [_vp, _c_int, _vp, _c_i64, _c_i64, _c_int, _vp, _c_int]),
     "xmca_get_maps": (_c_int, [_vp, _c_int, _vp, _c_i64, _c_i64, _c_int, _vp, _c_int, _vp, _c_i64, _c_int, _c_int, _vp, _c_int, _vp]),
+    "xmca_get_maps_to": (_c_int, [_vp, _c_int, _vp, _c_i64, _c_i64, _c_int, _vp, _c_int, _vp, _c_i64, _c_int, _c_int, _vp, _c_int, _vp,
+                                  _c_int]),
     "xmca_center_field": (_c_int, [_vp, _c_int, _vp, _vp, ctypes.POINTER(_c_i64)]),
     "xmca_compact_field": (_c_int, [_vp, _c_int, _vp, ctypes.POINTER(_c_i64)]),
     "xmca_scale_field": (_c_int, [_vp, _c_int, _vp, _c_int]),
@@ -55,6 +59,7 @@ SIGNATURES = {
     "xmca_pearson_pvalues": (_c_int, [_vp, _vp, _c_i64, _c_i64, _vp]),
     "xmca_pvalue_log_norm": (_c_int, [_c_i64, _dp]),
     "xmca_correlation_maps": (_c_int, [_vp, _c_int, _vp, _c_i64, _c_i64, _vp, _c_i64, _c_int, _vp, _vp]),
+    "xmca_correlation_maps_to": (_c_int, [_vp, _c_int, _vp, _c_i64, _c_i64, _vp, _c_i64, _c_int, _vp, _vp, _c_int]),
     "xmca_project": (_c_int, [_vp, _c_int, _vp, _c_i64, _c_i64, _c_int, _vp, ctypes.POINTER(_c_int)]),
     "xmca_predict": (_c_int, [_vp, _c_int, _vp, _c_i64, _c_i64, _c_int, _vp, _c_i64, _vp, _vp, _vp, _c_int, _vp, _c_i64, _c_i64, _c_int,
                               _vp, ctypes.POINTER(_c_int)]),
@@ -62,6 +67,10 @@ SIGNATURES = {
     "xmca_predict_weighted": (_c_int, [_vp, _c_int, _vp, _c_i64, _c_i64, _c_int, _vp, _c_i64, _vp, _vp, _vp, _c_int, _vp, _c_i64, _c_i64,
                                        _c_int, _vp, ctypes.POINTER(_c_int), _vp]),
     "xmca_reconstruct_weighted": (_c_int, [_vp, _c_int, _vp, _c_i64, _c_i64, _c_int, _vp, _c_int, _vp, _c_i64, _c_i64, _vp, _vp, _vp, _vp]),
+    "xmca_predict_strided": (_c_int, [_vp, _c_int, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _vp, _c_i64, _vp, _vp, _vp, _c_int,
+                                      _vp, _c_i64, _c_i64, _c_int, _vp, ctypes.POINTER(_c_int), _vp]),
+    "xmca_reconstruct_to": (_c_int, [_vp, _c_int, _vp, _c_i64, _c_i64, _c_int, _vp, _c_int, _vp, _c_i64, _c_i64, _vp, _vp, _vp, _vp,
+                                     _c_int]),
     "xmca_is_complex": (_c_int, [_vp]),
     "xmca_vectors_are_f32": (_c_int, [_vp, _c_int]),
     "xmca_persistent_giveups": (ctypes.c_longlong, []),
@@ -109,6 +118,7 @@ def library_path():
 
 MAP_EOF, MAP_AMPLITUDE, MAP_PHASE = 0, 1, 2          # `kind` of xmca_get_maps
 SCALE_NONE, SCALE_MAX, SCALE_STD = 0, 1, 2           # ... and its `scaling`
+INGEST_ROWS, INGEST_TRANSPOSE, INGEST_GATHER = 0, 1, 2   # regimes of xmca_set_field_strided (xmca_ingest_regime)
 PVALUE_MAX_OBS = 1000000    # largest n_obs of xmca_pearson_pvalues / xmca_correlation_maps (csrc/kernels.h)
 ABI_VERSION = 15         # bumped whenever a signature of include/xmca_hip.h changes; checked against xmca_abi_version()
 
@@ -149,6 +159,31 @@ def pvalue_log_norm(n_obs):
     if rc != 0:
         raise ValueError("pvalue_log_norm: n_obs must be between 3 and 1 000 000")
     return out.value
+
+
+def ingest_regime(T, N, stride_t, stride_n):
+    """The copy kernel `xmca_set_field_strided` takes for a T x N view with these element strides: INGEST_ROWS (contiguous rows),
+    INGEST_TRANSPOSE (time is the fast axis) or INGEST_GATHER (xmca_ingest_regime; no device)."""
+    rc = load_library().xmca_ingest_regime(int(T), int(N), int(stride_t), int(stride_n))
+    if rc < 0:
+        raise ValueError("ingest_regime: a non-empty view with strides >= 0 is needed")
+    return rc
+
+
+class DeviceView:
+    """A real T x N view of memory on a handle's GPU: element (t, n) at `ptr` + (t * stride_t + n * stride_n) elements of `dtype`
+    (float32 / float64).  `owner` keeps the memory alive (a tensor); the library only ever reads it."""
+
+    def __init__(self, ptr, T, N, stride_t, stride_n, dtype, owner=None):
+        self.ptr, self.T, self.N = int(ptr), int(T), int(N)
+        self.stride_t, self.stride_n = int(stride_t), int(stride_n)
+        self.dtype = np.dtype(dtype)
+        self.owner = owner
+        self.shape = (self.T, self.N)
+        if self.dtype not in (np.float32, np.float64):
+            raise TypeError("DeviceView: float32 / float64 only, got %s" % self.dtype)
+        if self.stride_t < 0 or self.stride_n < 0:
+            raise ValueError("DeviceView: negative strides are not supported")
 
 
 class HipError(RuntimeError):
@@ -205,6 +240,16 @@ def _column_weights(what, w, N):
     if np.iscomplexobj(w) or w.shape != (N,):
         raise ValueError("%s: the weights must be %d real values, one per kept column, got shape %s" % (what, N, w.shape))
     return np.ascontiguousarray(w, dtype=np.float64)
+
+
+def _output(alloc, shape, dtype):
+    """(array, pointer argument, XMCA_HOST / XMCA_DEVICE) of a result: a new host array, or what `alloc(shape, dtype)` made on the
+    handle's GPU - `(array, device address)`."""
+    if alloc is None:
+        out = np.empty(shape, dtype=dtype)
+        return out, _ptr(out), HOST
+    out, address = alloc(shape, np.dtype(dtype))
+    return out, _vp(int(address)), DEVICE
 
 
 def _unpack(out, rows, cols, is_complex):
@@ -366,6 +411,16 @@ class Handle:
                                              _np_dtype_code(dtype), DEVICE))
         self.field_dtype = np.dtype(_real_np(_np_dtype_code(dtype)))
 
+    def set_field_strided(self, side, view):
+        """The field of `side` from a `DeviceView`: copied on the device into the library's own contiguous buffer
+        (xmca_set_field_strided), whatever its two strides; afterwards as after `set_field`.  The view's memory is not written and
+        not referenced once this returns; the caller has ordered its own work on it (a stream synchronisation) before."""
+        self.release_result()
+        self.fields_owner = None
+        code = _np_dtype_code(view.dtype)
+        self._check(self._lib.xmca_set_field_strided(self._h, side, _vp(view.ptr), view.T, view.N, view.stride_t, view.stride_n, code))
+        self.field_dtype = np.dtype(_real_np(code))
+
     def complexify(self, T):
         self.release_result()
         ht = hilbert_imag_column(T)
@@ -424,11 +479,13 @@ class Handle:
         self._check(self._lib.xmca_get_eofs(self._h, side, _ptr(W), m, q, int(w_cplx), _ptr(out), code))
         return out
 
-    def maps(self, side, N, m, W, col_factor, keep_idx, N_full, kind, scaling, dtype, want_stats=False):
+    def maps(self, side, N, m, W, col_factor, keep_idx, N_full, kind, scaling, dtype, want_stats=False, alloc=None):
         """(N_full x q) spatial map of `side` in its final layout (xmca_get_maps): the values of `eofs(side, N, m, W, dtype)` times the
         q per-column factors `col_factor` (None: as they are), as EOFs, amplitudes or phases (`kind`: MAP_*), every column divided
         by its largest value or its standard deviation over the N kept points (`scaling`: SCALE_*), NaN at the rows not in keep_idx
-        (None: N_full = N).  `dtype`: float32 / float64 components of the result.  want_stats: (map, the q float64 divisors)."""
+        (None: N_full = N).  `dtype`: float32 / float64 components of the result.  want_stats: (map, the q float64 divisors).
+        alloc: None, or `alloc(shape, numpy dtype) -> (array on this handle's GPU, its device address)`: the map is then written there
+        by the device (xmca_get_maps_to, XMCA_DEVICE) and that array returned - nothing is copied to the host."""
         cplx = bool(self._lib.xmca_is_complex(self._h))
         code = _np_dtype_code(dtype)
         W, w_cplx = _host_vectors(W)
@@ -443,10 +500,10 @@ class Handle:
         if idx is not None and idx.shape != (N,):
             raise ValueError("maps: keep_idx must hold one row index per kept point (%d), got shape %s" % (N, idx.shape))
         o_cplx = kind == MAP_EOF and (cplx or w_cplx or f_cplx)
-        out = np.empty((int(N_full), q), dtype=_cplx_np(code) if o_cplx else _real_np(code))
+        out, out_ptr, where = _output(alloc, (int(N_full), q), _cplx_np(code) if o_cplx else _real_np(code))
         stats = np.full(q, np.nan) if want_stats else None
-        self._check(self._lib.xmca_get_maps(self._h, side, _ptr(W), m, q, int(w_cplx), _ptr(f), int(f_cplx), _ptr(idx), int(N_full),
-                                            int(kind), int(scaling), _ptr(out), code, _ptr(stats)))
+        self._check(self._lib.xmca_get_maps_to(self._h, side, _ptr(W), m, q, int(w_cplx), _ptr(f), int(f_cplx), _ptr(idx), int(N_full),
+                                               int(kind), int(scaling), out_ptr, code, _ptr(stats), where))
         return (out, stats) if want_stats else out
 
     def project(self, side, V, T, m=None, N=None):
@@ -467,15 +524,19 @@ class Handle:
         it); keep_idx: kept columns or None; std None: no division; V: N' x m host vectors or None (the first m resident ones of
         the last solve of `side`); W: m x q mix.  weight: N' float64 factors applied after the division, numpy's in-place
         `x *= weight` (xmca_predict_weighted), or None.  The resident fields and vectors stay as they are."""
-        X = np.ascontiguousarray(X)
-        code = _np_dtype_code(X.dtype)
-        if np.iscomplexobj(X) or X.ndim != 2:
-            raise TypeError("predict: X must be a real 2-D array")
+        if isinstance(X, DeviceView):        # new data on this GPU: read where it is (xmca_predict_strided, XMCA_DEVICE)
+            x_ptr, x_strides, x_dtype, where = _vp(X.ptr), (X.stride_t, X.stride_n), X.dtype, DEVICE
+        else:
+            X = np.ascontiguousarray(X)
+            if np.iscomplexobj(X) or X.ndim != 2:
+                raise TypeError("predict: X must be a real 2-D array")
+            x_ptr, x_strides, x_dtype, where = _ptr(X), (X.shape[1], 1), X.dtype, HOST
+        code = _np_dtype_code(x_dtype)
         T, N_full = X.shape
         idx = None if keep_idx is None else np.ascontiguousarray(keep_idx, dtype=np.int64)
         N = N_full if idx is None else idx.size
-        mean = np.ascontiguousarray(np.broadcast_to(mean, (N,)), dtype=X.dtype)
-        std = None if std is None else np.ascontiguousarray(np.broadcast_to(std, (N,)), dtype=X.dtype)
+        mean = np.ascontiguousarray(np.broadcast_to(mean, (N,)), dtype=x_dtype)
+        std = None if std is None else np.ascontiguousarray(np.broadcast_to(std, (N,)), dtype=x_dtype)
         Vd, v_cplx = _host_vectors(V)
         Wd, w_cplx = _host_vectors(W)
         m, q = Wd.shape
@@ -483,20 +544,18 @@ class Handle:
             raise ValueError("predict: V must be N' x m = %d x %d, got %s" % (N, m, Vd.shape))
         out = np.empty((T, q), dtype=np.complex128)
         out_cplx = _c_int(0)
-        args = (self._h, side, _ptr(X), T, N_full, code, _ptr(idx), N, _ptr(mean), _ptr(std), _ptr(Vd), int(v_cplx), _ptr(Wd), m, q,
-                int(w_cplx), _ptr(out), ctypes.byref(out_cplx))
-        if weight is None:
-            self._check(self._lib.xmca_predict(*args))
-        else:
-            weight = _column_weights("predict", weight, N)
-            self._check(self._lib.xmca_predict_weighted(*args, _ptr(weight)))
+        weight = None if weight is None else _column_weights("predict", weight, N)
+        self._check(self._lib.xmca_predict_strided(self._h, side, x_ptr, T, N_full, x_strides[0], x_strides[1], where, code, _ptr(idx), N,
+                                                   _ptr(mean), _ptr(std), _ptr(Vd), int(v_cplx), _ptr(Wd), m, q, int(w_cplx), _ptr(out),
+                                                   ctypes.byref(out_cplx), _ptr(weight)))
         return _unpack(out, T, q, out_cplx.value)
 
-    def reconstruct(self, side, B, V, N, keep_idx=None, N_full=None, mean=None, std=None, inv_weight=None):
+    def reconstruct(self, side, B, V, N, keep_idx=None, N_full=None, mean=None, std=None, inv_weight=None, alloc=None):
         """Re(B V^H) (* std + mean) on the device (xmca_reconstruct), T x N_full float64 with NaN at the columns not in keep_idx.
         B: T x m coefficients; V: N x m host vectors or None (the first m resident ones of the last solve of `side`).
         inv_weight: N float64 factors the product is divided by first, numpy's `x /= inv_weight` (xmca_reconstruct_weighted), or
-        None.  The resident fields and vectors stay as they are."""
+        None.  alloc: as in `maps` - the result is written on the device (xmca_reconstruct_to, XMCA_DEVICE).  The resident fields
+        and vectors stay as they are."""
         Bd, b_cplx = _host_vectors(B)
         T, m = Bd.shape
         Vd, v_cplx = _host_vectors(V)
@@ -506,14 +565,10 @@ class Handle:
         N_full = N if N_full is None else N_full
         mean = None if mean is None else np.ascontiguousarray(np.broadcast_to(mean, (N,)), dtype=np.float64)
         std = None if std is None else np.ascontiguousarray(np.broadcast_to(std, (N,)), dtype=np.float64)
-        out = np.empty((T, N_full), dtype=np.float64)
-        args = (self._h, side, _ptr(Bd) if m else None, T, m, int(b_cplx), _ptr(Vd), int(v_cplx), _ptr(idx), N, N_full, _ptr(mean),
-                _ptr(std), _ptr(out))
-        if inv_weight is None:
-            self._check(self._lib.xmca_reconstruct(*args))
-        else:
-            inv_weight = _column_weights("reconstruct", inv_weight, N)
-            self._check(self._lib.xmca_reconstruct_weighted(*args, _ptr(inv_weight)))
+        out, out_ptr, where = _output(alloc, (T, int(N_full)), np.float64)
+        inv_weight = None if inv_weight is None else _column_weights("reconstruct", inv_weight, N)
+        self._check(self._lib.xmca_reconstruct_to(self._h, side, _ptr(Bd) if m else None, T, m, int(b_cplx), _ptr(Vd), int(v_cplx), _ptr(idx),
+                                                  N, N_full, _ptr(mean), _ptr(std), out_ptr, _ptr(inv_weight), where))
         return out
 
     def center_field(self, side, N):
@@ -596,17 +651,18 @@ class Handle:
         self._check(self._lib.xmca_pearson_pvalues(self._h, _ptr(rd), rd.size, int(n_obs), _ptr(p)))
         return p
 
-    def correlation_maps(self, side, Y, keep_idx, N_full, r_dtype):
+    def correlation_maps(self, side, Y, keep_idx, N_full, r_dtype, alloc=None):
         """(r, p), both N_full x m in their final layout: correlations of the resident field `side` with the columns of Y (T x m)
         in `r_dtype`, their two-sided p-values (float64, from the rounded r), NaN at the rows not in keep_idx (None: every row
-        is a column of the field).  xmca_correlation_maps."""
+        is a column of the field).  alloc: as in `maps` - both maps are written on the device (xmca_correlation_maps_to,
+        XMCA_DEVICE)."""
         Yd = np.ascontiguousarray(np.asarray(Y).real, dtype=np.float64)
         T, m = Yd.shape
         idx = None if keep_idx is None else np.ascontiguousarray(keep_idx, dtype=np.int64)
         code = _np_dtype_code(r_dtype)
-        r = np.empty((N_full, m), dtype=_real_np(code))
-        p = np.empty((N_full, m), dtype=np.float64)
-        self._check(self._lib.xmca_correlation_maps(self._h, side, _ptr(Yd), T, m, _ptr(idx), int(N_full), code, _ptr(r), _ptr(p)))
+        r, r_ptr, where = _output(alloc, (int(N_full), m), _real_np(code))
+        p, p_ptr, where = _output(alloc, (int(N_full), m), np.float64)
+        self._check(self._lib.xmca_correlation_maps_to(self._h, side, _ptr(Yd), T, m, _ptr(idx), int(N_full), code, r_ptr, p_ptr, where))
         return r, p
 
     # ---- rotation -----------------------------------------------------------------------------

@@ -13,6 +13,7 @@ There is no numpy fallback for these three: without the library or a GPU they ra
 """
 import cmath
 import os
+import sys
 import warnings
 from datetime import datetime
 
@@ -58,6 +59,65 @@ def _reconstruct_coefficients(P, A):
     """T x m coefficients B = P A^H of the reconstruction: (P @ V_rot^H).real = Re(B V[:, :m]^H) for V_rot = V[:, :m] A, with P the
     PCs in 'eigen' scaling (array.py:1263-1292)."""
     return P @ A.conj().T
+
+
+def _torch():
+    """torch when the process has imported it, else None: a tensor can only be handed over by code that has."""
+    return sys.modules.get('torch')
+
+
+def _is_tensor(x):
+    torch = _torch()
+    return torch is not None and isinstance(x, torch.Tensor)
+
+
+def _tensor_np_dtype(t):
+    """numpy dtype of a tensor's elements, or None when numpy has no such dtype (bfloat16)."""
+    try:
+        return np.dtype(str(t.dtype).replace('torch.', ''))
+    except TypeError:
+        return None
+
+
+def _flat_strides(shape, strides):
+    """Element strides (stride_t, stride_n) of the (T, N) view of an array of `shape` / `strides` (time first, the spatial
+    dimensions flattened in C order), or None when no two strides express it - the caller then makes the array contiguous.  The
+    spatial dimensions collapse when each one's stride is the next one's stride times its length; dimensions of one element do
+    not count, and neither does a negative stride."""
+    if len(shape) < 2 or any(st < 0 for st in strides):
+        return None
+    dims = [(n, st) for n, st in zip(shape[1:], strides[1:]) if n != 1]
+    for (_, st), (n_next, st_next) in zip(dims, dims[1:]):
+        if st != st_next * n_next:
+            return None
+    return int(strides[0]), int(dims[-1][1]) if dims else 1
+
+
+def _numpy_result(model, name, *args, **kwargs):
+    """Public getter `name` of `model` - as `model` resolves it: a subclass's override, or the base class's for the numpy view a
+    facade passes as `self` - with numpy results whatever the model's `output` says: what the numpy code of another getter
+    builds on."""
+    output = getattr(model, '_output', 'numpy')
+    model._output = 'numpy'
+    try:
+        return getattr(model, name)(*args, **kwargs)
+    finally:
+        model._output = output
+
+
+def _device_view(t, owner=None):
+    """`_hip.DeviceView` of a real float32 / float64 GPU tensor flattened to (T, N): as it lies in memory when two strides
+    express that view, else of a copy torch makes contiguous on the device."""
+    if t.dim() == 1:
+        t = t.unsqueeze(1)
+    flat = _flat_strides(tuple(t.shape), tuple(t.stride()))
+    if flat is None:
+        t = t.contiguous()
+        flat = _flat_strides(tuple(t.shape), tuple(t.stride()))
+    n = 1
+    for d in t.shape[1:]:
+        n *= int(d)
+    return _hip.DeviceView(t.data_ptr(), t.shape[0], n, flat[0], flat[1], _tensor_np_dtype(t), owner=t if owner is None else owner)
 
 
 class _LazyVectors(dict):
@@ -112,12 +172,19 @@ class _RawField:
     """Stand-in for a field that was preprocessed on the device (MCA(..., preprocess='device')): the raw input, the
     mask of its NaN-free columns, and the shape / dtype the centered field has."""
 
-    def __init__(self, raw, keep):
-        self.raw = raw
+    def __init__(self, raw, keep, tensor=None):
+        self._raw = raw
+        self.tensor = tensor     # a field handed over as a GPU tensor: kept for the recompute fallback only (`raw`)
         self.keep = keep
-        self.shape = (raw.shape[0], int(np.count_nonzero(keep)))
-        self.dtype = raw.dtype
+        self.shape = ((raw if tensor is None else tensor).shape[0], int(np.count_nonzero(keep)))
+        self.dtype = raw.dtype if tensor is None else _tensor_np_dtype(tensor)
         self.ops = []            # (divide, per-column factors) applied on the device after centering, in order
+
+    @property
+    def raw(self):
+        if self._raw is None:    # (the tensor as it is NOW: the model only owns the centered copy on the device)
+            self._raw = self.tensor.detach().reshape(self.tensor.shape[0], -1).cpu().numpy()
+        return self._raw
 
     @property
     def real(self):
@@ -135,15 +202,22 @@ class _RawField:
 
 
 class MCA:
-    """Maximum Covariance Analysis of one (EOF/PCA) or two `numpy.ndarray` fields; time is axis 0."""
+    """Maximum Covariance Analysis of one (EOF/PCA) or two fields - `numpy.ndarray`s or `torch.Tensor`s; time is axis 0."""
 
-    def __init__(self, *fields, handle=None, preprocess=None):
-        """fields: one or two numpy arrays, time first.  `handle`: a `_hip.Handle` (default: one per device).
+    def __init__(self, *fields, handle=None, preprocess=None, output=None):
+        """fields: one or two numpy arrays or `torch.Tensor`s, time first.  `handle`: a `_hip.Handle` (default: one per device).
         `preprocess` (extension): where the constructor's NaN-column / mean / std / centering passes (array.py:191-215)
         run.  `'device'`: on the GPU over the uploaded raw field - column means in float64 - and the centered field stays
         resident for solve(); the host copy `_fields` is fetched on first use.  `'host'`: the reference's numpy path
         (bit-identical means for float32 input).  Default (None): `'device'` when a GPU is visible and the fields are
-        plain real float32 / float64 arrays of one dtype, `'host'` otherwise (XMCA_PREPROCESS=host|device overrides)."""
+        plain real float32 / float64 arrays of one dtype, `'host'` otherwise (XMCA_PREPROCESS=host|device overrides).
+        Tensors (extension): a CPU tensor is taken as its numpy array.  Real float32 / float64 tensors on the handle's GPU, of one
+        dtype and with a spatial dimension, never visit the host: the library copies them, in whatever strided layout they have,
+        into its own buffer (`xmca_set_field_strided`) and preprocesses them there; the tensor is neither written nor needed
+        afterwards.  `output`: `'numpy'` or `'torch'` - what the getters that return dicts of arrays return; with `'torch'` they
+        are tensors on the handle's GPU, and the field-sized ones (eofs, spatial_amplitude, spatial_phase, reconstructed_fields,
+        homogeneous / heterogeneous_patterns) are written there by the device.  Spectra stay numpy.  Default: `'torch'` when a
+        field is a GPU tensor, else `'numpy'`."""
         if preprocess is None:
             preprocess = os.environ.get('XMCA_PREPROCESS') or 'auto'
         if preprocess not in ('host', 'device', 'auto'):
@@ -155,10 +229,24 @@ class MCA:
         if len(fields) == 2 and fields[0].shape[0] != fields[1].shape[0]:
             raise ValueError('''Time dimensions of given fields are different.
                 Time series should have same time lengths.''')
-        if not all(isinstance(f, np.ndarray) for f in fields):
+        if output not in (None, 'numpy', 'torch'):
+            raise ValueError("output must be 'numpy' or 'torch'")
+        fields = tuple(f.detach().numpy() if _is_tensor(f) and f.device.type == 'cpu' else f for f in fields)
+        if not all(isinstance(f, np.ndarray) or _is_tensor(f) for f in fields):
             raise TypeError('''One or more fields are not `numpy.ndarray`.
             Please provide `numpy.ndarray` only.''')
         self._handle_override = handle
+        on_gpu = any(_is_tensor(f) for f in fields)
+        if on_gpu:
+            self._check_gpu_tensors(fields)
+            if preprocess != 'device':                       # an explicit 'host': the reference's numpy path on a host copy
+                fields = tuple(f.detach().cpu().numpy() for f in fields)
+        self._output = output or ('torch' if on_gpu else 'numpy')
+        if self._output == 'torch':
+            try:
+                import torch      # noqa: F401
+            except ImportError as err:
+                raise ValueError("output='torch' needs PyTorch") from err
         self._preprocess = preprocess
         self._store_is_raw = False
         self._keys = ['left', 'right']
@@ -181,6 +269,9 @@ class MCA:
 
         data = {k: f for k, f in zip(self._keys, fields)}
         if not (preprocess == 'device' and self._ingest_on_device(data)):
+            if any(_is_tensor(f) for f in fields):           # no NaN-free column: the host path raises the reference's errors
+                fields = tuple(f.detach().cpu().numpy() for f in fields)
+                data = {k: f for k, f in zip(self._keys, fields)}
             if any(has_nan_time_steps(f) for f in fields):
                 raise ValueError('''One or more fields contain NaN time steps.
             Please remove these prior to analysis.''')
@@ -254,14 +345,24 @@ class MCA:
         field has no NaN-free column (the host path then raises the reference's errors)."""
         if len(data) == 0:
             return False
-        dtypes = {np.dtype(f.dtype) for f in data.values()}
+        tensors = any(_is_tensor(f) for f in data.values())          # (all of them then: `_check_gpu_tensors`)
+        dtypes = {_tensor_np_dtype(f) if tensors else np.dtype(f.dtype) for f in data.values()}
         if len(dtypes) != 1 or next(iter(dtypes)) not in (np.dtype(np.float32), np.dtype(np.float64)):
             return False
         dev = self._device()
-        flat = {k: np.ascontiguousarray(f.reshape(f.shape[0], int(np.prod(f.shape[1:])))) for k, f in data.items()}
+        if tensors:
+            # GPU tensors: flattened to (T, N) as strided views of their own memory (or of a contiguous copy torch makes) and
+            # copied by the device; first wait for whatever produces them on the caller's stream - the library works on its own
+            flat = {k: _device_view(f.detach()) for k, f in data.items()}
+            _torch().cuda.current_stream(dev.device).synchronize()
+        else:
+            flat = {k: np.ascontiguousarray(f.reshape(f.shape[0], int(np.prod(f.shape[1:])))) for k, f in data.items()}
         stats, keep = {}, {}
         for side, k in enumerate(self._keys):
-            dev.set_field(side, flat[k])
+            if tensors:
+                dev.set_field_strided(side, flat[k])
+            else:
+                dev.set_field(side, flat[k])
             keep[k], n_keep = dev.compact_field(side, flat[k].shape[1])      # array.py:191-197 on the device
             if n_keep == 0:
                 dev.fields_owner = None
@@ -273,7 +374,7 @@ class MCA:
             self._no_nan_index[k] = keep[k]
             self._field_means[k] = stats[k][0].astype(f.dtype, copy=False)
             self._field_stds[k] = stats[k][1].astype(f.dtype, copy=False)
-            store[k] = _RawField(f, keep[k])
+            store[k] = _RawField(None, keep[k], tensor=data[k].detach()) if tensors else _RawField(f, keep[k])
         self._fields_store = store              # stand-ins: only shape / dtype are read while `_store_is_raw`
         self._store_is_raw = True
         dev.fields_owner = self._owner_key()
@@ -294,6 +395,56 @@ class MCA:
     def _device(self):
         return self._handle_override or _hip.default_handle()
 
+    def _check_gpu_tensors(self, fields):
+        """The fields that may take the device route: all of them real float32 / float64 tensors of one dtype on the handle's GPU,
+        each with a spatial dimension.  Anything else says what is wrong."""
+        dev = self._device()
+        for f in fields:
+            if not _is_tensor(f):
+                raise TypeError('Fields on the GPU and on the host cannot be mixed: pass tensors of one device, or arrays.')
+            if f.device.type != 'cuda' or f.device.index != dev.device:
+                raise ValueError('A field is on {:}, the handle works on GPU {:}. Move the tensor, or pass a handle of its '
+                                 'device.'.format(f.device, dev.device))
+            if _tensor_np_dtype(f) not in (np.dtype(np.float32), np.dtype(np.float64)):
+                raise TypeError('A GPU tensor field has dtype {:}: only real float32 and float64 tensors are '
+                                'supported.'.format(f.dtype))
+            if f.dim() < 2:
+                raise ValueError('A GPU tensor field has {:} dimension(s): time and at least one spatial dimension are '
+                                 'needed.'.format(f.dim()))
+        if len({f.dtype for f in fields}) != 1:
+            raise TypeError('The GPU tensor fields have different dtypes ({:}): both must be float32 or both '
+                            'float64.'.format(', '.join(str(f.dtype) for f in fields)))
+
+    # ------------------------------------------------------------------------------------------
+    # output='torch': results as tensors on the handle's GPU
+    # ------------------------------------------------------------------------------------------
+    def _alloc(self):
+        """None for numpy results; for torch results the allocator the device routes write through (`_hip.Handle.maps`): a new
+        tensor on the handle's GPU and its address.  torch's allocator may hand out memory that work queued on the caller's stream
+        still uses, so that stream is drained first; the library's call synchronises its own stream before it returns."""
+        if getattr(self, '_output', 'numpy') != 'torch':
+            return None
+        import torch
+        device = torch.device('cuda', self._device().device)
+        torch.cuda.current_stream(device).synchronize()
+
+        def alloc(shape, dtype):
+            t = torch.empty(tuple(int(n) for n in shape), dtype=getattr(torch, np.dtype(dtype).name), device=device)
+            return t, t.data_ptr()
+        return alloc
+
+    def _deliver(self, result):
+        """A getter's dict (or tuple of dicts) in the model's output type: numpy arrays become tensors on the handle's GPU when
+        it is 'torch' (the results that were computed on the host); tensors pass."""
+        if getattr(self, '_output', 'numpy') != 'torch':
+            return result
+        if isinstance(result, tuple):
+            return tuple(self._deliver(r) for r in result)
+        import torch
+        device = torch.device('cuda', self._device().device)
+        return {k: v if isinstance(v, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(v)).to(device)
+                for k, v in result.items()}
+
     # ------------------------------------------------------------------------------------------
     # constructor helpers (array.py:191-240)
     # ------------------------------------------------------------------------------------------
@@ -309,10 +460,11 @@ class MCA:
 
     def _set_field_meta(self, data):
         for k, field in data.items():
-            self._shape[k] = field.shape
-            self._n_observations[k] = field.shape[0]
-            self._fields_spatial_shape[k] = field.shape[1:]
-            self._n_variables[k] = int(np.prod(field.shape[1:]))
+            shape = tuple(int(n) for n in field.shape)      # (a tensor's torch.Size as the tuple numpy has)
+            self._shape[k] = shape
+            self._n_observations[k] = shape[0]
+            self._fields_spatial_shape[k] = shape[1:]
+            self._n_variables[k] = int(np.prod(shape[1:]))
             self._field_names[k] = k
 
     def _reshape_to_2d(self, data):
@@ -778,12 +930,13 @@ class MCA:
                     out[k] = (side, n_k, max_mode, np.eye(max_mode)[:, keep], Vl._dtype)
         return out
 
-    def _maps_from_device(self, n, rotated, kind, scaling='None', phase_shift=0):
+    def _maps_from_device(self, n, rotated, kind, scaling='None', phase_shift=0, alloc=None):
         """eofs() / spatial_amplitude() / spatial_phase() of every field in their final (space..., modes) arrays from the device
         (`xmca_get_maps`): phase shift and 'eigen' norms as per-column factors, 'max' / 'std' divisors, amplitude or phase and the
         NaN rows of the masked grid points, without a pass over N x q on the host.  The dtype of each result is worked out here with
         the promotions the numpy code below performs, and passed down.  None when the vectors are not resident, the selection is
-        empty, `_maps_on_host` is set or a float32 / complex64 result is to be scaled by 'std': the caller then runs the numpy code."""
+        empty, `_maps_on_host` is set or a float32 / complex64 result is to be scaled by 'std': the caller then runs the numpy code.
+        alloc (`_alloc`): the maps are written into tensors on the GPU and those returned."""
         if getattr(self, '_maps_on_host', False) or scaling not in _MAP_SCALINGS:
             return None
         mix = self._eof_mix(n, rotated)
@@ -817,17 +970,17 @@ class MCA:
             plan[k] = (side, n_k, m, W, dtype, factor, dt, plain)
         out = {}
         for k, (side, n_k, m, W, dtype, factor, dt, plain) in plan.items():
-            if plain:
+            if plain and alloc is None:
                 full = dev.eofs(side, n_k, m, W, dtype)   # no mask, no scaling, no phase shift: `xmca_get_eofs` as it is
-            else:
+            else:                                         # (on the GPU the plain case is a map without options: the same bits)
                 masked = self._n_variables[k] != n_k
                 full = dev.maps(side, n_k, m, W, factor, np.flatnonzero(self._no_nan_index[k]) if masked else None,
-                                self._n_variables[k], kind, _MAP_SCALINGS[scaling], dt)
+                                self._n_variables[k], kind, _MAP_SCALINGS[scaling], dt, alloc=alloc)
             out[k] = full.reshape(self._fields_spatial_shape[k] + (full.shape[1],))
         return out
 
-    def _get_eofs(self, n=None, scaling='None', phase_shift=0, rotated=True):
-        eofs = self._maps_from_device(n, rotated, _hip.MAP_EOF, scaling, phase_shift)
+    def _get_eofs(self, n=None, scaling='None', phase_shift=0, rotated=True, alloc=None):
+        eofs = self._maps_from_device(n, rotated, _hip.MAP_EOF, scaling, phase_shift, alloc=alloc)
         if eofs is not None:
             return eofs
         V = self._eofs_from_device(n, rotated)
@@ -944,7 +1097,7 @@ class MCA:
     # ------------------------------------------------------------------------------------------
     def fields(self, original_scale=False):
         """The (centered / normalised / complexified) input fields, optionally back in original units."""
-        return self._get_fields(original_scale)
+        return self._deliver(self._get_fields(original_scale))
 
     def singular_values(self, n=None):
         return self._get_svals(n)
@@ -965,40 +1118,40 @@ class MCA:
         return self._get_variance(n=n, sorted=True) / self._analysis['total_covariance'] * 100
 
     def pcs(self, n=None, scaling='None', phase_shift=0, rotated=True):
-        return self._get_pcs(n, scaling, phase_shift, rotated)
+        return self._deliver(self._get_pcs(n, scaling, phase_shift, rotated))
 
     def eofs(self, n=None, scaling='None', phase_shift=0, rotated=True):
-        return self._get_eofs(n, scaling, phase_shift, rotated)
+        return self._deliver(self._get_eofs(n, scaling, phase_shift, rotated, alloc=self._alloc()))
 
     def spatial_amplitude(self, n=None, scaling='None', rotated=True):
-        out = self._maps_from_device(n, rotated, _hip.MAP_AMPLITUDE, 'max' if scaling == 'max' else 'None')
+        out = self._maps_from_device(n, rotated, _hip.MAP_AMPLITUDE, 'max' if scaling == 'max' else 'None', alloc=self._alloc())
         if out is not None:
             return out
         out = {}
-        for k, eof in self.eofs(n, scaling='None', rotated=rotated).items():
+        for k, eof in _numpy_result(self, 'eofs', n, scaling='None', rotated=rotated).items():
             out[k] = np.sqrt(eof * eof.conjugate()).real
             if scaling == 'max':
                 out[k] /= np.nanmax(out[k], axis=tuple(range(out[k].ndim - 1)))
-        return out
+        return self._deliver(out)
 
     def spatial_phase(self, n=None, phase_shift=0, rotated=True):
-        out = self._maps_from_device(n, rotated, _hip.MAP_PHASE, 'None', phase_shift)
+        out = self._maps_from_device(n, rotated, _hip.MAP_PHASE, 'None', phase_shift, alloc=self._alloc())
         if out is not None:
             return out
-        return {k: np.arctan2(e.imag, e.real).real
-                for k, e in self.eofs(n, phase_shift=phase_shift, rotated=rotated).items()}
+        return self._deliver({k: np.arctan2(e.imag, e.real).real
+                              for k, e in _numpy_result(self, 'eofs', n, phase_shift=phase_shift, rotated=rotated).items()})
 
     def temporal_amplitude(self, n=None, scaling='None', rotated=True):
         out = {}
-        for k, pc in self.pcs(n, scaling='None', rotated=rotated).items():
+        for k, pc in _numpy_result(self, 'pcs', n, scaling='None', rotated=rotated).items():
             out[k] = np.sqrt(pc * pc.conjugate()).real
             if scaling == 'max':
                 out[k] /= np.nanmax(out[k], axis=0)
-        return out
+        return self._deliver(out)
 
     def temporal_phase(self, n=None, phase_shift=0, rotated=True):
-        return {k: np.arctan2(p.imag, p.real).real
-                for k, p in self.pcs(n, phase_shift=phase_shift, rotated=rotated).items()}
+        return self._deliver({k: np.arctan2(p.imag, p.real).real
+                              for k, p in _numpy_result(self, 'pcs', n, phase_shift=phase_shift, rotated=rotated).items()})
 
     def _correlation_maps(self, n, phase_shift, pair):
         """Pearson correlation of every grid point (real part of the field) with the PCs and its p-value
@@ -1014,6 +1167,7 @@ class MCA:
             self._upload_fields(dev)
         n_obs = self._n_observations['left']
         on_host = n_obs < 3 or n_obs > _hip.PVALUE_MAX_OBS or getattr(self, '_patterns_on_host', False)
+        alloc = None if on_host else self._alloc()
         rvals, pvals = {}, {}
         for side, k in enumerate(self._keys):
             try:
@@ -1028,10 +1182,10 @@ class MCA:
             else:
                 mask = self._no_nan_index[k]
                 keep_idx = None if self._fields_store[k].shape[1] == mask.size else np.flatnonzero(mask)
-                r, p = dev.correlation_maps(side, y, keep_idx, mask.size, r_dtype)
+                r, p = dev.correlation_maps(side, y, keep_idx, mask.size, r_dtype, alloc=alloc)
             rvals[k] = r.reshape(self._fields_spatial_shape[k] + (r.shape[1],))
             pvals[k] = p.reshape(self._fields_spatial_shape[k] + (p.shape[1],))
-        return rvals, pvals
+        return self._deliver((rvals, pvals))
 
     def homogeneous_patterns(self, n=None, phase_shift=0):
         return self._correlation_maps(n, phase_shift, {k: k for k in self._keys})
@@ -1064,7 +1218,7 @@ class MCA:
         this hook keeps the host route (`_transform_vectors`)."""
         return None
 
-    def _reconstruct_on_device(self, mode, original_scale, full):
+    def _reconstruct_on_device(self, mode, original_scale, full, alloc=None):
         """`(pcs(mode, 'eigen') @ V_rot^H).real`, scaled back and (full) with the masked points re-inserted as NaN, as one product
         over the vectors on the device per field (xmca_reconstruct): B = P A^H (T x m, `_reconstruct_coefficients`) is the only
         host work.  Returns {k: T x N (full) or T x N'} or None when the host path has to run."""
@@ -1102,7 +1256,8 @@ class MCA:
             mask = self._no_nan_index[k]
             keep_idx = np.flatnonzero(mask) if (full and n_keep != mask.size) else None
             X = dev.reconstruct(side, B, None if Vh is None else Vh[:, :B.shape[1]], n_keep, keep_idx=keep_idx,
-                                N_full=mask.size if keep_idx is not None else n_keep, mean=mean, std=std, inv_weight=inv_weight)
+                                N_full=mask.size if keep_idx is not None else n_keep, mean=mean, std=std, inv_weight=inv_weight,
+                                alloc=alloc)
             out[k] = X if full else X.astype(dtype, copy=False)
         return out
 
@@ -1119,14 +1274,14 @@ class MCA:
 
     def reconstructed_fields(self, mode=None, original_scale=True):
         n_obs = self._n_observations['left']
-        rec = self._reconstruct_on_device(mode, original_scale, full=True)
+        rec = self._reconstruct_on_device(mode, original_scale, full=True, alloc=self._alloc())
         if rec is not None:                  # final layout from the device: NaN at the masked points, float64
             return {k: X.reshape((-1,) + self._fields_spatial_shape[k]) for k, X in rec.items()}
         out = {}
         for k, X in self._reconstructed_X(mode=mode, original_scale=original_scale).items():
             full = self._with_nan_columns(k, np.asarray(X, dtype=float), (n_obs,))
             out[k] = full.reshape((-1,) + self._fields_spatial_shape[k])
-        return out
+        return self._deliver(out)
 
     _reconstructed_fields = reconstructed_fields
 
@@ -1137,8 +1292,18 @@ class MCA:
         """Project new data on the singular vectors (rotated if the model is).  Real new data of the model's field dtype is
         projected on the device (xmca_predict: the vectors stay there), anything else on the host as the reference does."""
         given = {k: d for k, d in zip(self._keys, [left, right]) if d is not None}
-        on_device = all(isinstance(d, np.ndarray) and d.dtype == _real_dtype(self._fields_store[k].dtype)
-                        and self._transform_vectors(k) is not None for k, d in given.items())
+        given = {k: d.detach() if _is_tensor(d) else d for k, d in given.items()}
+        given = {k: d.numpy() if _is_tensor(d) and d.device.type == 'cpu' else d for k, d in given.items()}
+
+        def device_ready(k, d):   # real new data of the field's dtype: a numpy array, or a tensor the handle's GPU can read in place
+            if _is_tensor(d):
+                dtype = _tensor_np_dtype(d) if d.device.type == 'cuda' and d.device.index == self._device().device else None
+            else:
+                dtype = d.dtype if isinstance(d, np.ndarray) else None
+            return dtype == _real_dtype(self._fields_store[k].dtype) and self._transform_vectors(k) is not None
+        on_device = all(device_ready(k, d) for k, d in given.items())
+        if not on_device:         # the host route, as the reference: tensors come down first
+            given = {k: d.cpu().numpy() if _is_tensor(d) else d for k, d in given.items()}
         if on_device:
             V = None
             svals = self._get_svals()
@@ -1153,7 +1318,11 @@ class MCA:
         out = {}
         for k, x in given.items():
             try:
-                x = x.reshape(x.shape[0], self._n_variables[k])
+                if _is_tensor(x):     # (stays as it lies in memory: `_device_view` flattens it)
+                    if x.dim() < 1 or x.shape[0] * self._n_variables[k] != x.numel():
+                        raise ValueError('cannot flatten the tensor to (time, {:})'.format(self._n_variables[k]))
+                else:
+                    x = x.reshape(x.shape[0], self._n_variables[k])
                 if not on_device:
                     x = x[:, self._no_nan_index[k]]
             except ValueError as err:
@@ -1190,7 +1359,7 @@ class MCA:
             else:
                 raise ValueError(_SCALINGS_MSG.format(scaling))
             out[k] = pcs
-        return out
+        return self._deliver(out)
 
     def _predict_on_device(self, k, x, svals, R_inv_t, n_rot, n):
         """`(x[:, kept] - mean) / std @ V[:, :n_rot] / sqrt(s) @ R^-H`, columns ordered and selected, for the raw T' x N new data x
@@ -1206,6 +1375,9 @@ class MCA:
         std = self._field_stds[k] if self._analysis['is_normalized'] else None
         side = self._keys.index(k)
         weights = self._device_column_weights(k)
+        if _is_tensor(x):         # (T', N) as it lies on the GPU; its producer on the caller's stream has finished first
+            x = _device_view(x)
+            _torch().cuda.current_stream(dev.device).synchronize()
         return dev.predict(side, x, keep_idx, self._field_means[k], std, None if Vh is None else Vh[:, :W.shape[0]], W,
                            weight=None if weights is None else weights[0])
 

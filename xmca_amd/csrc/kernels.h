@@ -531,6 +531,101 @@ static inline dim3 row_col_grid(int64_t rows, int64_t cols) {
   return dim3((unsigned)bx, (unsigned)by);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Strided device ingest (xmca_set_field_strided, the device entrance of xmca_predict_strided): a T x N view of device memory with
+// element (t, n) at src[t * stride_t + n * stride_n] -> a contiguous row-major T x N array.  Pure copies (the bits of every
+// element, NaN payloads included), 64-bit index arithmetic throughout, no scratch, no atomics.  Three regimes, chosen on the
+// host from the strides (ingest_regime).
+// ------------------------------------------------------------------------------------------------
+constexpr int INGEST_ROWS = 0, INGEST_TRANSPOSE = 1, INGEST_GATHER = 2;
+constexpr int INGEST_TILE = 64;      // edge of the transpose tile: one wave reads / writes 64 consecutive elements
+
+// rows contiguous (stride_n == 1), `pitch` elements apart: a coalesced copy.  A row whose source and destination both start on a
+// 16-byte boundary moves 16 bytes per lane and finishes with single elements; any other row (a base aligned to the element
+// only, a pitch that moves the alignment from row to row) moves single elements.  The choice is uniform over the workgroup.
+template <typename T>
+__global__ void ingest_rows_kernel(const T* __restrict__ src, int64_t pitch, int64_t rows, int64_t cols, T* __restrict__ dst) {
+  constexpr int V = 16 / (int)sizeof(T);
+  typedef T vec_t __attribute__((ext_vector_type(V)));
+  const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, step = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t t = blockIdx.y; t < rows; t += gridDim.y) {
+    const T* s = src + t * pitch;
+    T* d = dst + t * cols;
+    int64_t done = 0;
+    if ((((uintptr_t)s | (uintptr_t)d) & 15) == 0) {
+      const int64_t nv = cols / V;
+      for (int64_t i = i0; i < nv; i += step) reinterpret_cast<vec_t*>(d)[i] = reinterpret_cast<const vec_t*>(s)[i];
+      done = nv * V;
+    }
+    for (int64_t i = done + i0; i < cols; i += step) d[i] = s[i];
+  }
+}
+
+// time is the fast axis (stride_t == 1), columns `pitch` elements apart: a transpose, one 64 x 64 tile at a time through LDS.  A
+// wave reads 64 consecutive time steps of one column and writes 64 consecutive columns of one time step.  The tile rows are
+// padded by one element: the row-wise stores and the column-wise loads (65 dwords apart for float, 130 for double - 32 lanes on
+// 32 / 64 distinct banks) are both free of bank conflicts.  Partial tiles at both edges are masked.
+template <typename T>
+__global__ __launch_bounds__(256) void ingest_transpose_kernel(const T* __restrict__ src, int64_t pitch, int64_t rows, int64_t cols,
+                                                              T* __restrict__ dst) {
+  __shared__ T tile[INGEST_TILE][INGEST_TILE + 1];
+  const int tx = threadIdx.x & (INGEST_TILE - 1), ty = threadIdx.x / INGEST_TILE;      // 64 x 4
+  const int64_t tiles_t = (rows + INGEST_TILE - 1) / INGEST_TILE, tiles_n = (cols + INGEST_TILE - 1) / INGEST_TILE;
+  for (int64_t tile_id = blockIdx.x; tile_id < tiles_t * tiles_n; tile_id += gridDim.x) {
+    const int64_t t0 = (tile_id / tiles_n) * INGEST_TILE, n0 = (tile_id % tiles_n) * INGEST_TILE;
+    for (int r = ty; r < INGEST_TILE; r += 4) {
+      const int64_t t = t0 + tx, n = n0 + r;
+      if (t < rows && n < cols) tile[r][tx] = src[n * pitch + t];
+    }
+    __syncthreads();
+    for (int r = ty; r < INGEST_TILE; r += 4) {
+      const int64_t t = t0 + r, n = n0 + tx;
+      if (t < rows && n < cols) dst[t * cols + n] = tile[tx][r];
+    }
+    __syncthreads();
+  }
+}
+
+// any other pair of strides: one element per lane, the writes coalesced.  Rows over blockIdx.y, columns over x.
+template <typename T>
+__global__ void ingest_gather_kernel(const T* __restrict__ src, int64_t stride_t, int64_t stride_n, int64_t rows, int64_t cols,
+                                     T* __restrict__ dst) {
+  for (int64_t t = blockIdx.y; t < rows; t += gridDim.y) {
+    const T* s = src + t * stride_t;
+    T* d = dst + t * cols;
+    for (int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; n < cols; n += (int64_t)gridDim.x * blockDim.x) d[n] = s[n * stride_n];
+  }
+}
+
+// The regime of a T x N view: a dimension of one element has no stride to speak of.
+static inline int ingest_regime(int64_t T, int64_t N, int64_t stride_t, int64_t stride_n) {
+  if (stride_n == 1 || N == 1) return INGEST_ROWS;
+  if (stride_t == 1 || T == 1) return INGEST_TRANSPOSE;
+  return INGEST_GATHER;
+}
+
+// dst (T x N, contiguous) = the view, on stream `st`; the caller checks the launch and synchronises
+template <typename T_>
+static void ingest_strided(hipStream_t st, const T_* src, int64_t T, int64_t N, int64_t stride_t, int64_t stride_n, T_* dst) {
+  const int regime = ingest_regime(T, N, stride_t, stride_n);
+  if (regime == INGEST_ROWS) {
+    int64_t rows = T, cols = N, pitch = stride_t;
+    if (pitch == cols || rows == 1) { cols *= rows; rows = 1; pitch = cols; }      // one contiguous run
+    constexpr int V = 16 / (int)sizeof(T_);
+    const int64_t bx = std::max<int64_t>(1, std::min<int64_t>((cols + (int64_t)EW_BLOCK * V - 1) / ((int64_t)EW_BLOCK * V), 4096));
+    const dim3 grid((unsigned)bx, (unsigned)std::min<int64_t>(rows, 4096));
+    hipLaunchKernelGGL((ingest_rows_kernel<T_>), grid, dim3(EW_BLOCK), 0, st, src, pitch, rows, cols, dst);
+  } else if (regime == INGEST_TRANSPOSE) {
+    const int64_t tiles = ((T + INGEST_TILE - 1) / INGEST_TILE) * ((N + INGEST_TILE - 1) / INGEST_TILE);
+    hipLaunchKernelGGL((ingest_transpose_kernel<T_>), dim3((unsigned)std::min<int64_t>(tiles, (int64_t)1 << 20)), dim3(256), 0, st, src,
+                       stride_n, T, N, dst);
+  } else {
+    const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>((N + EW_BLOCK - 1) / EW_BLOCK, 4096)),
+                    (unsigned)std::min<int64_t>(T, 4096));
+    hipLaunchKernelGGL((ingest_gather_kernel<T_>), grid, dim3(EW_BLOCK), 0, st, src, stride_t, stride_n, T, N, dst);
+  }
+}
+
 // out[t][:] = in[idx[t]][:]   (row resampling of a rows x cols matrix)
 template <typename T>
 __global__ void gather_rows_kernel(const T* __restrict__ in, T* __restrict__ out, const int64_t* __restrict__ idx, int rows,

@@ -190,6 +190,21 @@ void check_side(const char* what, int side) {
   XMCA_CHECK(side == 0 || side == 1, XMCA_ERR_INVALID, std::string(what) + ": side must be 0 or 1");
 }
 
+// a caller's device pointer (xmca_set_field_strided, the XMCA_DEVICE outputs): device memory of the handle's GPU
+void check_device_pointer(xmca_handle* h, const char* what, const void* p) {
+  hipPointerAttribute_t a;
+  const hipError_t e = hipPointerGetAttributes(&a, p);
+  if (e != hipSuccess) (void)hipGetLastError();
+  XMCA_CHECK(e == hipSuccess && a.type == hipMemoryTypeDevice && a.device == h->device, XMCA_ERR_INVALID,
+             std::string(what) + ": not a pointer to memory of the handle's device");
+}
+
+// the memory space of an output: XMCA_HOST, or XMCA_DEVICE with a pointer the handle's GPU can write
+void check_out_location(xmca_handle* h, const char* what, int location, const void* out) {
+  XMCA_CHECK(location == XMCA_HOST || location == XMCA_DEVICE, XMCA_ERR_INVALID, std::string(what) + ": the location must be XMCA_HOST or XMCA_DEVICE");
+  if (location == XMCA_DEVICE) check_device_pointer(h, what, out);
+}
+
 // rotation of every replicate (xmca_rule_n, xmca_bootstrap_runs*); `detail`: the entry point's own wording of the requirement
 void check_rotation_args(const char* what, const char* detail, int rotated, int p, int power) {
   XMCA_CHECK(!rotated || (p >= 2 && power >= 1), XMCA_ERR_INVALID, std::string(what) + ": " + detail);
@@ -428,7 +443,7 @@ void get_eofs_impl(xmca_handle* h, int side, const double* W, int64_t m, int64_t
 // mask.  The compact values are read twice, the output is written once.
 template <typename TO>
 void get_maps_impl(xmca_handle* h, int side, const double* W, int64_t m, int64_t q, bool w_cplx, const double* col_factor, bool f_cplx,
-                   const int64_t* keep_idx, int64_t N_full, int kind, int scaling, void* out, double* stat_out) {
+                   const int64_t* keep_idx, int64_t N_full, int kind, int scaling, void* out, double* stat_out, bool out_dev) {
   const int64_t N = h->res.ldv[side];
   const bool c_cplx = h->res.cplx || (W && w_cplx);
   const bool o_cplx = kind == MAP_EOF && (c_cplx || (col_factor && f_cplx));
@@ -465,12 +480,12 @@ void get_maps_impl(xmca_handle* h, int side, const double* W, int64_t m, int64_t
   const size_t total = (size_t)N_full * q;
   hipLaunchKernelGGL((map_finish_kernel<TO>), ew_grid((int64_t)total), dim3(EW_BLOCK), 0, h->st, tmp.get(), (int)c_cplx,
                      keep_idx ? row_of.get() : nullptr, N_full, (int)q, f.r, f.i, scaling != XMCA_SCALE_NONE ? div.get() : nullptr, kind,
-                     (int)o_cplx, fin.ensure(total * (o_cplx ? 2 : 1)));
+                     (int)o_cplx, out_dev ? static_cast<TO*>(out) : fin.ensure(total * (o_cplx ? 2 : 1)));     // (a device destination is final)
   XMCA_HIP(hipGetLastError());
   h->tm.end();
   if (stat_out && scaling != XMCA_SCALE_NONE)
     XMCA_HIP(hipMemcpyAsync(stat_out, div.get(), sizeof(double) * q, hipMemcpyDeviceToHost, h->st));
-  XMCA_HIP(hipMemcpyAsync(out, fin.get(), sizeof(TO) * total * (o_cplx ? 2 : 1), hipMemcpyDeviceToHost, h->st));
+  if (!out_dev) XMCA_HIP(hipMemcpyAsync(out, fin.get(), sizeof(TO) * total * (o_cplx ? 2 : 1), hipMemcpyDeviceToHost, h->st));
   XMCA_HIP(hipStreamSynchronize(h->st));
 }
 
@@ -613,7 +628,8 @@ void vec_operand(xmca_handle* h, int side, const void* V, int64_t N, int64_t m, 
 // out (T_new x q) = (((X[:, keep] - mean) / std * weight) V[:, :m]) W   (see xmca_predict, xmca_predict_weighted).  TI: element type
 // of the data (ingest arithmetic), TP: element type of the vectors (product).
 template <typename TI, typename TP>
-void predict_impl(xmca_handle* h, int side, const TI* X, int64_t T, int64_t N_full, const int64_t* keep_idx, int64_t N, const TI* mean,
+void predict_impl(xmca_handle* h, int side, const TI* X, bool x_dev, int64_t stride_t, int64_t stride_n, int64_t T, int64_t N_full,
+                  const int64_t* keep_idx, int64_t N, const TI* mean,
                   const TI* stdv, const double* weight, const void* V, bool v_cplx, const double* W, int64_t m, int64_t q, bool w_cplx,
                   double* out, int* out_cplx) {
   VecOperand<TP> vo;
@@ -634,7 +650,10 @@ void predict_impl(xmca_handle* h, int side, const TI* X, int64_t T, int64_t N_fu
   DevBuf<TI> raw;
   DevBuf<TP> xs;
   DevBuf<double> yr, yi, o_r, o_i, packed;
-  raw.ensure((size_t)rows * N_full);
+  // new data on the device is not staged: rows that are contiguous are read in place with their pitch, any other view is made
+  // contiguous block by block (ingest_strided)
+  const bool in_place = x_dev && (stride_n == 1 || N_full == 1);
+  if (!in_place) raw.ensure((size_t)rows * N_full);
   xs.ensure((size_t)rows * N);
   yr.ensure((size_t)rows * m);
   if (vc) yi.ensure((size_t)rows * m);
@@ -642,9 +661,11 @@ void predict_impl(xmca_handle* h, int side, const TI* X, int64_t T, int64_t N_fu
   if (oc) { o_i.ensure((size_t)rows * q); packed.ensure((size_t)rows * q * 2); }
   for (int64_t t0 = 0; t0 < T; t0 += rows) {
     const int tb = (int)std::min<int64_t>(rows, T - t0);
-    XMCA_HIP(hipMemcpyAsync(raw.get(), X + t0 * N_full, sizeof(TI) * tb * N_full, hipMemcpyHostToDevice, h->st));
+    if (!x_dev) XMCA_HIP(hipMemcpyAsync(raw.get(), X + t0 * N_full, sizeof(TI) * tb * N_full, hipMemcpyHostToDevice, h->st));
     h->tm.begin("predict_ingest");
-    hipLaunchKernelGGL((ingest_columns_kernel<TI, TP>), row_col_grid(tb, N), dim3(EW_BLOCK), 0, h->st, raw.get(), N_full,
+    if (x_dev && !in_place) ingest_strided<TI>(h->st, X + t0 * stride_t, tb, N_full, stride_t, stride_n, raw.get());
+    hipLaunchKernelGGL((ingest_columns_kernel<TI, TP>), row_col_grid(tb, N), dim3(EW_BLOCK), 0, h->st,
+                       in_place ? X + t0 * stride_t : raw.get(), in_place ? stride_t : N_full,
                        keep_idx ? idx.get() : nullptr, tb, N, mu.get(), stdv ? sd.get() : nullptr, weight ? wt.get() : nullptr,
                        xs.get());
     XMCA_HIP(hipGetLastError());
@@ -687,7 +708,7 @@ void predict_impl(xmca_handle* h, int side, const TI* X, int64_t T, int64_t N_fu
 template <typename TP>
 void reconstruct_impl(xmca_handle* h, int side, const double* B, int64_t T, int64_t m, bool b_cplx, const void* V, bool v_cplx,
                       const int64_t* keep_idx, int64_t N, int64_t N_full, const double* mean, const double* stdv,
-                      const double* inv_weight, double* out) {
+                      const double* inv_weight, double* out, bool out_dev) {
   VecOperand<TP> vo;
   if (m > 0) vec_operand<TP>(h, side, V, N, m, v_cplx, vo);
   const bool both_cplx = b_cplx && vo.i != nullptr;        // Re((Br + i Bi)(Vr - i Vi)^T) = Br Vr^T + Bi Vi^T
@@ -707,7 +728,7 @@ void reconstruct_impl(xmca_handle* h, int side, const double* B, int64_t T, int6
   const int64_t rows = transform_rows(T, (N + N_full) * (int64_t)sizeof(double));
   DevBuf<double> C, full;
   C.ensure((size_t)rows * N);
-  full.ensure((size_t)rows * N_full);
+  if (!out_dev) full.ensure((size_t)rows * N_full);
   for (int64_t t0 = 0; t0 < T; t0 += rows) {
     const int tb = (int)std::min<int64_t>(rows, T - t0);
     h->tm.begin("reconstruct_gemm");
@@ -727,12 +748,15 @@ void reconstruct_impl(xmca_handle* h, int side, const double* B, int64_t T, int6
     h->tm.begin("reconstruct_epilogue");
     hipLaunchKernelGGL(reconstruct_epilogue_kernel, row_col_grid(tb, N_full), dim3(EW_BLOCK), 0, h->st, C.get(), N,
                        keep_idx ? col_of.get() : nullptr, tb, N_full, inv_weight ? iw.get() : nullptr, stdv ? sd.get() : nullptr,
-                       mean ? mu.get() : nullptr, full.get());
+                       mean ? mu.get() : nullptr, out_dev ? out + t0 * N_full : full.get());     // (a device destination is final)
     XMCA_HIP(hipGetLastError());
     h->tm.end();
-    XMCA_HIP(hipMemcpyAsync(out + t0 * N_full, full.get(), sizeof(double) * tb * N_full, hipMemcpyDeviceToHost, h->st));
-    XMCA_HIP(hipStreamSynchronize(h->st));
+    if (!out_dev) {
+      XMCA_HIP(hipMemcpyAsync(out + t0 * N_full, full.get(), sizeof(double) * tb * N_full, hipMemcpyDeviceToHost, h->st));
+      XMCA_HIP(hipStreamSynchronize(h->st));
+    }
   }
+  XMCA_HIP(hipStreamSynchronize(h->st));
 }
 
 // checks shared by xmca_predict / xmca_reconstruct: the vectors (resident or host), the kept columns
@@ -807,7 +831,7 @@ void pearson_pvalues_impl(xmca_handle* h, const double* r, int64_t count, int64_
 // r (TR) and p (float64) of one field in their final N_full x m layout  (see xmca_correlation_maps)
 template <typename TI, typename TR>
 void correlation_maps_impl(xmca_handle* h, int side, const double* Y, int64_t T, int64_t m, const int64_t* keep_idx, int64_t N_full,
-                           TR* r_out, double* p_out) {
+                           TR* r_out, double* p_out, bool out_dev) {
   DevBuf<double> C, pd;
   DevBuf<TR> rd;
   DevBuf<int64_t> row_of;
@@ -822,12 +846,14 @@ void correlation_maps_impl(xmca_handle* h, int side, const double* Y, int64_t T,
   const size_t total = (size_t)N_full * m;
   h->tm.begin("correlation_maps");
   hipLaunchKernelGGL((correlation_maps_kernel<TR>), ew_grid((int64_t)total), dim3(EW_BLOCK), 0, h->st, C.get(),
-                     keep_idx ? row_of.get() : nullptr, N_full, (int)m, 0.5 * (double)T - 1.0, pvalue_log_norm(T), rd.ensure(total),
-                     pd.ensure(total));
+                     keep_idx ? row_of.get() : nullptr, N_full, (int)m, 0.5 * (double)T - 1.0, pvalue_log_norm(T),
+                     out_dev ? r_out : rd.ensure(total), out_dev ? p_out : pd.ensure(total));     // (device destinations are final)
   XMCA_HIP(hipGetLastError());
   h->tm.end();
-  XMCA_HIP(hipMemcpyAsync(r_out, rd.get(), sizeof(TR) * total, hipMemcpyDeviceToHost, h->st));
-  XMCA_HIP(hipMemcpyAsync(p_out, pd.get(), sizeof(double) * total, hipMemcpyDeviceToHost, h->st));
+  if (!out_dev) {
+    XMCA_HIP(hipMemcpyAsync(r_out, rd.get(), sizeof(TR) * total, hipMemcpyDeviceToHost, h->st));
+    XMCA_HIP(hipMemcpyAsync(p_out, pd.get(), sizeof(double) * total, hipMemcpyDeviceToHost, h->st));
+  }
   XMCA_HIP(hipStreamSynchronize(h->st));
 }
 
@@ -1300,8 +1326,8 @@ static void bench_gemm_impl(xmca_handle* h, int M, int N, int K, int a_kfast, in
 
 extern "C" {
 
-int xmca_set_field(xmca_handle* h, int side, const void* re, const void* im, int64_t T, int64_t N, int dtype, int location) {
-  API_BEGIN(h)
+// checks and state changes shared by xmca_set_field and xmca_set_field_strided: left before right, one dtype, one T
+static void begin_set_field(xmca_handle* h, int side, const void* re, int64_t T, int64_t N, int dtype) {
   check_side("set_field", side);
   XMCA_CHECK(re && T >= 2 && N >= 1, XMCA_ERR_INVALID, "set_field: need a T x N field with T >= 2, N >= 1");
   XMCA_CHECK(dtype == XMCA_F32 || dtype == XMCA_F64, XMCA_ERR_INVALID, "set_field: dtype must be float32 or float64");
@@ -1312,10 +1338,44 @@ int xmca_set_field(xmca_handle* h, int side, const void* re, const void* im, int
     XMCA_CHECK(dtype == h->dtype, XMCA_ERR_INVALID, "set_field: both fields must have the same dtype");
     XMCA_CHECK(T == resident_T(h), XMCA_ERR_INVALID, "set_field: time dimensions of the fields differ");
   }
-  with_dtype(dtype, [&](auto t) { set_field_impl<decltype(t)>(h, side, re, im, T, N, location); });
+}
+static void end_set_field(xmca_handle* h, int side) {
   h->field_set[side] = true;
   h->solved = false;
   if (side == 0) h->op_pending = false;
+}
+
+int xmca_set_field(xmca_handle* h, int side, const void* re, const void* im, int64_t T, int64_t N, int dtype, int location) {
+  API_BEGIN(h)
+  begin_set_field(h, side, re, T, N, dtype);
+  with_dtype(dtype, [&](auto t) { set_field_impl<decltype(t)>(h, side, re, im, T, N, location); });
+  end_set_field(h, side);
+  API_END(h)
+}
+
+int xmca_ingest_regime(int64_t T, int64_t N, int64_t stride_t, int64_t stride_n) {
+  if (T < 1 || N < 1 || stride_t < 0 || stride_n < 0) return XMCA_ERR_INVALID;
+  return ingest_regime(T, N, stride_t, stride_n);
+}
+
+int xmca_set_field_strided(xmca_handle* h, int side, const void* re, int64_t T, int64_t N, int64_t stride_t, int64_t stride_n, int dtype) {
+  API_BEGIN(h)
+  begin_set_field(h, side, re, T, N, dtype);
+  XMCA_CHECK(stride_t >= 0 && stride_n >= 0, XMCA_ERR_INVALID, "set_field_strided: strides must not be negative");
+  check_device_pointer(h, "set_field_strided", re);
+  with_dtype(dtype, [&](auto t) {
+    using TI = decltype(t);
+    FieldData<TI>& f = typed<TI>(h).f[side];
+    f.T = T; f.N = N;
+    f.has_im = false;
+    f.ext_re = nullptr; f.ext_im = nullptr;
+    h->tm.begin("ingest_strided");
+    ingest_strided<TI>(h->st, static_cast<const TI*>(re), T, N, stride_t, stride_n, f.re.ensure((size_t)T * N));
+    XMCA_HIP(hipGetLastError());
+    h->tm.end();
+    XMCA_HIP(hipStreamSynchronize(h->st));        // (the caller's memory is not referenced after the call)
+  });
+  end_set_field(h, side);
   API_END(h)
 }
 
@@ -1428,12 +1488,20 @@ int xmca_get_eofs(xmca_handle* h, int side, const double* W, int64_t m, int64_t 
 int xmca_get_maps(xmca_handle* h, int side, const double* W, int64_t m, int64_t q, int w_is_complex, const double* col_factor,
                   int factor_is_complex, const int64_t* keep_idx, int64_t N_full, int kind, int scaling, void* out, int dtype,
                   double* stat_out) {
+  return xmca_get_maps_to(h, side, W, m, q, w_is_complex, col_factor, factor_is_complex, keep_idx, N_full, kind, scaling, out, dtype,
+                          stat_out, XMCA_HOST);
+}
+
+int xmca_get_maps_to(xmca_handle* h, int side, const double* W, int64_t m, int64_t q, int w_is_complex, const double* col_factor,
+                     int factor_is_complex, const int64_t* keep_idx, int64_t N_full, int kind, int scaling, void* out, int dtype,
+                     double* stat_out, int out_location) {
   API_BEGIN(h)
   XMCA_CHECK(h->solved, XMCA_ERR_STATE, "maps requested before solve");
   check_side("get_maps", side);
   XMCA_CHECK(out && q >= 1 && q <= INT32_MAX && m >= 1 && m <= h->res.n_vec && (W || q == m) && h->res.ldv[side] > 0, XMCA_ERR_INVALID,
              "get_maps: more modes requested than were back-projected, or a bad mixing matrix");
   XMCA_CHECK(dtype == XMCA_F32 || dtype == XMCA_F64, XMCA_ERR_INVALID, "get_maps: dtype must be XMCA_F32 or XMCA_F64");
+  check_out_location(h, "get_maps", out_location, out);
   XMCA_CHECK((kind == XMCA_MAP_EOF && (scaling == XMCA_SCALE_NONE || scaling == XMCA_SCALE_MAX || scaling == XMCA_SCALE_STD)) ||
                  (kind == XMCA_MAP_AMPLITUDE && (scaling == XMCA_SCALE_NONE || scaling == XMCA_SCALE_MAX)) ||
                  (kind == XMCA_MAP_PHASE && scaling == XMCA_SCALE_NONE),
@@ -1448,7 +1516,7 @@ int xmca_get_maps(xmca_handle* h, int side, const double* W, int64_t m, int64_t 
   }
   with_dtype(dtype, [&](auto t) {
     get_maps_impl<decltype(t)>(h, side, W, m, q, w_is_complex != 0, col_factor, factor_is_complex != 0, keep_idx, N_full, kind, scaling,
-                               out, stat_out);
+                               out, stat_out, out_location == XMCA_DEVICE);
   });
   API_END(h)
 }
@@ -1476,18 +1544,34 @@ int xmca_predict(xmca_handle* h, int side, const void* X, int64_t T_new, int64_t
 int xmca_predict_weighted(xmca_handle* h, int side, const void* X, int64_t T_new, int64_t N_full, int dtype, const int64_t* keep_idx,
                           int64_t N_keep, const void* mean, const void* std, const void* V, int v_is_complex, const double* W, int64_t m,
                           int64_t q, int w_is_complex, double* out, int* out_is_complex, const double* weight) {
+  return xmca_predict_strided(h, side, X, T_new, N_full, N_full, 1, XMCA_HOST, dtype, keep_idx, N_keep, mean, std, V, v_is_complex, W, m, q,
+                              w_is_complex, out, out_is_complex, weight);
+}
+
+int xmca_predict_strided(xmca_handle* h, int side, const void* X, int64_t T_new, int64_t N_full, int64_t stride_t, int64_t stride_n,
+                         int x_location, int dtype, const int64_t* keep_idx, int64_t N_keep, const void* mean, const void* std,
+                         const void* V, int v_is_complex, const double* W, int64_t m, int64_t q, int w_is_complex, double* out,
+                         int* out_is_complex, const double* weight) {
   API_BEGIN(h)
   check_transform(h, "predict", side, V, m, keep_idx, N_keep, N_full);
   XMCA_CHECK(X && mean && W && out && out_is_complex && T_new >= 1 && m >= 1 && q >= 1 && q <= INT32_MAX, XMCA_ERR_INVALID,
              "predict: need new data, means, an m x q mix (m, q >= 1) and an output");
   XMCA_CHECK(dtype == XMCA_F32 || dtype == XMCA_F64, XMCA_ERR_INVALID, "predict: dtype must be XMCA_F32 or XMCA_F64");
+  XMCA_CHECK(x_location == XMCA_HOST || x_location == XMCA_DEVICE, XMCA_ERR_INVALID, "predict: the location must be XMCA_HOST or XMCA_DEVICE");
+  if (x_location == XMCA_DEVICE) {
+    XMCA_CHECK(stride_t >= 0 && stride_n >= 0, XMCA_ERR_INVALID, "predict: strides must not be negative");
+    check_device_pointer(h, "predict", X);
+  } else {
+    XMCA_CHECK(stride_t == N_full && stride_n == 1, XMCA_ERR_INVALID, "predict: host data must be contiguous rows");
+  }
   const bool vt32 = !V && h->res.vt_f32[side];
   const bool vc = v_is_complex != 0, wc = w_is_complex != 0;
   // 2 x 2: the data's element type TI (the ingest arithmetic) x the resident vectors' element type TP (the product)
   with_dtype(dtype, [&](auto ti) {
     using TI = decltype(ti);
     with_dtype(vt32 ? XMCA_F32 : XMCA_F64, [&](auto tp) {
-      predict_impl<TI, decltype(tp)>(h, side, static_cast<const TI*>(X), T_new, N_full, keep_idx, N_keep, static_cast<const TI*>(mean),
+      predict_impl<TI, decltype(tp)>(h, side, static_cast<const TI*>(X), x_location == XMCA_DEVICE, stride_t, stride_n, T_new, N_full,
+                                     keep_idx, N_keep, static_cast<const TI*>(mean),
                                      static_cast<const TI*>(std), weight, V, vc, W, m, q, wc, out, out_is_complex);
     });
   });
@@ -1502,13 +1586,21 @@ int xmca_reconstruct(xmca_handle* h, int side, const double* B, int64_t T, int64
 int xmca_reconstruct_weighted(xmca_handle* h, int side, const double* B, int64_t T, int64_t m, int b_is_complex, const void* V,
                               int v_is_complex, const int64_t* keep_idx, int64_t N_keep, int64_t N_full, const double* mean,
                               const double* std, double* out, const double* inv_weight) {
+  return xmca_reconstruct_to(h, side, B, T, m, b_is_complex, V, v_is_complex, keep_idx, N_keep, N_full, mean, std, out, inv_weight,
+                             XMCA_HOST);
+}
+
+int xmca_reconstruct_to(xmca_handle* h, int side, const double* B, int64_t T, int64_t m, int b_is_complex, const void* V,
+                        int v_is_complex, const int64_t* keep_idx, int64_t N_keep, int64_t N_full, const double* mean,
+                        const double* std, double* out, const double* inv_weight, int out_location) {
   API_BEGIN(h)
   check_transform(h, "reconstruct", side, V, m, keep_idx, N_keep, N_full);
   XMCA_CHECK(out && T >= 1 && (B || m == 0), XMCA_ERR_INVALID, "reconstruct: need a T x m coefficient matrix and an output");
+  check_out_location(h, "reconstruct", out_location, out);
   // the product runs in the element type of the resident vectors it reads (float64 for host vectors)
   with_dtype(m > 0 && !V && h->res.vt_f32[side] ? XMCA_F32 : XMCA_F64, [&](auto tp) {
     reconstruct_impl<decltype(tp)>(h, side, B, T, m, b_is_complex != 0, V, v_is_complex != 0, keep_idx, N_keep, N_full, mean, std, inv_weight,
-                                   out);
+                                   out, out_location == XMCA_DEVICE);
   });
   API_END(h)
 }
@@ -1618,6 +1710,11 @@ int xmca_pearson_pvalues(xmca_handle* h, const double* r, int64_t count, int64_t
 
 int xmca_correlation_maps(xmca_handle* h, int side, const double* Y, int64_t T, int64_t m, const int64_t* keep_idx, int64_t N_full,
                           int r_dtype, void* r_out, double* p_out) {
+  return xmca_correlation_maps_to(h, side, Y, T, m, keep_idx, N_full, r_dtype, r_out, p_out, XMCA_HOST);
+}
+
+int xmca_correlation_maps_to(xmca_handle* h, int side, const double* Y, int64_t T, int64_t m, const int64_t* keep_idx, int64_t N_full,
+                             int r_dtype, void* r_out, double* p_out, int out_location) {
   API_BEGIN(h)
   check_side("correlation_maps", side);
   XMCA_CHECK(h->field_set[side], XMCA_ERR_STATE, "correlation_maps: no field resident for this side");
@@ -1625,6 +1722,8 @@ int xmca_correlation_maps(xmca_handle* h, int side, const double* Y, int64_t T, 
   XMCA_CHECK(T >= 3, XMCA_ERR_INVALID, "correlation_maps: the null distribution needs T >= 3");
   XMCA_CHECK(T <= PVALUE_MAX_OBS, XMCA_ERR_UNSUPPORTED, "correlation_maps: T above " + std::to_string(PVALUE_MAX_OBS));
   XMCA_CHECK(r_dtype == XMCA_F32 || r_dtype == XMCA_F64, XMCA_ERR_INVALID, "correlation_maps: r_dtype must be XMCA_F32 or XMCA_F64");
+  check_out_location(h, "correlation_maps", out_location, r_out);
+  check_out_location(h, "correlation_maps", out_location, p_out);
   const int64_t N = resident_N(h, side);
   XMCA_CHECK(N_full >= N && N_full <= INT32_MAX && (keep_idx || N_full == N), XMCA_ERR_INVALID,
              "correlation_maps: N_full must be the field's " + std::to_string(N) + " columns, or more with keep_idx");
@@ -1635,7 +1734,8 @@ int xmca_correlation_maps(xmca_handle* h, int side, const double* Y, int64_t T, 
   }
   with_dtype(h->dtype, [&](auto t) {
     with_dtype(r_dtype, [&](auto tr) {
-      correlation_maps_impl<decltype(t), decltype(tr)>(h, side, Y, T, m, keep_idx, N_full, static_cast<decltype(tr)*>(r_out), p_out);
+      correlation_maps_impl<decltype(t), decltype(tr)>(h, side, Y, T, m, keep_idx, N_full, static_cast<decltype(tr)*>(r_out), p_out,
+                                                       out_location == XMCA_DEVICE);
     });
   });
   API_END(h)
