@@ -82,6 +82,24 @@ def test_eigh_matches_lapack(hip, n, cplx):
     assert hip.last_eigh_info["sweeps"] <= 25
 
 
+@pytest.mark.parametrize("n,cplx,tile,slots", [(20, False, 32, 1), (100, False, 64, 2), (150, False, 64, 3), (128, False, 64, 2),
+                                                (50, True, 32, 2), (130, True, 32, 5)])
+def test_eigh_values_only_takes_the_jacobi_sweeps(hip, n, cplx, tile, slots):
+    """Below 192 rows `vectors=False` stays on the block Jacobi sweeps, launched without eigenvector planes: one tile,
+    the unfused pair (2 slots; n = 128 has no padding, so no Frobenius pass) and the fused rounds (3 and 5 slots)."""
+    rng = np.random.default_rng(n)
+    G = _herm(rng, n, 3 * n + 10, cplx)
+    lam, U = hip.eigh(G, vectors=False)
+    assert U is None
+    info = hip.last_eigh_info
+    assert info["tridiag"] == 0 and info["tile"] == tile and info["slots"] == slots, info
+    assert np.all(np.diff(lam) <= 0)
+    ref = np.linalg.eigvalsh(G)[::-1]
+    err = float(np.max(np.abs(lam - ref)))
+    print("values-only Jacobi n=%d cplx=%d: max |lam - eigvalsh| / lam_max = %.3e" % (n, cplx, err / ref[0]))
+    assert err < 1e-11 * ref[0], info
+
+
 def test_eigh_rank_deficient_complex(hip):
     """analytic signals have rank T/2: the null space must not stall the sweeps."""
     from scipy.signal import hilbert

@@ -16,69 +16,22 @@
 //   after 2S-1 rounds every pair of half-blocks has met once (= one sweep); jacobi_offmax_kernel decides when to stop.
 //
 // Z accumulates Q^H: at the end row i of Z is the conjugated eigenvector i.
+// The kernels are in jacobi_kernels.h; this file holds the workspace, the host driver of the sweeps (jacobi_evd) and the
+// entry point that chooses between them and the tridiagonal route (hermitian_evd).
 // Replaces the LAPACK *gesdd calls of xmca/array.py:479 and :570.
 #pragma once
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <type_traits>
 
 #include "common.h"
 #include "gemm.h"
 #include "cholesky.h"
 #include "tridiag.h"
 #include "tridiag_vec.h"
+#include "jacobi_kernels.h"
 
 namespace xmca {
-
-__host__ __device__ inline int jacobi_dest_block(int p, int h, int S) {
-  // half h (0 = top, 1 = bottom) of slot p moves to this half-block index for the next round
-  if (S == 1) return h;
-  if (h == 0) {
-    if (p == 0) return 0;
-    if (p == S - 1) return 2 * (S - 1) + 1;
-    return 2 * (p + 1);
-  }
-  if (p == 0) return 2;
-  return 2 * (p - 1) + 1;
-}
-
-// scal[3] += sum of |a_ij|^2 (the Frobenius norm bounds every eigenvalue: the padding has to sit below all of them)
-__global__ void jacobi_frobenius_kernel(const double* __restrict__ Ar, const double* __restrict__ Ai, int n, int64_t lda, double* scal) {
-  double s = 0.0;
-  for (int r = blockIdx.x; r < n; r += gridDim.x)
-    for (int c = threadIdx.x; c < n; c += blockDim.x) {
-      const double a = Ar[(int64_t)r * lda + c], b = Ai ? Ai[(int64_t)r * lda + c] : 0.0;
-      s += a * a + b * b;
-    }
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-  if ((threadIdx.x & 63) == 0) atomicAdd(scal + 3, s);
-}
-
-// scal[0] = scale of the working matrix (max |diag|), scal[1] = absolute rotation floor (floor_rel * scale), scal[2] =
-// diagonal value of the padding (below every eigenvalue; from scal[3] = squared Frobenius norm), scal[4] = factor applied to
-// the input when the working copy is made: 1, or 1 / max |diag| for the single-precision sweeps (normalise != 0), whose
-// working matrix then has scale 1
-__global__ void jacobi_init_scale_kernel(const double* __restrict__ Ar, int n, int64_t lda, double floor_rel, int normalise, double* scal) {
-  __shared__ double red[256];
-  double m = 0.0;
-  for (int i = threadIdx.x; i < n; i += blockDim.x) m = fmax(m, fabs(Ar[(int64_t)i * lda + i]));
-  red[threadIdx.x] = m;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) red[threadIdx.x] = fmax(red[threadIdx.x], red[threadIdx.x + s]);
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    double g = red[0];
-    if (!(g > 0.0)) g = 1.0;
-    const double f = normalise ? 1.0 / g : 1.0;
-    scal[0] = g * f;
-    scal[1] = floor_rel * g * f;   // rotations below this absolute size are rounding noise of the null space
-    scal[2] = -2.0 * fmax(sqrt(scal[3]) * f, g * f);
-    scal[4] = f;
-  }
-}
 
 struct EvdInfo {
   int sweeps = 0;
@@ -90,60 +43,302 @@ struct EvdInfo {
   int tridiag = 0;        // 1: solved by reduction to tridiagonal form (tridiag.h), no Jacobi sweeps
 };
 
-
-// knobs of one eigensolver run (hermitian_evd_impl)
-struct EvdParams {
-  double tol = 1e-10;          // stop when the largest off-diagonal entry a sweep leaves behind is below tol * scale
-  int max_sweeps = 50;
-  double stall = 0.0;          // > 0: also stop when a sweep (from the third on) leaves more than stall * (previous) behind
-  const double* Z0r = nullptr; // start basis instead of the identity (n x n planes, row i = i-th basis vector, conjugated)
-  const double* Z0i = nullptr;
-  int64_t ldz0 = 0;
-  bool no_lr = false;          // never insert the Cholesky LR step
-};
-
-namespace jac64 {
-using jreal = double;
-using jacc_t = d4_t;
-#include "jacobi_impl.inc"
-}  // namespace jac64
-
 struct EvdWorkspace {
-  jac64::EvdWorkspaceT w64;
+  DevBuf<double> G[2][2], Z[2][2];   // [ping-pong][plane]
+  DevBuf<double> J[2][2], D[2][2];   // [round parity][plane]: rotations J_P and transformed diagonal tiles; the lookahead
+                                     // solve of round r+1 writes one parity while round r reads the other
+  DevBuf<double> diag, scal;
+  DevBuf<unsigned long long> off;    // one accumulator per sweep (ring)
+  DevBuf<int> perm;
+  DevBuf<unsigned int> work;         // one work counter per round (fused round kernel)
+  GemmWorkspace lr_gws;              // Cholesky LR step
+  DevBuf<double> lr_R[2], lr_T[2];
+  // hipEvent timing of the fused round launches (one event pair around the rounds of each sweep, read at the sweep's
+  // own host synchronisation): what bench.py's roofline of jacobi_fused_round_kernel is computed from
+  hipEvent_t ev_a = nullptr, ev_b = nullptr;
+  double round_ms = 0.0;
+  long long round_launches = 0;
   GemmWorkspace gws;             // products of the tridiagonal route's back-transformation and clean-up
   TrdWorkspace trd;              // tridiagonal route (tridiag.h)
   TrdVecWorkspace trdv;          // ... its eigenvectors (tridiag_vec.h)
   DevBuf<double> lam_tmp;
+  ~EvdWorkspace() {
+    if (ev_a) (void)hipEventDestroy(ev_a);
+    if (ev_b) (void)hipEventDestroy(ev_b);
+  }
 };
 
-// one run in one precision; tile size by problem kind (64 x 64 complex tiles do not fit the LDS of the update kernel)
-#define XMCA_EVD_RUN(NS, WS)                                                                                                   \
-  do {                                                                                                                         \
-    if (Ai) {                                                                                                                  \
-      NS::hermitian_evd_impl<true, 32>(st, WS, Ar, Ai, n, lda, lam_host, lam_dev, Zr, Zi, ldz, prm, info);                     \
-    } else {                                                                                                                   \
-      const int nt = force_tile ? force_tile : (n > 32 ? 64 : 32);                                                             \
-      if (nt == 32) NS::hermitian_evd_impl<false, 32>(st, WS, Ar, nullptr, n, lda, lam_host, lam_dev, Zr, nullptr, ldz, prm, info); \
-      else NS::hermitian_evd_impl<false, 64>(st, WS, Ar, nullptr, n, lda, lam_host, lam_dev, Zr, nullptr, ldz, prm, info);     \
-    }                                                                                                                          \
-  } while (0)
+constexpr int JAC_OFF_RING = 64;
 
-inline void hermitian_evd_f64(hipStream_t st, EvdWorkspace& ws, const double* Ar, const double* Ai, int n, int64_t lda,
-                              std::vector<double>& lam_host, double* lam_dev, double* Zr, double* Zi, int64_t ldz,
-                              const EvdParams& prm, EvdInfo* info, int force_tile) {
-  XMCA_EVD_RUN(jac64, ws.w64);
+// The block Jacobi sweeps:  A = U diag(lam) U^H, lam descending.
+//   Ar/Ai : n x n row-major planes (Ai == nullptr for a real symmetric matrix), lda
+//   lam_host : n eigenvalues (descending); lam_dev (nullable) gets the same on the device
+//   Zr/Zi : n x n, row i = conj(u_i)   (ldz); Zr == nullptr: eigenvalues only
+//   tol : stop when the largest off-diagonal entry a sweep leaves behind is below tol * scale
+template <bool CPLX, int NT>
+void jacobi_evd(hipStream_t st, EvdWorkspace& ws, const double* Ar, const double* Ai, int n, int64_t lda,
+                std::vector<double>& lam_host, double* lam_dev, double* Zr, double* Zi, int64_t ldz, const double tol,
+                EvdInfo* info) {
+  int max_sweeps = 50;
+  if (const char* e = std::getenv("XMCA_JACOBI_MAX_SWEEPS")) { if (std::atoi(e) > 0) max_sweeps = std::atoi(e); }   // (tests: the non-convergence error)
+  if (info) *info = EvdInfo{};
+  const int S = std::max(ceil_div(n, NT), 1);
+  const int npad = S * NT;
+  const size_t nn = (size_t)npad * npad;
+  const bool want_z = Zr != nullptr;      // eigenvalues only: the eigenvector tiles (half of the work) are skipped
+  for (int b = 0; b < 2; ++b) {
+    ws.G[b][0].ensure(nn);
+    if (want_z) ws.Z[b][0].ensure(nn);
+    ws.J[b][0].ensure((size_t)S * NT * NT);
+    ws.D[b][0].ensure((size_t)S * NT * NT);
+    if (CPLX) {
+      ws.G[b][1].ensure(nn);
+      if (want_z) ws.Z[b][1].ensure(nn);
+      ws.J[b][1].ensure((size_t)S * NT * NT);
+      ws.D[b][1].ensure((size_t)S * NT * NT);
+    }
+  }
+  ws.diag.ensure((size_t)npad);
+  ws.scal.ensure(8);
+  ws.off.ensure(JAC_OFF_RING);
+  ws.perm.ensure((size_t)npad);
+  if (max_sweeps > JAC_OFF_RING - 2) max_sweeps = JAC_OFF_RING - 2;   // the last slot holds the post-sweep measure
+
+  XMCA_HIP(hipMemsetAsync(ws.off.get(), 0, sizeof(unsigned long long) * JAC_OFF_RING, st));
+  XMCA_HIP(hipMemsetAsync(ws.scal.get(), 0, sizeof(double) * 8, st));
+  if (npad > n)
+    hipLaunchKernelGGL(jacobi_frobenius_kernel, dim3(std::min(n, 1024)), dim3(256), 0, st, Ar, CPLX ? Ai : nullptr, n, lda, ws.scal.get());
+  hipLaunchKernelGGL(jacobi_init_scale_kernel, dim3(1), dim3(256), 0, st, Ar, n, lda, 1e-13, ws.scal.get());
+  hipLaunchKernelGGL(jacobi_init_kernel, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, st, Ar, CPLX ? Ai : nullptr, n, lda,
+                     ws.G[0][0].get(), CPLX ? ws.G[0][1].get() : nullptr, want_z ? ws.Z[0][0].get() : nullptr,
+                     (CPLX && want_z) ? ws.Z[0][1].get() : nullptr, npad, ws.scal.get());
+  XMCA_HIP(hipGetLastError());
+
+  const double tile_tol = 2e-15;
+  const bool lookahead = S >= 3;       // (the fused round with the look-ahead tile solves; the unfused form was slower)
+
+  int cur = 0;
+  const int rounds = (S == 1) ? 1 : 2 * S - 1;
+  const int zchunks = want_z ? (S + JAC_ZW - 1) / JAC_ZW : 0;   // 0: the launches simply do not contain Z tiles
+  const int n_off = S * (S - 1) / 2;
+  // Inexact inner solves: a diagonal tile is swept only ONCE per visit.  Measured on MI355X (C2, T = 2920): 1 sweep per
+  // visit needs the same 13 outer sweeps as a full tile solve at a third of the time; more were measured slower overall.
+  // Tiles are swept in full once per outer sweep (its first round), cross-block only otherwise.
+  auto is_cross = [&](int round_in_sweep) { return S > 1 && round_in_sweep != 0; };
+  auto evd = [&](hipStream_t s, int gbuf, int par, int sweep_slot, int round_in_sweep) {
+    hipLaunchKernelGGL((jacobi_tile_evd_kernel<NT, CPLX>), dim3(S), dim3(jac_threads<NT>()), 0, s, ws.G[gbuf][0].get(),
+                       CPLX ? ws.G[gbuf][1].get() : nullptr, npad, ws.J[par][0].get(), CPLX ? ws.J[par][1].get() : nullptr,
+                       ws.D[par][0].get(), CPLX ? ws.D[par][1].get() : nullptr, tile_tol, ws.scal.get(),
+                       ws.off.get() + sweep_slot, S == 1 ? 60 : 1, is_cross(round_in_sweep) ? 1 : 0);
+  };
+  auto update = [&](hipStream_t s, int par, int grid) {
+    hipLaunchKernelGGL((jacobi_update_kernel<NT, CPLX>), dim3(grid), dim3(jac_threads<NT>()), 0, s, ws.G[cur][0].get(),
+                       CPLX ? ws.G[cur][1].get() : nullptr, ws.G[cur ^ 1][0].get(), CPLX ? ws.G[cur ^ 1][1].get() : nullptr,
+                       ws.Z[cur][0].get(), CPLX ? ws.Z[cur][1].get() : nullptr, ws.Z[cur ^ 1][0].get(),
+                       CPLX ? ws.Z[cur ^ 1][1].get() : nullptr, ws.J[par][0].get(), CPLX ? ws.J[par][1].get() : nullptr,
+                       ws.D[par][0].get(), CPLX ? ws.D[par][1].get() : nullptr, S, npad);
+  };
+
+  // fused rounds: persistent workgroups (two per CU) pull items from one counter per round
+  const int zch2 = want_z ? S : 0;
+  const int fused_items = n_off + S * zch2;
+  static const int resident_wgs = [] {
+    int dev = 0, cus = 256;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    return jacobi_fused_wgs_per_cu<NT>() * cus;
+  }();
+  const int fused_grid = std::max(S, std::min(resident_wgs, S + fused_items));
+  const int n_workers = fused_grid - S;
+  // eigenvector tiles handed out statically per worker (the G tiles always are): the whole even split (a sweep of the
+  // share, 75..100 %, was flat above 90 %: profiles/r02_*)
+  const int n_static = n_workers <= 0 ? 0 : S * zch2 / n_workers;
+  // eigenvalues only: the tile solves get their CUs to themselves
+  // (measured: eigenvalues of a 2920^2 real matrix 57.5 -> 51.8 ms; with four workgroups per CU - the 32 x 32 complex
+  //  tiles - a quarter of the workers would leave and the solve gets slower, 86 -> 95 ms at n = 2501)
+  const int ncu = resident_wgs / jacobi_fused_wgs_per_cu<NT>();
+  const bool exile = !want_z && jacobi_fused_wgs_per_cu<NT>() == 2 && fused_grid == resident_wgs && S < ncu / 2;
+  const int exile_ncu = exile ? ncu : 0;
+  if (lookahead) {
+    ws.work.ensure((size_t)max_sweeps * rounds);
+    XMCA_HIP(hipMemsetAsync(ws.work.get(), 0, sizeof(unsigned int) * (size_t)max_sweeps * rounds, st));
+  }
+
+  int sweeps = 0;
+  double off = 0.0;
+  int64_t round_no = 0;
+  bool lr_applied = false;
+  bool converged = S == 1;      // (a single tile is solved to its own tolerance inside the kernel)
+  double lr_delta = 0.0, last_left = 0.0;
+  if (lookahead) evd(st, cur, 0, 0, 0);  // diagonal tiles of the very first round
+  if (lookahead && !ws.ev_a) {
+    XMCA_HIP(hipEventCreate(&ws.ev_a));
+    XMCA_HIP(hipEventCreate(&ws.ev_b));
+  }
+  for (int sweep = 0; sweep < max_sweeps; ++sweep) {
+    if (lookahead) XMCA_HIP(hipEventRecord(ws.ev_a, st));
+    for (int r = 0; r < rounds; ++r, ++round_no) {
+      const int par = (int)(round_no & 1);
+      if (!lookahead) {
+        evd(st, cur, par, sweep, r);
+        update(st, par, S + n_off + S * zchunks);
+      } else {
+        // ONE launch: tile solves of round r+1 (assembled from this round's G, J, D) + the whole update of round r.
+        // Cross code 3 = cross-block sweep, in its two-level form where there is one (64 x 64 real tiles: 85k against the
+        // flat sweep's 127k cycles per round); the 32 x 32 tiles take the flat cross sweep.
+        const int next_slot = (r == rounds - 1) ? sweep + 1 : sweep;
+        hipLaunchKernelGGL((jacobi_fused_round_kernel<NT, CPLX>), dim3(fused_grid), dim3(jac_threads<NT>()), 0, st,
+                           ws.G[cur][0].get(), CPLX ? ws.G[cur][1].get() : nullptr, ws.G[cur ^ 1][0].get(),
+                           CPLX ? ws.G[cur ^ 1][1].get() : nullptr, ws.Z[cur][0].get(), CPLX ? ws.Z[cur][1].get() : nullptr,
+                           ws.Z[cur ^ 1][0].get(), CPLX ? ws.Z[cur ^ 1][1].get() : nullptr, ws.J[par][0].get(),
+                           CPLX ? ws.J[par][1].get() : nullptr, ws.D[par][0].get(), CPLX ? ws.D[par][1].get() : nullptr,
+                           ws.J[par ^ 1][0].get(), CPLX ? ws.J[par ^ 1][1].get() : nullptr, ws.D[par ^ 1][0].get(),
+                           CPLX ? ws.D[par ^ 1][1].get() : nullptr, tile_tol, ws.scal.get(), ws.off.get() + next_slot,
+                           1, is_cross((r + 1) % rounds) ? 3 : 0, S, npad, ws.work.get() + round_no, zch2, n_static,
+                           exile_ncu);
+      }
+      cur ^= 1;
+    }
+    if (lookahead) XMCA_HIP(hipEventRecord(ws.ev_b, st));
+    XMCA_HIP(hipGetLastError());
+    // two measures per sweep: `off` = the largest entry the sweep met when it visited the tiles (also carries the NaN
+    // flag), `left` = the largest entry of the matrix it leaves behind (one 25 us pass).  Stopping on `left` saves the
+    // sweep that would only confirm convergence.
+    unsigned long long bits[2] = {0, 0};
+    if (S > 1) {
+      XMCA_HIP(hipMemsetAsync(ws.off.get() + JAC_OFF_RING - 1, 0, sizeof(unsigned long long), st));
+      if (lr_applied)
+        hipLaunchKernelGGL(jacobi_diag_kernel, dim3(ceil_div(npad, 256)), dim3(256), 0, st, ws.G[cur][0].get(), npad, ws.diag.get());
+      hipLaunchKernelGGL(jacobi_offmax_kernel, dim3(1024), dim3(256), 0, st, ws.G[cur][0].get(), CPLX ? ws.G[cur][1].get() : nullptr,
+                         npad, NT / 2, ws.scal.get(), lr_applied ? ws.diag.get() : nullptr, ws.off.get() + JAC_OFF_RING - 1);
+      XMCA_HIP(hipMemcpyAsync(&bits[1], ws.off.get() + JAC_OFF_RING - 1, sizeof(bits[1]), hipMemcpyDeviceToHost, st));
+    }
+    XMCA_HIP(hipMemcpyAsync(&bits[0], ws.off.get() + sweep, sizeof(bits[0]), hipMemcpyDeviceToHost, st));
+    XMCA_HIP(hipStreamSynchronize(st));
+    if (lookahead) {
+      float t = 0.f;
+      XMCA_HIP(hipEventElapsedTime(&t, ws.ev_a, ws.ev_b));
+      ws.round_ms += t;
+      ws.round_launches += rounds;
+    }
+    std::memcpy(&off, &bits[0], sizeof(double));
+    double left = off;
+    if (S > 1) std::memcpy(&left, &bits[1], sizeof(double));
+    last_left = left;
+    ++sweeps;
+    static const bool trace = xmca_trace("jacobi");
+    if (trace) std::fprintf(stderr, "[xmca jacobi f64] n=%d NT=%d cplx=%d sweep %d: max off/scale seen = %.3e, left = %.3e\n", n, NT, (int)CPLX, sweeps, off, left);
+    if (S == 1) break;
+    if (!(left >= tol) || !std::isfinite(left)) { off = left; converged = true; break; }   // (NaN is reported below)
+    // Cholesky LR step for graded spectra.  With eigenvalues spread evenly over many decades the couplings between
+    // large and small eigenvalues have to fall far below the small ones before those start to converge, and the
+    // sweeps only converge linearly (measured: 30 sweeps for 12 decades at n = 2920, 12 for a flat bulk).  One step of
+    // the Cholesky LR iteration, G + delta I = R^H R -> M = R R^H (= R G R^-1 + delta I), removes exactly these
+    // long-range couplings (11 sweeps for the same matrix); it costs about one sweep, so it is taken only when the
+    // diagonal after `lr_after` sweeps says the spectrum is graded.  Z <- R Z turns the accumulated rows into
+    // sqrt(lambda_i) x eigenvector, which the final gather normalises.
+    static const int lr_mode = [] { const char* e = std::getenv("XMCA_JACOBI_LR"); return e ? std::atoi(e) : 1; }();   // 0 off, 1 auto, 2 always
+    constexpr double lr_spread = 100.0;     // q10 / q90 of the sorted diagonal beyond which the spectrum counts as graded
+    constexpr int lr_after = 2;             // ... looked at after the second sweep
+    if (lookahead && lr_mode != 0 && sweeps == lr_after && !lr_applied) {
+      hipLaunchKernelGGL(jacobi_diag_kernel, dim3(ceil_div(npad, 256)), dim3(256), 0, st, ws.G[cur][0].get(), npad, ws.diag.get());
+      std::vector<double> dd(npad);
+      XMCA_HIP(hipMemcpyAsync(dd.data(), ws.diag.get(), sizeof(double) * npad, hipMemcpyDeviceToHost, st));
+      XMCA_HIP(hipStreamSynchronize(st));
+      std::vector<int> pm(npad);
+      for (int i = 0; i < npad; ++i) pm[i] = i;
+      std::stable_sort(pm.begin(), pm.end(), [&](int a, int b) { return dd[a] > dd[b]; });
+      // the padding (-scale, decoupled) must be what sorts last; a matrix with diagonal entries down there is not a
+      // Gram matrix and stays on the plain path
+      const double dmax = dd[pm[0]], dmin = dd[pm[n - 1]];
+      const double q10 = dd[pm[n / 10]], q90 = std::max(dd[pm[(int64_t)n * 9 / 10]], 1e-14 * dmax);
+      const double spread = (dmax > 0.0 && q10 > 0.0) ? q10 / q90 : 0.0;
+      if (info) info->diag_spread = spread;
+      if (dmin > -0.25 * dmax && dmax > 0.0 && std::isfinite(dmax) && (lr_mode == 2 || spread > lr_spread)) {
+        XMCA_HIP(hipMemcpyAsync(ws.perm.get(), pm.data(), sizeof(int) * npad, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(jacobi_permute_kernel, dim3(std::min(ceil_div(npad, 256), 16), npad), dim3(256), 0, st, ws.G[cur][0].get(),
+                           CPLX ? ws.G[cur][1].get() : nullptr, want_z ? ws.Z[cur][0].get() : nullptr,
+                           (CPLX && want_z) ? ws.Z[cur][1].get() : nullptr, npad, NT / 2, ws.perm.get(), ws.G[cur ^ 1][0].get(),
+                           CPLX ? ws.G[cur ^ 1][1].get() : nullptr, want_z ? ws.Z[cur ^ 1][0].get() : nullptr,
+                           (CPLX && want_z) ? ws.Z[cur ^ 1][1].get() : nullptr);
+        XMCA_HIP(hipGetLastError());
+        cur ^= 1;
+        const size_t row = sizeof(double) * (size_t)n, pitch = sizeof(double) * (size_t)npad;
+        for (int pl = 0; pl < (CPLX ? 2 : 1); ++pl) {
+          ws.lr_R[pl].ensure((size_t)n * n);
+          XMCA_HIP(hipMemcpy2DAsync(ws.lr_R[pl].get(), row, ws.G[cur][pl].get(), pitch, row, n, hipMemcpyDeviceToDevice, st));
+        }
+        double* Rr = ws.lr_R[0].get();
+        double* Ri = CPLX ? ws.lr_R[1].get() : nullptr;
+        const double rel_shift = 1e-13;
+        if (cholesky_upper(st, ws.lr_gws, Rr, Ri, n, n, rel_shift)) {
+          // M = R R^H over the leading block of G (the padding stays decoupled)
+          cgemm<double>(st, ws.lr_gws, Rr, Ri, n, true, false, Rr, Ri, n, false, true, ws.G[cur][0].get(),
+                        CPLX ? ws.G[cur][1].get() : nullptr, npad, n, n, n, 1.0, nullptr, nullptr, true);
+          if (want_z) {
+            for (int pl = 0; pl < (CPLX ? 2 : 1); ++pl) ws.lr_T[pl].ensure((size_t)n * n);
+            cgemm<double>(st, ws.lr_gws, Rr, Ri, n, true, false, ws.Z[cur][0].get(), CPLX ? ws.Z[cur][1].get() : nullptr, npad, true, false,
+                          ws.lr_T[0].get(), CPLX ? ws.lr_T[1].get() : nullptr, n, n, n, n, 1.0, nullptr, nullptr, false);
+            for (int pl = 0; pl < (CPLX ? 2 : 1); ++pl)
+              XMCA_HIP(hipMemcpy2DAsync(ws.Z[cur][pl].get(), pitch, ws.lr_T[pl].get(), row, row, n, hipMemcpyDeviceToDevice, st));
+          }
+          lr_applied = true;
+          lr_delta = rel_shift * dmax;
+          // M is positive definite with a meaningful (graded) diagonal: from here on rotations and the stopping rule are
+          // relative to sqrt(m_ii m_jj) alone - the orthogonality of the back-transformed vectors is the scaled
+          // off-diagonal part of the final M - and the absolute rotation floor is dropped
+          XMCA_HIP(hipMemsetAsync(ws.scal.get() + 1, 0, sizeof(double), st));
+        }
+        XMCA_HIP(hipStreamSynchronize(st));   // pm goes out of scope
+        evd(st, cur, (int)(round_no & 1), sweep + 1, 0);   // the lookahead solve of the next round saw the old matrix
+        if (trace) std::fprintf(stderr, "[xmca jacobi] n=%d diagonal spread q10/q90 = %.3e: Cholesky LR step %s\n", n, spread, lr_applied ? "taken" : "failed (not positive definite)");
+      } else if (trace) {
+        std::fprintf(stderr, "[xmca jacobi] n=%d diagonal spread q10/q90 = %.3e: no LR step\n", n, spread);
+      }
+    }
+  }
+  XMCA_CHECK(std::isfinite(off), XMCA_ERR_NUMERIC, "SVD failed. NaN entries may be the problem.");
+  // like LAPACK's gesdd the solver either converges or says so: an unconverged basis is never returned as singular vectors
+  if (!converged) {
+    char msg[160];
+    std::snprintf(msg, sizeof(msg), "SVD did not converge: %d Jacobi sweeps left relative off-diagonal entries of %.3e behind (limit %.1e)",
+                  sweeps, last_left, tol);
+    throw Error(XMCA_ERR_NUMERIC, msg);
+  }
+
+  // eigenvalues = diagonal; sort descending on the host, drop the padding (= the most negative entries)
+  hipLaunchKernelGGL(jacobi_diag_kernel, dim3(ceil_div(npad, 256)), dim3(256), 0, st, ws.G[cur][0].get(), npad, ws.diag.get());
+  std::vector<double> d(npad);
+  XMCA_HIP(hipMemcpyAsync(d.data(), ws.diag.get(), sizeof(double) * npad, hipMemcpyDeviceToHost, st));
+  XMCA_HIP(hipStreamSynchronize(st));
+  std::vector<int> perm(npad);
+  for (int i = 0; i < npad; ++i) perm[i] = i;
+  std::stable_sort(perm.begin(), perm.end(), [&](int a, int b) { return d[a] > d[b]; });
+  lam_host.resize(n);
+  for (int i = 0; i < n; ++i) lam_host[i] = d[perm[i]] - lr_delta;
+  XMCA_HIP(hipMemcpyAsync(ws.perm.get(), perm.data(), sizeof(int) * n, hipMemcpyHostToDevice, st));
+  if (lam_dev) XMCA_HIP(hipMemcpyAsync(lam_dev, lam_host.data(), sizeof(double) * n, hipMemcpyHostToDevice, st));
+  if (Zr && lr_applied) {
+    hipLaunchKernelGGL(jacobi_gather_normalize_kernel, dim3(n), dim3(256), 0, st, ws.Z[cur][0].get(), CPLX ? ws.Z[cur][1].get() : nullptr,
+                       npad, ws.perm.get(), n, Zr, CPLX ? Zi : nullptr, ldz);
+    XMCA_HIP(hipGetLastError());
+  } else if (Zr) {
+    hipLaunchKernelGGL(jacobi_gather_kernel, dim3(std::min(ceil_div(n, 256), 64), n), dim3(256), 0, st, ws.Z[cur][0].get(),
+                       CPLX ? ws.Z[cur][1].get() : nullptr, npad, ws.perm.get(), n, Zr, CPLX ? Zi : nullptr, ldz);
+    XMCA_HIP(hipGetLastError());
+  }
+  XMCA_HIP(hipStreamSynchronize(st));   // perm / lam_host staging buffers go out of scope
+  if (info) { info->sweeps = sweeps; info->tile = NT; info->slots = S; info->last_off = off; info->lr_step = lr_applied ? 1 : 0; }
 }
-#undef XMCA_EVD_RUN
 
-// Hermitian EVD  A = U diag(lam) U^H, lam descending (see jacobi_impl.inc for the arguments).
+// Hermitian EVD  A = U diag(lam) U^H, lam descending (see jacobi_evd for the arguments).
 //
 // Two solvers share this entry point: the reduction to tridiagonal form (tridiag.h, tridiag_vec.h: eigenproblems of 192 and
 // more without vectors, 768 and more with vectors) and the block Jacobi sweeps of this file (everything else, nearly
-// diagonal problems, and spectra with clusters the tridiagonal route hands back).  The mixed-precision variant of the
-// sweeps of rounds 1-2 (float sweeps, Newton-Schulz, double sweeps) was measured slower on MI355X and has been removed.
+// diagonal problems, and spectra with clusters the tridiagonal route hands back).
 inline void hermitian_evd(hipStream_t st, EvdWorkspace& ws, const double* Ar, const double* Ai, int n, int64_t lda,
                           std::vector<double>& lam_host, double* lam_dev, double* Zr, double* Zi, int64_t ldz,
-                          EvdInfo* info = nullptr, int force_tile = 0, bool nearly_diagonal = false) {
+                          EvdInfo* info = nullptr, bool nearly_diagonal = false) {
   // `nearly_diagonal`: the caller knows that a few Jacobi sweeps finish the problem (the weak block of solver.h, three
   // sweeps) - cheaper than any reduction, whose cost does not depend on the matrix.
   // eigenvalues only (rule_n without rotation, every n_vec = 0 solve): Householder tridiagonalisation + Sturm multisection
@@ -151,23 +346,7 @@ inline void hermitian_evd(hipStream_t st, EvdWorkspace& ws, const double* Ar, co
   const int trd_min_n = [] { const char* e = std::getenv("XMCA_TRIDIAG_MIN_N"); return e ? std::atoi(e) : 192; }();
   if (!Zr && !nearly_diagonal && trd_enabled() && n >= trd_min_n && trd_fits(n, Ai != nullptr)) {
     TrdParams P = trd_reduce(st, ws.trd, Ar, Ai, n, lda, false);
-    if (xmca_trace("trdsum")) {       // (debug: checksums of the input matrix and of (d, e) - pairs a reduction's output with its input)
-      std::vector<double> in((size_t)n * lda), d(n), e(n);
-      XMCA_HIP(hipStreamSynchronize(st));
-      XMCA_HIP(hipMemcpy(in.data(), Ar, sizeof(double) * in.size(), hipMemcpyDeviceToHost));
-      XMCA_HIP(hipMemcpy(d.data(), P.d, sizeof(double) * n, hipMemcpyDeviceToHost));
-      XMCA_HIP(hipMemcpy(e.data(), P.e, sizeof(double) * n, hipMemcpyDeviceToHost));
-      unsigned long long ci = 1469598103934665603ull, co = ci;
-      for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) { unsigned long long b; std::memcpy(&b, &in[(size_t)i * lda + j], 8); ci = (ci ^ b) * 1099511628211ull; }
-      for (int i = 0; i < n; ++i) { unsigned long long b; std::memcpy(&b, &d[i], 8); co = (co ^ b) * 1099511628211ull; if (i + 1 < n) { std::memcpy(&b, &e[i], 8); co = (co ^ b) * 1099511628211ull; } }
-      std::fprintf(stderr, "trdsum n=%d in=%016llx out=%016llx\n", n, ci, co);
-      if (const char* dir = std::getenv("XMCA_TRD_DUMP_DIR")) {      // (d, e) of every distinct (input, output) pair: scripts/de_diff.py
-        char name[512];
-        std::snprintf(name, sizeof(name), "%s/de_%016llx_%016llx.bin", dir, ci, co);
-        if (FILE* f0 = std::fopen(name, "rb")) std::fclose(f0);
-        else if (FILE* f1 = std::fopen(name, "wb")) { std::fwrite(d.data(), 8, n, f1); std::fwrite(e.data(), 8, n, f1); std::fclose(f1); }
-      }
-    }
+    if (xmca_trace("trdsum")) trd_trace_checksums(st, P, Ar, n, lda);
     trd_eigenvalues(st, ws.trd, P, lam_host, lam_dev, ws.lam_tmp);
     if (info) {
       *info = EvdInfo{};
@@ -213,12 +392,14 @@ inline void hermitian_evd(hipStream_t st, EvdWorkspace& ws, const double* Ar, co
   }
   // stop after the first sweep that leaves no off-diagonal entry above 1e-10 * max|diag| behind: with the (at least
   // fast-linear, normally quadratic) convergence the next sweep would only confirm it
-  EvdParams prm;
   // eigenvalues only (rule_n): an eigenvalue is off by sum_j |g_ij|^2 / (lam_i - lam_j), second order in what is left -
   // 1e-8 left behind bounds that by ~n 1e-16 lam_max for a spectrum without exact clusters, and the sweep that would
   // push the vectors' first-order error down is not needed (C4 surrogates: 12 -> 11 sweeps)
-  if (!Zr) prm.tol = 1e-8;
-  hermitian_evd_f64(st, ws, Ar, Ai, n, lda, lam_host, lam_dev, Zr, Zi, ldz, prm, info, force_tile);
+  const double tol = Zr ? 1e-10 : 1e-8;
+  // tile size by problem kind (64 x 64 complex tiles do not fit the LDS of the update kernel)
+  if (Ai) jacobi_evd<true, 32>(st, ws, Ar, Ai, n, lda, lam_host, lam_dev, Zr, Zi, ldz, tol, info);
+  else if (n > 32) jacobi_evd<false, 64>(st, ws, Ar, nullptr, n, lda, lam_host, lam_dev, Zr, nullptr, ldz, tol, info);
+  else jacobi_evd<false, 32>(st, ws, Ar, nullptr, n, lda, lam_host, lam_dev, Zr, nullptr, ldz, tol, info);
 }
 
 }  // namespace xmca

@@ -1194,7 +1194,7 @@ class Solver {
       cgemm<double>(st, gws, el_r, el_i, m, true, false, er_r, er_i, m, false, true, Hw.r(), Hw.i(cplx), nw, nw, nw, m,
                     1.0 / (dof * dof), nullptr, nullptr, true);
       std::vector<double> lam;
-      hermitian_evd(st, ews, Hw.r(), Hw.i(cplx), nw, nw, lam, nullptr, Z.r(), Z.i(cplx), nw, &out.evd_info[1], 0, true);   // nearly diagonal: ~3 sweeps
+      hermitian_evd(st, ews, Hw.r(), Hw.i(cplx), nw, nw, lam, nullptr, Z.r(), Z.i(cplx), nw, &out.evd_info[1], true);   // nearly diagonal: ~3 sweeps
       for (double* base : {er_r, el_r}) {
         double* im = base == er_r ? er_i : el_i;
         cgemm<double>(st, gws, Z.r(), Z.i(cplx), nw, true, false, base, im, m, true, false, Tmp.r(), Tmp.i(cplx), m, nw, m, nw, 1.0,

@@ -23,6 +23,7 @@
 #pragma once
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <vector>
 
 #include "common.h"
@@ -1760,6 +1761,27 @@ inline TrdParams trd_reduce(hipStream_t st, TrdWorkspace& ws, const double* Ar, 
     }
   }
   return P;
+}
+
+// XMCA_TRACE=trdsum (debug): checksums of the input matrix and of the (d, e) that trd_reduce made of it - pairs a
+// reduction's output with its input.  With XMCA_TRD_DUMP_DIR, (d, e) of every distinct (input, output) pair is written there
+// (scripts/de_diff.py).  Synchronises `st`.
+inline void trd_trace_checksums(hipStream_t st, const TrdParams& P, const double* Ar, int n, int64_t lda) {
+  std::vector<double> in((size_t)n * lda), d(n), e(n);
+  XMCA_HIP(hipStreamSynchronize(st));
+  XMCA_HIP(hipMemcpy(in.data(), Ar, sizeof(double) * in.size(), hipMemcpyDeviceToHost));
+  XMCA_HIP(hipMemcpy(d.data(), P.d, sizeof(double) * n, hipMemcpyDeviceToHost));
+  XMCA_HIP(hipMemcpy(e.data(), P.e, sizeof(double) * n, hipMemcpyDeviceToHost));
+  unsigned long long ci = 1469598103934665603ull, co = ci;
+  for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) { unsigned long long b; std::memcpy(&b, &in[(size_t)i * lda + j], 8); ci = (ci ^ b) * 1099511628211ull; }
+  for (int i = 0; i < n; ++i) { unsigned long long b; std::memcpy(&b, &d[i], 8); co = (co ^ b) * 1099511628211ull; if (i + 1 < n) { std::memcpy(&b, &e[i], 8); co = (co ^ b) * 1099511628211ull; } }
+  std::fprintf(stderr, "trdsum n=%d in=%016llx out=%016llx\n", n, ci, co);
+  if (const char* dir = std::getenv("XMCA_TRD_DUMP_DIR")) {
+    char name[512];
+    std::snprintf(name, sizeof(name), "%s/de_%016llx_%016llx.bin", dir, ci, co);
+    if (FILE* f0 = std::fopen(name, "rb")) std::fclose(f0);
+    else if (FILE* f1 = std::fopen(name, "wb")) { std::fwrite(d.data(), 8, n, f1); std::fwrite(e.data(), 8, n, f1); std::fclose(f1); }
+  }
 }
 
 // all eigenvalues, descending, into lam_dev (device, n doubles; may be nullptr) and lam_host.  Synchronises `st`.

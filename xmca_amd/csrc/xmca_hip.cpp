@@ -1161,9 +1161,9 @@ void run_lanes(xmca_handle* h, int lanes, F&& lane_body) {
     }
     lane->tm.ms.clear();
     lane->tm.order.clear();
-    h->ews.w64.round_ms += lane->ews.w64.round_ms; h->ews.w64.round_launches += lane->ews.w64.round_launches;
-    lane->ews.w64.round_ms = 0.0;
-    lane->ews.w64.round_launches = 0;
+    h->ews.round_ms += lane->ews.round_ms; h->ews.round_launches += lane->ews.round_launches;
+    lane->ews.round_ms = 0.0;
+    lane->ews.round_launches = 0;
     h->ews.trd.reduce_ms += lane->ews.trd.reduce_ms; h->ews.trd.reduce_calls += lane->ews.trd.reduce_calls;
     h->ews.trd.resident_calls += lane->ews.trd.resident_calls;
     lane->ews.trd.reduce_ms = 0.0; lane->ews.trd.reduce_calls = 0; lane->ews.trd.resident_calls = 0;
@@ -2013,9 +2013,9 @@ int xmca_get_timings(xmca_handle* h, char* names, int names_len, double* ms, int
     ++n;
   }
   // kernel-level entries: total duration and launch count of the eigensolver's fused round kernel (hipEvents around the
-  // rounds of every sweep, jacobi_impl.inc) - ms[] carries the count for the second name
-  const double rk_ms = h->ews.w64.round_ms;
-  const double rk_n = (double)h->ews.w64.round_launches;
+  // rounds of every sweep, jacobi.h) - ms[] carries the count for the second name
+  const double rk_ms = h->ews.round_ms;
+  const double rk_n = (double)h->ews.round_launches;
   if (rk_n > 0 && n + 2 <= max_n) {
     joined += (n ? ";" : "") + std::string("jacobi_round_kernel_ms;jacobi_round_kernel_launches");
     if (ms) { ms[n] = rk_ms; ms[n + 1] = rk_n; }
@@ -2040,8 +2040,8 @@ int xmca_reset_timings(xmca_handle* h) {
     if (h->tail.pending && h->tail.err_code == XMCA_OK) { (void)hipSetDevice(h->device); join_tail(h); }
     h->tm.reset();
   } catch (...) { return XMCA_ERR_HIP; }
-  h->ews.w64.round_ms = 0.0;
-  h->ews.w64.round_launches = 0;
+  h->ews.round_ms = 0.0;
+  h->ews.round_launches = 0;
   h->ews.trd.reduce_ms = 0.0;
   h->ews.trd.reduce_calls = 0;
   h->ews.trd.resident_calls = 0;
