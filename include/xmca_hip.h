@@ -342,7 +342,14 @@ long long xmca_persistent_giveups(void);
 /* Diagnostics of the last solve: for each of the up to three eigen-decompositions (left Gram, right Gram, kernel):
  * info[3*i + 0] = outer sweeps, info[3*i + 1] = tile size, info[3*i + 2] = pair slots (i = 0..2), then
  * info[9 + i]: bit 0 = the eigensolver inserted a Cholesky LR step (graded spectrum), bit 1 = the problem was solved by
- * reduction to tridiagonal form (csrc/tridiag.h: then no sweeps, tile and slots are 0).  n <= 12. */
+ * reduction to tridiagonal form (csrc/tridiag.h: then no sweeps, tile and slots are 0).
+ * A caller that passes n > 12 also gets (a caller passing 12 sees no change):
+ * info[12 + i] = eigenvectors the eigensolver actually formed for problem i: 0 (values only), the order of the problem, or -
+ *   one field solved with 0 < n_vec < order - the k' >= n_vec of the partial eigenvector stage;
+ * info[15] = modes whose vectors are resident (the n_vec of the solve, clipped to the rank);
+ * info[16 + s] = KiB of the device blocks that hold the vector planes of side s (what is allocated, not a product of shapes).
+ * n <= 18.  No signature changes and a library of before fills nothing beyond 12, which reads as "not reported": the ABI number
+ * stays as it is. */
 int xmca_get_solve_info(xmca_handle* h, int* info, int n);
 
 /* promax / varimax of xmca/tools/rotation.py:84-149, :15-78 on a host loading matrix L (N x p row-major,

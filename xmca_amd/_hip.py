@@ -447,10 +447,19 @@ class Handle:
         return int(rank.value)
 
     def solve_info(self):
-        info = np.zeros(12, dtype=np.int32)
-        self._check(self._lib.xmca_get_solve_info(self._h, _ptr(info), 12))
+        """Per eigenproblem of the last solve (left Gram, right Gram, kernel): sweeps / tile / slots of the Jacobi solver, whether a
+        Cholesky LR step or the tridiagonal route was taken, and `n_eigvec`, the eigenvectors actually formed - the order of the
+        problem, or the k' >= n_vec of the partial stage for a one-field `solve(n_fields, n_vec=k)`."""
+        info = np.zeros(18, dtype=np.int32)
+        self._check(self._lib.xmca_get_solve_info(self._h, _ptr(info), 18))
         return [{"sweeps": int(info[3 * i]), "tile": int(info[3 * i + 1]), "slots": int(info[3 * i + 2]), "lr_step": int(info[9 + i]) & 1,
-                 "tridiag": (int(info[9 + i]) >> 1) & 1} for i in range(3)]
+                 "tridiag": (int(info[9 + i]) >> 1) & 1, "n_eigvec": int(info[12 + i])} for i in range(3)]
+
+    def result_info(self):
+        """What the last solve left resident: `n_vec` modes, and the KiB their vector planes occupy per side."""
+        info = np.zeros(18, dtype=np.int32)
+        self._check(self._lib.xmca_get_solve_info(self._h, _ptr(info), 18))
+        return {"n_vec": int(info[15]), "vector_kib": [int(info[16]), int(info[17])]}
 
     def singular_values(self, n):
         out = np.empty(n, dtype=np.float64)

@@ -122,7 +122,8 @@ def _device_view(t, owner=None):
 
 class _LazyVectors(dict):
     """`MCA._V` after solve(): (N', rank) singular vectors per field, fetched from the device when first read.  `head`
-    fetches only the leading modes while the full array has not been asked for."""
+    fetches only the leading modes while the full array has not been asked for.  After `solve(n_modes=k)` `rank` is k: the
+    device holds no further vectors."""
 
     def __init__(self, dev, where, rank, dtype):
         super().__init__({k: None for k in where})
@@ -661,13 +662,26 @@ class MCA:
     # ------------------------------------------------------------------------------------------
     # solve (array.py:509-603) - numerical core on the device
     # ------------------------------------------------------------------------------------------
-    def solve(self, complexify=False, extend=False, period=1):
+    def solve(self, complexify=False, extend=False, period=1, n_modes=None):
         """EOF analysis / MCA: singular value decomposition of the (cross-)covariance matrix.
 
         complexify : Hilbert-transform the fields first (complex EOF/MCA).
         extend     : False, 'exp' or 'theta' - fore/back-cast before the Hilbert transform.
         period     : season length (theta) / e-folding time (exp).
+        n_modes    : None - all modes - or an integer k >= 1 (extension): the model is left as `solve()` followed by
+                     `truncate(k)` leaves it - k singular values and the vectors of k modes, the totals of the full spectrum - but
+                     the device forms, back-projects and keeps the vectors of those k modes only, and nothing is fetched to the
+                     host.  k at or above the rank is the same as None.  The values are the bits of `solve()` wherever
+                     both take the same eigensolver; a field of numerical rank far below its length sends the full
+                     `solve()` to Jacobi sweeps that the k leading vectors do not need, and the two then agree to
+                     n eps sigma_1.
         """
+        if n_modes is not None:
+            if isinstance(n_modes, (bool, np.bool_)) or not isinstance(n_modes, (int, np.integer)):
+                raise ValueError('`n_modes` must be None or an integer >= 1, not {!r}'.format(n_modes))
+            if n_modes < 1:
+                raise ValueError('`n_modes` must be >= 1, not {!r}'.format(n_modes))
+            n_modes = int(n_modes)
         store = self._fields_store
         if len(store) == 0 or (not self._store_is_raw and any(np.isnan(f).all() for f in store.values())):
             raise RuntimeError('''
@@ -701,8 +715,11 @@ class MCA:
                 self._fields = real
         self._upload_fields(dev)
 
+        # n_modes: the device is asked for that many modes' vectors only (all singular values come back in any case)
+        full_rank = min(min(f.shape) for f in self._fields_store.values())
+        n_vec = -1 if n_modes is None or n_modes >= full_rank else n_modes
         try:
-            rank = dev.solve(len(self._keys))
+            rank = dev.solve(len(self._keys), n_vec)
         except np.linalg.LinAlgError as err:                       # array.py:575-578 (the device message is the cause)
             raise np.linalg.LinAlgError('''SVD failed. NaN entries may be the problem.''') from err
 
@@ -712,7 +729,8 @@ class MCA:
         singular_values = dev.singular_values(rank).astype(real_dtype, copy=False)
         # the vectors stay on the device until something reads them (233 MB at C2; pcs / eofs / rotate of a few modes
         # fetch just those modes); anything that would invalidate them on the handle makes this model fetch them first
-        self._V = _LazyVectors(dev, {k: (side, self._fields_store[k].shape[1]) for side, k in enumerate(self._keys)}, rank, real_dtype)
+        n_kept = rank if n_vec < 0 else min(n_vec, rank)
+        self._V = _LazyVectors(dev, {k: (side, self._fields_store[k].shape[1]) for side, k in enumerate(self._keys)}, n_kept, real_dtype)
         dev.hold_result(self)
 
         self._singular_values = singular_values
@@ -731,6 +749,11 @@ class MCA:
             if hasattr(self, name):
                 delattr(self, name)
         self._analysis['is_truncated_at'] = len(singular_values)
+        if n_kept < len(singular_values):
+            # what truncate(n_kept) does to this state - without its fetch of every vector (there are no others to drop)
+            self._singular_values = self._singular_values[:n_kept]
+            self._analysis['is_truncated'] = True
+            self._analysis['is_truncated_at'] = n_kept
 
     # ------------------------------------------------------------------------------------------
     # state accessors used by the getters (array.py:605-779)
@@ -845,6 +868,7 @@ class MCA:
             if not self._vectors_resident():
                 return None, None
         m = self._analysis['rank'] if max_mode is None else min(int(max_mode), self._analysis['rank'])
+        m = min(m, self._V._rank)                 # (solve(n_modes=k): k modes are resident, as `_get_V` finds k after truncate(k))
         T = self._n_observations['left']
         vdt = {k: self._resident_dtype() for k in self._keys}
         if m < 1:
@@ -912,6 +936,7 @@ class MCA:
         rotated = rotated and self._analysis['is_rotated']
         max_mode = self._max_mode(n, rotated)
         max_mode = self._analysis['rank'] if max_mode is None else min(max_mode, self._analysis['rank'])
+        max_mode = min(max_mode, Vl._rank)
         keep = self._get_slice(n)
         if max_mode < 1 or len(range(max_mode)[keep]) < 1:
             return None
@@ -1046,7 +1071,7 @@ class MCA:
         dev = self._device()
         V = getattr(self, '_V', None)
         if (isinstance(V, _LazyVectors) and V._pending == set(self._keys) and dev.holds_result_of(self)
-                and n_rot <= self._analysis['rank'] and (V._dtype == np.float64 or dev.vectors_are_f32(0))):
+                and n_rot <= self._analysis['rank'] and n_rot <= V._rank and (V._dtype == np.float64 or dev.vectors_are_f32(0))):
             # the vectors of solve() are still resident: the stacked loadings V sqrt(s) are built on the device.  float32
             # models: the reference rotates float32 loadings (float32 vectors x float32 sqrt(s)) - the device does the same
             # product when the vectors are resident in float32 (one real field, dual side); any other float32 model
@@ -1230,8 +1255,7 @@ class MCA:
         max_mode = self._max_mode(mode, rotated)
         max_mode = self._analysis['rank'] if max_mode is None else min(int(max_mode), self._analysis['rank'])
         for dev, Vh in route.values():
-            if Vh is not None:
-                max_mode = min(max_mode, Vh.shape[1])
+            max_mode = min(max_mode, self._V._rank if Vh is None else Vh.shape[1])
         P = self._get_pcs(n=mode, scaling='eigen', rotated=True)
         T = self._n_observations['left']
         out = {}

@@ -41,6 +41,7 @@ struct EvdInfo {
   int lr_step = 0;        // 1: a Cholesky LR step was inserted (graded spectrum)
   double diag_spread = 0; // q10/q90 of the diagonal when that was decided
   int tridiag = 0;        // 1: solved by reduction to tridiagonal form (tridiag.h), no Jacobi sweeps
+  int n_eigvec = 0;       // eigenvectors actually formed: 0 (values only), n, or the k' of the partial route (hermitian_evd)
 };
 
 struct EvdWorkspace {
@@ -328,7 +329,7 @@ void jacobi_evd(hipStream_t st, EvdWorkspace& ws, const double* Ar, const double
     XMCA_HIP(hipGetLastError());
   }
   XMCA_HIP(hipStreamSynchronize(st));   // perm / lam_host staging buffers go out of scope
-  if (info) { info->sweeps = sweeps; info->tile = NT; info->slots = S; info->last_off = off; info->lr_step = lr_applied ? 1 : 0; }
+  if (info) { info->sweeps = sweeps; info->tile = NT; info->slots = S; info->last_off = off; info->lr_step = lr_applied ? 1 : 0; info->n_eigvec = Zr ? n : 0; }
 }
 
 // Hermitian EVD  A = U diag(lam) U^H, lam descending (see jacobi_evd for the arguments).
@@ -336,9 +337,58 @@ void jacobi_evd(hipStream_t st, EvdWorkspace& ws, const double* Ar, const double
 // Two solvers share this entry point: the reduction to tridiagonal form (tridiag.h, tridiag_vec.h: eigenproblems of 192 and
 // more without vectors, 768 and more with vectors) and the block Jacobi sweeps of this file (everything else, nearly
 // diagonal problems, and spectra with clusters the tridiagonal route hands back).
+// The guard of the partial route.  lam: all n eigenvalues, descending.  Returns the first k' >= n_lead behind which the spectrum
+// is clear of the computed set - or n when no such k' lies within the cap (the caller then forms all vectors).  DESIGN.md 2.10:
+//   * twisted vectors of lam_k', lam_k'+1 overlap by up to eps ||T|| / (lam_k' - lam_k'+1) (tridiag_vec.h); inside the set the
+//     clean-up repairs an overlap up to 0.3, across the cut nothing can.  What the cut may leave behind is held to what one
+//     Newton-Schulz step leaves of the largest defect the clean-up accepts, (3/4) 0.3^2;
+//   * a pair that agrees to a relative gap below 1e-3 - the bound below which the MRRR literature (LAPACK dlarrv, MINRGP) stops
+//     trusting independent twisted vectors, eps / relgap ~ 2e-13, the square of the 1e-6 at which the clean-up is one step from
+//     done - is a cluster as far as the vectors are concerned and is kept whole.
+constexpr double TRD_PARTIAL_RELGAP = 1e-3;
+constexpr double TRD_PARTIAL_LEAK = 0.75 * 0.3 * 0.3;
+constexpr int TRD_PARTIAL_CAP = 32;            // half a block of the twisted kernel
+inline int trd_partial_count(const std::vector<double>& lam, int n, int n_lead) {
+  if (n_lead < 1 || n_lead >= n) return n;
+  const double norm = std::max(std::fabs(lam.front()), std::fabs(lam.back()));
+  const int last = std::min(n_lead + TRD_PARTIAL_CAP, n - 1);
+  for (int k = n_lead; k <= last; ++k) {       // k vectors: the cut lies between lam[k-1] and lam[k]
+    const double gap = lam[(size_t)k - 1] - lam[(size_t)k];
+    const bool rel_ok = gap > TRD_PARTIAL_RELGAP * std::fabs(lam[(size_t)k - 1]);
+    const bool abs_ok = 2.220446049250313e-16 * norm <= TRD_PARTIAL_LEAK * gap;
+    if (rel_ok && abs_ok) return 4 * k <= n ? k : n;      // (a set of more than n / 4 vectors is no longer thin)
+  }
+  return n;
+}
+
+// n_lead: the number of leading eigenvectors wanted (Zr then needs n_lead rows only); < 0 or >= n: all of them, exactly the
+// path of a call without the argument.  On the tridiagonal route fewer vectors than n are then FORMED as well (k' >= n_lead of
+// them, info->n_eigvec: trd_partial_count, trd_eigenvectors_partial); where that route does not apply or the partial stage hands
+// the problem back, all n are formed - from the same reduction - in scratch planes and the leading n_lead rows copied out.
 inline void hermitian_evd(hipStream_t st, EvdWorkspace& ws, const double* Ar, const double* Ai, int n, int64_t lda,
                           std::vector<double>& lam_host, double* lam_dev, double* Zr, double* Zi, int64_t ldz,
-                          EvdInfo* info = nullptr, bool nearly_diagonal = false) {
+                          EvdInfo* info = nullptr, bool nearly_diagonal = false, int n_lead = -1) {
+  const bool cplx = Ai != nullptr;
+  const bool part = Zr && n_lead >= 0 && n_lead < n;
+  if (part) XMCA_CHECK(n_lead >= 1, XMCA_ERR_INVALID, "hermitian_evd: n_lead must be at least 1 when vectors are wanted");
+  // Where all n vectors have to be formed although the caller wants (and has room for) n_lead rows only, they go to scratch
+  // planes of this call and the leading rows are copied out; the stream is synchronised before the planes are given back.
+  DevBuf<double> full[2];
+  double *Fr = Zr, *Fi = Zi;
+  int64_t ldf = ldz;
+  auto all_rows = [&] {
+    if (!part || Fr != Zr) return;
+    Fr = full[0].ensure((size_t)n * n);
+    Fi = cplx ? full[1].ensure((size_t)n * n) : nullptr;
+    ldf = n;
+  };
+  auto hand_out = [&] {
+    if (!part) return;
+    const size_t row = sizeof(double) * (size_t)n;
+    XMCA_HIP(hipMemcpy2DAsync(Zr, sizeof(double) * (size_t)ldz, Fr, row, row, (size_t)n_lead, hipMemcpyDeviceToDevice, st));
+    if (cplx) XMCA_HIP(hipMemcpy2DAsync(Zi, sizeof(double) * (size_t)ldz, Fi, row, row, (size_t)n_lead, hipMemcpyDeviceToDevice, st));
+    XMCA_HIP(hipStreamSynchronize(st));
+  };
   // `nearly_diagonal`: the caller knows that a few Jacobi sweeps finish the problem (the weak block of solver.h, three
   // sweeps) - cheaper than any reduction, whose cost does not depend on the matrix.
   // eigenvalues only (rule_n without rotation, every n_vec = 0 solve): Householder tridiagonalisation + Sturm multisection
@@ -364,6 +414,34 @@ inline void hermitian_evd(hipStream_t st, EvdWorkspace& ws, const double* Ar, co
     trd_wy_prepare(st, ws.trdv, ws.gws, P, Ai != nullptr);  // (from the second call on: on a second stream, under the two kernels below)
     std::vector<double> lam_t;
     trd_eigenvalues(st, ws.trd, P, lam_t, lam_dev, ws.lam_tmp, ws.trdv.lam_asc.ensure((size_t)n));
+    if (part) {
+      // The leading n_lead vectors only: k' of them are formed (the guard above).  Whatever keeps the partial stage from
+      // finishing - no gap within the cap, more than n / 4 vectors, bit-equal leading values, a refused clean-up - goes on
+      // below with THIS reduction and these eigenvalues: all vectors by the full stage, or the sweeps.
+      const int kp = trd_partial_count(lam_t, n, n_lead);
+      bool rep_lead = false, ran = false, done = false;
+      const double lmax = std::max(std::fabs(lam_t.front()), std::fabs(lam_t.back()));
+      // bit-equal eigenvalues among the leading k' + 1 (the set and its neighbour) go to the sweeps, as on the full route
+      for (int i = 0; i < kp && i + 1 < n && !rep_lead; ++i) rep_lead = lam_t[(size_t)i] - lam_t[(size_t)i + 1] <= 2.2e-16 * lmax;
+      if (kp < n && !rep_lead) {
+        ran = true;
+        done = trd_eigenvectors_partial(st, ws.trdv, ws.gws, P, cplx, kp, n_lead, Zr, Zi, ldz);
+      }
+      if (xmca_trace("solve"))
+        std::fprintf(stderr, "xmca: eigh n = %d, %d leading vectors wanted: %d formed%s\n", n, n_lead, done ? kp : n,
+                     done ? "" : (kp >= n ? " (no gap within the cap)" : rep_lead ? " (repeated eigenvalues)" : " (clean-up refused)"));
+      if (done) {
+        XMCA_HIP(hipStreamSynchronize(st));
+        lam_host = lam_t;
+        if (info) {
+          *info = EvdInfo{};
+          info->tridiag = 1;
+          info->n_eigvec = kp;
+        }
+        return;
+      }
+      if (ran) ws.trdv.prepared = true;      // (joined by the partial stage; T V^H of every super-block is untouched)
+    }
     // Eigenvalues that coincide to the last bit of the largest one (a null space of dimension > 1: repeated samples, low-rank
     // fields) are not resolved by the twisted vectors - the clean-up would find that out only after the back-transformation
     // and two n^3 products (advisor, round 3); they are on the host already, so the sweeps below start right away.
@@ -380,13 +458,16 @@ inline void hermitian_evd(hipStream_t st, EvdWorkspace& ws, const double* Ar, co
       ws.trdv.prepared = false;
       ws.trdv.joined = true;
     }
-    if (!repeated && trd_eigenvectors(st, ws.trd, ws.trdv, ws.gws, P, Ai != nullptr, Zr, Zi, ldz)) {
+    if (!repeated) all_rows();
+    if (!repeated && trd_eigenvectors(st, ws.trd, ws.trdv, ws.gws, P, Ai != nullptr, Fr, Fi, ldf)) {
       XMCA_HIP(hipStreamSynchronize(st));
       lam_host = lam_t;
       if (info) {
         *info = EvdInfo{};
         info->tridiag = 1;
+        info->n_eigvec = n;
       }
+      hand_out();
       return;
     }
   }
@@ -397,9 +478,11 @@ inline void hermitian_evd(hipStream_t st, EvdWorkspace& ws, const double* Ar, co
   // push the vectors' first-order error down is not needed (C4 surrogates: 12 -> 11 sweeps)
   const double tol = Zr ? 1e-10 : 1e-8;
   // tile size by problem kind (64 x 64 complex tiles do not fit the LDS of the update kernel)
-  if (Ai) jacobi_evd<true, 32>(st, ws, Ar, Ai, n, lda, lam_host, lam_dev, Zr, Zi, ldz, tol, info);
-  else if (n > 32) jacobi_evd<false, 64>(st, ws, Ar, nullptr, n, lda, lam_host, lam_dev, Zr, nullptr, ldz, tol, info);
-  else jacobi_evd<false, 32>(st, ws, Ar, nullptr, n, lda, lam_host, lam_dev, Zr, nullptr, ldz, tol, info);
+  all_rows();
+  if (Ai) jacobi_evd<true, 32>(st, ws, Ar, Ai, n, lda, lam_host, lam_dev, Fr, Fi, ldf, tol, info);
+  else if (n > 32) jacobi_evd<false, 64>(st, ws, Ar, nullptr, n, lda, lam_host, lam_dev, Fr, nullptr, ldf, tol, info);
+  else jacobi_evd<false, 32>(st, ws, Ar, nullptr, n, lda, lam_host, lam_dev, Fr, nullptr, ldf, tol, info);
+  hand_out();
 }
 
 }  // namespace xmca

@@ -31,19 +31,21 @@ __device__ __forceinline__ double trd_lane_value(double v, int u) {
   return __hiloint2double(hi, lo);
 }
 
-// Yt[i * ldy + k] = component i of the eigenvector of eigenvalue k (ascending);  W: work plane of the same shape.
+// Yt[i * ldy + k] = component i of the eigenvector of eigenvalue lam[k], k < nev;  W: work plane of the same shape (n x ldy).
+// n is the order of the tridiagonal matrix, nev the number of eigenvalues handed in: all n of them (ascending) on the full
+// route, the k' leading ones on the partial route (trd_eigenvectors_partial), whose planes are n x k' only.
 // 128 threads per 64 eigenvalues: the forward (D+) and the backward (D-) factorisation are independent recurrences and run
 // in the two waves side by side; so do the two halves of the vector (upwards / downwards from the twist index) and of the
 // final scaling.  Every loop requests its operands one chunk (64 rows of d / e, 32 rows of the planes) ahead of the recurrence.
-__global__ __launch_bounds__(128) void trd_twisted_kernel(const double* __restrict__ d, const double* __restrict__ e, int n,
+__global__ __launch_bounds__(128) void trd_twisted_kernel(const double* __restrict__ d, const double* __restrict__ e, int n, int nev,
                                                          const double* __restrict__ lam, double* __restrict__ W, double* __restrict__ Yt,
                                                          int64_t ldy) {
   __shared__ double nrm_sh[2][64];
   __shared__ int idx_sh[2][64];
   const int lane = threadIdx.x & 63, half = threadIdx.x >> 6;
   const int k = blockIdx.x * 64 + lane;
-  const bool live = k < n;
-  const int kk = live ? k : n - 1;                           // (idle lanes shadow the last eigenvalue and store nothing)
+  const bool live = k < nev;
+  const int kk = live ? k : nev - 1;                         // (idle lanes shadow the last eigenvalue and store nothing)
   const double l = lam[kk];
   if (n == 1) { if (live && half == 0) Yt[k] = 1.0; return; }
   constexpr int B = 32;
@@ -500,7 +502,7 @@ inline bool trd_eigenvectors(hipStream_t st, TrdWorkspace& ws, TrdVecWorkspace& 
   double* Yi = cplx ? vw.Y[1].ensure(plane) : nullptr;
   double* Wr = vw.Wk[0].ensure(plane);
   double* Wi = cplx ? vw.Wk[1].ensure(plane) : nullptr;
-  hipLaunchKernelGGL(trd_twisted_kernel, dim3(ceil_div(n, 64)), dim3(128), 0, st, P.d, P.e, n, vw.lam_asc.get(), Wr, Yr, ld);
+  hipLaunchKernelGGL(trd_twisted_kernel, dim3(ceil_div(n, 64)), dim3(128), 0, st, P.d, P.e, n, n, vw.lam_asc.get(), Wr, Yr, ld);
   XMCA_HIP(hipGetLastError());
   if (cplx) XMCA_HIP(hipMemsetAsync(Yi, 0, sizeof(double) * plane, st));
   const int nref = n - 1;
@@ -562,6 +564,98 @@ inline bool trd_eigenvectors(hipStream_t st, TrdWorkspace& ws, TrdVecWorkspace& 
     cgemm<double>(st, gws, Yr, Yi, ld, true, false, Wr, Wi, ld, true, false, Sr, Si, ld, n, n, n, 1.0, nullptr, nullptr, false);
     XMCA_HIP(hipMemcpyAsync(Yr, Sr, sizeof(double) * plane, hipMemcpyDeviceToDevice, st));
     if (cplx) XMCA_HIP(hipMemcpyAsync(Yi, Si, sizeof(double) * plane, hipMemcpyDeviceToDevice, st));
+    ++vw.ns_steps;
+  }
+  return false;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The partial route: eigenvectors of the k' LEADING eigenvalues only (hermitian_evd with n_lead < n).
+// Z is n x k' with k' << n.  The two products of a super-block, X = (T V^H) Z and Z -= V X, go to the tiled GEMM like those of
+// the full route: kernels written for the skinny shape (k' columns across the lanes, reflector tiles staged in LDS, the
+// contraction cut over the workgroups and summed in chunk order) were measured 0.3 - 0.5 ms SLOWER per solve than the GEMM's
+// split-K on the same planes (profiles/partial_solve_skinny_vs_gemm.json) and are not part of the library.
+// ---------------------------------------------------------------------------------------------------------------------
+// Eigenvectors of the kp LEADING eigenvalues of the matrix reduced by trd_reduce(..., keep_reflectors = true):
+// Zr / Zi (n_out x ldz planes, n_out <= kp) get row i = conj(u_i), eigenvalues descending - the first n_out rows of what
+// trd_eigenvectors writes.  vw.lam_asc holds all n eigenvalues (ascending); the work planes are n x kp.  The kp vectors are
+// orthonormalised among themselves (S = Z^H Z is kp x kp, the same criterion and Newton-Schulz steps as the full route): the
+// caller has chosen kp so that the eigenvalue behind the last one is clear of it (hermitian_evd).  Returns false when the
+// clean-up cannot repair the set - the caller then forms all vectors.
+inline bool trd_eigenvectors_partial(hipStream_t st, TrdVecWorkspace& vw, GemmWorkspace& gws, const TrdParams& P, bool cplx, int kp, int n_out,
+                                     double* Zr, double* Zi, int64_t ldz) {
+  const int n = P.n;
+  const int64_t ldv = P.ld;
+  constexpr int SBK = TRD_SBK;
+  const int64_t ld = ((int64_t)kp + 15) & ~(int64_t)15;      // columns of the n x kp planes
+  const size_t plane = (size_t)n * ld;
+  double* Yr = vw.Y[0].ensure(plane);
+  double* Yi = cplx ? vw.Y[1].ensure(plane) : nullptr;
+  double* Wr = vw.Wk[0].ensure(plane);
+  double* Wi = cplx ? vw.Wk[1].ensure(plane) : nullptr;
+  // (the padding columns kp .. ld-1 are read by nobody, but the planes are handed to the GEMM with leading dimension ld)
+  XMCA_HIP(hipMemsetAsync(Yr, 0, sizeof(double) * plane, st));
+  XMCA_HIP(hipMemsetAsync(Wr, 0, sizeof(double) * plane, st));
+  if (cplx) XMCA_HIP(hipMemsetAsync(Yi, 0, sizeof(double) * plane, st));
+  if (cplx) XMCA_HIP(hipMemsetAsync(Wi, 0, sizeof(double) * plane, st));
+  // column c = eigenvalue n - kp + c of the ascending list
+  hipLaunchKernelGGL(trd_twisted_kernel, dim3(ceil_div(kp, 64)), dim3(128), 0, st, P.d, P.e, n, kp, vw.lam_asc.get() + (n - kp), Wr, Yr, ld);
+  XMCA_HIP(hipGetLastError());
+  const int nref = n - 1;
+  if (nref > 0) {
+    XMCA_CHECK(vw.prepared, XMCA_ERR_STATE, "trd_eigenvectors_partial: trd_wy_prepare has not run");
+    vw.prepared = false;
+    if (!vw.joined) XMCA_HIP(hipStreamWaitEvent(st, vw.ev_join, 0));
+    vw.joined = true;
+    const double* TVr = vw.TV[0].get();
+    const double* TVi = cplx ? vw.TV[1].get() : nullptr;
+    double* sm = vw.small.ensure(2 * (size_t)SBK * ld);
+    double* Xr = sm; double* Xi = cplx ? Xr + (size_t)SBK * ld : nullptr;
+    for (int j0 = ((nref - 1) / SBK) * SBK; j0 >= 0; j0 -= SBK) {
+      const int nb = std::min(SBK, nref - j0);
+      const int i0 = j0 + 1, mb = n - i0;                    // support of the super-block: rows i0 .. n-1
+      const int64_t vo = (int64_t)j0 * ldv + i0;
+      double* Zr0 = Yr + (int64_t)i0 * ld;
+      double* Zi0 = cplx ? Yi + (int64_t)i0 * ld : nullptr;
+      cgemm<double>(st, gws, TVr + vo, cplx ? TVi + vo : nullptr, ldv, true, false, Zr0, Zi0, ld, true, false, Xr, Xi, ld, nb, kp, mb, 1.0, nullptr,
+                    nullptr, false);
+      cgemm<double>(st, gws, P.Vr + vo, cplx ? P.Vi + vo : nullptr, ldv, false, false, Xr, Xi, ld, true, false, Zr0, Zi0, ld, mb, kp, nb, -1.0,
+                    nullptr, nullptr, false, 1.0);
+    }
+  }
+  XMCA_HIP(hipGetLastError());
+  // ---- S = Z^H Z (kp x kp), Newton-Schulz clean-up inside the set, the leading n_out rows in the caller's layout ----
+  const size_t small_plane = (size_t)kp * ld;
+  double* Sr = vw.S[0].ensure(2 * small_plane);
+  double* Si = cplx ? vw.S[1].ensure(2 * small_plane) : nullptr;
+  double* Cr = Sr + small_plane;                             // 3/2 I - 1/2 S
+  double* Ci = cplx ? Si + small_plane : nullptr;
+  vw.orth.ensure(2);
+  vw.ns_steps = 0;
+  for (int round = 0; round < 3; ++round) {
+    cgemm<double>(st, gws, Yr, Yi, ld, false, true, Yr, Yi, ld, true, false, Sr, Si, ld, kp, kp, n, 1.0, nullptr, nullptr, true);
+    XMCA_HIP(hipMemsetAsync(vw.orth.get(), 0, sizeof(unsigned long long) * 2, st));
+    hipLaunchKernelGGL(trd_orth_kernel, dim3(std::min(kp, 1024)), dim3(256), 0, st, Sr, Si, kp, ld, vw.orth.get());
+    // out = (3/2 I - 1/2 S)[rows reversed] Z^H, its first n_out rows: queued before the host learns the number, as on the full route
+    hipLaunchKernelGGL(trd_ns_matrix_kernel, dim3(kp), dim3(256), 0, st, Sr, Si, kp, ld, 1, Cr, Ci);
+    cgemm<double>(st, gws, Cr, Ci, ld, true, false, Yr, Yi, ld, false, true, Zr, Zi, ldz, n_out, n, kp, 1.0, nullptr, nullptr, false);
+    XMCA_HIP(hipGetLastError());
+    unsigned long long bits = 0;
+    XMCA_HIP(hipMemcpyAsync(&bits, vw.orth.get(), sizeof(bits), hipMemcpyDeviceToHost, st));
+    XMCA_HIP(hipStreamSynchronize(st));
+    double off;
+    std::memcpy(&off, &bits, sizeof(off));
+    if (round == 0) vw.last_orth = off;
+    if (!(off <= 0.3)) return false;
+    if (off <= 1e-6) {
+      ++vw.ns_steps;
+      return true;
+    }
+    // Z <- Z (3/2 I - 1/2 S)
+    hipLaunchKernelGGL(trd_ns_matrix_kernel, dim3(kp), dim3(256), 0, st, Sr, Si, kp, ld, 0, Cr, Ci);
+    cgemm<double>(st, gws, Yr, Yi, ld, true, false, Cr, Ci, ld, true, false, Wr, Wi, ld, n, kp, kp, 1.0, nullptr, nullptr, false);
+    XMCA_HIP(hipMemcpyAsync(Yr, Wr, sizeof(double) * plane, hipMemcpyDeviceToDevice, st));
+    if (cplx) XMCA_HIP(hipMemcpyAsync(Yi, Wi, sizeof(double) * plane, hipMemcpyDeviceToDevice, st));
     ++vw.ns_steps;
   }
   return false;

@@ -355,10 +355,16 @@ void complexify_impl(xmca_handle* h, const ComplexOp& op) {
 template <typename TI>
 void solve_impl(xmca_handle* h, int n_fields, int64_t n_vec) {
   FieldData<TI>* f = typed<TI>(h).f;
+  if (n_vec > 0) {
+    // A buffer only grows: the planes of an earlier, larger result on this handle would stay behind a result of n_vec modes.
+    // They go back to the pool (xmca_trim_pool frees them) and the solve takes blocks of the size it needs.
+    for (int s = 0; s < 2; ++s) { h->res.Vt[s].re.release(); h->res.Vt[s].im.release(); h->res.Vt32[s].release(); }
+  }
   if (h->op_pending) {
     if (Solver<TI>::analytic_route(h->op.kind == ComplexOp::CIRCULANT, f[0].T, f[0].N, n_fields == 2 ? f[1].N : 0, n_fields,
                                    f[0].has_im || (n_fields == 2 && f[1].has_im))) {
       Solver<TI> s(h->st, h->gws, h->ews, h->tm);
+      s.partial_vectors = true;
       s.solve_analytic(f, n_fields, (int)n_vec, h->res);
       return;
     }
@@ -369,6 +375,7 @@ void solve_impl(xmca_handle* h, int n_fields, int64_t n_vec) {
   if (n_fields == 2) XMCA_CHECK(f[1].has_im == cplx, XMCA_ERR_INVALID, "solve: both fields must be real or both complex");
   Solver<TI> s(h->st, h->gws, h->ews, h->tm);
   s.f32_vectors = true;          // (only the one-field dual route of a real float32 field uses it)
+  s.partial_vectors = true;      // (one field, n_vec > 0: no more eigenvectors are formed than modes are back-projected)
   if (n_fields == 1) {           // ... and only it may leave the tail of its back-projection in flight
     h->tail.count_call();
     s.defer = &h->tail;
@@ -1461,6 +1468,14 @@ int xmca_get_solve_info(xmca_handle* h, int* info, int n) {
     info[i] = (i % 3 == 0) ? e.sweeps : (i % 3 == 1) ? e.tile : e.slots;
   }
   for (int i = 9; i < n && i < 12; ++i) info[i] = h->res.evd_info[i - 9].lr_step + 2 * h->res.evd_info[i - 9].tridiag;   // bit 1: tridiagonal route
+  for (int i = 12; i < n && i < 15; ++i) info[i] = h->res.evd_info[i - 12].n_eigvec;
+  if (n > 15) info[15] = h->solved ? h->res.n_vec : 0;
+  for (int i = 16; i < n && i < 18; ++i) {       // KiB of the device blocks that hold the vector planes of side i - 16
+    const SolveResult& r = h->res;
+    const int s = i - 16;
+    const size_t bytes = r.Vt[s].re.cap_bytes + r.Vt[s].im.cap_bytes + r.Vt32[s].cap_bytes;
+    info[i] = (int)((bytes + 1023) / 1024);
+  }
   return XMCA_OK;
 }
 
