@@ -455,6 +455,16 @@ int xmca_gemm_ex(xmca_handle* h, const void* A, int64_t lda, int a_kfast, const 
  * bit 0: Cholesky LR step taken, bit 1: solved by tridiagonalisation (csrc/tridiag.h; then no sweeps).  The device time of the
  * solve is recorded under "eigh_vectors" / "eigh_values" (xmca_get_timings). */
 int xmca_eigh(xmca_handle* h, const double* A, int n, int is_complex, double* lam, double* Zh, int* info);
+/* The same decomposition with the vectors of the n_lead (1 .. n) leading eigenvalues only, as the solver poses it for
+ * solve(n_modes=k) (kernel tests only): lam gets all n values, Zh n_lead rows of n (row i = conj(u_i), descending).  On the
+ * device the vector planes have n_lead + 1 rows of (n rounded up to 16) + 16 elements; the padding columns and the extra row
+ * hold a sentinel before the solve.  info (6 ints): the four of xmca_eigh, the number of eigenvectors formed (n_lead or more
+ * on the partial route, else n), and 1 when every sentinel word came back unchanged, 0 otherwise. */
+int xmca_eigh_lead(xmca_handle* h, const double* A, int n, int is_complex, int n_lead, double* lam, double* Zh, int* info);
+/* Host only, no handle, no device call: the number of eigenvectors the partial route forms for n_lead wanted ones given all n
+ * eigenvalues in descending order (n: all of them), and in *rep_lead (may be NULL) whether bit-equal values among the leading
+ * ones send the solve to the Jacobi sweeps - both exactly as the eigensolver decides them.  -1: bad arguments. */
+int xmca_partial_count(const double* lam_desc, int n, int n_lead, int* rep_lead);
 /* Blocked Cholesky of an n x n Hermitian host matrix (interleaved complex when is_complex): R (n x n, upper
  * triangular, row-major, same element layout) with R^H R = A + rel_shift * max(diag A) * I; *ok = 0 when a pivot was
  * not positive.  (The device routine behind the values-only two-field solve; exported for the kernel tests.) */

@@ -101,6 +101,8 @@ SIGNATURES = {
     "xmca_gemm_ex": (_c_int, [_vp, _vp, _c_i64, _c_int, _vp, _c_i64, _c_int, _vp, _c_i64, _c_int, _c_int, _c_int, _c_int, _c_int,
                               _c_dbl, _c_dbl, _vp, _vp, _c_int, _c_int, _c_int]),
     "xmca_eigh": (_c_int, [_vp, _vp, _c_int, _c_int, _vp, _vp, _vp]),
+    "xmca_eigh_lead": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _vp, _vp, _vp]),
+    "xmca_partial_count": (_c_int, [_vp, _c_int, _c_int, _vp]),
     "xmca_cholesky": (_c_int, [_vp, _vp, _c_int, _c_int, _c_dbl, _vp, ctypes.POINTER(_c_int)]),
     "xmca_cholesky_ex": (_c_int, [_vp, _vp, _c_int, _c_i64, _c_int, _c_int, _c_dbl, _vp, ctypes.POINTER(_c_int)]),
     "xmca_fft_ex": (_c_int, [_vp, _vp, _vp, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _vp, _c_int, _c_int, _c_int, _vp, _vp, _c_i64,
@@ -159,6 +161,18 @@ def pvalue_log_norm(n_obs):
     if rc != 0:
         raise ValueError("pvalue_log_norm: n_obs must be between 3 and 1 000 000")
     return out.value
+
+
+def partial_count(lam_desc, n_lead):
+    """(k', repeated): the number of eigenvectors the partial route of the eigensolver forms for `n_lead` wanted ones, given all
+    eigenvalues in descending order (n: all of them), and whether bit-equal leading values send the solve to the Jacobi sweeps
+    (xmca_partial_count; no device)."""
+    lam = np.ascontiguousarray(lam_desc, dtype=np.float64)
+    rep = _c_int(0)
+    kp = load_library().xmca_partial_count(_ptr(lam), int(lam.size), int(n_lead), ctypes.byref(rep))
+    if kp < 0:
+        raise ValueError("partial_count: at least one eigenvalue is needed")
+    return kp, bool(rep.value)
 
 
 def ingest_regime(T, N, stride_t, stride_n):
@@ -846,16 +860,28 @@ class Handle:
                                            int(upper_only), int(mirror), int(splits)))
         return C
 
-    def eigh(self, A, vectors=True):
-        """Returns (lam descending, U) with A = U diag(lam) U^H; `vectors=False`: (lam, None), eigenvalues only."""
+    def eigh(self, A, vectors=True, n_lead=None):
+        """Returns (lam descending, U) with A = U diag(lam) U^H; `vectors=False`: (lam, None), eigenvalues only.  `n_lead=k`: all
+        eigenvalues, and U (n x k) of the k leading ones only, posed as solve(n_modes=k) poses it (xmca_eigh_lead);
+        `last_eigh_info` then also says how many vectors were formed (`n_eigvec`) and whether the guard row and padding columns
+        around the k x n result came back untouched (`guard_rows_clean`; None without `n_lead`)."""
         Ad, cplx = _host_vectors(A)
         n = Ad.shape[0]
         lam = np.empty(n)
-        Zh = np.empty((n, n), dtype=Ad.dtype) if vectors else None
-        info = np.zeros(4, dtype=np.int32)
-        self._check(self._lib.xmca_eigh(self._h, _ptr(Ad), n, int(cplx), _ptr(lam), _ptr(Zh) if vectors else None, _ptr(info)))
+        if n_lead is None:
+            Zh = np.empty((n, n), dtype=Ad.dtype) if vectors else None
+            info = np.zeros(4, dtype=np.int32)
+            self._check(self._lib.xmca_eigh(self._h, _ptr(Ad), n, int(cplx), _ptr(lam), _ptr(Zh) if vectors else None, _ptr(info)))
+            n_eigvec, clean = (n if vectors else 0), None
+        else:
+            if not vectors or isinstance(n_lead, bool) or int(n_lead) != n_lead or not 1 <= n_lead <= n:
+                raise ValueError("eigh: n_lead is an integer between 1 and n, and needs vectors=True")
+            Zh = np.empty((int(n_lead), n), dtype=Ad.dtype)
+            info = np.zeros(6, dtype=np.int32)
+            self._check(self._lib.xmca_eigh_lead(self._h, _ptr(Ad), n, int(cplx), int(n_lead), _ptr(lam), _ptr(Zh), _ptr(info)))
+            n_eigvec, clean = int(info[4]), bool(info[5])
         self.last_eigh_info = {"sweeps": int(info[0]), "tile": int(info[1]), "slots": int(info[2]), "lr_step": int(info[3]) & 1,
-                               "tridiag": (int(info[3]) >> 1) & 1}
+                               "tridiag": (int(info[3]) >> 1) & 1, "n_eigvec": n_eigvec, "guard_rows_clean": clean}
         return lam, (Zh.conj().T if vectors else None)
 
     def cholesky(self, A, rel_shift=0.0):

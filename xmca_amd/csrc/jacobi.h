@@ -361,6 +361,15 @@ inline int trd_partial_count(const std::vector<double>& lam, int n, int n_lead) 
   return n;
 }
 
+// The `repeated` test of the partial route: bit-equal eigenvalues (to the last bit of the largest one in magnitude) among the
+// leading kp + 1 - the set and its neighbour - go to the Jacobi sweeps, as on the full route.  lam: all n, descending.
+inline bool trd_repeated_leading(const std::vector<double>& lam, int n, int kp) {
+  const double lmax = n > 0 ? std::max(std::fabs(lam.front()), std::fabs(lam.back())) : 0.0;
+  for (int i = 0; i < kp && i + 1 < n; ++i)
+    if (lam[(size_t)i] - lam[(size_t)i + 1] <= 2.2e-16 * lmax) return true;
+  return false;
+}
+
 // n_lead: the number of leading eigenvectors wanted (Zr then needs n_lead rows only); < 0 or >= n: all of them, exactly the
 // path of a call without the argument.  On the tridiagonal route fewer vectors than n are then FORMED as well (k' >= n_lead of
 // them, info->n_eigvec: trd_partial_count, trd_eigenvectors_partial); where that route does not apply or the partial stage hands
@@ -419,10 +428,9 @@ inline void hermitian_evd(hipStream_t st, EvdWorkspace& ws, const double* Ar, co
       // finishing - no gap within the cap, more than n / 4 vectors, bit-equal leading values, a refused clean-up - goes on
       // below with THIS reduction and these eigenvalues: all vectors by the full stage, or the sweeps.
       const int kp = trd_partial_count(lam_t, n, n_lead);
-      bool rep_lead = false, ran = false, done = false;
-      const double lmax = std::max(std::fabs(lam_t.front()), std::fabs(lam_t.back()));
+      bool ran = false, done = false;
       // bit-equal eigenvalues among the leading k' + 1 (the set and its neighbour) go to the sweeps, as on the full route
-      for (int i = 0; i < kp && i + 1 < n && !rep_lead; ++i) rep_lead = lam_t[(size_t)i] - lam_t[(size_t)i + 1] <= 2.2e-16 * lmax;
+      const bool rep_lead = trd_repeated_leading(lam_t, n, kp);
       if (kp < n && !rep_lead) {
         ran = true;
         done = trd_eigenvectors_partial(st, ws.trdv, ws.gws, P, cplx, kp, n_lead, Zr, Zi, ldz);

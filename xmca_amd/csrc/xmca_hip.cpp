@@ -2252,15 +2252,19 @@ int xmca_fft_ex(xmca_handle* h, const double* in_re, const double* in_im, int64_
   API_END(h)
 }
 
-int xmca_eigh(xmca_handle* h, const double* A, int n, int is_complex, double* lam, double* Zh, int* info) {
-  API_BEGIN(h)
-  XMCA_CHECK(A && n >= 1 && lam, XMCA_ERR_INVALID, "eigh: bad arguments");
-  const bool cplx = is_complex != 0;
+// xmca_eigh and xmca_eigh_lead: upload, hermitian_evd, packed rows back.  n_lead < 0: the n x n planes of xmca_eigh.  Otherwise the
+// planes handed to hermitian_evd have n_lead + 1 rows of ldz = (n rounded up to 16) + 16 elements, the padding columns and the
+// extra row filled with a sentinel beforehand; *guard_clean says whether every sentinel word is still there afterwards.
+static void eigh_body(xmca_handle* h, const double* A, int n, bool cplx, int n_lead, double* lam, double* Zh, EvdInfo& ei, int* guard_clean) {
   const size_t nn = (size_t)n * n;
+  const bool lead = n_lead >= 0;
+  const int rows = lead ? n_lead : n;
+  const int64_t ldz = lead ? (((int64_t)n + 15) & ~(int64_t)15) + 16 : n;
+  const size_t zcount = lead ? (size_t)(rows + 1) * (size_t)ldz : nn;
   DevBuf<double> raw, zout;
   CPlanes Ap, Zp;
   Ap.ensure(nn, cplx);
-  Zp.ensure(nn, cplx);
+  Zp.ensure(zcount, cplx);
   if (cplx) {
     XMCA_HIP(hipMemcpyAsync(raw.ensure(2 * nn), A, sizeof(double) * 2 * nn, hipMemcpyHostToDevice, h->st));
     hipLaunchKernelGGL((split_complex_kernel<double, double>), ew_grid((int64_t)nn), dim3(EW_BLOCK), 0, h->st, raw.get(), Ap.r(),
@@ -2268,24 +2272,69 @@ int xmca_eigh(xmca_handle* h, const double* A, int n, int is_complex, double* la
   } else {
     XMCA_HIP(hipMemcpyAsync(Ap.r(), A, sizeof(double) * nn, hipMemcpyHostToDevice, h->st));
   }
+  const uint64_t sentinel_bits = 0xC7D5A5A5A5A5A5A5ull;       // (a finite double nobody computes)
+  double sentinel;
+  std::memcpy(&sentinel, &sentinel_bits, sizeof(sentinel));
+  std::vector<double> guard;
+  if (lead) {
+    guard.assign(zcount, sentinel);
+    for (int c = 0; c < (cplx ? 2 : 1); ++c)
+      XMCA_HIP(hipMemcpyAsync(c ? Zp.im.get() : Zp.r(), guard.data(), sizeof(double) * zcount, hipMemcpyHostToDevice, h->st));
+  }
   std::vector<double> lh;
-  EvdInfo ei;
   XMCA_HIP(hipStreamSynchronize(h->st));
   h->tm.begin(Zh ? "eigh_vectors" : "eigh_values");
   // Zh == NULL: eigenvalues only (the n_vec = 0 solves of rule_n; tridiagonal route of csrc/tridiag.h)
-  hermitian_evd(h->st, h->ews, Ap.r(), Ap.i(cplx), n, n, lh, nullptr, Zh ? Zp.r() : nullptr, Zh ? Zp.i(cplx) : nullptr, n, &ei);
+  hermitian_evd(h->st, h->ews, Ap.r(), Ap.i(cplx), n, n, lh, nullptr, Zh ? Zp.r() : nullptr, Zh ? Zp.i(cplx) : nullptr, ldz, &ei, false,
+                lead ? n_lead : -1);
   h->tm.end();
   std::memcpy(lam, lh.data(), sizeof(double) * n);
-  if (info) { info[0] = ei.sweeps; info[1] = ei.tile; info[2] = ei.slots; info[3] = ei.lr_step + 2 * ei.tridiag; }
   if (Zh) {
-    const size_t no = nn * (cplx ? 2 : 1);
-    hipLaunchKernelGGL((pack_rows_kernel<double>), ew_grid((int64_t)nn), dim3(EW_BLOCK), 0, h->st, Zp.r(), Zp.i(cplx), (int64_t)n, n, n,
+    const size_t cnt = (size_t)rows * n, no = cnt * (cplx ? 2 : 1);
+    hipLaunchKernelGGL((pack_rows_kernel<double>), ew_grid((int64_t)cnt), dim3(EW_BLOCK), 0, h->st, Zp.r(), Zp.i(cplx), ldz, rows, n,
                        zout.ensure(no), 0);
     XMCA_HIP(hipGetLastError());
     XMCA_HIP(hipMemcpyAsync(Zh, zout.get(), sizeof(double) * no, hipMemcpyDeviceToHost, h->st));
     XMCA_HIP(hipStreamSynchronize(h->st));
   }
+  if (lead) {
+    bool clean = true;
+    for (int c = 0; c < (cplx ? 2 : 1); ++c) {
+      XMCA_HIP(hipMemcpyAsync(guard.data(), c ? Zp.im.get() : Zp.r(), sizeof(double) * zcount, hipMemcpyDeviceToHost, h->st));
+      XMCA_HIP(hipStreamSynchronize(h->st));
+      for (int r = 0; r <= rows && clean; ++r)
+        for (int64_t q = r < rows ? n : 0; q < ldz && clean; ++q)
+          clean = std::memcmp(&guard[(size_t)r * (size_t)ldz + (size_t)q], &sentinel, sizeof(double)) == 0;
+    }
+    *guard_clean = clean ? 1 : 0;
+  }
+}
+
+int xmca_eigh(xmca_handle* h, const double* A, int n, int is_complex, double* lam, double* Zh, int* info) {
+  API_BEGIN(h)
+  XMCA_CHECK(A && n >= 1 && lam, XMCA_ERR_INVALID, "eigh: bad arguments");
+  EvdInfo ei;
+  eigh_body(h, A, n, is_complex != 0, -1, lam, Zh, ei, nullptr);
+  if (info) { info[0] = ei.sweeps; info[1] = ei.tile; info[2] = ei.slots; info[3] = ei.lr_step + 2 * ei.tridiag; }
   API_END(h)
+}
+
+int xmca_eigh_lead(xmca_handle* h, const double* A, int n, int is_complex, int n_lead, double* lam, double* Zh, int* info) {
+  API_BEGIN(h)
+  XMCA_CHECK(A && n >= 1 && lam && Zh && info && n_lead >= 1 && n_lead <= n, XMCA_ERR_INVALID, "eigh_lead: bad arguments");
+  EvdInfo ei;
+  int clean = 0;
+  eigh_body(h, A, n, is_complex != 0, n_lead, lam, Zh, ei, &clean);
+  info[0] = ei.sweeps; info[1] = ei.tile; info[2] = ei.slots; info[3] = ei.lr_step + 2 * ei.tridiag; info[4] = ei.n_eigvec; info[5] = clean;
+  API_END(h)
+}
+
+int xmca_partial_count(const double* lam_desc, int n, int n_lead, int* rep_lead) {
+  if (!lam_desc || n < 1) return -1;
+  const std::vector<double> lam(lam_desc, lam_desc + n);
+  const int kp = trd_partial_count(lam, n, n_lead);
+  if (rep_lead) *rep_lead = trd_repeated_leading(lam, n, kp) ? 1 : 0;
+  return kp;
 }
 
 int xmca_bench_gram(xmca_handle* h, int side, int reps, double* avg_ms, double* kernel_ms, double* flops) {
