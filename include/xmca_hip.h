@@ -95,6 +95,37 @@ int xmca_complexify(xmca_handle* h, const double* hilbert_col);
  * Undone by xmca_complexify(h, NULL) or the next xmca_set_field of the left field, like xmca_complexify. */
 int xmca_complexify_extended(xmca_handle* h, const double* col3, const double* hbar, const double* U, const double* W, int rank);
 
+/* Complexify with the Theta fore/back-cast of solve(complexify=True, extend='theta', period=m) on the device (an entry point added to
+ * ABI 15 - no existing signature changes).  Replaces the host path of xmca/array.py:367-376, :429-472 (one statsmodels ThetaModel
+ * per grid point, forecast and backcast).  The extension is the one DESIGN.md 2.11 defines: additive seasonal means from the centred
+ * moving average of length m, the least-squares drift b0 of the deseasonalised column, simple exponential smoothing with alpha on
+ * [1e-4, 1 - 1e-4] found by six rounds of 33 grid candidates, and the forecast
+ *   f_h = 0.95 b0 (h + (1 - (1 - alpha)^T) / alpha) + level + s[(T + h) mod m],   h = 0 .. T-1;
+ * the backcast is the same map of the reversed column, reversed.  The fit is not linear in the column, its forecast is linear in
+ * 2 + m fitted coefficients c = (level + 0.95 b0 (1 - (1 - alpha)^T) / alpha, 0.95 b0, s_0 .. s_{m-1}), so
+ *   X_im = G0 X + B C,   G0[t][s] = col3[(t - s) mod 3T] - hbar[s]
+ * with G0 the operator of xmca_complexify_extended at rank 0 and C (2 (2 + m) x N) the coefficients of every column, fitted by
+ * the kernels of csrc/theta.h and never leaving the device.
+ *   col3, hbar  as in xmca_complexify_extended
+ *   B           T x 2 (2 + m) row-major float64, host memory: the images under the 3T Hilbert operator (rows [T, 2T), column means
+ *               removed) of the forecast basis (1, h, the m indicators of (T + h) mod m) placed at [2T, 3T), then of the backcast
+ *               basis (the same columns in reversed time) placed at [0, T)     (xmca_amd/_hip.py theta_imag_parts)
+ *   period      m >= 1 with T >= 2 m; XMCA_ERR_INVALID otherwise
+ * Float32 fields are promoted to float64 first, as by xmca_complexify_extended.  Undone by xmca_complexify(h, NULL) or the next
+ * xmca_set_field of the left field. */
+int xmca_complexify_theta(xmca_handle* h, const double* col3, const double* hbar, const double* B, int period);
+
+/* The Theta fits behind xmca_complexify_theta of the resident real field of `side`, to host memory (parity tests; an entry point
+ * added to ABI 15).  out: 2 x (3 + m) x N float64, the forecast's fit and then the backcast's (the fit of the reversed column), each
+ * the rows alpha, b0, level, s_0 .. s_{m-1} over the N columns.  A column's values are the same bits on every call.  The resident
+ * fields are not changed (a float32 field is fitted through a float64 copy). */
+int xmca_theta_fit(xmca_handle* h, int side, int period, double* out);
+
+/* Imaginary plane of the resident float64 field of `side` after xmca_complexify_extended / xmca_complexify_theta (an entry point
+ * added to ABI 15): out, T x N float64, host memory - with xmca_get_field the analytic signal the solve worked on.  The planes are
+ * formed first when no solve or projection has done so; XMCA_ERR_STATE when the field has no imaginary plane. */
+int xmca_get_field_imag(xmca_handle* h, int side, double* out);
+
 /* MCA.solve numerical core (xmca/array.py:549-584): per-field SVD, kernel, kernel SVD, back-projection.
  *   n_fields  1 (EOF/PCA) or 2 (MCA)
  *   n_vec     number of leading modes to back-project into grid space; -1 = all `rank` modes

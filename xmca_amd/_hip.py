@@ -37,6 +37,9 @@ SIGNATURES = {
     "xmca_ingest_regime": (_c_int, [_c_i64, _c_i64, _c_i64, _c_i64]),
     "xmca_complexify": (_c_int, [_vp, _vp]),
     "xmca_complexify_extended": (_c_int, [_vp, _vp, _vp, _vp, _vp, _c_int]),
+    "xmca_complexify_theta": (_c_int, [_vp, _vp, _vp, _vp, _c_int]),
+    "xmca_theta_fit": (_c_int, [_vp, _c_int, _c_int, _vp]),
+    "xmca_get_field_imag": (_c_int, [_vp, _c_int, _vp]),
     "xmca_solve": (_c_int, [_vp, _c_int, _c_i64, ctypes.POINTER(_c_i64)]),
     "xmca_get_singular_values": (_c_int, [_vp, _vp, _c_i64]),
     "xmca_get_vectors": (_c_int, [_vp, _c_int, _vp, _c_i64, _c_int]),
@@ -354,6 +357,53 @@ def extended_imag_parts(T, period):
     return np.ascontiguousarray(col3), np.ascontiguousarray(hbar), U, np.ascontiguousarray(W)
 
 
+def _hilbert_weights(n):
+    """The frequency weights of scipy.signal.hilbert at length n."""
+    h = np.zeros(n)
+    if n % 2 == 0:
+        h[0] = h[n // 2] = 1.0
+        h[1:n // 2] = 2.0
+    else:
+        h[0] = 1.0
+        h[1:(n + 1) // 2] = 2.0
+    return h
+
+
+def theta_forecast_basis(T, period):
+    """(T, 2 + period) basis F of the Theta forecast of a column of length T: the columns 1, h and the indicators of
+    (T + h) mod period == p, so that the forecast is F c with c = (level + 0.95 b0 (1 - (1 - alpha)^T) / alpha, 0.95 b0, s_0 ..)."""
+    h = np.arange(T)
+    F = np.zeros((T, 2 + period))
+    F[:, 0] = 1.0
+    F[:, 1] = h
+    F[h, 2 + (T + h) % period] = 1.0
+    return F
+
+
+def theta_imag_parts(T, period):
+    """O(T period) parts of the imaginary planes of the Theta fore/back-cast analytic signal (extend='theta', xmca/array.py:367-376,
+    :429-472).  The forecast of a column is not linear in it, but it is F c with the 2 + period fitted coefficients c of the column
+    (`theta_forecast_basis`), and the backcast F[::-1] c' with those of the reversed column.  After `hilbert` at length 3T, the trim to
+    [T, 2T) and `remove_mean` a centered field X becomes X + i (G0 X + B C) with
+
+      col3, hbar  the operator G0[t, s] = col3[(t - s) mod 3T] - hbar[s] of `extended_imag_parts` at rank 0
+      B  (T, 2 (2 + period))   the centered images H3[T:2T, 2T:3T] F of the forecast basis, then H3[T:2T, 0:T] F[::-1] of the backcast's
+
+    and C (2 (2 + period), N) the coefficients of every column, fitted on the device (xmca_complexify_theta)."""
+    T, period = int(T), int(period)
+    if period < 1 or T < 2 * period:
+        raise ValueError("extend='theta' needs period >= 1 and at least 2 * period time steps")
+    col3, hbar, _, _ = extended_imag_parts(T, 1.0)           # (col3 and hbar do not depend on the period of 'exp')
+    kc = 2 + period
+    F = theta_forecast_basis(T, period)
+    ext = np.zeros((3 * T, 2 * kc))
+    ext[2 * T:, :kc] = F
+    ext[:T, kc:] = F[::-1]
+    B = np.fft.ifft(np.fft.fft(ext, axis=0) * _hilbert_weights(3 * T)[:, None], axis=0).imag[T:2 * T]
+    B = np.ascontiguousarray(B - B.mean(axis=0))
+    return col3, hbar, B
+
+
 class Handle:
     """One device + stream + workspace.  Not thread-safe."""
 
@@ -447,6 +497,28 @@ class Handle:
         col3, hbar, U, W = extended_imag_parts(T, period)
         self._check(self._lib.xmca_complexify_extended(self._h, _ptr(col3), _ptr(hbar), _ptr(U), _ptr(W), U.shape[1]))
         self.field_dtype = np.dtype(np.float64)
+
+    def complexify_theta(self, T, period):
+        """solve(complexify=True, extend='theta', period=period) on the resident fields: X~ = X + i (G0 X + B C) with the parts of
+        `theta_imag_parts` and the Theta fits C of every column made on the device (xmca_complexify_theta).  Float32 fields become
+        float64 fields on the device."""
+        self.release_result()
+        col3, hbar, B = theta_imag_parts(T, period)
+        self._check(self._lib.xmca_complexify_theta(self._h, _ptr(col3), _ptr(hbar), _ptr(B), int(period)))
+        self.field_dtype = np.dtype(np.float64)
+
+    def theta_fit(self, side, N, period):
+        """The Theta fits of the columns of the resident real field of `side` (xmca_theta_fit): (2, 3 + period, N) float64 - forecast
+        and backcast; rows alpha, b0, level, s_0 .. s_{period-1}."""
+        out = np.empty((2, 3 + int(period), int(N)), dtype=np.float64)
+        self._check(self._lib.xmca_theta_fit(self._h, side, int(period), _ptr(out)))
+        return out
+
+    def get_field_imag(self, side, shape):
+        """Imaginary plane (float64) of the resident field of `side` after `complexify_extended` / `complexify_theta`."""
+        out = np.empty(shape, dtype=np.float64)
+        self._check(self._lib.xmca_get_field_imag(self._h, side, _ptr(out)))
+        return out
 
     def decomplexify(self):
         """Back to the real resident fields (undoes `complexify` for the next solve)."""

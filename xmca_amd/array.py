@@ -257,6 +257,7 @@ class MCA:
         self._pending_hilbert = False
         self._device_hilbert = False
         self._device_extend = None          # period of extend='exp' when the device applies the extended operator
+        self._device_theta = None           # season length of extend='theta' when the device fits and applies the extension
         self._upload_serial = 0
         self._token = object()              # identity of this model as owner of a handle's resident fields (never reused, unlike id())
         self._shape = {}
@@ -308,7 +309,9 @@ class MCA:
         if self._store_is_raw:
             self._materialize_fields()
         if self._pending_hilbert:
-            if getattr(self, '_device_extend', None) is not None:
+            if getattr(self, '_device_theta', None) is not None:
+                self._fields_store = self._fetch_analytic_fields()            # the signal the device solved: its planes
+            elif getattr(self, '_device_extend', None) is not None:
                 self._fields_store = self._complexify(self._fields_store)     # the reference's own extension (array.py:429-472)
             else:
                 from scipy.signal import hilbert
@@ -316,10 +319,26 @@ class MCA:
             self._pending_hilbert = False
         return self._fields_store
 
+    def _device_extension(self):
+        """True when the last solve complexified with a fore/back-cast extension applied on the device ('exp' or 'theta')."""
+        return getattr(self, '_device_extend', None) is not None or getattr(self, '_device_theta', None) is not None
+
+    def _fetch_analytic_fields(self):
+        """extend='theta': the analytic signal as the device formed it - the real fields in float64 and the imaginary planes
+        G0 X + B C fetched from the handle.  When something else has used the handle since the solve, the fields go up and are
+        extended there again first (the fits of a column are the same bits on every call)."""
+        dev = self._device()
+        if not self._owns_device_fields(dev):
+            self._upload_serial += 1
+            self._upload_fields(dev)
+        store = self._fields_store
+        return {k: np.asarray(store[k].real, dtype=np.float64) + 1j * dev.get_field_imag(side, store[k].shape)
+                for side, k in enumerate(self._keys)}
+
     def _real_fields(self):
-        """Real parts of `_fields` without materialising a pending analytic signal on the host.  extend='exp': float64, as the
-        reference's real part of its complex128 signal (the imaginary part never enters the replicates of `bootstrapping`)."""
-        if not (self._pending_hilbert and getattr(self, '_device_extend', None) is not None):
+        """Real parts of `_fields` without materialising a pending analytic signal on the host.  extend='exp' / 'theta': float64, as
+        the reference's real part of its complex128 signal (the imaginary part never enters the replicates of `bootstrapping`)."""
+        if not (self._pending_hilbert and self._device_extension()):
             return {k: x.real for k, x in self._get_X(original_scale=False).items()}
         if self._store_is_raw:
             self._materialize_fields()
@@ -666,8 +685,12 @@ class MCA:
         """EOF analysis / MCA: singular value decomposition of the (cross-)covariance matrix.
 
         complexify : Hilbert-transform the fields first (complex EOF/MCA).
-        extend     : False, 'exp' or 'theta' - fore/back-cast before the Hilbert transform.
-        period     : season length (theta) / e-folding time (exp).
+        extend     : False, 'exp' or 'theta' - fore/back-cast before the Hilbert transform.  Both run on the device in float64
+                     (float32 fields are promoted; the result is complex128): 'exp' is one linear operator along time, 'theta'
+                     fits every grid point there - additive seasonal means of season length `period`, drift, simple exponential
+                     smoothing with alpha from a fixed grid zoom - and forecasts with theta = 20 as the reference does
+                     (the Theta method restated from the published algorithm, not compared with statsmodels).
+        period     : season length (theta: an integer >= 1, at most half the number of time steps) / e-folding time (exp).
         n_modes    : None - all modes - or an integer k >= 1 (extension): the model is left as `solve()` followed by
                      `truncate(k)` leaves it - k singular values and the vectors of k modes, the totals of the full spectrum - but
                      the device forms, back-projects and keeps the vectors of those k modes only, and nothing is fetched to the
@@ -682,6 +705,14 @@ class MCA:
             if n_modes < 1:
                 raise ValueError('`n_modes` must be >= 1, not {!r}'.format(n_modes))
             n_modes = int(n_modes)
+        if complexify and extend == 'theta':
+            n_obs = self._n_observations.get('left', 0)
+            if isinstance(period, (bool, np.bool_)) or not isinstance(period, (int, np.integer)) or period < 1:
+                raise ValueError("`period` must be an integer >= 1 for extend='theta', not {!r}".format(period))
+            if n_obs < 2 * period:
+                raise ValueError("`period` = {:} needs at least 2 * period = {:} time steps for extend='theta'; the fields have "
+                                 "{:}".format(period, 2 * period, n_obs))
+            period = int(period)
         store = self._fields_store
         if len(store) == 0 or (not self._store_is_raw and any(np.isnan(f).all() for f in store.values())):
             raise RuntimeError('''
@@ -695,11 +726,15 @@ class MCA:
 
         dev = self._device()
         # extend='exp' is a fixed linear operator along time (`_hip.extended_imag_parts`): X_im = G X on the device, in float64
-        # like the reference; `_extend_on_host` (private) keeps the reference's host procedure for comparison
-        extend_exp = bool(complexify) and extend == 'exp' and not getattr(self, '_extend_on_host', False)
+        # like the reference; extend='theta' is fitted per column on the device and its forecast is linear in the fitted coefficients
+        # (`_hip.theta_imag_parts`): X_im = G0 X + B C.  `_extend_on_host` (private) keeps the reference's host procedure for comparison
+        on_host = getattr(self, '_extend_on_host', False)
+        extend_exp = bool(complexify) and extend == 'exp' and not on_host
+        extend_theta = bool(complexify) and extend == 'theta' and not on_host
         self._device_extend = period if extend_exp else None
-        if complexify and extend and not extend_exp:
-            self._fields = self._complexify(self._fields)           # host path (theta: nonlinear extension)
+        self._device_theta = period if extend_theta else None
+        if complexify and extend and not (extend_exp or extend_theta):
+            self._fields = self._complexify(self._fields)           # host path (`_extend_on_host`, or an unknown extension's error)
             self._device_hilbert = False
         elif self._store_is_raw:
             self._device_hilbert = bool(complexify)                  # centered real fields are resident already
@@ -724,7 +759,7 @@ class MCA:
             raise np.linalg.LinAlgError('''SVD failed. NaN entries may be the problem.''') from err
 
         real_dtype = _real_dtype(next(iter(self._fields_store.values())).dtype)
-        if extend_exp:
+        if extend_exp or extend_theta:
             real_dtype = np.float64                                  # float32 input is extended in float64 (complex128 result)
         singular_values = dev.singular_values(rank).astype(real_dtype, copy=False)
         # the vectors stay on the device until something reads them (233 MB at C2; pcs / eofs / rotate of a few modes
@@ -811,11 +846,15 @@ class MCA:
         """Makes the fields solve() works on resident on the device and records this model as their owner."""
         T = self._n_observations['left']
         extend = getattr(self, '_device_extend', None)
+        theta = getattr(self, '_device_theta', None)
+        extended = self._device_extension()
         if self._store_is_raw:
-            # (float32 fields promoted by an earlier extend='exp' solve are resident as float64: a plain solve uploads them again)
+            # (float32 fields promoted by an earlier extend='exp' / 'theta' solve are resident as float64: a plain solve uploads them again)
             same_dtype = getattr(dev, 'field_dtype', None) in (None, np.dtype(self._fields_store[self._keys[0]].dtype))
-            if self._owns_device_fields(dev) and (extend is not None or same_dtype):   # still resident: nothing to send
-                if extend is not None:
+            if self._owns_device_fields(dev) and (extended or same_dtype):   # still resident: nothing to send
+                if theta is not None:
+                    dev.complexify_theta(T, theta)
+                elif extend is not None:
                     dev.complexify_extended(T, extend)
                 elif self._device_hilbert:
                     dev.complexify(T)
@@ -828,8 +867,10 @@ class MCA:
             dev.set_field(side, _device_ready(store[k]))
         if self._device_hilbert and not any(np.iscomplexobj(f) for f in store.values()):
             # (a materialised host analytic signal goes up as it is); the extended operator, never the plain Hilbert one, for
-            # a model solved with extend='exp'
-            if extend is not None:
+            # a model solved with extend='exp' / 'theta'
+            if theta is not None:
+                dev.complexify_theta(T, theta)
+            elif extend is not None:
                 dev.complexify_extended(T, extend)
             else:
                 dev.complexify(T)
@@ -1452,7 +1493,8 @@ class MCA:
         resampled), centering, solve, rotation, variance - run on the device (`xmca_bootstrap_runs`, `xmca_bootstrap_runs_columns`).
         A model solved with extend='exp' runs there too, every replicate complexified with the same extended operator in float64
         (`xmca_bootstrap_runs_extended`, `xmca_bootstrap_runs_columns_extended`).  Only extend='theta' keeps the reference's host
-        loop with one device solve per replicate.
+        loop over the replicates: each replicate is resampled on the host and solved on the device, its Theta extension fitted
+        there too (`xmca_complexify_theta`; statsmodels is not needed).
         """
         complexify = self._analysis['is_complex']
         extend = self._analysis['extend']
@@ -1467,7 +1509,7 @@ class MCA:
         dev = self._device()
         n_obs = self._n_observations['left']
         for mode in range(n_modes):
-            X_surr = self._real_fields() if extend_exp else self._get_X(original_scale=False, real=True)
+            X_surr = self._real_fields() if self._device_extension() else self._get_X(original_scale=False, real=True)
             if strategy == 'iterative':
                 X_rec = self._reconstructed_X(mode=mode, original_scale=False)
                 for k in X_surr:

@@ -9,18 +9,22 @@
 
 #include "solver.h"
 #include "comm.h"
+#include "theta.h"
 
 using namespace xmca;
 
 // The operator of a complexification X~ = X + i Op X along time (xmca_complexify / xmca_complexify_extended): the circulant
 // Hilbert operator of scipy.signal.hilbert (first column, T values) or the operator of the fore/back-cast analytic signal of
 // extend='exp' (xmca_amd/_hip.py extended_imag_parts: col3 of length 3T, hbar, U and W of T x r).  Host copies; the T x T matrix
-// is assembled on the device when it is needed (build_operator).
+// is assembled on the device when it is needed (build_operator).  extend='theta' (xmca_complexify_theta) is the extended operator
+// of rank 0 plus B C: C the coefficients of the Theta fits of the columns (csrc/theta.h), B the images of their forecast basis.
 struct ComplexOp {
-  enum Kind { CIRCULANT, EXTENDED } kind = CIRCULANT;
+  enum Kind { CIRCULANT, EXTENDED, THETA } kind = CIRCULANT;
   int64_t T = 0;
   int r = 0;
+  int period = 0;                    // THETA: season length m
   std::vector<double> col, hbar, U, W;
+  std::vector<double> B;             // THETA: T x 2 (THETA_HEAD + m), zero columns where a fit holds alpha, b0 and the level
   static ComplexOp circulant(const double* col, int64_t T) {
     ComplexOp op;
     op.T = T;
@@ -36,6 +40,18 @@ struct ComplexOp {
     op.hbar.assign(hbar, hbar + T);
     op.U.assign(U, U + T * r);
     op.W.assign(W, W + T * r);
+    return op;
+  }
+  // B: T x 2 (2 + m) row-major, the forecast's columns (1, h, the m phases) and then the backcast's
+  static ComplexOp theta(const double* col3, const double* hbar, const double* B, int period, int64_t T) {
+    ComplexOp op = extended(col3, hbar, nullptr, nullptr, 0, T);
+    op.kind = THETA;
+    op.period = period;
+    const int64_t kc = 2 + period, rows = ::xmca::theta_fit_rows(period);
+    op.B.assign((size_t)(T * 2 * rows), 0.0);
+    for (int64_t t = 0; t < T; ++t)
+      for (int d = 0; d < 2; ++d)
+        for (int64_t k = 0; k < kc; ++k) op.B[(t * 2 + d) * rows + (rows - kc) + k] = B[(t * 2 + d) * kc + k];
     return op;
   }
 };
@@ -323,8 +339,12 @@ void build_operator(xmca_handle* h, const ComplexOp& op, DevBuf<TI>& g) {
   DevBuf<double> col3, hbar, U, W;
   XMCA_HIP(hipMemcpyAsync(col3.ensure((size_t)(3 * T)), op.col.data(), sizeof(double) * 3 * T, hipMemcpyHostToDevice, h->st));
   XMCA_HIP(hipMemcpyAsync(hbar.ensure((size_t)T), op.hbar.data(), sizeof(double) * T, hipMemcpyHostToDevice, h->st));
-  XMCA_HIP(hipMemcpyAsync(U.ensure((size_t)(T * op.r) + 1), op.U.data(), sizeof(double) * T * op.r, hipMemcpyHostToDevice, h->st));
-  XMCA_HIP(hipMemcpyAsync(W.ensure((size_t)(T * op.r) + 1), op.W.data(), sizeof(double) * T * op.r, hipMemcpyHostToDevice, h->st));
+  U.ensure((size_t)(T * op.r) + 1);
+  W.ensure((size_t)(T * op.r) + 1);
+  if (op.r > 0) {                 // (rank 0: the operator of extend='theta', nothing to copy)
+    XMCA_HIP(hipMemcpyAsync(U.get(), op.U.data(), sizeof(double) * T * op.r, hipMemcpyHostToDevice, h->st));
+    XMCA_HIP(hipMemcpyAsync(W.get(), op.W.data(), sizeof(double) * T * op.r, hipMemcpyHostToDevice, h->st));
+  }
   hipLaunchKernelGGL((extended_operator_kernel<TI>), ew_grid(T * T), dim3(EW_BLOCK), 0, h->st, col3.get(), hbar.get(), U.get(), W.get(),
                      op.r, (int)T, g.ensure((size_t)T * T));
   XMCA_HIP(hipGetLastError());
@@ -339,12 +359,34 @@ void complexify_impl(xmca_handle* h, const ComplexOp& op) {
   DevBuf<TI> htb;
   build_operator<TI>(h, op, htb);
   struct { const TI* r; } ht{htb.get()};
+  // extend='theta': the fits of every column first, C (2 (THETA_HEAD + m) x N per field); they stay on the device
+  const bool theta = op.kind == ComplexOp::THETA;
+  DevBuf<double> fit[2], bdev;
+  const int kb = theta ? (int)(2 * theta_fit_rows(op.period)) : 0;
+  if (theta) {
+    XMCA_CHECK((std::is_same<TI, double>::value), XMCA_ERR_STATE, "complexify_theta: the fields must be float64");
+    XMCA_CHECK((int64_t)op.B.size() == T * kb, XMCA_ERR_STATE, "complexify_theta: inconsistent parts");
+    XMCA_HIP(hipMemcpyAsync(bdev.ensure(op.B.size()), op.B.data(), sizeof(double) * op.B.size(), hipMemcpyHostToDevice, h->st));
+    h->tm.begin("theta_fit");
+    if constexpr (std::is_same<TI, double>::value) {
+      for (int s = 0; s < 2; ++s)
+        if (h->field_set[s]) theta_fit(h->st, f[s].r(), T, f[s].N, op.period, fit[s].ensure((size_t)kb * f[s].N));
+    }
+    h->tm.end();
+  }
   h->tm.begin(op.kind == ComplexOp::CIRCULANT ? "hilbert" : "hilbert_extended");
   for (int s = 0; s < 2; ++s) {
     if (!h->field_set[s]) continue;
     GemmOpts o;   // X_im = Ht X (or G X)   (T x T) (T x N)
     TI* dst = f[s].im.ensure((size_t)T * f[s].N);
     gemm<TI, TI>(h->st, h->gws, ht.r, T, f[s].r(), f[s].N, dst, f[s].N, (int)T, (int)f[s].N, (int)T, o);
+    if constexpr (std::is_same<TI, double>::value) {
+      if (theta) {   // X_im += B C   (T x kb) (kb x N)
+        GemmOpts acc;
+        acc.beta = 1.0;
+        gemm<double, double>(h->st, h->gws, bdev.get(), kb, fit[s].get(), f[s].N, dst, f[s].N, (int)T, (int)f[s].N, kb, acc);
+      }
+    }
     f[s].has_im = true;
     f[s].ext_im = nullptr;
   }
@@ -502,7 +544,7 @@ void project_impl(xmca_handle* h, int side, const void* V, int64_t N, int64_t m,
   FieldData<TI>& f = typed<TI>(h).f[side];
   XMCA_CHECK(f.N == N, XMCA_ERR_INVALID, "project: V has " + std::to_string(N) + " rows, the field has " + std::to_string(f.N) + " columns");
   const int64_t T = f.T;
-  if (h->op_pending && h->op.kind == ComplexOp::EXTENDED) {     // no implicit form: the imaginary planes G X are formed first
+  if (h->op_pending && h->op.kind != ComplexOp::CIRCULANT) {    // no implicit form: the imaginary planes G X (+ B C) are formed first
     complexify_impl<TI>(h, h->op);
     h->op_pending = false;
   }
@@ -1401,10 +1443,8 @@ int xmca_complexify(xmca_handle* h, const double* hilbert_col) {
   API_END(h)
 }
 
-int xmca_complexify_extended(xmca_handle* h, const double* col3, const double* hbar, const double* U, const double* W, int rank) {
-  API_BEGIN(h)
-  XMCA_CHECK(h->field_set[0], XMCA_ERR_STATE, "complexify_extended: set a field first");
-  check_extended_parts("complexify_extended", col3, hbar, U, W, rank);
+// the resident real float32 fields become float64 fields (xmca_complexify_extended, xmca_complexify_theta)
+static void promote_fields(xmca_handle* h) {
   if (h->dtype == XMCA_F32) {     // (not a dispatch: only float32 fields are moved, from typed<float> to typed<double>)
     // the reference extends in float64 (the forecast of a float32 column is float64, array.py:394-410): the resident real
     // float32 fields become float64 fields, exactly (every float32 is a float64)
@@ -1424,11 +1464,79 @@ int xmca_complexify_extended(xmca_handle* h, const double* col3, const double* h
     }
     h->dtype = XMCA_F64;
   }
+}
+
+int xmca_complexify_extended(xmca_handle* h, const double* col3, const double* hbar, const double* U, const double* W, int rank) {
+  API_BEGIN(h)
+  XMCA_CHECK(h->field_set[0], XMCA_ERR_STATE, "complexify_extended: set a field first");
+  check_extended_parts("complexify_extended", col3, hbar, U, W, rank);
+  promote_fields(h);
   const int64_t T = h->s64.f[0].T;
   check_operator_size("complexify_extended", T);
   h->op = ComplexOp::extended(col3, hbar, U, W, rank, T);
   h->op_pending = true;           // xmca_solve / xmca_project form X_im = G X (there is no subspace formulation of G)
   h->solved = false;
+  API_END(h)
+}
+
+int xmca_complexify_theta(xmca_handle* h, const double* col3, const double* hbar, const double* B, int period) {
+  API_BEGIN(h)
+  XMCA_CHECK(h->field_set[0], XMCA_ERR_STATE, "complexify_theta: set a field first");
+  XMCA_CHECK(col3 && hbar && B, XMCA_ERR_INVALID, "complexify_theta: need col3, hbar and the T x 2 (2 + period) matrix B");
+  const int64_t T = resident_T(h);
+  XMCA_CHECK(period >= 1 && T >= 2 * (int64_t)period, XMCA_ERR_INVALID, "complexify_theta: period must be >= 1 and T >= 2 period");
+  check_operator_size("complexify_theta", T);
+  promote_fields(h);
+  h->op = ComplexOp::theta(col3, hbar, B, period, T);
+  h->op_pending = true;           // xmca_solve / xmca_project / xmca_get_field_imag form X_im = G0 X + B C
+  h->solved = false;
+  API_END(h)
+}
+
+int xmca_theta_fit(xmca_handle* h, int side, int period, double* out) {
+  API_BEGIN(h)
+  check_side("theta_fit", side);
+  XMCA_CHECK(h->field_set[side] && out, XMCA_ERR_STATE, "theta_fit: set the field first");
+  const int64_t T = resident_T(h), N = resident_N(h, side);
+  XMCA_CHECK(period >= 1 && T >= 2 * (int64_t)period, XMCA_ERR_INVALID, "theta_fit: period must be >= 1 and T >= 2 period");
+  check_operator_size("theta_fit", T);
+  const int64_t rows = theta_fit_rows(period), keep = 3 + period;
+  DevBuf<double> wide, fit;
+  const double* x = nullptr;
+  with_dtype(h->dtype, [&](auto t) {
+    using TI = decltype(t);
+    const FieldData<TI>& f = typed<TI>(h).f[side];
+    if constexpr (std::is_same<TI, double>::value) {
+      x = f.r();
+    } else {
+      hipLaunchKernelGGL((convert_kernel<float, double>), ew_grid(T * N), dim3(EW_BLOCK), 0, h->st, f.r(), wide.ensure((size_t)(T * N)), T * N);
+      XMCA_HIP(hipGetLastError());
+      x = wide.get();
+    }
+  });
+  theta_fit(h->st, x, T, N, period, fit.ensure((size_t)(2 * rows * N)));
+  std::vector<double> host((size_t)(2 * rows * N));
+  XMCA_HIP(hipMemcpyAsync(host.data(), fit.get(), sizeof(double) * host.size(), hipMemcpyDeviceToHost, h->st));
+  XMCA_HIP(hipStreamSynchronize(h->st));
+  for (int d = 0; d < 2; ++d)
+    for (int64_t r = 0; r < keep; ++r)       // alpha, b0, level, then the seasonal means (the two forecast coefficients between are left out)
+      std::memcpy(out + (d * keep + r) * N, host.data() + (d * rows + (r < 3 ? r : r + 2)) * N, sizeof(double) * (size_t)N);
+  API_END(h)
+}
+
+int xmca_get_field_imag(xmca_handle* h, int side, double* out) {
+  API_BEGIN(h)
+  check_side("get_field_imag", side);
+  XMCA_CHECK(h->field_set[side] && out, XMCA_ERR_STATE, "get_field_imag: no field resident for this side");
+  XMCA_CHECK(h->dtype == XMCA_F64, XMCA_ERR_STATE, "get_field_imag: only after xmca_complexify_extended / xmca_complexify_theta");
+  if (h->op_pending && h->op.kind != ComplexOp::CIRCULANT) {
+    complexify_impl<double>(h, h->op);
+    h->op_pending = false;
+  }
+  const FieldData<double>& f = h->s64.f[side];
+  XMCA_CHECK(f.has_im && f.i(), XMCA_ERR_STATE, "get_field_imag: the field has no imaginary plane");
+  XMCA_HIP(hipMemcpyAsync(out, f.i(), sizeof(double) * (size_t)f.T * f.N, hipMemcpyDeviceToHost, h->st));
+  XMCA_HIP(hipStreamSynchronize(h->st));
   API_END(h)
 }
 
