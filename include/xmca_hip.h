@@ -360,6 +360,21 @@ int xmca_bootstrap_runs_columns(xmca_handle* h, const double* hilbert_col, const
 int xmca_bootstrap_runs_columns_extended(xmca_handle* h, const double* col3, const double* hbar, const double* U, const double* W,
                                          int rank, const int64_t* cols_left, const int64_t* cols_right, int64_t n_runs, int rotated,
                                          int p, int power, double tol, double* spectra_out, int* kept_out, int64_t n_out);
+/* xmca_bootstrap_runs / xmca_bootstrap_runs_columns of a model solved with extend='theta' (entry points added to ABI 15 - no existing
+ * signature changes).  col3, hbar, B and period are the arguments of xmca_complexify_theta for T = the T of xmca_bootstrap_begin.
+ * The Theta fit is not linear in the column, so nothing of it carries over from the model: every replicate is gathered, centred,
+ * FITTED AGAIN by the kernels of csrc/theta.h, and complexified as X_im = G0 X + B C, the arithmetic of xmca_complexify_theta,
+ * on its lane's stream.  A lane owns its operator G0, its copy of B and one fit buffer (2 (5 + period) x N float64) per field; the
+ * handle keeps none of them after the call.  The stage timers of the call show "resample" and "theta_fit".
+ * Refused before anything is launched: the errors of xmca_bootstrap_runs; a missing col3, hbar or B, period < 1 or T < 2 period, and
+ * working copies that are not float64 (XMCA_ERR_INVALID: the reference's replicates are float64); no xmca_bootstrap_begin
+ * (XMCA_ERR_STATE); T above the bound of the T x T assembly (XMCA_ERR_UNSUPPORTED).  Outputs as for the entries above. */
+int xmca_bootstrap_runs_theta(xmca_handle* h, const double* col3, const double* hbar, const double* B, int period,
+                              const int64_t* idx_left, const int64_t* idx_right, int64_t n_runs, int rotated, int p, int power,
+                              double tol, double* spectra_out, int* kept_out, int64_t n_out);
+int xmca_bootstrap_runs_columns_theta(xmca_handle* h, const double* col3, const double* hbar, const double* B, int period,
+                                      const int64_t* cols_left, const int64_t* cols_right, int64_t n_runs, int rotated, int p,
+                                      int power, double tol, double* spectra_out, int* kept_out, int64_t n_out);
 int xmca_is_complex(xmca_handle* h);
 /* 1 when the singular vectors of `side` from the last xmca_solve are resident in float32: a real float32 field decomposed on
  * its dual side (N > T) keeps `_V` in the input's dtype as the reference does (xmca/array.py:584, the dtype of

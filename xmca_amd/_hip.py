@@ -58,6 +58,9 @@ SIGNATURES = {
     "xmca_bootstrap_runs_columns": (_c_int, [_vp, _vp, _vp, _vp, _c_i64, _c_int, _c_int, _c_int, _c_dbl, _vp, _vp, _c_i64]),
     "xmca_bootstrap_runs_columns_extended": (_c_int, [_vp, _vp, _vp, _vp, _vp, _c_int, _vp, _vp, _c_i64, _c_int, _c_int, _c_int, _c_dbl,
                                                       _vp, _vp, _c_i64]),
+    "xmca_bootstrap_runs_theta": (_c_int, [_vp, _vp, _vp, _vp, _c_int, _vp, _vp, _c_i64, _c_int, _c_int, _c_int, _c_dbl, _vp, _vp, _c_i64]),
+    "xmca_bootstrap_runs_columns_theta": (_c_int, [_vp, _vp, _vp, _vp, _c_int, _vp, _vp, _c_i64, _c_int, _c_int, _c_int, _c_dbl, _vp, _vp,
+                                                   _c_i64]),
     "xmca_correlate": (_c_int, [_vp, _c_int, _vp, _c_i64, _c_i64, _vp]),
     "xmca_pearson_pvalues": (_c_int, [_vp, _vp, _c_i64, _c_i64, _vp]),
     "xmca_pvalue_log_norm": (_c_int, [_c_i64, _dp]),
@@ -703,13 +706,18 @@ class Handle:
         self.release_result()
         self._check(self._lib.xmca_bootstrap_begin(self._h, n_fields))
 
-    def bootstrap_runs(self, T, complexify, idx_left, idx_right, n_runs, rotated, p, power, tol, n_out, extend_period=None, axis=0):
+    def bootstrap_runs(self, T, complexify, idx_left, idx_right, n_runs, rotated, p, power, tol, n_out, extend_period=None,
+                       theta_period=None, axis=0):
         """All replicates in one call (several in flight on the device).  idx_*: COMPOSED indices into the fields as they were at
         `bootstrap_begin`, or None - axis=0: (n_runs, T) row indices; axis=1: (n_runs, Nl) / (n_runs, Nr) column indices into
         [left | right] (xmca_bootstrap_runs_columns*).  `extend_period`: replicates of a complex model with extend='exp' and
-        this period (xmca_bootstrap_runs*_extended; float64 fields).  Returns (spectra[n_runs, n_out], kept[n_runs])."""
+        this period (xmca_bootstrap_runs*_extended; float64 fields).  `theta_period`: replicates of a complex model with
+        extend='theta' and this season length, every one fitted again on the device (xmca_bootstrap_runs*_theta; float64 fields).
+        Returns (spectra[n_runs, n_out], kept[n_runs])."""
         if axis not in (0, 1):
             raise ValueError('{:} not a valid axis. either 0 or 1.'.format(axis))
+        if extend_period is not None and theta_period is not None:
+            raise ValueError("bootstrap_runs: extend_period (extend='exp') and theta_period (extend='theta') exclude each other")
         il = None if idx_left is None else np.ascontiguousarray(idx_left, dtype=np.int64).reshape(n_runs, -1)
         ir = None if idx_right is None else np.ascontiguousarray(idx_right, dtype=np.int64).reshape(n_runs, -1)
         if axis == 0 and any(i is not None and i.shape[1] != T for i in (il, ir)):
@@ -721,6 +729,12 @@ class Handle:
             col3, hbar, U, W = extended_imag_parts(T, extend_period)
             run = getattr(self._lib, "xmca_bootstrap_runs%s_extended" % columns)
             self._check(run(self._h, _ptr(col3), _ptr(hbar), _ptr(U), _ptr(W), U.shape[1], _ptr(il), _ptr(ir), n_runs, int(rotated),
+                            int(p), int(power), float(tol), _ptr(out), _ptr(kept), n_out))
+            return out, kept.astype(bool)
+        if complexify and theta_period is not None:
+            col3, hbar, B = theta_imag_parts(T, theta_period)          # (once per call, not per replicate)
+            run = getattr(self._lib, "xmca_bootstrap_runs%s_theta" % columns)
+            self._check(run(self._h, _ptr(col3), _ptr(hbar), _ptr(B), int(theta_period), _ptr(il), _ptr(ir), n_runs, int(rotated),
                             int(p), int(power), float(tol), _ptr(out), _ptr(kept), n_out))
             return out, kept.astype(bool)
         ht = hilbert_imag_column(T) if complexify else None

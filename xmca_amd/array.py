@@ -1492,9 +1492,13 @@ class MCA:
         cumulative resampling of rows (`axis=0`) or of columns (`axis=1`; of the concatenation [left | right] when both sides are
         resampled), centering, solve, rotation, variance - run on the device (`xmca_bootstrap_runs`, `xmca_bootstrap_runs_columns`).
         A model solved with extend='exp' runs there too, every replicate complexified with the same extended operator in float64
-        (`xmca_bootstrap_runs_extended`, `xmca_bootstrap_runs_columns_extended`).  Only extend='theta' keeps the reference's host
-        loop over the replicates: each replicate is resampled on the host and solved on the device, its Theta extension fitted
-        there too (`xmca_complexify_theta`; statsmodels is not needed).
+        (`xmca_bootstrap_runs_extended`, `xmca_bootstrap_runs_columns_extended`).  So does a model solved with extend='theta':
+        the Theta fit is not linear in a column, so every replicate is fitted again after it has been gathered and centered, by the
+        kernels of the solve, and complexified as X_im = G0 X + B C (`xmca_bootstrap_runs_theta`,
+        `xmca_bootstrap_runs_columns_theta`; statsmodels is not needed).  All of these keep several replicates in flight and are
+        sharded over the ranks of a `torch.distributed` job.  The reference's host loop over the replicates - one model per
+        replicate - remains only for a model whose extension was applied on the host (`_extend_on_host`, private) and behind
+        `_bootstrap_on_host` (private), for comparison.
         """
         complexify = self._analysis['is_complex']
         extend = self._analysis['extend']
@@ -1505,7 +1509,15 @@ class MCA:
         n_modes_max = self._get_min_mode(n_modes, rotated=True)
         var_surr = np.zeros([n_modes_max, n_runs])
         extend_exp = bool(complexify) and extend == 'exp' and getattr(self, '_device_extend', None) is not None
-        on_device = (not extend or extend_exp) and not getattr(self, '_bootstrap_on_host', False)
+        extend_theta = bool(complexify) and extend == 'theta' and getattr(self, '_device_theta', None) is not None
+        on_device = (not extend or extend_exp or extend_theta) and not getattr(self, '_bootstrap_on_host', False)
+        extension = {}
+        if extend_exp:
+            extension['extend_period'] = period
+        if extend_theta:
+            extension['theta_period'] = period
+        if axis == 1:
+            extension['axis'] = 1
         dev = self._device()
         n_obs = self._n_observations['left']
         for mode in range(n_modes):
@@ -1526,8 +1538,7 @@ class MCA:
                 # (replicates are independent once composed: sharded over the ranks of a torch.distributed job like the Rule-N runs)
                 from . import dist
                 spec, kept = dist.sharded_bootstrap(dev, n_runs, T=n_obs, complexify=complexify, idx_left=idx_left, idx_right=idx_right,
-                                                    rotated=is_rotated, p=n_rot, power=max(power, 1), tol=1e-8, n_out=n_out,
-                                                    extend_period=period if extend_exp else None, **({'axis': 1} if axis == 1 else {}))
+                                                    rotated=is_rotated, p=n_rot, power=max(power, 1), tol=1e-8, n_out=n_out, **extension)
                 for run in range(n_runs):
                     if kept[run]:
                         var_surr[mode:, run] = spec[run, :n_modes_max - mode]

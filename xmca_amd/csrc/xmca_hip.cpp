@@ -351,6 +351,26 @@ void build_operator(xmca_handle* h, const ComplexOp& op, DevBuf<TI>& g) {
   XMCA_HIP(hipStreamSynchronize(h->st));
 }
 
+// "Apply this operator to a centred real field", stated once (complexify_impl, ReplicateRunner::run): the imaginary plane of `f`
+// becomes g X, g the T x T device operator of build_operator, plus B C when `bdev` is given (extend='theta': bdev T x kb, `fit`
+// the kb x N Theta fits of X, theta_fit).  Queued on the handle's stream.
+template <typename TI>
+void apply_operator(xmca_handle* h, const TI* g, const double* bdev, const double* fit, int kb, FieldData<TI>& f) {
+  const int64_t T = f.T, N = f.N;
+  GemmOpts o;   // X_im = Ht X (or G X)   (T x T) (T x N)
+  TI* dst = f.im.ensure((size_t)T * N);
+  gemm<TI, TI>(h->st, h->gws, g, T, f.r(), N, dst, N, (int)T, (int)N, (int)T, o);
+  if constexpr (std::is_same<TI, double>::value) {
+    if (bdev) {   // X_im += B C   (T x kb) (kb x N)
+      GemmOpts acc;
+      acc.beta = 1.0;
+      gemm<double, double>(h->st, h->gws, bdev, kb, fit, N, dst, N, (int)T, (int)N, kb, acc);
+    }
+  }
+  f.has_im = true;
+  f.ext_im = nullptr;
+}
+
 template <typename TI>
 void complexify_impl(xmca_handle* h, const ComplexOp& op) {
   FieldData<TI>* f = typed<TI>(h).f;
@@ -375,21 +395,8 @@ void complexify_impl(xmca_handle* h, const ComplexOp& op) {
     h->tm.end();
   }
   h->tm.begin(op.kind == ComplexOp::CIRCULANT ? "hilbert" : "hilbert_extended");
-  for (int s = 0; s < 2; ++s) {
-    if (!h->field_set[s]) continue;
-    GemmOpts o;   // X_im = Ht X (or G X)   (T x T) (T x N)
-    TI* dst = f[s].im.ensure((size_t)T * f[s].N);
-    gemm<TI, TI>(h->st, h->gws, ht.r, T, f[s].r(), f[s].N, dst, f[s].N, (int)T, (int)f[s].N, (int)T, o);
-    if constexpr (std::is_same<TI, double>::value) {
-      if (theta) {   // X_im += B C   (T x kb) (kb x N)
-        GemmOpts acc;
-        acc.beta = 1.0;
-        gemm<double, double>(h->st, h->gws, bdev.get(), kb, fit[s].get(), f[s].N, dst, f[s].N, (int)T, (int)f[s].N, kb, acc);
-      }
-    }
-    f[s].has_im = true;
-    f[s].ext_im = nullptr;
-  }
+  for (int s = 0; s < 2; ++s)
+    if (h->field_set[s]) apply_operator<TI>(h, ht.r, theta ? bdev.get() : nullptr, fit[s].get(), kb, f[s]);
   h->tm.end();
   XMCA_HIP(hipStreamSynchronize(h->st));
 }
@@ -1072,6 +1079,10 @@ struct ReplicateRunner {
   double tol;
   bool cplx, analytic;
   DevBuf<TI> htb;
+  // extend='theta' (ComplexOp::THETA): the lane's own copy of B and one fit buffer per field, 2 (THETA_HEAD + m) x N, reused by
+  // every replicate of the lane.  The season kernel accumulates its phase sums in the fit buffer: no two lanes may share one.
+  int period = 0, kb = 0;
+  DevBuf<double> bdev, fit[2];
   Solver<TI> solver;
   Rotator rot;
   SolveResult res;
@@ -1084,20 +1095,32 @@ struct ReplicateRunner {
     const ComplexOp* op = s.op;
     analytic = cplx && Solver<TI>::analytic_route(op->kind == ComplexOp::CIRCULANT, T, s.Nx, s.Ny, n_fields, false);
     if (cplx) XMCA_CHECK(op->T == T, XMCA_ERR_INVALID, "replicates: the operator was made for another number of time steps");
+    if (cplx && op->kind == ComplexOp::THETA) {
+      XMCA_CHECK((std::is_same<TI, double>::value), XMCA_ERR_INVALID, "replicates: the Theta extension needs float64 fields");
+      period = op->period;
+      kb = (int)(2 * theta_fit_rows(period));
+      XMCA_CHECK(period >= 1 && T >= 2 * (int64_t)period && (int64_t)op->B.size() == T * kb, XMCA_ERR_STATE,
+                 "replicates: inconsistent parts of the Theta extension");
+      // (the copy has landed when build_operator below has synchronised the stream)
+      XMCA_HIP(hipMemcpyAsync(bdev.ensure(op->B.size()), op->B.data(), sizeof(double) * op->B.size(), hipMemcpyHostToDevice, h->st));
+      for (int k = 0; k < n_fields; ++k) fit[k].ensure((size_t)kb * Ns[k]);
+    }
     if (cplx && !analytic) build_operator<TI>(h, *op, htb);
   }
   int64_t rank() const { return std::min(T, n_fields == 2 ? std::min(Ns[0], Ns[1]) : Ns[0]); }
 
   // f[s].re holds the centered field; returns 1 (kept) or 0 (Varimax failed: the replicate is dropped, array.py:1762-1763)
   int run(FieldData<TI>* f, double* out, int64_t n_out) {
+    if constexpr (std::is_same<TI, double>::value) {
+      if (kb > 0) {     // the Theta fits C of the centred replicate, as complexify_impl fits the resident field
+        h->tm.begin("theta_fit");
+        for (int s = 0; s < n_fields; ++s) theta_fit(h->st, f[s].r(), T, Ns[s], period, fit[s].get());
+        h->tm.end();
+      }
+    }
     for (int s = 0; s < n_fields; ++s) {
       f[s].has_im = false;
-      if (cplx && !analytic) {
-        GemmOpts o;
-        gemm<TI, TI>(h->st, h->gws, htb.get(), T, f[s].r(), Ns[s], f[s].im.ensure((size_t)(T * Ns[s])), Ns[s], (int)T, (int)Ns[s], (int)T, o);
-        f[s].has_im = true;
-        f[s].ext_im = nullptr;
-      }
+      if (cplx && !analytic) apply_operator<TI>(h, htb.get(), kb > 0 ? bdev.get() : nullptr, fit[s].get(), kb, f[s]);
     }
     if (analytic) solver.solve_analytic(f, n_fields, rotated ? p : 0, res);
     else solver.solve(f, n_fields, cplx, rotated ? p : 0, res);
@@ -1335,6 +1358,22 @@ void bootstrap_runs_extended_entry(xmca_handle* h, int axis, const double* col3,
   XMCA_CHECK(h->dtype == XMCA_F64, XMCA_ERR_INVALID, "bootstrap: the extended operator needs float64 fields (the reference's replicates are float64)");
   check_operator_size("bootstrap", h->boot_T);
   const ComplexOp op = ComplexOp::extended(col3, hbar, U, W, rank, h->boot_T);
+  bootstrap_runs_impl<double>(h, &op, axis, idx_left, idx_right, n_runs, rotated, p, power, tol, spectra_out, kept_out, n_out);
+  h->tm.collect();
+}
+
+// xmca_bootstrap_runs_theta / xmca_bootstrap_runs_columns_theta: replicates complexified with the Theta fore/back-cast, every
+// replicate fitted again on its lane (ReplicateRunner)
+void bootstrap_runs_theta_entry(xmca_handle* h, int axis, const double* col3, const double* hbar, const double* B, int period,
+                                const int64_t* idx_left, const int64_t* idx_right, int64_t n_runs, int rotated, int p, int power,
+                                double tol, double* spectra_out, int* kept_out, int64_t n_out) {
+  check_bootstrap_runs(spectra_out, kept_out, n_out, n_runs, rotated, p, power);
+  XMCA_CHECK(col3 && hbar && B, XMCA_ERR_INVALID, "bootstrap: need col3, hbar and the T x 2 (2 + period) matrix B");
+  XMCA_CHECK(h->boot_fields >= 1 && h->boot_T > 0, XMCA_ERR_STATE, "bootstrap: call xmca_bootstrap_begin first");
+  XMCA_CHECK(h->dtype == XMCA_F64, XMCA_ERR_INVALID, "bootstrap: the Theta extension needs float64 fields (the reference's replicates are float64)");
+  XMCA_CHECK(period >= 1 && h->boot_T >= 2 * (int64_t)period, XMCA_ERR_INVALID, "bootstrap: period must be >= 1 and T >= 2 period");
+  check_operator_size("bootstrap", h->boot_T);
+  const ComplexOp op = ComplexOp::theta(col3, hbar, B, period, h->boot_T);
   bootstrap_runs_impl<double>(h, &op, axis, idx_left, idx_right, n_runs, rotated, p, power, tol, spectra_out, kept_out, n_out);
   h->tm.collect();
 }
@@ -1804,6 +1843,24 @@ int xmca_bootstrap_runs_columns_extended(xmca_handle* h, const double* col3, con
   API_BEGIN(h)
   bootstrap_runs_extended_entry(h, 1, col3, hbar, U, W, rank, cols_left, cols_right, n_runs, rotated, p, power, tol, spectra_out,
                                 kept_out, n_out);
+  API_END(h)
+}
+
+int xmca_bootstrap_runs_theta(xmca_handle* h, const double* col3, const double* hbar, const double* B, int period,
+                              const int64_t* idx_left, const int64_t* idx_right, int64_t n_runs, int rotated, int p, int power,
+                              double tol, double* spectra_out, int* kept_out, int64_t n_out) {
+  API_BEGIN(h)
+  bootstrap_runs_theta_entry(h, 0, col3, hbar, B, period, idx_left, idx_right, n_runs, rotated, p, power, tol, spectra_out, kept_out,
+                             n_out);
+  API_END(h)
+}
+
+int xmca_bootstrap_runs_columns_theta(xmca_handle* h, const double* col3, const double* hbar, const double* B, int period,
+                                      const int64_t* cols_left, const int64_t* cols_right, int64_t n_runs, int rotated, int p,
+                                      int power, double tol, double* spectra_out, int* kept_out, int64_t n_out) {
+  API_BEGIN(h)
+  bootstrap_runs_theta_entry(h, 1, col3, hbar, B, period, cols_left, cols_right, n_runs, rotated, p, power, tol, spectra_out, kept_out,
+                             n_out);
   API_END(h)
 }
 

@@ -217,13 +217,16 @@ def broadcast_array(a, dev=None):
     return t.cpu().numpy()
 
 
-def sharded_bootstrap(dev, n_runs, *, T, complexify, idx_left, idx_right, rotated, p, power, tol, n_out, extend_period=None, axis=0):
+def sharded_bootstrap(dev, n_runs, *, T, complexify, idx_left, idx_right, rotated, p, power, tol, n_out, extend_period=None,
+                      theta_period=None, axis=0):
     """Bootstrap replicates sharded like the Rule-N runs (xmca/array.py:1935-1947 is the loop; the replicates are independent once
     the row indices are COMPOSED on the host): rank r runs the contiguous block [r*n/W, (r+1)*n/W) of replicates on its own GPU
     (which holds the same fields), ONE all_gather of (n_out + 1) float64 per replicate.  `idx_*`: (n_runs, T) composed row
     indices (axis=0), (n_runs, Nl) / (n_runs, Nr) composed column indices into [left | right] (axis=1), or None; rank 0's draws
-    are used on every rank (they come from numpy's GLOBAL generator, which the ranks need not share).  `extend_period`: replicates of a complex model with extend='exp' (`_hip.Handle.bootstrap_runs`).  Returns (spectra
-    [n_runs x n_out], kept [n_runs] bool) on every rank; any rank's failure raises on all of them."""
+    are used on every rank (they come from numpy's GLOBAL generator, which the ranks need not share).  `extend_period`: replicates
+    of a complex model with extend='exp'; `theta_period`: of one with extend='theta', every replicate fitted again on its rank's
+    GPU (`_hip.Handle.bootstrap_runs`; each keyword is forwarded only when it is set).  Returns (spectra [n_runs x n_out], kept
+    [n_runs] bool) on every rank; any rank's failure raises on all of them."""
     td = _dist()
     rank, world = rank_world()
     if td is not None:
@@ -237,6 +240,8 @@ def sharded_bootstrap(dev, n_runs, *, T, complexify, idx_left, idx_right, rotate
     try:
         if end > begin:
             ext = {} if extend_period is None else {"extend_period": extend_period}
+            if theta_period is not None:
+                ext["theta_period"] = theta_period
             if axis != 0:
                 ext["axis"] = axis
             spec, kept = dev.bootstrap_runs(T, complexify, None if idx_left is None else idx_left[begin:end],
