@@ -10,7 +10,7 @@ for f in sys.argv[1:]:
     a = np.loadtxt(f)
     n = a.shape[0]
     st = a[:, 1:7].copy()
-    st[st > 1e15] = np.nan                      # (a stamp that was not taken: the tagged exchange has no drain / poll)
+    st[st > 1e15] = np.nan                      # (a stamp that was not taken - stamp 5 never is: the exchange has no drain / poll, so the last two phases are not printed)
     d = np.diff(np.concatenate([np.zeros((n, 1)), st], axis=1), axis=1)
     print("%s: n = %d, %.0f cycles per column" % (f, n, a[1:, 0].mean()))
     for lo, hi in ((0, n // 4), (n // 4, n // 2), (n // 2, 3 * n // 4), (3 * n // 4, n - 1)):

@@ -545,12 +545,10 @@ def test_rule_n_spectra_do_not_depend_on_the_number_of_lanes():
             assert np.array_equal(o[k], outs[0][k]), k
 
 
-@pytest.mark.parametrize("tagged", ["1", "0"])
-def test_persistent_reduction_gives_the_same_bits_for_one_and_two_lanes_in_both_exchange_forms(tagged):
-    """The persistent tridiagonal reduction (eigenproblems of 451 rows: T = 900 complex) inside 1 and 2 surrogate lanes, with
-    the tagged exchange and with the epoch flags (XMCA_TRD_TAGGED=0).  Inside lanes the tagged form deals CONTIGUOUS rows to
-    the workgroups (they leave early); the flags form sums per-workgroup partials of p^H v, so its row ownership must not
-    depend on the lane count (advisor, round 4: it did) - a rank that holds a single run gets one lane, its neighbour three."""
+def test_persistent_reduction_gives_the_same_bits_for_one_and_two_lanes():
+    """The persistent tridiagonal reduction (eigenproblems of 451 rows: T = 900 complex) inside 1 and 2 surrogate lanes.  Inside
+    lanes it deals CONTIGUOUS rows to the workgroups (they leave early); the arithmetic of a row must not depend on its owner,
+    hence not on the lane count - a rank that holds a single run gets one lane, its neighbour three."""
     import subprocess
     import tempfile
     code = ("import sys, numpy as np; sys.path.insert(0, %r); from xmca_amd import _hip; h = _hip.Handle(0);"
@@ -561,7 +559,7 @@ def test_persistent_reduction_gives_the_same_bits_for_one_and_two_lanes_in_both_
     with tempfile.TemporaryDirectory() as tmp:
         for lanes in ("1", "2"):
             dst = os.path.join(tmp, "l%s.npz" % lanes)
-            env = dict(os.environ, XMCA_RULE_N_LANES=lanes, XMCA_TRD_TAGGED=tagged)
+            env = dict(os.environ, XMCA_RULE_N_LANES=lanes)
             r = subprocess.run([sys.executable, "-c", code, dst], env=env, capture_output=True, text=True, timeout=600)
             assert r.returncode == 0, r.stderr[-2000:]
             outs.append(dict(np.load(dst)))

@@ -4,7 +4,7 @@ replaces LAPACK's *gesdd / eigh on the T x T stage of xmca/array.py:479 and :570
 768 (with vectors) and more.  Everything against numpy.linalg.eigh / eigvalsh on the same matrices:
 
 * both forms of the reduction - one launch per column, and the persistent kernel with the matrix resident in registers
-  (its column exchange by tagged values and by epoch flags) - real and complex, sizes around the chunk / row-slot boundaries of the kernels;
+  (its columns exchanged as tagged values) - real and complex, sizes around the chunk / row-slot boundaries of the kernels;
 * spectra the twisted vectors cannot resolve (repeated eigenvalues, wide null spaces) come back through the Jacobi sweeps;
 * bit-reproducibility (every sum has a fixed order) and NaN input -> LinAlgError like gesdd.
 """
@@ -25,13 +25,11 @@ def _gram(n, cplx, seed=None, spikes=20):
 
 
 def _reduction_form(monkeypatch, form):
-    """"0": one launch per column; "tagged" / "flags": the persistent kernel with either form of its column exchange"""
+    """"0": one launch per column; "tagged": the persistent kernel (its columns exchanged as tagged values)"""
     monkeypatch.setenv("XMCA_TRD_RESIDENT", "0" if form == "0" else "1")
-    if form != "0":
-        monkeypatch.setenv("XMCA_TRD_TAGGED", "1" if form == "tagged" else "0")
 
 
-@pytest.mark.parametrize("resident", ["tagged", "flags", "0"])
+@pytest.mark.parametrize("resident", ["tagged", "0"])
 @pytest.mark.parametrize("n,cplx", [(2, False), (3, True), (64, False), (127, True), (129, False), (385, False), (512, True), (1000, False),
                                     (1025, True), (1100, False), (2049, False), (2100, True)])
 def test_eigenvalues_only_match_lapack(hip, monkeypatch, n, cplx, resident):
@@ -94,7 +92,7 @@ def test_indefinite_matrix_with_zero_diagonal(hip, monkeypatch, cplx, scale):
     assert np.max(np.linalg.norm(A @ U - U * lam, axis=0)) < 1e-12 * nrm
 
 
-@pytest.mark.parametrize("resident", ["tagged", "flags", "0"])
+@pytest.mark.parametrize("resident", ["tagged", "0"])
 @pytest.mark.parametrize("n,cplx", [(70, False), (200, True), (777, False), (1000, True), (1500, False)])
 def test_eigenvectors_match_lapack(hip, monkeypatch, n, cplx, resident):
     monkeypatch.setenv("XMCA_TRIDIAG_VEC_MIN_N", "2")
@@ -269,3 +267,25 @@ def test_chain_at_the_instantiation_boundaries(hip, monkeypatch, n, cplx):
     assert np.array_equal(lam, one)
     ref = np.linalg.eigvalsh(G)[::-1]
     assert np.max(np.abs(lam - ref)) < 1e-13 * ref[0]
+
+
+def test_packed_links_give_the_bits_of_the_plain_chain(hip, monkeypatch):
+    """Inside several surrogate lanes the late links of a complex chain are packed (tridiag.h `trd_stage_rr_packed`: more rows
+    per wave, fewer workgroups), and the lane tests run one-link problems: XMCA_TRD_PACK=1 forces the packed instantiations
+    <complex,12,3>, <complex,8,2>, <complex,4,2> here.  Order 1537 is the smallest whose chain is NC = 16 -> 12 -> 8 -> 4 (cuts
+    at 256, 768, 1280).  The arithmetic of a row does not depend on its owner: the same bits as the plain chain."""
+    monkeypatch.setenv("XMCA_TRIDIAG_MIN_N", "2")
+    monkeypatch.setenv("XMCA_TRD_RESIDENT_MIN_N", "2")
+    G = _gram(1537, True)
+    monkeypatch.setenv("XMCA_TRD_PACK", "1")
+    packed, _ = hip.eigh(G, vectors=False)
+    info = hip.reduction_info()
+    assert info.count("trd_resident_kernel<") == 4, info
+    assert "NC=12,RR=3" in info and "NC=8,RR=2" in info and "NC=4,RR=2" in info, info
+    monkeypatch.setenv("XMCA_TRD_PACK", "0")
+    plain, _ = hip.eigh(G, vectors=False)
+    info = hip.reduction_info()
+    assert "NC=12,RR=2" in info and "NC=8,RR=1" in info and "NC=4,RR=1" in info, info
+    assert np.array_equal(packed, plain)
+    ref = np.linalg.eigvalsh(G)[::-1]
+    assert np.max(np.abs(packed - ref)) < 1e-13 * ref[0]

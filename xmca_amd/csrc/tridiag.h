@@ -429,26 +429,31 @@ __global__ __launch_bounds__(TRD_THREADS) void trd_step_kernel(TrdParams P, int 
 // per lane) x RR rows = the last 1024 RR
 // rows - the ones that live longest; earlier rows are streamed from global memory by their owner wave until they die), the
 // three vectors of a step live in LDS as before, and a column costs one all-to-all exchange instead of a pass over HBM:
-//   pass: every wave updates its rows, p_i = tau_j (row . v_j) -> published (write-through stores) together with the
-//         workgroup's partial p^H v and, by its owner, row j+1 of the stored matrix; drain; ONE epoch flag per workgroup;
-//   exchange: one wave polls the flags of all workgroups (bounded), then every thread reads p, the partial sums and row
-//         j+1 with agent-scope (sc1) loads - cdna_hip_programming.md G16 form R1 with sc1 loads in place of the acquire;
+//   pass: every wave updates its rows, p_i = tau_j (row . v_j) -> published (agent-scope write-through stores) into the
+//         exchange records of the next column together with, by its owner, row j+1 of the stored matrix.  Every published
+//         double carries the epoch tag of the column that consumes it in its lowest mantissa bit (below): a value is its
+//         own flag - no drain, no flag store, no poll;
+//   exchange: every thread asks for the records of its own slots with agent-scope (sc1) loads and asks again (bounded) for
+//         exactly those whose tag is still the old one; p^H v is summed by every workgroup from its own copy of v_{j-1};
 //   prologue: as in the step kernel, redundantly in every workgroup.
-// Buffers alternate with the column parity (a workgroup is at most one column ahead of the slowest).  The grid must be
-// resident: one workgroup per CU (the LDS request guarantees it is alone), launched under a process-wide mutex so that two
-// lanes never interleave two persistent grids; a workgroup that is missing makes every spin run out -> give_up -> the host
-// repeats the reduction with the launch-per-column kernels.
+// Records alternate with the column parity (a publishing workgroup is at most one column ahead of the slowest; one whose
+// rows are all dead leaves, see the column loop).  The grid must be resident: one workgroup per CU (the LDS request
+// guarantees it is alone), launched under a process-wide gate so that two lanes never interleave two persistent grids; a
+// workgroup that is missing makes every spin run out -> give_up -> the host repeats the reduction with the
+// launch-per-column kernels.  (Until round 4 the exchange also existed with a drain, one epoch flag per workgroup and a
+// polling wave; the measurements of both forms and the sweeps of their delays are in HISTORY.md.)
 struct TrdSync {
-  double* pub[2][2];      // [parity][re / im]  p_j by global row index
-  double* gpart[2][2];    // partial p^H v per workgroup
-  double* rowbuf[2][2];   // row j of the stored matrix (parity of j), by global column index
-  unsigned int* flags;    // epoch per workgroup
+  // layout kept: removing them re-allocates SGPRs, see profiles/tridiag_exchange_refactor.json (never read; the host leaves them null / 0)
+  double* pub[2][2];
+  double* gpart[2][2];
+  double* rowbuf[2][2];
+  unsigned int* flags;
   int* give_up;
-  int poll_delay;         // 64-cycle units to sleep before the first poll (polling early only disturbs the publishers)
-  int tag_delay;          // tagged exchange: 64-cycle units to sleep before the loads of a column are requested
+  int poll_delay;
+  int tag_delay;
   int contiguous;         // rows of a wave: first_res + RR g + t (its RR rows adjacent) instead of first_res + g + NW t (strided)
   unsigned int spin_limit;  // bounded spins of a wait: 2^20 (~1.5 s) for the first launch of a process on a cold device, 2^17 (~0.2 s) afterwards
-  // Chained launches (round 6, tagged form only): a launch reduces the columns [j_begin, j_end) of the problem it is handed and the
+  // Chained launches (round 6): a launch reduces the columns [j_begin, j_end) of the problem it is handed and the
   // next one - a smaller instantiation, re-packed: fewer slots per vector, fuller rows, fewer publishers - continues on the
   // trailing block.  Handed over: the resident rows (written back to the working copy by the last pass), u_{j-1} and the four
   // scalars of the previous column (hand_u / hand_s), p_{j-1} and row j in the exchange buffers (they keep their tags: the origin
@@ -456,7 +461,7 @@ struct TrdSync {
   int j_begin, j_end, cont;
   double* hand_u[2];      // u_{j_end - 1} by column index (re / im)
   double* hand_s;         // tau (re, im), scale (re, im) of column j_end - 1
-  // Tagged form, round 6: ONE record per slot and column parity holds what column j gathers for slot k - row j's entry and
+  // Round 6: ONE record per slot and column parity holds what column j gathers for slot k - row j's entry and
   // p_{j-1}[k], {row, p} (real, 16 bytes) or {row re, row im, p re, p im} (complex, 32 bytes) - so a consumer asks with one (two)
   // 16-byte load(s) per slot instead of two (four) 8-byte ones: the gather of a column is bound by the number of requests the
   // 256 workgroups put to the L2s, not by their bytes.  Every double still carries its own tag: a torn record is just a stale half.
@@ -464,16 +469,14 @@ struct TrdSync {
   int xch_pb;
 };
 
-
-__device__ __forceinline__ double trd_ld_sc1(const double* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void trd_st_sc1(double* p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-// Tagged exchange (TAG instantiations): the lowest mantissa bit of every published double carries the epoch tag of the
-// column that consumes it, so a value is its own flag - no drain, no flag store, no poll, no partial sums: a consumer asks
-// again for exactly the values whose tag is still the old one.  Buffers alternate with the column parity, so the value a slot
-// held before is the one of two columns ago: tag(j) = ((j + 1) >> 1) & 1 differs between the two, and the first use of each
-// buffer expects 1 over the zero-filled memory.  The tag bit is cleared on arrival: every workgroup sees the same p and
-// row j, rounded down by at most one ulp - below the rounding of the products they come from.
+// Tagged exchange: the lowest mantissa bit of every published double carries the epoch tag of the column that consumes it,
+// so a value is its own flag: a consumer asks again for exactly the values whose tag is still the old one.  Buffers
+// alternate with the column parity, so the value a slot held before is the one of two columns ago: tag(j) = ((j + 1) >> 1) & 1
+// differs between the two, and the first use of each buffer expects 1 over the zero-filled memory.  The tag bit is cleared
+// on arrival: every workgroup sees the same p and row j, rounded down by at most one ulp - below the rounding of the
+// products they come from.
 #ifndef TRD_TAG_MASK
 #define TRD_TAG_MASK 1u
 #endif
@@ -517,11 +520,10 @@ __device__ __forceinline__ void trd_st16_sc1(double* base, int bytes, int voff, 
 }
 
 constexpr int TRD_RES_THREADS = 256;   // one wave per SIMD: 512 registers per lane for the resident rows
-template <bool CPLX, int NC, int RR, bool TAG>
+template <bool CPLX, int NC, int RR>
 __global__ __launch_bounds__(TRD_RES_THREADS) void trd_resident_kernel(TrdParams P, TrdSync S, int first_res) {
   extern __shared__ __attribute__((aligned(16))) double trd_lds[];
   __shared__ double red2[2][2][TRD_RES_THREADS / 64][2];   // [column parity][which sum]: block sums with one barrier each
-  __shared__ double gam_sh[TRD_RES_THREADS / 64][2];
   __shared__ double dj_sh;
   __shared__ double pj_sh[2][2], a0_sh[2][2];                // [column parity]: p_{j-1}[j] and column j's first sub-diagonal entry
   __shared__ double rowpart[2][TRD_RES_THREADS / 64][2];     // streamed rows: the waves' shares of row . v
@@ -563,15 +565,6 @@ __global__ __launch_bounds__(TRD_RES_THREADS) void trd_resident_kernel(TrdParams
   double* bV[2] = {trd_lds, trd_lds + 3 * LV};                       // v_{j-1}   (re, im)
   double* bW[2] = {trd_lds + LV, trd_lds + 4 * LV};                  // w_{j-1}
   double* bX[2] = {trd_lds + 2 * LV, trd_lds + 5 * LV};              // column j -> v_j
-  // every pointer of the exchange in registers once (indexing the kernel arguments with the parity costs a scalar load
-  // and a wait per access)
-  double* const pub_r[2] = {S.pub[0][0], S.pub[1][0]};
-  double* const pub_i[2] = {S.pub[0][1], S.pub[1][1]};
-  double* const gp_r[2] = {S.gpart[0][0], S.gpart[1][0]};
-  double* const gp_i[2] = {S.gpart[0][1], S.gpart[1][1]};
-  double* const rb_r[2] = {S.rowbuf[0][0], S.rowbuf[1][0]};
-  double* const rb_i[2] = {S.rowbuf[0][1], S.rowbuf[1][1]};
-  unsigned int* const flags = S.flags;
   // ---- resident rows -> registers (rows beyond the matrix: zeros, they stay zero) ----
   double2 ar[RR][NC], ai[RR][NC];
 #pragma unroll
@@ -596,7 +589,7 @@ __global__ __launch_bounds__(TRD_RES_THREADS) void trd_resident_kernel(TrdParams
   double spr = 0.0, spi = 0.0;                     // ... and the scale of its reflector: v_{j-1} = u_{j-1} (spr + i spi) beyond its leading 1
   __syncthreads();
 
-  if (TAG && S.cont) {                             // continue a previous launch: u_{j-1} (zero below j) and its scalars
+  if (S.cont) {                                    // continue a previous launch: u_{j-1} (zero below j) and its scalars
     for (int s = tid; s < LV; s += TRD_RES_THREADS) {
       const bool in = s >= S.j_begin && s < n;
       bV[0][s] = in ? S.hand_u[0][s] : 0.0;
@@ -607,32 +600,24 @@ __global__ __launch_bounds__(TRD_RES_THREADS) void trd_resident_kernel(TrdParams
     __syncthreads();
   }
   const bool prof = P.prof && is_writer && tid == 0;
-  const bool cont = TAG && S.cont != 0;
+  const bool cont = S.cont != 0;
   const int j_end = S.j_end;
   // (an earlier launch of the chain ran out of its spins: nothing to do, the host starts again)
   for (int j = (cont && S.give_up[0]) ? j_end : S.j_begin; j < j_end; ++j) {
     const bool has_prev = j > 0 || cont;
-    // Tagged exchange: a workgroup whose rows are all dead has nothing left to publish - so nobody waits for it - and nothing
+    // A workgroup whose rows are all dead has nothing left to publish - so nobody waits for it - and nothing
     // to update: it leaves.  Staying on as a listener was a hazard: it is not flow-controlled, and once it fell two columns
     // behind (a second surrogate lane's kernels on its CU are enough) the live workgroups had overwritten the slots it was
     // still waiting for with the tag of the column after next - its spins ran out, the whole reduction was repeated launch by
     // launch (0.2 s; with two lanes at n = 451 complex in nearly every call, at n = 2000 in one of thirty).
-    if (TAG && !is_writer && wg_last <= j) break;
+    if (!is_writer && wg_last <= j) break;
     const int prev = (j + 1) & 1, cur = j & 1;
     const int m = n - j - 1;
     if (prof) P.prof[8 * j + 0] = __builtin_amdgcn_s_memtime();
-    // ---- prologue: p_{j-1}, its partial sums, row j - every load requested at once, no predicates (the buffers are
-    // zero-filled before the launch and hold row 0 in rowbuf[0]: column 0 needs no special case) ----
-    const double* const prr = pub_r[prev];
-    const double* const pri = pub_i[prev];
-    // (tagged exchange: row 0 is put into the records of parity 0 by trd_prefill_kernel, tag bits cleared - column 2 expects 1)
-    const double* const rwr = rb_r[cur];
-    const double* const rwi = rb_i[cur];
+    // ---- prologue: p_{j-1}, row j - every load requested at once, no predicates (the records are zero-filled before the
+    // launch and row 0 is put into those of parity 0 by trd_prefill_kernel, tag bits cleared - column 2 expects 1: column 0
+    // needs no special case) ----
     double gr = 0.0, gi = 0.0;
-    if (!TAG && tid < nwg) {
-      gr = trd_ld_sc1(gp_r[prev] + tid);
-      if (CPLX) gi = trd_ld_sc1(gp_i[prev] + tid);
-    }
     // ---- the reflector of the PREVIOUS column gets its scale here (round 5): column j-1 left u_{j-1} = x - beta e_j in what is
     // now bV and ran its pass on that (p = tau s A u is linear in the scale s), so the scaling sits in the wait of the exchange -
     // the values of column j are still on their way - instead of between two barriers in front of the pass.
@@ -680,79 +665,61 @@ __global__ __launch_bounds__(TRD_RES_THREADS) void trd_resident_kernel(TrdParams
         }
       }
     }
-    if (TAG && has_prev) {
-      // (a request that arrives before the values costs a whole round trip: better to ask a little later)
-      for (int q = 0; q < S.tag_delay; ++q) __builtin_amdgcn_s_sleep(1);
-    }
     double lr_[NS], li_[NS], lp_[NS], lq_[NS];
-    // (tagged: the records of this column's parity; slot k = tid + 256 t sits 16 * 256 t bytes - a scalar offset - behind the thread's first)
+    // (the records of this column's parity; slot k = tid + 256 t sits 16 * 256 t bytes - a scalar offset - behind the thread's first)
     const int xrd = cur * S.xch_pb, xwr = prev * S.xch_pb, xbytes = 2 * S.xch_pb, xhalf = S.xch_pb >> 1;
     auto gather_slot = [&](int t) {
-      if constexpr (TAG) {
-        const int soff = xrd + t * (16 * TRD_RES_THREADS);
-        if constexpr (CPLX) {                      // (complex: the {re, im} records of the row, then - half a parity further on - those of p)
-          trd_ld16_sc1(S.xch, xbytes, tid * 16, soff, lr_[t], li_[t]);
-          trd_ld16_sc1(S.xch, xbytes, tid * 16, soff + xhalf, lp_[t], lq_[t]);
-        } else {
-          trd_ld16_sc1(S.xch, xbytes, tid * 16, soff, lr_[t], lp_[t]);
-          li_[t] = 0.0;
-          lq_[t] = 0.0;
-        }
+      const int soff = xrd + t * (16 * TRD_RES_THREADS);
+      if constexpr (CPLX) {                        // (complex: the {re, im} records of the row, then - half a parity further on - those of p)
+        trd_ld16_sc1(S.xch, xbytes, tid * 16, soff, lr_[t], li_[t]);
+        trd_ld16_sc1(S.xch, xbytes, tid * 16, soff + xhalf, lp_[t], lq_[t]);
       } else {
-        const int k = tid + t * TRD_RES_THREADS;
-        lr_[t] = trd_ld_sc1(rwr + k);
-        lp_[t] = trd_ld_sc1(prr + k);
+        trd_ld16_sc1(S.xch, xbytes, tid * 16, soff, lr_[t], lp_[t]);
         li_[t] = 0.0;
         lq_[t] = 0.0;
-        if (CPLX) {
-          li_[t] = trd_ld_sc1(rwi + k);
-          lq_[t] = trd_ld_sc1(pri + k);
-        }
       }
     };
 #pragma unroll
     for (int t = 0; t < NS; ++t) gather_slot(t);
-    if constexpr (TAG) {
-      // wait for the values of column j (tag), each thread for its own slots; p^H v from every workgroup's own copy of v_{j-1}
-      const unsigned int tg = trd_tag_of(j);
-      if (has_prev) {
-        unsigned int spins = 0;
-        for (;;) {
-          bool all = true;
+    // wait for the values of column j (tag), each thread for its own slots; p^H v from every workgroup's own copy of v_{j-1}
+    const unsigned int tg = trd_tag_of(j);
+    if (has_prev) {
+      unsigned int spins = 0;
+      for (;;) {
+        bool all = true;
 #pragma unroll
-          for (int t = 0; t < NS; ++t) {
-            const int k = tid + t * TRD_RES_THREADS;
-            if (k >= j && k < n) {
-              bool ok = trd_tag_is(lr_[t], tg) && trd_tag_is(lp_[t], tg);
-              if (CPLX) ok = ok && trd_tag_is(li_[t], tg) && trd_tag_is(lq_[t], tg);
-              if (!ok) {
-                all = false;
-                gather_slot(t);
-              }
+        for (int t = 0; t < NS; ++t) {
+          const int k = tid + t * TRD_RES_THREADS;
+          if (k >= j && k < n) {
+            bool ok = trd_tag_is(lr_[t], tg) && trd_tag_is(lp_[t], tg);
+            if (CPLX) ok = ok && trd_tag_is(li_[t], tg) && trd_tag_is(lq_[t], tg);
+            if (!ok) {
+              all = false;
+              gather_slot(t);
             }
           }
-          if (__all(all)) break;
-          if (++spins > S.spin_limit) {
-            if (tid == 0 && atomicCAS(S.give_up + 1, 0, 1) == 0) { S.give_up[2] = j; S.give_up[3] = (int)blockIdx.x; }   // (XMCA_TRACE=giveup)
-            give_up_sh = 1; break;
-          }       // a workgroup is missing: report, never hang.  All persistent launches of THIS process pass one gate (common.h), so only a foreign process can cause it; the bound is ~1.5 s for the first launch of a process (0.2 s was less than a first launch on a cold device can take) and ~0.2 s afterwards (TrdSync::spin_limit; advisor, round 4)
-          __builtin_amdgcn_s_sleep(1);
         }
+        if (__all(all)) break;
+        if (++spins > S.spin_limit) {
+          if (tid == 0 && atomicCAS(S.give_up + 1, 0, 1) == 0) { S.give_up[2] = j; S.give_up[3] = (int)blockIdx.x; }   // (XMCA_TRACE=giveup)
+          give_up_sh = 1; break;
+        }       // a workgroup is missing: report, never hang.  All persistent launches of THIS process pass one gate (common.h), so only a foreign process can cause it; the bound is ~1.5 s for the first launch of a process (0.2 s was less than a first launch on a cold device can take) and ~0.2 s afterwards (TrdSync::spin_limit; advisor, round 4)
+        __builtin_amdgcn_s_sleep(1);
       }
+    }
 #pragma unroll
-      for (int t = 0; t < NS; ++t) {
-        const int k = tid + t * TRD_RES_THREADS;
-        lr_[t] = trd_untagged(lr_[t]);
-        lp_[t] = trd_untagged(lp_[t]);
-        if (CPLX) {
-          li_[t] = trd_untagged(li_[t]);
-          lq_[t] = trd_untagged(lq_[t]);
-        }
-        if (k >= j && k < n) {
-          const double vr = KEEPV ? vv_r[t] : bV[0][k], vi = CPLX ? (KEEPV ? vv_i[t] : bV[1][k]) : 0.0;
-          gr += lp_[t] * vr + lq_[t] * vi;              // conj(p) v
-          gi += lp_[t] * vi - lq_[t] * vr;
-        }
+    for (int t = 0; t < NS; ++t) {
+      const int k = tid + t * TRD_RES_THREADS;
+      lr_[t] = trd_untagged(lr_[t]);
+      lp_[t] = trd_untagged(lp_[t]);
+      if (CPLX) {
+        li_[t] = trd_untagged(li_[t]);
+        lq_[t] = trd_untagged(lq_[t]);
+      }
+      if (k >= j && k < n) {
+        const double vr = KEEPV ? vv_r[t] : bV[0][k], vi = CPLX ? (KEEPV ? vv_i[t] : bV[1][k]) : 0.0;
+        gr += lp_[t] * vr + lq_[t] * vi;              // conj(p) v
+        gi += lp_[t] * vi - lq_[t] * vr;
       }
     }
     // p_{j-1}[j] is needed by every thread in front of the fused loop below (w_{j-1}[j] enters column j): its owner parks it
@@ -764,7 +731,7 @@ __global__ __launch_bounds__(TRD_RES_THREADS) void trd_resident_kernel(TrdParams
         pj_sh[cur][1] = CPLX ? lq_[t] : 0.0;
       }
     trd_block_sum2_1b<TRD_RES_THREADS / 64>(gr, gi, red2[cur][0]);
-    if (TAG && give_up_sh) {
+    if (give_up_sh) {
       if (tid == 0) atomicExch(S.give_up, 1);
       break;
     }
@@ -874,28 +841,13 @@ __global__ __launch_bounds__(TRD_RES_THREADS) void trd_resident_kernel(TrdParams
     // columns are zero in all three vectors; whole groups of CG dead chunks are skipped with one scalar branch.
     const int g0 = ((j + 1) >> 7) / CG;             // groups below hold dead columns only
     const int c0 = (j + 1) >> 7;
-    double gwr = 0.0, gwi = 0.0;
     // bX holds x with x[j+1] as stored; the pass multiplies by u_j = x - beta e_{j+1}.  EVERY wave writes the leading entry itself:
     // the LDS operations of a wave complete in order, so its own reads below see it without a barrier (four stores of one value).
     if (lane == 0) bX[0][j + 1] = a0r - beta;
-    // v_j[i] = s u_j[i] (1 at i = j + 1) for the partial sums p^H v of the flags form
-    auto v_of = [&](int i, double& vr, double& vi) {
-      if (i == j + 1) { vr = 1.0; vi = 0.0; return; }
-      const double xr = bX[0][i], xi = CPLX ? bX[1][i] : 0.0;
-      vr = xr * sr_next - xi * si_next;
-      vi = xr * si_next + xi * sr_next;
-    };
-    double* const pbr = pub_r[cur];
-    double* const pbi = pub_i[cur];
-    double* const nrr = rb_r[prev];
-    double* const nri = rb_i[prev];
     const unsigned int tgn = trd_tag_of(j + 1);      // what is published now is consumed by column j+1
-    double* const xnext = TAG ? reinterpret_cast<double*>(reinterpret_cast<char*>(S.xch) + xwr) : nullptr;   // the records column j+1 reads
+    double* const xnext = reinterpret_cast<double*>(reinterpret_cast<char*>(S.xch) + xwr);   // the records column j+1 reads
     auto publish_p = [&](int i, double pr, double pi) {
-      if constexpr (!TAG) {
-        trd_st_sc1(pbr + i, pr);
-        if (CPLX) trd_st_sc1(pbi + i, pi);
-      } else if constexpr (CPLX) {
+      if constexpr (CPLX) {
         trd_st16_sc1(S.xch, xbytes, 16 * i, xwr + xhalf, trd_tagged(pr, tgn), trd_tagged(pi, tgn));
       } else {
         trd_st_sc1(xnext + 2 * i + 1, trd_tagged(pr, tgn));
@@ -958,13 +910,8 @@ __global__ __launch_bounds__(TRD_RES_THREADS) void trd_resident_kernel(TrdParams
               sr += a.y * xk.y - b.y * xki.y;
               si += a.y * xki.y + b.y * xk.y;
               if (pubrow) {
-                if constexpr (TAG) {
-                  trd_st16_sc1(S.xch, xbytes, 16 * k, xwr, trd_tagged(a.x, tgn), trd_tagged(b.x, tgn));
-                  trd_st16_sc1(S.xch, xbytes, 16 * k + 16, xwr, trd_tagged(a.y, tgn), trd_tagged(b.y, tgn));
-                } else {
-                  trd_st_sc1(nri + k, b.x);
-                  trd_st_sc1(nri + k + 1, b.y);
-                }
+                trd_st16_sc1(S.xch, xbytes, 16 * k, xwr, trd_tagged(a.x, tgn), trd_tagged(b.x, tgn));
+                trd_st16_sc1(S.xch, xbytes, 16 * k + 16, xwr, trd_tagged(a.y, tgn), trd_tagged(b.y, tgn));
               }
             } else {
               a.x -= svr_ * wk.x + swr_ * vk.x;
@@ -974,10 +921,7 @@ __global__ __launch_bounds__(TRD_RES_THREADS) void trd_resident_kernel(TrdParams
               sr += a.y * xk.y;
             }
             if (pubrow) {
-              if constexpr (!TAG) {
-                trd_st_sc1(nrr + k, a.x);
-                trd_st_sc1(nrr + k + 1, a.y);
-              } else if constexpr (!CPLX) {
+              if constexpr (!CPLX) {
                 trd_st_sc1(xnext + 2 * k, trd_tagged(a.x, tgn));
                 trd_st_sc1(xnext + 2 * k + 2, trd_tagged(a.y, tgn));
               }
@@ -997,12 +941,6 @@ __global__ __launch_bounds__(TRD_RES_THREADS) void trd_resident_kernel(TrdParams
           const double yi = CPLX ? ((rowpart[par][0][1] + rowpart[par][1][1]) + rowpart[par][2][1]) + rowpart[par][3][1] : 0.0;
           const double pr = mr_ * yr - mi_ * yi, pi = mr_ * yi + mi_ * yr;
           if (lane == 0) publish_p(i, pr, pi);
-          if constexpr (!TAG) {
-            double vr, vi;
-            v_of(i, vr, vi);
-            gwr += pr * vr + pi * vi;
-            gwi += pr * vi - pi * vr;
-          }
         }
       }
     }
@@ -1067,21 +1005,14 @@ __global__ __launch_bounds__(TRD_RES_THREADS) void trd_resident_kernel(TrdParams
         if (rowi[t] == j + 1) {             // wave-uniform
           // (the lane offset goes through an empty asm: the NC store offsets 128 c + 2 lane are loop invariants, and hipcc
           // hoists them out of the COLUMN loop into registers of their own - 18 to 32 of them next to the resident rows,
-          // which is what pushed the tagged complex NC = 20 build into scratch in round 3)
+          // which is what pushed the complex NC = 20 build into scratch in round 3)
           int lane2 = 2 * lane;
           asm volatile("" : "+v"(lane2));
 #pragma unroll
           for (int c = 0; c < NC; ++c) {
             if (c >= c0) {
               const int k = 128 * c + lane2;
-              if constexpr (!TAG) {
-                trd_st_sc1(nrr + k, ar[t][c].x);
-                trd_st_sc1(nrr + k + 1, ar[t][c].y);
-                if (CPLX) {
-                  trd_st_sc1(nri + k, ai[t][c].x);
-                  trd_st_sc1(nri + k + 1, ai[t][c].y);
-                }
-              } else if constexpr (CPLX) {
+              if constexpr (CPLX) {
                 trd_st16_sc1(S.xch, xbytes, 16 * k, xwr, trd_tagged(ar[t][c].x, tgn), trd_tagged(ai[t][c].x, tgn));
                 trd_st16_sc1(S.xch, xbytes, 16 * k + 16, xwr, trd_tagged(ar[t][c].y, tgn), trd_tagged(ai[t][c].y, tgn));
               } else {
@@ -1094,7 +1025,7 @@ __global__ __launch_bounds__(TRD_RES_THREADS) void trd_resident_kernel(TrdParams
       }
       // In the LAST column of a launch that hands over to another one (chain, TrdSync) the live rows go back to the working
       // copy: the next launch loads its resident rows from there.
-      if (TAG && j + 1 == j_end && j_end < n) {
+      if (j + 1 == j_end && j_end < n) {
 #pragma unroll
         for (int t = 0; t < RR; ++t) {
           if (rowi[t] > j && rowi[t] < n) {             // wave-uniform
@@ -1121,52 +1052,10 @@ __global__ __launch_bounds__(TRD_RES_THREADS) void trd_resident_kernel(TrdParams
           const double yi = CPLX ? trd_wave_sum_dpp(acci[t]) : 0.0;
           const double pr = mr_ * yr - mi_ * yi, pi = mr_ * yi + mi_ * yr;
           if (lane == 0) publish_p(i, pr, pi);
-          if constexpr (!TAG) {
-            double vr, vi;
-            v_of(i, vr, vi);
-            gwr += pr * vr + pi * vi;
-            gwi += pr * vi - pi * vr;
-          }
         }
       }
     }
     if (prof) P.prof[8 * j + 4] = __builtin_amdgcn_s_memtime();
-    if constexpr (!TAG) {
-      if (lane == 0) {
-        gam_sh[wave][0] = gwr;
-        gam_sh[wave][1] = gwi;
-      }
-      __syncthreads();
-      if (tid == 0) {
-        double sr = 0.0, si = 0.0;
-  #pragma unroll
-        for (int w = 0; w < TRD_RES_THREADS / 64; ++w) { sr += gam_sh[w][0]; si += gam_sh[w][1]; }
-        trd_st_sc1(gp_r[cur] + blockIdx.x, sr);
-        if (CPLX) trd_st_sc1(gp_i[cur] + blockIdx.x, si);
-      }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // every storing wave drains before the flag goes out
-      __syncthreads();
-      if (tid == 0) __hip_atomic_store(flags + blockIdx.x, (unsigned int)(j + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (prof) P.prof[8 * j + 5] = __builtin_amdgcn_s_memtime();
-      // ---- exchange: wait until every workgroup has published column j ----
-      if (wave == 0) {
-        // the first poll waits ~1000 cycles: polling while the other workgroups still publish only slows them down (measured:
-        // n = 2920 26.9 -> 25.2 ms; counting arrivals in 8 sharded counters instead of 256 flags: 32 ms)
-        if (S.poll_delay >= 32) __builtin_amdgcn_s_sleep(32);
-        else if (S.poll_delay >= 16) __builtin_amdgcn_s_sleep(16);
-        else if (S.poll_delay >= 8) __builtin_amdgcn_s_sleep(8);
-        else if (S.poll_delay >= 4) __builtin_amdgcn_s_sleep(4);
-        unsigned int spins = 0;
-        for (;;) {
-          bool ok = true;
-          for (int w = lane; w < nwg; w += 64)
-            ok &= __hip_atomic_load(flags + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= (unsigned int)(j + 1);
-          if (__all(ok)) break;
-          __builtin_amdgcn_s_sleep(1);
-          if (++spins > S.spin_limit) { if (lane == 0) give_up_sh = 1; break; }     // a workgroup is missing: report, never hang (bound: TrdSync::spin_limit)
-        }
-      }
-    }
     __syncthreads();
     if (prof) P.prof[8 * j + 6] = __builtin_amdgcn_s_memtime();
     if (give_up_sh) {
@@ -1175,7 +1064,7 @@ __global__ __launch_bounds__(TRD_RES_THREADS) void trd_resident_kernel(TrdParams
     }
     // ---- hand-over to the next launch of the chain (last column of this one, columns remain): u_j and its scalars; the resident
     // rows went back to the working copy in the pass ----
-    if (TAG && is_writer && j + 1 == j_end && j_end < n) {
+    if (is_writer && j + 1 == j_end && j_end < n) {
       int s0 = tid;
       asm volatile("" : "+v"(s0));                 // (the store addresses are loop invariants: not to be hoisted into registers of the column loop)
       for (int s = s0; s < LV; s += TRD_RES_THREADS) {
@@ -1465,7 +1354,7 @@ struct TrdStage {
   int col0;              // origin of the stage's block
   int j_begin, j_end;    // columns (global indices) the stage reduces
 };
-// instantiations a LATER stage of a chain may take (tagged form): NC = 4, 8, 12, 16, 20 (real) chunks of 128 columns; the first stage
+// instantiations a LATER stage of a chain may take: NC = 4, 8, 12, 16, 20 (real) chunks of 128 columns; the first stage
 // is the one a single launch would take (trd_resident_nc)
 inline int trd_stage_nc(int n, bool cplx) {
   for (int nc = 4; nc <= (cplx ? 20 : 24); nc += 4)
@@ -1497,8 +1386,7 @@ inline std::vector<TrdStage> trd_plan(int n, bool cplx, int nc) {
   const char* eb = std::getenv("XMCA_TRD_BREAKS");
   const char* ec = std::getenv("XMCA_TRD_CHAIN");
   const bool chain = !(ec && ec[0] == '0');
-  const bool tagged = [] { const char* e = std::getenv("XMCA_TRD_TAGGED"); return e ? e[0] != '0' : true; }();
-  if (chain && tagged) {
+  if (chain) {
     if (eb && eb[0]) {
       for (const char* q = eb; *q;) {
         const int c = std::atoi(q);
@@ -1521,8 +1409,8 @@ inline std::vector<TrdStage> trd_plan(int n, bool cplx, int nc) {
     const int end = q < cuts.size() ? cuts[q] : n;
     TrdStage sg{};
     sg.col0 = begin;
-    sg.nc = (q == 0 && !(chain && tagged)) ? nc : trd_stage_nc(n - begin, cplx);   // (the tagged chain also STARTS in the smallest instantiation that fits)
-    sg.rr = (q > 0 && chain && tagged && trd_pack_lanes()) ? trd_stage_rr_packed(sg.nc, cplx) : trd_stage_rr(sg.nc, cplx);
+    sg.nc = (q == 0 && !chain) ? nc : trd_stage_nc(n - begin, cplx);   // (the chain also STARTS in the smallest instantiation that fits)
+    sg.rr = (q > 0 && chain && trd_pack_lanes()) ? trd_stage_rr_packed(sg.nc, cplx) : trd_stage_rr(sg.nc, cplx);
     sg.j_begin = begin;
     sg.j_end = end;
     st.push_back(sg);
@@ -1573,66 +1461,44 @@ inline TrdParams trd_reduce(hipStream_t st, TrdWorkspace& ws, const double* Ar, 
     PersistGate& gate = persist_gate();       // (per device: CU count and the claims of every persistent kernel)
     const int n_cus = gate.n_cus;
     const size_t lv = (size_t)(ld > (int64_t)nc * 128 ? ld : (int64_t)nc * 128);   // slots of an exchange vector: every stage's padded range
-    const size_t nvs = std::max(nv, lv);                   // (the prologue loads every slot of a vector, dead or not)
-    const size_t rec = cplx ? 4 : 2;                       // doubles per exchange record (tagged form)
-    const size_t sync_doubles = 4 * nvs + 4 * (size_t)TRD_MAX_WGS + 4 * lv + 2 * lv + 8 + 2 * rec * lv;
+    const size_t rec = cplx ? 4 : 2;                       // doubles per exchange record
+    const size_t sync_doubles = 2 * lv + 8 + 2 * rec * lv;
     ws.sync.ensure(sync_doubles);
-    ws.flags.ensure(TRD_MAX_WGS + 32);
+    ws.flags.ensure(4);
+    // (row 0 is read from the working copy by trd_prefill_kernel: the exchange records must start as zeros)
     XMCA_HIP(hipMemsetAsync(ws.sync.get(), 0, sizeof(double) * sync_doubles, st));
-    XMCA_HIP(hipMemsetAsync(ws.flags.get(), 0, sizeof(unsigned int) * (TRD_MAX_WGS + 32), st));
+    XMCA_HIP(hipMemsetAsync(ws.flags.get(), 0, sizeof(unsigned int) * 4, st));
     TrdSync S{};
     double* q = ws.sync.get();
-    for (int a = 0; a < 2; ++a) for (int c = 0; c < 2; ++c) { S.pub[a][c] = q; q += nvs; }
-    for (int a = 0; a < 2; ++a) for (int c = 0; c < 2; ++c) { S.gpart[a][c] = q; q += TRD_MAX_WGS; }
-    for (int a = 0; a < 2; ++a) for (int c = 0; c < 2; ++c) { S.rowbuf[a][c] = q; q += lv; }
     for (int c = 0; c < 2; ++c) { S.hand_u[c] = q; q += lv; }
     S.hand_s = q; q += 8;
     S.xch = q;
     S.xch_pb = (int)(rec * lv * sizeof(double));
-    S.flags = ws.flags.get();
-    S.poll_delay = 16;      // (flags form; swept 8...48 in round 3: flat)
-    S.tag_delay = 0;        // round 5: the scaling of the previous reflector fills what used to be the delay (swept again 0...32: 0 for every shape; rounds 3-4: 24 x 64 cycles of sleep)
-    // column 0 reads its row like every other column: from rowbuf (parity 0)
-    // (the tagged form reads row 0 from the working copy: the exchange buffers must start as zeros)
-    // exchange by tagged values or by epoch flags.  Measured with the request delay tuned (XMCA_TRD_TAG_DELAY), tagged / flags:
-    // real n = 1000 3.7 / 5.0 ms, 2048 11.0 / 13.2, 2920 21.6 / 24.3; complex n = 1000 5.7 / 6.9, 2048 18.4 / 20.4, 2501 26.9 / 28.2
-    // (round 4: the tagged NC = 20 build no longer spills - see the publication of row j + 1 in the kernel) - so: tagged for
-    // everything (XMCA_TRD_TAGGED=0 keeps the flags, which the tests still run)
-    const bool tagged = [] { const char* e = std::getenv("XMCA_TRD_TAGGED"); return e ? e[0] != '0' : true; }();
-    // Contiguous row ownership only with the tagged exchange: there the arithmetic of a row does not depend on its owner (same
-    // bits for any lane count), and workgroups that leave early feed the other lanes.  In the flags form p^H v is a sum of
-    // per-workgroup partials - regrouping rows would change its order and the bits - and nobody leaves early (advisor, round 4).
-    S.contiguous = (tagged && in_surrogate_lanes()) ? 1 : 0;
+    // Contiguous row ownership inside surrogate lanes: the arithmetic of a row does not depend on its owner (same bits for any
+    // lane count), and workgroups that leave early feed the other lanes.
+    S.contiguous = in_surrogate_lanes() ? 1 : 0;
     S.spin_limit = trd_spin_limit();
-    if (!tagged) {
-      XMCA_HIP(hipMemcpyAsync(S.rowbuf[0][0], P.Ar, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st));
-      if (cplx) XMCA_HIP(hipMemcpyAsync(S.rowbuf[0][1], P.Ai, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st));
-    }
-    if (tagged) hipLaunchKernelGGL(trd_prefill_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, P.Ar, P.Ai, n, S.xch);
-    S.give_up = reinterpret_cast<int*>(ws.flags.get() + TRD_MAX_WGS);
+    hipLaunchKernelGGL(trd_prefill_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, P.Ar, P.Ai, n, S.xch);
+    S.give_up = reinterpret_cast<int*>(ws.flags.get());
     using ResFn = void (*)(TrdParams, TrdSync, int);
     auto pick = [&](int snc, int srr) -> ResFn {
-      if (tagged) {
-        if (cplx) {
-          switch (snc) {
-            case 4: return srr == 2 ? trd_resident_kernel<true, 4, 2, true> : trd_resident_kernel<true, 4, 1, true>;
-            case 8: return srr == 2 ? trd_resident_kernel<true, 8, 2, true> : trd_resident_kernel<true, 8, 1, true>;
-            case 12: return srr == 3 ? trd_resident_kernel<true, 12, 3, true> : trd_resident_kernel<true, 12, 2, true>;
-            case 16: return trd_resident_kernel<true, 16, 2, true>;
-            default: return trd_resident_kernel<true, 20, 2, true>;
-          }
-        }
+      if (cplx) {
         switch (snc) {
-          case 4: return trd_resident_kernel<false, 4, 1, true>;
-          case 8: return trd_resident_kernel<false, 8, 1, true>;
-          case 12: return trd_resident_kernel<false, 12, 2, true>;
-          case 16: return trd_resident_kernel<false, 16, 2, true>;
-          case 20: return trd_resident_kernel<false, 20, 3, true>;
-          default: return trd_resident_kernel<false, 24, 3, true>;
+          case 4: return srr == 2 ? trd_resident_kernel<true, 4, 2> : trd_resident_kernel<true, 4, 1>;
+          case 8: return srr == 2 ? trd_resident_kernel<true, 8, 2> : trd_resident_kernel<true, 8, 1>;
+          case 12: return srr == 3 ? trd_resident_kernel<true, 12, 3> : trd_resident_kernel<true, 12, 2>;
+          case 16: return trd_resident_kernel<true, 16, 2>;
+          default: return trd_resident_kernel<true, 20, 2>;
         }
       }
-      if (cplx) return snc == 8 ? trd_resident_kernel<true, 8, 1, false> : snc == 16 ? trd_resident_kernel<true, 16, 2, false> : trd_resident_kernel<true, 20, 2, false>;
-      return snc == 8 ? trd_resident_kernel<false, 8, 1, false> : snc == 16 ? trd_resident_kernel<false, 16, 2, false> : trd_resident_kernel<false, 24, 3, false>;
+      switch (snc) {
+        case 4: return trd_resident_kernel<false, 4, 1>;
+        case 8: return trd_resident_kernel<false, 8, 1>;
+        case 12: return trd_resident_kernel<false, 12, 2>;
+        case 16: return trd_resident_kernel<false, 16, 2>;
+        case 20: return trd_resident_kernel<false, 20, 3>;
+        default: return trd_resident_kernel<false, 24, 3>;
+      }
     };
     static const char* prof_file_r = std::getenv("XMCA_TRD_PROF");
     if (prof_file_r) {
@@ -1660,7 +1526,6 @@ inline TrdParams trd_reduce(hipStream_t st, TrdWorkspace& ws, const double* Ar, 
         if (P.Vi) Pq.Vi = P.Vi + off;
         if (P.prof) Pq.prof = P.prof + (size_t)8 * c0;
         TrdSync Sq = S;
-        for (int a = 0; a < 2; ++a) for (int c = 0; c < 2; ++c) { Sq.pub[a][c] = S.pub[a][c] + c0; Sq.rowbuf[a][c] = S.rowbuf[a][c] + c0; }
         Sq.hand_u[0] = S.hand_u[0] + c0; Sq.hand_u[1] = S.hand_u[1] + c0;
         Sq.xch = S.xch + 2 * (size_t)c0;     // (16 bytes per slot in each block of records)
         Sq.j_begin = sg.j_begin - c0;
@@ -1688,7 +1553,7 @@ inline TrdParams trd_reduce(hipStream_t st, TrdWorkspace& ws, const double* Ar, 
       for (size_t q = 0; q < stages.size(); ++q) {
         const TrdStage& sg = stages[q];
         d += (q ? " -> " : "") + std::string("trd_resident_kernel<") + (cplx ? "complex" : "real") + ",NC=" + std::to_string(sg.nc) + ",RR=" + std::to_string(sg.rr) +
-             (tagged ? ",tagged>" : ",flags>") + " columns [" + std::to_string(sg.j_begin) + "," + std::to_string(sg.j_end) + ")";
+             ",tagged> columns [" + std::to_string(sg.j_begin) + "," + std::to_string(sg.j_end) + ")";
       }
       ws.last_desc = d;
     }
