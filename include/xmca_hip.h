@@ -461,6 +461,32 @@ int xmca_rule_n_sharded(xmca_handle* h, xmca_comm* c, int64_t n_runs, int64_t T,
 /* Surrogate generator on its own (tests): T*N standard normals of (seed, run, side) as float64 on the host. */
 int xmca_surrogate(xmca_handle* h, int64_t n, uint64_t seed, uint32_t run, uint32_t side, double* out);
 
+/* Red-noise (AR(1)) surrogates for the Rule-N test.  Column c of the surrogate of (run, side) is
+ *   x[0] = e[0],  x[t] = phi_c x[t-1] + sqrt(1 - phi_c^2) e[t]
+ * with e the normals of xmca_surrogate rounded to the run dtype: stationary, unit variance, lag-1 autocorrelation phi_c.  The
+ * recurrence runs in float64; phi_c = 0 leaves the white surrogate bit for bit.  Time is cut into segments that depend on
+ * (T, N) only, so the surrogates do not depend on lanes, ranks or the device's load.
+ *   xmca_lag1_autocorrelation  phi_out[c] (N float64, host) = sum_t (x[t]-m)(x[t+1]-m) / sum_t (x[t]-m)^2 of the columns of the
+ *                              resident real plane of `side` (the handle's dtype; float64 after an extend='exp' / 'theta'
+ *                              complexification), in float64, 0 for a constant column; the same bits on every call.
+ *   xmca_rule_n_ar1            xmca_rule_n with the surrogates filtered: phi_left (Nx) / phi_right (Ny; NULL for one field) are
+ *                              host arrays, uploaded once per call.  A value that is not finite or has |phi| >= 1 is
+ *                              XMCA_ERR_INVALID, before anything is launched.
+ *   xmca_rule_n_ar1_sharded    xmca_rule_n_sharded with those surrogates; phi must be the same on every rank.
+ *   xmca_surrogate_ar1         (tests) the filtered, uncentred T x N field of (seed, run, side) in `dtype`, widened to float64.
+ *   xmca_ar1_segments          (no device) the filter's segments at this shape: segment k covers the rows
+ *                              [k length, min(T, (k + 1) length)), k < count. */
+int xmca_lag1_autocorrelation(xmca_handle* h, int side, double* phi_out);
+int xmca_rule_n_ar1(xmca_handle* h, int64_t T, int64_t Nx, int64_t Ny, int n_fields, const double* hilbert_col, int rotated,
+                    int p, int power, double tol, int64_t run_begin, int64_t run_end, uint64_t seed, int dtype,
+                    double* spectra_out, int* kept_out, int64_t n_out, const double* phi_left, const double* phi_right);
+int xmca_rule_n_ar1_sharded(xmca_handle* h, xmca_comm* c, int64_t n_runs, int64_t T, int64_t Nx, int64_t Ny, int n_fields,
+                            const double* hilbert_col, int rotated, int p, int power, double tol, uint64_t seed, int dtype,
+                            double* spectra_out, int* kept_out, int64_t n_out, const double* phi_left, const double* phi_right);
+int xmca_surrogate_ar1(xmca_handle* h, int64_t T, int64_t N, const double* phi, uint64_t seed, uint32_t run, uint32_t side, int dtype,
+                       double* out);
+int xmca_ar1_segments(int64_t T, int64_t N, int64_t* count_out, int64_t* length_out);
+
 /* hipEvent stage timers of the calls since the last reset: names are written as a ';'-separated list.  Two
  * kernel-level entries follow the stages when the eigensolver ran: "jacobi_round_kernel_ms" (total duration of the
  * jacobi_fused_round_kernel launches, events around the rounds of every sweep) and "jacobi_round_kernel_launches"

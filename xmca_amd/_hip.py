@@ -96,6 +96,13 @@ SIGNATURES = {
     "xmca_rule_n_sharded": (_c_int, [_vp, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _vp, _c_int, _c_int, _c_int, _c_dbl,
                                      ctypes.c_uint64, _c_int, _vp, _vp, _c_i64]),
     "xmca_surrogate": (_c_int, [_vp, _c_i64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _vp]),
+    "xmca_lag1_autocorrelation": (_c_int, [_vp, _c_int, _vp]),
+    "xmca_rule_n_ar1": (_c_int, [_vp, _c_i64, _c_i64, _c_i64, _c_int, _vp, _c_int, _c_int, _c_int, _c_dbl, _c_i64, _c_i64,
+                                 ctypes.c_uint64, _c_int, _vp, _vp, _c_i64, _vp, _vp]),
+    "xmca_rule_n_ar1_sharded": (_c_int, [_vp, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _vp, _c_int, _c_int, _c_int, _c_dbl,
+                                         ctypes.c_uint64, _c_int, _vp, _vp, _c_i64, _vp, _vp]),
+    "xmca_surrogate_ar1": (_c_int, [_vp, _c_i64, _c_i64, _vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, _c_int, _vp]),
+    "xmca_ar1_segments": (_c_int, [_c_i64, _c_i64, ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64)]),
     "xmca_get_timings": (_c_int, [_vp, ctypes.c_char_p, _c_int, _vp, _c_int]),
     "xmca_get_reduction_info": (_c_int, [_vp, ctypes.c_char_p, _c_int]),
     "xmca_reset_timings": (_c_int, [_vp]),
@@ -188,6 +195,37 @@ def ingest_regime(T, N, stride_t, stride_n):
     if rc < 0:
         raise ValueError("ingest_regime: a non-empty view with strides >= 0 is needed")
     return rc
+
+
+def ar1_segments(T, N):
+    """The time segments [(begin, end), ...] of the AR(1) filter of a T x N surrogate (xmca_ar1_segments; no device): a function of
+    the shape alone, so the red-noise surrogates do not depend on lanes, ranks or the load of the device."""
+    count, length = _c_i64(0), _c_i64(0)
+    rc = load_library().xmca_ar1_segments(int(T), int(N), ctypes.byref(count), ctypes.byref(length))
+    if rc != 0:
+        raise ValueError("ar1_segments: T and N must be >= 1")
+    return [(k * length.value, min(int(T), (k + 1) * length.value)) for k in range(count.value)]
+
+
+def _phi_array(what, phi, N):
+    """The lag-1 autocorrelations of N columns as contiguous float64: finite, |phi| < 1 (checked here, before any device call)."""
+    phi = np.ascontiguousarray(phi, dtype=np.float64)
+    if phi.shape != (int(N),):
+        raise ValueError("%s: phi must hold one value per column (%d), got shape %s" % (what, N, phi.shape))
+    if not np.all(np.abs(phi) < 1.0):                   # (False for NaN)
+        raise ValueError("%s: every phi must be finite with |phi| < 1" % what)
+    return phi
+
+
+def _phi_pair(what, ar1, Nx, Ny, n_fields):
+    """`ar1 = (phi_left, phi_right or None)` of rule_n / rule_n_sharded as two checked arrays (the right one None for one field)."""
+    try:
+        left, right = ar1
+    except (TypeError, ValueError):
+        raise ValueError("%s: ar1 must be the pair (phi_left, phi_right or None)" % what)
+    if (right is not None) != (n_fields == 2):
+        raise ValueError("%s: ar1 needs a phi for each of the %d field(s), and none for a field the model lacks" % (what, n_fields))
+    return _phi_array(what, left, Nx), None if right is None else _phi_array(what, right, Ny)
 
 
 class DeviceView:
@@ -816,7 +854,11 @@ class Handle:
         return ref is not None and ref() is holder
 
     # ---- rule N -------------------------------------------------------------------------------
-    def rule_n(self, T, Nx, Ny, n_fields, complexify, rotated, p, power, tol, run_begin, run_end, seed, dtype, n_out):
+    def rule_n(self, T, Nx, Ny, n_fields, complexify, rotated, p, power, tol, run_begin, run_end, seed, dtype, n_out, ar1=None):
+        """ar1 = (phi_left, phi_right or None): red-noise surrogates with these lag-1 autocorrelations per column (xmca_rule_n_ar1);
+        None: the white surrogates of xmca_rule_n."""
+        if ar1 is not None:
+            ar1 = _phi_pair("rule_n", ar1, Nx, Ny, n_fields)
         self.release_result()
         n = run_end - run_begin
         self.fields_owner = None            # the surrogates overwrite the resident fields
@@ -824,29 +866,61 @@ class Handle:
         kept = np.zeros(max(n, 0), dtype=np.int32)
         ht = hilbert_imag_column(T) if complexify else None
         self.field_dtype = None
-        if n > 0:
+        if n > 0 and ar1 is None:
             self._check(self._lib.xmca_rule_n(self._h, T, Nx, Ny if n_fields == 2 else 0, n_fields, _ptr(ht), int(rotated),
                                               int(p), int(power), float(tol), run_begin, run_end, int(seed),
                                               _np_dtype_code(dtype), _ptr(spectra), _ptr(kept), n_out))
+        elif n > 0:
+            self._check(self._lib.xmca_rule_n_ar1(self._h, T, Nx, Ny if n_fields == 2 else 0, n_fields, _ptr(ht), int(rotated),
+                                                  int(p), int(power), float(tol), run_begin, run_end, int(seed),
+                                                  _np_dtype_code(dtype), _ptr(spectra), _ptr(kept), n_out, _ptr(ar1[0]), _ptr(ar1[1])))
         return spectra, kept
 
-    def rule_n_sharded(self, comm, n_runs, T, Nx, Ny, n_fields, complexify, rotated, p, power, tol, seed, dtype, n_out):
+    def rule_n_sharded(self, comm, n_runs, T, Nx, Ny, n_fields, complexify, rotated, p, power, tol, seed, dtype, n_out, ar1=None):
         """xmca_rule_n_sharded: this rank's block of the runs [0, n_runs) + ONE ncclAllGather (native RCCL communicator
-        `comm`, see `Comm`); every rank gets all n_runs x n_out spectra and kept flags."""
+        `comm`, see `Comm`); every rank gets all n_runs x n_out spectra and kept flags.  ar1 = (phi_left, phi_right or None):
+        red-noise surrogates (xmca_rule_n_ar1_sharded); the caller passes the same phi on every rank."""
+        if ar1 is not None:
+            ar1 = _phi_pair("rule_n_sharded", ar1, Nx, Ny, n_fields)
         self.release_result()
         self.fields_owner = None
         self.field_dtype = None
         spectra = np.zeros((max(n_runs, 0), n_out), dtype=np.float64)
         kept = np.zeros(max(n_runs, 0), dtype=np.int32)
         ht = hilbert_imag_column(T) if complexify else None
-        self._check(self._lib.xmca_rule_n_sharded(self._h, comm._c, int(n_runs), T, Nx, Ny if n_fields == 2 else 0, n_fields,
-                                                  _ptr(ht), int(rotated), int(p), int(power), float(tol), int(seed),
-                                                  _np_dtype_code(dtype), _ptr(spectra), _ptr(kept), n_out))
+        if ar1 is None:
+            self._check(self._lib.xmca_rule_n_sharded(self._h, comm._c, int(n_runs), T, Nx, Ny if n_fields == 2 else 0, n_fields,
+                                                      _ptr(ht), int(rotated), int(p), int(power), float(tol), int(seed),
+                                                      _np_dtype_code(dtype), _ptr(spectra), _ptr(kept), n_out))
+        else:
+            self._check(self._lib.xmca_rule_n_ar1_sharded(self._h, comm._c, int(n_runs), T, Nx, Ny if n_fields == 2 else 0, n_fields,
+                                                          _ptr(ht), int(rotated), int(p), int(power), float(tol), int(seed),
+                                                          _np_dtype_code(dtype), _ptr(spectra), _ptr(kept), n_out, _ptr(ar1[0]),
+                                                          _ptr(ar1[1])))
         return spectra, kept
 
     def surrogate(self, n, seed, run, side):
         out = np.empty(n, dtype=np.float64)
         self._check(self._lib.xmca_surrogate(self._h, n, int(seed), int(run), int(side), _ptr(out)))
+        return out
+
+    def surrogate_ar1(self, T, N, phi, seed, run, side, dtype):
+        """(tests) the red-noise surrogate of (seed, run, side) before it is centred: (T, N) float64 holding the values of the run
+        `dtype` (xmca_surrogate_ar1).  phi: N values; one that is not finite or has |phi| >= 1 is refused by the library
+        (ValueError) before anything is launched."""
+        phi = np.ascontiguousarray(phi, dtype=np.float64)
+        if phi.shape != (int(N),):
+            raise ValueError("surrogate_ar1: phi must hold one value per column (%d), got shape %s" % (N, phi.shape))
+        out = np.empty((int(T), int(N)), dtype=np.float64)
+        self._check(self._lib.xmca_surrogate_ar1(self._h, int(T), int(N), _ptr(phi), int(seed), int(run), int(side),
+                                                 _np_dtype_code(dtype), _ptr(out)))
+        return out
+
+    def lag1_autocorrelation(self, side, N):
+        """Lag-1 autocorrelation of every column of the resident real field of `side` (xmca_lag1_autocorrelation): N float64 values,
+        0 for a constant column.  The field stays as it is; N doubles come back."""
+        out = np.empty(int(N), dtype=np.float64)
+        self._check(self._lib.xmca_lag1_autocorrelation(self._h, int(side), _ptr(out)))
         return out
 
     # ---- instrumentation ----------------------------------------------------------------------

@@ -1449,16 +1449,94 @@ class MCA:
     # ------------------------------------------------------------------------------------------
     # significance (array.py:1716-1952)
     # ------------------------------------------------------------------------------------------
-    def rule_n(self, n_runs, n_modes=None, seed=None, dtype=np.float64):
+    def lag1_autocorrelation(self):
+        """Lag-1 autocorrelation of every grid point's series, estimated on the device from the centred real fields (a complex
+        model: their real parts): {field name: float64 array in the field's spatial shape, NaN at masked points}.
+
+        phi_c = sum_t (x[t] - m)(x[t+1] - m) / sum_t (x[t] - m)^2, in float64 for either field dtype, 0 for a constant series.  It
+        does not change when a column is rescaled (`normalize`, `apply_weights`).  The fields are made resident as for the
+        projections; only the values themselves come back.  This is the phi of `rule_n(noise='ar1')`."""
+        self._get_svals(1)                    # (before `solve`: the getters' RuntimeError)
+        dev = self._device()
+        if not self._owns_device_fields(dev):
+            self._upload_serial += 1
+            self._upload_fields(dev)
+        out = {}
+        for side, k in enumerate(self._keys):
+            phi = dev.lag1_autocorrelation(side, int(np.count_nonzero(self._no_nan_index[k])))
+            out[k] = self._with_nan_columns(k, phi, ()).reshape(self._fields_spatial_shape[k])
+        return out
+
+    def _phi_columns(self, phi):
+        """`phi` of `rule_n(noise='ar1')` as one float64 array per field, a value for every column of the surrogates: the kept
+        points take the given values, the masked ones 0 (their columns stay white, as in the white test).  ValueError for anything
+        else than the documented forms, and for a value at a kept point that is not finite or has |phi| >= 1."""
+        keys = self._keys
+        if isinstance(phi, dict):
+            extra = [k for k in phi if k not in keys]
+            if extra or any(k not in phi for k in keys):
+                raise ValueError('`phi` must hold one entry for each field {:}; got {:}'.format(list(keys), list(phi)))
+            per_field = [phi[k] for k in keys]
+        elif isinstance(phi, tuple):
+            if len(phi) != 2:
+                raise ValueError('`phi` as a tuple is the pair (left, right or None)')
+            if (phi[1] is not None) != (len(keys) == 2):
+                raise ValueError('`phi` must hold one entry for each field {:}, and none for a field the model lacks'.format(list(keys)))
+            per_field = list(phi[:len(keys)])
+        elif np.ndim(phi) == 0:
+            per_field = [phi] * len(keys)
+        elif len(keys) == 1:
+            per_field = [phi]
+        else:
+            raise ValueError('`phi` of a model of two fields is a scalar, a dict or the pair (left, right)')
+        out = []
+        for k, value in zip(keys, per_field):
+            keep = np.asarray(self._no_nan_index[k], dtype=bool)
+            n_all, n_keep = keep.size, int(np.count_nonzero(keep))
+            try:
+                value = np.asarray(value, dtype=np.float64)
+            except (TypeError, ValueError):
+                raise ValueError('`phi` of field {:} is not numeric'.format(k))
+            if value.ndim == 0:
+                kept = np.full(n_keep, float(value))
+            elif value.shape == tuple(self._fields_spatial_shape[k]) or value.shape == (n_all,):
+                kept = value.reshape(-1)[keep]              # (NaN at masked points, as `lag1_autocorrelation` returns them, is dropped here)
+            elif value.shape == (n_keep,):
+                kept = value
+            else:
+                raise ValueError('`phi` of field {:} has shape {:}; expected a scalar, {:}, ({:},) or ({:},)'.format(
+                    k, value.shape, tuple(self._fields_spatial_shape[k]), n_all, n_keep))
+            if not np.all(np.abs(kept) < 1.0):              # (False for NaN)
+                raise ValueError('`phi` of field {:} must be finite with |phi| < 1 at every kept point'.format(k))
+            full = np.zeros(n_all, dtype=np.float64)
+            full[keep] = kept
+            out.append(full)
+        return out[0], (out[1] if len(out) == 2 else None)
+
+    def rule_n(self, n_runs, n_modes=None, seed=None, dtype=np.float64, noise='white', phi=None):
         """Rule N (Overland & Preisendorfer 1982): spectra of `n_runs` Gaussian surrogates, scaled to the model's sum.
 
         The surrogate loop (array.py:1753-1765) runs on the device; when `torch.distributed` is initialised the
         runs are sharded over the ranks (contiguous blocks) and gathered with one collective.
         `seed` (extension): key of the counter-based device generator; default: drawn from numpy's global RNG, so
         `np.random.seed(s)` makes the result reproducible like the reference's use of the global stream.
+        `noise` (extension): 'white' - uncorrelated surrogates, the reference's test; 'ar1' - red noise: every column of a surrogate
+        is an AR(1) series of unit variance with the lag-1 autocorrelation `phi` of its grid point, made on the device from the same
+        normals (phi = 0 gives the white surrogates bit for bit).  `phi`: None - estimated from the model's fields
+        (`lag1_autocorrelation`); a scalar; or per field (a dict by field name, or the pair (left, right)) a scalar or an array in
+        the field's spatial shape, flat over all grid points, or flat over the kept ones.  Masked points take no phi (NaN is
+        accepted there): their surrogate columns stay white.  With several ranks every rank must pass the same phi.
         Returns an array (modes x kept runs); runs whose rotation does not converge are dropped (array.py:1762-1763).
         """
         from . import dist
+        if noise not in ('white', 'ar1'):
+            raise ValueError("{:} is not a valid noise model. Either 'white' or 'ar1'.".format(noise))
+        if noise == 'white' and phi is not None:
+            raise ValueError("`phi` belongs to noise='ar1'; white surrogates have none.")
+        red = {}
+        if noise == 'ar1':
+            # (estimated before the surrogates take over the handle)
+            red['ar1'] = self._phi_columns(self.lag1_autocorrelation() if phi is None else phi)
         if seed is None:
             seed = int(np.random.randint(0, 2 ** 31 - 1)) * 2 ** 31 + int(np.random.randint(0, 2 ** 31 - 1))
         m = self._n_observations
@@ -1470,7 +1548,7 @@ class MCA:
         spectra, kept = dist.sharded_rule_n(
             self._device(), n_runs, T=m['left'], Nx=n['left'], Ny=n.get('right', 0), n_fields=len(self._keys),
             complexify=self._analysis['is_complex'], rotated=rotated, p=n_rot, power=self._analysis['power'],
-            tol=1e-8, seed=seed, dtype=dtype, n_out=n_out)
+            tol=1e-8, seed=seed, dtype=dtype, n_out=n_out, **red)
         svals = spectra[kept.astype(bool)].T          # modes x kept runs
         ref = self._get_variance()
         svals /= svals.sum(axis=0) / ref.sum()

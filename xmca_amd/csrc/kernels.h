@@ -412,6 +412,54 @@ __global__ void column_finish_sums_kernel(const int* __restrict__ part_nan, cons
   if (mean) mean[c] = s / rows;
 }
 
+// Lag-1 autocorrelation of every column, the same row chunks: part[0 / 1 / 2][chunk][c] = sum x, sum x^2 and
+// sum x[t] x[t+1] over the rows t of the chunk (the product belongs to the chunk of t: a chunk reads one row past its end);
+// ends[0][c] = x[0][c], ends[1][c] = x[rows-1][c].
+template <typename T>
+__global__ void lag1_partial_kernel(const T* __restrict__ x, int rows, int64_t cols, double* __restrict__ part, double* __restrict__ ends) {
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= cols) return;
+  const int per = (rows + (int)gridDim.y - 1) / (int)gridDim.y;
+  const int r0 = (int)blockIdx.y * per, r1 = min(rows, r0 + per);
+  double s = 0.0, q = 0.0, l = 0.0;
+  if (r0 < r1) {
+    double v = (double)x[(int64_t)r0 * cols + c];
+    if (r0 == 0) ends[c] = v;
+    for (int r = r0; r < r1; ++r) {
+      const double next = r + 1 < rows ? (double)x[(int64_t)(r + 1) * cols + c] : 0.0;
+      s += v;
+      q += v * v;
+      l += v * next;
+      if (r == rows - 1) ends[cols + c] = v;
+      v = next;
+    }
+  }
+  const int64_t plane = (int64_t)gridDim.y * cols, at = (int64_t)blockIdx.y * cols + c;
+  part[at] = s;
+  part[plane + at] = q;
+  part[2 * plane + at] = l;
+}
+
+// phi[c] = sum_t (x[t] - m)(x[t+1] - m) / sum_t (x[t] - m)^2 from the raw sums of the chunks, added in a fixed order:
+// (L - m (2 S - x_0 - x_last) + (rows - 1) m^2) / (Q - rows m^2).  A column that is constant to rounding (the denominator is
+// within the rounding error of Q) gives 0: never a NaN.
+__global__ void lag1_finish_kernel(const double* __restrict__ part, const double* __restrict__ ends, int chunks, int rows, int64_t cols,
+                                   double* __restrict__ phi) {
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= cols) return;
+  const int64_t plane = (int64_t)chunks * cols;
+  double s = 0.0, q = 0.0, l = 0.0;
+  for (int k = 0; k < chunks; ++k) {
+    s += part[(int64_t)k * cols + c];
+    q += part[plane + (int64_t)k * cols + c];
+    l += part[2 * plane + (int64_t)k * cols + c];
+  }
+  const double m = s / rows;
+  const double den = q - (double)rows * m * m;
+  const double num = l - m * (2.0 * s - ends[c] - ends[cols + c]) + (double)(rows - 1) * m * m;
+  phi[c] = den > 4.0 * rows * 1.1102230246251565e-16 * q ? num / den : 0.0;
+}
+
 // x[r][c] -= mean[c]
 template <typename T>
 __global__ void subtract_column_means_kernel(T* __restrict__ x, int rows, int64_t cols, const double* __restrict__ mean) {
@@ -980,6 +1028,102 @@ __global__ void philox_normal_kernel(T* __restrict__ out, int64_t n, uint64_t se
     out[2 * i] = (T)(rad * cs);
     if (2 * i + 1 < n) out[2 * i + 1] = (T)(rad * sn);
   }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Red-noise surrogates: the AR(1) recurrence down the columns of the T x N plane of normals e that
+// philox_normal_kernel has just filled, in place,
+//   x[0] = e[0],   x[t] = fma(phi_c, x[t-1], sqrt(1 - phi_c^2) e[t]),
+// in float64 whatever the plane's type (x is rounded on store, the state is not).  A lane per column, a row per step: every
+// access is one coalesced row piece.  Columns alone leave the chip empty, so time is cut into segments that depend on
+// (T, N) ONLY - never on lanes, ranks or occupancy: the surrogates must not depend on who makes them.
+// ------------------------------------------------------------------------------------------------
+constexpr int AR1_BLOCK = 64;           // one wave per workgroup: the grid spreads over the CUs at every width
+constexpr int AR1_ROWS_IN_FLIGHT = 8;   // independent row loads issued ahead of the dependent FMA chain
+constexpr int AR1_MIN_SEGMENT = 32;     // rows: a shorter segment is not worth its carry
+constexpr int AR1_MAX_SEGMENTS = 64;
+constexpr int AR1_TARGET_WAVES = 2048;  // 256 CUs x 8 waves
+
+struct Ar1Segments {
+  int64_t count, length;     // segment k covers the rows [k length, min(T, (k + 1) length))
+};
+
+// as many segments as fill the chip at this width, none shorter than AR1_MIN_SEGMENT rows (the last one excepted)
+__host__ __device__ inline Ar1Segments ar1_segments(int64_t T, int64_t N) {
+  const int64_t waves = (N + 63) / 64;
+  int64_t want = (AR1_TARGET_WAVES + waves - 1) / waves;
+  if (want > AR1_MAX_SEGMENTS) want = AR1_MAX_SEGMENTS;
+  int64_t length = (T + want - 1) / want;
+  if (length < AR1_MIN_SEGMENT) length = AR1_MIN_SEGMENT;
+  return {(T + length - 1) / length, length};
+}
+
+// sqrt(1 - phi^2) as sqrt((1 - phi)(1 + phi)): no cancellation near |phi| = 1, and nothing the compiler may fuse
+__device__ __forceinline__ double ar1_innovation_scale(double phi) { return sqrt((1.0 - phi) * (1.0 + phi)); }
+
+__device__ __forceinline__ double ar1_ipow(double b, int64_t n) {
+  double r = 1.0;
+  for (; n > 0; n >>= 1, b *= b)
+    if (n & 1) r *= b;
+  return r;
+}
+
+// the rows [r0, r1) of column c from the state `prev` (the value of row r0 - 1; row 0 is e[0] itself): returns the value of row
+// r1 - 1.  STORE: x is written over e.  The loads of a batch do not depend on the recurrence and are issued together.
+template <typename T, bool STORE>
+__device__ __forceinline__ double ar1_run(T* __restrict__ x, int64_t cols, int64_t c, int64_t r0, int64_t r1, double phi, double a,
+                                          double prev) {
+  int64_t r = r0;
+  if (r == 0) {
+    prev = (double)x[c];
+    r = 1;
+  }
+  for (; r + AR1_ROWS_IN_FLIGHT <= r1; r += AR1_ROWS_IN_FLIGHT) {
+    double e[AR1_ROWS_IN_FLIGHT];
+#pragma unroll
+    for (int j = 0; j < AR1_ROWS_IN_FLIGHT; ++j) e[j] = (double)x[(r + j) * cols + c];
+#pragma unroll
+    for (int j = 0; j < AR1_ROWS_IN_FLIGHT; ++j) {
+      prev = fma(phi, prev, a * e[j]);
+      if (STORE) x[(r + j) * cols + c] = (T)prev;
+    }
+  }
+  for (; r < r1; ++r) {
+    prev = fma(phi, prev, a * (double)x[r * cols + c]);
+    if (STORE) x[r * cols + c] = (T)prev;
+  }
+  return prev;
+}
+
+// Pass A: carry[k][c] = the value the last row of segment k takes from a zero state in front of it (segment 0: its true value);
+// grid (columns, segments - 1), the last segment hands nothing on.  Reads only.
+template <typename T>
+__global__ void ar1_carry_kernel(const T* __restrict__ e, int64_t rows, int64_t cols, int64_t seg_len, const double* __restrict__ phi,
+                                 double* __restrict__ carry) {
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= cols) return;
+  const int64_t k = blockIdx.y, r0 = k * seg_len, r1 = min(rows, r0 + seg_len);
+  const double p = phi[c], a = ar1_innovation_scale(p);
+  carry[k * cols + c] = ar1_run<T, false>(const_cast<T*>(e), cols, c, r0, r1, p, a, 0.0);
+}
+
+// Pass B: the state in front of segment k in a fixed order, in_1 = carry_0, in_j = phi^len in_{j-1} + carry_{j-1}, then the
+// segment is run again from it and stored: within a segment the bits are those of the sequential recurrence.  grid (columns,
+// segments); `carry` may be null when there is one segment.
+template <typename T>
+__global__ void ar1_filter_kernel(T* __restrict__ x, int64_t rows, int64_t cols, int64_t seg_len, const double* __restrict__ phi,
+                                  const double* __restrict__ carry) {
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= cols) return;
+  const int64_t k = blockIdx.y, r0 = k * seg_len, r1 = min(rows, r0 + seg_len);
+  const double p = phi[c], a = ar1_innovation_scale(p);
+  double in = 0.0;
+  if (k > 0) {
+    const double decay = ar1_ipow(p, seg_len);
+    in = carry[c];
+    for (int64_t j = 1; j < k; ++j) in = fma(decay, in, carry[j * cols + c]);
+  }
+  (void)ar1_run<T, true>(x, cols, c, r0, r1, p, a, in);
 }
 
 }  // namespace xmca

@@ -3,7 +3,9 @@
 #include <exception>
 #include "../../include/xmca_hip.h"
 
+#include <cmath>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <type_traits>
 
@@ -1262,19 +1264,79 @@ void run_replicates(xmca_handle* h, const ReplicateSpec& spec, int64_t n_runs, F
   run_lanes(h, lanes, [&](xmca_handle* lh, int j) { lane_body(lh, (int64_t)j, (int64_t)lanes); });
 }
 
-// runs [run_begin, run_end) of xmca_rule_n: the fields of run r are N(0,1) surrogates keyed by (seed, r, side)
+// Queues the AR(1) recurrence (kernels.h) over the T x N plane of normals in x, in place.  phi: N values on the
+// device; carry: scratch of the calling lane, (segments - 1) x N.
+template <typename TI>
+void ar1_filter(hipStream_t st, TI* x, int64_t T, int64_t N, const double* phi, DevBuf<double>& carry) {
+  const Ar1Segments seg = ar1_segments(T, N);
+  const unsigned gx = (unsigned)ceil_div(N, (int64_t)AR1_BLOCK);
+  double* cr = nullptr;
+  if (seg.count > 1) {
+    cr = carry.ensure((size_t)((seg.count - 1) * N));
+    hipLaunchKernelGGL((ar1_carry_kernel<TI>), dim3(gx, (unsigned)(seg.count - 1)), dim3(AR1_BLOCK), 0, st, (const TI*)x, T, N, seg.length,
+                       phi, cr);
+  }
+  hipLaunchKernelGGL((ar1_filter_kernel<TI>), dim3(gx, (unsigned)seg.count), dim3(AR1_BLOCK), 0, st, x, T, N, seg.length, phi,
+                     (const double*)cr);
+}
+
+// every phi finite and inside (-1, 1): checked on the host before anything is launched
+void check_phi(const char* what, const double* phi, int64_t N) {
+  XMCA_CHECK(phi != nullptr, XMCA_ERR_INVALID, std::string(what) + ": phi is missing");
+  for (int64_t c = 0; c < N; ++c)
+    XMCA_CHECK(std::fabs(phi[c]) < 1.0, XMCA_ERR_INVALID, std::string(what) + ": every phi must be finite with |phi| < 1");   // (false for NaN)
+}
+
+// runs [run_begin, run_end) of xmca_rule_n: the fields of run r are N(0,1) surrogates keyed by (seed, r, side); with phi (device
+// pointers of Nx / Ny values that every lane only reads) they are filtered into AR(1) columns, xmca_rule_n_ar1
 template <typename TI>
 void rule_n_impl(xmca_handle* h, const ReplicateSpec& spec, int64_t run_begin, int64_t run_end, uint64_t seed, double* spectra, int* kept,
-                 int64_t n_out) {
+                 int64_t n_out, const double* const* phi = nullptr) {
   const int64_t Ns[2] = {spec.Nx, spec.Ny};
   run_replicates(h, spec, run_end - run_begin, [&](xmca_handle* lh, int64_t first, int64_t stride) {
+    DevBuf<double> carry;      // the lane's own: reused by its replicates in stream order
     replicate_lane<TI>(lh, "rule_n", "surrogate", spec, first, stride, run_end - run_begin, false, spectra, kept, n_out,
                        [&](int s, TI* x, int64_t run) {
                          const int64_t n = spec.T * Ns[s];
                          hipLaunchKernelGGL((philox_normal_kernel<TI>), ew_grid((n + 1) / 2), dim3(EW_BLOCK), 0, lh->st, x, n, seed,
                                             (uint32_t)(run_begin + run), (uint32_t)s);
+                         if (phi) ar1_filter<TI>(lh->st, x, spec.T, Ns[s], phi[s], carry);
                        });
   });
+}
+
+// xmca_lag1_autocorrelation: phi of the columns of the resident real plane of `side`, chunked like the column passes of the
+// constructor and finished in a fixed order
+template <typename TI>
+void lag1_impl(xmca_handle* h, int side, double* phi_out) {
+  const FieldData<TI>& f = typed<TI>(h).f[side];
+  const int64_t T = f.T, N = f.N;
+  XMCA_CHECK(T >= 2 && N >= 1, XMCA_ERR_STATE, "lag1_autocorrelation: the field needs at least 2 time steps");
+  const int chunks = (int)std::min<int64_t>(COL_CHUNKS, T);
+  const unsigned gx = (unsigned)ceil_div(N, (int64_t)256);
+  DevBuf<double> part, ends, phi;
+  hipLaunchKernelGGL((lag1_partial_kernel<TI>), dim3(gx, (unsigned)chunks), dim3(256), 0, h->st, f.r(), (int)T, N,
+                     part.ensure((size_t)3 * chunks * N), ends.ensure((size_t)2 * N));
+  hipLaunchKernelGGL(lag1_finish_kernel, dim3(gx), dim3(256), 0, h->st, (const double*)part.get(), (const double*)ends.get(), chunks, (int)T, N,
+                     phi.ensure((size_t)N));
+  XMCA_HIP(hipGetLastError());
+  XMCA_HIP(hipMemcpyAsync(phi_out, phi.get(), sizeof(double) * N, hipMemcpyDeviceToHost, h->st));
+  XMCA_HIP(hipStreamSynchronize(h->st));
+}
+
+// xmca_surrogate_ar1: the filtered, uncentred field of one run in the run dtype, widened to float64 on the host
+template <typename TI>
+void surrogate_ar1_impl(xmca_handle* h, int64_t T, int64_t N, const double* phi, uint64_t seed, uint32_t run, uint32_t side, double* out) {
+  const int64_t n = T * N;
+  DevBuf<TI> x;
+  DevBuf<double> phi_dev, carry, wide;
+  XMCA_HIP(hipMemcpyAsync(phi_dev.ensure((size_t)N), phi, sizeof(double) * N, hipMemcpyHostToDevice, h->st));
+  hipLaunchKernelGGL((philox_normal_kernel<TI>), ew_grid((n + 1) / 2), dim3(EW_BLOCK), 0, h->st, x.ensure((size_t)n), n, seed, run, side);
+  ar1_filter<TI>(h->st, x.get(), T, N, phi_dev.get(), carry);
+  hipLaunchKernelGGL((convert_kernel<TI, double>), ew_grid(n), dim3(EW_BLOCK), 0, h->st, (const TI*)x.get(), wide.ensure((size_t)n), n);
+  XMCA_HIP(hipGetLastError());
+  XMCA_HIP(hipMemcpyAsync(out, wide.get(), sizeof(double) * n, hipMemcpyDeviceToHost, h->st));
+  XMCA_HIP(hipStreamSynchronize(h->st));
 }
 
 // ---- bootstrapping: working copies on the device -----------------------------------------------------------------
@@ -1981,9 +2043,10 @@ int xmca_rotate_solved(xmca_handle* h, int p, int power, double tol, int max_ite
   API_END(h)
 }
 
-int xmca_rule_n(xmca_handle* h, int64_t T, int64_t Nx, int64_t Ny, int n_fields, const double* hilbert_col, int rotated,
-                int p, int power, double tol, int64_t run_begin, int64_t run_end, uint64_t seed, int dtype,
-                double* spectra_out, int* kept_out, int64_t n_out) {
+// xmca_rule_n (ar1 == false: white surrogates, phi_* unused) and xmca_rule_n_ar1 (phi_left, and phi_right for two fields)
+static int rule_n_entry(xmca_handle* h, int64_t T, int64_t Nx, int64_t Ny, int n_fields, const double* hilbert_col, int rotated, int p,
+                        int power, double tol, int64_t run_begin, int64_t run_end, uint64_t seed, int dtype, double* spectra_out,
+                        int* kept_out, int64_t n_out, bool ar1, const double* phi_left, const double* phi_right) {
   API_BEGIN(h)
   XMCA_CHECK(n_fields == 1 || n_fields == 2, XMCA_ERR_INVALID, "rule_n: n_fields must be 1 or 2");
   XMCA_CHECK(T >= 2 && Nx >= 1 && (n_fields == 1 || Ny >= 1), XMCA_ERR_INVALID, "rule_n: bad field shape");
@@ -1992,8 +2055,65 @@ int xmca_rule_n(xmca_handle* h, int64_t T, int64_t Nx, int64_t Ny, int n_fields,
   ComplexOp hop;
   if (hilbert_col) hop = ComplexOp::circulant(hilbert_col, T);
   const ReplicateSpec spec{T, Nx, Ny, n_fields, hilbert_col ? &hop : nullptr, rotated, p, power, tol};
-  with_dtype(dtype, [&](auto t) { rule_n_impl<decltype(t)>(h, spec, run_begin, run_end, seed, spectra_out, kept_out, n_out); });
+  // phi goes up once, before the lanes start; they only read it
+  DevBuf<double> phi_dev[2];
+  const double* phi[2] = {nullptr, nullptr};
+  if (ar1) {
+    const double* phi_host[2] = {phi_left, phi_right};
+    const int64_t Ns[2] = {Nx, Ny};
+    XMCA_CHECK(n_fields == 2 || !phi_right, XMCA_ERR_INVALID, "rule_n_ar1: phi_right given for a model of one field");
+    for (int s = 0; s < n_fields; ++s) check_phi("rule_n_ar1", phi_host[s], Ns[s]);
+    for (int s = 0; s < n_fields; ++s) {
+      XMCA_HIP(hipMemcpyAsync(phi_dev[s].ensure((size_t)Ns[s]), phi_host[s], sizeof(double) * Ns[s], hipMemcpyHostToDevice, h->st));
+      phi[s] = phi_dev[s].get();
+    }
+    XMCA_HIP(hipStreamSynchronize(h->st));
+  }
+  with_dtype(dtype, [&](auto t) {
+    rule_n_impl<decltype(t)>(h, spec, run_begin, run_end, seed, spectra_out, kept_out, n_out, ar1 ? phi : nullptr);
+  });
   h->tm.collect();
+  API_END(h)
+}
+
+int xmca_rule_n(xmca_handle* h, int64_t T, int64_t Nx, int64_t Ny, int n_fields, const double* hilbert_col, int rotated,
+                int p, int power, double tol, int64_t run_begin, int64_t run_end, uint64_t seed, int dtype,
+                double* spectra_out, int* kept_out, int64_t n_out) {
+  return rule_n_entry(h, T, Nx, Ny, n_fields, hilbert_col, rotated, p, power, tol, run_begin, run_end, seed, dtype, spectra_out, kept_out,
+                      n_out, false, nullptr, nullptr);
+}
+
+int xmca_rule_n_ar1(xmca_handle* h, int64_t T, int64_t Nx, int64_t Ny, int n_fields, const double* hilbert_col, int rotated,
+                    int p, int power, double tol, int64_t run_begin, int64_t run_end, uint64_t seed, int dtype,
+                    double* spectra_out, int* kept_out, int64_t n_out, const double* phi_left, const double* phi_right) {
+  return rule_n_entry(h, T, Nx, Ny, n_fields, hilbert_col, rotated, p, power, tol, run_begin, run_end, seed, dtype, spectra_out, kept_out,
+                      n_out, true, phi_left, phi_right);
+}
+
+int xmca_lag1_autocorrelation(xmca_handle* h, int side, double* phi_out) {
+  API_BEGIN(h)
+  check_side("lag1_autocorrelation", side);
+  XMCA_CHECK(phi_out, XMCA_ERR_INVALID, "lag1_autocorrelation: no output");
+  XMCA_CHECK(h->field_set[side], XMCA_ERR_STATE, "lag1_autocorrelation: set the field first");
+  with_dtype(h->dtype, [&](auto t) { lag1_impl<decltype(t)>(h, side, phi_out); });
+  API_END(h)
+}
+
+int xmca_ar1_segments(int64_t T, int64_t N, int64_t* count_out, int64_t* length_out) {
+  if (T < 1 || N < 1 || !count_out || !length_out) return XMCA_ERR_INVALID;
+  const ::xmca::Ar1Segments seg = ::xmca::ar1_segments(T, N);
+  *count_out = seg.count;
+  *length_out = seg.length;
+  return XMCA_OK;
+}
+
+int xmca_surrogate_ar1(xmca_handle* h, int64_t T, int64_t N, const double* phi, uint64_t seed, uint32_t run, uint32_t side, int dtype,
+                       double* out) {
+  API_BEGIN(h)
+  XMCA_CHECK(T >= 1 && N >= 1 && out, XMCA_ERR_INVALID, "surrogate_ar1: bad arguments");
+  XMCA_CHECK(dtype == XMCA_F32 || dtype == XMCA_F64, XMCA_ERR_INVALID, "surrogate_ar1: dtype must be XMCA_F32 or XMCA_F64");
+  check_phi("surrogate_ar1", phi, N);
+  with_dtype(dtype, [&](auto t) { surrogate_ar1_impl<decltype(t)>(h, T, N, phi, seed, run, side, out); });
   API_END(h)
 }
 
@@ -2097,9 +2217,10 @@ int xmca_comm_info(xmca_comm* c, int* rank, int* world, int64_t* collectives, in
   return XMCA_OK;
 }
 
-int xmca_rule_n_sharded(xmca_handle* h, xmca_comm* c, int64_t n_runs, int64_t T, int64_t Nx, int64_t Ny, int n_fields,
-                        const double* hilbert_col, int rotated, int p, int power, double tol, uint64_t seed, int dtype,
-                        double* spectra_out, int* kept_out, int64_t n_out) {
+// Shard, all-gather and status row of xmca_rule_n_sharded / xmca_rule_n_ar1_sharded: local(b, e, seed, spectra, kept) runs this
+// rank's block [b, e) of the runs with the seed of rank 0 and returns its status
+static int rule_n_sharded_body(xmca_handle* h, xmca_comm* c, int64_t n_runs, uint64_t seed, double* spectra_out, int* kept_out,
+                               int64_t n_out, const std::function<int(int64_t, int64_t, uint64_t, double*, int*)>& local_runs) {
   if (!h || !c) return XMCA_ERR_INVALID;
   if (n_runs < 0 || n_out < 1 || !spectra_out || !kept_out) { h->err = "rule_n_sharded: bad arguments"; return XMCA_ERR_INVALID; }
   if (c->device != h->device) { h->err = "rule_n_sharded: the communicator belongs to another device"; return XMCA_ERR_INVALID; }
@@ -2122,7 +2243,7 @@ int xmca_rule_n_sharded(xmca_handle* h, xmca_comm* c, int64_t n_runs, int64_t T,
   std::vector<double> local((size_t)rows * width, 0.0), all;
   std::vector<double> sp((size_t)std::max<int64_t>(e - b, 1) * n_out, 0.0);
   std::vector<int> kp((size_t)std::max<int64_t>(e - b, 1), 0);
-  int local_rc = xmca_rule_n(h, T, Nx, Ny, n_fields, hilbert_col, rotated, p, power, tol, b, e, seed, dtype, sp.data(), kp.data(), n_out);
+  int local_rc = local_runs(b, e, seed, sp.data(), kp.data());
   if (const char* inj = std::getenv("XMCA_TEST_FAIL_RANK"))          // (tests: make this rank's shard fail)
     if (std::atoi(inj) == c->rank && local_rc == XMCA_OK) { local_rc = XMCA_ERR_NUMERIC; h->err = "rule_n_sharded: injected failure (XMCA_TEST_FAIL_RANK)"; }
   const std::string local_err = h->err;
@@ -2155,6 +2276,22 @@ int xmca_rule_n_sharded(xmca_handle* h, xmca_comm* c, int64_t n_runs, int64_t T,
     }
   }
   return XMCA_OK;
+}
+
+int xmca_rule_n_sharded(xmca_handle* h, xmca_comm* c, int64_t n_runs, int64_t T, int64_t Nx, int64_t Ny, int n_fields,
+                        const double* hilbert_col, int rotated, int p, int power, double tol, uint64_t seed, int dtype,
+                        double* spectra_out, int* kept_out, int64_t n_out) {
+  return rule_n_sharded_body(h, c, n_runs, seed, spectra_out, kept_out, n_out, [&](int64_t b, int64_t e, uint64_t sd, double* sp, int* kp) {
+    return xmca_rule_n(h, T, Nx, Ny, n_fields, hilbert_col, rotated, p, power, tol, b, e, sd, dtype, sp, kp, n_out);
+  });
+}
+
+int xmca_rule_n_ar1_sharded(xmca_handle* h, xmca_comm* c, int64_t n_runs, int64_t T, int64_t Nx, int64_t Ny, int n_fields,
+                            const double* hilbert_col, int rotated, int p, int power, double tol, uint64_t seed, int dtype,
+                            double* spectra_out, int* kept_out, int64_t n_out, const double* phi_left, const double* phi_right) {
+  return rule_n_sharded_body(h, c, n_runs, seed, spectra_out, kept_out, n_out, [&](int64_t b, int64_t e, uint64_t sd, double* sp, int* kp) {
+    return xmca_rule_n_ar1(h, T, Nx, Ny, n_fields, hilbert_col, rotated, p, power, tol, b, e, sd, dtype, sp, kp, n_out, phi_left, phi_right);
+  });
 }
 
 int xmca_surrogate(xmca_handle* h, int64_t n, uint64_t seed, uint32_t run, uint32_t side, double* out) {

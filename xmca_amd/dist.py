@@ -140,13 +140,17 @@ def _process_start_time():
         return time.time()
 
 
-def sharded_rule_n(dev, n_runs, *, T, Nx, Ny, n_fields, complexify, rotated, p, power, tol, seed, dtype, n_out, comm=None):
+def sharded_rule_n(dev, n_runs, *, T, Nx, Ny, n_fields, complexify, rotated, p, power, tol, seed, dtype, n_out, comm=None, ar1=None):
     """Returns (spectra [n_runs x n_out], kept [n_runs]) assembled on every rank.
 
     `comm`: a native communicator (`init_native`) - shard, seed broadcast and the all-gather then run inside the library
-    (xmca_rule_n_sharded); otherwise the torch.distributed group when one is initialised; otherwise a single rank."""
+    (xmca_rule_n_sharded); otherwise the torch.distributed group when one is initialised; otherwise a single rank.
+    `ar1 = (phi_left, phi_right or None)`: red-noise surrogates with these lag-1 autocorrelations per column; the keyword is
+    forwarded to the device only when it is set.  phi is NOT broadcast: every rank estimates it from the same fields with a
+    deterministic kernel (`MCA.lag1_autocorrelation`), and a phi the user supplies is the caller's to keep equal across ranks."""
+    red = {} if ar1 is None else {"ar1": ar1}
     if comm is not None:
-        return dev.rule_n_sharded(comm, n_runs, T, Nx, Ny, n_fields, complexify, rotated, p, power, tol, seed, dtype, n_out)
+        return dev.rule_n_sharded(comm, n_runs, T, Nx, Ny, n_fields, complexify, rotated, p, power, tol, seed, dtype, n_out, **red)
     td = _dist()
     rank, world = rank_world()
     seed = broadcast_seed(seed, dev)
@@ -157,7 +161,7 @@ def sharded_rule_n(dev, n_runs, *, T, Nx, Ny, n_fields, complexify, rotated, p, 
     failure = None
     spectra = kept = None
     try:
-        spectra, kept = dev.rule_n(T, Nx, Ny, n_fields, complexify, rotated, p, power, tol, begin, end, seed, dtype, n_out)
+        spectra, kept = dev.rule_n(T, Nx, Ny, n_fields, complexify, rotated, p, power, tol, begin, end, seed, dtype, n_out, **red)
     except Exception as err:                                      # noqa: BLE001  (reported on every rank below)
         if td is None:
             raise
