@@ -375,6 +375,35 @@ int xmca_bootstrap_runs_theta(xmca_handle* h, const double* col3, const double* 
 int xmca_bootstrap_runs_columns_theta(xmca_handle* h, const double* col3, const double* hbar, const double* B, int period,
                                       const int64_t* cols_left, const int64_t* cols_right, int64_t n_runs, int rotated, int p,
                                       int power, double tol, double* spectra_out, int* kept_out, int64_t n_out);
+/* Bootstrap mean and standard error of the k leading singular vectors (an extension), after xmca_bootstrap_begin.
+ * Replicate r gathers the rows idx[r * T .. (r + 1) * T) of EVERY working copy (a pairs bootstrap; independent draws, not
+ * composed), is centred, complexified with the Hilbert transform (hilbert_col; NULL: real) and solved for its k leading vectors
+ * v_r.  With the model's unit vectors v0 (host float64 planes of k x N[side], mode-major; the im planes NULL for a real model, the
+ * right ones NULL for one field):  c_rj = sum over sides and columns of conj(v0[j, n]) v_r[j, n];  u_rj = conj(c_rj) / |c_rj|
+ * (1 where c_rj = 0);  d = u_rj v_r - v0;  S = sum_r d and Q = sum_r |d|^2 in float64.
+ *   mean_*        k x N[side] float64, interleaved (re, im) when complex:  v0 + S / n_runs
+ *   std_*         k x N[side] float64:  sqrt(max(0, Q - |S|^2 / n_runs) / (n_runs - 1))
+ *   congruence_out  n_runs x k:  |c_rj| / n_fields, in [0, 1]
+ *   sigma_out     n_runs x k: the replicates' leading singular values;  kept_out  n_runs flags (always 1: nothing is rotated)
+ * No sum uses an atomic: a call repeats its bits.  The association of S and Q follows the lanes the runs fall on
+ * (XMCA_RULE_N_LANES), so two lane counts agree to rounding; congruence_out and sigma_out do not depend on the lanes.
+ * Refused before anything is launched (XMCA_ERR_INVALID): n_runs < 2, k < 1 or above min(T, N), an index outside [0, T), missing
+ * vectors or outputs; no xmca_bootstrap_begin: XMCA_ERR_STATE. */
+int xmca_bootstrap_patterns(xmca_handle* h, const double* hilbert_col, const int64_t* idx, int64_t n_runs, int k,
+                            const double* v0_left_re, const double* v0_left_im, const double* v0_right_re, const double* v0_right_im,
+                            double* mean_left, double* std_left, double* mean_right, double* std_right, double* congruence_out,
+                            double* sigma_out, int* kept_out);
+/* (tests) The statistics of xmca_bootstrap_patterns from replicate vectors given by the host: v_* are n_runs x k x N[side] float64
+ * planes, narrowed to float32 on the device when plane_dtype is XMCA_F32; N_right = 0: one side.  Run r is accumulated in the
+ * accumulators r % n_lanes (1 <= n_lanes <= 8), which are then merged as the lanes of a bootstrap are.  Outputs as above. */
+int xmca_pattern_stats(xmca_handle* h, const double* v0_left_re, const double* v0_left_im, const double* v0_right_re,
+                       const double* v0_right_im, const double* v_left_re, const double* v_left_im, const double* v_right_re,
+                       const double* v_right_im, int64_t n_runs, int k, int64_t N_left, int64_t N_right, int is_complex, int plane_dtype,
+                       int n_lanes, double* mean_left, double* std_left, double* mean_right, double* std_right,
+                       double* congruence_out);
+/* (no device) Columns per partial sum of the alignment c_rj: a compile-time constant, so the association of that sum is a
+ * function of N alone. */
+int xmca_pattern_tile(void);
 int xmca_is_complex(xmca_handle* h);
 /* 1 when the singular vectors of `side` from the last xmca_solve are resident in float32: a real float32 field decomposed on
  * its dual side (N > T) keeps `_V` in the input's dtype as the reference does (xmca/array.py:584, the dtype of

@@ -61,6 +61,10 @@ SIGNATURES = {
     "xmca_bootstrap_runs_theta": (_c_int, [_vp, _vp, _vp, _vp, _c_int, _vp, _vp, _c_i64, _c_int, _c_int, _c_int, _c_dbl, _vp, _vp, _c_i64]),
     "xmca_bootstrap_runs_columns_theta": (_c_int, [_vp, _vp, _vp, _vp, _c_int, _vp, _vp, _c_i64, _c_int, _c_int, _c_int, _c_dbl, _vp, _vp,
                                                    _c_i64]),
+    "xmca_bootstrap_patterns": (_c_int, [_vp, _vp, _vp, _c_i64, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "xmca_pattern_stats": (_c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _c_int, _c_i64, _c_i64, _c_int, _c_int, _c_int,
+                                    _vp, _vp, _vp, _vp, _vp]),
+    "xmca_pattern_tile": (_c_int, []),
     "xmca_correlate": (_c_int, [_vp, _c_int, _vp, _c_i64, _c_i64, _vp]),
     "xmca_pearson_pvalues": (_c_int, [_vp, _vp, _c_i64, _c_i64, _vp]),
     "xmca_pvalue_log_norm": (_c_int, [_c_i64, _dp]),
@@ -205,6 +209,25 @@ def ar1_segments(T, N):
     if rc != 0:
         raise ValueError("ar1_segments: T and N must be >= 1")
     return [(k * length.value, min(int(T), (k + 1) * length.value)) for k in range(count.value)]
+
+
+def pattern_tile():
+    """Columns per partial sum of the alignment of `bootstrap_patterns` (xmca_pattern_tile; no device): a constant of the build."""
+    return int(load_library().xmca_pattern_tile())
+
+
+def _mode_major_planes(what, V, k, cplx):
+    """The vectors of one field, N x k (or None), as the contiguous float64 planes k x N the pattern entries read: (re, im or None, N)."""
+    if V is None:
+        return None, None, 0
+    V = np.asarray(V)
+    if V.ndim != 2 or V.shape[1] != k or V.shape[0] < 1:
+        raise ValueError("%s: the vectors of a field must be N x %d, got shape %s" % (what, k, V.shape))
+    if np.iscomplexobj(V) and not cplx:
+        raise ValueError("%s: complex vectors for a real model" % what)
+    re = np.ascontiguousarray(V.real.T, dtype=np.float64)
+    im = np.ascontiguousarray(V.imag.T, dtype=np.float64) if cplx else None
+    return re, im, V.shape[0]
 
 
 def _phi_array(what, phi, N):
@@ -780,6 +803,61 @@ class Handle:
         self._check(run(self._h, _ptr(ht), _ptr(il), _ptr(ir), n_runs, int(rotated), int(p), int(power), float(tol), _ptr(out),
                         _ptr(kept), n_out))
         return out, kept.astype(bool)
+
+    def bootstrap_patterns(self, T, complexify, idx, n_runs, k, v0_left, v0_right=None):
+        """Bootstrap mean and standard error of the k leading vectors (xmca_bootstrap_patterns), after `bootstrap_begin`: run r
+        resamples the rows idx[r] (n_runs x T, the same for every field), is centred, complexified like the model and solved; its
+        vectors are aligned with v0 (N x k per field, unit columns) and accumulated on the device.  Returns (mean, std, congruence,
+        sigma, kept): mean / std lists of N x k arrays per field (mean complex for a complex model, std real), congruence and sigma
+        n_runs x k, kept n_runs flags."""
+        n_runs, k, cplx = int(n_runs), int(k), bool(complexify)
+        if n_runs < 2:
+            raise ValueError("bootstrap_patterns: a standard error needs n_runs >= 2")
+        idx = np.ascontiguousarray(idx, dtype=np.int64)
+        if idx.shape != (n_runs, int(T)):
+            raise ValueError("bootstrap_patterns: the row indices must be n_runs x T")
+        sides = [_mode_major_planes("bootstrap_patterns", V, k, cplx) for V in (v0_left, v0_right)]
+        mean = [np.empty((k, N), dtype=np.complex128 if cplx else np.float64) if re is not None else None for re, _, N in sides]
+        std = [np.empty((k, N), dtype=np.float64) if re is not None else None for re, _, N in sides]
+        congruence = np.empty((n_runs, k), dtype=np.float64)
+        sigma = np.zeros((n_runs, k), dtype=np.float64)
+        kept = np.zeros(n_runs, dtype=np.int32)
+        ht = hilbert_imag_column(int(T)) if cplx else None
+        self._check(self._lib.xmca_bootstrap_patterns(
+            self._h, _ptr(ht), _ptr(idx), n_runs, k, _ptr(sides[0][0]), _ptr(sides[0][1]), _ptr(sides[1][0]), _ptr(sides[1][1]),
+            _ptr(mean[0]), _ptr(std[0]), _ptr(mean[1]), _ptr(std[1]), _ptr(congruence), _ptr(sigma), _ptr(kept)))
+        n = 1 if v0_right is None else 2
+        return [m.T for m in mean[:n]], [s.T for s in std[:n]], congruence, sigma, kept.astype(bool)
+
+    def pattern_stats(self, v0_left, v_left, v0_right=None, v_right=None, plane_dtype=np.float64, n_lanes=1):
+        """(tests) The statistics of `bootstrap_patterns` from given replicate vectors (xmca_pattern_stats): v0_* N x k, v_* n_runs x
+        N x k (complex: a complex model); the replicate planes are narrowed to `plane_dtype` on the device, run r goes to the
+        accumulators r % n_lanes.  Returns (mean, std, congruence) as `bootstrap_patterns` does."""
+        v_left = np.asarray(v_left)
+        n_runs, _, k = v_left.shape
+        cplx = any(V is not None and np.iscomplexobj(V) for V in (v0_left, v_left, v0_right, v_right))
+        sides = [_mode_major_planes("pattern_stats", V, k, cplx) for V in (v0_left, v0_right)]
+        reps = []
+        for V, (_, _, N) in zip((v_left, v_right), sides):
+            if V is None:
+                reps.append((None, None))
+                continue
+            V = np.asarray(V)
+            if V.shape != (n_runs, N, k):
+                raise ValueError("pattern_stats: the replicate vectors of a field must be n_runs x N x k")
+            Vt = np.swapaxes(V, 1, 2)
+            reps.append((np.ascontiguousarray(Vt.real, dtype=np.float64), np.ascontiguousarray(Vt.imag, dtype=np.float64) if cplx else None))
+        if (v0_right is None) != (v_right is None):
+            raise ValueError("pattern_stats: a right side needs both its model vectors and its replicates")
+        mean = [np.empty((k, N), dtype=np.complex128 if cplx else np.float64) if re is not None else None for re, _, N in sides]
+        std = [np.empty((k, N), dtype=np.float64) if re is not None else None for re, _, N in sides]
+        congruence = np.empty((n_runs, k), dtype=np.float64)
+        self._check(self._lib.xmca_pattern_stats(
+            self._h, _ptr(sides[0][0]), _ptr(sides[0][1]), _ptr(sides[1][0]), _ptr(sides[1][1]), _ptr(reps[0][0]), _ptr(reps[0][1]),
+            _ptr(reps[1][0]), _ptr(reps[1][1]), int(n_runs), int(k), sides[0][2], sides[1][2], int(cplx), _np_dtype_code(plane_dtype),
+            int(n_lanes), _ptr(mean[0]), _ptr(std[0]), _ptr(mean[1]), _ptr(std[1]), _ptr(congruence)))
+        n = 1 if v0_right is None else 2
+        return [m.T for m in mean[:n]], [s.T for s in std[:n]], congruence
 
     def correlate(self, side, Y, N):
         """r (N x m) = Pearson correlation of the real part of every column of the resident field `side` with the columns

@@ -1651,6 +1651,66 @@ class MCA:
                 break
         return var_surr
 
+    def bootstrap_eofs(self, n_runs, n_modes=10, block_size=1, seed=None, indices=None):
+        """Bootstrap mean and standard error of the leading EOFs at every grid point (an extension).
+
+        `n_runs` (>= 2) replicates resample the time steps of all fields with the same moving-block index (a pairs bootstrap;
+        `bootstrap_row_indices(n_runs, T, block_size, seed)`, or `indices`, an (n_runs, T) integer array, instead of the draw).
+        The replicates are independent draws from the model's fields as `solve` saw them - weights and standardisation are
+        kept, not estimated again - and are centred, Hilbert-transformed if the model is complex, and solved on the device,
+        several in flight.  The first `n_modes` singular vectors of a replicate are aligned with the model's - one sign (real) or
+        phase (complex) per mode, shared by both fields - and their deviation from the model's is accumulated on the device in
+        float64; only the statistics come back.
+
+        Returns a dict: 'mean' and 'std' - per field an array in the layout of `eofs(n_modes)`, spatial shape + (n_modes,), NaN at
+        masked points; the mean is complex for a complex model, the standard error (ddof = 1, both parts of a complex vector) is
+        real; 'congruence' - n_modes x n_runs, |<v0, v_r>| / number of fields in [0, 1], small where a replicate's mode is not the
+        model's (degenerate or swapped modes inflate 'std' there); 'singular_values' - n_modes x n_runs, the replicates'.
+
+        The results are float64 / complex128 numpy arrays for every field dtype, also for a model made with output='torch'.
+        Under an initialised `torch.distributed` group every rank computes all replicates: nothing is sharded and no collective
+        is called.  Rotated models and models solved with `extend=` are not supported (ValueError)."""
+        self._get_svals(1)                    # (before `solve`: the getters' RuntimeError)
+        if isinstance(n_runs, (bool, np.bool_)) or not isinstance(n_runs, (int, np.integer)) or n_runs < 2:
+            raise ValueError('`n_runs` must be an integer >= 2 (a standard error needs two replicates), not {!r}'.format(n_runs))
+        if self._analysis['is_rotated']:
+            raise ValueError('bootstrap_eofs does not support rotated models (out of scope: the modes of a replicate would have '
+                             'to be matched with the rotated ones)')
+        if self._analysis['extend']:
+            raise ValueError('bootstrap_eofs does not support models solved with `extend=` (out of scope)')
+        resident = len(self._singular_values)
+        if isinstance(n_modes, (bool, np.bool_)) or not isinstance(n_modes, (int, np.integer)) or not 1 <= n_modes <= resident:
+            raise ValueError('`n_modes` must be an integer between 1 and the {:} modes the model holds, not {!r}'.format(resident, n_modes))
+        n_runs, k = int(n_runs), int(n_modes)
+        n_obs = self._n_observations['left']
+        if indices is None:
+            indices = bootstrap_row_indices(n_runs, n_obs, block_size=block_size, seed=seed)
+        else:
+            indices = np.asarray(indices)
+            if indices.shape != (n_runs, n_obs) or not np.issubdtype(indices.dtype, np.integer):
+                raise ValueError('`indices` must be an integer array of shape (n_runs, n_obs) = ({:}, {:})'.format(n_runs, n_obs))
+            if indices.min() < 0 or indices.max() >= n_obs:
+                raise ValueError('`indices` must lie in [0, {:})'.format(n_obs))
+        complexify = bool(self._analysis['is_complex'])
+        V0 = self._get_V(k, rotated=False)              # (fetched before the replicates take over the handle)
+        dev = self._device()
+        if not self._owns_device_fields(dev):
+            X = self._get_X(original_scale=False, real=True)
+            for side, key in enumerate(self._keys):
+                dev.set_field(side, _device_ready(np.ascontiguousarray(X[key])))
+        # (else the fields solve() worked on are still resident: their real planes are what the replicates resample, and
+        #  the replicates work on copies, so the model keeps owning them)
+        dev.bootstrap_begin(len(self._keys))
+        mean, std, congruence, sigma, _ = dev.bootstrap_patterns(
+            n_obs, complexify, indices, n_runs, k, V0[self._keys[0]], V0[self._keys[1]] if len(self._keys) == 2 else None)
+        out = {'mean': {}, 'std': {}, 'congruence': np.ascontiguousarray(congruence.T), 'singular_values': np.ascontiguousarray(sigma.T)}
+        for side, key in enumerate(self._keys):
+            shape = self._fields_spatial_shape[key] + (k,)
+            for name, values in (('mean', mean[side]), ('std', std[side])):
+                full = self._with_nan_columns(key, np.asarray(values).T, (k,)).T
+                out[name][key] = np.ascontiguousarray(full).reshape(shape)
+        return out
+
     # ------------------------------------------------------------------------------------------
     # truncation / persistence (array.py:1602-1714, :1954-2012)
     # ------------------------------------------------------------------------------------------
@@ -1809,6 +1869,25 @@ def compose_bootstrap_indices(n_runs, axis, n_obs, widths, on_left, on_right, bl
         n_left = widths[0]
         return np.ascontiguousarray(composed[:, :n_left]), (np.ascontiguousarray(composed[:, n_left:]) if n_fields == 2 else None)
     return (composed, None) if on_left else (None, composed)
+
+
+def bootstrap_row_indices(n_runs, T, block_size=1, seed=None):
+    """Row indices of a moving-block bootstrap, (n_runs, T) int64: every run is ceil(T / block_size) blocks of `block_size`
+    consecutive time steps with independently drawn starts in [0, T - block_size], cut to T rows.  The runs are independent draws
+    from the original series (not composed like `compose_bootstrap_indices`).  `seed` keys `np.random.default_rng`; None draws
+    one from numpy's global RNG, so `np.random.seed(s)` makes the result reproducible.  No device is involved."""
+    n_runs, T, b = int(n_runs), int(T), int(block_size)
+    if T < 1 or n_runs < 0:
+        raise ValueError('`n_runs` must be >= 0 and `T` >= 1')
+    if not 1 <= b <= T:
+        raise ValueError('`block_size` must be between 1 and the number of time steps ({:}), not {:}'.format(T, block_size))
+    if seed is None:
+        seed = int(np.random.randint(0, 2 ** 31 - 1)) * 2 ** 31 + int(np.random.randint(0, 2 ** 31 - 1))
+    rng = np.random.default_rng(seed)
+    nb = -(-T // b)
+    starts = rng.integers(0, T - b + 1, (n_runs, nb))
+    rows = (starts[..., None] + np.arange(b)).reshape(n_runs, nb * b)[:, :T]
+    return np.ascontiguousarray(rows, dtype=np.int64)
 
 
 def _gpu_visible():

@@ -12,6 +12,7 @@
 #include "solver.h"
 #include "comm.h"
 #include "theta.h"
+#include "boot_patterns.h"
 
 using namespace xmca;
 
@@ -1068,6 +1069,7 @@ struct ReplicateSpec {
   const ComplexOp* op = nullptr;
   int rotated = 0, p = 0, power = 1;
   double tol = 0.0;
+  int n_vec = 0;     // unrotated replicates: back-project the vectors of this many leading modes (xmca_bootstrap_patterns)
   int64_t eig_n() const { return std::min(T, n_fields == 2 ? std::min(Nx, Ny) : Nx); }     // order of the eigenproblems = rank
 };
 
@@ -1077,7 +1079,7 @@ template <typename TI>
 struct ReplicateRunner {
   xmca_handle* h;
   int64_t T, Ns[2];
-  int n_fields, rotated, p, power;
+  int n_fields, rotated, p, power, n_vec;
   double tol;
   bool cplx, analytic;
   DevBuf<TI> htb;
@@ -1092,9 +1094,13 @@ struct ReplicateRunner {
   DevBuf<double> sigma_dev;
 
   ReplicateRunner(xmca_handle* h_, const ReplicateSpec& s)
-      : h(h_), T(s.T), Ns{s.Nx, s.Ny}, n_fields(s.n_fields), rotated(s.rotated), p(s.p), power(s.power), tol(s.tol), cplx(s.op != nullptr),
+      : h(h_), T(s.T), Ns{s.Nx, s.Ny}, n_fields(s.n_fields), rotated(s.rotated), p(s.p), power(s.power), n_vec(s.n_vec),
+        tol(s.tol), cplx(s.op != nullptr),
         solver(h_->st, h_->gws, h_->ews, h_->tm), rot(h_->st, h_->tm, h_->gws, h_->ews) {
     const ComplexOp* op = s.op;
+    // vectors of n_vec modes wanted (xmca_bootstrap_patterns): a one-field replicate forms only those eigenvectors, as
+    // xmca_solve does for solve(n_modes=k); the values-only and rotated replicates keep their routes - their bits are pinned
+    solver.partial_vectors = n_vec > 0;
     analytic = cplx && Solver<TI>::analytic_route(op->kind == ComplexOp::CIRCULANT, T, s.Nx, s.Ny, n_fields, false);
     if (cplx) XMCA_CHECK(op->T == T, XMCA_ERR_INVALID, "replicates: the operator was made for another number of time steps");
     if (cplx && op->kind == ComplexOp::THETA) {
@@ -1124,8 +1130,8 @@ struct ReplicateRunner {
       f[s].has_im = false;
       if (cplx && !analytic) apply_operator<TI>(h, htb.get(), kb > 0 ? bdev.get() : nullptr, fit[s].get(), kb, f[s]);
     }
-    if (analytic) solver.solve_analytic(f, n_fields, rotated ? p : 0, res);
-    else solver.solve(f, n_fields, cplx, rotated ? p : 0, res);
+    if (analytic) solver.solve_analytic(f, n_fields, rotated ? p : n_vec, res);
+    else solver.solve(f, n_fields, cplx, rotated ? p : n_vec, res);
     if (!rotated) {
       for (int64_t i = 0; i < n_out; ++i) out[i] = res.sigma[i];
       return 1;
@@ -1148,15 +1154,17 @@ struct ReplicateRunner {
 // queues the raw real field of `side` (T x N, row-major) into x on the lane's stream; the field is centered like the MCA
 // constructor does (array.py:117) and handed to the runner.  `stage` names the stage timer of that preparation.  sync_each_run:
 // the stream is synchronised after every replicate (a fill that uploads from a buffer it reuses for the next replicate), else
-// once when the lane has queued its last one.
+// once when the lane has queued its last one.  after(run, result), when given, queues what the caller makes of the replicate's
+// vectors (spec.n_vec modes) behind its solve, before that synchronisation.
 template <typename TI, typename Fill>
 void replicate_lane(xmca_handle* h, const char* what, const char* stage, const ReplicateSpec& spec, int64_t first, int64_t stride,
-                    int64_t n_runs, bool sync_each_run, double* spectra, int* kept, int64_t n_out, Fill&& fill) {
+                    int64_t n_runs, bool sync_each_run, double* spectra, int* kept, int64_t n_out, Fill&& fill,
+                    const std::function<void(int64_t, const SolveResult&)>& after = nullptr) {
   FieldData<TI> f[2];
   const int64_t T = spec.T, Ns[2] = {spec.Nx, spec.Ny};
   ReplicateRunner<TI> runner(h, spec);
-  XMCA_CHECK(n_out == (spec.rotated ? (int64_t)spec.p : runner.rank()), XMCA_ERR_INVALID,
-             std::string(what) + ": n_out must be rank (unrotated) or p (rotated)");
+  XMCA_CHECK(n_out == (spec.rotated ? (int64_t)spec.p : spec.n_vec > 0 ? (int64_t)spec.n_vec : runner.rank()), XMCA_ERR_INVALID,
+             std::string(what) + ": n_out must be rank (unrotated), p (rotated) or the modes whose vectors are wanted");
   for (int64_t run = first; run < n_runs; run += stride) {
     h->tm.begin(stage);
     for (int s = 0; s < spec.n_fields; ++s) {
@@ -1168,6 +1176,7 @@ void replicate_lane(xmca_handle* h, const char* what, const char* stage, const R
     }
     h->tm.end();
     kept[run] = runner.run(f, spectra + run * n_out, n_out);
+    if (after) after(run, runner.res);
     if (sync_each_run) XMCA_HIP(hipStreamSynchronize(h->st));
   }
   if (!sync_each_run) XMCA_HIP(hipStreamSynchronize(h->st));
@@ -1339,6 +1348,89 @@ void surrogate_ar1_impl(xmca_handle* h, int64_t T, int64_t N, const double* phi,
   XMCA_HIP(hipStreamSynchronize(h->st));
 }
 
+// ---- bootstrap statistics of the vectors (boot_patterns.h) ------------------------------------------------
+// What one xmca_bootstrap_patterns / xmca_pattern_stats call keeps on the device: the model's vectors (uploaded once; the lanes
+// only read them), one set of float64 accumulators per lane and side, and the congruence of every run.  Allocated from the
+// caller's pool on the caller's stream and synchronised (begin) before a lane touches it.
+struct PatternStats {
+  int k = 0, n_sides = 1, lanes = 1;
+  bool cplx = false;
+  int64_t N[2] = {0, 0}, n_runs = 0;
+  int tile_off[2] = {0, 0}, total_tiles = 0;
+  DevBuf<double> v0_re[2], v0_im[2], acc[2], g;
+  int ncomp() const { return cplx ? 3 : 2; }
+  size_t kN(int s) const { return (size_t)k * (size_t)N[s]; }
+  double* lane_acc(int s, int lane, int comp) const { return acc[s].get() + ((size_t)lane * ncomp() + comp) * kN(s); }
+
+  void begin(xmca_handle* h, const double* const v0_re_host[2], const double* const v0_im_host[2]) {
+    int64_t tiles = 0;
+    for (int s = 0; s < n_sides; ++s) {
+      tile_off[s] = (int)tiles;
+      tiles += pattern_tiles(N[s]);
+      XMCA_HIP(hipMemcpyAsync(v0_re[s].ensure(kN(s)), v0_re_host[s], sizeof(double) * kN(s), hipMemcpyHostToDevice, h->st));
+      if (cplx) XMCA_HIP(hipMemcpyAsync(v0_im[s].ensure(kN(s)), v0_im_host[s], sizeof(double) * kN(s), hipMemcpyHostToDevice, h->st));
+      const size_t n_acc = (size_t)lanes * ncomp() * kN(s);
+      XMCA_HIP(hipMemsetAsync(acc[s].ensure(n_acc), 0, sizeof(double) * n_acc, h->st));
+    }
+    XMCA_CHECK(tiles <= INT32_MAX / 4, XMCA_ERR_UNSUPPORTED, "pattern statistics: too many columns");
+    total_tiles = (int)tiles;
+    g.ensure((size_t)(n_runs * k));
+    XMCA_HIP(hipStreamSynchronize(h->st));
+  }
+
+  // the three per-replicate kernels on `st`: vectors of run `run` (planes of TV, k rows of stride ldv; im nullptr when real)
+  // into the accumulators of `lane`; part (2 k total_tiles) and u (2 k) are scratch of the calling lane
+  template <typename TV>
+  void queue(hipStream_t st, int lane, int64_t run, const TV* const v_re[2], const TV* const v_im[2], const int64_t ldv[2], double* part,
+             double* u) const {
+    for (int s = 0; s < n_sides; ++s)
+      hipLaunchKernelGGL((pattern_dot_partial_kernel<TV>), dim3((unsigned)pattern_tiles(N[s]), (unsigned)k), dim3(PATTERN_BLOCK), 0, st,
+                         (const double*)v0_re[s].get(), (const double*)(cplx ? v0_im[s].get() : nullptr), N[s], v_re[s],
+                         cplx ? v_im[s] : (const TV*)nullptr, ldv[s], N[s], tile_off[s], total_tiles, part);
+    hipLaunchKernelGGL(pattern_phase_kernel, dim3((unsigned)ceil_div((int64_t)k, (int64_t)64)), dim3(64), 0, st, (const double*)part, total_tiles,
+                       k, n_sides, u, g.get() + run * k);
+    for (int s = 0; s < n_sides; ++s)
+      hipLaunchKernelGGL((pattern_accumulate_kernel<TV>), dim3((unsigned)ceil_div(N[s], (int64_t)PATTERN_BLOCK), (unsigned)k),
+                         dim3(PATTERN_BLOCK), 0, st, (const double*)v0_re[s].get(), (const double*)(cplx ? v0_im[s].get() : nullptr), N[s],
+                         v_re[s], cplx ? v_im[s] : (const TV*)nullptr, ldv[s], N[s], (const double*)u, lane_acc(s, lane, 0),
+                         cplx ? lane_acc(s, lane, 1) : (double*)nullptr, lane_acc(s, lane, ncomp() - 1));
+    XMCA_HIP(hipGetLastError());
+  }
+
+  // the vectors of a replicate's result, in whichever planes its solve left them
+  void queue_result(hipStream_t st, int lane, int64_t run, const SolveResult& r, double* part, double* u) const {
+    XMCA_CHECK(r.n_vec >= k && r.cplx == cplx, XMCA_ERR_STATE, "bootstrap_patterns: the replicate has not the vectors asked for");
+    for (int s = 0; s < n_sides; ++s)
+      XMCA_CHECK(r.ldv[s] == N[s] && r.vt_f32[s] == r.vt_f32[0], XMCA_ERR_STATE, "bootstrap_patterns: unexpected layout of the replicate's vectors");
+    if (r.vt_f32[0]) {
+      XMCA_CHECK(!cplx, XMCA_ERR_STATE, "bootstrap_patterns: float32-resident vectors are real");
+      const float* re[2] = {r.Vt32[0].get(), r.Vt32[1].get()};
+      const float* im[2] = {nullptr, nullptr};
+      queue<float>(st, lane, run, re, im, r.ldv, part, u);
+    } else {
+      const double* re[2] = {r.Vt[0].r(), r.Vt[1].r()};
+      const double* im[2] = {r.Vt[0].i(cplx), r.Vt[1].i(cplx)};
+      queue<double>(st, lane, run, re, im, r.ldv, part, u);
+    }
+  }
+
+  // after every lane's stream has been synchronised: merge in lane order, download (mean interleaved when complex)
+  void finish(xmca_handle* h, double* const mean_out[2], double* const std_out[2], double* congruence_out) {
+    DevBuf<double> mean[2], sd[2];
+    for (int s = 0; s < n_sides; ++s) {
+      const size_t n = kN(s), nm = n * (cplx ? 2 : 1);
+      hipLaunchKernelGGL(pattern_merge_kernel, ew_grid((int64_t)n), dim3(EW_BLOCK), 0, h->st, (const double*)acc[s].get(), lanes, cplx ? 1 : 0,
+                         (int64_t)n, (const double*)v0_re[s].get(), (const double*)(cplx ? v0_im[s].get() : nullptr), (double)n_runs,
+                         mean[s].ensure(nm), sd[s].ensure(n));
+      XMCA_HIP(hipGetLastError());
+      XMCA_HIP(hipMemcpyAsync(mean_out[s], mean[s].get(), sizeof(double) * nm, hipMemcpyDeviceToHost, h->st));
+      XMCA_HIP(hipMemcpyAsync(std_out[s], sd[s].get(), sizeof(double) * n, hipMemcpyDeviceToHost, h->st));
+    }
+    XMCA_HIP(hipMemcpyAsync(congruence_out, g.get(), sizeof(double) * (size_t)(n_runs * k), hipMemcpyDeviceToHost, h->st));
+    XMCA_HIP(hipStreamSynchronize(h->st));
+  }
+};
+
 // ---- bootstrapping: working copies on the device -----------------------------------------------------------------
 template <typename TI>
 void bootstrap_begin_impl(xmca_handle* h, int n_fields) {
@@ -1359,10 +1451,12 @@ void bootstrap_begin_impl(xmca_handle* h, int n_fields) {
 // c_r = c_{r-1}[idx_r] - so the replicates do not depend on each other on the device and can run in lanes.  Row indices address
 // the T rows of a side's own copy; column indices address the columns of [left | right], Nl + Nr of them (the reference
 // resamples the concatenation when both sides are, tools/array.py:91-138 through array.py:1921-1928), N[side] per replicate.
-// A side without indices is copied as it is.
+// A side without indices is copied as it is.  With `stats` (xmca_bootstrap_patterns: unrotated, n_out = stats->k) every replicate
+// back-projects its k leading modes and queues the pattern kernels behind its solve; lane j owns the accumulators j.
 template <typename TI>
 void bootstrap_runs_impl(xmca_handle* h, const ComplexOp* op, int axis, const int64_t* idx_left, const int64_t* idx_right, int64_t n_runs,
-                         int rotated, int p, int power, double tol, double* spectra, int* kept, int64_t n_out) {
+                         int rotated, int p, int power, double tol, double* spectra, int* kept, int64_t n_out,
+                         const PatternStats* stats = nullptr) {
   const int64_t T = h->boot_T;
   const int64_t Nl = h->boot_N[0], Nr = h->boot_fields == 2 ? h->boot_N[1] : 0;
   const int64_t* idx_host[2] = {idx_left, idx_right};
@@ -1372,10 +1466,18 @@ void bootstrap_runs_impl(xmca_handle* h, const ComplexOp* op, int axis, const in
       for (int64_t i = 0; i < n_runs * idx_len[s]; ++i)
         XMCA_CHECK(idx_host[s][i] >= 0 && idx_host[s][i] < bound, XMCA_ERR_INVALID,
                    axis == 0 ? "bootstrap: row index out of range" : "bootstrap: column index out of range");
-  const ReplicateSpec spec{T, Nl, Nr, h->boot_fields, op, rotated, p, power, tol};
+  const ReplicateSpec spec{T, Nl, Nr, h->boot_fields, op, rotated, p, power, tol, stats ? stats->k : 0};
   const DevBuf<TI>* work = typed<TI>(h).boot;
   run_replicates(h, spec, n_runs, [&](xmca_handle* lh, int64_t first, int64_t stride) {
     DevBuf<int64_t> idx_dev[2];
+    DevBuf<double> part, u;      // scratch of the lane's pattern kernels, reused in stream order
+    std::function<void(int64_t, const SolveResult&)> after;
+    if (stats) {
+      XMCA_CHECK(first < stats->lanes, XMCA_ERR_STATE, "bootstrap_patterns: more lanes than accumulators");
+      part.ensure((size_t)2 * stats->k * stats->total_tiles);
+      u.ensure((size_t)2 * stats->k);
+      after = [&, first](int64_t run, const SolveResult& r) { stats->queue_result(lh->st, (int)first, run, r, part.get(), u.get()); };
+    }
     // (synchronised after every replicate: the index buffers are overwritten by the next replicate's upload)
     replicate_lane<TI>(lh, "bootstrap", "resample", spec, first, stride, n_runs, true, spectra, kept, n_out, [&](int s, TI* x, int64_t run) {
       const int64_t N = h->boot_N[s];
@@ -1392,7 +1494,7 @@ void bootstrap_runs_impl(xmca_handle* h, const ComplexOp* op, int axis, const in
       else
         hipLaunchKernelGGL((gather_concat_columns_kernel<TI>), gather_cols_grid(T, N), dim3(GATHER_COLS_BLOCK), 0, lh->st, work[0].get(), Nl,
                            Nr > 0 ? work[1].get() : (const TI*)nullptr, Nr, idx_dev[s].get(), x, N, (int)T);
-    });
+    }, after);
   });
 }
 
@@ -1438,6 +1540,73 @@ void bootstrap_runs_theta_entry(xmca_handle* h, int axis, const double* col3, co
   const ComplexOp op = ComplexOp::theta(col3, hbar, B, period, h->boot_T);
   bootstrap_runs_impl<double>(h, &op, axis, idx_left, idx_right, n_runs, rotated, p, power, tol, spectra_out, kept_out, n_out);
   h->tm.collect();
+}
+
+// xmca_bootstrap_patterns: pairs bootstrap of the rows (one index per run, shared by the sides), k vectors per replicate, statistics
+void bootstrap_patterns_entry(xmca_handle* h, const double* hilbert_col, const int64_t* idx, int64_t n_runs, int k,
+                              const double* const v0_re[2], const double* const v0_im[2], double* const mean_out[2],
+                              double* const std_out[2], double* congruence_out, double* sigma_out, int* kept_out) {
+  XMCA_CHECK(h->boot_fields >= 1 && h->boot_T > 0, XMCA_ERR_STATE, "bootstrap_patterns: call xmca_bootstrap_begin first");
+  const int n_sides = h->boot_fields;
+  const bool cplx = hilbert_col != nullptr;
+  const int64_t T = h->boot_T;
+  XMCA_CHECK(n_runs >= 2, XMCA_ERR_INVALID, "bootstrap_patterns: a standard error needs n_runs >= 2");
+  XMCA_CHECK(idx && congruence_out && sigma_out && kept_out, XMCA_ERR_INVALID, "bootstrap_patterns: indices or output buffers missing");
+  PatternStats ps;
+  ps.n_sides = n_sides;
+  ps.cplx = cplx;
+  ps.n_runs = n_runs;
+  int64_t rank = T;
+  for (int s = 0; s < n_sides; ++s) {
+    ps.N[s] = h->boot_N[s];
+    rank = std::min(rank, ps.N[s]);
+    XMCA_CHECK(v0_re[s] && (!cplx || v0_im[s]) && mean_out[s] && std_out[s], XMCA_ERR_INVALID,
+               "bootstrap_patterns: the model's vectors or an output is missing for a side");
+  }
+  XMCA_CHECK(k >= 1 && k <= rank, XMCA_ERR_INVALID, "bootstrap_patterns: k must be between 1 and the rank min(T, N)");
+  for (int64_t i = 0; i < n_runs * T; ++i)
+    XMCA_CHECK(idx[i] >= 0 && idx[i] < T, XMCA_ERR_INVALID, "bootstrap_patterns: row index out of range");
+  ps.k = k;
+  const ReplicateSpec shape{T, ps.N[0], n_sides == 2 ? ps.N[1] : 0, n_sides};
+  ps.lanes = lanes_for(shape.eig_n(), n_runs);
+  ComplexOp hop;
+  if (cplx) hop = ComplexOp::circulant(hilbert_col, T);
+  ps.begin(h, v0_re, v0_im);
+  with_dtype(h->dtype, [&](auto t) {
+    bootstrap_runs_impl<decltype(t)>(h, cplx ? &hop : nullptr, 0, idx, n_sides == 2 ? idx : nullptr, n_runs, 0, 0, 1, 0.0, sigma_out,
+                                     kept_out, k, &ps);
+  });
+  ps.finish(h, mean_out, std_out, congruence_out);
+  h->tm.collect();
+}
+
+// xmca_pattern_stats: host vectors (n_runs x k x N per side and plane) through the kernels of xmca_bootstrap_patterns, run r
+// into the accumulators r % n_lanes, all on the handle's stream
+template <typename TV>
+void pattern_stats_impl(xmca_handle* h, PatternStats& ps, const double* const v0_re[2], const double* const v0_im[2],
+                        const double* const v_re[2], const double* const v_im[2], double* const mean_out[2], double* const std_out[2],
+                        double* congruence_out) {
+  ps.begin(h, v0_re, v0_im);
+  DevBuf<double> wide[2][2], part, u;
+  Narrow<TV> planes[2];
+  const TV* re[2] = {nullptr, nullptr};
+  const TV* im[2] = {nullptr, nullptr};
+  for (int s = 0; s < ps.n_sides; ++s) {
+    const size_t n = (size_t)ps.n_runs * ps.kN(s);
+    XMCA_HIP(hipMemcpyAsync(wide[s][0].ensure(n), v_re[s], sizeof(double) * n, hipMemcpyHostToDevice, h->st));
+    if (ps.cplx) XMCA_HIP(hipMemcpyAsync(wide[s][1].ensure(n), v_im[s], sizeof(double) * n, hipMemcpyHostToDevice, h->st));
+    planes[s].from(h->st, wide[s][0].get(), ps.cplx ? wide[s][1].get() : nullptr, (int64_t)n);
+    re[s] = planes[s].r;
+    im[s] = planes[s].i;
+  }
+  part.ensure((size_t)2 * ps.k * ps.total_tiles);
+  u.ensure((size_t)2 * ps.k);
+  for (int64_t r = 0; r < ps.n_runs; ++r) {
+    const TV* rr[2] = {re[0] + r * ps.kN(0), ps.n_sides == 2 ? re[1] + r * ps.kN(1) : nullptr};
+    const TV* ri[2] = {ps.cplx ? im[0] + r * ps.kN(0) : nullptr, ps.cplx && ps.n_sides == 2 ? im[1] + r * ps.kN(1) : nullptr};
+    ps.queue<TV>(h->st, (int)(r % ps.lanes), r, rr, ri, ps.N, part.get(), u.get());
+  }
+  ps.finish(h, mean_out, std_out, congruence_out);
 }
 
 }  // namespace
@@ -1925,6 +2094,55 @@ int xmca_bootstrap_runs_columns_theta(xmca_handle* h, const double* col3, const 
                              n_out);
   API_END(h)
 }
+
+int xmca_bootstrap_patterns(xmca_handle* h, const double* hilbert_col, const int64_t* idx, int64_t n_runs, int k,
+                            const double* v0_left_re, const double* v0_left_im, const double* v0_right_re, const double* v0_right_im,
+                            double* mean_left, double* std_left, double* mean_right, double* std_right, double* congruence_out,
+                            double* sigma_out, int* kept_out) {
+  API_BEGIN(h)
+  const double* const v0_re[2] = {v0_left_re, v0_right_re};
+  const double* const v0_im[2] = {v0_left_im, v0_right_im};
+  double* const mean_out[2] = {mean_left, mean_right};
+  double* const std_out[2] = {std_left, std_right};
+  bootstrap_patterns_entry(h, hilbert_col, idx, n_runs, k, v0_re, v0_im, mean_out, std_out, congruence_out, sigma_out, kept_out);
+  API_END(h)
+}
+
+int xmca_pattern_stats(xmca_handle* h, const double* v0_left_re, const double* v0_left_im, const double* v0_right_re,
+                       const double* v0_right_im, const double* v_left_re, const double* v_left_im, const double* v_right_re,
+                       const double* v_right_im, int64_t n_runs, int k, int64_t N_left, int64_t N_right, int is_complex, int plane_dtype,
+                       int n_lanes, double* mean_left, double* std_left, double* mean_right, double* std_right,
+                       double* congruence_out) {
+  API_BEGIN(h)
+  const bool cplx = is_complex != 0;
+  const double* const v0_re[2] = {v0_left_re, v0_right_re};
+  const double* const v0_im[2] = {v0_left_im, v0_right_im};
+  const double* const v_re[2] = {v_left_re, v_right_re};
+  const double* const v_im[2] = {v_left_im, v_right_im};
+  double* const mean_out[2] = {mean_left, mean_right};
+  double* const std_out[2] = {std_left, std_right};
+  XMCA_CHECK(n_runs >= 2 && n_runs <= (1 << 20) && k >= 1 && k <= 65535 && N_left >= 1 && N_right >= 0 && n_lanes >= 1 && n_lanes <= 8 &&
+                 congruence_out,
+             XMCA_ERR_INVALID, "pattern_stats: need n_runs >= 2, 1 <= k <= 65535, N_left >= 1 and 1 <= n_lanes <= 8");
+  XMCA_CHECK(plane_dtype == XMCA_F32 || plane_dtype == XMCA_F64, XMCA_ERR_INVALID, "pattern_stats: plane_dtype must be XMCA_F32 or XMCA_F64");
+  PatternStats ps;
+  ps.k = k;
+  ps.n_sides = N_right > 0 ? 2 : 1;
+  ps.lanes = n_lanes;
+  ps.cplx = cplx;
+  ps.n_runs = n_runs;
+  ps.N[0] = N_left;
+  ps.N[1] = N_right;
+  for (int s = 0; s < ps.n_sides; ++s)
+    XMCA_CHECK(v0_re[s] && v_re[s] && (!cplx || (v0_im[s] && v_im[s])) && mean_out[s] && std_out[s], XMCA_ERR_INVALID,
+               "pattern_stats: vectors or an output missing for a side");
+  with_dtype(plane_dtype, [&](auto tv) {
+    pattern_stats_impl<decltype(tv)>(h, ps, v0_re, v0_im, v_re, v_im, mean_out, std_out, congruence_out);
+  });
+  API_END(h)
+}
+
+int xmca_pattern_tile(void) { return PATTERN_TILE; }
 
 int xmca_correlate(xmca_handle* h, int side, const double* Y, int64_t T, int64_t m, double* r_out) {
   API_BEGIN(h)

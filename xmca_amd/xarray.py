@@ -259,6 +259,14 @@ class xMCA(MCA):
         return self._run_array(_NumpyView(self).bootstrapping_base(n_runs, n_modes, 0, on_left, on_right, block_size,
                                                                     replace, strategy, disable_progress))
 
+    def bootstrap_eofs(self, n_runs, n_modes=10, block_size=1, seed=None, indices=None):
+        """`MCA.bootstrap_eofs` with 'mean' and 'std' as DataArrays over the dims and coordinates of `eofs(n_modes)`; 'congruence'
+        and 'singular_values' (n_modes x n_runs) stay numpy arrays."""
+        out = super().bootstrap_eofs(n_runs, n_modes, block_size=block_size, seed=seed, indices=indices)
+        out['mean'] = {k: self._space_array(k, v, n_modes, 'bootstrap mean of eofs') for k, v in out['mean'].items()}
+        out['std'] = {k: self._space_array(k, v, n_modes, 'bootstrap std of eofs') for k, v in out['std'].items()}
+        return out
+
     # ------------------------------------------------------------------ persistence (netCDF through xarray)
     def _save_data(self, data, path, engine='h5netcdf', *args, **kwargs):
         out = os.path.join(path, secure_str('.'.join([data.name, 'nc'])))
