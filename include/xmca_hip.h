@@ -404,6 +404,33 @@ int xmca_pattern_stats(xmca_handle* h, const double* v0_left_re, const double* v
 /* (no device) Columns per partial sum of the alignment c_rj: a compile-time constant, so the association of that sum is a
  * function of N alone. */
 int xmca_pattern_tile(void);
+
+/* Extended EOF analysis (lag-embedded EOFs; an extension; entry points added to ABI 15 - no existing signature
+ * changes).  With X the resident real T x N field of side 0 as solve() sees it, M = embedding, T' = T - (M - 1) tau and
+ * X_j = X[j tau : j tau + T', :], the analysis is the SVD of Y = [X_0 | ... | X_{M-1}] with every column centred over its T' rows.
+ * Y is never formed: its Gram matrix is K[t][s] = sum_{j < M} G[t + j tau][s + j tau] of G = X X^T, the centring is the double
+ * centring K_c = H K H (H = I - 1 1^T / T'), the patterns of lag j are X_j^T u_c / sigma_c.
+ *   xmca_extended_eofs  Gram product, lag sum and centring (csrc/lag_gram.h), the n_modes leading eigenvectors of K_c (the partial
+ *                       eigensolver of solve(n_modes=k), with its guard at the cut), one back-projection per lag on a row-offset view
+ *                       of the field with 1 / sigma_c in the product's epilogue, sign, final layout.
+ *     keep_idx, N_full  as in xmca_get_maps: N increasing row indices below N_full, every other row of a pattern NaN; NULL: N_full = N
+ *     lam_out           T' float64: all eigenvalues of K_c (sigma^2), descending
+ *     pcs_out           T' x n_modes float64, row-major: u_c sqrt(T' - 1)
+ *     eofs_out          embedding x N_full x n_modes float64: slice j the patterns at lag j tau; unit norm over lags x points
+ *                       Sign of mode c: the entry of largest magnitude of its lag-0 pattern is positive (the first one on a tie).
+ *                       XMCA_ERR_INVALID: embedding or tau < 1, T' < 2, n_modes outside [1, min(T' - 1, M N)], a complex resident field;
+ *                       XMCA_ERR_STATE: no field.  The call works in buffers of its own: the result of a solve, its rotation, a
+ *                       back-projection tail and the field planes are left as they are.  Stage timers: "gram", "lag_gram",
+ *                       "eeof_eigh", "eeof_project", "eeof_assemble".  No sum uses an atomic: a call repeats its bits.
+ *   xmca_lag_gram       (tests) the lag-sum and centring kernels alone on a host n x n float64 matrix G (symmetric): K_out,
+ *                       T' x T' with T' = n - (embedding - 1) tau >= 1, is the lag sum (terms added in the order j = 0 .. M-1) and,
+ *                       with center != 0, its double centring K - (r_t + r_s) + g from the means r of its columns and their mean g.
+ *   xmca_lag_gram_tile  (no device) the output tile edge of the lag-sum kernel.  A tile's M shifted windows are staged through LDS as
+ *                       one diagonal band when tau is below the tile edge and tile + (M - 1) tau <= 96 rows; plain row reads otherwise. */
+int xmca_extended_eofs(xmca_handle* h, int embedding, int tau, int n_modes, const int64_t* keep_idx, int64_t N_full, double* lam_out,
+                       double* pcs_out, double* eofs_out);
+int xmca_lag_gram(xmca_handle* h, const double* G, int64_t n, int embedding, int tau, int center, double* K_out);
+int xmca_lag_gram_tile(void);
 int xmca_is_complex(xmca_handle* h);
 /* 1 when the singular vectors of `side` from the last xmca_solve are resident in float32: a real float32 field decomposed on
  * its dual side (N > T) keeps `_V` in the input's dtype as the reference does (xmca/array.py:584, the dtype of

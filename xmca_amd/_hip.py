@@ -65,6 +65,9 @@ SIGNATURES = {
     "xmca_pattern_stats": (_c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_i64, _c_int, _c_i64, _c_i64, _c_int, _c_int, _c_int,
                                     _vp, _vp, _vp, _vp, _vp]),
     "xmca_pattern_tile": (_c_int, []),
+    "xmca_extended_eofs": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _c_i64, _vp, _vp, _vp]),
+    "xmca_lag_gram": (_c_int, [_vp, _vp, _c_i64, _c_int, _c_int, _c_int, _vp]),
+    "xmca_lag_gram_tile": (_c_int, []),
     "xmca_correlate": (_c_int, [_vp, _c_int, _vp, _c_i64, _c_i64, _vp]),
     "xmca_pearson_pvalues": (_c_int, [_vp, _vp, _c_i64, _c_i64, _vp]),
     "xmca_pvalue_log_norm": (_c_int, [_c_i64, _dp]),
@@ -214,6 +217,11 @@ def ar1_segments(T, N):
 def pattern_tile():
     """Columns per partial sum of the alignment of `bootstrap_patterns` (xmca_pattern_tile; no device): a constant of the build."""
     return int(load_library().xmca_pattern_tile())
+
+
+def lag_gram_tile():
+    """Output tile edge of the lag-sum kernel of `extended_eofs` (xmca_lag_gram_tile; no device): a constant of the build."""
+    return int(load_library().xmca_lag_gram_tile())
 
 
 def _mode_major_planes(what, V, k, cplx):
@@ -1000,6 +1008,38 @@ class Handle:
         out = np.empty(int(N), dtype=np.float64)
         self._check(self._lib.xmca_lag1_autocorrelation(self._h, int(side), _ptr(out)))
         return out
+
+    def lag_gram(self, G, embedding, tau, center):
+        """(tests) The lag-sum and centring kernels of `extended_eofs` on a host matrix (xmca_lag_gram): K[t, s] = sum_j G[t + j tau,
+        s + j tau] for the symmetric n x n float64 `G`, T' x T' with T' = n - (embedding - 1) tau, doubly centred when `center`."""
+        G = np.ascontiguousarray(G, dtype=np.float64)
+        if G.ndim != 2 or G.shape[0] != G.shape[1]:
+            raise ValueError("lag_gram: G must be a square matrix, got shape %s" % (G.shape,))
+        n_out = G.shape[0] - (int(embedding) - 1) * int(tau)
+        if int(embedding) < 1 or int(tau) < 1 or n_out < 1:
+            raise ValueError("lag_gram: embedding and tau must be >= 1 with (embedding - 1) * tau below n")
+        out = np.empty((n_out, n_out), dtype=np.float64)
+        self._check(self._lib.xmca_lag_gram(self._h, _ptr(G), G.shape[0], int(embedding), int(tau), int(bool(center)), _ptr(out)))
+        return out
+
+    def extended_eofs(self, T, N, embedding, tau, n_modes, keep_idx=None, N_full=None):
+        """Extended EOFs of the resident real T x N field of side 0 (xmca_extended_eofs): (lam, pcs, eofs) - all T' = T - (embedding - 1)
+        tau eigenvalues sigma^2 of the centred lag-embedded field, descending; the T' x n_modes PCs of unit variance; the patterns,
+        embedding x N_full x n_modes in their final layout, NaN at the rows not in keep_idx (None: N_full = N).  All float64.  The
+        result of a solve and the fields stay as they are."""
+        M, tau, k = int(embedding), int(tau), int(n_modes)
+        n_out = int(T) - (M - 1) * tau
+        idx = None if keep_idx is None else np.ascontiguousarray(keep_idx, dtype=np.int64)
+        if idx is not None and idx.shape != (int(N),):
+            raise ValueError("extended_eofs: keep_idx must hold one row index per kept point (%d), got shape %s" % (N, idx.shape))
+        N_full = int(N) if N_full is None else int(N_full)
+        if M < 1 or tau < 1 or n_out < 2 or not 1 <= k <= min(n_out - 1, M * int(N)):
+            raise ValueError("extended_eofs: embedding, tau >= 1, T' >= 2 and 1 <= n_modes <= min(T' - 1, embedding * N) are needed")
+        lam = np.empty(n_out, dtype=np.float64)
+        pcs = np.empty((n_out, k), dtype=np.float64)
+        eofs = np.empty((M, N_full, k), dtype=np.float64)
+        self._check(self._lib.xmca_extended_eofs(self._h, M, tau, k, _ptr(idx), N_full, _ptr(lam), _ptr(pcs), _ptr(eofs)))
+        return lam, pcs, eofs
 
     # ---- instrumentation ----------------------------------------------------------------------
     def reduction_info(self):

@@ -1711,6 +1711,61 @@ class MCA:
                 out[name][key] = np.ascontiguousarray(full).reshape(shape)
         return out
 
+    def extended_eofs(self, embedding, tau=1, n_modes=10):
+        """Extended EOF analysis (EEOF; Weare & Nasstrom 1982; with a long window, multichannel SSA) of one real field: the EOFs
+        of the field embedded with its own time lags (an extension).
+
+        With X the field exactly as `solve()` sees it (T x N: centred, normalised / weighted if asked, masked columns removed),
+        M = `embedding` and T' = T - (M - 1) * `tau`, the embedded matrix is Y = [X_0 | X_1 | ... | X_{M-1}] with
+        X_j = X[j tau : j tau + T', :].  Every column of Y is centred over its T' rows and Y_c = U S V^H decomposed, with the
+        one-field conventions of `solve()`, so that `extended_eofs(1)` is `solve()`.  Y is never formed: the device sums M
+        diagonal shifts of the field's Gram matrix, centres the sum from both sides, takes `n_modes` leading eigenvectors and
+        back-projects them on row-offset views of the resident field.  A prior `solve()` is not needed; a solved (and rotated)
+        model keeps its result.
+
+        Returns a dict of float64 numpy arrays (for float32 fields and for models made with output='torch' too):
+        'singular_values' (n_modes,): S^2 / (T' - 1);  'explained_variance' (n_modes,): percent of the sum of all T' eigenvalues;
+        'pcs' (T', n_modes): U sqrt(T' - 1), row t the window that starts at time step t;  'eofs': {field name: array of shape
+        (embedding,) + spatial shape + (n_modes,)}, slice [j] the pattern at lag j * tau, NaN at masked points; a mode's patterns
+        have unit norm over all lags and grid points together.
+
+        Sign: the entry of largest magnitude of a mode's lag-0 pattern is positive (the first such entry on a tie), so repeated
+        calls return the same bits.  Under an initialised `torch.distributed` group every rank computes everything: nothing is
+        sharded and no collective is called.  ValueError: `embedding` or `tau` not an integer >= 1, T' < 2, `n_modes` not an
+        integer in [1, min(T' - 1, M * N)], a model of two fields, a complex model."""
+        for name, value in (('embedding', embedding), ('tau', tau)):
+            if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or value < 1:
+                raise ValueError('`{:}` must be an integer >= 1, not {!r}'.format(name, value))
+        if isinstance(n_modes, (bool, np.bool_)) or not isinstance(n_modes, (int, np.integer)):
+            raise ValueError('`n_modes` must be an integer >= 1, not {!r}'.format(n_modes))
+        if len(self._keys) != 1:
+            raise ValueError('extended_eofs takes a model of one field (extended MCA of two fields is out of scope)')
+        if self._analysis['is_complex']:
+            raise ValueError('extended_eofs does not support complex models (out of scope)')
+        M, tau, k = int(embedding), int(tau), int(n_modes)
+        key = self._keys[0]
+        T = self._n_observations[key]
+        n_kept = int(np.count_nonzero(self._no_nan_index[key]))
+        n_win = T - (M - 1) * tau
+        if n_win < 2:
+            raise ValueError('embedding = {:} with tau = {:} leaves T - (embedding - 1) * tau = {:} of {:} time steps; at least 2 '
+                             'are needed'.format(M, tau, n_win, T))
+        most = min(n_win - 1, M * n_kept)
+        if not 1 <= k <= most:
+            raise ValueError('`n_modes` must be an integer between 1 and min(T\' - 1, embedding * N) = {:}, not {!r}'.format(most, n_modes))
+        dev = self._device()
+        if not self._owns_device_fields(dev):
+            self._upload_serial += 1
+            self._upload_fields(dev)
+        n_full = self._n_variables[key]
+        masked = n_full != n_kept
+        lam, pcs, eofs = dev.extended_eofs(T, n_kept, M, tau, k, np.flatnonzero(self._no_nan_index[key]) if masked else None, n_full)
+        total = np.maximum(lam, 0.0).sum()
+        return {'singular_values': lam[:k] / (n_win - 1),
+                'explained_variance': lam[:k] / total * 100.0,
+                'pcs': pcs,
+                'eofs': {key: eofs.reshape((M,) + tuple(self._fields_spatial_shape[key]) + (k,))}}
+
     # ------------------------------------------------------------------------------------------
     # truncation / persistence (array.py:1602-1714, :1954-2012)
     # ------------------------------------------------------------------------------------------

@@ -13,6 +13,7 @@
 #include "comm.h"
 #include "theta.h"
 #include "boot_patterns.h"
+#include "lag_gram.h"
 
 using namespace xmca;
 
@@ -1432,6 +1433,87 @@ struct PatternStats {
 };
 
 // ---- bootstrapping: working copies on the device -----------------------------------------------------------------
+// xmca_extended_eofs on the resident real field of side 0: Gram matrix, lag sum and double centring (csrc/lag_gram.h),
+// the k leading eigenvectors of the T' x T' matrix, one back-projection per lag on a row-offset view of the field with 1 / sigma_c
+// in the epilogue, sign, and the (M, N_full, k) layout by the transposition and scatter kernels of xmca_get_maps.  Every buffer is
+// this call's own: the result of a solve, its vectors and the field planes are only read.
+template <typename TI>
+void extended_eofs_impl(xmca_handle* h, int M, int tau, int k, const int64_t* keep_idx, int64_t N_full, double* lam_out, double* pcs_out,
+                        double* eofs_out) {
+  const FieldData<TI>& f = typed<TI>(h).f[0];
+  const int T = (int)f.T, np = T - (M - 1) * tau;
+  const int64_t N = f.N;
+  Solver<TI> s(h->st, h->gws, h->ews, h->tm);
+  CPlanes G;
+  s.gram(f, false, G);
+  DevBuf<double> K, part, mean, Z, lam_dev, inv_dev, P, scale, tmp, out;
+  DevBuf<int64_t> row_of;
+  h->tm.begin("lag_gram");
+  lag_gram(h->st, G.r(), T, T, M, tau, true, K.ensure((size_t)np * np), part, mean);
+  h->tm.end();
+  std::vector<double> lam;
+  EvdInfo info;
+  h->tm.begin("eeof_eigh");
+  hermitian_evd(h->st, h->ews, K.get(), nullptr, np, np, lam, lam_dev.ensure((size_t)np), Z.ensure((size_t)k * np), nullptr, np, &info, false,
+                k < np ? k : -1);
+  XMCA_HIP(hipStreamSynchronize(h->st));
+  h->tm.end();
+  XMCA_CHECK(std::isfinite(lam[0]) && lam[0] > 0.0, XMCA_ERR_NUMERIC, "extended_eofs: the field has no variance (or holds NaN)");
+  // 1 / sigma_c rides in the epilogue for the modes clear of the Gram matrix's rounding noise (the cuts of the one-field solve);
+  // the others are divided by their measured norm afterwards (eeof_sign_norm_kernel)
+  const double cut = (std::is_same<TI, float>::value ? 1e-4 : 1e-6) * lam[0];
+  std::vector<double> inv((size_t)k, 1.0);
+  int known = 0;
+  while (known < k && lam[(size_t)known] > cut) { inv[(size_t)known] = 1.0 / std::sqrt(lam[(size_t)known]); ++known; }
+  XMCA_HIP(hipMemcpyAsync(inv_dev.ensure((size_t)k), inv.data(), sizeof(double) * k, hipMemcpyHostToDevice, h->st));
+  if (keep_idx) {
+    std::vector<int64_t> inverse((size_t)N_full, -1);
+    for (int64_t c = 0; c < N; ++c) inverse[(size_t)keep_idx[c]] = c;
+    XMCA_HIP(hipMemcpyAsync(row_of.ensure((size_t)N_full), inverse.data(), sizeof(int64_t) * N_full, hipMemcpyHostToDevice, h->st));
+    XMCA_HIP(hipStreamSynchronize(h->st));      // (inverse is a host temporary)
+  }
+  Narrow<TI> z;
+  z.from(h->st, Z.get(), nullptr, (int64_t)k * np);
+  const int64_t plane = (int64_t)k * N;
+  P.ensure((size_t)M * plane);
+  h->tm.begin("eeof_project");
+  for (int j = 0; j < M; ++j) {
+    GemmOpts o;
+    o.a_kfast = true; o.b_nfast = true;
+    o.row_scale = inv_dev.get();
+    gemm<TI, double>(h->st, h->gws, z.r, np, f.r() + (int64_t)j * tau * N, N, P.get() + j * plane, N, k, (int)N, np, o);
+  }
+  hipLaunchKernelGGL(eeof_sign_norm_kernel, dim3((unsigned)k), dim3(256), 0, h->st, (const double*)P.get(), plane, N, N, M, known,
+                     scale.ensure((size_t)k));
+  XMCA_HIP(hipGetLastError());
+  h->tm.end();
+  h->tm.begin("eeof_assemble");
+  const size_t slice = (size_t)N_full * k;
+  tmp.ensure((size_t)N * k);
+  out.ensure((size_t)M * slice);
+  for (int j = 0; j < M; ++j) {
+    hipLaunchKernelGGL((eof_transpose_kernel<double, double>), dim3((unsigned)ceil_div(N, (int64_t)32), (unsigned)ceil_div(k, 32)), dim3(256), 0,
+                       h->st, (const double*)(P.get() + j * plane), (const double*)nullptr, N, N, k, tmp.get());
+    hipLaunchKernelGGL((map_finish_kernel<double>), ew_grid((int64_t)slice), dim3(EW_BLOCK), 0, h->st, (const double*)tmp.get(), 0,
+                       keep_idx ? (const int64_t*)row_of.get() : (const int64_t*)nullptr, N_full, k, (const double*)scale.get(),
+                       (const double*)nullptr, (const double*)nullptr, (int)MAP_EOF, 0, out.get() + (size_t)j * slice);
+  }
+  XMCA_HIP(hipGetLastError());
+  h->tm.end();
+  std::vector<double> zh((size_t)k * np), sc((size_t)k);
+  XMCA_HIP(hipMemcpyAsync(eofs_out, out.get(), sizeof(double) * (size_t)M * slice, hipMemcpyDeviceToHost, h->st));
+  XMCA_HIP(hipMemcpyAsync(zh.data(), Z.get(), sizeof(double) * (size_t)k * np, hipMemcpyDeviceToHost, h->st));
+  XMCA_HIP(hipMemcpyAsync(sc.data(), scale.get(), sizeof(double) * k, hipMemcpyDeviceToHost, h->st));
+  XMCA_HIP(hipStreamSynchronize(h->st));
+  // PCs: U sqrt(T' - 1) with the patterns' signs (T' x k values)
+  const double root = std::sqrt((double)(np - 1));
+  for (int c = 0; c < k; ++c) {
+    const double w = sc[(size_t)c] < 0.0 ? -root : root;
+    for (int t = 0; t < np; ++t) pcs_out[(size_t)t * k + c] = zh[(size_t)c * np + t] * w;
+  }
+  std::memcpy(lam_out, lam.data(), sizeof(double) * np);
+}
+
 template <typename TI>
 void bootstrap_begin_impl(xmca_handle* h, int n_fields) {
   TypedState<TI>& ts = typed<TI>(h);
@@ -2143,6 +2225,54 @@ int xmca_pattern_stats(xmca_handle* h, const double* v0_left_re, const double* v
 }
 
 int xmca_pattern_tile(void) { return PATTERN_TILE; }
+
+int xmca_lag_gram_tile(void) { return LAG_TILE; }
+
+int xmca_lag_gram(xmca_handle* h, const double* G, int64_t n, int embedding, int tau, int center, double* K_out) {
+  API_BEGIN(h)
+  XMCA_CHECK(G && K_out && n >= 1 && embedding >= 1 && tau >= 1, XMCA_ERR_INVALID, "lag_gram: bad arguments");
+  check_operator_size("lag_gram", n);
+  const int64_t np = n - (int64_t)(embedding - 1) * tau;
+  XMCA_CHECK(np >= 1, XMCA_ERR_INVALID, "lag_gram: (embedding - 1) * tau must be below n");
+  DevBuf<double> Gd, K, part, mean;
+  XMCA_HIP(hipMemcpyAsync(Gd.ensure((size_t)n * n), G, sizeof(double) * (size_t)n * n, hipMemcpyHostToDevice, h->st));
+  h->tm.begin("lag_gram");
+  lag_gram(h->st, Gd.get(), n, (int)n, embedding, tau, center != 0, K.ensure((size_t)np * np), part, mean);
+  h->tm.end();
+  XMCA_HIP(hipMemcpyAsync(K_out, K.get(), sizeof(double) * (size_t)np * np, hipMemcpyDeviceToHost, h->st));
+  XMCA_HIP(hipStreamSynchronize(h->st));
+  API_END(h)
+}
+
+int xmca_extended_eofs(xmca_handle* h, int embedding, int tau, int n_modes, const int64_t* keep_idx, int64_t N_full, double* lam_out,
+                       double* pcs_out, double* eofs_out) {
+  API_BEGIN(h)
+  XMCA_CHECK(h->field_set[0], XMCA_ERR_STATE, "extended_eofs: no field set");
+  XMCA_CHECK(lam_out && pcs_out && eofs_out && embedding >= 1 && tau >= 1 && n_modes >= 1, XMCA_ERR_INVALID, "extended_eofs: bad arguments");
+  const int64_t T = resident_T(h), N = resident_N(h, 0);
+  bool has_im = false;
+  with_dtype(h->dtype, [&](auto t) { has_im = typed<decltype(t)>(h).f[0].has_im; });
+  XMCA_CHECK(!has_im && !h->op_pending, XMCA_ERR_INVALID, "extended_eofs: the resident field is complex (real fields only)");
+  check_operator_size("extended_eofs", T);
+  const int64_t np = T - (int64_t)(embedding - 1) * tau;
+  XMCA_CHECK(np >= 2, XMCA_ERR_INVALID, "extended_eofs: T - (embedding - 1) * tau must be at least 2");
+  XMCA_CHECK(n_modes <= np - 1 && n_modes <= (int64_t)embedding * N, XMCA_ERR_INVALID,
+             "extended_eofs: n_modes must not exceed min(T' - 1, embedding * N)");
+  XMCA_CHECK(N < ((int64_t)1 << 31) && (int64_t)embedding * n_modes * std::max(N, N_full) < ((int64_t)1 << 40), XMCA_ERR_UNSUPPORTED,
+             "extended_eofs: pattern array too large");
+  if (keep_idx) {
+    XMCA_CHECK(N_full >= N, XMCA_ERR_INVALID, "extended_eofs: N_full is below the number of kept points");
+    for (int64_t c = 0; c < N; ++c)
+      XMCA_CHECK(keep_idx[c] >= 0 && keep_idx[c] < N_full && (c == 0 || keep_idx[c] > keep_idx[c - 1]), XMCA_ERR_INVALID,
+                 "extended_eofs: keep_idx must be increasing row indices below N_full");
+  } else {
+    XMCA_CHECK(N_full == N, XMCA_ERR_INVALID, "extended_eofs: N_full must equal N without keep_idx");
+  }
+  with_dtype(h->dtype, [&](auto t) {
+    extended_eofs_impl<decltype(t)>(h, embedding, tau, n_modes, keep_idx, N_full, lam_out, pcs_out, eofs_out);
+  });
+  API_END(h)
+}
 
 int xmca_correlate(xmca_handle* h, int side, const double* Y, int64_t T, int64_t m, double* r_out) {
   API_BEGIN(h)

@@ -267,6 +267,27 @@ class xMCA(MCA):
         out['std'] = {k: self._space_array(k, v, n_modes, 'bootstrap std of eofs') for k, v in out['std'].items()}
         return out
 
+    def extended_eofs(self, embedding, tau=1, n_modes=10):
+        """`MCA.extended_eofs` with 'eofs' as DataArrays with a leading `lag` dimension (coordinate arange(embedding) * tau) in front
+        of the dims and coordinates of `eofs(n_modes)`, and 'pcs' as a DataArray over the first T' time coordinates and `mode`;
+        'singular_values' and 'explained_variance' stay numpy arrays."""
+        xr = _xr()
+        out = super().extended_eofs(embedding, tau=tau, n_modes=n_modes)
+        key = self._keys[0]
+        k = out['pcs'].shape[1]
+        lag = np.arange(int(embedding)) * int(tau)
+        eofs = {}
+        for name, values in out['eofs'].items():
+            c = self._field_coords[name]
+            eofs[name] = xr.DataArray(values, dims=['lag', 'lat', 'lon', 'mode'],
+                                      coords={'lag': lag, 'lon': c['lon'], 'lat': c['lat'], 'mode': self._modes(n_modes, k)},
+                                      name=' '.join([self._field_names[name], 'extended eofs']), attrs=self._attrs())
+        out['eofs'] = eofs
+        time = self._field_coords[key]['time'][:out['pcs'].shape[0]]
+        out['pcs'] = xr.DataArray(out['pcs'], dims=['time', 'mode'], coords={'time': time, 'mode': self._modes(n_modes, k)},
+                                  name=' '.join([self._field_names[key], 'extended pcs']), attrs=self._attrs())
+        return out
+
     # ------------------------------------------------------------------ persistence (netCDF through xarray)
     def _save_data(self, data, path, engine='h5netcdf', *args, **kwargs):
         out = os.path.join(path, secure_str('.'.join([data.name, 'nc'])))
