@@ -431,6 +431,36 @@ int xmca_extended_eofs(xmca_handle* h, int embedding, int tau, int n_modes, cons
                        double* pcs_out, double* eofs_out);
 int xmca_lag_gram(xmca_handle* h, const double* G, int64_t n, int embedding, int tau, int center, double* K_out);
 int xmca_lag_gram_tile(void);
+
+/* Reconstructed components of extended EOFs (an extension; entry points added to ABI 15 - no existing signature
+ * changes).  Notation as above; mu the row of column means of Y, Y^ = sum over the selected modes of s_k u_k v_k^T.  With
+ * J(t) = { j : 0 <= j < M, 0 <= t - j tau < T' } and c_t = |J(t)|, the reconstructed component on the T time steps of the field is
+ * R[t][n] = (1 / c_t) sum_{j in J(t)} Y^[t - j tau][j N + n], the diagonal averaging of Y^, and m[t][n] the same average of mu.
+ *   xmca_extended_reconstruct  the front of xmca_extended_eofs (the leading modes[n_sel - 1] + 1 eigenvectors), then
+ *                       R = diag(1 / c) A~ P with A~ from lag_expand_kernel and P the back-projections Z_sel X_j of the uncentred
+ *                       windows (no division by sigma, no sign), as one product per block of rows into the finish of
+ *                       xmca_reconstruct_to:  out (T x N_full, float64) = ((R + m) / inv_weight) * std + mean, NaN at the columns
+ *                       not in keep_idx.  add_means == 0 leaves m out; mean, std, inv_weight (N_keep values each) may be NULL.
+ *     modes             n_sel 0-based, strictly increasing mode indices below min(T' - 1, M N)
+ *     keep_idx, N_keep, N_full, out, out_location   as in xmca_reconstruct_to; N_keep is the number of columns of the field
+ *                       XMCA_ERR_INVALID: embedding or tau < 1, T' < 2, tau > T' with embedding > 1 (time steps in no window),
+ *                       n_sel < 1, modes unsorted or out of range, a complex resident field;  XMCA_ERR_STATE: no field.  The call
+ *                       works in buffers of its own: the result of a solve, its rotation, a back-projection tail and the field
+ *                       planes are left as they are.  Stage timers: those of xmca_extended_eofs up to "eeof_project", then
+ *                       "eeof_expand", "eeof_window_means", "eeof_reconstruct".  No sum uses an atomic: a call repeats its bits.
+ *   xmca_lag_expand     (tests) lag_expand_kernel alone: from the host q x Tp float64 matrix Z (row c one vector), A_out is
+ *                       T x embedding (q + 1) (with_indicators != 0) or T x embedding q, T = Tp + (embedding - 1) tau, row-major:
+ *                       A[t][j q + c] = Z[c][t - j tau] inside window j, else 0; A[t][embedding q + j] = 1 inside window j, else 0;
+ *                       inv_count_out[t] = 1 / c_t.  XMCA_ERR_INVALID: tau > Tp with embedding > 1.
+ *   xmca_lag_window_means  (tests) the means of the embedding windows of every column of the resident field of side 0,
+ *                       embedding x N float64: one pass over the field, rows cut at the window boundaries and summed in increasing
+ *                       order in float64 (a float32 field too). */
+int xmca_extended_reconstruct(xmca_handle* h, int embedding, int tau, const int* modes, int n_sel, int add_means,
+                              const int64_t* keep_idx, int64_t N_keep, int64_t N_full, const double* mean, const double* std,
+                              const double* inv_weight, double* out, int out_location);
+int xmca_lag_expand(xmca_handle* h, const double* Z, int q, int Tp, int embedding, int tau, int with_indicators, double* A_out,
+                    double* inv_count_out);
+int xmca_lag_window_means(xmca_handle* h, int embedding, int tau, double* means_out);
 int xmca_is_complex(xmca_handle* h);
 /* 1 when the singular vectors of `side` from the last xmca_solve are resident in float32: a real float32 field decomposed on
  * its dual side (N > T) keeps `_V` in the input's dtype as the reference does (xmca/array.py:584, the dtype of

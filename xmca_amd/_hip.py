@@ -68,6 +68,9 @@ SIGNATURES = {
     "xmca_extended_eofs": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _c_i64, _vp, _vp, _vp]),
     "xmca_lag_gram": (_c_int, [_vp, _vp, _c_i64, _c_int, _c_int, _c_int, _vp]),
     "xmca_lag_gram_tile": (_c_int, []),
+    "xmca_extended_reconstruct": (_c_int, [_vp, _c_int, _c_int, _vp, _c_int, _c_int, _vp, _c_i64, _c_i64, _vp, _vp, _vp, _vp, _c_int]),
+    "xmca_lag_expand": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp]),
+    "xmca_lag_window_means": (_c_int, [_vp, _c_int, _c_int, _vp]),
     "xmca_correlate": (_c_int, [_vp, _c_int, _vp, _c_i64, _c_i64, _vp]),
     "xmca_pearson_pvalues": (_c_int, [_vp, _vp, _c_i64, _c_i64, _vp]),
     "xmca_pvalue_log_norm": (_c_int, [_c_i64, _dp]),
@@ -1040,6 +1043,59 @@ class Handle:
         eofs = np.empty((M, N_full, k), dtype=np.float64)
         self._check(self._lib.xmca_extended_eofs(self._h, M, tau, k, _ptr(idx), N_full, _ptr(lam), _ptr(pcs), _ptr(eofs)))
         return lam, pcs, eofs
+
+    def lag_expand(self, Z, embedding, tau, with_indicators):
+        """(tests) The placement kernel of `extended_reconstruct` on a host matrix (xmca_lag_expand): (A, inv_count) from the q x T'
+        float64 `Z` - A is T x embedding (q + 1) with the indicator columns, T x embedding q without, T = T' + (embedding - 1) tau;
+        A[t, j q + c] = Z[c, t - j tau] inside window j, else 0; inv_count[t] = 1 / (number of windows that hold t)."""
+        Z = np.ascontiguousarray(Z, dtype=np.float64)
+        M, tau = int(embedding), int(tau)
+        if Z.ndim != 2 or Z.shape[0] < 1 or Z.shape[1] < 1:
+            raise ValueError("lag_expand: Z must be a q x T' matrix, got shape %s" % (Z.shape,))
+        q, n_win = Z.shape
+        if M < 1 or tau < 1 or (M > 1 and tau > n_win):
+            raise ValueError("lag_expand: embedding and tau must be >= 1, and tau <= T' when embedding > 1")
+        T = n_win + (M - 1) * tau
+        A = np.empty((T, M * (q + (1 if with_indicators else 0))), dtype=np.float64)
+        inv_count = np.empty(T, dtype=np.float64)
+        self._check(self._lib.xmca_lag_expand(self._h, _ptr(Z), q, n_win, M, tau, int(bool(with_indicators)), _ptr(A), _ptr(inv_count)))
+        return A, inv_count
+
+    def lag_window_means(self, T, N, embedding, tau):
+        """(tests) The means of the `embedding` windows X[j tau : j tau + T'] of every column of the resident real T x N field of side
+        0 (xmca_lag_window_means): embedding x N float64, summed in float64 in one pass over the field."""
+        M, tau = int(embedding), int(tau)
+        if M < 1 or tau < 1 or int(T) - (M - 1) * tau < 1:
+            raise ValueError("lag_window_means: embedding and tau must be >= 1 with (embedding - 1) * tau below T")
+        out = np.empty((M, int(N)), dtype=np.float64)
+        self._check(self._lib.xmca_lag_window_means(self._h, M, tau, _ptr(out)))
+        return out
+
+    def extended_reconstruct(self, T, N, embedding, tau, modes, add_means, keep_idx=None, N_full=None, mean=None, std=None,
+                             inv_weight=None, alloc=None):
+        """The reconstructed component of the 0-based, increasing extended modes `modes` of the resident real T x N field of side 0
+        (xmca_extended_reconstruct): T x N_full float64, the diagonal averaging of the truncated lag-embedded matrix, plus the
+        window means when `add_means`, then / inv_weight, * std, + mean (None: left out), NaN at the columns not in keep_idx
+        (None: N_full = N).  alloc: as in `reconstruct` - the result is written on the device.  The result of a solve and the fields
+        stay as they are."""
+        M, tau, T, N = int(embedding), int(tau), int(T), int(N)
+        n_win = T - (M - 1) * tau
+        sel = np.ascontiguousarray(modes, dtype=np.intc).reshape(-1)
+        if M < 1 or tau < 1 or n_win < 2 or (M > 1 and tau > n_win):
+            raise ValueError("extended_reconstruct: embedding, tau >= 1, T' >= 2 and tau <= T' (embedding > 1) are needed")
+        if sel.size < 1 or sel[0] < 0 or sel[-1] >= min(n_win - 1, M * N) or np.any(np.diff(sel) <= 0):
+            raise ValueError("extended_reconstruct: modes must be increasing 0-based indices below min(T' - 1, embedding * N)")
+        idx = None if keep_idx is None else np.ascontiguousarray(keep_idx, dtype=np.int64)
+        if idx is not None and idx.shape != (N,):
+            raise ValueError("extended_reconstruct: keep_idx must hold one index per kept point (%d), got shape %s" % (N, idx.shape))
+        N_full = N if N_full is None else int(N_full)
+        mean = None if mean is None else np.ascontiguousarray(np.broadcast_to(mean, (N,)), dtype=np.float64)
+        std = None if std is None else np.ascontiguousarray(np.broadcast_to(std, (N,)), dtype=np.float64)
+        inv_weight = None if inv_weight is None else _column_weights("extended_reconstruct", inv_weight, N)
+        out, out_ptr, where = _output(alloc, (T, N_full), np.float64)
+        self._check(self._lib.xmca_extended_reconstruct(self._h, M, tau, _ptr(sel), int(sel.size), int(bool(add_means)), _ptr(idx), N, N_full,
+                                                        _ptr(mean), _ptr(std), _ptr(inv_weight), out_ptr, where))
+        return out
 
     # ---- instrumentation ----------------------------------------------------------------------
     def reduction_info(self):

@@ -1766,6 +1766,80 @@ class MCA:
                 'pcs': pcs,
                 'eofs': {key: eofs.reshape((M,) + tuple(self._fields_spatial_shape[key]) + (k,))}}
 
+    def extended_reconstruct(self, embedding, tau=1, mode=None, original_scale=True):
+        """Reconstructed component (RC) of a group of extended EOF modes: the part of the field, on its own T time steps and its own
+        grid, that the chosen modes of `extended_eofs(embedding, tau)` carry (an extension) - the M-SSA counterpart
+        of `reconstructed_fields`.
+
+        With Y_c = U S V^H the centred embedded matrix of `extended_eofs` and Y^ its truncation to the chosen modes, time step t of
+        the RC is the average of Y^[t - j tau, lag j] over the c_t windows j that hold t (diagonal averaging).  The device forms it
+        as one product diag(1 / c) A~ P of the lag-placed eigenvectors with their back-projections on row-offset views of the
+        resident field; neither Y nor the patterns are formed, and nothing but the result leaves the device.
+
+        `mode` as in `reconstructed_fields`: None - all min(T' - 1, M N) modes; an int n - modes 1..n; a slice - 1-based with an
+        inclusive stop.  original_scale=False: the RC in the units `solve()` sees.  original_scale=True: the window means that the
+        centring of the embedded columns took out are added back (averaged the same way), then weights, `normalize()` and the
+        field's mean are undone as in `reconstructed_fields(original_scale=True)`; with all modes the result is the field.
+
+        Returns {field name: float64 array (T,) + spatial shape}, NaN at masked points; for output='torch' models a tensor written
+        on the GPU.  A prior `solve()` is not needed; a solved (and rotated) model keeps its result.  Each call is self-contained:
+        nothing is kept from an earlier `extended_eofs`.  ValueError: the argument rules of `extended_eofs`, `tau` > T' with
+        `embedding` > 1 (time steps that lie in no window), a `mode` that is neither None, int nor slice, a selection that is
+        empty or reaches past min(T' - 1, M N), a model of two fields, a complex model, `original_scale` on a subclass that
+        overrides the scaling methods without the `_device_column_weights` hook."""
+        for name, value in (('embedding', embedding), ('tau', tau)):
+            if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or value < 1:
+                raise ValueError('`{:}` must be an integer >= 1, not {!r}'.format(name, value))
+        if isinstance(mode, (bool, np.bool_)) or not (mode is None or isinstance(mode, (int, np.integer, slice))):
+            raise ValueError('Invalid `mode` {!r}. Must be None, an int or a slice.'.format(mode))
+        if len(self._keys) != 1:
+            raise ValueError('extended_reconstruct takes a model of one field (extended MCA of two fields is out of scope)')
+        if self._analysis['is_complex']:
+            raise ValueError('extended_reconstruct does not support complex models (out of scope)')
+        M, tau = int(embedding), int(tau)
+        key = self._keys[0]
+        T = self._n_observations[key]
+        n_kept = int(np.count_nonzero(self._no_nan_index[key]))
+        n_win = T - (M - 1) * tau
+        if n_win < 2:
+            raise ValueError('embedding = {:} with tau = {:} leaves T - (embedding - 1) * tau = {:} of {:} time steps; at least 2 '
+                             'are needed'.format(M, tau, n_win, T))
+        if M > 1 and tau > n_win:
+            raise ValueError('tau = {:} is above the window count T\' = {:}: some time steps lie in no window and cannot be '
+                             'reconstructed'.format(tau, n_win))
+        most = min(n_win - 1, M * n_kept)
+        if mode is None:
+            first, stop, step = 0, most, 1
+        elif isinstance(mode, slice):
+            first = 0 if mode.start is None else int(mode.start) - 1
+            stop = most if mode.stop is None else int(mode.stop)
+            step = 1 if mode.step is None else int(mode.step)
+        else:
+            first, stop, step = 0, int(mode), 1
+        modes = np.arange(first, stop, step) if step >= 1 else np.arange(0)
+        if first < 0 or modes.size < 1 or modes[-1] >= most:
+            raise ValueError('`mode` = {!r} must select at least one of the modes 1..min(T\' - 1, embedding * N) = {:}'.format(mode, most))
+        cls = type(self)
+        if (original_scale and (cls._scale_X is not MCA._scale_X or cls._scale_X_inverse is not MCA._scale_X_inverse)
+                and cls._device_column_weights is MCA._device_column_weights):
+            raise ValueError('this class scales its fields in its own `_scale_X_inverse` without a `_device_column_weights`: '
+                             'only original_scale=False is available')
+        dev = self._device()
+        if not self._owns_device_fields(dev):
+            self._upload_serial += 1
+            self._upload_fields(dev)
+        mean = std = inv_weight = None
+        if original_scale:
+            mean = self._field_means[key]
+            std = self._field_stds[key] if self._analysis['is_normalized'] else None
+            weights = self._device_column_weights(key)
+            inv_weight = None if weights is None else weights[1]
+        n_full = self._n_variables[key]
+        keep_idx = np.flatnonzero(self._no_nan_index[key]) if n_full != n_kept else None
+        X = dev.extended_reconstruct(T, n_kept, M, tau, modes, bool(original_scale), keep_idx=keep_idx, N_full=n_full, mean=mean, std=std,
+                                     inv_weight=inv_weight, alloc=self._alloc())
+        return {key: X.reshape((-1,) + tuple(self._fields_spatial_shape[key]))}
+
     # ------------------------------------------------------------------------------------------
     # truncation / persistence (array.py:1602-1714, :1954-2012)
     # ------------------------------------------------------------------------------------------

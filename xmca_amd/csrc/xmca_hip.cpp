@@ -14,6 +14,7 @@
 #include "theta.h"
 #include "boot_patterns.h"
 #include "lag_gram.h"
+#include "lag_reconstruct.h"
 
 using namespace xmca;
 
@@ -763,6 +764,48 @@ void predict_impl(xmca_handle* h, int side, const TI* X, bool x_dev, int64_t str
   *out_cplx = oc ? 1 : 0;
 }
 
+// The finish of a reconstruction, shared by xmca_reconstruct* and xmca_extended_reconstruct: the compact tb x N product C of a block
+// of rows goes to its final tb x N_full float64 layout (reconstruct_epilogue_kernel: / inv_weight, * std, + mean, NaN at the masked
+// columns), on the device where the destination is there, else through a staging block.  `begin` uploads the per-column factors and
+// sizes the row block; the caller fills C.get() (rows x N) and calls `finish` block by block.
+struct ReconstructTail {
+  DevBuf<int64_t> col_of;
+  DevBuf<double> mu, sd, iw, C, full;
+  int64_t N = 0, N_full = 0, rows = 0;
+  bool out_dev = false;
+  void begin(xmca_handle* h, int64_t T, const int64_t* keep_idx, int64_t N_, int64_t N_full_, const double* mean, const double* stdv,
+             const double* inv_weight, bool out_dev_) {
+    N = N_; N_full = N_full_; out_dev = out_dev_;
+    if (keep_idx) {
+      std::vector<int64_t> inv((size_t)N_full, -1);
+      for (int64_t c = 0; c < N; ++c) inv[(size_t)keep_idx[c]] = c;
+      XMCA_HIP(hipMemcpyAsync(col_of.ensure((size_t)N_full), inv.data(), sizeof(int64_t) * N_full, hipMemcpyHostToDevice, h->st));
+      XMCA_HIP(hipStreamSynchronize(h->st));      // (inv is a host temporary)
+    }
+    if (mean) XMCA_HIP(hipMemcpyAsync(mu.ensure((size_t)N), mean, sizeof(double) * N, hipMemcpyHostToDevice, h->st));
+    if (stdv) XMCA_HIP(hipMemcpyAsync(sd.ensure((size_t)N), stdv, sizeof(double) * N, hipMemcpyHostToDevice, h->st));
+    if (inv_weight) XMCA_HIP(hipMemcpyAsync(iw.ensure((size_t)N), inv_weight, sizeof(double) * N, hipMemcpyHostToDevice, h->st));
+    rows = transform_rows(T, (N + N_full) * (int64_t)sizeof(double));
+  }
+  void allocate() {
+    C.ensure((size_t)rows * N);
+    if (!out_dev) full.ensure((size_t)rows * N_full);
+  }
+  // rows [t0, t0 + tb) of the result from C; `timer`: the stage the epilogue is booked under
+  void finish(xmca_handle* h, const char* timer, int64_t t0, int tb, double* out) {
+    h->tm.begin(timer);
+    hipLaunchKernelGGL(reconstruct_epilogue_kernel, row_col_grid(tb, N_full), dim3(EW_BLOCK), 0, h->st, C.get(), N,
+                       col_of.get(), tb, N_full, iw.get(), sd.get(), mu.get(),      // (a buffer that was not filled is a null pointer)
+                       out_dev ? out + t0 * N_full : full.get());                   // (a device destination is final)
+    XMCA_HIP(hipGetLastError());
+    h->tm.end();
+    if (!out_dev) {
+      XMCA_HIP(hipMemcpyAsync(out + t0 * N_full, full.get(), sizeof(double) * tb * N_full, hipMemcpyDeviceToHost, h->st));
+      XMCA_HIP(hipStreamSynchronize(h->st));
+    }
+  }
+};
+
 // out (T x N_full, float64) = Re(B V[:, :m]^H) / inv_weight * std + mean, NaN at the masked columns  (see xmca_reconstruct,
 // xmca_reconstruct_weighted).  TP: element type of the vectors (product).
 template <typename TP>
@@ -772,49 +815,29 @@ void reconstruct_impl(xmca_handle* h, int side, const double* B, int64_t T, int6
   VecOperand<TP> vo;
   if (m > 0) vec_operand<TP>(h, side, V, N, m, v_cplx, vo);
   const bool both_cplx = b_cplx && vo.i != nullptr;        // Re((Br + i Bi)(Vr - i Vi)^T) = Br Vr^T + Bi Vi^T
-  DevBuf<int64_t> col_of;
-  DevBuf<double> mu, sd, iw;
-  if (keep_idx) {
-    std::vector<int64_t> inv((size_t)N_full, -1);
-    for (int64_t c = 0; c < N; ++c) inv[(size_t)keep_idx[c]] = c;
-    XMCA_HIP(hipMemcpyAsync(col_of.ensure((size_t)N_full), inv.data(), sizeof(int64_t) * N_full, hipMemcpyHostToDevice, h->st));
-    XMCA_HIP(hipStreamSynchronize(h->st));      // (inv is a host temporary)
-  }
-  if (mean) XMCA_HIP(hipMemcpyAsync(mu.ensure((size_t)N), mean, sizeof(double) * N, hipMemcpyHostToDevice, h->st));
-  if (stdv) XMCA_HIP(hipMemcpyAsync(sd.ensure((size_t)N), stdv, sizeof(double) * N, hipMemcpyHostToDevice, h->st));
-  if (inv_weight) XMCA_HIP(hipMemcpyAsync(iw.ensure((size_t)N), inv_weight, sizeof(double) * N, hipMemcpyHostToDevice, h->st));
+  ReconstructTail tail;
+  tail.begin(h, T, keep_idx, N, N_full, mean, stdv, inv_weight, out_dev);
   HostPlanes<TP> bp;             // B in the product's element type
   if (m > 0) upload_planes<TP>(h, B, (size_t)T * m, b_cplx, bp);
-  const int64_t rows = transform_rows(T, (N + N_full) * (int64_t)sizeof(double));
-  DevBuf<double> C, full;
-  C.ensure((size_t)rows * N);
-  if (!out_dev) full.ensure((size_t)rows * N_full);
+  tail.allocate();
+  const int64_t rows = tail.rows;
   for (int64_t t0 = 0; t0 < T; t0 += rows) {
     const int tb = (int)std::min<int64_t>(rows, T - t0);
     h->tm.begin("reconstruct_gemm");
     if (m == 0) {
-      XMCA_HIP(hipMemsetAsync(C.get(), 0, sizeof(double) * tb * N, h->st));
+      XMCA_HIP(hipMemsetAsync(tail.C.get(), 0, sizeof(double) * tb * N, h->st));
     } else {
       // C = B V^T (tb x N, K = m): A = the rows of B, B(j, n) = V[n, j]
       GemmOpts o;
       o.b_nfast = vo.mode_major;
-      gemm<TP, double>(h->st, h->gws, bp.r + t0 * m, m, vo.r, vo.ld, C.get(), N, tb, (int)N, (int)m, o);
+      gemm<TP, double>(h->st, h->gws, bp.r + t0 * m, m, vo.r, vo.ld, tail.C.get(), N, tb, (int)N, (int)m, o);
       if (both_cplx) {
         o.beta = 1.0;
-        gemm<TP, double>(h->st, h->gws, bp.i + t0 * m, m, vo.i, vo.ld, C.get(), N, tb, (int)N, (int)m, o);
+        gemm<TP, double>(h->st, h->gws, bp.i + t0 * m, m, vo.i, vo.ld, tail.C.get(), N, tb, (int)N, (int)m, o);
       }
     }
     h->tm.end();
-    h->tm.begin("reconstruct_epilogue");
-    hipLaunchKernelGGL(reconstruct_epilogue_kernel, row_col_grid(tb, N_full), dim3(EW_BLOCK), 0, h->st, C.get(), N,
-                       keep_idx ? col_of.get() : nullptr, tb, N_full, inv_weight ? iw.get() : nullptr, stdv ? sd.get() : nullptr,
-                       mean ? mu.get() : nullptr, out_dev ? out + t0 * N_full : full.get());     // (a device destination is final)
-    XMCA_HIP(hipGetLastError());
-    h->tm.end();
-    if (!out_dev) {
-      XMCA_HIP(hipMemcpyAsync(out + t0 * N_full, full.get(), sizeof(double) * tb * N_full, hipMemcpyDeviceToHost, h->st));
-      XMCA_HIP(hipStreamSynchronize(h->st));
-    }
+    tail.finish(h, "reconstruct_epilogue", t0, tb, out);
   }
   XMCA_HIP(hipStreamSynchronize(h->st));
 }
@@ -1433,6 +1456,33 @@ struct PatternStats {
 };
 
 // ---- bootstrapping: working copies on the device -----------------------------------------------------------------
+// The front shared by xmca_extended_eofs and xmca_extended_reconstruct: Gram product of the resident field of side 0, lag sum and
+// double centring, the k leading eigenvectors Z (k x T', row c the vector of mode c) and all eigenvalues `lam` of the T' x T' matrix.
+// The buffers live as long as the struct: the caller keeps it for the whole call.
+struct EeofFront {
+  CPlanes G;
+  DevBuf<double> K, part, mean, Z, lam_dev;
+  std::vector<double> lam;
+};
+
+template <typename TI>
+void eeof_leading_vectors(xmca_handle* h, const char* what, int M, int tau, int k, EeofFront& w) {
+  const FieldData<TI>& f = typed<TI>(h).f[0];
+  const int T = (int)f.T, np = T - (M - 1) * tau;
+  Solver<TI> s(h->st, h->gws, h->ews, h->tm);
+  s.gram(f, false, w.G);
+  h->tm.begin("lag_gram");
+  lag_gram(h->st, w.G.r(), T, T, M, tau, true, w.K.ensure((size_t)np * np), w.part, w.mean);
+  h->tm.end();
+  EvdInfo info;
+  h->tm.begin("eeof_eigh");
+  hermitian_evd(h->st, h->ews, w.K.get(), nullptr, np, np, w.lam, w.lam_dev.ensure((size_t)np), w.Z.ensure((size_t)k * np), nullptr, np, &info,
+                false, k < np ? k : -1);
+  XMCA_HIP(hipStreamSynchronize(h->st));
+  h->tm.end();
+  XMCA_CHECK(std::isfinite(w.lam[0]) && w.lam[0] > 0.0, XMCA_ERR_NUMERIC, std::string(what) + ": the field has no variance (or holds NaN)");
+}
+
 // xmca_extended_eofs on the resident real field of side 0: Gram matrix, lag sum and double centring (csrc/lag_gram.h),
 // the k leading eigenvectors of the T' x T' matrix, one back-projection per lag on a row-offset view of the field with 1 / sigma_c
 // in the epilogue, sign, and the (M, N_full, k) layout by the transposition and scatter kernels of xmca_get_maps.  Every buffer is
@@ -1443,22 +1493,12 @@ void extended_eofs_impl(xmca_handle* h, int M, int tau, int k, const int64_t* ke
   const FieldData<TI>& f = typed<TI>(h).f[0];
   const int T = (int)f.T, np = T - (M - 1) * tau;
   const int64_t N = f.N;
-  Solver<TI> s(h->st, h->gws, h->ews, h->tm);
-  CPlanes G;
-  s.gram(f, false, G);
-  DevBuf<double> K, part, mean, Z, lam_dev, inv_dev, P, scale, tmp, out;
+  EeofFront front;
+  eeof_leading_vectors<TI>(h, "extended_eofs", M, tau, k, front);
+  const std::vector<double>& lam = front.lam;
+  DevBuf<double>& Z = front.Z;
+  DevBuf<double> inv_dev, P, scale, tmp, out;
   DevBuf<int64_t> row_of;
-  h->tm.begin("lag_gram");
-  lag_gram(h->st, G.r(), T, T, M, tau, true, K.ensure((size_t)np * np), part, mean);
-  h->tm.end();
-  std::vector<double> lam;
-  EvdInfo info;
-  h->tm.begin("eeof_eigh");
-  hermitian_evd(h->st, h->ews, K.get(), nullptr, np, np, lam, lam_dev.ensure((size_t)np), Z.ensure((size_t)k * np), nullptr, np, &info, false,
-                k < np ? k : -1);
-  XMCA_HIP(hipStreamSynchronize(h->st));
-  h->tm.end();
-  XMCA_CHECK(std::isfinite(lam[0]) && lam[0] > 0.0, XMCA_ERR_NUMERIC, "extended_eofs: the field has no variance (or holds NaN)");
   // 1 / sigma_c rides in the epilogue for the modes clear of the Gram matrix's rounding noise (the cuts of the one-field solve);
   // the others are divided by their measured norm afterwards (eeof_sign_norm_kernel)
   const double cut = (std::is_same<TI, float>::value ? 1e-4 : 1e-6) * lam[0];
@@ -1512,6 +1552,75 @@ void extended_eofs_impl(xmca_handle* h, int M, int tau, int k, const int64_t* ke
     for (int t = 0; t < np; ++t) pcs_out[(size_t)t * k + c] = zh[(size_t)c * np + t] * w;
   }
   std::memcpy(lam_out, lam.data(), sizeof(double) * np);
+}
+
+// xmca_extended_reconstruct: the reconstructed component of the n_sel modes `modes` on the T time steps of the
+// resident field.  The front of extended_eofs gives the leading eigenvectors; the selected ones are gathered (Z_sel, q x T'), one
+// thin GEMM per lag on a row-offset view of the field forms P (row j q + c = Z_sel[c] X_j; the vectors sum to zero, so the
+// uncentred windows give the centred product), lag_expand_kernel forms A~ and 1 / c, the window means fill the last M rows of P
+// (add_means), and R = diag(1 / c) A~ P runs row block by row block into the finish of xmca_reconstruct.  Every buffer is this
+// call's own.
+template <typename TI>
+void extended_reconstruct_impl(xmca_handle* h, int M, int tau, const int* modes, int q, bool add_means, const int64_t* keep_idx,
+                               int64_t N_full, const double* mean, const double* stdv, const double* inv_weight, double* out, bool out_dev) {
+  const FieldData<TI>& f = typed<TI>(h).f[0];
+  const int T = (int)f.T, np = T - (M - 1) * tau;
+  const int64_t N = f.N;
+  const int k = modes[q - 1] + 1;
+  const int kin = M * (q + (add_means ? 1 : 0));
+  EeofFront front;
+  eeof_leading_vectors<TI>(h, "extended_reconstruct", M, tau, k, front);
+  DevBuf<double> Zsel, A, inv_count, P, part;
+  DevBuf<int> sel, table;
+  XMCA_HIP(hipMemcpyAsync(sel.ensure((size_t)q), modes, sizeof(int) * q, hipMemcpyHostToDevice, h->st));
+  XMCA_HIP(hipStreamSynchronize(h->st));          // (modes is the caller's)
+  h->tm.begin("eeof_expand");
+  hipLaunchKernelGGL(lag_select_rows_kernel, ew_grid((int64_t)q * np), dim3(EW_BLOCK), 0, h->st, (const double*)front.Z.get(), np,
+                     (const int*)sel.get(), q, Zsel.ensure((size_t)q * np));
+  XMCA_HIP(hipGetLastError());
+  lag_expand(h->st, Zsel.get(), q, np, M, tau, add_means, A.ensure((size_t)T * kin), inv_count.ensure((size_t)T));
+  h->tm.end();
+  P.ensure((size_t)kin * N);
+  Narrow<TI> z;
+  z.from(h->st, Zsel.get(), nullptr, (int64_t)q * np);
+  h->tm.begin("eeof_project");
+  for (int j = 0; j < M; ++j) {
+    GemmOpts o;
+    o.a_kfast = true; o.b_nfast = true;
+    gemm<TI, double>(h->st, h->gws, z.r, np, f.r() + (int64_t)j * tau * N, N, P.get() + (int64_t)j * q * N, N, q, (int)N, np, o);
+  }
+  h->tm.end();
+  if (add_means) {
+    h->tm.begin("eeof_window_means");
+    lag_window_means<TI>(h->st, f.r(), T, N, M, tau, P.get() + (int64_t)M * q * N, table, part);
+    h->tm.end();
+  }
+  ReconstructTail tail;
+  tail.begin(h, T, keep_idx, N, N_full, mean, stdv, inv_weight, out_dev);
+  tail.allocate();
+  for (int64_t t0 = 0; t0 < T; t0 += tail.rows) {
+    const int tb = (int)std::min<int64_t>(tail.rows, T - t0);
+    h->tm.begin("eeof_reconstruct");
+    GemmOpts o;          // C = diag(1 / c) A~ P (tb x N, K = kin)
+    o.row_scale = inv_count.get() + t0;
+    gemm<double, double>(h->st, h->gws, A.get() + t0 * kin, kin, P.get(), N, tail.C.get(), N, tb, (int)N, kin, o);
+    h->tm.end();
+    tail.finish(h, "eeof_reconstruct", t0, tb, out);
+  }
+  XMCA_HIP(hipStreamSynchronize(h->st));
+}
+
+// (tests) xmca_lag_window_means on the resident field of side 0
+template <typename TI>
+void lag_window_means_impl(xmca_handle* h, int M, int tau, double* means_out) {
+  const FieldData<TI>& f = typed<TI>(h).f[0];
+  DevBuf<double> means, part;
+  DevBuf<int> table;
+  h->tm.begin("eeof_window_means");
+  lag_window_means<TI>(h->st, f.r(), (int)f.T, f.N, M, tau, means.ensure((size_t)M * f.N), table, part);
+  h->tm.end();
+  XMCA_HIP(hipMemcpyAsync(means_out, means.get(), sizeof(double) * (size_t)M * f.N, hipMemcpyDeviceToHost, h->st));
+  XMCA_HIP(hipStreamSynchronize(h->st));
 }
 
 template <typename TI>
@@ -2271,6 +2380,81 @@ int xmca_extended_eofs(xmca_handle* h, int embedding, int tau, int n_modes, cons
   with_dtype(h->dtype, [&](auto t) {
     extended_eofs_impl<decltype(t)>(h, embedding, tau, n_modes, keep_idx, N_full, lam_out, pcs_out, eofs_out);
   });
+  API_END(h)
+}
+
+// the resident field of side 0 and the embedding of the lag entries: a real field, embedding and tau >= 1, T' >= min_window
+int64_t check_lag_embedding(xmca_handle* h, const char* what, int embedding, int tau, int64_t min_window) {
+  const std::string w(what);
+  XMCA_CHECK(h->field_set[0], XMCA_ERR_STATE, w + ": no field set");
+  XMCA_CHECK(embedding >= 1 && tau >= 1, XMCA_ERR_INVALID, w + ": embedding and tau must be at least 1");
+  bool has_im = false;
+  with_dtype(h->dtype, [&](auto t) { has_im = typed<decltype(t)>(h).f[0].has_im; });
+  XMCA_CHECK(!has_im && !h->op_pending, XMCA_ERR_INVALID, w + ": the resident field is complex (real fields only)");
+  const int64_t T = resident_T(h);
+  check_operator_size(what, T);
+  const int64_t np = T - (int64_t)(embedding - 1) * tau;
+  XMCA_CHECK(np >= min_window, XMCA_ERR_INVALID, w + ": T - (embedding - 1) * tau must be at least " + std::to_string(min_window));
+  return np;
+}
+
+int xmca_extended_reconstruct(xmca_handle* h, int embedding, int tau, const int* modes, int n_sel, int add_means, const int64_t* keep_idx,
+                              int64_t N_keep, int64_t N_full, const double* mean, const double* stdv, const double* inv_weight, double* out,
+                              int out_location) {
+  API_BEGIN(h)
+  const int64_t np = check_lag_embedding(h, "extended_reconstruct", embedding, tau, 2);
+  const int64_t T = resident_T(h), N = resident_N(h, 0);
+  XMCA_CHECK(embedding == 1 || tau <= np, XMCA_ERR_INVALID,
+             "extended_reconstruct: tau above T' leaves time steps outside every window (no reconstruction there)");
+  XMCA_CHECK(modes && n_sel >= 1 && out, XMCA_ERR_INVALID, "extended_reconstruct: need at least one mode and an output");
+  const int64_t most = std::min<int64_t>(np - 1, (int64_t)embedding * N);
+  for (int c = 0; c < n_sel; ++c)
+    XMCA_CHECK(modes[c] >= 0 && modes[c] < most && (c == 0 || modes[c] > modes[c - 1]), XMCA_ERR_INVALID,
+               "extended_reconstruct: modes must be increasing 0-based indices below min(T' - 1, embedding * N)");
+  XMCA_CHECK(N_keep == N, XMCA_ERR_INVALID, "extended_reconstruct: N_keep must be the field's " + std::to_string(N) + " columns");
+  XMCA_CHECK(N_full >= N && N_full <= INT32_MAX && (keep_idx || N_full == N), XMCA_ERR_INVALID,
+             "extended_reconstruct: N_full must be N_keep, or more with keep_idx");
+  if (keep_idx) {
+    for (int64_t c = 0; c < N; ++c)
+      XMCA_CHECK(keep_idx[c] >= 0 && keep_idx[c] < N_full && (c == 0 || keep_idx[c] > keep_idx[c - 1]), XMCA_ERR_INVALID,
+                 "extended_reconstruct: keep_idx must be increasing column indices below N_full");
+  }
+  const int64_t kin = (int64_t)embedding * (n_sel + 1);
+  XMCA_CHECK(kin <= INT32_MAX && kin * std::max(N, T) < ((int64_t)1 << 40), XMCA_ERR_UNSUPPORTED,
+             "extended_reconstruct: coefficient matrices too large");
+  check_out_location(h, "extended_reconstruct", out_location, out);
+  with_dtype(h->dtype, [&](auto t) {
+    extended_reconstruct_impl<decltype(t)>(h, embedding, tau, modes, n_sel, add_means != 0, keep_idx, N_full, mean, stdv, inv_weight, out,
+                                           out_location == XMCA_DEVICE);
+  });
+  API_END(h)
+}
+
+int xmca_lag_expand(xmca_handle* h, const double* Z, int q, int Tp, int embedding, int tau, int with_indicators, double* A_out,
+                    double* inv_count_out) {
+  API_BEGIN(h)
+  XMCA_CHECK(Z && A_out && inv_count_out && q >= 1 && Tp >= 1 && embedding >= 1 && tau >= 1, XMCA_ERR_INVALID, "lag_expand: bad arguments");
+  XMCA_CHECK(embedding == 1 || tau <= Tp, XMCA_ERR_INVALID, "lag_expand: tau above T' leaves time steps outside every window");
+  const int64_t T = (int64_t)Tp + (int64_t)(embedding - 1) * tau, kin = (int64_t)embedding * (q + (with_indicators ? 1 : 0));
+  check_operator_size("lag_expand", T);
+  XMCA_CHECK(kin <= INT32_MAX && kin * T < ((int64_t)1 << 34) && (int64_t)q * Tp < ((int64_t)1 << 34), XMCA_ERR_UNSUPPORTED,
+             "lag_expand: coefficient matrix too large");
+  DevBuf<double> Zd, A, inv_count;
+  XMCA_HIP(hipMemcpyAsync(Zd.ensure((size_t)q * Tp), Z, sizeof(double) * (size_t)q * Tp, hipMemcpyHostToDevice, h->st));
+  h->tm.begin("eeof_expand");
+  lag_expand(h->st, Zd.get(), q, Tp, embedding, tau, with_indicators != 0, A.ensure((size_t)(T * kin)), inv_count.ensure((size_t)T));
+  h->tm.end();
+  XMCA_HIP(hipMemcpyAsync(A_out, A.get(), sizeof(double) * (size_t)(T * kin), hipMemcpyDeviceToHost, h->st));
+  XMCA_HIP(hipMemcpyAsync(inv_count_out, inv_count.get(), sizeof(double) * (size_t)T, hipMemcpyDeviceToHost, h->st));
+  XMCA_HIP(hipStreamSynchronize(h->st));
+  API_END(h)
+}
+
+int xmca_lag_window_means(xmca_handle* h, int embedding, int tau, double* means_out) {
+  API_BEGIN(h)
+  check_lag_embedding(h, "lag_window_means", embedding, tau, 1);
+  XMCA_CHECK(means_out && resident_N(h, 0) < ((int64_t)1 << 31), XMCA_ERR_INVALID, "lag_window_means: bad arguments");
+  with_dtype(h->dtype, [&](auto t) { lag_window_means_impl<decltype(t)>(h, embedding, tau, means_out); });
   API_END(h)
 }
 

@@ -288,6 +288,14 @@ class xMCA(MCA):
                                   name=' '.join([self._field_names[key], 'extended pcs']), attrs=self._attrs())
         return out
 
+    def extended_reconstruct(self, embedding, tau=1, mode=None, original_scale=True):
+        """`MCA.extended_reconstruct` as DataArrays over the field's own dims and coordinates, like `reconstructed_fields`; with
+        `original_scale` the coslat weights are taken out on the device."""
+        xr = _xr()
+        out = super().extended_reconstruct(embedding, tau=tau, mode=mode, original_scale=original_scale)
+        return {k: xr.DataArray(v, dims=self._field_dims[k], coords=self._field_coords[k],
+                                name='extended_reconstructed_{:}_field'.format(k)) for k, v in out.items()}
+
     # ------------------------------------------------------------------ persistence (netCDF through xarray)
     def _save_data(self, data, path, engine='h5netcdf', *args, **kwargs):
         out = os.path.join(path, secure_str('.'.join([data.name, 'nc'])))
