@@ -4,7 +4,8 @@
  * The reference (nicrie/xmca v1.4.2) is pure Python: it has no FFI of its own.  The drop-in boundary is
  * therefore the private numerical core of xmca.array.MCA, and every entry point below names the reference
  * lines it replaces.  The host side (xmca_amd/array.py) binds these symbols through ctypes; INTEGRATION.md
- * shows the stub a maintainer of the reference would add.
+ * shows the stub a maintainer of the reference would add.  xmca_fill_gaps (DINEOF gap filling) stands beside
+ * the model: it takes a field with NaN gaps and needs no resident state.
  *
  * Conventions
  *   - extern "C", plain pointers and sizes only.  Return value: 0 = ok, negative = error code below;
@@ -461,6 +462,40 @@ int xmca_extended_reconstruct(xmca_handle* h, int embedding, int tau, const int*
 int xmca_lag_expand(xmca_handle* h, const double* Z, int q, int Tp, int embedding, int tau, int with_indicators, double* A_out,
                     double* inv_count_out);
 int xmca_lag_window_means(xmca_handle* h, int embedding, int tau, double* means_out);
+
+/* DINEOF gap filling of one real field (an extension; entry points added to ABI 15 - no existing signature changes).
+ * X is T x N in `dtype`, NaN marks a missing value.  Every column is centred over its present values (float64 sums in a fixed
+ * order), missing entries start at 0 and are replaced, iteration after iteration, by the truncated reconstruction of the plane A:
+ * G = A A^T, Z its n_modes leading eigenvectors (the partial eigensolver of solve(n_modes=k)), P = Z A, A[t][n] = sum_c Z[c][t]
+ * P[c][n] at the masked entries only.  d_i = sqrt(sum of the squared changes / masked entries) / scale, scale the RMS of the present
+ * anomalies; the loop ends with d_i < tol or after max_iter iterations (tol = 0: exactly max_iter).
+ *   xmca_fill_gaps      cv_idx, n_cv   flat indices into X of present entries that are withheld (treated as missing) during the
+ *                                      iteration and restored afterwards; NULL, 0: none
+ *                       out            T x N in `dtype`: X with its missing entries filled (reconstruction + column mean); present
+ *                                      and withheld entries keep the bits of X
+ *                       history_out    max_iter float64: d_1 .. d_iters (the rest is not written);  iters_out: iterations run
+ *                       cv_rms_out     RMS over the withheld entries of (filled - true) in the units of X; NaN without any
+ *                       lam_out        the n_modes leading eigenvalues of G of the last iteration
+ *                       XMCA_ERR_INVALID, before anything is launched: n_modes outside [1, min(T, N) - 1], max_iter < 1, tol
+ *                       negative or not finite, a column without a finite value, an Inf in X, a cv_idx entry out of range,
+ *                       repeated or pointing at a NaN.  XMCA_ERR_NUMERIC: the present anomalies have no variance.  The call works
+ *                       in buffers of its own: a resident field, the result of a solve, its rotation and a back-projection tail
+ *                       are left as they are.  Stage timers: "gap_center", "gram", "gap_eigh", "gap_project", "gap_fill",
+ *                       "gap_finish".  No sum uses an atomic: a call repeats its bits.
+ *   xmca_gap_center     (tests) the centring and mask kernels alone on a host field: the N column means, the T x N mask bytes
+ *                       (0 present, 1 missing), the centred plane widened to float64 (0 at the missing entries) and scale.
+ *   xmca_gap_fill_step  (tests) the fill kernel alone on host inputs: A (T x N in `dtype`), mask bytes (non-zero: fill), Z
+ *                       (n_modes x T) and P (n_modes x N) in float64; A_out is the updated plane, sum_out the sum of the squared
+ *                       changes.  Entries with a zero mask byte come back with their bits.
+ *   xmca_gap_fill_tile  (no device) rows and columns of a tile of the fill kernel: one workgroup per tile, one lane per column,
+ *                       P in registers in chunks of 16 modes, the Z values of 16 rows at a time through LDS. */
+int xmca_fill_gaps(xmca_handle* h, const void* X, int64_t T, int64_t N, int dtype, const int64_t* cv_idx, int64_t n_cv, int n_modes,
+                   int max_iter, double tol, void* out, double* history_out, int* iters_out, double* cv_rms_out, double* lam_out);
+int xmca_gap_center(xmca_handle* h, const void* X, int64_t T, int64_t N, int dtype, double* mean_out, unsigned char* mask_out,
+                    double* A_out, double* scale_out);
+int xmca_gap_fill_step(xmca_handle* h, const void* A, const unsigned char* mask, const double* Z, const double* P, int64_t T, int64_t N,
+                       int n_modes, int dtype, void* A_out, double* sum_out);
+int xmca_gap_fill_tile(int* rows_out, int* cols_out);
 int xmca_is_complex(xmca_handle* h);
 /* 1 when the singular vectors of `side` from the last xmca_solve are resident in float32: a real float32 field decomposed on
  * its dual side (N > T) keeps `_V` in the input's dtype as the reference does (xmca/array.py:584, the dtype of

@@ -71,6 +71,10 @@ SIGNATURES = {
     "xmca_extended_reconstruct": (_c_int, [_vp, _c_int, _c_int, _vp, _c_int, _c_int, _vp, _c_i64, _c_i64, _vp, _vp, _vp, _vp, _c_int]),
     "xmca_lag_expand": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp]),
     "xmca_lag_window_means": (_c_int, [_vp, _c_int, _c_int, _vp]),
+    "xmca_fill_gaps": (_c_int, [_vp, _vp, _c_i64, _c_i64, _c_int, _vp, _c_i64, _c_int, _c_int, _c_dbl, _vp, _vp, _ip, _dp, _vp]),
+    "xmca_gap_center": (_c_int, [_vp, _vp, _c_i64, _c_i64, _c_int, _vp, _vp, _vp, _dp]),
+    "xmca_gap_fill_step": (_c_int, [_vp, _vp, _vp, _vp, _vp, _c_i64, _c_i64, _c_int, _c_int, _vp, _dp]),
+    "xmca_gap_fill_tile": (_c_int, [_ip, _ip]),
     "xmca_correlate": (_c_int, [_vp, _c_int, _vp, _c_i64, _c_i64, _vp]),
     "xmca_pearson_pvalues": (_c_int, [_vp, _vp, _c_i64, _c_i64, _vp]),
     "xmca_pvalue_log_norm": (_c_int, [_c_i64, _dp]),
@@ -225,6 +229,21 @@ def pattern_tile():
 def lag_gram_tile():
     """Output tile edge of the lag-sum kernel of `extended_eofs` (xmca_lag_gram_tile; no device): a constant of the build."""
     return int(load_library().xmca_lag_gram_tile())
+
+
+def gap_fill_tile():
+    """(rows, columns) of a tile of the fill kernel of `fill_gaps` (xmca_gap_fill_tile; no device): constants of the build."""
+    rows, cols = _c_int(0), _c_int(0)
+    load_library().xmca_gap_fill_tile(ctypes.byref(rows), ctypes.byref(cols))
+    return int(rows.value), int(cols.value)
+
+
+def _gap_plane(what, X):
+    """A field with gaps as a contiguous 2-D float32 / float64 array."""
+    X = np.asarray(X)
+    if X.ndim != 2 or X.dtype not in (np.float32, np.float64):
+        raise ValueError("%s: need a T x N float32 or float64 array, got %s of shape %s" % (what, X.dtype, X.shape))
+    return np.ascontiguousarray(X)
 
 
 def _mode_major_planes(what, V, k, cplx):
@@ -1043,6 +1062,57 @@ class Handle:
         eofs = np.empty((M, N_full, k), dtype=np.float64)
         self._check(self._lib.xmca_extended_eofs(self._h, M, tau, k, _ptr(idx), N_full, _ptr(lam), _ptr(pcs), _ptr(eofs)))
         return lam, pcs, eofs
+
+    def fill_gaps(self, X, n_modes, max_iter, tol, cv_idx=None):
+        """DINEOF gap filling of the T x N float32 / float64 field `X` with NaN gaps (xmca_fill_gaps): (field, history, cv_rms, lam) -
+        X with its gaps filled, in X's dtype and with the present entries untouched; the relative changes d_i of the iterations run;
+        the RMS error at the withheld entries `cv_idx` (flat indices of present entries; None without any); the n_modes leading
+        eigenvalues of the last iterate's Gram matrix.  Resident fields and the result of a solve stay as they are."""
+        X = _gap_plane("fill_gaps", X)
+        T, N = X.shape
+        idx = None if cv_idx is None else np.ascontiguousarray(cv_idx, dtype=np.int64).ravel()
+        n_cv = 0 if idx is None else idx.size
+        k, max_iter = int(n_modes), int(max_iter)
+        if max_iter < 1:
+            raise ValueError("fill_gaps: max_iter must be at least 1")
+        out = np.empty_like(X)
+        history = np.full(max_iter, np.nan, dtype=np.float64)
+        lam = np.empty(max(k, 1), dtype=np.float64)
+        iters, cv_rms = _c_int(0), _c_dbl(np.nan)
+        self._check(self._lib.xmca_fill_gaps(self._h, _ptr(X), T, N, _np_dtype_code(X.dtype), _ptr(idx) if n_cv else None, n_cv, k, max_iter,
+                                             float(tol), _ptr(out), _ptr(history), ctypes.byref(iters), ctypes.byref(cv_rms), _ptr(lam)))
+        return out, history[:iters.value].copy(), (float(cv_rms.value) if n_cv else None), lam[:k]
+
+    def gap_center(self, X):
+        """(tests) The centring and mask kernels of `fill_gaps` on a host field (xmca_gap_center): (mean, mask, A, scale) - the N column
+        means over the present entries, the T x N mask bytes (0 present, 1 missing), the centred plane widened to float64 and the RMS
+        of the present anomalies."""
+        X = _gap_plane("gap_center", X)
+        T, N = X.shape
+        mean = np.empty(N, dtype=np.float64)
+        mask = np.empty((T, N), dtype=np.uint8)
+        A = np.empty((T, N), dtype=np.float64)
+        scale = _c_dbl(0.0)
+        self._check(self._lib.xmca_gap_center(self._h, _ptr(X), T, N, _np_dtype_code(X.dtype), _ptr(mean), _ptr(mask), _ptr(A),
+                                              ctypes.byref(scale)))
+        return mean, mask, A, float(scale.value)
+
+    def gap_fill_step(self, A, mask, Z, P):
+        """(tests) The fill kernel of `fill_gaps` on host inputs (xmca_gap_fill_step): (A_new, sum) - the T x N float32 / float64 plane
+        `A` with Z.T @ P written where `mask` (T x N bytes) is non-zero, Z n_modes x T and P n_modes x N in float64, and the sum of
+        the squared changes."""
+        A = _gap_plane("gap_fill_step", A)
+        T, N = A.shape
+        mask = np.ascontiguousarray(mask, dtype=np.uint8)
+        Z = np.ascontiguousarray(Z, dtype=np.float64)
+        P = np.ascontiguousarray(P, dtype=np.float64)
+        if mask.shape != (T, N) or Z.ndim != 2 or Z.shape[0] < 1 or Z.shape[1] != T or P.shape != (Z.shape[0], N):
+            raise ValueError("gap_fill_step: need a T x N mask, Z of k x T and P of k x N, got %s, %s, %s" % (mask.shape, Z.shape, P.shape))
+        out = np.empty_like(A)
+        total = _c_dbl(0.0)
+        self._check(self._lib.xmca_gap_fill_step(self._h, _ptr(A), _ptr(mask), _ptr(Z), _ptr(P), T, N, Z.shape[0], _np_dtype_code(A.dtype),
+                                                 _ptr(out), ctypes.byref(total)))
+        return out, float(total.value)
 
     def lag_expand(self, Z, embedding, tau, with_indicators):
         """(tests) The placement kernel of `extended_reconstruct` on a host matrix (xmca_lag_expand): (A, inv_count) from the q x T'

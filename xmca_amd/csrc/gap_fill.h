@@ -1,0 +1,259 @@
+// DINEOF gap filling: a T x N field with missing values (NaN) is centred over its present values, the gaps are
+// set to zero and then replaced, iteration after iteration, by the field's own truncated EOF reconstruction
+//   A[t][n] <- sum_{c < k} Z[c][t] P[c][n]   at the masked entries only,   Z the k leading eigenvectors of A A^T,  P = Z A,
+// until the filled values stop moving.  The Gram product, the eigenvectors and P come from the library's GEMM and eigensolver;
+// the kernels here are the masked passes around them.  Every sum is float64 in a fixed order and nothing uses an atomic, so a
+// call repeats its bits.  The mask plane holds one byte per entry: 0 present, 1 missing, 2 withheld for cross-validation.
+#pragma once
+#include "kernels.h"
+
+namespace xmca {
+
+constexpr int GAP_COLS = 256;                    // columns of a fill tile: one lane each (xmca_gap_fill_tile)
+constexpr int GAP_ROWS = 64;                     // rows of a fill tile (xmca_gap_fill_tile), walked in pieces of GAP_SUB
+constexpr int GAP_SUB = 16;                      // rows whose Z values are staged at a time
+constexpr int GAP_KC = 16;                       // modes a lane holds of its column of P at a time
+constexpr int GAP_CHUNKS = 32;                   // partial sums per column of the centring
+constexpr double GAP_POLISH_MIN_GAP = 1e-10;     // x lam[0]: pairs across the cut closer than this are left alone by the polish
+static_assert(GAP_COLS == GAP_KC * GAP_SUB, "the fill kernel stages one Z value per lane");
+static_assert(GAP_ROWS % GAP_SUB == 0, "a fill tile is a whole number of staged pieces");
+
+static inline int gap_chunks(int T) { return T < GAP_CHUNKS ? T : GAP_CHUNKS; }
+
+// Sum and count of the finite entries of column n over the rows of chunk blockIdx.y, rows ascending: psum / pcnt[chunk * N + n]
+template <typename TI>
+__global__ __launch_bounds__(256) void gap_col_partial_kernel(const TI* __restrict__ X, int T, int64_t N, int chunks,
+                                                              double* __restrict__ psum, int* __restrict__ pcnt) {
+  const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (n >= N) return;
+  const int len = (T + chunks - 1) / chunks;
+  const int r0 = (int)blockIdx.y * len, r1 = r0 + len < T ? r0 + len : T;
+  double acc = 0.0;
+  int cnt = 0;
+  for (int r = r0; r < r1; ++r) {
+    const double v = (double)X[(int64_t)r * N + n];
+    if (v == v) { acc += v; ++cnt; }
+  }
+  psum[(int64_t)blockIdx.y * N + n] = acc;
+  pcnt[(int64_t)blockIdx.y * N + n] = cnt;
+}
+
+// mean[n] = (sum of the partials of column n, chunk 0 first) / (present entries of column n); then, over the rows of chunk
+// blockIdx.y: A = x - mean and mask = 0 where x is present, A = 0 and mask = 1 where it is not, and the chunk's sum of squared
+// anomalies pss[chunk * N + n].  A column needs one present entry (checked on the host before the launch).
+template <typename TI>
+__global__ __launch_bounds__(256) void gap_center_kernel(const TI* __restrict__ X, int T, int64_t N, int chunks,
+                                                         const double* __restrict__ psum, const int* __restrict__ pcnt,
+                                                         double* __restrict__ mean, TI* __restrict__ A, unsigned char* __restrict__ mask,
+                                                         double* __restrict__ pss) {
+  const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (n >= N) return;
+  double sum = psum[n];
+  int cnt = pcnt[n];
+  for (int c = 1; c < chunks; ++c) { sum += psum[(int64_t)c * N + n]; cnt += pcnt[(int64_t)c * N + n]; }
+  const double mu = sum / (double)cnt;
+  if (blockIdx.y == 0) mean[n] = mu;
+  const int len = (T + chunks - 1) / chunks;
+  const int r0 = (int)blockIdx.y * len, r1 = r0 + len < T ? r0 + len : T;
+  double ss = 0.0;
+  for (int r = r0; r < r1; ++r) {
+    const int64_t i = (int64_t)r * N + n;
+    const double v = (double)X[i];
+    const bool present = v == v;
+    const TI a = present ? (TI)(v - mu) : (TI)0;
+    A[i] = a;
+    mask[i] = present ? 0 : 1;
+    ss = fma((double)a, (double)a, ss);
+  }
+  pss[(int64_t)blockIdx.y * N + n] = ss;
+}
+
+// stat[0] = scale, the RMS of the present anomalies; stat[1] = their number.  One workgroup, lanes strided over the chunks * N
+// partials, then the block's tree: the same association on every call.
+__global__ __launch_bounds__(256) void gap_scale_kernel(const double* __restrict__ pss, const int* __restrict__ pcnt, int64_t n_part,
+                                                        double* __restrict__ stat) {
+  __shared__ double red[4];
+  double ss = 0.0, cnt = 0.0;
+  for (int64_t i = threadIdx.x; i < n_part; i += 256) { ss += pss[i]; cnt += (double)pcnt[i]; }
+  ss = block_sum_256(ss, red);
+  cnt = block_sum_256(cnt, red);
+  if (threadIdx.x == 0) {
+    stat[0] = cnt > 0.0 ? sqrt(ss / cnt) : 0.0;
+    stat[1] = cnt;
+  }
+}
+
+// Cross-validation: the n_cv present entries idx (flat, distinct, checked on the host) are saved, zeroed and marked 2
+template <typename TI>
+__global__ void gap_withhold_kernel(TI* __restrict__ A, unsigned char* __restrict__ mask, const int64_t* __restrict__ idx, int64_t n_cv,
+                                    TI* __restrict__ saved) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_cv; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t e = idx[i];
+    saved[i] = A[e];
+    A[e] = (TI)0;
+    mask[e] = 2;
+  }
+}
+
+// The fill step.  A workgroup owns GAP_ROWS rows x GAP_COLS columns; a lane owns one column n and keeps GAP_KC values of P[:, n]
+// in registers (one chunk of modes; k <= GAP_KC: loaded once per workgroup, else once per piece of rows and chunk).  The Z values
+// of GAP_SUB rows x GAP_KC modes go through LDS, one per lane, and are read back as broadcasts.  Row by row the lane reads its
+// mask byte - loads and stores run along n - and only a masked entry reads and writes A.  The sum over the modes runs c = 0 .. k-1
+// as one fma chain in float64; modes past k are staged as zeros.  part[tile] = the tile's sum of squared changes (of the values
+// as stored, in the plane's type): lanes in row order, then the block's tree.
+// Bounds: a mask byte is read only for t < T and n < N and is taken as 0 elsewhere, and A is touched only where the mask is set.
+template <typename TI>
+__global__ __launch_bounds__(GAP_COLS) void gap_fill_kernel(TI* __restrict__ A, const unsigned char* __restrict__ mask,
+                                                            const double* __restrict__ Z, const double* __restrict__ P, int T, int64_t N,
+                                                            int k, double* __restrict__ part) {
+  __shared__ double zs[GAP_KC][GAP_SUB];
+  __shared__ double red[4];
+  const int tid = threadIdx.x;
+  const int64_t n = (int64_t)blockIdx.x * GAP_COLS + tid;
+  const bool live = n < N;
+  const int t_begin = (int)blockIdx.y * GAP_ROWS;
+  const int t_end = t_begin + GAP_ROWS < T ? t_begin + GAP_ROWS : T;
+  const int n_chunks = (k + GAP_KC - 1) / GAP_KC;
+  const int zc = tid / GAP_SUB, zr = tid % GAP_SUB;
+  double p[GAP_KC];
+  double change = 0.0;
+  for (int t0 = t_begin; t0 < t_end; t0 += GAP_SUB) {
+    unsigned char m[GAP_SUB];
+    double acc[GAP_SUB];
+#pragma unroll
+    for (int r = 0; r < GAP_SUB; ++r) {
+      m[r] = (live && t0 + r < T) ? mask[(int64_t)(t0 + r) * N + n] : (unsigned char)0;
+      acc[r] = 0.0;
+    }
+    for (int ch = 0; ch < n_chunks; ++ch) {
+      const int c0 = ch * GAP_KC;
+      if (n_chunks > 1 || t0 == t_begin) {
+#pragma unroll
+        for (int c = 0; c < GAP_KC; ++c) p[c] = (live && c0 + c < k) ? P[(int64_t)(c0 + c) * N + n] : 0.0;
+      }
+      __syncthreads();          // the readers of the previous piece are through
+      zs[zc][zr] = (c0 + zc < k && t0 + zr < T) ? Z[(int64_t)(c0 + zc) * T + t0 + zr] : 0.0;
+      __syncthreads();
+#pragma unroll
+      for (int r = 0; r < GAP_SUB; ++r) {
+        if (m[r]) {
+          double a = acc[r];
+#pragma unroll
+          for (int c = 0; c < GAP_KC; ++c) a = fma(zs[c][r], p[c], a);
+          acc[r] = a;
+        }
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < GAP_SUB; ++r) {
+      if (m[r]) {
+        const int64_t i = (int64_t)(t0 + r) * N + n;
+        const TI v = (TI)acc[r];
+        const double d = (double)v - (double)A[i];
+        change = fma(d, d, change);
+        A[i] = v;
+      }
+    }
+  }
+  change = block_sum_256(change, red);
+  if (tid == 0) part[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = change;
+}
+
+// Polish of the k leading rows of an eigenvector basis V (n x n, row j the vector of lam[j], descending).  The block Jacobi sweeps
+// leave couplings below 2e-15 lam[0] unrotated, which tilts the leading subspace by that over the gap lam[k-1] - lam[k]; the fill
+// depends on nothing but this subspace, and the iteration carries the tilt along.  With S[i][j] = v_i G v_j^T the first-order
+// correction is v_i += sum_{j >= k} S[i][j] / (lam[i] - lam[j]) v_j (rotations inside the leading subspace change nothing and are
+// left out).  The rotations of many sweeps also leave the rows orthonormal to ~1e-14 only; with O[i][j] = v_i v_j^T the step of
+// Ogita & Aishima (2018) takes that along, (S[i][j] - lam[i] O[i][j]) / (lam[i] - lam[j]) across the cut, and inside the leading
+// set the symmetric first-order orthonormalisation -O[i][j] / 2 (j != i), (1 - O[i][i]) / 2 stands in: no division by a
+// difference of two leading eigenvalues.  A pair across the cut closer than GAP_POLISH_MIN_GAP lam[0] (k above the numerical
+// rank, duplicated rows) is left alone: there the quotient is no small correction - S and O are ~1e-14 lam[0], so elsewhere a
+// coefficient stays below ~1e-4 and the step first-order - and the span is not determined to better than that anyway.
+// In place: S (k x n) becomes the coefficients C, and the caller forms V_k += C V.
+__global__ void gap_polish_coeff_kernel(double* __restrict__ S, const double* __restrict__ O, const double* __restrict__ lam, int k, int n) {
+  const int64_t total = (int64_t)k * n;
+  const double min_gap = GAP_POLISH_MIN_GAP * fabs(lam[0]);
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
+    const int i = (int)(e / n), j = (int)(e - (int64_t)i * n);
+    const double den = lam[i] - lam[j];
+    double c;
+    if (j == i) c = 0.5 * (1.0 - O[e]);
+    else if (j < k) c = -0.5 * O[e];
+    else c = fabs(den) > min_gap ? (S[e] - lam[i] * O[e]) / den : 0.0;
+    S[e] = c;
+  }
+}
+
+// hist[0] = sqrt((sum of the tiles' partials) / n_masked) / scale, sum[0] the sum itself (nullable): one workgroup, lanes
+// strided over the tiles, then the block's tree
+__global__ __launch_bounds__(256) void gap_change_kernel(const double* __restrict__ part, int64_t n_part, double n_masked,
+                                                         const double* __restrict__ stat, double* __restrict__ hist,
+                                                         double* __restrict__ sum) {
+  __shared__ double red[4];
+  double tot = 0.0;
+  for (int64_t i = threadIdx.x; i < n_part; i += 256) tot += part[i];
+  tot = block_sum_256(tot, red);
+  if (threadIdx.x == 0) {
+    if (sum) sum[0] = tot;
+    if (hist) hist[0] = n_masked > 0.0 ? sqrt(tot / n_masked) / stat[0] : 0.0;
+  }
+}
+
+// out[0] = RMS over the withheld entries of (filled - saved anomaly): one workgroup, a fixed order
+template <typename TI>
+__global__ __launch_bounds__(256) void gap_cv_rms_kernel(const TI* __restrict__ A, const int64_t* __restrict__ idx,
+                                                         const TI* __restrict__ saved, int64_t n_cv, double* __restrict__ out) {
+  __shared__ double red[4];
+  double tot = 0.0;
+  for (int64_t i = threadIdx.x; i < n_cv; i += 256) {
+    const double d = (double)A[idx[i]] - (double)saved[i];
+    tot = fma(d, d, tot);
+  }
+  tot = block_sum_256(tot, red);
+  if (threadIdx.x == 0) out[0] = sqrt(tot / (double)n_cv);
+}
+
+// The result in the raw plane: only a missing entry (mask 1) is written, filled anomaly + column mean; present and withheld
+// entries keep the bits they came with
+template <typename TI>
+__global__ void gap_finish_kernel(TI* __restrict__ raw, const TI* __restrict__ A, const unsigned char* __restrict__ mask,
+                                  const double* __restrict__ mean, int64_t N, int64_t total) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x)
+    if (mask[i] == 1) raw[i] = (TI)((double)A[i] + mean[i % N]);
+}
+
+// Scratch of the centring, the caller's (it must outlive the kernels on `st`)
+struct GapCenterScratch {
+  DevBuf<double> psum, pss;
+  DevBuf<int> pcnt;
+};
+
+// Centring and mask of the T x N plane X (NaN = missing; every column has a present entry): A, mask, mean (N), stat (2)
+template <typename TI>
+static inline void gap_center(hipStream_t st, const TI* X, int T, int64_t N, TI* A, unsigned char* mask, double* mean, double* stat,
+                              GapCenterScratch& w) {
+  const int chunks = gap_chunks(T);
+  const dim3 grid((unsigned)ceil_div(N, 256), (unsigned)chunks);
+  w.psum.ensure((size_t)chunks * N);
+  w.pcnt.ensure((size_t)chunks * N);
+  w.pss.ensure((size_t)chunks * N);
+  hipLaunchKernelGGL((gap_col_partial_kernel<TI>), grid, dim3(256), 0, st, X, T, N, chunks, w.psum.get(), w.pcnt.get());
+  hipLaunchKernelGGL((gap_center_kernel<TI>), grid, dim3(256), 0, st, X, T, N, chunks, (const double*)w.psum.get(), (const int*)w.pcnt.get(),
+                     mean, A, mask, w.pss.get());
+  hipLaunchKernelGGL(gap_scale_kernel, dim3(1), dim3(256), 0, st, (const double*)w.pss.get(), (const int*)w.pcnt.get(), (int64_t)chunks * N,
+                     stat);
+  XMCA_HIP(hipGetLastError());
+}
+
+static inline int64_t gap_fill_tiles(int T, int64_t N) { return (int64_t)ceil_div(T, GAP_ROWS) * ceil_div(N, GAP_COLS); }
+
+// One fill step on the plane A; part: gap_fill_tiles(T, N) doubles
+template <typename TI>
+static inline void gap_fill_step(hipStream_t st, TI* A, const unsigned char* mask, const double* Z, const double* P, int T, int64_t N, int k,
+                                 double* part) {
+  const dim3 grid((unsigned)ceil_div(N, GAP_COLS), (unsigned)ceil_div(T, GAP_ROWS));
+  hipLaunchKernelGGL((gap_fill_kernel<TI>), grid, dim3(GAP_COLS), 0, st, A, mask, Z, P, T, N, k, part);
+  XMCA_HIP(hipGetLastError());
+}
+
+}  // namespace xmca

@@ -370,6 +370,13 @@ inline bool trd_repeated_leading(const std::vector<double>& lam, int n, int kp) 
   return false;
 }
 
+// Which solver forms eigenvectors of a matrix of order n: the tridiagonal route (true) or the block Jacobi sweeps, which form all
+// n vectors whatever is asked for.  XMCA_TRIDIAG_VEC_MIN_N (default 768), XMCA_TRIDIAG=0 and the route's size limits decide.
+inline bool evd_vectors_by_reduction(int n, bool cplx) {
+  const int trd_vec_min_n = [] { const char* e = std::getenv("XMCA_TRIDIAG_VEC_MIN_N"); return e ? std::atoi(e) : 768; }();
+  return trd_enabled() && n >= trd_vec_min_n && trd_fits(n, cplx);
+}
+
 // n_lead: the number of leading eigenvectors wanted (Zr then needs n_lead rows only); < 0 or >= n: all of them, exactly the
 // path of a call without the argument.  On the tridiagonal route fewer vectors than n are then FORMED as well (k' >= n_lead of
 // them, info->n_eigvec: trd_partial_count, trd_eigenvectors_partial); where that route does not apply or the partial stage hands
@@ -416,8 +423,7 @@ inline void hermitian_evd(hipStream_t st, EvdWorkspace& ws, const double* Ar, co
   // with eigenvectors: the same reduction, twisted-factorisation vectors of the tridiagonal matrix, back-transformation by
   // blocked reflectors and a Newton-Schulz clean-up (tridiag_vec.h).  Spectra with clusters the clean-up cannot repair
   // (repeated eigenvalues, null spaces of dimension > 1) come back here and take the Jacobi sweeps below.
-  const int trd_vec_min_n = [] { const char* e = std::getenv("XMCA_TRIDIAG_VEC_MIN_N"); return e ? std::atoi(e) : 768; }();
-  if (Zr && !nearly_diagonal && trd_enabled() && n >= trd_vec_min_n && trd_fits(n, Ai != nullptr)) {
+  if (Zr && !nearly_diagonal && evd_vectors_by_reduction(n, Ai != nullptr)) {
     ws.trdv.count_call();
     TrdParams P = trd_reduce(st, ws.trd, Ar, Ai, n, lda, true);
     trd_wy_prepare(st, ws.trdv, ws.gws, P, Ai != nullptr);  // (from the second call on: on a second stream, under the two kernels below)

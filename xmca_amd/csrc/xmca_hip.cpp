@@ -3,6 +3,7 @@
 #include <exception>
 #include "../../include/xmca_hip.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <functional>
@@ -15,6 +16,7 @@
 #include "boot_patterns.h"
 #include "lag_gram.h"
 #include "lag_reconstruct.h"
+#include "gap_fill.h"
 
 using namespace xmca;
 
@@ -1623,6 +1625,192 @@ void lag_window_means_impl(xmca_handle* h, int M, int tau, double* means_out) {
   XMCA_HIP(hipStreamSynchronize(h->st));
 }
 
+// ---- DINEOF gap filling (csrc/gap_fill.h) ----------------------------------------------------------------------
+// The host checks of a field with gaps, before anything is launched: no Inf, a finite value in every column.  Returns the number
+// of present entries.
+template <typename TI>
+int64_t gap_check_field(const std::string& what, const TI* X, int64_t T, int64_t N) {
+  std::vector<unsigned char> seen((size_t)N, 0);
+  int64_t present = 0;
+  bool inf = false;
+  for (int64_t t = 0; t < T; ++t) {
+    const TI* row = X + t * N;
+    for (int64_t n = 0; n < N; ++n) {
+      const TI v = row[n];
+      if (v == v) { inf = inf || std::isinf(v); seen[(size_t)n] = 1; ++present; }
+    }
+  }
+  XMCA_CHECK(!inf, XMCA_ERR_INVALID, what + ": the field holds an Inf (NaN marks a missing value)");
+  for (int64_t n = 0; n < N; ++n) XMCA_CHECK(seen[(size_t)n], XMCA_ERR_INVALID, what + ": a column has no finite value (set it aside first)");
+  return present;
+}
+
+// ... and of the withheld entries: flat indices of present entries, each once
+template <typename TI>
+void gap_check_withheld(const TI* X, int64_t total, const int64_t* cv_idx, int64_t n_cv) {
+  std::vector<int64_t> sorted(cv_idx, cv_idx + n_cv);
+  std::sort(sorted.begin(), sorted.end());
+  for (int64_t i = 0; i < n_cv; ++i) {
+    const int64_t e = sorted[(size_t)i];
+    XMCA_CHECK(e >= 0 && e < total, XMCA_ERR_INVALID, "fill_gaps: a cross-validation index is out of range");
+    XMCA_CHECK(i == 0 || e != sorted[(size_t)i - 1], XMCA_ERR_INVALID, "fill_gaps: a cross-validation index is repeated");
+    XMCA_CHECK(X[e] == X[e], XMCA_ERR_INVALID, "fill_gaps: a cross-validation index points at a missing value");
+  }
+}
+
+// xmca_fill_gaps: the raw plane stays on the device and only its missing entries are written at the end, so present entries come
+// back with their bits.  One iteration is the Gram product of the working plane A, its k leading eigenvectors Z, P = Z A and the
+// fill kernel; the change d_i comes back to the host after every iteration (the eigensolver has synchronised the stream before).
+// Every buffer is this call's own.
+template <typename TI>
+void fill_gaps_impl(xmca_handle* h, const TI* X, int T, int64_t N, int64_t n_present, const int64_t* cv_idx, int64_t n_cv, int k, int max_iter,
+                    double tol, TI* out, double* history_out, int* iters_out, double* cv_rms_out, double* lam_out) {
+  const size_t total = (size_t)T * N;
+  const int64_t tiles = gap_fill_tiles(T, N);
+  DevBuf<TI> raw, A, saved;
+  DevBuf<unsigned char> mask;
+  DevBuf<double> mean, stat, part, P, Z, lam_dev, hist, cv, W, S, Zp;
+  DevBuf<int64_t> idx;
+  GapCenterScratch scratch;
+  CPlanes G;
+  Narrow<TI> z;
+  XMCA_HIP(hipMemcpyAsync(raw.ensure(total), X, sizeof(TI) * total, hipMemcpyHostToDevice, h->st));
+  h->tm.begin("gap_center");
+  gap_center<TI>(h->st, raw.get(), T, N, A.ensure(total), mask.ensure(total), mean.ensure((size_t)N), stat.ensure(2), scratch);
+  if (n_cv > 0) {
+    XMCA_HIP(hipMemcpyAsync(idx.ensure((size_t)n_cv), cv_idx, sizeof(int64_t) * n_cv, hipMemcpyHostToDevice, h->st));
+    hipLaunchKernelGGL((gap_withhold_kernel<TI>), ew_grid(n_cv), dim3(EW_BLOCK), 0, h->st, A.get(), mask.get(), (const int64_t*)idx.get(), n_cv,
+                       saved.ensure((size_t)n_cv));
+    XMCA_HIP(hipGetLastError());
+  }
+  h->tm.end();
+  double stat_host[2] = {0.0, 0.0};
+  XMCA_HIP(hipMemcpyAsync(stat_host, stat.get(), sizeof(stat_host), hipMemcpyDeviceToHost, h->st));
+  XMCA_HIP(hipStreamSynchronize(h->st));
+  XMCA_CHECK(std::isfinite(stat_host[0]) && stat_host[0] > 0.0, XMCA_ERR_NUMERIC, "fill_gaps: the present values have no variance about their column means");
+  const double n_masked = (double)((int64_t)total - n_present + n_cv);
+  FieldData<TI> f;          // the working plane as a field of the solver's Gram product
+  f.T = T;
+  f.N = N;
+  f.ext_re = A.get();
+  Solver<TI> s(h->st, h->gws, h->ews, h->tm);
+  std::vector<double> lam;
+  P.ensure((size_t)k * N);
+  // Where the eigensolver takes the block Jacobi sweeps it forms all T vectors whatever is asked for: they are all taken, and the
+  // leading k are polished against the others (csrc/gap_fill.h).  On the tridiagonal route the partial stage gives the leading k
+  // alone and nothing is polished.  Not covered: a problem that the partial stage hands back to the sweeps (bit-equal leading
+  // eigenvalues, a refused clean-up) comes back as k unpolished Jacobi vectors.
+  const bool polish = !evd_vectors_by_reduction(T, false);
+  Z.ensure((size_t)(polish ? T : k) * T);
+  if (polish) { W.ensure((size_t)k * T); S.ensure((size_t)k * T); Zp.ensure((size_t)k * T); }
+  lam_dev.ensure((size_t)T);
+  part.ensure((size_t)tiles);
+  hist.ensure((size_t)max_iter);
+  int iters = 0;
+  for (int i = 0; i < max_iter; ++i) {
+    s.gram(f, false, G);
+    EvdInfo info;
+    h->tm.begin("gap_eigh");
+    hermitian_evd(h->st, h->ews, G.r(), nullptr, T, T, lam, lam_dev.get(), Z.get(), nullptr, T, &info, false, polish ? -1 : k);
+    XMCA_HIP(hipStreamSynchronize(h->st));
+    const bool usable = std::isfinite(lam[0]) && lam[0] > 0.0;
+    const double* Zk = Z.get();
+    if (polish && usable) {         // (csrc/gap_fill.h gap_polish_coeff_kernel) S = (Z_k G) Z^T, O = Z_k Z^T, coefficients, Z_k += C Z
+      GemmOpts o;
+      gemm<double, double>(h->st, h->gws, (const double*)Z.get(), T, (const double*)G.r(), T, W.get(), T, k, T, T, o);
+      o.b_nfast = false;
+      gemm<double, double>(h->st, h->gws, (const double*)W.get(), T, (const double*)Z.get(), T, S.get(), T, k, T, T, o);
+      gemm<double, double>(h->st, h->gws, (const double*)Z.get(), T, (const double*)Z.get(), T, W.get(), T, k, T, T, o);
+      hipLaunchKernelGGL(gap_polish_coeff_kernel, ew_grid((int64_t)k * T), dim3(EW_BLOCK), 0, h->st, S.get(), (const double*)W.get(),
+                         (const double*)lam_dev.get(), k, T);
+      XMCA_HIP(hipGetLastError());
+      XMCA_HIP(hipMemcpyAsync(Zp.get(), Z.get(), sizeof(double) * (size_t)k * T, hipMemcpyDeviceToDevice, h->st));
+      o.b_nfast = true;
+      o.beta = 1.0;
+      gemm<double, double>(h->st, h->gws, (const double*)S.get(), T, (const double*)Z.get(), T, Zp.get(), T, k, T, T, o);
+      Zk = Zp.get();
+    }
+    h->tm.end();
+    XMCA_CHECK(usable, XMCA_ERR_NUMERIC, "fill_gaps: the iterate has no variance");
+    h->tm.begin("gap_project");
+    z.from(h->st, Zk, nullptr, (int64_t)k * T);
+    GemmOpts o;
+    o.a_kfast = true; o.b_nfast = true;
+    gemm<TI, double>(h->st, h->gws, z.r, T, (const TI*)A.get(), N, P.get(), N, k, (int)N, T, o);
+    h->tm.end();
+    h->tm.begin("gap_fill");
+    gap_fill_step<TI>(h->st, A.get(), mask.get(), Zk, P.get(), T, N, k, part.get());
+    hipLaunchKernelGGL(gap_change_kernel, dim3(1), dim3(256), 0, h->st, (const double*)part.get(), tiles, n_masked, (const double*)stat.get(),
+                       hist.get() + i, (double*)nullptr);
+    XMCA_HIP(hipGetLastError());
+    h->tm.end();
+    XMCA_HIP(hipMemcpyAsync(history_out + i, hist.get() + i, sizeof(double), hipMemcpyDeviceToHost, h->st));
+    XMCA_HIP(hipStreamSynchronize(h->st));
+    iters = i + 1;
+    if (history_out[i] < tol) break;
+  }
+  h->tm.begin("gap_finish");
+  if (n_cv > 0)
+    hipLaunchKernelGGL((gap_cv_rms_kernel<TI>), dim3(1), dim3(256), 0, h->st, (const TI*)A.get(), (const int64_t*)idx.get(), (const TI*)saved.get(),
+                       n_cv, cv.ensure(1));
+  hipLaunchKernelGGL((gap_finish_kernel<TI>), ew_grid((int64_t)total), dim3(EW_BLOCK), 0, h->st, raw.get(), (const TI*)A.get(),
+                     (const unsigned char*)mask.get(), (const double*)mean.get(), N, (int64_t)total);
+  XMCA_HIP(hipGetLastError());
+  h->tm.end();
+  *cv_rms_out = std::nan("");
+  if (n_cv > 0) XMCA_HIP(hipMemcpyAsync(cv_rms_out, cv.get(), sizeof(double), hipMemcpyDeviceToHost, h->st));
+  XMCA_HIP(hipMemcpyAsync(out, raw.get(), sizeof(TI) * total, hipMemcpyDeviceToHost, h->st));
+  XMCA_HIP(hipStreamSynchronize(h->st));
+  *iters_out = iters;
+  std::memcpy(lam_out, lam.data(), sizeof(double) * (size_t)k);
+}
+
+// (tests) xmca_gap_center: the centring and mask kernels alone
+template <typename TI>
+void gap_center_impl(xmca_handle* h, const TI* X, int T, int64_t N, double* mean_out, unsigned char* mask_out, double* A_out, double* scale_out) {
+  const size_t total = (size_t)T * N;
+  DevBuf<TI> raw, A;
+  DevBuf<unsigned char> mask;
+  DevBuf<double> mean, stat, wide;
+  GapCenterScratch scratch;
+  XMCA_HIP(hipMemcpyAsync(raw.ensure(total), X, sizeof(TI) * total, hipMemcpyHostToDevice, h->st));
+  h->tm.begin("gap_center");
+  gap_center<TI>(h->st, raw.get(), T, N, A.ensure(total), mask.ensure(total), mean.ensure((size_t)N), stat.ensure(2), scratch);
+  h->tm.end();
+  hipLaunchKernelGGL((convert_kernel<TI, double>), ew_grid((int64_t)total), dim3(EW_BLOCK), 0, h->st, (const TI*)A.get(), wide.ensure(total),
+                     (int64_t)total);
+  XMCA_HIP(hipGetLastError());
+  XMCA_HIP(hipMemcpyAsync(mean_out, mean.get(), sizeof(double) * (size_t)N, hipMemcpyDeviceToHost, h->st));
+  XMCA_HIP(hipMemcpyAsync(mask_out, mask.get(), total, hipMemcpyDeviceToHost, h->st));
+  XMCA_HIP(hipMemcpyAsync(A_out, wide.get(), sizeof(double) * total, hipMemcpyDeviceToHost, h->st));
+  XMCA_HIP(hipMemcpyAsync(scale_out, stat.get(), sizeof(double), hipMemcpyDeviceToHost, h->st));
+  XMCA_HIP(hipStreamSynchronize(h->st));
+}
+
+// (tests) xmca_gap_fill_step: the fill kernel and the finish of its partial sums alone
+template <typename TI>
+void gap_fill_step_impl(xmca_handle* h, const TI* A_in, const unsigned char* mask_in, const double* Z_in, const double* P_in, int T, int64_t N,
+                        int k, TI* A_out, double* sum_out) {
+  const size_t total = (size_t)T * N;
+  const int64_t tiles = gap_fill_tiles(T, N);
+  DevBuf<TI> A;
+  DevBuf<unsigned char> mask;
+  DevBuf<double> Z, P, part, sum;
+  XMCA_HIP(hipMemcpyAsync(A.ensure(total), A_in, sizeof(TI) * total, hipMemcpyHostToDevice, h->st));
+  XMCA_HIP(hipMemcpyAsync(mask.ensure(total), mask_in, total, hipMemcpyHostToDevice, h->st));
+  XMCA_HIP(hipMemcpyAsync(Z.ensure((size_t)k * T), Z_in, sizeof(double) * (size_t)k * T, hipMemcpyHostToDevice, h->st));
+  XMCA_HIP(hipMemcpyAsync(P.ensure((size_t)k * N), P_in, sizeof(double) * (size_t)k * N, hipMemcpyHostToDevice, h->st));
+  h->tm.begin("gap_fill");
+  gap_fill_step<TI>(h->st, A.get(), mask.get(), Z.get(), P.get(), T, N, k, part.ensure((size_t)tiles));
+  hipLaunchKernelGGL(gap_change_kernel, dim3(1), dim3(256), 0, h->st, (const double*)part.get(), tiles, 0.0, (const double*)nullptr,
+                     (double*)nullptr, sum.ensure(1));
+  XMCA_HIP(hipGetLastError());
+  h->tm.end();
+  XMCA_HIP(hipMemcpyAsync(A_out, A.get(), sizeof(TI) * total, hipMemcpyDeviceToHost, h->st));
+  XMCA_HIP(hipMemcpyAsync(sum_out, sum.get(), sizeof(double), hipMemcpyDeviceToHost, h->st));
+  XMCA_HIP(hipStreamSynchronize(h->st));
+}
+
 template <typename TI>
 void bootstrap_begin_impl(xmca_handle* h, int n_fields) {
   TypedState<TI>& ts = typed<TI>(h);
@@ -2379,6 +2567,68 @@ int xmca_extended_eofs(xmca_handle* h, int embedding, int tau, int n_modes, cons
   }
   with_dtype(h->dtype, [&](auto t) {
     extended_eofs_impl<decltype(t)>(h, embedding, tau, n_modes, keep_idx, N_full, lam_out, pcs_out, eofs_out);
+  });
+  API_END(h)
+}
+
+int xmca_gap_fill_tile(int* rows_out, int* cols_out) {
+  if (!rows_out || !cols_out) return XMCA_ERR_INVALID;
+  *rows_out = GAP_ROWS;
+  *cols_out = GAP_COLS;
+  return XMCA_OK;
+}
+
+// the plane of the gap entries: dtype, T x N within the eigensolver's and the kernels' index ranges
+void check_gap_plane(const char* what, int64_t T, int64_t N, int dtype) {
+  const std::string w(what);
+  XMCA_CHECK(dtype == XMCA_F32 || dtype == XMCA_F64, XMCA_ERR_INVALID, w + ": dtype must be XMCA_F32 or XMCA_F64");
+  XMCA_CHECK(T >= 1 && N >= 1, XMCA_ERR_INVALID, w + ": the field must have at least one row and one column");
+  check_operator_size(what, T);
+  XMCA_CHECK(N < ((int64_t)1 << 31) && T * N < ((int64_t)1 << 40), XMCA_ERR_UNSUPPORTED, w + ": field too large");
+}
+
+int xmca_fill_gaps(xmca_handle* h, const void* X, int64_t T, int64_t N, int dtype, const int64_t* cv_idx, int64_t n_cv, int n_modes,
+                   int max_iter, double tol, void* out, double* history_out, int* iters_out, double* cv_rms_out, double* lam_out) {
+  API_BEGIN(h)
+  XMCA_CHECK(X && out && history_out && iters_out && cv_rms_out && lam_out && n_cv >= 0 && (cv_idx || n_cv == 0), XMCA_ERR_INVALID,
+             "fill_gaps: bad arguments");
+  check_gap_plane("fill_gaps", T, N, dtype);
+  XMCA_CHECK(n_modes >= 1 && n_modes <= std::min(T, N) - 1, XMCA_ERR_INVALID, "fill_gaps: n_modes must lie in [1, min(T, N) - 1]");
+  XMCA_CHECK(max_iter >= 1, XMCA_ERR_INVALID, "fill_gaps: max_iter must be at least 1");
+  XMCA_CHECK(std::isfinite(tol) && tol >= 0.0, XMCA_ERR_INVALID, "fill_gaps: tol must be finite and not negative");
+  with_dtype(dtype, [&](auto t) {
+    using TI = decltype(t);
+    const TI* Xt = static_cast<const TI*>(X);
+    const int64_t n_present = gap_check_field<TI>("fill_gaps", Xt, T, N);
+    gap_check_withheld<TI>(Xt, T * N, cv_idx, n_cv);
+    fill_gaps_impl<TI>(h, Xt, (int)T, N, n_present, cv_idx, n_cv, n_modes, max_iter, tol, static_cast<TI*>(out), history_out, iters_out,
+                       cv_rms_out, lam_out);
+  });
+  API_END(h)
+}
+
+int xmca_gap_center(xmca_handle* h, const void* X, int64_t T, int64_t N, int dtype, double* mean_out, unsigned char* mask_out, double* A_out,
+                    double* scale_out) {
+  API_BEGIN(h)
+  XMCA_CHECK(X && mean_out && mask_out && A_out && scale_out, XMCA_ERR_INVALID, "gap_center: bad arguments");
+  check_gap_plane("gap_center", T, N, dtype);
+  with_dtype(dtype, [&](auto t) {
+    using TI = decltype(t);
+    gap_check_field<TI>("gap_center", static_cast<const TI*>(X), T, N);
+    gap_center_impl<TI>(h, static_cast<const TI*>(X), (int)T, N, mean_out, mask_out, A_out, scale_out);
+  });
+  API_END(h)
+}
+
+int xmca_gap_fill_step(xmca_handle* h, const void* A, const unsigned char* mask, const double* Z, const double* P, int64_t T, int64_t N,
+                       int n_modes, int dtype, void* A_out, double* sum_out) {
+  API_BEGIN(h)
+  XMCA_CHECK(A && mask && Z && P && A_out && sum_out && n_modes >= 1, XMCA_ERR_INVALID, "gap_fill_step: bad arguments");
+  check_gap_plane("gap_fill_step", T, N, dtype);
+  XMCA_CHECK((int64_t)n_modes * std::max(T, N) < ((int64_t)1 << 34), XMCA_ERR_UNSUPPORTED, "gap_fill_step: coefficient matrices too large");
+  with_dtype(dtype, [&](auto t) {
+    using TI = decltype(t);
+    gap_fill_step_impl<TI>(h, static_cast<const TI*>(A), mask, Z, P, (int)T, N, n_modes, static_cast<TI*>(A_out), sum_out);
   });
   API_END(h)
 }
