@@ -667,6 +667,13 @@ int xmca_cholesky(xmca_handle* h, const double* A, int n, int is_complex, double
  * n - first, leading dimension lda.  The buffer goes to the device as it is and comes back whole in R (n x lda), so the
  * caller sees what was written outside the block.  (Kernel tests only.) */
 int xmca_cholesky_ex(xmca_handle* h, const double* A, int n, int64_t lda, int first, int is_complex, double rel_shift, double* R, int* ok);
+/* The skinny product behind the leading modes of a one-field solve (csrc/kernels.h lead_rows; kernel tests only), host in /
+ * host out:  out[r*ldo + j] = scale[r] * sum_{k < K} A[r*lda + k] * B(k, j),  r < rows <= 16, j < n, with
+ * B(k, j) = B[j*ldb + k] when b_kfast (B: n rows of ldb >= K) and B[k*ldb + j] otherwise (B: K rows of ldb >= n).  scale may be
+ * NULL.  out (rows x ldo) goes to the device before the launch and comes back whole: padding returns as it went in.  *chunks
+ * (may be NULL): into how many pieces the contraction was cut over the workgroups. */
+int xmca_lead_rows(xmca_handle* h, const double* A, int64_t lda, const double* B, int64_t ldb, int b_kfast, int rows, int K, int n,
+                   const double* scale, double* out, int64_t ldo, int* chunks);
 /* The batched DFT of csrc/fft.h with every argument of fft_batch, host in / host out (kernel tests only):
  *   out[b*out_bs + k*out_es] = sa[k] sb[b] scale * sum_{t < n_in} x[b][t] exp(sign 2 pi i k t / n),  b < batch, k < n_keep,
  * x[b][t] = in[b*in_bs + t*in_es], or sin[t] * conj(in[...]) with conj_in (sin alone scales without conjugating).  in_im, sin

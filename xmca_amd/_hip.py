@@ -132,6 +132,7 @@ SIGNATURES = {
     "xmca_partial_count": (_c_int, [_vp, _c_int, _c_int, _vp]),
     "xmca_cholesky": (_c_int, [_vp, _vp, _c_int, _c_int, _c_dbl, _vp, ctypes.POINTER(_c_int)]),
     "xmca_cholesky_ex": (_c_int, [_vp, _vp, _c_int, _c_i64, _c_int, _c_int, _c_dbl, _vp, ctypes.POINTER(_c_int)]),
+    "xmca_lead_rows": (_c_int, [_vp, _vp, _c_i64, _vp, _c_i64, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _c_i64, ctypes.POINTER(_c_int)]),
     "xmca_fft_ex": (_c_int, [_vp, _vp, _vp, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _vp, _c_int, _c_int, _c_int, _vp, _vp, _c_i64,
                              _c_i64, _c_i64, _c_int, _vp, _vp, _c_dbl]),
     "xmca_bench_gram": (_c_int, [_vp, _c_int, _c_int, _dp, _dp, _dp]),
@@ -1315,6 +1316,26 @@ class Handle:
         self._check(self._lib.xmca_cholesky_ex(self._h, _ptr(Ad), n, lda, int(first), int(cplx), float(rel_shift), _ptr(R),
                                                ctypes.byref(ok)))
         return R, bool(ok.value)
+
+    def lead_rows(self, A, B, b_kfast, K, n, scale=None, out=None):
+        """out[r, j] = scale[r] * sum_k A[r, k] B(k, j) by the skinny kernel of the one-field solve (xmca_lead_rows): A is
+        (rows <= 16, lda >= K); B is (n, ldb >= K) when b_kfast - B(k, j) = B[j, k] - and (K, ldb >= n) otherwise; only the
+        leading K (or n) columns of a row are operands, the rest is padding.  `out`: the (rows, ldo >= n) buffer as it is
+        before the call (default: NaN, ldo = n).  Returns (a copy of it with the product written, the number of pieces the
+        contraction was cut into)."""
+        Ad = np.ascontiguousarray(A, dtype=np.float64)
+        Bd = np.ascontiguousarray(B, dtype=np.float64)
+        rows = Ad.shape[0]
+        if Ad.ndim != 2 or Bd.ndim != 2 or Ad.shape[1] < K or Bd.shape != ((n, Bd.shape[1]) if b_kfast else (K, Bd.shape[1])):
+            raise ValueError("lead_rows: A is (rows, lda >= K), B is (n, ldb) or (K, ldb)")
+        od = np.full((rows, n), np.nan) if out is None else np.array(out, dtype=np.float64, order="C", copy=True)
+        sd = None if scale is None else np.ascontiguousarray(scale, dtype=np.float64)
+        if od.shape[0] != rows or (sd is not None and sd.size != rows):
+            raise ValueError("lead_rows: out and scale have one row / entry per row of A")
+        chunks = _c_int(0)
+        self._check(self._lib.xmca_lead_rows(self._h, _ptr(Ad), Ad.shape[1], _ptr(Bd), Bd.shape[1], int(bool(b_kfast)), rows, int(K),
+                                             int(n), None if sd is None else _ptr(sd), _ptr(od), od.shape[1], ctypes.byref(chunks)))
+        return od, chunks.value
 
     def fft_ex(self, in_re, in_im, batch, n, out_re, out_im, sign=-1, in_bs=None, in_es=1, n_in=None, conj_in=False, sin=None,
                out_bs=None, out_es=1, n_keep=None, sa=None, sb=None, scale=1.0):

@@ -381,9 +381,10 @@ inline bool evd_vectors_by_reduction(int n, bool cplx) {
 // path of a call without the argument.  On the tridiagonal route fewer vectors than n are then FORMED as well (k' >= n_lead of
 // them, info->n_eigvec: trd_partial_count, trd_eigenvectors_partial); where that route does not apply or the partial stage hands
 // the problem back, all n are formed - from the same reduction - in scratch planes and the leading n_lead rows copied out.
+// lead_hook (all vectors wanted, real): see TrdLeadHook - trd_eigenvectors fills it in its common case, nobody else touches it.
 inline void hermitian_evd(hipStream_t st, EvdWorkspace& ws, const double* Ar, const double* Ai, int n, int64_t lda,
                           std::vector<double>& lam_host, double* lam_dev, double* Zr, double* Zi, int64_t ldz,
-                          EvdInfo* info = nullptr, bool nearly_diagonal = false, int n_lead = -1) {
+                          EvdInfo* info = nullptr, bool nearly_diagonal = false, int n_lead = -1, TrdLeadHook* lead_hook = nullptr) {
   const bool cplx = Ai != nullptr;
   const bool part = Zr && n_lead >= 0 && n_lead < n;
   if (part) XMCA_CHECK(n_lead >= 1, XMCA_ERR_INVALID, "hermitian_evd: n_lead must be at least 1 when vectors are wanted");
@@ -473,7 +474,7 @@ inline void hermitian_evd(hipStream_t st, EvdWorkspace& ws, const double* Ar, co
       ws.trdv.joined = true;
     }
     if (!repeated) all_rows();
-    if (!repeated && trd_eigenvectors(st, ws.trd, ws.trdv, ws.gws, P, Ai != nullptr, Fr, Fi, ldf)) {
+    if (!repeated && trd_eigenvectors(st, ws.trd, ws.trdv, ws.gws, P, Ai != nullptr, Fr, Fi, ldf, part ? nullptr : lead_hook)) {
       XMCA_HIP(hipStreamSynchronize(st));
       lam_host = lam_t;
       if (info) {

@@ -1126,4 +1126,136 @@ __global__ void ar1_filter_kernel(T* __restrict__ x, int64_t rows, int64_t cols,
   (void)ar1_run<T, true>(x, cols, c, r0, r1, p, a, in);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Leading rows of a product:  out (R x n, R <= 16) = A (R x K) B, float64, optionally row r times scale[r].
+// The rotation behind a one-field solve reads 10 - 12 modes; the tiled GEMM spends a whole 128 x 128 tile's dependent chain
+// (0.39 ms at K = 2920) on them whatever their number.  Here B is streamed once - a memory-bound pass - and A, 16 rows, comes
+// through the scalar cache: the k index is uniform in a wave, every lane owns one output column and 16 sums.
+//   KFAST = false:  B(k, j) = B[k * ldb + j]   (rows of the field: lanes along j read 512 contiguous bytes per k)
+//   KFAST = true :  B(k, j) = B[j * ldb + k]   (rows of the eigenvector plane: a wave turns 64 columns x 32 k through LDS)
+// The contraction is cut over the workgroups of grid.y (kchunk each, a multiple of LEAD_KSTEP) and inside a chunk over the four
+// waves; the waves' sums are added in wave order, the chunks' in chunk order (lead_rows_sum_kernel): no atomics, and the same
+// bits for the same shape from call to call.
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int LEAD_ROWS = 16;
+constexpr int LEAD_COLS = 64;                        // output columns of a workgroup, one per lane
+constexpr int LEAD_WAVES = 4;
+constexpr int LEAD_KT = 32;                          // KFAST: k per wave and step
+constexpr int LEAD_KSTEP = LEAD_WAVES * LEAD_KT;
+
+template <bool KFAST>
+__global__ __launch_bounds__(LEAD_WAVES * 64) void lead_rows_kernel(const double* __restrict__ A, int64_t lda, const double* __restrict__ B,
+                                                                    int64_t ldb, int R, int K, int n, int kchunk, double* __restrict__ out,
+                                                                    int64_t ldo, const double* __restrict__ scale, double* __restrict__ part) {
+  // KFAST: one 64 x 32 tile per wave, element (c, t) at [c * 32 + (t ^ (c & 31))] - the 32 lanes of a half-wave hit 32 different
+  // bank pairs on the write (c fixed, t = lane) and on the read (t fixed, c = lane); 64 KiB.  Both: the waves' sums, [w][r][c].
+  __shared__ double sh[KFAST ? LEAD_WAVES * LEAD_COLS * LEAD_KT : LEAD_WAVES * LEAD_ROWS * LEAD_COLS];
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int c0 = blockIdx.x * LEAD_COLS;
+  const int kb = blockIdx.y * kchunk, ke = min(K, kb + kchunk);       // (the grid has no empty chunk: kb < K)
+  double acc[LEAD_ROWS];
+  int ao[LEAD_ROWS];                                 // row r >= R repeats row R - 1 (its sums are dropped): A is never read outside R x K
+#pragma unroll
+  for (int r = 0; r < LEAD_ROWS; ++r) {
+    acc[r] = 0.0;
+    ao[r] = min(r, R - 1) * (int)lda;                // (lead_rows checks that A fits 32-bit offsets: scalar loads take one as it is)
+  }
+  if (KFAST) {
+    double* tile = sh + w * (LEAD_COLS * LEAD_KT);
+    const int kk = lane & 31, half = lane >> 5;
+    for (int ks = kb; ks < ke; ks += LEAD_KSTEP) {
+      const int k0 = ks + w * LEAD_KT;               // this wave's 32 k of the step (may lie behind ke: the tile is then not read)
+      const int kc = min(k0 + kk, ke - 1);
+      double v[LEAD_KT];
+#pragma unroll
+      for (int j = 0; j < LEAD_KT; ++j) v[j] = B[(int64_t)min(c0 + 2 * j + half, n - 1) * ldb + kc];
+#pragma unroll
+      for (int j = 0; j < LEAD_KT; ++j) {
+        const int c = 2 * j + half;
+        tile[c * LEAD_KT + (kk ^ (c & 31))] = v[j];
+      }
+      __syncthreads();
+      const int tmax = max(0, min(LEAD_KT, ke - k0));
+      for (int t = 0; t < tmax; ++t) {
+        const double y = tile[lane * LEAD_KT + (t ^ (lane & 31))];
+        const double* Ak = A + k0 + t;
+#pragma unroll
+        for (int r = 0; r < LEAD_ROWS; ++r) acc[r] = fma(Ak[ao[r]], y, acc[r]);
+      }
+      __syncthreads();
+    }
+  } else {
+    const int per = kchunk / LEAD_WAVES;
+    const int k0 = kb + w * per, k1 = min(ke, k0 + per);
+    const double* Bc = B + min(c0 + lane, n - 1);    // (lanes behind the last column repeat it; their sums are dropped)
+    int k = k0;
+    for (; k + 8 <= k1; k += 8) {
+      double y[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) y[u] = Bc[(int64_t)(k + u) * ldb];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const double* Ak = A + k + u;
+#pragma unroll
+        for (int r = 0; r < LEAD_ROWS; ++r) acc[r] = fma(Ak[ao[r]], y[u], acc[r]);
+      }
+    }
+    for (; k < k1; ++k) {
+      const double y = Bc[(int64_t)k * ldb];
+      const double* Ak = A + k;
+#pragma unroll
+      for (int r = 0; r < LEAD_ROWS; ++r) acc[r] = fma(Ak[ao[r]], y, acc[r]);
+    }
+  }
+  // (KFAST: the loop ended on a barrier, the tiles are free)
+#pragma unroll
+  for (int r = 0; r < LEAD_ROWS; ++r) sh[(w * LEAD_ROWS + r) * LEAD_COLS + lane] = acc[r];
+  __syncthreads();
+  for (int o = threadIdx.x; o < LEAD_ROWS * LEAD_COLS; o += LEAD_WAVES * 64) {
+    const int r = o / LEAD_COLS, col = c0 + o % LEAD_COLS;
+    if (r >= R || col >= n) continue;
+    double s = sh[o];
+#pragma unroll
+    for (int q = 1; q < LEAD_WAVES; ++q) s += sh[q * LEAD_ROWS * LEAD_COLS + o];
+    if (part) part[((int64_t)blockIdx.y * R + r) * n + col] = s;
+    else out[(int64_t)r * ldo + col] = scale ? s * scale[r] : s;
+  }
+}
+
+// out[r][c] = scale[r] * (part[0][r][c] + part[1][r][c] + ...), the chunks in their order
+__global__ void lead_rows_sum_kernel(const double* __restrict__ part, int chunks, int R, int n, double* __restrict__ out, int64_t ldo,
+                                     const double* __restrict__ scale) {
+  const int64_t cnt = (int64_t)R * n;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < cnt; i += (int64_t)gridDim.x * blockDim.x) {
+    double s = part[i];
+    for (int q = 1; q < chunks; ++q) s += part[(int64_t)q * cnt + i];
+    const int64_t r = i / n;
+    out[r * ldo + (i - r * n)] = scale ? s * scale[r] : s;
+  }
+}
+
+// The cut of the contraction depends on the shape alone: about three workgroups per CU of a 256-CU device where K allows it
+// (B is read once whatever the cut; the chunks' sums cost ks * R * n doubles of traffic, <3 % of B at the shapes of a solve).
+// The 768 is deliberately a constant and NOT the device's CU count: the cut fixes the order of the sums, and a result must
+// not change its bits with the device (or the partition of one) it was computed on.
+inline int lead_rows_chunk(int K, int n) {
+  const int want = std::max(1, ceil_div(768, ceil_div(n, LEAD_COLS)));
+  return ceil_div(ceil_div(K, want), LEAD_KSTEP) * LEAD_KSTEP;
+}
+// `part`: scratch for the chunks' sums, the caller's (it must stay until the stream has run the two kernels)
+inline void lead_rows(hipStream_t st, bool b_kfast, const double* A, int64_t lda, const double* B, int64_t ldb, int R, int K, int n,
+                      double* out, int64_t ldo, const double* scale, DevBuf<double>& part) {
+  XMCA_CHECK(A && B && out && R >= 1 && R <= LEAD_ROWS && K >= 1 && n >= 1 && lda >= K && ldo >= n && ldb >= (b_kfast ? K : n) &&
+                 lda * LEAD_ROWS < ((int64_t)1 << 28),
+             XMCA_ERR_INVALID, "lead_rows: bad shape");
+  const int kchunk = lead_rows_chunk(K, n), ks = ceil_div(K, kchunk);
+  double* p = ks > 1 ? part.ensure((size_t)ks * R * n) : nullptr;
+  const dim3 grid((unsigned)ceil_div(n, LEAD_COLS), (unsigned)ks);
+  if (b_kfast) hipLaunchKernelGGL(lead_rows_kernel<true>, grid, dim3(LEAD_WAVES * 64), 0, st, A, lda, B, ldb, R, K, n, kchunk, out, ldo, scale, p);
+  else hipLaunchKernelGGL(lead_rows_kernel<false>, grid, dim3(LEAD_WAVES * 64), 0, st, A, lda, B, ldb, R, K, n, kchunk, out, ldo, scale, p);
+  if (ks > 1) hipLaunchKernelGGL(lead_rows_sum_kernel, ew_grid((int64_t)R * n), dim3(EW_BLOCK), 0, st, p, ks, R, n, out, ldo, scale);
+  XMCA_HIP(hipGetLastError());
+}
+
 }  // namespace xmca

@@ -154,6 +154,16 @@ struct DeferredTail {
   int err_code = XMCA_OK;              // a failure while the tail was queued: thrown at the join
   std::string err;
   int calls = 0;
+  // The lead route (real float64, vectors by the tridiagonal route; Solver::back_project): the first `head` = LEAD_ROWS modes
+  // come from lead_rows (kernels.h) into `lead_vt` (head x N, outside the pool), and the tail's stream runs the eigensolver's
+  // last n x n product, the WHOLE back-projection and a copy of lead_vt over its first rows.  Until the join the leading modes
+  // are read here; the plane holds the same bits behind it.
+  DevBuf<double> lead_vt, lead_part;
+  hipEvent_t ev_lead = nullptr;
+  bool lead_active = false;
+  const double* lead_modes() const { return pending && lead_active ? lead_vt.get() : nullptr; }
+  // From the second xmca_solve of a handle on, with the switch on or off (the route's bits must not depend on the switch)
+  bool lead_route() const { return calls >= 2 && !in_surrogate_lanes(); }
 
   static bool enabled() {              // XMCA_DEFER_BACKPROJECT=0: the single launch
     static const bool on = [] { const char* e = std::getenv("XMCA_DEFER_BACKPROJECT"); return !(e && e[0] == '0'); }();
@@ -174,7 +184,9 @@ struct DeferredTail {
   // a stream costs ~10 ms to make, so the first solve of a handle stays serial, and it is made with every CU claimed at the
   // gate of the persistent kernels.
   void count_call() {
-    if (stream || !enabled() || in_surrogate_lanes() || ++calls < 2) return;
+    if (in_surrogate_lanes()) return;
+    if (calls < 2) ++calls;
+    if (stream || !enabled() || calls < 2) return;
     PersistGate& gate = persist_gate();
     PersistGate::Claim alone(gate, gate.n_cus);
     hipStream_t s = nullptr;
@@ -204,6 +216,7 @@ struct DeferredTail {
     XMCA_HIP(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
     XMCA_HIP(hipEventCreate(&ev_begin));
     XMCA_HIP(hipEventCreate(&ev_done));
+    XMCA_HIP(hipEventCreateWithFlags(&ev_lead, hipEventDisableTiming));
     stream = s;
   }
   bool usable() const { return stream && enabled() && !pending && !in_surrogate_lanes(); }
@@ -213,11 +226,14 @@ struct DeferredTail {
     gws.counters.release();
     gws.counters_ready = 0;
     part.release();
+    lead_vt.release();
+    lead_part.release();
   }
   // Waits for the tail, gives back what it read and returns its device time (ms); throws what went wrong with it.
   double join() {
     if (!pending) return 0.0;
     pending = false;
+    lead_active = false;
     const hipError_t e = hipStreamSynchronize(stream);
     float ms = 0.f;
     if (e == hipSuccess && err_code == XMCA_OK) (void)hipEventElapsedTime(&ms, ev_begin, ev_done);
@@ -240,6 +256,7 @@ struct DeferredTail {
     (void)hipEventDestroy(ev_fork);
     (void)hipEventDestroy(ev_begin);
     (void)hipEventDestroy(ev_done);
+    (void)hipEventDestroy(ev_lead);
     (void)hipStreamDestroy(stream);
   }
   DeferredTail() = default;
@@ -308,15 +325,17 @@ class Solver {
 
   // n_lead: eigenvectors wanted - all (< 0), none (0: eigenvalues only) or the leading n_lead; R.Z then has n_lead rows and the
   // eigensolver forms no more vectors than it must (hermitian_evd).  All eigenvalues come back in every case.
-  void reduce_field(const FieldData<TI>& f, bool cplx, Reduced& R, CPlanes& G, EvdInfo* info, int n_lead = -1) {
+  // lead_hook: the one-field route of xmca_solve (TrdLeadHook, tridiag_vec.h); everybody else passes none.
+  void reduce_field(const FieldData<TI>& f, bool cplx, Reduced& R, CPlanes& G, EvdInfo* info, int n_lead = -1,
+                    TrdLeadHook* lead_hook = nullptr) {
     R.reduced = f.N > f.T;
     R.r = (int)std::min(f.T, f.N);
     if (!R.reduced) return;
     gram(f, cplx, G);
-    reduce_gram(G, (int)f.T, cplx, R, info, n_lead);
+    reduce_gram(G, (int)f.T, cplx, R, info, n_lead, lead_hook);
   }
   // ... from the Gram matrix G (n x n Hermitian) of the field, in either frame
-  void reduce_gram(const CPlanes& G, int n, bool cplx, Reduced& R, EvdInfo* info, int n_lead = -1) {
+  void reduce_gram(const CPlanes& G, int n, bool cplx, Reduced& R, EvdInfo* info, int n_lead = -1, TrdLeadHook* lead_hook = nullptr) {
     R.reduced = true;
     R.r = n;
     tm.begin("eigh");
@@ -327,7 +346,7 @@ class Solver {
     DevBuf<double> lam_dev;
     lam_dev.ensure((size_t)n);
     hermitian_evd(st, ews, G.r(), G.i(cplx), n, n, R.lam, lam_dev.get(), want_vectors ? R.Z.r() : nullptr,
-                  want_vectors ? R.Z.i(cplx) : nullptr, n, info, false, rows < n ? rows : -1);
+                  want_vectors ? R.Z.i(cplx) : nullptr, n, info, false, rows < n ? rows : -1, lead_hook);
     hipLaunchKernelGGL(sqrt_clamp_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, lam_dev.get(), R.s.get(), n, 1.0);
     XMCA_HIP(hipStreamSynchronize(st));
     tm.end();
@@ -346,7 +365,7 @@ class Solver {
   // of Yr / Yi, which then has to outlive the caller's scope.
   void back_project(const FieldData<TI>& f, bool cplx, const double* Yr, const double* Yi, int m, CPlanes& Vt,
                     const double* row_norm = nullptr, int n_known = 0, DevBuf<float>* Vt32 = nullptr, DeferredTail* tail = nullptr,
-                    CPlanes* Ykeep = nullptr) {
+                    CPlanes* Ykeep = nullptr, TrdLeadHook* lead = nullptr) {
     const int T = (int)f.T;
     Narrow<TI> y;
     y.from(st, Yr, Yi, (int64_t)m * T);
@@ -399,6 +418,10 @@ class Solver {
     // in the epilogue (n_known >= H: the rows normalised afterwards, and their number - which selects the form of
     // normalize_rows - are then the single launch's), a tail at least as long as the head, and a field the handle owns (an
     // adopted device pointer is the caller's to overwrite as soon as solve has returned).
+    if (lead && lead->lead) {
+      back_project_lead(f, *lead, m, Vt, inv_dev, rows, *tail, Ykeep);
+      return;
+    }
     int H = m;
     if (tail && tail->usable() && !f.ext_re && !f.ext_im) {
       const int h0 = DeferredTail::head_rows();
@@ -430,6 +453,61 @@ class Solver {
       if (Ykeep) { tail->keep(Ykeep->re); tail->keep(Ykeep->im); }
     }
     XMCA_HIP(hipStreamSynchronize(st));   // `y` temporaries are released on return
+  }
+
+  // The lead route of back_project (one real float64 field whose vectors came from trd_eigenvectors with `lead`
+  // filled in, every leading row scaled in the epilogue).  Modes [0, R) by lead_rows from the eigensolver's leading rows, on
+  // `st` and finished before this returns.  On the tail's stream: the clean-up product the eigensolver handed back, the WHOLE
+  // back-projection - one launch, as the serial path - and the copy of the leading modes over its first rows.  When the
+  // eigensolver did not defer (XMCA_DEFER_BACKPROJECT=0) the same launches follow in line: the same kernels on the same
+  // operands either way, the same bits.  `rows`: the launch of back_project.
+  template <typename Rows>
+  void back_project_lead(const FieldData<TI>& f, TrdLeadHook& lead, int m, CPlanes& Vt, DevBuf<double>& inv_dev, Rows&& rows,
+                         DeferredTail& tail, CPlanes* Ykeep) {
+    if constexpr (std::is_same<TI, double>::value) {
+      const int T = (int)f.T, N = (int)f.N, R = lead.rows;
+      const size_t lead_bytes = sizeof(double) * (size_t)R * N;
+      const bool deferred = lead.pending;
+      double* Lv;
+      {
+        PoolScope outside(nullptr);        // (the tail's stream reads it)
+        Lv = tail.lead_vt.ensure((size_t)R * N);
+        if (deferred) XMCA_HIP(hipEventRecord(tail.ev_fork, st));       // behind the upload of the row scales: the tail starts at once
+        lead_rows(st, false, lead.lead, T, f.r(), f.N, R, T, N, Lv, N, inv_dev.get(), tail.lead_part);
+      }
+      static const bool trace = xmca_trace("solve");
+      if (trace)
+        std::fprintf(stderr, "[xmca solve] back-projection: modes [0, %d) by the skinny kernel; clean-up product and all %d modes %s\n", R, m,
+                     deferred ? "deferred to the second stream" : "in line");
+      if (!deferred) {
+        rows(st, gws, 0, m, nullptr);
+        XMCA_HIP(hipMemcpyAsync(Vt.r(), Lv, lead_bytes, hipMemcpyDeviceToDevice, st));
+        XMCA_HIP(hipStreamSynchronize(st));
+        return;
+      }
+      tail.head = R;
+      tail.pending = true;
+      tail.lead_active = true;
+      lead.pending = false;
+      try {
+        XMCA_HIP(hipEventRecord(tail.ev_lead, st));         // the leading modes are written
+        PoolScope outside(nullptr);        // the handle's pool is ordered by `st` alone: nothing of the tail comes from it
+        XMCA_HIP(hipStreamWaitEvent(tail.stream, tail.ev_fork, 0));
+        XMCA_HIP(hipEventRecord(tail.ev_begin, tail.stream));
+        trd_cleanup_product(tail.stream, tail.gws, lead.product);
+        rows(tail.stream, tail.gws, 0, m, &tail.part);
+        XMCA_HIP(hipStreamWaitEvent(tail.stream, tail.ev_lead, 0));
+        XMCA_HIP(hipMemcpyAsync(Vt.r(), Lv, lead_bytes, hipMemcpyDeviceToDevice, tail.stream));
+        XMCA_HIP(hipEventRecord(tail.ev_done, tail.stream));
+      } catch (const Error& e) {           // surfaces where the tail is joined
+        (void)hipGetLastError();
+        tail.err_code = e.code;
+        tail.err = e.what();
+      }
+      tail.keep(inv_dev);
+      if (Ykeep) { tail.keep(Ykeep->re); tail.keep(Ykeep->im); }
+      XMCA_HIP(hipStreamSynchronize(st));
+    }
   }
 
   // n_vec < 0: all modes
@@ -594,7 +672,15 @@ class Solver {
     }
     Reduced Ra, Rb;
     CPlanes G;
-    reduce_field(A, cplx, Ra, G, &out.evd_info[0], n_fields == 2 ? -1 : lead_count(n_vec_req));
+    // The lead route (back_project_lead): one real float64 field of the handle's own, from the second xmca_solve on.  Whether the
+    // eigensolver takes it up (vectors by the tridiagonal route, one clean-up step) shows in hook.lead afterwards.
+    TrdLeadHook hook;
+    const bool ask_lead = n_fields == 1 && std::is_same<TI, double>::value && !cplx && defer && defer->lead_route() && !A.ext_re && !A.ext_im;
+    if (ask_lead) {
+      hook.rows = LEAD_ROWS;
+      hook.defer = defer->usable();
+    }
+    reduce_field(A, cplx, Ra, G, &out.evd_info[0], n_fields == 2 ? -1 : lead_count(n_vec_req), ask_lead ? &hook : nullptr);
 
     if (n_fields == 1) {
       if (Ra.reduced) {
@@ -616,7 +702,13 @@ class Solver {
           while (known < m && Ra.lam[(size_t)known] > cut) { nrm[(size_t)known] = std::sqrt(Ra.lam[(size_t)known]); ++known; }
           const bool v32 = f32_vectors && std::is_same<TI, float>::value && !cplx;
           out.vt_f32[0] = v32;
-          back_project(A, cplx, Ra.Z.r(), Ra.Z.i(cplx), m, out.Vt[0], nrm.data(), known, v32 ? &out.Vt32[0] : nullptr, defer, &Ra.Z);
+          // The lead route needs its rows scaled in the epilogue (as the head of the deferred tail does) and something behind them
+          if (hook.lead && !(known >= hook.rows && m > hook.rows)) hook.lead = nullptr;
+          if (!hook.lead && hook.pending) {    // (not taken up: Z as without the hook)
+            trd_cleanup_product(st, gws, hook.product);
+            hook.pending = false;
+          }
+          back_project(A, cplx, Ra.Z.r(), Ra.Z.i(cplx), m, out.Vt[0], nrm.data(), known, v32 ? &out.Vt32[0] : nullptr, defer, &Ra.Z, &hook);
         }
         tm.end();
       } else {

@@ -419,6 +419,7 @@ struct TrdVecWorkspace {
   TrdVecWorkspace(const TrdVecWorkspace&) = delete;
   TrdVecWorkspace& operator=(const TrdVecWorkspace&) = delete;
   DevBuf<double> lam_asc;
+  DevBuf<double> lead, lead_part;   // leading rows of the result (TrdLeadHook), the chunk sums of their kernel
   DevBuf<unsigned long long> orth;
   double last_orth = 0.0;     // max |Z^H Z - I| before the clean-up of the last call
   int ns_steps = 0;
@@ -488,11 +489,43 @@ inline void trd_wy_prepare(hipStream_t st, TrdVecWorkspace& vw, GemmWorkspace& g
   vw.prepared = true;
 }
 
+// The last product of trd_eigenvectors, out = (3/2 I - 1/2 S)[rows reversed] Z^H: out[kk][i] = conj(u_{n-1-kk}[i]), with
+// B(k, n = i) = conj(Z[i][k]), the vectors as they lie.
+// As a descriptor handed to another stream (TrdLeadHook): C and Y are vw.Wk / vw.Y, blocks that TrdVecWorkspace took from the
+// handle's pool and KEEPS - a DevBuf gives its block back only when it grows or dies, and the next call that could grow one
+// (the next decomposition with vectors on this workspace) or destroy it (the handle) lies behind the join of the tail.  They
+// are therefore never in the pool's free list while the second stream reads them, which is what "outside the pool" buys.
+struct TrdCleanupProduct {
+  const double *Cr = nullptr, *Ci = nullptr, *Yr = nullptr, *Yi = nullptr;
+  int64_t ld = 0;
+  double *Zr = nullptr, *Zi = nullptr;
+  int64_t ldz = 0;
+  int n = 0;
+};
+inline void trd_cleanup_product(hipStream_t st, GemmWorkspace& gws, const TrdCleanupProduct& p) {
+  cgemm<double>(st, gws, p.Cr, p.Ci, p.ld, true, false, p.Yr, p.Yi, p.ld, false, true, p.Zr, p.Zi, p.ldz, p.n, p.n, p.n, 1.0, nullptr, nullptr, false);
+}
+// What the one-field solve hands to hermitian_evd so that the rotation behind it does not wait for n rows when it reads ten
+// (DESIGN.md 2.9).  In: `rows` <= LEAD_ROWS and `defer`.  Out, only when the vectors came from trd_eigenvectors with one clean-up
+// step (the common case; `lead` stays null otherwise and Z is complete as without a hook): `lead`, the leading rows of the
+// result (rows x n, dense) computed by lead_rows and queued on the stream - the rows the GEMM writes differ from them in the
+// last bits, so the caller uses THESE wherever it reads a leading row; `pending` (only with `defer`): the n x n product has not
+// been launched and is the caller's to run (`product`; its operands live in the workspace until the next decomposition, Z is
+// the caller's).  Queueing the product on the caller's second stream at once, before the host has read max |S - I|, was
+// measured and dropped.
+struct TrdLeadHook {
+  int rows = 0;
+  bool defer = false;
+  const double* lead = nullptr;
+  bool pending = false;
+  TrdCleanupProduct product;
+};
+
 // Eigenvectors of the matrix reduced by trd_reduce(..., keep_reflectors = true): Zr / Zi (n x ldz planes) get row i =
 // conj(u_i) for the eigenvalues in DESCENDING order (the layout of hermitian_evd).  Returns false when the vectors of the
 // tridiagonal are too far from orthonormal to be repaired (clusters) - the caller then uses the Jacobi solver.
 inline bool trd_eigenvectors(hipStream_t st, TrdWorkspace& ws, TrdVecWorkspace& vw, GemmWorkspace& gws, const TrdParams& P, bool cplx,
-                             double* Zr, double* Zi, int64_t ldz) {
+                             double* Zr, double* Zi, int64_t ldz, TrdLeadHook* hook = nullptr) {
   const int n = P.n;
   const int64_t ldv = P.ld;                                   // reflectors: row j = v_j, zero outside its support j+1 .. n-1
   constexpr int SBK = TRD_SBK;
@@ -546,7 +579,13 @@ inline bool trd_eigenvectors(hipStream_t st, TrdWorkspace& ws, TrdVecWorkspace& 
     // copy).  One host round trip per call instead of two; a spectrum that needs a second step (or the Jacobi sweeps) pays
     // for a product whose result is overwritten.
     hipLaunchKernelGGL(trd_ns_matrix_kernel, dim3(n), dim3(256), 0, st, Sr, Si, n, ld, 1, Wr, Wi);
-    cgemm<double>(st, gws, Wr, Wi, ld, true, false, Yr, Yi, ld, false, true, Zr, Zi, ldz, n, n, n, 1.0, nullptr, nullptr, false);
+    // With a hook (real, first round): the R leading rows of `out` by the skinny kernel, in a buffer of their own, and - when
+    // the caller defers - the n x n product not launched but handed back once the host knows that this step is the last one.
+    // Every other outcome goes on as without a hook: the next round (or the Jacobi sweeps) writes all of Z.
+    const bool lead = hook && !cplx && round == 0 && hook->rows >= 1 && hook->rows <= n;
+    const TrdCleanupProduct product{Wr, Wi, Yr, Yi, ld, Zr, Zi, ldz, n};
+    if (lead) lead_rows(st, true, Wr, ld, Yr, ld, hook->rows, n, n, vw.lead.ensure((size_t)hook->rows * n), n, nullptr, vw.lead_part);
+    if (!(lead && hook->defer)) trd_cleanup_product(st, gws, product);
     XMCA_HIP(hipGetLastError());
     unsigned long long bits = 0;
     XMCA_HIP(hipMemcpyAsync(&bits, vw.orth.get(), sizeof(bits), hipMemcpyDeviceToHost, st));
@@ -557,6 +596,11 @@ inline bool trd_eigenvectors(hipStream_t st, TrdWorkspace& ws, TrdVecWorkspace& 
     if (!(off <= 0.3)) return false;                          // clusters (or NaN): not repairable by Newton-Schulz
     if (off <= 1e-6) {                                        // the step queued above was the last one
       ++vw.ns_steps;
+      if (lead) {
+        hook->lead = vw.lead.get();
+        hook->pending = hook->defer;
+        hook->product = product;
+      }
       return true;
     }
     // Z <- Z (3/2 I - 1/2 S)

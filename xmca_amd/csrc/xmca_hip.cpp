@@ -459,7 +459,9 @@ void get_vectors_impl(xmca_handle* h, int side, void* out, int64_t m) {
     return;
   }
   DevBuf<TO> tmp;
-  pack_download<TO>(h, r.Vt[side].r(), r.Vt[side].i(cplx), N, (int)m, (int)N, tmp.ensure(n_out), out);
+  // (the caller has joined unless m <= tail.head; on the lead route those modes are in a buffer of their own until the join)
+  const double* lead = h->tail.lead_modes();
+  pack_download<TO>(h, lead ? lead : r.Vt[side].r(), r.Vt[side].i(cplx), N, (int)m, (int)N, tmp.ensure(n_out), out);
   XMCA_HIP(hipStreamSynchronize(h->st));
 }
 
@@ -1063,8 +1065,9 @@ void check_rot(const RotateResult& rr) {
 
 // Promax of the first p modes of `res` where its vectors are (array.py:815-833): the loadings V sqrt(sigma) of both fields
 // stacked (array.py:818-822; Nl left rows, Nr right rows, 0 for a one-field result) are built in `d`, then rotated.
+// `lead_left` (xmca_rotate_solved beside a deferred tail): where the leading modes of the real left field are until the join.
 void rotate_resident(xmca_handle* h, Rotator& rot, RotationDevice& d, DevBuf<double>& sigma_dev, const SolveResult& res, int64_t Nl,
-                     int64_t Nr, int p, int power, double tol, int max_iter, RotateResult& rr) {
+                     int64_t Nr, int p, int power, double tol, int max_iter, RotateResult& rr, const double* lead_left = nullptr) {
   const bool cplx = res.cplx;
   rot.alloc(d, Nl + Nr, Nl, p, cplx);
   XMCA_HIP(hipMemcpyAsync(sigma_dev.ensure((size_t)p), res.sigma.data(), sizeof(double) * p, hipMemcpyHostToDevice, h->st));
@@ -1080,9 +1083,9 @@ void rotate_resident(xmca_handle* h, Rotator& rot, RotationDevice& d, DevBuf<dou
     hipLaunchKernelGGL((rot_build_loadings_kernel<true>), ew_grid(Nl + Nr), dim3(EW_BLOCK), 0, h->st, Vl.r(), Vl.i(true), Nl, Nl,
                        Vr.r(), Vr.i(true), Nr > 0 ? Nr : Nl, Nr, sigma_dev.get(), p, d.A.r(), d.A.i(true), d.h.get());
   } else {
-    hipLaunchKernelGGL((rot_build_loadings_kernel<false>), ew_grid(Nl + Nr), dim3(EW_BLOCK), 0, h->st, Vl.r(), (const double*)nullptr,
-                       Nl, Nl, Vr.r(), (const double*)nullptr, Nr > 0 ? Nr : Nl, Nr, sigma_dev.get(), p, d.A.r(), (double*)nullptr,
-                       d.h.get());
+    hipLaunchKernelGGL((rot_build_loadings_kernel<false>), ew_grid(Nl + Nr), dim3(EW_BLOCK), 0, h->st, lead_left ? lead_left : Vl.r(),
+                       (const double*)nullptr, Nl, Nl, Vr.r(), (const double*)nullptr, Nr > 0 ? Nr : Nl, Nr, sigma_dev.get(), p, d.A.r(),
+                       (double*)nullptr, d.h.get());
   }
   rot.run(d, power, tol, max_iter, rr, nullptr, false);
 }
@@ -2807,8 +2810,13 @@ int xmca_rotate_loadings(xmca_handle* h, const double* L, int64_t N, int64_t n_l
 
 int xmca_rotate_solved(xmca_handle* h, int p, int power, double tol, int max_iter, double* R_out, double* Phi_out,
                        double* norm_left, double* norm_right, int* iters_out) {
-  API_BEGIN(h)
+  API_BEGIN_NO_JOIN(h)
+  if (!h->solved) join_tail(h);       // (no tail is pending without a result; an entry point joins unless it says why not)
   XMCA_CHECK(h->solved, XMCA_ERR_STATE, "rotate: no solve result on this handle");
+  // The rule of xmca_rotate_loadings: on the fourth-moment route (real, few modes) the loop is one workgroup and runs beside the
+  // tail, provided the loadings come from modes that were complete when solve returned - the first tail.head rows of the
+  // plane (float64 or float32) on the head / tail route, tail.lead_modes() on the lead route; every other case joins.
+  if (!(Rotator::single_workgroup_loop(p, h->res.cplx) && p <= h->tail.head)) join_tail(h);
   XMCA_CHECK(p >= 2, XMCA_ERR_INVALID, "rotate: `n_rot` must be > 1");
   XMCA_CHECK(power >= 1 && max_iter >= 1, XMCA_ERR_INVALID, "rotate: `power` must be >= 1");
   const SolveResult& r = h->res;
@@ -2817,7 +2825,7 @@ int xmca_rotate_solved(xmca_handle* h, int p, int power, double tol, int max_ite
   Rotator rot(h->st, h->tm, h->gws, h->ews);
   DevBuf<double> sigma_dev;
   RotateResult rr;
-  rotate_resident(h, rot, h->rot, sigma_dev, r, r.ldv[0], r.ldv[1] > 0 ? r.ldv[1] : 0, p, power, tol, max_iter, rr);
+  rotate_resident(h, rot, h->rot, sigma_dev, r, r.ldv[0], r.ldv[1] > 0 ? r.ldv[1] : 0, p, power, tol, max_iter, rr, h->tail.lead_modes());
   h->tm.collect();
   if (iters_out) *iters_out = rr.iters;
   check_rot(rr);
@@ -3293,6 +3301,24 @@ int xmca_cholesky_ex(xmca_handle* h, const double* A, int n, int64_t lda, int fi
   XMCA_HIP(hipGetLastError());
   XMCA_HIP(hipMemcpyAsync(R, rout.get(), sizeof(double) * no, hipMemcpyDeviceToHost, h->st));
   XMCA_HIP(hipStreamSynchronize(h->st));
+  API_END(h)
+}
+
+int xmca_lead_rows(xmca_handle* h, const double* A, int64_t lda, const double* B, int64_t ldb, int b_kfast, int rows, int K, int n,
+                   const double* scale, double* out, int64_t ldo, int* chunks) {
+  API_BEGIN(h)
+  XMCA_CHECK(A && B && out && rows >= 1 && rows <= LEAD_ROWS && K >= 1 && n >= 1 && lda >= K && ldo >= n && ldb >= (b_kfast ? K : n),
+             XMCA_ERR_INVALID, "lead_rows: bad arguments");
+  const size_t na = (size_t)rows * (size_t)lda, nb = (size_t)(b_kfast ? n : K) * (size_t)ldb, no = (size_t)rows * (size_t)ldo;
+  DevBuf<double> Ad, Bd, Sd, Od, part;
+  XMCA_HIP(hipMemcpyAsync(Ad.ensure(na), A, sizeof(double) * na, hipMemcpyHostToDevice, h->st));
+  XMCA_HIP(hipMemcpyAsync(Bd.ensure(nb), B, sizeof(double) * nb, hipMemcpyHostToDevice, h->st));
+  XMCA_HIP(hipMemcpyAsync(Od.ensure(no), out, sizeof(double) * no, hipMemcpyHostToDevice, h->st));
+  if (scale) XMCA_HIP(hipMemcpyAsync(Sd.ensure((size_t)rows), scale, sizeof(double) * rows, hipMemcpyHostToDevice, h->st));
+  lead_rows(h->st, b_kfast != 0, Ad.get(), lda, Bd.get(), ldb, rows, K, n, Od.get(), ldo, scale ? Sd.get() : nullptr, part);
+  XMCA_HIP(hipMemcpyAsync(out, Od.get(), sizeof(double) * no, hipMemcpyDeviceToHost, h->st));
+  XMCA_HIP(hipStreamSynchronize(h->st));
+  if (chunks) *chunks = ceil_div(K, lead_rows_chunk(K, n));
   API_END(h)
 }
 
