@@ -354,6 +354,14 @@ def _column_weights(what, w, N):
     return np.ascontiguousarray(w, dtype=np.float64)
 
 
+def _kept_index(what, keep_idx, N=None):
+    """The kept columns as contiguous int64 indices (None: all are kept); `N`: how many there must be, where the caller knows."""
+    idx = None if keep_idx is None else np.ascontiguousarray(keep_idx, dtype=np.int64)
+    if idx is not None and N is not None and idx.shape != (int(N),):
+        raise ValueError("%s: keep_idx must hold one index per kept point (%d), got shape %s" % (what, N, idx.shape))
+    return idx
+
+
 def _output(alloc, shape, dtype):
     """(array, pointer argument, XMCA_HOST / XMCA_DEVICE) of a result: a new host array, or what `alloc(shape, dtype)` made on the
     handle's GPU - `(array, device address)`."""
@@ -686,9 +694,7 @@ class Handle:
         f, f_cplx = _host_vectors(col_factor)
         if f is not None and f.shape != (q,):
             raise ValueError("maps: col_factor must hold one value per column (%d), got shape %s" % (q, f.shape))
-        idx = None if keep_idx is None else np.ascontiguousarray(keep_idx, dtype=np.int64)
-        if idx is not None and idx.shape != (N,):
-            raise ValueError("maps: keep_idx must hold one row index per kept point (%d), got shape %s" % (N, idx.shape))
+        idx = _kept_index("maps", keep_idx, N)
         o_cplx = kind == MAP_EOF and (cplx or w_cplx or f_cplx)
         out, out_ptr, where = _output(alloc, (int(N_full), q), _cplx_np(code) if o_cplx else _real_np(code))
         stats = np.full(q, np.nan) if want_stats else None
@@ -723,7 +729,7 @@ class Handle:
             x_ptr, x_strides, x_dtype, where = _ptr(X), (X.shape[1], 1), X.dtype, HOST
         code = _np_dtype_code(x_dtype)
         T, N_full = X.shape
-        idx = None if keep_idx is None else np.ascontiguousarray(keep_idx, dtype=np.int64)
+        idx = _kept_index("predict", keep_idx)
         N = N_full if idx is None else idx.size
         mean = np.ascontiguousarray(np.broadcast_to(mean, (N,)), dtype=x_dtype)
         std = None if std is None else np.ascontiguousarray(np.broadcast_to(std, (N,)), dtype=x_dtype)
@@ -751,7 +757,7 @@ class Handle:
         Vd, v_cplx = _host_vectors(V)
         if Vd is not None and Vd.shape != (N, m):
             raise ValueError("reconstruct: V must be N x m = %d x %d, got %s" % (N, m, Vd.shape))
-        idx = None if keep_idx is None else np.ascontiguousarray(keep_idx, dtype=np.int64)
+        idx = _kept_index("reconstruct", keep_idx)
         N_full = N if N_full is None else N_full
         mean = None if mean is None else np.ascontiguousarray(np.broadcast_to(mean, (N,)), dtype=np.float64)
         std = None if std is None else np.ascontiguousarray(np.broadcast_to(std, (N,)), dtype=np.float64)
@@ -817,22 +823,19 @@ class Handle:
         out = np.zeros((n_runs, n_out), dtype=np.float64)
         kept = np.zeros(n_runs, dtype=np.int32)
         columns = "_columns" if axis == 1 else ""
+        # the operator of the replicates' complexification: the symbol's suffix and its leading arguments
         if complexify and extend_period is not None:
             col3, hbar, U, W = extended_imag_parts(T, extend_period)
-            run = getattr(self._lib, "xmca_bootstrap_runs%s_extended" % columns)
-            self._check(run(self._h, _ptr(col3), _ptr(hbar), _ptr(U), _ptr(W), U.shape[1], _ptr(il), _ptr(ir), n_runs, int(rotated),
-                            int(p), int(power), float(tol), _ptr(out), _ptr(kept), n_out))
-            return out, kept.astype(bool)
-        if complexify and theta_period is not None:
+            suffix, lead = "_extended", (_ptr(col3), _ptr(hbar), _ptr(U), _ptr(W), U.shape[1])
+        elif complexify and theta_period is not None:
             col3, hbar, B = theta_imag_parts(T, theta_period)          # (once per call, not per replicate)
-            run = getattr(self._lib, "xmca_bootstrap_runs%s_theta" % columns)
-            self._check(run(self._h, _ptr(col3), _ptr(hbar), _ptr(B), int(theta_period), _ptr(il), _ptr(ir), n_runs, int(rotated),
-                            int(p), int(power), float(tol), _ptr(out), _ptr(kept), n_out))
-            return out, kept.astype(bool)
-        ht = hilbert_imag_column(T) if complexify else None
-        run = getattr(self._lib, "xmca_bootstrap_runs" + columns)
-        self._check(run(self._h, _ptr(ht), _ptr(il), _ptr(ir), n_runs, int(rotated), int(p), int(power), float(tol), _ptr(out),
-                        _ptr(kept), n_out))
+            suffix, lead = "_theta", (_ptr(col3), _ptr(hbar), _ptr(B), int(theta_period))
+        else:
+            ht = hilbert_imag_column(T) if complexify else None
+            suffix, lead = "", (_ptr(ht),)
+        run = getattr(self._lib, "xmca_bootstrap_runs" + columns + suffix)
+        self._check(run(self._h, *lead, _ptr(il), _ptr(ir), n_runs, int(rotated), int(p), int(power), float(tol), _ptr(out), _ptr(kept),
+                        n_out))
         return out, kept.astype(bool)
 
     def bootstrap_patterns(self, T, complexify, idx, n_runs, k, v0_left, v0_right=None):
@@ -914,7 +917,7 @@ class Handle:
         XMCA_DEVICE)."""
         Yd = np.ascontiguousarray(np.asarray(Y).real, dtype=np.float64)
         T, m = Yd.shape
-        idx = None if keep_idx is None else np.ascontiguousarray(keep_idx, dtype=np.int64)
+        idx = _kept_index("correlation_maps", keep_idx)
         code = _np_dtype_code(r_dtype)
         r, r_ptr, where = _output(alloc, (int(N_full), m), _real_np(code))
         p, p_ptr, where = _output(alloc, (int(N_full), m), np.float64)
@@ -1052,9 +1055,7 @@ class Handle:
         result of a solve and the fields stay as they are."""
         M, tau, k = int(embedding), int(tau), int(n_modes)
         n_out = int(T) - (M - 1) * tau
-        idx = None if keep_idx is None else np.ascontiguousarray(keep_idx, dtype=np.int64)
-        if idx is not None and idx.shape != (int(N),):
-            raise ValueError("extended_eofs: keep_idx must hold one row index per kept point (%d), got shape %s" % (N, idx.shape))
+        idx = _kept_index("extended_eofs", keep_idx, N)
         N_full = int(N) if N_full is None else int(N_full)
         if M < 1 or tau < 1 or n_out < 2 or not 1 <= k <= min(n_out - 1, M * int(N)):
             raise ValueError("extended_eofs: embedding, tau >= 1, T' >= 2 and 1 <= n_modes <= min(T' - 1, embedding * N) are needed")
@@ -1156,9 +1157,7 @@ class Handle:
             raise ValueError("extended_reconstruct: embedding, tau >= 1, T' >= 2 and tau <= T' (embedding > 1) are needed")
         if sel.size < 1 or sel[0] < 0 or sel[-1] >= min(n_win - 1, M * N) or np.any(np.diff(sel) <= 0):
             raise ValueError("extended_reconstruct: modes must be increasing 0-based indices below min(T' - 1, embedding * N)")
-        idx = None if keep_idx is None else np.ascontiguousarray(keep_idx, dtype=np.int64)
-        if idx is not None and idx.shape != (N,):
-            raise ValueError("extended_reconstruct: keep_idx must hold one index per kept point (%d), got shape %s" % (N, idx.shape))
+        idx = _kept_index("extended_reconstruct", keep_idx, N)
         N_full = N if N_full is None else int(N_full)
         mean = None if mean is None else np.ascontiguousarray(np.broadcast_to(mean, (N,)), dtype=np.float64)
         std = None if std is None else np.ascontiguousarray(np.broadcast_to(std, (N,)), dtype=np.float64)

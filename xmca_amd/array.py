@@ -61,6 +61,11 @@ def _reconstruct_coefficients(P, A):
     return P @ A.conj().T
 
 
+def _is_int(x):
+    """A python or numpy integer that is not a bool."""
+    return isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_))
+
+
 def _torch():
     """torch when the process has imported it, else None: a tensor can only be handed over by code that has."""
     return sys.modules.get('torch')
@@ -327,10 +332,7 @@ class MCA:
         """extend='theta': the analytic signal as the device formed it - the real fields in float64 and the imaginary planes
         G0 X + B C fetched from the handle.  When something else has used the handle since the solve, the fields go up and are
         extended there again first (the fits of a column are the same bits on every call)."""
-        dev = self._device()
-        if not self._owns_device_fields(dev):
-            self._upload_serial += 1
-            self._upload_fields(dev)
+        dev = self._resident_device()
         store = self._fields_store
         return {k: np.asarray(store[k].real, dtype=np.float64) + 1j * dev.get_field_imag(side, store[k].shape)
                 for side, k in enumerate(self._keys)}
@@ -358,6 +360,20 @@ class MCA:
 
     def _owns_device_fields(self, dev):
         return getattr(dev, 'fields_owner', None) == self._owner_key()
+
+    def _resident_device(self):
+        """The handle, with the fields `solve()` works on resident: they go up again when another model, `rule_n` or a bootstrap
+        has used the handle in between."""
+        dev = self._device()
+        if not self._owns_device_fields(dev):
+            self._upload_serial += 1
+            self._upload_fields(dev)
+        return dev
+
+    def _kept_columns(self, k):
+        """(indices of the kept columns of field k, or None when none is masked; its full width)."""
+        mask = self._no_nan_index[k]
+        return (None if mask.all() else np.flatnonzero(mask)), mask.size
 
     def _ingest_on_device(self, data):
         """preprocess='device': upload the raw fields, drop their NaN columns and center them there, keep them resident.
@@ -700,14 +716,14 @@ class MCA:
                      n eps sigma_1.
         """
         if n_modes is not None:
-            if isinstance(n_modes, (bool, np.bool_)) or not isinstance(n_modes, (int, np.integer)):
+            if not _is_int(n_modes):
                 raise ValueError('`n_modes` must be None or an integer >= 1, not {!r}'.format(n_modes))
             if n_modes < 1:
                 raise ValueError('`n_modes` must be >= 1, not {!r}'.format(n_modes))
             n_modes = int(n_modes)
         if complexify and extend == 'theta':
             n_obs = self._n_observations.get('left', 0)
-            if isinstance(period, (bool, np.bool_)) or not isinstance(period, (int, np.integer)) or period < 1:
+            if not _is_int(period) or period < 1:
                 raise ValueError("`period` must be an integer >= 1 for extend='theta', not {!r}".format(period))
             if n_obs < 2 * period:
                 raise ValueError("`period` = {:} needs at least 2 * period = {:} time steps for extend='theta'; the fields have "
@@ -878,10 +894,7 @@ class MCA:
 
     def _project_on_device(self, V):
         """fields[k] @ V[k] of `_get_U` (array.py:391) as a device GEMM over the resident fields."""
-        dev = self._device()
-        if not self._owns_device_fields(dev):
-            self._upload_serial += 1          # another model / rule_n used the handle in between: upload again
-            self._upload_fields(dev)
+        dev = self._resident_device()
         T = self._n_observations['left']
         if next(iter(V.values())).shape[1] == 0:          # pcs(0): nothing to project (bootstrapping's first iterative step)
             return {k: np.zeros((T, 0), dtype=V[k].dtype) for k in self._keys}
@@ -902,12 +915,9 @@ class MCA:
         or uploaded again.  (None, None) when they are not resident - the caller then takes `_get_V`."""
         if not self._vectors_resident():
             return None, None
-        dev = self._device()
-        if not self._owns_device_fields(dev):
-            self._upload_serial += 1
-            self._upload_fields(dev)              # (may release the result: checked again below)
-            if not self._vectors_resident():
-                return None, None
+        dev = self._resident_device()
+        if not self._vectors_resident():          # (an upload may have released the result)
+            return None, None
         m = self._analysis['rank'] if max_mode is None else min(int(max_mode), self._analysis['rank'])
         m = min(m, self._V._rank)                 # (solve(n_modes=k): k modes are resident, as `_get_V` finds k after truncate(k))
         T = self._n_observations['left']
@@ -1039,9 +1049,8 @@ class MCA:
             if plain and alloc is None:
                 full = dev.eofs(side, n_k, m, W, dtype)   # no mask, no scaling, no phase shift: `xmca_get_eofs` as it is
             else:                                         # (on the GPU the plain case is a map without options: the same bits)
-                masked = self._n_variables[k] != n_k
-                full = dev.maps(side, n_k, m, W, factor, np.flatnonzero(self._no_nan_index[k]) if masked else None,
-                                self._n_variables[k], kind, _MAP_SCALINGS[scaling], dt, alloc=alloc)
+                keep_idx, n_full = self._kept_columns(k)
+                full = dev.maps(side, n_k, m, W, factor, keep_idx, n_full, kind, _MAP_SCALINGS[scaling], dt, alloc=alloc)
             out[k] = full.reshape(self._fields_spatial_shape[k] + (full.shape[1],))
         return out
 
@@ -1227,10 +1236,7 @@ class MCA:
         distribution does not exist: every p is NaN) and `_patterns_on_host` take the host route: `xmca_correlate`, then
         `_two_sided_p` and the re-layout in numpy."""
         pcs = self._get_pcs(n=n, phase_shift=phase_shift)
-        dev = self._device()
-        if not self._owns_device_fields(dev):
-            self._upload_serial += 1
-            self._upload_fields(dev)
+        dev = self._resident_device()
         n_obs = self._n_observations['left']
         on_host = n_obs < 3 or n_obs > _hip.PVALUE_MAX_OBS or getattr(self, '_patterns_on_host', False)
         alloc = None if on_host else self._alloc()
@@ -1246,9 +1252,7 @@ class MCA:
                 p = _two_sided_p(r, n_obs)
                 r, p = (self._with_nan_columns(k, src.T, (src.shape[1],)).T for src in (r, p))
             else:
-                mask = self._no_nan_index[k]
-                keep_idx = None if self._fields_store[k].shape[1] == mask.size else np.flatnonzero(mask)
-                r, p = dev.correlation_maps(side, y, keep_idx, mask.size, r_dtype, alloc=alloc)
+                r, p = dev.correlation_maps(side, y, *self._kept_columns(k), r_dtype, alloc=alloc)
             rvals[k] = r.reshape(self._fields_spatial_shape[k] + (r.shape[1],))
             pvals[k] = p.reshape(self._fields_spatial_shape[k] + (p.shape[1],))
         return self._deliver((rvals, pvals))
@@ -1268,9 +1272,7 @@ class MCA:
         V = getattr(self, '_V', None)
         if getattr(self, '_transform_on_host', False) or not isinstance(V, _LazyVectors):
             return None
-        cls = type(self)
-        if ((cls._scale_X is not MCA._scale_X or cls._scale_X_inverse is not MCA._scale_X_inverse)
-                and cls._device_column_weights is MCA._device_column_weights):
+        if not self._scaling_known_to_device():
             return None                   # a subclass scales differently and does not say how: its own host path
         dev = self._device()
         if k in V._pending:
@@ -1283,6 +1285,20 @@ class MCA:
         `inverse` first - or None (nothing, the array class).  A subclass that overrides the scaling methods without overriding
         this hook keeps the host route (`_transform_vectors`)."""
         return None
+
+    def _scaling_known_to_device(self):
+        """False for a subclass that overrides `_scale_X` / `_scale_X_inverse` without stating it through `_device_column_weights`."""
+        cls = type(self)
+        return ((cls._scale_X is MCA._scale_X and cls._scale_X_inverse is MCA._scale_X_inverse)
+                or cls._device_column_weights is not MCA._device_column_weights)
+
+    def _inverse_scaling(self, k, original_scale):
+        """(mean, std, inv_weight) of field k that the device's reconstructions undo for `original_scale`, else three None."""
+        if not original_scale:
+            return None, None, None
+        weights = self._device_column_weights(k)
+        return (self._field_means[k], self._field_stds[k] if self._analysis['is_normalized'] else None,
+                None if weights is None else weights[1])
 
     def _reconstruct_on_device(self, mode, original_scale, full, alloc=None):
         """`(pcs(mode, 'eigen') @ V_rot^H).real`, scaled back and (full) with the masked points re-inserted as NaN, as one product
@@ -1312,17 +1328,10 @@ class MCA:
             B = _reconstruct_coefficients(P[k], A) if A.shape[1] else np.zeros((T, 0))
             dtype = _real_dtype(np.result_type(P[k].dtype, vdt))            # the reference's (U @ V^H).real
             n_keep = self._fields_store[k].shape[1]
-            mean = std = inv_weight = None
-            if original_scale:
-                mean = self._field_means[k]
-                std = self._field_stds[k] if self._analysis['is_normalized'] else None
-                weights = self._device_column_weights(k)
-                inv_weight = None if weights is None else weights[1]
-            mask = self._no_nan_index[k]
-            keep_idx = np.flatnonzero(mask) if (full and n_keep != mask.size) else None
+            mean, std, inv_weight = self._inverse_scaling(k, original_scale)
+            keep_idx, n_full = self._kept_columns(k) if full else (None, n_keep)      # (not full: the compact columns, no scatter)
             X = dev.reconstruct(side, B, None if Vh is None else Vh[:, :B.shape[1]], n_keep, keep_idx=keep_idx,
-                                N_full=mask.size if keep_idx is not None else n_keep, mean=mean, std=std, inv_weight=inv_weight,
-                                alloc=alloc)
+                                N_full=n_full, mean=mean, std=std, inv_weight=inv_weight, alloc=alloc)
             out[k] = X if full else X.astype(dtype, copy=False)
         return out
 
@@ -1435,8 +1444,7 @@ class MCA:
         if W.shape[1] == 0:
             return np.zeros((x.shape[0], 0), dtype=np.result_type(W.dtype, self._resident_dtype()))
         dev, Vh = self._transform_vectors(k)
-        mask = self._no_nan_index[k]
-        keep_idx = None if mask.all() else np.flatnonzero(mask)
+        keep_idx = self._kept_columns(k)[0]
         std = self._field_stds[k] if self._analysis['is_normalized'] else None
         side = self._keys.index(k)
         weights = self._device_column_weights(k)
@@ -1457,10 +1465,7 @@ class MCA:
         does not change when a column is rescaled (`normalize`, `apply_weights`).  The fields are made resident as for the
         projections; only the values themselves come back.  This is the phi of `rule_n(noise='ar1')`."""
         self._get_svals(1)                    # (before `solve`: the getters' RuntimeError)
-        dev = self._device()
-        if not self._owns_device_fields(dev):
-            self._upload_serial += 1
-            self._upload_fields(dev)
+        dev = self._resident_device()
         out = {}
         for side, k in enumerate(self._keys):
             phi = dev.lag1_autocorrelation(side, int(np.count_nonzero(self._no_nan_index[k])))
@@ -1671,7 +1676,7 @@ class MCA:
         Under an initialised `torch.distributed` group every rank computes all replicates: nothing is sharded and no collective
         is called.  Rotated models and models solved with `extend=` are not supported (ValueError)."""
         self._get_svals(1)                    # (before `solve`: the getters' RuntimeError)
-        if isinstance(n_runs, (bool, np.bool_)) or not isinstance(n_runs, (int, np.integer)) or n_runs < 2:
+        if not _is_int(n_runs) or n_runs < 2:
             raise ValueError('`n_runs` must be an integer >= 2 (a standard error needs two replicates), not {!r}'.format(n_runs))
         if self._analysis['is_rotated']:
             raise ValueError('bootstrap_eofs does not support rotated models (out of scope: the modes of a replicate would have '
@@ -1679,7 +1684,7 @@ class MCA:
         if self._analysis['extend']:
             raise ValueError('bootstrap_eofs does not support models solved with `extend=` (out of scope)')
         resident = len(self._singular_values)
-        if isinstance(n_modes, (bool, np.bool_)) or not isinstance(n_modes, (int, np.integer)) or not 1 <= n_modes <= resident:
+        if not _is_int(n_modes) or not 1 <= n_modes <= resident:
             raise ValueError('`n_modes` must be an integer between 1 and the {:} modes the model holds, not {!r}'.format(resident, n_modes))
         n_runs, k = int(n_runs), int(n_modes)
         n_obs = self._n_observations['left']
@@ -1711,6 +1716,29 @@ class MCA:
                 out[name][key] = np.ascontiguousarray(full).reshape(shape)
         return out
 
+    def _lag_window(self, what, embedding, tau, arg_error):
+        """The argument checks and window arithmetic shared by `extended_eofs` and `extended_reconstruct` (`what`): `embedding` and
+        `tau` integers >= 1, the caller's own argument (`arg_error`: its message, or None), one real field, T' >= 2.  Returns
+        (M, tau, key, T, n_kept, T', min(T' - 1, M * n_kept))."""
+        for name, value in (('embedding', embedding), ('tau', tau)):
+            if not _is_int(value) or value < 1:
+                raise ValueError('`{:}` must be an integer >= 1, not {!r}'.format(name, value))
+        if arg_error is not None:
+            raise ValueError(arg_error)
+        if len(self._keys) != 1:
+            raise ValueError('{:} takes a model of one field (extended MCA of two fields is out of scope)'.format(what))
+        if self._analysis['is_complex']:
+            raise ValueError('{:} does not support complex models (out of scope)'.format(what))
+        M, tau = int(embedding), int(tau)
+        key = self._keys[0]
+        T = self._n_observations[key]
+        n_kept = int(np.count_nonzero(self._no_nan_index[key]))
+        n_win = T - (M - 1) * tau
+        if n_win < 2:
+            raise ValueError('embedding = {:} with tau = {:} leaves T - (embedding - 1) * tau = {:} of {:} time steps; at least 2 '
+                             'are needed'.format(M, tau, n_win, T))
+        return M, tau, key, T, n_kept, n_win, min(n_win - 1, M * n_kept)
+
     def extended_eofs(self, embedding, tau=1, n_modes=10):
         """Extended EOF analysis (EEOF; Weare & Nasstrom 1982; with a long window, multichannel SSA) of one real field: the EOFs
         of the field embedded with its own time lags (an extension).
@@ -1733,33 +1761,14 @@ class MCA:
         calls return the same bits.  Under an initialised `torch.distributed` group every rank computes everything: nothing is
         sharded and no collective is called.  ValueError: `embedding` or `tau` not an integer >= 1, T' < 2, `n_modes` not an
         integer in [1, min(T' - 1, M * N)], a model of two fields, a complex model."""
-        for name, value in (('embedding', embedding), ('tau', tau)):
-            if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or value < 1:
-                raise ValueError('`{:}` must be an integer >= 1, not {!r}'.format(name, value))
-        if isinstance(n_modes, (bool, np.bool_)) or not isinstance(n_modes, (int, np.integer)):
-            raise ValueError('`n_modes` must be an integer >= 1, not {!r}'.format(n_modes))
-        if len(self._keys) != 1:
-            raise ValueError('extended_eofs takes a model of one field (extended MCA of two fields is out of scope)')
-        if self._analysis['is_complex']:
-            raise ValueError('extended_eofs does not support complex models (out of scope)')
-        M, tau, k = int(embedding), int(tau), int(n_modes)
-        key = self._keys[0]
-        T = self._n_observations[key]
-        n_kept = int(np.count_nonzero(self._no_nan_index[key]))
-        n_win = T - (M - 1) * tau
-        if n_win < 2:
-            raise ValueError('embedding = {:} with tau = {:} leaves T - (embedding - 1) * tau = {:} of {:} time steps; at least 2 '
-                             'are needed'.format(M, tau, n_win, T))
-        most = min(n_win - 1, M * n_kept)
+        M, tau, key, T, n_kept, n_win, most = self._lag_window(
+            'extended_eofs', embedding, tau,
+            None if _is_int(n_modes) else '`n_modes` must be an integer >= 1, not {!r}'.format(n_modes))
+        k = int(n_modes)
         if not 1 <= k <= most:
             raise ValueError('`n_modes` must be an integer between 1 and min(T\' - 1, embedding * N) = {:}, not {!r}'.format(most, n_modes))
-        dev = self._device()
-        if not self._owns_device_fields(dev):
-            self._upload_serial += 1
-            self._upload_fields(dev)
-        n_full = self._n_variables[key]
-        masked = n_full != n_kept
-        lam, pcs, eofs = dev.extended_eofs(T, n_kept, M, tau, k, np.flatnonzero(self._no_nan_index[key]) if masked else None, n_full)
+        dev = self._resident_device()
+        lam, pcs, eofs = dev.extended_eofs(T, n_kept, M, tau, k, *self._kept_columns(key))
         total = np.maximum(lam, 0.0).sum()
         return {'singular_values': lam[:k] / (n_win - 1),
                 'explained_variance': lam[:k] / total * 100.0,
@@ -1787,27 +1796,13 @@ class MCA:
         `embedding` > 1 (time steps that lie in no window), a `mode` that is neither None, int nor slice, a selection that is
         empty or reaches past min(T' - 1, M N), a model of two fields, a complex model, `original_scale` on a subclass that
         overrides the scaling methods without the `_device_column_weights` hook."""
-        for name, value in (('embedding', embedding), ('tau', tau)):
-            if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or value < 1:
-                raise ValueError('`{:}` must be an integer >= 1, not {!r}'.format(name, value))
-        if isinstance(mode, (bool, np.bool_)) or not (mode is None or isinstance(mode, (int, np.integer, slice))):
-            raise ValueError('Invalid `mode` {!r}. Must be None, an int or a slice.'.format(mode))
-        if len(self._keys) != 1:
-            raise ValueError('extended_reconstruct takes a model of one field (extended MCA of two fields is out of scope)')
-        if self._analysis['is_complex']:
-            raise ValueError('extended_reconstruct does not support complex models (out of scope)')
-        M, tau = int(embedding), int(tau)
-        key = self._keys[0]
-        T = self._n_observations[key]
-        n_kept = int(np.count_nonzero(self._no_nan_index[key]))
-        n_win = T - (M - 1) * tau
-        if n_win < 2:
-            raise ValueError('embedding = {:} with tau = {:} leaves T - (embedding - 1) * tau = {:} of {:} time steps; at least 2 '
-                             'are needed'.format(M, tau, n_win, T))
+        M, tau, key, T, n_kept, n_win, most = self._lag_window(
+            'extended_reconstruct', embedding, tau,
+            None if mode is None or isinstance(mode, slice) or _is_int(mode)
+            else 'Invalid `mode` {!r}. Must be None, an int or a slice.'.format(mode))
         if M > 1 and tau > n_win:
             raise ValueError('tau = {:} is above the window count T\' = {:}: some time steps lie in no window and cannot be '
                              'reconstructed'.format(tau, n_win))
-        most = min(n_win - 1, M * n_kept)
         if mode is None:
             first, stop, step = 0, most, 1
         elif isinstance(mode, slice):
@@ -1819,23 +1814,12 @@ class MCA:
         modes = np.arange(first, stop, step) if step >= 1 else np.arange(0)
         if first < 0 or modes.size < 1 or modes[-1] >= most:
             raise ValueError('`mode` = {!r} must select at least one of the modes 1..min(T\' - 1, embedding * N) = {:}'.format(mode, most))
-        cls = type(self)
-        if (original_scale and (cls._scale_X is not MCA._scale_X or cls._scale_X_inverse is not MCA._scale_X_inverse)
-                and cls._device_column_weights is MCA._device_column_weights):
+        if original_scale and not self._scaling_known_to_device():
             raise ValueError('this class scales its fields in its own `_scale_X_inverse` without a `_device_column_weights`: '
                              'only original_scale=False is available')
-        dev = self._device()
-        if not self._owns_device_fields(dev):
-            self._upload_serial += 1
-            self._upload_fields(dev)
-        mean = std = inv_weight = None
-        if original_scale:
-            mean = self._field_means[key]
-            std = self._field_stds[key] if self._analysis['is_normalized'] else None
-            weights = self._device_column_weights(key)
-            inv_weight = None if weights is None else weights[1]
-        n_full = self._n_variables[key]
-        keep_idx = np.flatnonzero(self._no_nan_index[key]) if n_full != n_kept else None
+        dev = self._resident_device()
+        mean, std, inv_weight = self._inverse_scaling(key, original_scale)
+        keep_idx, n_full = self._kept_columns(key)
         X = dev.extended_reconstruct(T, n_kept, M, tau, modes, bool(original_scale), keep_idx=keep_idx, N_full=n_full, mean=mean, std=std,
                                      inv_weight=inv_weight, alloc=self._alloc())
         return {key: X.reshape((-1,) + tuple(self._fields_spatial_shape[key]))}

@@ -208,6 +208,20 @@ void with_dtype(int code, F&& f) {
   else f(double{});
 }
 
+// number of time steps of the resident fields
+int64_t resident_T(xmca_handle* h) {
+  int64_t T = 0;
+  with_dtype(h->dtype, [&](auto t) { T = typed<decltype(t)>(h).f[0].T; });
+  return T;
+}
+
+// number of columns of the resident field of `side`
+int64_t resident_N(xmca_handle* h, int side) {
+  int64_t N = 0;
+  with_dtype(h->dtype, [&](auto t) { N = typed<decltype(t)>(h).f[side].N; });
+  return N;
+}
+
 // ---- argument checks shared by the entry points (`what`: the entry point's prefix of the message) ---------------------------
 void check_side(const char* what, int side) {
   XMCA_CHECK(side == 0 || side == 1, XMCA_ERR_INVALID, std::string(what) + ": side must be 0 or 1");
@@ -248,6 +262,41 @@ void check_bootstrap_runs(const double* spectra_out, const int* kept_out, int64_
                           int p, int power) {
   XMCA_CHECK(spectra_out && kept_out && n_out >= 1 && n_runs >= 0, XMCA_ERR_INVALID, "bootstrap: output buffers missing");
   check_rotation_args("bootstrap", "rotation needs n_rot >= 2 and power >= 1", rotated, p, power);
+}
+
+// the kept columns of a masked output: N of N_full <= max_full columns, keep_idx (NULL: all of them, N_full == N) their strictly
+// increasing indices in [0, N_full)
+void check_kept_columns(const char* what, const int64_t* keep_idx, int64_t N, int64_t N_full, int64_t max_full) {
+  const std::string w(what);
+  XMCA_CHECK(N_full >= N && N_full <= max_full && (keep_idx || N_full == N), XMCA_ERR_INVALID,
+             w + ": N_full must be the " + std::to_string(N) + " kept columns, or more with keep_idx");
+  for (int64_t c = 0; keep_idx && c < N; ++c)
+    XMCA_CHECK(keep_idx[c] >= 0 && keep_idx[c] < N_full && (c == 0 || keep_idx[c] > keep_idx[c - 1]), XMCA_ERR_INVALID,
+               w + ": keep_idx must be increasing indices below N_full, one per kept column");
+}
+
+// the resident field of side 0 and the embedding of the lag entries: a real field, embedding and tau >= 1, T' >= min_window
+int64_t check_lag_embedding(xmca_handle* h, const char* what, int embedding, int tau, int64_t min_window) {
+  const std::string w(what);
+  XMCA_CHECK(h->field_set[0], XMCA_ERR_STATE, w + ": no field set");
+  XMCA_CHECK(embedding >= 1 && tau >= 1, XMCA_ERR_INVALID, w + ": embedding and tau must be at least 1");
+  bool has_im = false;
+  with_dtype(h->dtype, [&](auto t) { has_im = typed<decltype(t)>(h).f[0].has_im; });
+  XMCA_CHECK(!has_im && !h->op_pending, XMCA_ERR_INVALID, w + ": the resident field is complex (real fields only)");
+  const int64_t T = resident_T(h);
+  check_operator_size(what, T);
+  const int64_t np = T - (int64_t)(embedding - 1) * tau;
+  XMCA_CHECK(np >= min_window, XMCA_ERR_INVALID, w + ": T - (embedding - 1) * tau must be at least " + std::to_string(min_window));
+  return np;
+}
+
+// the plane of the gap entries: dtype, T x N within the eigensolver's and the kernels' index ranges
+void check_gap_plane(const char* what, int64_t T, int64_t N, int dtype) {
+  const std::string w(what);
+  XMCA_CHECK(dtype == XMCA_F32 || dtype == XMCA_F64, XMCA_ERR_INVALID, w + ": dtype must be XMCA_F32 or XMCA_F64");
+  XMCA_CHECK(T >= 1 && N >= 1, XMCA_ERR_INVALID, w + ": the field must have at least one row and one column");
+  check_operator_size(what, T);
+  XMCA_CHECK(N < ((int64_t)1 << 31) && T * N < ((int64_t)1 << 40), XMCA_ERR_UNSUPPORTED, w + ": field too large");
 }
 
 // ---- host arrays <-> device planes --------------------------------------------------------------------------------------------
@@ -291,18 +340,15 @@ void pack_download(xmca_handle* h, const double* re, const double* im, int64_t l
   XMCA_HIP(hipMemcpyAsync(host, packed, sizeof(TO) * (size_t)rows * cols * (im ? 2 : 1), hipMemcpyDeviceToHost, h->st));
 }
 
-// number of time steps of the resident fields
-int64_t resident_T(xmca_handle* h) {
-  int64_t T = 0;
-  with_dtype(h->dtype, [&](auto t) { T = typed<decltype(t)>(h).f[0].T; });
-  return T;
-}
-
-// number of columns of the resident field of `side`
-int64_t resident_N(xmca_handle* h, int side) {
-  int64_t N = 0;
-  with_dtype(h->dtype, [&](auto t) { N = typed<decltype(t)>(h).f[side].N; });
-  return N;
+// The inverse of keep_idx on the device: entry n of N_full is the kept column that full column n is, or -1.  Returns its device
+// pointer, or null without keep_idx (every column kept).
+const int64_t* upload_inverse_map(xmca_handle* h, const int64_t* keep_idx, int64_t N, int64_t N_full, DevBuf<int64_t>& dev) {
+  if (!keep_idx) return nullptr;
+  std::vector<int64_t> inv((size_t)N_full, -1);
+  for (int64_t c = 0; c < N; ++c) inv[(size_t)keep_idx[c]] = c;
+  XMCA_HIP(hipMemcpyAsync(dev.ensure((size_t)N_full), inv.data(), sizeof(int64_t) * N_full, hipMemcpyHostToDevice, h->st));
+  XMCA_HIP(hipStreamSynchronize(h->st));      // (inv is a host temporary)
+  return dev.get();
 }
 
 template <typename TI>
@@ -518,12 +564,7 @@ void get_maps_impl(xmca_handle* h, int side, const double* W, int64_t m, int64_t
   HostPlanes<double> w, f;
   eofs_compact<double>(h, side, W, m, q, w_cplx, w, tmp);
   if (col_factor) upload_planes<double>(h, col_factor, (size_t)q, f_cplx, f, false);
-  if (keep_idx) {
-    std::vector<int64_t> inv((size_t)N_full, -1);
-    for (int64_t c = 0; c < N; ++c) inv[(size_t)keep_idx[c]] = c;
-    XMCA_HIP(hipMemcpyAsync(row_of.ensure((size_t)N_full), inv.data(), sizeof(int64_t) * N_full, hipMemcpyHostToDevice, h->st));
-    XMCA_HIP(hipStreamSynchronize(h->st));      // (inv is a host temporary)
-  }
+  const int64_t* rows = upload_inverse_map(h, keep_idx, N, N_full, row_of);
   h->tm.begin("maps");
   if (scaling != XMCA_SCALE_NONE) {
     const int blocks = (int)std::min<int64_t>(ceil_div(N, (int64_t)256), MAP_STAT_BLOCKS);
@@ -544,7 +585,7 @@ void get_maps_impl(xmca_handle* h, int side, const double* W, int64_t m, int64_t
   }
   const size_t total = (size_t)N_full * q;
   hipLaunchKernelGGL((map_finish_kernel<TO>), ew_grid((int64_t)total), dim3(EW_BLOCK), 0, h->st, tmp.get(), (int)c_cplx,
-                     keep_idx ? row_of.get() : nullptr, N_full, (int)q, f.r, f.i, scaling != XMCA_SCALE_NONE ? div.get() : nullptr, kind,
+                     rows, N_full, (int)q, f.r, f.i, scaling != XMCA_SCALE_NONE ? div.get() : nullptr, kind,
                      (int)o_cplx, out_dev ? static_cast<TO*>(out) : fin.ensure(total * (o_cplx ? 2 : 1)));     // (a device destination is final)
   XMCA_HIP(hipGetLastError());
   h->tm.end();
@@ -780,12 +821,7 @@ struct ReconstructTail {
   void begin(xmca_handle* h, int64_t T, const int64_t* keep_idx, int64_t N_, int64_t N_full_, const double* mean, const double* stdv,
              const double* inv_weight, bool out_dev_) {
     N = N_; N_full = N_full_; out_dev = out_dev_;
-    if (keep_idx) {
-      std::vector<int64_t> inv((size_t)N_full, -1);
-      for (int64_t c = 0; c < N; ++c) inv[(size_t)keep_idx[c]] = c;
-      XMCA_HIP(hipMemcpyAsync(col_of.ensure((size_t)N_full), inv.data(), sizeof(int64_t) * N_full, hipMemcpyHostToDevice, h->st));
-      XMCA_HIP(hipStreamSynchronize(h->st));      // (inv is a host temporary)
-    }
+    upload_inverse_map(h, keep_idx, N, N_full, col_of);
     if (mean) XMCA_HIP(hipMemcpyAsync(mu.ensure((size_t)N), mean, sizeof(double) * N, hipMemcpyHostToDevice, h->st));
     if (stdv) XMCA_HIP(hipMemcpyAsync(sd.ensure((size_t)N), stdv, sizeof(double) * N, hipMemcpyHostToDevice, h->st));
     if (inv_weight) XMCA_HIP(hipMemcpyAsync(iw.ensure((size_t)N), inv_weight, sizeof(double) * N, hipMemcpyHostToDevice, h->st));
@@ -851,13 +887,8 @@ void check_transform(xmca_handle* h, const char* what, int side, const void* V, 
                      int64_t N_full) {
   const std::string w(what);
   check_side(what, side);
-  XMCA_CHECK(N_keep >= 1 && N_full >= N_keep && m >= 0 && m <= INT32_MAX && N_full <= INT32_MAX, XMCA_ERR_INVALID, w + ": bad sizes");
-  XMCA_CHECK(keep_idx || N_keep == N_full, XMCA_ERR_INVALID, w + ": all columns are kept without keep_idx");
-  if (keep_idx) {
-    for (int64_t c = 0; c < N_keep; ++c)
-      XMCA_CHECK(keep_idx[c] >= 0 && keep_idx[c] < N_full && (c == 0 || keep_idx[c] > keep_idx[c - 1]), XMCA_ERR_INVALID,
-                 w + ": keep_idx must be increasing column indices below N_full");
-  }
+  XMCA_CHECK(N_keep >= 1 && m >= 0 && m <= INT32_MAX, XMCA_ERR_INVALID, w + ": bad sizes");
+  check_kept_columns(what, keep_idx, N_keep, N_full, INT32_MAX);
   if (!V && m > 0)
     XMCA_CHECK(h->solved && m <= h->res.n_vec && h->res.ldv[side] == N_keep, XMCA_ERR_INVALID,
                w + ": the resident vectors of the last solve do not have N_keep rows and m modes");
@@ -924,16 +955,11 @@ void correlation_maps_impl(xmca_handle* h, int side, const double* Y, int64_t T,
   DevBuf<int64_t> row_of;
   correlate_device<TI>(h, "correlation_maps", side, Y, T, m, C);
   const int64_t N = typed<TI>(h).f[side].N;
-  if (keep_idx) {
-    std::vector<int64_t> inv((size_t)N_full, -1);
-    for (int64_t c = 0; c < N; ++c) inv[(size_t)keep_idx[c]] = c;
-    XMCA_HIP(hipMemcpyAsync(row_of.ensure((size_t)N_full), inv.data(), sizeof(int64_t) * N_full, hipMemcpyHostToDevice, h->st));
-    XMCA_HIP(hipStreamSynchronize(h->st));      // (inv is a host temporary)
-  }
+  const int64_t* rows = upload_inverse_map(h, keep_idx, N, N_full, row_of);
   const size_t total = (size_t)N_full * m;
   h->tm.begin("correlation_maps");
-  hipLaunchKernelGGL((correlation_maps_kernel<TR>), ew_grid((int64_t)total), dim3(EW_BLOCK), 0, h->st, C.get(),
-                     keep_idx ? row_of.get() : nullptr, N_full, (int)m, 0.5 * (double)T - 1.0, pvalue_log_norm(T),
+  hipLaunchKernelGGL((correlation_maps_kernel<TR>), ew_grid((int64_t)total), dim3(EW_BLOCK), 0, h->st, C.get(), rows, N_full,
+                     (int)m, 0.5 * (double)T - 1.0, pvalue_log_norm(T),
                      out_dev ? r_out : rd.ensure(total), out_dev ? p_out : pd.ensure(total));     // (device destinations are final)
   XMCA_HIP(hipGetLastError());
   h->tm.end();
@@ -1460,7 +1486,22 @@ struct PatternStats {
   }
 };
 
-// ---- bootstrapping: working copies on the device -----------------------------------------------------------------
+// ---- extended (lag-embedded) EOFs (csrc/lag_gram.h, csrc/lag_reconstruct.h) -----------------------------
+// Back-projection of leading vectors on the lagged views of a plane: Z (q x Tp, float64) is narrowed to the plane's element type
+// into the caller's `z`, then one thin GEMM per lag j < M of Z against the rows [j tau, j tau + Tp) of X (T x N, row stride N)
+// fills the rows [j q, (j + 1) q) of P, row c times row_scale[c] where that is given.  xmca_fill_gaps is the case M = 1.
+template <typename TI>
+void lag_back_project(xmca_handle* h, Narrow<TI>& z, const double* Z, int q, int Tp, int M, int tau, const TI* X, int64_t N,
+                      const double* row_scale, double* P) {
+  z.from(h->st, Z, nullptr, (int64_t)q * Tp);
+  for (int j = 0; j < M; ++j) {
+    GemmOpts o;
+    o.a_kfast = true; o.b_nfast = true;
+    o.row_scale = row_scale;
+    gemm<TI, double>(h->st, h->gws, z.r, Tp, X + (int64_t)j * tau * N, N, P + (int64_t)j * q * N, N, q, (int)N, Tp, o);
+  }
+}
+
 // The front shared by xmca_extended_eofs and xmca_extended_reconstruct: Gram product of the resident field of side 0, lag sum and
 // double centring, the k leading eigenvectors Z (k x T', row c the vector of mode c) and all eigenvalues `lam` of the T' x T' matrix.
 // The buffers live as long as the struct: the caller keeps it for the whole call.
@@ -1511,23 +1552,12 @@ void extended_eofs_impl(xmca_handle* h, int M, int tau, int k, const int64_t* ke
   int known = 0;
   while (known < k && lam[(size_t)known] > cut) { inv[(size_t)known] = 1.0 / std::sqrt(lam[(size_t)known]); ++known; }
   XMCA_HIP(hipMemcpyAsync(inv_dev.ensure((size_t)k), inv.data(), sizeof(double) * k, hipMemcpyHostToDevice, h->st));
-  if (keep_idx) {
-    std::vector<int64_t> inverse((size_t)N_full, -1);
-    for (int64_t c = 0; c < N; ++c) inverse[(size_t)keep_idx[c]] = c;
-    XMCA_HIP(hipMemcpyAsync(row_of.ensure((size_t)N_full), inverse.data(), sizeof(int64_t) * N_full, hipMemcpyHostToDevice, h->st));
-    XMCA_HIP(hipStreamSynchronize(h->st));      // (inverse is a host temporary)
-  }
+  const int64_t* rows = upload_inverse_map(h, keep_idx, N, N_full, row_of);
   Narrow<TI> z;
-  z.from(h->st, Z.get(), nullptr, (int64_t)k * np);
   const int64_t plane = (int64_t)k * N;
   P.ensure((size_t)M * plane);
   h->tm.begin("eeof_project");
-  for (int j = 0; j < M; ++j) {
-    GemmOpts o;
-    o.a_kfast = true; o.b_nfast = true;
-    o.row_scale = inv_dev.get();
-    gemm<TI, double>(h->st, h->gws, z.r, np, f.r() + (int64_t)j * tau * N, N, P.get() + j * plane, N, k, (int)N, np, o);
-  }
+  lag_back_project<TI>(h, z, Z.get(), k, np, M, tau, f.r(), N, inv_dev.get(), P.get());
   hipLaunchKernelGGL(eeof_sign_norm_kernel, dim3((unsigned)k), dim3(256), 0, h->st, (const double*)P.get(), plane, N, N, M, known,
                      scale.ensure((size_t)k));
   XMCA_HIP(hipGetLastError());
@@ -1540,7 +1570,7 @@ void extended_eofs_impl(xmca_handle* h, int M, int tau, int k, const int64_t* ke
     hipLaunchKernelGGL((eof_transpose_kernel<double, double>), dim3((unsigned)ceil_div(N, (int64_t)32), (unsigned)ceil_div(k, 32)), dim3(256), 0,
                        h->st, (const double*)(P.get() + j * plane), (const double*)nullptr, N, N, k, tmp.get());
     hipLaunchKernelGGL((map_finish_kernel<double>), ew_grid((int64_t)slice), dim3(EW_BLOCK), 0, h->st, (const double*)tmp.get(), 0,
-                       keep_idx ? (const int64_t*)row_of.get() : (const int64_t*)nullptr, N_full, k, (const double*)scale.get(),
+                       rows, N_full, k, (const double*)scale.get(),
                        (const double*)nullptr, (const double*)nullptr, (int)MAP_EOF, 0, out.get() + (size_t)j * slice);
   }
   XMCA_HIP(hipGetLastError());
@@ -1587,13 +1617,8 @@ void extended_reconstruct_impl(xmca_handle* h, int M, int tau, const int* modes,
   h->tm.end();
   P.ensure((size_t)kin * N);
   Narrow<TI> z;
-  z.from(h->st, Zsel.get(), nullptr, (int64_t)q * np);
   h->tm.begin("eeof_project");
-  for (int j = 0; j < M; ++j) {
-    GemmOpts o;
-    o.a_kfast = true; o.b_nfast = true;
-    gemm<TI, double>(h->st, h->gws, z.r, np, f.r() + (int64_t)j * tau * N, N, P.get() + (int64_t)j * q * N, N, q, (int)N, np, o);
-  }
+  lag_back_project<TI>(h, z, Zsel.get(), q, np, M, tau, f.r(), N, nullptr, P.get());
   h->tm.end();
   if (add_means) {
     h->tm.begin("eeof_window_means");
@@ -1736,10 +1761,7 @@ void fill_gaps_impl(xmca_handle* h, const TI* X, int T, int64_t N, int64_t n_pre
     h->tm.end();
     XMCA_CHECK(usable, XMCA_ERR_NUMERIC, "fill_gaps: the iterate has no variance");
     h->tm.begin("gap_project");
-    z.from(h->st, Zk, nullptr, (int64_t)k * T);
-    GemmOpts o;
-    o.a_kfast = true; o.b_nfast = true;
-    gemm<TI, double>(h->st, h->gws, z.r, T, (const TI*)A.get(), N, P.get(), N, k, (int)N, T, o);
+    lag_back_project<TI>(h, z, Zk, k, T, 1, 1, (const TI*)A.get(), N, nullptr, P.get());
     h->tm.end();
     h->tm.begin("gap_fill");
     gap_fill_step<TI>(h->st, A.get(), mask.get(), Zk, P.get(), T, N, k, part.get());
@@ -1814,6 +1836,7 @@ void gap_fill_step_impl(xmca_handle* h, const TI* A_in, const unsigned char* mas
   XMCA_HIP(hipStreamSynchronize(h->st));
 }
 
+// ---- bootstrapping: working copies on the device -----------------------------------------------------------------
 template <typename TI>
 void bootstrap_begin_impl(xmca_handle* h, int n_fields) {
   TypedState<TI>& ts = typed<TI>(h);
@@ -2281,14 +2304,7 @@ int xmca_get_maps_to(xmca_handle* h, int side, const double* W, int64_t m, int64
                  (kind == XMCA_MAP_AMPLITUDE && (scaling == XMCA_SCALE_NONE || scaling == XMCA_SCALE_MAX)) ||
                  (kind == XMCA_MAP_PHASE && scaling == XMCA_SCALE_NONE),
              XMCA_ERR_INVALID, "get_maps: EOFs scale by NONE / MAX / STD, amplitudes by NONE / MAX, phases not at all");
-  const int64_t N = h->res.ldv[side];
-  XMCA_CHECK(N_full >= N && N_full <= INT32_MAX && (keep_idx || N_full == N), XMCA_ERR_INVALID,
-             "get_maps: N_full must be the vectors' " + std::to_string(N) + " rows, or more with keep_idx");
-  if (keep_idx) {
-    for (int64_t c = 0; c < N; ++c)
-      XMCA_CHECK(keep_idx[c] >= 0 && keep_idx[c] < N_full && (c == 0 || keep_idx[c] > keep_idx[c - 1]), XMCA_ERR_INVALID,
-                 "get_maps: keep_idx must be increasing row indices below N_full, one per row of the vectors");
-  }
+  check_kept_columns("get_maps", keep_idx, h->res.ldv[side], N_full, INT32_MAX);      // (kept columns: the rows of the vectors)
   with_dtype(dtype, [&](auto t) {
     get_maps_impl<decltype(t)>(h, side, W, m, q, w_is_complex != 0, col_factor, factor_is_complex != 0, keep_idx, N_full, kind, scaling,
                                out, stat_out, out_location == XMCA_DEVICE);
@@ -2547,27 +2563,17 @@ int xmca_lag_gram(xmca_handle* h, const double* G, int64_t n, int embedding, int
 int xmca_extended_eofs(xmca_handle* h, int embedding, int tau, int n_modes, const int64_t* keep_idx, int64_t N_full, double* lam_out,
                        double* pcs_out, double* eofs_out) {
   API_BEGIN(h)
-  XMCA_CHECK(h->field_set[0], XMCA_ERR_STATE, "extended_eofs: no field set");
-  XMCA_CHECK(lam_out && pcs_out && eofs_out && embedding >= 1 && tau >= 1 && n_modes >= 1, XMCA_ERR_INVALID, "extended_eofs: bad arguments");
-  const int64_t T = resident_T(h), N = resident_N(h, 0);
-  bool has_im = false;
-  with_dtype(h->dtype, [&](auto t) { has_im = typed<decltype(t)>(h).f[0].has_im; });
-  XMCA_CHECK(!has_im && !h->op_pending, XMCA_ERR_INVALID, "extended_eofs: the resident field is complex (real fields only)");
-  check_operator_size("extended_eofs", T);
-  const int64_t np = T - (int64_t)(embedding - 1) * tau;
-  XMCA_CHECK(np >= 2, XMCA_ERR_INVALID, "extended_eofs: T - (embedding - 1) * tau must be at least 2");
+  // (the outputs and n_modes come before the embedding wherever a field is set, as ever: with a T above the operator's bound a
+  // missing output is INVALID, not UNSUPPORTED)
+  XMCA_CHECK(!h->field_set[0] || (lam_out && pcs_out && eofs_out && n_modes >= 1), XMCA_ERR_INVALID, "extended_eofs: bad arguments");
+  const int64_t np = check_lag_embedding(h, "extended_eofs", embedding, tau, 2);
+  const int64_t N = resident_N(h, 0);
   XMCA_CHECK(n_modes <= np - 1 && n_modes <= (int64_t)embedding * N, XMCA_ERR_INVALID,
              "extended_eofs: n_modes must not exceed min(T' - 1, embedding * N)");
   XMCA_CHECK(N < ((int64_t)1 << 31) && (int64_t)embedding * n_modes * std::max(N, N_full) < ((int64_t)1 << 40), XMCA_ERR_UNSUPPORTED,
              "extended_eofs: pattern array too large");
-  if (keep_idx) {
-    XMCA_CHECK(N_full >= N, XMCA_ERR_INVALID, "extended_eofs: N_full is below the number of kept points");
-    for (int64_t c = 0; c < N; ++c)
-      XMCA_CHECK(keep_idx[c] >= 0 && keep_idx[c] < N_full && (c == 0 || keep_idx[c] > keep_idx[c - 1]), XMCA_ERR_INVALID,
-                 "extended_eofs: keep_idx must be increasing row indices below N_full");
-  } else {
-    XMCA_CHECK(N_full == N, XMCA_ERR_INVALID, "extended_eofs: N_full must equal N without keep_idx");
-  }
+  // (no INT32_MAX bound on N_full here: this entry's size limits are the two above, which the assembly kernels index within)
+  check_kept_columns("extended_eofs", keep_idx, N, N_full, INT64_MAX);
   with_dtype(h->dtype, [&](auto t) {
     extended_eofs_impl<decltype(t)>(h, embedding, tau, n_modes, keep_idx, N_full, lam_out, pcs_out, eofs_out);
   });
@@ -2579,15 +2585,6 @@ int xmca_gap_fill_tile(int* rows_out, int* cols_out) {
   *rows_out = GAP_ROWS;
   *cols_out = GAP_COLS;
   return XMCA_OK;
-}
-
-// the plane of the gap entries: dtype, T x N within the eigensolver's and the kernels' index ranges
-void check_gap_plane(const char* what, int64_t T, int64_t N, int dtype) {
-  const std::string w(what);
-  XMCA_CHECK(dtype == XMCA_F32 || dtype == XMCA_F64, XMCA_ERR_INVALID, w + ": dtype must be XMCA_F32 or XMCA_F64");
-  XMCA_CHECK(T >= 1 && N >= 1, XMCA_ERR_INVALID, w + ": the field must have at least one row and one column");
-  check_operator_size(what, T);
-  XMCA_CHECK(N < ((int64_t)1 << 31) && T * N < ((int64_t)1 << 40), XMCA_ERR_UNSUPPORTED, w + ": field too large");
 }
 
 int xmca_fill_gaps(xmca_handle* h, const void* X, int64_t T, int64_t N, int dtype, const int64_t* cv_idx, int64_t n_cv, int n_modes,
@@ -2636,21 +2633,6 @@ int xmca_gap_fill_step(xmca_handle* h, const void* A, const unsigned char* mask,
   API_END(h)
 }
 
-// the resident field of side 0 and the embedding of the lag entries: a real field, embedding and tau >= 1, T' >= min_window
-int64_t check_lag_embedding(xmca_handle* h, const char* what, int embedding, int tau, int64_t min_window) {
-  const std::string w(what);
-  XMCA_CHECK(h->field_set[0], XMCA_ERR_STATE, w + ": no field set");
-  XMCA_CHECK(embedding >= 1 && tau >= 1, XMCA_ERR_INVALID, w + ": embedding and tau must be at least 1");
-  bool has_im = false;
-  with_dtype(h->dtype, [&](auto t) { has_im = typed<decltype(t)>(h).f[0].has_im; });
-  XMCA_CHECK(!has_im && !h->op_pending, XMCA_ERR_INVALID, w + ": the resident field is complex (real fields only)");
-  const int64_t T = resident_T(h);
-  check_operator_size(what, T);
-  const int64_t np = T - (int64_t)(embedding - 1) * tau;
-  XMCA_CHECK(np >= min_window, XMCA_ERR_INVALID, w + ": T - (embedding - 1) * tau must be at least " + std::to_string(min_window));
-  return np;
-}
-
 int xmca_extended_reconstruct(xmca_handle* h, int embedding, int tau, const int* modes, int n_sel, int add_means, const int64_t* keep_idx,
                               int64_t N_keep, int64_t N_full, const double* mean, const double* stdv, const double* inv_weight, double* out,
                               int out_location) {
@@ -2665,13 +2647,7 @@ int xmca_extended_reconstruct(xmca_handle* h, int embedding, int tau, const int*
     XMCA_CHECK(modes[c] >= 0 && modes[c] < most && (c == 0 || modes[c] > modes[c - 1]), XMCA_ERR_INVALID,
                "extended_reconstruct: modes must be increasing 0-based indices below min(T' - 1, embedding * N)");
   XMCA_CHECK(N_keep == N, XMCA_ERR_INVALID, "extended_reconstruct: N_keep must be the field's " + std::to_string(N) + " columns");
-  XMCA_CHECK(N_full >= N && N_full <= INT32_MAX && (keep_idx || N_full == N), XMCA_ERR_INVALID,
-             "extended_reconstruct: N_full must be N_keep, or more with keep_idx");
-  if (keep_idx) {
-    for (int64_t c = 0; c < N; ++c)
-      XMCA_CHECK(keep_idx[c] >= 0 && keep_idx[c] < N_full && (c == 0 || keep_idx[c] > keep_idx[c - 1]), XMCA_ERR_INVALID,
-                 "extended_reconstruct: keep_idx must be increasing column indices below N_full");
-  }
+  check_kept_columns("extended_reconstruct", keep_idx, N, N_full, INT32_MAX);
   const int64_t kin = (int64_t)embedding * (n_sel + 1);
   XMCA_CHECK(kin <= INT32_MAX && kin * std::max(N, T) < ((int64_t)1 << 40), XMCA_ERR_UNSUPPORTED,
              "extended_reconstruct: coefficient matrices too large");
@@ -2751,14 +2727,7 @@ int xmca_correlation_maps_to(xmca_handle* h, int side, const double* Y, int64_t 
   XMCA_CHECK(r_dtype == XMCA_F32 || r_dtype == XMCA_F64, XMCA_ERR_INVALID, "correlation_maps: r_dtype must be XMCA_F32 or XMCA_F64");
   check_out_location(h, "correlation_maps", out_location, r_out);
   check_out_location(h, "correlation_maps", out_location, p_out);
-  const int64_t N = resident_N(h, side);
-  XMCA_CHECK(N_full >= N && N_full <= INT32_MAX && (keep_idx || N_full == N), XMCA_ERR_INVALID,
-             "correlation_maps: N_full must be the field's " + std::to_string(N) + " columns, or more with keep_idx");
-  if (keep_idx) {
-    for (int64_t c = 0; c < N; ++c)
-      XMCA_CHECK(keep_idx[c] >= 0 && keep_idx[c] < N_full && (c == 0 || keep_idx[c] > keep_idx[c - 1]), XMCA_ERR_INVALID,
-                 "correlation_maps: keep_idx must be increasing row indices below N_full, one per column of the field");
-  }
+  check_kept_columns("correlation_maps", keep_idx, resident_N(h, side), N_full, INT32_MAX);
   with_dtype(h->dtype, [&](auto t) {
     with_dtype(r_dtype, [&](auto tr) {
       correlation_maps_impl<decltype(t), decltype(tr)>(h, side, Y, T, m, keep_idx, N_full, static_cast<decltype(tr)*>(r_out), p_out,
