@@ -463,6 +463,39 @@ int xmca_lag_expand(xmca_handle* h, const double* Z, int q, int Tp, int embeddin
                     double* inv_count_out);
 int xmca_lag_window_means(xmca_handle* h, int embedding, int tau, double* means_out);
 
+/* Monte-Carlo SSA test of extended EOFs (Allen & Smith 1996; an extension; entry points added to ABI 15 - no existing
+ * signature changes).  Notation as above; H Y = U S V^T, lambda_k = s_k^2, v_k = Y^T u_k / s_k the unit-norm patterns of
+ * xmca_extended_eofs.  For a surrogate field R (T x N) with the embedded matrix Y_R, the statistic of mode k is
+ * Lambda_k(R) = || H Y_R v_k ||^2: with V_j (N x n_modes) the lag-j patterns and W = R [V_0 | ... | V_{M-1}] (T x M n_modes, one
+ * thin product over the whole surrogate), Q[t][c] = sum_{j < M} W[t + j tau][j n_modes + c] and Lambda_c = sum_t (Q[t][c] -
+ * mean_t Q[.][c])^2 (csrc/lag_project.h).  Neither Y_R nor a T x T matrix is formed, and no surrogate is decomposed.
+ * Lambda_k(X) = lambda_k.  The null is one AR(1) series per column: column c of R is the unit-variance series of
+ * xmca_surrogate_ar1 - the same generator, segments and key (seed, run, side = 0) - times d_c, the sample standard deviation
+ * (ddof = 1) of column c of the resident field; d is folded into the patterns once (W = R (diag(d) V)), the surrogate is never
+ * rescaled.  No bias correction of phi or d is applied.
+ *   xmca_extended_rule_n   the front of xmca_extended_eofs and its patterns once, then for every run of [run_begin, run_end): the
+ *                       surrogate in a buffer of the call's own, the product, the projection; the values stay on the device until
+ *                       the one download at the end.
+ *     phi               N host float64, every one finite with |phi| < 1 (checked before anything is launched)
+ *     lam_out           T' float64: all eigenvalues of K_c, descending (those of xmca_extended_eofs)
+ *     scale_out         N float64: d_c
+ *     surrogates_out    (run_end - run_begin) x n_modes float64, row-major: Lambda_c of every run
+ *                       Errors as xmca_extended_eofs, and XMCA_ERR_INVALID for a bad run range or phi.  The call works in buffers
+ *                       of its own: a resident field, the result of a solve, its rotation and a back-projection tail are left as
+ *                       they are.  Stage timers: those of xmca_extended_eofs up to "eeof_project", then "mcssa_scale",
+ *                       "mcssa_surrogate", "mcssa_gemm", "mcssa_project".  No sum uses an atomic: a call repeats its bits, and a
+ *                       run's values do not depend on the range it is part of.
+ *   xmca_extended_project  (tests) the same front and the same scale, product and projection kernels applied to the host T x N
+ *                       float64 field R, narrowed to the resident field's dtype: out (n_modes) = Lambda_c(R), with d folded in
+ *                       when apply_scale != 0.  R = the field and apply_scale == 0 give lambda_c.
+ *   xmca_lag_project    (tests) the projection kernels alone on a host T x embedding k float64 matrix W: out (k) = Lambda_c.
+ *   xmca_lag_project_tile  (no device) rows and columns of Q one workgroup of the projection kernels handles. */
+int xmca_extended_rule_n(xmca_handle* h, int embedding, int tau, int n_modes, const double* phi, int64_t run_begin, int64_t run_end,
+                         uint64_t seed, double* lam_out, double* scale_out, double* surrogates_out);
+int xmca_extended_project(xmca_handle* h, int embedding, int tau, int n_modes, const double* R, int apply_scale, double* out);
+int xmca_lag_project(xmca_handle* h, const double* W, int64_t T, int embedding, int tau, int k, double* out);
+int xmca_lag_project_tile(int* rows_out, int* cols_out);
+
 /* DINEOF gap filling of one real field (an extension; entry points added to ABI 15 - no existing signature changes).
  * X is T x N in `dtype`, NaN marks a missing value.  Every column is centred over its present values (float64 sums in a fixed
  * order), missing entries start at 0 and are replaced, iteration after iteration, by the truncated reconstruction of the plane A:

@@ -71,6 +71,10 @@ SIGNATURES = {
     "xmca_extended_reconstruct": (_c_int, [_vp, _c_int, _c_int, _vp, _c_int, _c_int, _vp, _c_i64, _c_i64, _vp, _vp, _vp, _vp, _c_int]),
     "xmca_lag_expand": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp]),
     "xmca_lag_window_means": (_c_int, [_vp, _c_int, _c_int, _vp]),
+    "xmca_extended_rule_n": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _c_i64, _c_i64, ctypes.c_uint64, _vp, _vp, _vp]),
+    "xmca_extended_project": (_c_int, [_vp, _c_int, _c_int, _c_int, _vp, _c_int, _vp]),
+    "xmca_lag_project": (_c_int, [_vp, _vp, _c_i64, _c_int, _c_int, _c_int, _vp]),
+    "xmca_lag_project_tile": (_c_int, [_ip, _ip]),
     "xmca_fill_gaps": (_c_int, [_vp, _vp, _c_i64, _c_i64, _c_int, _vp, _c_i64, _c_int, _c_int, _c_dbl, _vp, _vp, _ip, _dp, _vp]),
     "xmca_gap_center": (_c_int, [_vp, _vp, _c_i64, _c_i64, _c_int, _vp, _vp, _vp, _dp]),
     "xmca_gap_fill_step": (_c_int, [_vp, _vp, _vp, _vp, _vp, _c_i64, _c_i64, _c_int, _c_int, _vp, _dp]),
@@ -230,6 +234,14 @@ def pattern_tile():
 def lag_gram_tile():
     """Output tile edge of the lag-sum kernel of `extended_eofs` (xmca_lag_gram_tile; no device): a constant of the build."""
     return int(load_library().xmca_lag_gram_tile())
+
+
+def lag_project_tile():
+    """(rows, columns) of Q one workgroup of the projection kernels of `extended_rule_n` handles (xmca_lag_project_tile; no
+    device): constants of the build."""
+    rows, cols = _c_int(0), _c_int(0)
+    load_library().xmca_lag_project_tile(ctypes.byref(rows), ctypes.byref(cols))
+    return int(rows.value), int(cols.value)
 
 
 def gap_fill_tile():
@@ -1064,6 +1076,58 @@ class Handle:
         eofs = np.empty((M, N_full, k), dtype=np.float64)
         self._check(self._lib.xmca_extended_eofs(self._h, M, tau, k, _ptr(idx), N_full, _ptr(lam), _ptr(pcs), _ptr(eofs)))
         return lam, pcs, eofs
+
+    @staticmethod
+    def _lag_modes(what, T, N, embedding, tau, n_modes):
+        """(M, tau, k, T') of the Monte-Carlo SSA entries, with the argument rules of `extended_eofs`."""
+        M, tau, k = int(embedding), int(tau), int(n_modes)
+        n_out = int(T) - (M - 1) * tau
+        if M < 1 or tau < 1 or n_out < 2 or not 1 <= k <= min(n_out - 1, M * int(N)):
+            raise ValueError("%s: embedding, tau >= 1, T' >= 2 and 1 <= n_modes <= min(T' - 1, embedding * N) are needed" % what)
+        return M, tau, k, n_out
+
+    def extended_rule_n(self, T, N, embedding, tau, n_modes, phi, run_begin, run_end, seed):
+        """Monte-Carlo SSA test of the extended EOFs of the resident real T x N field of side 0 (xmca_extended_rule_n): (lam, scale,
+        surrogates) - all T' eigenvalues of `extended_eofs`; the N column standard deviations d (ddof = 1); Lambda of the runs
+        [run_begin, run_end), (runs, n_modes).  phi: N values, every one finite with |phi| < 1.  All float64.  The result of a
+        solve and the fields stay as they are."""
+        M, tau, k, n_out = self._lag_modes("extended_rule_n", T, N, embedding, tau, n_modes)
+        phi = np.ascontiguousarray(phi, dtype=np.float64)
+        run_begin, run_end = int(run_begin), int(run_end)
+        if phi.shape != (int(N),):
+            raise ValueError("extended_rule_n: phi must hold one value per column (%d), got shape %s" % (N, phi.shape))
+        if not 0 <= run_begin <= run_end:
+            raise ValueError("extended_rule_n: the runs must be a range [run_begin, run_end) with 0 <= run_begin <= run_end")
+        lam = np.empty(n_out, dtype=np.float64)
+        scale = np.empty(int(N), dtype=np.float64)
+        surrogates = np.empty((run_end - run_begin, k), dtype=np.float64)
+        self._check(self._lib.xmca_extended_rule_n(self._h, M, tau, k, _ptr(phi), run_begin, run_end, int(seed), _ptr(lam), _ptr(scale),
+                                                   _ptr(surrogates)))
+        return lam, scale, surrogates
+
+    def extended_project(self, T, N, embedding, tau, n_modes, R, apply_scale):
+        """(tests) Lambda_c(R) of the host T x N field `R` on the extended EOFs of the resident field of side 0
+        (xmca_extended_project): n_modes float64 values from the front, scale, product and projection kernels of `extended_rule_n`;
+        `apply_scale` multiplies column c of R by the resident field's standard deviation d_c."""
+        M, tau, k, _ = self._lag_modes("extended_project", T, N, embedding, tau, n_modes)
+        R = np.ascontiguousarray(R, dtype=np.float64)
+        if R.shape != (int(T), int(N)):
+            raise ValueError("extended_project: R must be the field's shape (%d, %d), got %s" % (T, N, R.shape))
+        out = np.empty(k, dtype=np.float64)
+        self._check(self._lib.xmca_extended_project(self._h, M, tau, k, _ptr(R), int(bool(apply_scale)), _ptr(out)))
+        return out
+
+    def lag_project(self, W, embedding, tau, k):
+        """(tests) The projection kernels of `extended_rule_n` on a host matrix (xmca_lag_project): from the T x embedding k float64
+        `W`, Q[t, c] = sum_j W[t + j tau, j k + c] over the T' = T - (embedding - 1) tau windows and the k sums of squares of its
+        centred columns."""
+        W = np.ascontiguousarray(W, dtype=np.float64)
+        M, tau, k = int(embedding), int(tau), int(k)
+        if M < 1 or tau < 1 or k < 1 or W.ndim != 2 or W.shape[1] != M * k or W.shape[0] - (M - 1) * tau < 1:
+            raise ValueError("lag_project: W must be T x embedding k with embedding, tau, k >= 1 and (embedding - 1) * tau below T")
+        out = np.empty(k, dtype=np.float64)
+        self._check(self._lib.xmca_lag_project(self._h, _ptr(W), W.shape[0], M, tau, k, _ptr(out)))
+        return out
 
     def fill_gaps(self, X, n_modes, max_iter, tol, cv_idx=None):
         """DINEOF gap filling of the T x N float32 / float64 field `X` with NaN gaps (xmca_fill_gaps): (field, history, cv_rms, lam) -

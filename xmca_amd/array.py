@@ -1775,6 +1775,57 @@ class MCA:
                 'pcs': pcs,
                 'eofs': {key: eofs.reshape((M,) + tuple(self._fields_spatial_shape[key]) + (k,))}}
 
+    def extended_rule_n(self, embedding, tau=1, n_runs=100, n_modes=10, seed=None, phi=None):
+        """Monte-Carlo SSA test (Allen & Smith 1996) of the modes of `extended_eofs(embedding, tau, n_modes)` against red noise: which
+        modes, and above all which oscillatory pair, carry more variance than AR(1) noise would put there (an extension;
+        DESIGN.md 2.17).
+
+        With Y_c = U S V^H the centred embedded matrix of `extended_eofs` and lambda_k = s_k^2, every run draws a surrogate field R
+        from the null, embeds it like the data (Y_R, every column centred over its T' rows) and projects it on the DATA's patterns:
+        Lambda_k(R) = ||Y_R,c v_k||^2, to be compared with lambda_k = Lambda_k(X).  No surrogate is decomposed and Y_R is never
+        formed: per run the device generates R, forms W = R [V_0 | ... | V_{M-1}] with one thin product and sums M row-shifted
+        column blocks of W.
+
+        The null: column c of R is an AR(1) series with the lag-1 autocorrelation phi_c and the sample standard deviation
+        (ddof = 1) of column c of the field as `solve()` sees it - the generator, segments and key (seed, run) of
+        `rule_n(noise='ar1')`.  Unlike `rule_n`, whose surrogates have a (white) column for every masked grid point too, these have
+        the kept columns only: a masked point has no pattern and takes no part.  No bias correction is applied to phi or to the
+        variance (both are biased low in short records); pass corrected values as `phi`.  `phi`: None - estimated from the field
+        (the values of `lag1_autocorrelation()`); else as in `rule_n`: a scalar or an array in the field's spatial shape, flat over
+        all grid points, or flat over the kept ones.  `seed` as in `rule_n`.
+
+        Returns a dict of float64 numpy arrays: 'singular_values' (n_modes,): lambda / (T' - 1), those of `extended_eofs`;
+        'surrogates' (n_modes, n_runs): Lambda / (T' - 1);  'exceedance' (n_modes,): the share of runs with Lambda_k(R) >= lambda_k;
+        'phi' and 'scale': the null's parameters in the field's spatial shape, NaN at masked points.
+
+        A prior `solve()` is not needed; a solved (and rotated) model keeps its result.  Repeated calls with one seed return the
+        same bits.  Under an initialised `torch.distributed` group every rank computes everything: nothing is sharded and no
+        collective is called.  ValueError: the argument rules of `extended_eofs`, `n_runs` not an integer >= 1, a `phi` that
+        `rule_n` would refuse."""
+        M, tau, key, T, n_kept, n_win, most = self._lag_window(
+            'extended_rule_n', embedding, tau,
+            None if _is_int(n_modes) else '`n_modes` must be an integer >= 1, not {!r}'.format(n_modes))
+        k = int(n_modes)
+        if not 1 <= k <= most:
+            raise ValueError('`n_modes` must be an integer between 1 and min(T\' - 1, embedding * N) = {:}, not {!r}'.format(most, n_modes))
+        if not _is_int(n_runs) or n_runs < 1:
+            raise ValueError('`n_runs` must be an integer >= 1, not {!r}'.format(n_runs))
+        keep = np.asarray(self._no_nan_index[key], dtype=bool)
+        phi_kept = None if phi is None else self._phi_columns(phi)[0][keep]
+        if seed is None:
+            seed = int(np.random.randint(0, 2 ** 31 - 1)) * 2 ** 31 + int(np.random.randint(0, 2 ** 31 - 1))
+        dev = self._resident_device()
+        if phi_kept is None:
+            phi_kept = dev.lag1_autocorrelation(0, n_kept)
+        lam, scale, runs = dev.extended_rule_n(T, n_kept, M, tau, k, phi_kept, 0, int(n_runs), seed)
+        shape = tuple(self._fields_spatial_shape[key])
+        svals, null = lam[:k] / (n_win - 1), np.ascontiguousarray(runs.T) / (n_win - 1)
+        return {'singular_values': svals,
+                'surrogates': null,
+                'exceedance': np.mean(null >= svals[:, None], axis=1),
+                'phi': self._with_nan_columns(key, np.asarray(phi_kept, dtype=np.float64), ()).reshape(shape),
+                'scale': self._with_nan_columns(key, scale, ()).reshape(shape)}
+
     def extended_reconstruct(self, embedding, tau=1, mode=None, original_scale=True):
         """Reconstructed component (RC) of a group of extended EOF modes: the part of the field, on its own T time steps and its own
         grid, that the chosen modes of `extended_eofs(embedding, tau)` carry (an extension) - the M-SSA counterpart

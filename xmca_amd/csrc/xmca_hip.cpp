@@ -15,6 +15,7 @@
 #include "theta.h"
 #include "boot_patterns.h"
 #include "lag_gram.h"
+#include "lag_project.h"
 #include "lag_reconstruct.h"
 #include "gap_fill.h"
 
@@ -1529,6 +1530,40 @@ void eeof_leading_vectors(xmca_handle* h, const char* what, int M, int tau, int 
   XMCA_CHECK(std::isfinite(w.lam[0]) && w.lam[0] > 0.0, XMCA_ERR_NUMERIC, std::string(what) + ": the field has no variance (or holds NaN)");
 }
 
+// The patterns of the k leading modes of a front, shared by xmca_extended_eofs and the Monte-Carlo SSA entries: P (M planes of
+// k x N, row c of plane j the lag-j pattern of mode c) and scale (k values: P times scale has unit norm over lags x points and
+// the sign of the sign rule).  Stage timer "eeof_project".  The buffers, and the host values on their way up, live as long as the
+// struct: the caller keeps it until it has synchronised the stream.
+template <typename TI>
+struct EeofPatterns {
+  std::vector<double> inv;
+  DevBuf<double> inv_dev, P, scale;
+  Narrow<TI> z;
+};
+
+template <typename TI>
+void eeof_patterns(xmca_handle* h, const EeofFront& front, int M, int tau, int k, EeofPatterns<TI>& w) {
+  const FieldData<TI>& f = typed<TI>(h).f[0];
+  const int np = (int)f.T - (M - 1) * tau;
+  const int64_t N = f.N, plane = (int64_t)k * N;
+  const std::vector<double>& lam = front.lam;
+  // 1 / sigma_c rides in the epilogue for the modes clear of the Gram matrix's rounding noise (the cuts of the one-field solve);
+  // the others are divided by their measured norm afterwards (eeof_sign_norm_kernel)
+  const double cut = (std::is_same<TI, float>::value ? 1e-4 : 1e-6) * lam[0];
+  std::vector<double>& inv = w.inv;
+  inv.assign((size_t)k, 1.0);
+  int known = 0;
+  while (known < k && lam[(size_t)known] > cut) { inv[(size_t)known] = 1.0 / std::sqrt(lam[(size_t)known]); ++known; }
+  XMCA_HIP(hipMemcpyAsync(w.inv_dev.ensure((size_t)k), inv.data(), sizeof(double) * k, hipMemcpyHostToDevice, h->st));
+  w.P.ensure((size_t)M * plane);
+  h->tm.begin("eeof_project");
+  lag_back_project<TI>(h, w.z, front.Z.get(), k, np, M, tau, f.r(), N, w.inv_dev.get(), w.P.get());
+  hipLaunchKernelGGL(eeof_sign_norm_kernel, dim3((unsigned)k), dim3(256), 0, h->st, (const double*)w.P.get(), plane, N, N, M, known,
+                     w.scale.ensure((size_t)k));
+  XMCA_HIP(hipGetLastError());
+  h->tm.end();
+}
+
 // xmca_extended_eofs on the resident real field of side 0: Gram matrix, lag sum and double centring (csrc/lag_gram.h),
 // the k leading eigenvectors of the T' x T' matrix, one back-projection per lag on a row-offset view of the field with 1 / sigma_c
 // in the epilogue, sign, and the (M, N_full, k) layout by the transposition and scatter kernels of xmca_get_maps.  Every buffer is
@@ -1543,25 +1578,14 @@ void extended_eofs_impl(xmca_handle* h, int M, int tau, int k, const int64_t* ke
   eeof_leading_vectors<TI>(h, "extended_eofs", M, tau, k, front);
   const std::vector<double>& lam = front.lam;
   DevBuf<double>& Z = front.Z;
-  DevBuf<double> inv_dev, P, scale, tmp, out;
+  EeofPatterns<TI> pat;
+  DevBuf<double> tmp, out;
   DevBuf<int64_t> row_of;
-  // 1 / sigma_c rides in the epilogue for the modes clear of the Gram matrix's rounding noise (the cuts of the one-field solve);
-  // the others are divided by their measured norm afterwards (eeof_sign_norm_kernel)
-  const double cut = (std::is_same<TI, float>::value ? 1e-4 : 1e-6) * lam[0];
-  std::vector<double> inv((size_t)k, 1.0);
-  int known = 0;
-  while (known < k && lam[(size_t)known] > cut) { inv[(size_t)known] = 1.0 / std::sqrt(lam[(size_t)known]); ++known; }
-  XMCA_HIP(hipMemcpyAsync(inv_dev.ensure((size_t)k), inv.data(), sizeof(double) * k, hipMemcpyHostToDevice, h->st));
   const int64_t* rows = upload_inverse_map(h, keep_idx, N, N_full, row_of);
-  Narrow<TI> z;
   const int64_t plane = (int64_t)k * N;
-  P.ensure((size_t)M * plane);
-  h->tm.begin("eeof_project");
-  lag_back_project<TI>(h, z, Z.get(), k, np, M, tau, f.r(), N, inv_dev.get(), P.get());
-  hipLaunchKernelGGL(eeof_sign_norm_kernel, dim3((unsigned)k), dim3(256), 0, h->st, (const double*)P.get(), plane, N, N, M, known,
-                     scale.ensure((size_t)k));
-  XMCA_HIP(hipGetLastError());
-  h->tm.end();
+  eeof_patterns<TI>(h, front, M, tau, k, pat);
+  DevBuf<double>& P = pat.P;
+  DevBuf<double>& scale = pat.scale;
   h->tm.begin("eeof_assemble");
   const size_t slice = (size_t)N_full * k;
   tmp.ensure((size_t)N * k);
@@ -1650,6 +1674,110 @@ void lag_window_means_impl(xmca_handle* h, int M, int tau, double* means_out) {
   lag_window_means<TI>(h->st, f.r(), (int)f.T, f.N, M, tau, means.ensure((size_t)M * f.N), table, part);
   h->tm.end();
   XMCA_HIP(hipMemcpyAsync(means_out, means.get(), sizeof(double) * (size_t)M * f.N, hipMemcpyDeviceToHost, h->st));
+  XMCA_HIP(hipStreamSynchronize(h->st));
+}
+
+// ---- Monte-Carlo SSA test of extended EOFs (csrc/lag_project.h) ---------------------------------------------
+// What one xmca_extended_rule_n / xmca_extended_project call keeps on the device: the front and the patterns of
+// xmca_extended_eofs, the column scale d, the GEMM's B operand (the unit-norm patterns, times d where asked) and the scratch of
+// one projection.  Every buffer is this call's own: the result of a solve, its vectors and the field planes are only read.
+template <typename TI>
+struct McssaState {
+  EeofFront front;
+  EeofPatterns<TI> pat;
+  DevBuf<double> d, col_part, col_dev, W, Q, part;
+  DevBuf<TI> B;
+  int T = 0, M = 0, tau = 0, k = 0;
+  int64_t N = 0;
+
+  void begin(xmca_handle* h, const char* what, int M_, int tau_, int k_, bool apply_scale) {
+    const FieldData<TI>& f = typed<TI>(h).f[0];
+    T = (int)f.T; N = f.N; M = M_; tau = tau_; k = k_;
+    eeof_leading_vectors<TI>(h, what, M, tau, k, front);
+    eeof_patterns<TI>(h, front, M, tau, k, pat);
+    h->tm.begin("mcssa_scale");
+    lag_column_scale<TI>(h->st, f.r(), T, N, d.ensure((size_t)N), col_part, col_dev);
+    const int64_t total = (int64_t)M * k * N;
+    hipLaunchKernelGGL((lagp_scale_patterns_kernel<TI>), ew_grid(total), dim3(EW_BLOCK), 0, h->st, (const double*)pat.P.get(),
+                       (const double*)pat.scale.get(), (const double*)(apply_scale ? d.get() : nullptr), k, N, total,
+                       B.ensure((size_t)total));
+    XMCA_HIP(hipGetLastError());
+    h->tm.end();
+    const int np = T - (M - 1) * tau;
+    W.ensure((size_t)T * M * k);
+    Q.ensure((size_t)np * k);
+    part.ensure(lag_project_scratch(np, k));
+  }
+
+  // Lambda of the T x N plane R (k values at `out`, on the device), queued on the handle's stream: W = R B^T, then the shift sum,
+  // the centring and the squares
+  void project(xmca_handle* h, const TI* R, double* out) {
+    h->tm.begin("mcssa_gemm");
+    GemmOpts o;
+    o.a_kfast = true; o.b_nfast = false;
+    gemm<TI, double>(h->st, h->gws, R, N, (const TI*)B.get(), N, W.get(), (int64_t)M * k, T, M * k, (int)N, o);
+    h->tm.end();
+    h->tm.begin("mcssa_project");
+    lag_project(h->st, W.get(), T, M, tau, k, Q.get(), part.get(), out);
+    h->tm.end();
+  }
+};
+
+// xmca_extended_rule_n: runs [run_begin, run_end) of the test.  phi: N values on the host, checked by the caller.
+template <typename TI>
+void extended_rule_n_impl(xmca_handle* h, int M, int tau, int k, const double* phi, int64_t run_begin, int64_t run_end, uint64_t seed,
+                          double* lam_out, double* scale_out, double* surrogates_out) {
+  McssaState<TI> s;
+  s.begin(h, "extended_rule_n", M, tau, k, true);
+  const int64_t n_runs = run_end - run_begin, n = (int64_t)s.T * s.N;
+  DevBuf<TI> R;
+  DevBuf<double> phi_dev, carry, lam_dev;
+  XMCA_HIP(hipMemcpyAsync(phi_dev.ensure((size_t)s.N), phi, sizeof(double) * s.N, hipMemcpyHostToDevice, h->st));
+  XMCA_HIP(hipStreamSynchronize(h->st));          // (phi is the caller's)
+  if (n_runs > 0) {
+    R.ensure((size_t)n);
+    lam_dev.ensure((size_t)(n_runs * k));
+  }
+  for (int64_t r = 0; r < n_runs; ++r) {
+    h->tm.begin("mcssa_surrogate");
+    hipLaunchKernelGGL((philox_normal_kernel<TI>), ew_grid((n + 1) / 2), dim3(EW_BLOCK), 0, h->st, R.get(), n, seed,
+                       (uint32_t)(run_begin + r), (uint32_t)0);
+    ar1_filter<TI>(h->st, R.get(), s.T, s.N, phi_dev.get(), carry);
+    XMCA_HIP(hipGetLastError());
+    h->tm.end();
+    s.project(h, R.get(), lam_dev.get() + r * k);
+  }
+  if (n_runs > 0)
+    XMCA_HIP(hipMemcpyAsync(surrogates_out, lam_dev.get(), sizeof(double) * (size_t)(n_runs * k), hipMemcpyDeviceToHost, h->st));
+  XMCA_HIP(hipMemcpyAsync(scale_out, s.d.get(), sizeof(double) * (size_t)s.N, hipMemcpyDeviceToHost, h->st));
+  XMCA_HIP(hipStreamSynchronize(h->st));
+  std::memcpy(lam_out, s.front.lam.data(), sizeof(double) * (size_t)(s.T - (M - 1) * tau));
+}
+
+// (tests) xmca_extended_project: the same front, scale, GEMM and projection kernels on a field of the caller's
+template <typename TI>
+void extended_project_impl(xmca_handle* h, int M, int tau, int k, const double* R_host, bool apply_scale, double* out) {
+  McssaState<TI> s;
+  s.begin(h, "extended_project", M, tau, k, apply_scale);
+  const size_t n = (size_t)s.T * (size_t)s.N;
+  HostPlanes<TI> R;
+  DevBuf<double> lam_dev;
+  upload_planes<TI>(h, R_host, n, false, R);
+  s.project(h, R.r, lam_dev.ensure((size_t)k));
+  XMCA_HIP(hipMemcpyAsync(out, lam_dev.get(), sizeof(double) * (size_t)k, hipMemcpyDeviceToHost, h->st));
+  XMCA_HIP(hipStreamSynchronize(h->st));
+}
+
+// (tests) xmca_lag_project: the projection kernels alone on a host matrix
+inline void lag_project_impl(xmca_handle* h, const double* W_host, int T, int M, int tau, int k, double* out) {
+  const int np = T - (M - 1) * tau;
+  const size_t nw = (size_t)T * M * k;
+  DevBuf<double> W, Q, part, lam_dev;
+  XMCA_HIP(hipMemcpyAsync(W.ensure(nw), W_host, sizeof(double) * nw, hipMemcpyHostToDevice, h->st));
+  h->tm.begin("mcssa_project");
+  lag_project(h->st, W.get(), T, M, tau, k, Q.ensure((size_t)np * k), part.ensure(lag_project_scratch(np, k)), lam_dev.ensure((size_t)k));
+  h->tm.end();
+  XMCA_HIP(hipMemcpyAsync(out, lam_dev.get(), sizeof(double) * (size_t)k, hipMemcpyDeviceToHost, h->st));
   XMCA_HIP(hipStreamSynchronize(h->st));
 }
 
@@ -2685,6 +2813,58 @@ int xmca_lag_window_means(xmca_handle* h, int embedding, int tau, double* means_
   XMCA_CHECK(means_out && resident_N(h, 0) < ((int64_t)1 << 31), XMCA_ERR_INVALID, "lag_window_means: bad arguments");
   with_dtype(h->dtype, [&](auto t) { lag_window_means_impl<decltype(t)>(h, embedding, tau, means_out); });
   API_END(h)
+}
+
+// the checks of xmca_extended_eofs that the Monte-Carlo SSA entries share (its errors, in its order)
+static void check_mcssa(xmca_handle* h, const char* what, bool outputs, int embedding, int tau, int n_modes) {
+  const std::string w(what);
+  XMCA_CHECK(!h->field_set[0] || (outputs && n_modes >= 1), XMCA_ERR_INVALID, w + ": bad arguments");
+  const int64_t np = check_lag_embedding(h, what, embedding, tau, 2);
+  const int64_t T = resident_T(h), N = resident_N(h, 0);
+  XMCA_CHECK(n_modes <= np - 1 && n_modes <= (int64_t)embedding * N, XMCA_ERR_INVALID,
+             w + ": n_modes must not exceed min(T' - 1, embedding * N)");
+  XMCA_CHECK(N < ((int64_t)1 << 31) && (int64_t)embedding * n_modes * std::max(N, T) < ((int64_t)1 << 40) &&
+                 (int64_t)embedding * n_modes <= INT32_MAX,
+             XMCA_ERR_UNSUPPORTED, w + ": pattern array too large");
+}
+
+int xmca_extended_rule_n(xmca_handle* h, int embedding, int tau, int n_modes, const double* phi, int64_t run_begin, int64_t run_end,
+                         uint64_t seed, double* lam_out, double* scale_out, double* surrogates_out) {
+  API_BEGIN(h)
+  check_mcssa(h, "extended_rule_n", lam_out && scale_out && surrogates_out, embedding, tau, n_modes);
+  XMCA_CHECK(run_begin >= 0 && run_end >= run_begin && run_end <= (int64_t)UINT32_MAX && (run_end - run_begin) * n_modes < ((int64_t)1 << 34),
+             XMCA_ERR_INVALID, "extended_rule_n: bad run range");
+  check_phi("extended_rule_n", phi, resident_N(h, 0));
+  with_dtype(h->dtype, [&](auto t) {
+    extended_rule_n_impl<decltype(t)>(h, embedding, tau, n_modes, phi, run_begin, run_end, seed, lam_out, scale_out, surrogates_out);
+  });
+  h->tm.collect();
+  API_END(h)
+}
+
+int xmca_extended_project(xmca_handle* h, int embedding, int tau, int n_modes, const double* R, int apply_scale, double* out) {
+  API_BEGIN(h)
+  check_mcssa(h, "extended_project", R && out, embedding, tau, n_modes);
+  with_dtype(h->dtype, [&](auto t) { extended_project_impl<decltype(t)>(h, embedding, tau, n_modes, R, apply_scale != 0, out); });
+  API_END(h)
+}
+
+int xmca_lag_project(xmca_handle* h, const double* W, int64_t T, int embedding, int tau, int k, double* out) {
+  API_BEGIN(h)
+  XMCA_CHECK(W && out && T >= 1 && embedding >= 1 && tau >= 1 && k >= 1, XMCA_ERR_INVALID, "lag_project: bad arguments");
+  check_operator_size("lag_project", T);
+  XMCA_CHECK(T - (int64_t)(embedding - 1) * tau >= 1, XMCA_ERR_INVALID, "lag_project: (embedding - 1) * tau must be below T");
+  XMCA_CHECK((int64_t)embedding * k <= INT32_MAX && (int64_t)embedding * k * T < ((int64_t)1 << 34), XMCA_ERR_UNSUPPORTED,
+             "lag_project: matrix too large");
+  lag_project_impl(h, W, (int)T, embedding, tau, k, out);
+  API_END(h)
+}
+
+int xmca_lag_project_tile(int* rows_out, int* cols_out) {
+  if (!rows_out || !cols_out) return XMCA_ERR_INVALID;
+  *rows_out = LAGP_ROWS;
+  *cols_out = LAGP_COLS;
+  return XMCA_OK;
 }
 
 int xmca_correlate(xmca_handle* h, int side, const double* Y, int64_t T, int64_t m, double* r_out) {

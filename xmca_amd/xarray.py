@@ -289,6 +289,10 @@ class xMCA(MCA):
                                   name=' '.join([self._field_names[key], 'extended pcs']), attrs=self._attrs())
         return out
 
+    def extended_rule_n(self, embedding, tau=1, n_runs=100, n_modes=10, seed=None, phi=None):
+        """`MCA.extended_rule_n`; the dict of numpy arrays is passed through as it is."""
+        return super().extended_rule_n(embedding, tau=tau, n_runs=n_runs, n_modes=n_modes, seed=seed, phi=phi)
+
     def extended_reconstruct(self, embedding, tau=1, mode=None, original_scale=True):
         """`MCA.extended_reconstruct` as DataArrays over the field's own dims and coordinates, like `reconstructed_fields`; with
         `original_scale` the coslat weights are taken out on the device."""
