@@ -94,8 +94,8 @@ def trace_workload(what):
         h.lag1_autocorrelation(0, N)
 
 
-KERNELS = ("philox_normal_kernel", "ar1_carry_kernel", "ar1_filter_kernel", "lag1_partial_kernel", "lag1_finish_kernel",
-           "column_partial_sums_kernel")
+KERNELS = ("philox_normal_kernel", "ar1_carry_kernel", "ar1_filter_kernel", "Lag1Partial", "Lag1Finish",
+           "ColumnPartialSums")          # (the last three: functors of column_pass_kernel / column_finish_kernel)
 
 
 def kernel_stats(path, out, label):

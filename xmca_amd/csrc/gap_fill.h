@@ -13,60 +13,49 @@ constexpr int GAP_COLS = 256;                    // columns of a fill tile: one 
 constexpr int GAP_ROWS = 64;                     // rows of a fill tile (xmca_gap_fill_tile), walked in pieces of GAP_SUB
 constexpr int GAP_SUB = 16;                      // rows whose Z values are staged at a time
 constexpr int GAP_KC = 16;                       // modes a lane holds of its column of P at a time
-constexpr int GAP_CHUNKS = 32;                   // partial sums per column of the centring
 constexpr double GAP_POLISH_MIN_GAP = 1e-10;     // x lam[0]: pairs across the cut closer than this are left alone by the polish
 static_assert(GAP_COLS == GAP_KC * GAP_SUB, "the fill kernel stages one Z value per lane");
 static_assert(GAP_ROWS % GAP_SUB == 0, "a fill tile is a whole number of staged pieces");
 
-static inline int gap_chunks(int T) { return T < GAP_CHUNKS ? T : GAP_CHUNKS; }
-
-// Sum and count of the finite entries of column n over the rows of chunk blockIdx.y, rows ascending: psum / pcnt[chunk * N + n]
+// Sum and count of the finite entries of column n over the rows of a chunk of the column pass (column_pass.h), rows ascending:
+// psum / pcnt[chunk * N + n]
 template <typename TI>
-__global__ __launch_bounds__(256) void gap_col_partial_kernel(const TI* __restrict__ X, int T, int64_t N, int chunks,
-                                                              double* __restrict__ psum, int* __restrict__ pcnt) {
-  const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (n >= N) return;
-  const int len = (T + chunks - 1) / chunks;
-  const int r0 = (int)blockIdx.y * len, r1 = r0 + len < T ? r0 + len : T;
-  double acc = 0.0;
-  int cnt = 0;
-  for (int r = r0; r < r1; ++r) {
-    const double v = (double)X[(int64_t)r * N + n];
-    if (v == v) { acc += v; ++cnt; }
+struct GapColPartial {
+  const TI* X; int64_t N; double* psum; int* pcnt;
+  __device__ void operator()(const ColChunk& k) const {
+    double acc = 0.0;
+    int cnt = 0;
+    for (int r = k.r0; r < k.r1; ++r) {
+      const double v = (double)X[(int64_t)r * N + k.c];
+      if (v == v) { acc += v; ++cnt; }
+    }
+    psum[k.at] = acc;
+    pcnt[k.at] = cnt;
   }
-  psum[(int64_t)blockIdx.y * N + n] = acc;
-  pcnt[(int64_t)blockIdx.y * N + n] = cnt;
-}
+};
 
-// mean[n] = (sum of the partials of column n, chunk 0 first) / (present entries of column n); then, over the rows of chunk
-// blockIdx.y: A = x - mean and mask = 0 where x is present, A = 0 and mask = 1 where it is not, and the chunk's sum of squared
-// anomalies pss[chunk * N + n].  A column needs one present entry (checked on the host before the launch).
+// mean[n] = (sum of the partials of column n) / (present entries of column n); then, over the rows of the chunk: A = x - mean
+// and mask = 0 where x is present, A = 0 and mask = 1 where it is not, and the chunk's sum of squared anomalies
+// pss[chunk * N + n].  A column needs one present entry (checked on the host before the launch).
 template <typename TI>
-__global__ __launch_bounds__(256) void gap_center_kernel(const TI* __restrict__ X, int T, int64_t N, int chunks,
-                                                         const double* __restrict__ psum, const int* __restrict__ pcnt,
-                                                         double* __restrict__ mean, TI* __restrict__ A, unsigned char* __restrict__ mask,
-                                                         double* __restrict__ pss) {
-  const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (n >= N) return;
-  double sum = psum[n];
-  int cnt = pcnt[n];
-  for (int c = 1; c < chunks; ++c) { sum += psum[(int64_t)c * N + n]; cnt += pcnt[(int64_t)c * N + n]; }
-  const double mu = sum / (double)cnt;
-  if (blockIdx.y == 0) mean[n] = mu;
-  const int len = (T + chunks - 1) / chunks;
-  const int r0 = (int)blockIdx.y * len, r1 = r0 + len < T ? r0 + len : T;
-  double ss = 0.0;
-  for (int r = r0; r < r1; ++r) {
-    const int64_t i = (int64_t)r * N + n;
-    const double v = (double)X[i];
-    const bool present = v == v;
-    const TI a = present ? (TI)(v - mu) : (TI)0;
-    A[i] = a;
-    mask[i] = present ? 0 : 1;
-    ss = fma((double)a, (double)a, ss);
+struct GapCenter {
+  const TI* X; int64_t N; const double* psum; const int* pcnt; double* mean; TI* A; unsigned char* mask; double* pss;
+  __device__ void operator()(const ColChunk& k) const {
+    const double mu = chunk_sum(psum, k.chunks, N, k.c) / (double)chunk_sum(pcnt, k.chunks, N, k.c);
+    if (k.chunk == 0) mean[k.c] = mu;
+    double ss = 0.0;
+    for (int r = k.r0; r < k.r1; ++r) {
+      const int64_t i = (int64_t)r * N + k.c;
+      const double v = (double)X[i];
+      const bool present = v == v;
+      const TI a = present ? (TI)(v - mu) : (TI)0;
+      A[i] = a;
+      mask[i] = present ? 0 : 1;
+      ss = fma((double)a, (double)a, ss);
+    }
+    pss[k.at] = ss;
   }
-  pss[(int64_t)blockIdx.y * N + n] = ss;
-}
+};
 
 // stat[0] = scale, the RMS of the present anomalies; stat[1] = their number.  One workgroup, lanes strided over the chunks * N
 // partials, then the block's tree: the same association on every call.
@@ -232,14 +221,12 @@ struct GapCenterScratch {
 template <typename TI>
 static inline void gap_center(hipStream_t st, const TI* X, int T, int64_t N, TI* A, unsigned char* mask, double* mean, double* stat,
                               GapCenterScratch& w) {
-  const int chunks = gap_chunks(T);
-  const dim3 grid((unsigned)ceil_div(N, 256), (unsigned)chunks);
+  const int chunks = col_chunks(T);
   w.psum.ensure((size_t)chunks * N);
   w.pcnt.ensure((size_t)chunks * N);
   w.pss.ensure((size_t)chunks * N);
-  hipLaunchKernelGGL((gap_col_partial_kernel<TI>), grid, dim3(256), 0, st, X, T, N, chunks, w.psum.get(), w.pcnt.get());
-  hipLaunchKernelGGL((gap_center_kernel<TI>), grid, dim3(256), 0, st, X, T, N, chunks, (const double*)w.psum.get(), (const int*)w.pcnt.get(),
-                     mean, A, mask, w.pss.get());
+  column_pass(st, T, N, chunks, GapColPartial<TI>{X, N, w.psum.get(), w.pcnt.get()});
+  column_pass(st, T, N, chunks, GapCenter<TI>{X, N, w.psum.get(), w.pcnt.get(), mean, A, mask, w.pss.get()});
   hipLaunchKernelGGL(gap_scale_kernel, dim3(1), dim3(256), 0, st, (const double*)w.pss.get(), (const int*)w.pcnt.get(), (int64_t)chunks * N,
                      stat);
   XMCA_HIP(hipGetLastError());

@@ -2,6 +2,7 @@
 // normalisation, column centering and the Philox surrogate generator.
 #pragma once
 #include "common.h"
+#include "column_pass.h"
 
 namespace xmca {
 
@@ -373,92 +374,76 @@ static inline void normalize_rows(hipStream_t st, T* re, T* im, int64_t ld, int 
   XMCA_HIP(hipGetLastError());
 }
 
-// Column passes of the constructor stage.  A thread per column alone leaves the chip empty (10^4 columns = 40 workgroups):
-// the rows are split into gridDim.y chunks, every (chunk, column) writes its partial result to part[chunk][c], and a
-// finishing kernel adds the chunks in a fixed order (no floating-point atomics: results do not depend on scheduling).
-constexpr int COL_CHUNKS = 32;
-
+// Column passes of the constructor stage: functors of the chunked pass of column_pass.h.
 // part_nan[chunk][c] = NaN entries, part_sum[chunk][c] = sum of column c over the rows of the chunk (part_sum may be null)
 template <typename T>
-__global__ void column_partial_sums_kernel(const T* __restrict__ x, int rows, int64_t cols, int* __restrict__ part_nan,
-                                           double* __restrict__ part_sum) {
-  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= cols) return;
-  const int per = (rows + (int)gridDim.y - 1) / (int)gridDim.y;
-  const int r0 = (int)blockIdx.y * per, r1 = min(rows, r0 + per);
-  double s = 0.0;
-  int nans = 0;
-  for (int r = r0; r < r1; ++r) {
-    const double v = (double)x[(int64_t)r * cols + c];
-    if (v != v) ++nans;
-    s += v;
+struct ColumnPartialSums {
+  const T* x; int64_t cols; int* part_nan; double* part_sum;
+  __device__ void operator()(const ColChunk& k) const {
+    double s = 0.0;
+    int nans = 0;
+    for (int r = k.r0; r < k.r1; ++r) {
+      const double v = (double)x[(int64_t)r * cols + k.c];
+      if (v != v) ++nans;
+      s += v;
+    }
+    part_nan[k.at] = nans;
+    if (part_sum) part_sum[k.at] = s;
   }
-  part_nan[(int64_t)blockIdx.y * cols + c] = nans;
-  if (part_sum) part_sum[(int64_t)blockIdx.y * cols + c] = s;
-}
+};
 
-// nan_count[c] = sum over chunks; mean[c] = (sum over chunks) / rows   (mean may be null)
-__global__ void column_finish_sums_kernel(const int* __restrict__ part_nan, const double* __restrict__ part_sum, int chunks, int rows,
-                                          int64_t cols, int* __restrict__ nan_count, double* __restrict__ mean) {
-  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= cols) return;
-  int n = 0;
-  double s = 0.0;
-  for (int k = 0; k < chunks; ++k) {
-    n += part_nan[(int64_t)k * cols + c];
-    if (part_sum) s += part_sum[(int64_t)k * cols + c];
+// nan_count[c] = sum over chunks; mean[c] = (sum over chunks) / rows   (part_sum and mean may be null)
+struct ColumnFinishSums {
+  const int* part_nan; const double* part_sum; int chunks, rows; int64_t cols; int* nan_count; double* mean;
+  __device__ void operator()(int64_t c) const {
+    nan_count[c] = chunk_sum(part_nan, chunks, cols, c);
+    if (mean) mean[c] = chunk_sum(part_sum, chunks, cols, c) / rows;
   }
-  nan_count[c] = n;
-  if (mean) mean[c] = s / rows;
-}
+};
 
-// Lag-1 autocorrelation of every column, the same row chunks: part[0 / 1 / 2][chunk][c] = sum x, sum x^2 and
-// sum x[t] x[t+1] over the rows t of the chunk (the product belongs to the chunk of t: a chunk reads one row past its end);
+// Lag-1 autocorrelation of every column: part[0 / 1 / 2][chunk][c] = sum x, sum x^2 and sum x[t] x[t+1] over
+// the rows t of the chunk (the product belongs to the chunk of t: a chunk reads one row past its end);
 // ends[0][c] = x[0][c], ends[1][c] = x[rows-1][c].
 template <typename T>
-__global__ void lag1_partial_kernel(const T* __restrict__ x, int rows, int64_t cols, double* __restrict__ part, double* __restrict__ ends) {
-  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= cols) return;
-  const int per = (rows + (int)gridDim.y - 1) / (int)gridDim.y;
-  const int r0 = (int)blockIdx.y * per, r1 = min(rows, r0 + per);
-  double s = 0.0, q = 0.0, l = 0.0;
-  if (r0 < r1) {
-    double v = (double)x[(int64_t)r0 * cols + c];
-    if (r0 == 0) ends[c] = v;
-    for (int r = r0; r < r1; ++r) {
-      const double next = r + 1 < rows ? (double)x[(int64_t)(r + 1) * cols + c] : 0.0;
-      s += v;
-      q += v * v;
-      l += v * next;
-      if (r == rows - 1) ends[cols + c] = v;
-      v = next;
+struct Lag1Partial {
+  const T* x; int rows; int64_t cols; double* part; double* ends;
+  __device__ void operator()(const ColChunk& k) const {
+    const int64_t c = k.c;
+    double s = 0.0, q = 0.0, l = 0.0;
+    if (k.r0 < k.r1) {
+      double v = (double)x[(int64_t)k.r0 * cols + c];
+      if (k.r0 == 0) ends[c] = v;
+      for (int r = k.r0; r < k.r1; ++r) {
+        const double next = r + 1 < rows ? (double)x[(int64_t)(r + 1) * cols + c] : 0.0;
+        s += v;
+        q += v * v;
+        l += v * next;
+        if (r == rows - 1) ends[cols + c] = v;
+        v = next;
+      }
     }
+    const int64_t plane = (int64_t)k.chunks * cols;
+    part[k.at] = s;
+    part[plane + k.at] = q;
+    part[2 * plane + k.at] = l;
   }
-  const int64_t plane = (int64_t)gridDim.y * cols, at = (int64_t)blockIdx.y * cols + c;
-  part[at] = s;
-  part[plane + at] = q;
-  part[2 * plane + at] = l;
-}
+};
 
-// phi[c] = sum_t (x[t] - m)(x[t+1] - m) / sum_t (x[t] - m)^2 from the raw sums of the chunks, added in a fixed order:
+// phi[c] = sum_t (x[t] - m)(x[t+1] - m) / sum_t (x[t] - m)^2 from the raw sums of the chunks:
 // (L - m (2 S - x_0 - x_last) + (rows - 1) m^2) / (Q - rows m^2).  A column that is constant to rounding (the denominator is
 // within the rounding error of Q) gives 0: never a NaN.
-__global__ void lag1_finish_kernel(const double* __restrict__ part, const double* __restrict__ ends, int chunks, int rows, int64_t cols,
-                                   double* __restrict__ phi) {
-  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= cols) return;
-  const int64_t plane = (int64_t)chunks * cols;
-  double s = 0.0, q = 0.0, l = 0.0;
-  for (int k = 0; k < chunks; ++k) {
-    s += part[(int64_t)k * cols + c];
-    q += part[plane + (int64_t)k * cols + c];
-    l += part[2 * plane + (int64_t)k * cols + c];
+struct Lag1Finish {
+  const double* part; const double* ends; int chunks, rows; int64_t cols; double* phi;
+  __device__ void operator()(int64_t c) const {
+    const int64_t plane = (int64_t)chunks * cols;
+    const double s = chunk_sum(part, chunks, cols, c), q = chunk_sum(part + plane, chunks, cols, c);
+    const double l = chunk_sum(part + 2 * plane, chunks, cols, c);
+    const double m = s / rows;
+    const double den = q - (double)rows * m * m;
+    const double num = l - m * (2.0 * s - ends[c] - ends[cols + c]) + (double)(rows - 1) * m * m;
+    phi[c] = den > 4.0 * rows * 1.1102230246251565e-16 * q ? num / den : 0.0;
   }
-  const double m = s / rows;
-  const double den = q - (double)rows * m * m;
-  const double num = l - m * (2.0 * s - ends[c] - ends[cols + c]) + (double)(rows - 1) * m * m;
-  phi[c] = den > 4.0 * rows * 1.1102230246251565e-16 * q ? num / den : 0.0;
-}
+};
 
 // x[r][c] -= mean[c]
 template <typename T>
@@ -470,34 +455,30 @@ __global__ void subtract_column_means_kernel(T* __restrict__ x, int rows, int64_
 
 // x[r][c] -= mean[c] for the columns without NaN (a column holding one is left as it is); part_sq[chunk][c] = sum of squared deviations over the rows of the chunk
 template <typename T>
-__global__ void center_columns_chunk_kernel(T* __restrict__ x, int rows, int64_t cols, const double* __restrict__ mean,
-                                            const int* __restrict__ nan_count, double* __restrict__ part_sq) {
-  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= cols) return;
-  const int per = (rows + (int)gridDim.y - 1) / (int)gridDim.y;
-  const int r0 = (int)blockIdx.y * per, r1 = min(rows, r0 + per);
-  double q = 0.0;
-  if (nan_count[c] == 0) {
-    const double m = mean[c];
-    for (int r = r0; r < r1; ++r) {
-      const double d = (double)x[(int64_t)r * cols + c] - m;
-      q += d * d;
-      x[(int64_t)r * cols + c] = (T)d;
+struct CenterColumnsChunk {
+  T* x; int64_t cols; const double* mean; const int* nan_count; double* part_sq;
+  __device__ void operator()(const ColChunk& k) const {
+    double q = 0.0;
+    if (nan_count[k.c] == 0) {
+      const double m = mean[k.c];
+      for (int r = k.r0; r < k.r1; ++r) {
+        const double d = (double)x[(int64_t)r * cols + k.c] - m;
+        q += d * d;
+        x[(int64_t)r * cols + k.c] = (T)d;
+      }
     }
+    part_sq[k.at] = q;
   }
-  part_sq[(int64_t)blockIdx.y * cols + c] = q;
-}
+};
 
 // stdev[c] = sqrt(sum over chunks / rows)   (columns with NaN: the mean, as before)
-__global__ void column_finish_std_kernel(const double* __restrict__ part_sq, int chunks, int rows, int64_t cols,
-                                         const double* __restrict__ mean, const int* __restrict__ nan_count,
-                                         double* __restrict__ stdev) {
-  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= cols) return;
-  double q = 0.0;
-  for (int k = 0; k < chunks; ++k) q += part_sq[(int64_t)k * cols + c];
-  stdev[c] = nan_count[c] ? mean[c] : sqrt(q / rows);
-}
+struct ColumnFinishStd {
+  const double* part_sq; int chunks, rows; int64_t cols; const double* mean; const int* nan_count; double* stdev;
+  __device__ void operator()(int64_t c) const {
+    const double q = chunk_sum(part_sq, chunks, cols, c);
+    stdev[c] = nan_count[c] ? mean[c] : sqrt(q / rows);
+  }
+};
 
 // out[r][j] = in[r][idx[j]]   (column selection: rows x cols_in -> rows x cols_out)
 template <typename T>
@@ -732,21 +713,21 @@ static inline dim3 gather_cols_grid(int64_t rows, int64_t n_out) {
   return dim3((unsigned)((n_out + GATHER_COLS_BLOCK - 1) / GATHER_COLS_BLOCK), (unsigned)by);
 }
 
-// column sums and sums of squares of a rows x cols matrix (one thread per column, coalesced over columns)
+// column sums and sums of squares of a rows x cols matrix: the column pass with one chunk, all the rows of a column in one thread
 template <typename T>
-__global__ void column_moments_kernel(const T* __restrict__ x, int rows, int64_t cols, double* __restrict__ sum,
-                                      double* __restrict__ sumsq) {
-  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= cols) return;
-  double s = 0.0, q = 0.0;
-  for (int r = 0; r < rows; ++r) {
-    const double v = (double)x[(int64_t)r * cols + c];
-    s += v;
-    q += v * v;
+struct ColumnMoments {
+  const T* x; int64_t cols; double* sum; double* sumsq;
+  __device__ void operator()(const ColChunk& k) const {
+    double s = 0.0, q = 0.0;
+    for (int r = k.r0; r < k.r1; ++r) {
+      const double v = (double)x[(int64_t)r * cols + k.c];
+      s += v;
+      q += v * v;
+    }
+    sum[k.c] = s;
+    sumsq[k.c] = q;
   }
-  sum[c] = s;
-  sumsq[c] = q;
-}
+};
 
 // Pearson correlation from the raw cross products: r[n][j] = (C[n][j] - sx[n] sy[j] / T) / sqrt((qx[n] - sx[n]^2 / T) (qy[j] - sy[j]^2 / T)),
 // clamped to [-1, 1] as numpy.corrcoef clips: C (GEMM) and qx, qy (column moments) sum in different orders, so a perfectly

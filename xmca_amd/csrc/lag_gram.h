@@ -12,7 +12,6 @@ namespace xmca {
 constexpr int LAG_TILE = 32;                     // output tile edge of the lag-sum kernel (xmca_lag_gram_tile)
 constexpr int LAG_BAND_W = 2 * LAG_TILE;         // staged band: 2 LAG_TILE - 1 diagonals, padded to a power of two
 constexpr int LAG_BAND_ROWS = 96;                // most rows of G a workgroup stages (48 KiB of LDS)
-constexpr int LAG_CHUNKS = 32;                   // partial sums per column of the centring
 
 // The band path is taken when the shifted windows of a tile overlap (tau < LAG_TILE) and their union fits the staging buffer.
 static inline bool lag_band_fits(int M, int tau) {
@@ -64,26 +63,21 @@ __global__ __launch_bounds__(256) void lag_sum_kernel(const double* __restrict__
   }
 }
 
-// Column sums of K (= its row sums: K is symmetric) in LAG_CHUNKS pieces of consecutive rows: part[c * np + s], lanes along s
-__global__ __launch_bounds__(256) void lag_col_partial_kernel(const double* __restrict__ K, int64_t ldk, int np, int chunks,
-                                                              double* __restrict__ part) {
-  const int s = (int)blockIdx.x * 256 + threadIdx.x;
-  if (s >= np) return;
-  const int len = (np + chunks - 1) / chunks;
-  const int r0 = (int)blockIdx.y * len, r1 = r0 + len < np ? r0 + len : np;
-  double acc = 0.0;
-  for (int r = r0; r < r1; ++r) acc += K[(int64_t)r * ldk + s];
-  part[(int64_t)blockIdx.y * np + s] = acc;
-}
+// Column sums of K (= its row sums: K is symmetric) over the chunks of the column pass: part[chunk * np + s], lanes along s
+struct LagColPartial {
+  const double* K; int64_t ldk; double* part;
+  __device__ void operator()(const ColChunk& k) const {
+    double acc = 0.0;
+    for (int r = k.r0; r < k.r1; ++r) acc += K[(int64_t)r * ldk + k.c];
+    part[k.at] = acc;
+  }
+};
 
-// mean[s] = (sum of the partials of column s, chunk 0 first) / np, lanes along s
-__global__ __launch_bounds__(256) void lag_col_mean_kernel(const double* __restrict__ part, int np, int chunks, double* __restrict__ mean) {
-  const int s = (int)blockIdx.x * 256 + threadIdx.x;
-  if (s >= np) return;
-  double acc = part[s];
-  for (int c = 1; c < chunks; ++c) acc += part[(int64_t)c * np + s];
-  mean[s] = acc / (double)np;
-}
+// mean[s] = (sum of the partials of column s) / np, lanes along s
+struct LagColMean {
+  const double* part; int np, chunks; double* mean;
+  __device__ void operator()(int64_t s) const { mean[s] = chunk_sum(part, chunks, np, s) / (double)np; }
+};
 
 // mean[np] = (sum_s mean[s]) / np, the grand mean: one workgroup, lanes strided over s, then the block's tree - the same
 // association on every call
@@ -120,12 +114,11 @@ static inline void lag_gram(hipStream_t st, const double* G, int64_t ldg, int n,
   }
   XMCA_HIP(hipGetLastError());
   if (!center) return;
-  const int chunks = std::min(LAG_CHUNKS, np);
+  const int chunks = col_chunks(np);
   part.ensure((size_t)chunks * np);
   mean.ensure((size_t)np + 1);
-  hipLaunchKernelGGL(lag_col_partial_kernel, dim3((unsigned)ceil_div(np, 256), (unsigned)chunks), dim3(256), 0, st, (const double*)K,
-                     (int64_t)np, np, chunks, part.get());
-  hipLaunchKernelGGL(lag_col_mean_kernel, dim3((unsigned)ceil_div(np, 256)), dim3(256), 0, st, (const double*)part.get(), np, chunks, mean.get());
+  column_pass(st, np, np, chunks, LagColPartial{K, (int64_t)np, part.get()});
+  column_finish(st, np, LagColMean{part.get(), np, chunks, mean.get()});
   hipLaunchKernelGGL(lag_grand_mean_kernel, dim3(1), dim3(256), 0, st, np, mean.get());
   hipLaunchKernelGGL(lag_center_kernel, ew_grid((int64_t)np * np), dim3(EW_BLOCK), 0, st, K, (int64_t)np, np, (const double*)mean.get());
   XMCA_HIP(hipGetLastError());

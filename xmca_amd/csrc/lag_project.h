@@ -14,47 +14,38 @@ constexpr int LAGP_ROWS = 32;                    // rows of Q per workgroup of t
 constexpr int LAGP_COLS = 64;                    // ... and its columns (modes)
 
 // ---- column scale -----------------------------------------------------------------------------------------------------------
-// Sums of the columns of x (rows x cols) in gridDim.y chunks of consecutive rows, the chunks of lag1_partial_kernel:
-// part[chunk][c], lanes along c
+// Sums of the columns of x (rows x cols) over the chunks of the column pass (column_pass.h): part[chunk][c], lanes along c
 template <typename T>
-__global__ void lagp_col_sum_kernel(const T* __restrict__ x, int rows, int64_t cols, double* __restrict__ part) {
-  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= cols) return;
-  const int per = (rows + (int)gridDim.y - 1) / (int)gridDim.y;
-  const int r0 = (int)blockIdx.y * per, r1 = min(rows, r0 + per);
-  double s = 0.0;
-  for (int r = r0; r < r1; ++r) s += (double)x[(int64_t)r * cols + c];
-  part[(int64_t)blockIdx.y * cols + c] = s;
-}
-
-// Sums of the squared deviations from the column mean over the same chunks: the mean is the sum of `part` (chunk 0 first) over
-// rows, formed alike by every chunk; dev[chunk][c]
-template <typename T>
-__global__ void lagp_col_dev_kernel(const T* __restrict__ x, int rows, int64_t cols, const double* __restrict__ part,
-                                    double* __restrict__ dev) {
-  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= cols) return;
-  double s = 0.0;
-  for (int k = 0; k < (int)gridDim.y; ++k) s += part[(int64_t)k * cols + c];
-  const double m = s / rows;
-  const int per = (rows + (int)gridDim.y - 1) / (int)gridDim.y;
-  const int r0 = (int)blockIdx.y * per, r1 = min(rows, r0 + per);
-  double q = 0.0;
-  for (int r = r0; r < r1; ++r) {
-    const double d = (double)x[(int64_t)r * cols + c] - m;
-    q = fma(d, d, q);
+struct LagpColSum {
+  const T* x; int64_t cols; double* part;
+  __device__ void operator()(const ColChunk& k) const {
+    double s = 0.0;
+    for (int r = k.r0; r < k.r1; ++r) s += (double)x[(int64_t)r * cols + k.c];
+    part[k.at] = s;
   }
-  dev[(int64_t)blockIdx.y * cols + c] = q;
-}
+};
 
-// d[c] = sqrt(sum of the chunks of dev (chunk 0 first) / (rows - 1)): the sample standard deviation, ddof = 1
-__global__ void lagp_col_scale_kernel(const double* __restrict__ dev, int chunks, int rows, int64_t cols, double* __restrict__ d) {
-  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= cols) return;
-  double q = 0.0;
-  for (int k = 0; k < chunks; ++k) q += dev[(int64_t)k * cols + c];
-  d[c] = sqrt(q / (double)(rows - 1));
-}
+// Sums of the squared deviations from the column mean over the same chunks: the mean is the sum of `part` over rows, formed
+// alike by every chunk; dev[chunk][c]
+template <typename T>
+struct LagpColDev {
+  const T* x; int rows; int64_t cols; const double* part; double* dev;
+  __device__ void operator()(const ColChunk& k) const {
+    const double m = chunk_sum(part, k.chunks, cols, k.c) / rows;
+    double q = 0.0;
+    for (int r = k.r0; r < k.r1; ++r) {
+      const double d = (double)x[(int64_t)r * cols + k.c] - m;
+      q = fma(d, d, q);
+    }
+    dev[k.at] = q;
+  }
+};
+
+// d[c] = sqrt(sum of the chunks of dev / (rows - 1)): the sample standard deviation, ddof = 1
+struct LagpColScale {
+  const double* dev; int chunks, rows; int64_t cols; double* d;
+  __device__ void operator()(int64_t c) const { d[c] = sqrt(chunk_sum(dev, chunks, cols, c) / (double)(rows - 1)); }
+};
 
 // B[r][n] = P[r][n] |scale[r mod k]| d[n] in the element type of the GEMM's operand: the unit-norm patterns (scale: that of
 // eeof_sign_norm_kernel; the sign does not matter to a squared norm) times the column scale (d == nullptr: left out).
@@ -72,14 +63,12 @@ __global__ void lagp_scale_patterns_kernel(const double* __restrict__ P, const d
 
 template <typename TI>
 void lag_column_scale(hipStream_t st, const TI* x, int rows, int64_t cols, double* d, DevBuf<double>& part, DevBuf<double>& dev) {
-  const int chunks = (int)std::min<int64_t>(COL_CHUNKS, rows);
-  const unsigned gx = (unsigned)ceil_div(cols, (int64_t)256);
+  const int chunks = col_chunks(rows);
   part.ensure((size_t)chunks * cols);
   dev.ensure((size_t)chunks * cols);
-  hipLaunchKernelGGL((lagp_col_sum_kernel<TI>), dim3(gx, (unsigned)chunks), dim3(256), 0, st, x, rows, cols, part.get());
-  hipLaunchKernelGGL((lagp_col_dev_kernel<TI>), dim3(gx, (unsigned)chunks), dim3(256), 0, st, x, rows, cols, (const double*)part.get(),
-                     dev.get());
-  hipLaunchKernelGGL(lagp_col_scale_kernel, dim3(gx), dim3(256), 0, st, (const double*)dev.get(), chunks, rows, cols, d);
+  column_pass(st, rows, cols, chunks, LagpColSum<TI>{x, cols, part.get()});
+  column_pass(st, rows, cols, chunks, LagpColDev<TI>{x, rows, cols, part.get(), dev.get()});
+  column_finish(st, cols, LagpColScale{dev.get(), chunks, rows, cols, d});
   XMCA_HIP(hipGetLastError());
 }
 

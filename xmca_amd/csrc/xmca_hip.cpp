@@ -909,10 +909,9 @@ void correlate_device(xmca_handle* h, const char* what, int side, const double* 
   XMCA_HIP(hipMemcpyAsync(yh.ensure(ny), Y, sizeof(double) * ny, hipMemcpyHostToDevice, h->st));
   hipLaunchKernelGGL((convert_kernel<double, TI>), ew_grid((int64_t)ny), dim3(EW_BLOCK), 0, h->st, yh.get(), yt.ensure(ny), (int64_t)ny);
   h->tm.begin("correlate");
-  hipLaunchKernelGGL((column_moments_kernel<TI>), dim3((unsigned)ceil_div(N, (int64_t)256)), dim3(256), 0, h->st, f.r(), (int)T, N,
-                     sx.ensure((size_t)N), qx.ensure((size_t)N));
-  hipLaunchKernelGGL((column_moments_kernel<double>), dim3((unsigned)ceil_div(m, (int64_t)256)), dim3(256), 0, h->st, yh.get(), (int)T,
-                     m, sy.ensure((size_t)m), qy.ensure((size_t)m));
+  // (one chunk: cutting the rows would change the bits of the moments)
+  column_pass(h->st, (int)T, N, 1, ColumnMoments<TI>{f.r(), N, sx.ensure((size_t)N), qx.ensure((size_t)N)});
+  column_pass(h->st, (int)T, m, 1, ColumnMoments<double>{yh.get(), m, sy.ensure((size_t)m), qy.ensure((size_t)m)});
   XMCA_HIP(hipGetLastError());
   // C = X^T Y   (N x m): A(n, t) = X[t * N + n], B(t, j) = Y[t * m + j]
   GemmOpts o;
@@ -975,13 +974,11 @@ void correlation_maps_impl(xmca_handle* h, int side, const double* Y, int64_t T,
 // partial column sums over row chunks, means in a fixed order, one elementwise pass
 template <typename TI>
 void center_columns(xmca_handle* h, TI* x, int64_t T, int64_t N) {
-  const int chunks = (int)std::min<int64_t>(COL_CHUNKS, T);
-  const unsigned gx = (unsigned)ceil_div(N, (int64_t)256);
-  int* pn = h->center_nan.ensure((size_t)(chunks + 1) * N);
+  const int chunks = col_chunks(T);
+  int* pn = h->center_nan.ensure((size_t)(chunks + 1) * N);      // (the finished values behind the partials, in plane `chunks`)
   double* ps = h->center_sum.ensure((size_t)(chunks + 1) * N);
-  hipLaunchKernelGGL((column_partial_sums_kernel<TI>), dim3(gx, (unsigned)chunks), dim3(256), 0, h->st, x, (int)T, N, pn, ps);
-  hipLaunchKernelGGL(column_finish_sums_kernel, dim3(gx), dim3(256), 0, h->st, pn, ps, chunks, (int)T, N, pn + (size_t)chunks * N,
-                     ps + (size_t)chunks * N);
+  column_pass(h->st, (int)T, N, chunks, ColumnPartialSums<TI>{x, N, pn, ps});
+  column_finish(h->st, N, ColumnFinishSums{pn, ps, chunks, (int)T, N, pn + (size_t)chunks * N, ps + (size_t)chunks * N});
   hipLaunchKernelGGL((subtract_column_means_kernel<TI>), ew_grid(T * N), dim3(EW_BLOCK), 0, h->st, x, (int)T, N, ps + (size_t)chunks * N);
   XMCA_HIP(hipGetLastError());
 }
@@ -993,18 +990,14 @@ void center_field_impl(xmca_handle* h, int side, double* mean_out, double* std_o
   const int64_t N = f.N;
   DevBuf<double> mean, sd, part_sum, part_sq;
   DevBuf<int> nans, part_nan;
-  const int chunks = (int)std::min<int64_t>(COL_CHUNKS, f.T);
-  const dim3 grid2((unsigned)ceil_div(N, (int64_t)256), (unsigned)chunks), grid1((unsigned)ceil_div(N, (int64_t)256));
+  const int chunks = col_chunks(f.T), T = (int)f.T;
   part_nan.ensure((size_t)chunks * N);
   part_sum.ensure((size_t)chunks * N);
   part_sq.ensure((size_t)chunks * N);
-  hipLaunchKernelGGL((column_partial_sums_kernel<TI>), grid2, dim3(256), 0, h->st, f.re.get(), (int)f.T, N, part_nan.get(), part_sum.get());
-  hipLaunchKernelGGL(column_finish_sums_kernel, grid1, dim3(256), 0, h->st, part_nan.get(), part_sum.get(), chunks, (int)f.T, N,
-                     nans.ensure((size_t)N), mean.ensure((size_t)N));
-  hipLaunchKernelGGL((center_columns_chunk_kernel<TI>), grid2, dim3(256), 0, h->st, f.re.get(), (int)f.T, N, mean.get(), nans.get(),
-                     part_sq.get());
-  hipLaunchKernelGGL(column_finish_std_kernel, grid1, dim3(256), 0, h->st, part_sq.get(), chunks, (int)f.T, N, mean.get(), nans.get(),
-                     sd.ensure((size_t)N));
+  column_pass(h->st, T, N, chunks, ColumnPartialSums<TI>{f.re.get(), N, part_nan.get(), part_sum.get()});
+  column_finish(h->st, N, ColumnFinishSums{part_nan.get(), part_sum.get(), chunks, T, N, nans.ensure((size_t)N), mean.ensure((size_t)N)});
+  column_pass(h->st, T, N, chunks, CenterColumnsChunk<TI>{f.re.get(), N, mean.get(), nans.get(), part_sq.get()});
+  column_finish(h->st, N, ColumnFinishStd{part_sq.get(), chunks, T, N, mean.get(), nans.get(), sd.ensure((size_t)N)});
   XMCA_HIP(hipGetLastError());
   std::vector<int> nh((size_t)N);
   XMCA_HIP(hipMemcpyAsync(mean_out, mean.get(), sizeof(double) * N, hipMemcpyDeviceToHost, h->st));
@@ -1024,12 +1017,10 @@ void compact_field_impl(xmca_handle* h, int side, int* keep_out, int64_t* n_keep
   XMCA_CHECK(!f.has_im && !f.ext_re, XMCA_ERR_STATE, "compact_field: needs a real field owned by the library");
   const int64_t N = f.N;
   DevBuf<int> nans, part_nan;
-  const int chunks = (int)std::min<int64_t>(COL_CHUNKS, f.T);
+  const int chunks = col_chunks(f.T);
   part_nan.ensure((size_t)chunks * N);
-  hipLaunchKernelGGL((column_partial_sums_kernel<TI>), dim3((unsigned)ceil_div(N, (int64_t)256), (unsigned)chunks), dim3(256), 0, h->st,
-                     f.re.get(), (int)f.T, N, part_nan.get(), (double*)nullptr);
-  hipLaunchKernelGGL(column_finish_sums_kernel, dim3((unsigned)ceil_div(N, (int64_t)256)), dim3(256), 0, h->st, part_nan.get(),
-                     (const double*)nullptr, chunks, (int)f.T, N, nans.ensure((size_t)N), (double*)nullptr);
+  column_pass(h->st, (int)f.T, N, chunks, ColumnPartialSums<TI>{f.re.get(), N, part_nan.get(), nullptr});      // (no sum plane)
+  column_finish(h->st, N, ColumnFinishSums{part_nan.get(), nullptr, chunks, (int)f.T, N, nans.ensure((size_t)N), nullptr});
   XMCA_HIP(hipGetLastError());
   std::vector<int> nh((size_t)N);
   XMCA_HIP(hipMemcpyAsync(nh.data(), nans.get(), sizeof(int) * N, hipMemcpyDeviceToHost, h->st));
@@ -1377,13 +1368,10 @@ void lag1_impl(xmca_handle* h, int side, double* phi_out) {
   const FieldData<TI>& f = typed<TI>(h).f[side];
   const int64_t T = f.T, N = f.N;
   XMCA_CHECK(T >= 2 && N >= 1, XMCA_ERR_STATE, "lag1_autocorrelation: the field needs at least 2 time steps");
-  const int chunks = (int)std::min<int64_t>(COL_CHUNKS, T);
-  const unsigned gx = (unsigned)ceil_div(N, (int64_t)256);
+  const int chunks = col_chunks(T);
   DevBuf<double> part, ends, phi;
-  hipLaunchKernelGGL((lag1_partial_kernel<TI>), dim3(gx, (unsigned)chunks), dim3(256), 0, h->st, f.r(), (int)T, N,
-                     part.ensure((size_t)3 * chunks * N), ends.ensure((size_t)2 * N));
-  hipLaunchKernelGGL(lag1_finish_kernel, dim3(gx), dim3(256), 0, h->st, (const double*)part.get(), (const double*)ends.get(), chunks, (int)T, N,
-                     phi.ensure((size_t)N));
+  column_pass(h->st, (int)T, N, chunks, Lag1Partial<TI>{f.r(), (int)T, N, part.ensure((size_t)3 * chunks * N), ends.ensure((size_t)2 * N)});
+  column_finish(h->st, N, Lag1Finish{part.get(), ends.get(), chunks, (int)T, N, phi.ensure((size_t)N)});
   XMCA_HIP(hipGetLastError());
   XMCA_HIP(hipMemcpyAsync(phi_out, phi.get(), sizeof(double) * N, hipMemcpyDeviceToHost, h->st));
   XMCA_HIP(hipStreamSynchronize(h->st));
