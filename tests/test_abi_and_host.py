@@ -1,11 +1,13 @@
 """CPU: the C-ABI library loads and exports every symbol of include/xmca_hip.h; host logic of the drop-in class;
 the product path fails loudly without a GPU (no fallback)."""
+import ctypes
 import os
 import re
 
 import numpy as np
 import pytest
 
+from abi_cases import check_types, header_abi_version, header_declarations, header_define
 from golden_inputs import make_input
 from oracle import ref_numpy as O
 
@@ -41,12 +43,48 @@ def test_stale_library_is_refused(monkeypatch):
     """a library built from another revision of include/xmca_hip.h (ABI number) is not bound silently"""
     from xmca_amd import _hip
     _hip.load_library()
-    header = open(os.path.join(REPO, "include", "xmca_hip.h")).read()
-    assert int(re.search(r"#define XMCA_ABI_VERSION (\d+)", header).group(1)) == _hip.ABI_VERSION
+    assert header_abi_version() == _hip.ABI_VERSION == _hip.load_library().xmca_abi_version() == 15
     monkeypatch.setattr(_hip, "_lib", None)
     monkeypatch.setattr(_hip, "ABI_VERSION", _hip.ABI_VERSION + 1)
     with pytest.raises(ImportError, match="ABI"):
         _hip.load_library()
+
+
+# ------------------------------------------------------------------------------------------------
+# the binding table against the header, position by position (tests/abi_cases.py reads the header)
+# ------------------------------------------------------------------------------------------------
+def test_every_row_of_the_binding_table_says_what_the_header_declares():
+    """return type, argument count, the exact type of every value argument (a c_int where the header says int64_t keeps the count
+    right and breaks only when a value stops fitting into 32 bits) and a pointer at every pointer argument, for every entry"""
+    from xmca_amd import _hip
+    assert set(header_declarations()) == set(_declared_symbols()) == set(_hip.SIGNATURES)
+    for name, (restype, argtypes) in _hip.SIGNATURES.items():
+        check_types(name, restype, argtypes)
+
+
+@pytest.mark.parametrize("row", [(ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),        # n_vec: int64_t
+                                 (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64]),     # rank_out: a pointer
+                                 (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.POINTER(ctypes.c_int)]),
+                                 (ctypes.c_int, [ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p]),     # h: a pointer
+                                 (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64]),
+                                 (None, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p])])
+def test_a_wrong_row_is_told_from_the_header(row):
+    """int xmca_solve(xmca_handle* h, int n_fields, int64_t n_vec, int64_t* rank_out) bound in six wrong ways"""
+    check_types("xmca_solve", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)])
+    check_types("xmca_solve", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p])
+    with pytest.raises(AssertionError):
+        check_types("xmca_solve", *row)
+
+
+def test_constants_of_the_binding_are_those_of_the_header():
+    from xmca_amd import _hip
+    for name in ("XMCA_F32", "XMCA_F64"):
+        assert getattr(_hip, name) == header_define(name), name
+    for name in ("HOST", "DEVICE", "ERR_INVALID", "ERR_HIP", "ERR_NOT_CONVERGED", "ERR_STATE", "ERR_UNSUPPORTED", "ERR_NUMERIC",
+                 "MAP_EOF", "MAP_AMPLITUDE", "MAP_PHASE", "SCALE_NONE", "SCALE_MAX", "SCALE_STD", "INGEST_ROWS", "INGEST_TRANSPOSE",
+                 "INGEST_GATHER", "COMM_ID_BYTES", "ABI_VERSION"):
+        assert getattr(_hip, name) == header_define("XMCA_" + name), name
+    assert header_define("XMCA_ERR_NUMERIC") == -6 and header_define("XMCA_COMM_ID_BYTES") == 128
 
 
 def test_no_gpu_means_loud_failure():

@@ -1,30 +1,23 @@
 """CPU: the plumbing of `bootstrapping(axis=1)` that needs no device - the two column entry points in the header, the binding
 table and the built library (added at ABI 14; the number is 15 since the kernel-test entries), and the index composition `compose_bootstrap_indices` against `block_bootstrap(axis=1)`
 applied cumulatively the way the reference's loop applies it (xmca/array.py:1902-1928)."""
-import os
 import re
 
 import numpy as np
 import pytest
 
+from abi_cases import check_entry, header_abi_version
 from xmca_amd.array import compose_bootstrap_indices
 from xmca_amd.tools.array import block_bootstrap
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("xmca_bootstrap_runs_columns", "xmca_bootstrap_runs_columns_extended")
 
 
 def test_column_entries_are_declared_bound_and_exported_at_abi_14():
     from xmca_amd import _hip
-    header = open(os.path.join(REPO, "include", "xmca_hip.h")).read()
-    assert int(re.search(r"#define XMCA_ABI_VERSION (\d+)", header).group(1)) == 15
-    assert _hip.ABI_VERSION == 15
-    lib = _hip.load_library()
-    assert lib.xmca_abi_version() == 15
-    code = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
+    assert header_abi_version() == _hip.ABI_VERSION == _hip.load_library().xmca_abi_version()
     for name, row in zip(NEW, ("xmca_bootstrap_runs", "xmca_bootstrap_runs_extended")):
-        assert re.search(r"\bint %s\s*\(" % name, code), name
-        assert hasattr(lib, name), name
+        check_entry(name)
         assert _hip.SIGNATURES[name] == _hip.SIGNATURES[row]          # the same argument order as the row entries
 
 

@@ -1,18 +1,14 @@
 """CPU: `bootstrap_eofs` without a device - the row indices of the moving-block bootstrap, the argument errors and the forwarding
 of `indices` (a recorder stands in for the handle), the three ABI entries, and the numpy twin against its definition."""
-import ctypes
-import os
-import re
-
 import numpy as np
 import pytest
 
 import bootstrap_patterns_cases as B
+from abi_cases import check_entry, header_abi_version
 from xmca_amd import _hip
 from xmca_amd.array import MCA, bootstrap_row_indices
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = {"xmca_bootstrap_patterns": 16, "xmca_pattern_stats": 21, "xmca_pattern_tile": 1}
+NEW = {"xmca_bootstrap_patterns": 16, "xmca_pattern_stats": 21, "xmca_pattern_tile": 0}
 
 
 # ---- bootstrap_row_indices ----------------------------------------------------------------------------------------------
@@ -136,18 +132,9 @@ def test_indices_are_forwarded_and_the_results_take_the_layout_of_eofs():
 
 # ---- ABI ------------------------------------------------------------------------------------------------------------------
 def test_new_entries_are_declared_exported_and_bound_and_the_abi_number_stays():
-    lib = _hip.load_library()
-    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", "xmca_hip.h")).read(), flags=re.S)
     for name, n_args in NEW.items():
-        decl = re.search(r"\b%s\s*\(([^;]*)\)\s*;" % name, header)
-        assert decl, "%s is not declared" % name
-        assert len(decl.group(1).split(",")) == n_args
-        assert hasattr(lib, name), "%s is not exported" % name
-        restype, argtypes = _hip.SIGNATURES[name]
-        n_bound = 0 if decl.group(1).strip() == "void" else n_args
-        assert restype is ctypes.c_int and len(argtypes) == n_bound and getattr(lib, name).argtypes == list(argtypes)
-    assert int(re.search(r"#define XMCA_ABI_VERSION (\d+)", header).group(1)) == 15
-    assert _hip.ABI_VERSION == 15 and lib.xmca_abi_version() == 15
+        check_entry(name, n_args)
+    assert header_abi_version() == _hip.ABI_VERSION == _hip.load_library().xmca_abi_version()
 
 
 def test_the_tile_is_a_constant_of_the_build_known_without_a_device():

@@ -3,7 +3,6 @@ xmca_bootstrap_runs_columns_theta) are declared, exported and bound without a ne
 `theta_period` to the device's `bootstrap_runs` only when it is set - a device without that parameter keeps working - with the
 same result on the two ranks of a gloo job as in a single process."""
 import os
-import re
 import socket
 import sys
 
@@ -11,36 +10,28 @@ import numpy as np
 import pytest
 import torch.multiprocessing as mp
 
+from abi_cases import check_entry, header_abi_version, header_arguments
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("xmca_bootstrap_runs_theta", "xmca_bootstrap_runs_columns_theta")
-
-
-def _header():
-    text = open(os.path.join(REPO, "include", "xmca_hip.h")).read()
-    return text, re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+N_ARGS = 15                     # of either
 
 
 def test_header_declares_both_entries_and_keeps_the_abi_number():
-    text, code = _header()
-    assert int(re.search(r"#define XMCA_ABI_VERSION (\d+)", text).group(1)) == 15
+    from xmca_amd import _hip
+    assert header_abi_version() == _hip.ABI_VERSION
     for name in NEW:
-        decl = re.search(r"\bint\s+%s\s*\(([^;]*)\)\s*;" % name, code)
-        assert decl, "%s is not declared in include/xmca_hip.h" % name
-        args = [a.strip() for a in decl.group(1).split(",")]
-        assert len(args) == 15
+        args = header_arguments(name)
+        assert len(args) == N_ARGS
         assert [a.split()[-1].lstrip("*") for a in args[:5]] == ["h", "col3", "hbar", "B", "period"]
         assert args[4] == "int period" and args[-1] == "int64_t n_out"
 
 
 def test_library_exports_and_binding_declares_both_entries():
     from xmca_amd import _hip
-    lib = _hip.load_library()
-    assert _hip.ABI_VERSION == 15 and lib.xmca_abi_version() == 15
+    assert _hip.load_library().xmca_abi_version() == _hip.ABI_VERSION
     for name in NEW:
-        assert hasattr(lib, name), "%s is not exported" % name
-        assert name in _hip.SIGNATURES, "%s is not bound" % name
-        restype, argtypes = _hip.SIGNATURES[name]
-        assert len(argtypes) == 15 and getattr(lib, name).argtypes == list(argtypes)
+        check_entry(name, N_ARGS)
     assert _hip.SIGNATURES[NEW[0]] == _hip.SIGNATURES[NEW[1]]
 
 

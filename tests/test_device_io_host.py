@@ -1,17 +1,14 @@
 """No GPU: the host side of tensor input and tensor output - which views of a tensor two strides express and which copy kernel
 those strides select, the `output=` keyword, CPU tensors as numpy input, and the C ABI (same number, new symbols)."""
-import os
-import re
-
 import numpy as np
 import pytest
 
 torch = pytest.importorskip("torch")
 
+from abi_cases import check_entry, header_abi_version, header_define   # noqa: E402
 from xmca_amd import _hip                                       # noqa: E402
 from xmca_amd.array import MCA, _flat_strides, _tensor_np_dtype  # noqa: E402
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ["xmca_set_field_strided", "xmca_ingest_regime", "xmca_get_maps_to", "xmca_reconstruct_to", "xmca_correlation_maps_to",
                "xmca_predict_strided"]
 ROWS, TRANSPOSE, GATHER = _hip.INGEST_ROWS, _hip.INGEST_TRANSPOSE, _hip.INGEST_GATHER
@@ -114,14 +111,9 @@ def test_output_keyword_and_cpu_tensors():
 
 
 def test_abi_number_and_new_symbols():
-    header = open(os.path.join(REPO, "include", "xmca_hip.h")).read()
-    assert int(re.search(r"#define XMCA_ABI_VERSION (\d+)", header).group(1)) == 15 == _hip.ABI_VERSION
-    lib = _hip.load_library()
-    assert lib.xmca_abi_version() == 15
-    code = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
+    assert header_abi_version() == _hip.ABI_VERSION == _hip.load_library().xmca_abi_version()
     for name in NEW_SYMBOLS:
-        assert re.search(r"\b%s\s*\(" % name, code), name
-        assert name in _hip.SIGNATURES and hasattr(lib, name), name
+        check_entry(name)
     # the wrappers kept their signatures: the new entry points add one trailing memory-space argument (predict: strides + space)
     sig = _hip.SIGNATURES
     assert sig["xmca_get_maps_to"][1][:-1] == sig["xmca_get_maps"][1]
@@ -129,4 +121,4 @@ def test_abi_number_and_new_symbols():
     assert sig["xmca_correlation_maps_to"][1][:-1] == sig["xmca_correlation_maps"][1]
     assert len(sig["xmca_predict_strided"][1]) == len(sig["xmca_predict_weighted"][1]) + 3
     for name, value in (("XMCA_INGEST_ROWS", ROWS), ("XMCA_INGEST_TRANSPOSE", TRANSPOSE), ("XMCA_INGEST_GATHER", GATHER)):
-        assert int(re.search(r"#define %s (\d+)" % name, header).group(1)) == value
+        assert header_define(name) == value

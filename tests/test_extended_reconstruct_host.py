@@ -2,10 +2,8 @@
 call, the identity behind the device route (diag(1 / c) A~ P from the eigenvectors of the doubly centred lag sum against the
 diagonal averaging of the truncated SVD; tests/extended_reconstruct_cases.py), completeness with all modes, the two deliberate
 mistakes, the conditions the cases need, the three ABI entries, and the facade on a recorder."""
-import ctypes
 import inspect
 import os
-import re
 import sys
 
 import numpy as np
@@ -13,6 +11,7 @@ import pytest
 
 import extended_eofs_cases as E
 import extended_reconstruct_cases as C
+from abi_cases import check_entry, header_abi_version
 from xmca_amd import _hip
 from xmca_amd.array import MCA
 
@@ -24,7 +23,6 @@ except Exception:
 
 from xmca_amd.xarray import xMCA
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = {"xmca_extended_reconstruct": 14, "xmca_lag_expand": 9, "xmca_lag_window_means": 4}
 BOUND = 1e-12                 # x max|X|: route against truth, and completeness (measured: <= 1e-14)
 
@@ -219,17 +217,9 @@ def test_counts():
 
 # ---- ABI ----------------------------------------------------------------------------------------------------------------
 def test_new_entries_are_declared_exported_and_bound_and_the_abi_number_stays():
-    lib = _hip.load_library()
-    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", "xmca_hip.h")).read(), flags=re.S)
     for name, n_args in NEW.items():
-        decl = re.search(r"\b%s\s*\(([^;]*)\)\s*;" % name, header)
-        assert decl, "%s is not declared" % name
-        assert len(decl.group(1).split(",")) == n_args
-        assert hasattr(lib, name), "%s is not exported" % name
-        restype, argtypes = _hip.SIGNATURES[name]
-        assert restype is ctypes.c_int and len(argtypes) == n_args and getattr(lib, name).argtypes == list(argtypes)
-    assert int(re.search(r"#define XMCA_ABI_VERSION (\d+)", header).group(1)) == 15
-    assert _hip.ABI_VERSION == 15 and lib.xmca_abi_version() == 15
+        check_entry(name, n_args)
+    assert header_abi_version() == _hip.ABI_VERSION == _hip.load_library().xmca_abi_version()
 
 
 # ---- facade -------------------------------------------------------------------------------------------------------------

@@ -2,10 +2,8 @@
 the identities behind the device route (Lambda_k(X) = lambda_k; the shift sum of one thin product against the explicitly embedded
 surrogate; tests/extended_rule_n_cases.py), the gap condition of every case, the planted-signal case decided on the CPU, and the
 ABI entries."""
-import ctypes
 import inspect
 import os
-import re
 import sys
 
 import numpy as np
@@ -13,6 +11,7 @@ import pytest
 
 import ar1_cases as A
 import extended_rule_n_cases as C
+from abi_cases import check_entry, header_abi_version
 from xmca_amd import _hip
 from xmca_amd.array import MCA
 
@@ -24,7 +23,6 @@ except Exception:
 
 from xmca_amd.xarray import xMCA
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = {"xmca_extended_rule_n": 11, "xmca_extended_project": 7, "xmca_lag_project": 7, "xmca_lag_project_tile": 2}
 # the identities in float64: sums of at most M N = 900 products and T' = 119 squares, measured at 2e-15 and below
 BOUND_IDENTITY = 1e-13
@@ -179,17 +177,9 @@ def test_the_planted_pair_stands_out_on_the_cpu_with_room_to_spare():
 
 # ---- ABI ----------------------------------------------------------------------------------------------------------------
 def test_new_entries_are_declared_exported_and_bound_and_the_abi_number_stays():
-    lib = _hip.load_library()
-    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", "xmca_hip.h")).read(), flags=re.S)
     for name, n_args in NEW.items():
-        decl = re.search(r"\b%s\s*\(([^;]*)\)\s*;" % name, header)
-        assert decl, "%s is not declared" % name
-        assert len(decl.group(1).split(",")) == n_args
-        assert hasattr(lib, name), "%s is not exported" % name
-        restype, argtypes = _hip.SIGNATURES[name]
-        assert restype is ctypes.c_int and len(argtypes) == n_args and getattr(lib, name).argtypes == list(argtypes)
-    assert int(re.search(r"#define XMCA_ABI_VERSION (\d+)", header).group(1)) == 15
-    assert _hip.ABI_VERSION == 15 and lib.xmca_abi_version() == 15
+        check_entry(name, n_args)
+    assert header_abi_version() == _hip.ABI_VERSION == _hip.load_library().xmca_abi_version()
 
 
 def test_the_tile_is_a_constant_of_the_build_known_without_a_device():

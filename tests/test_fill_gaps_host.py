@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import fill_gaps_cases as C
+from abi_cases import check_entry, header_abi_version, header_text
 from xmca_amd import _hip, gaps
 
 try:
@@ -212,14 +213,10 @@ def test_withheld_indices_follow_the_kept_columns():
 
 # ---- ABI and facade -------------------------------------------------------------------------------------------------------------
 def test_the_header_declares_the_entries_and_the_binding_has_them():
-    text = open(os.path.join(REPO, "include", "xmca_hip.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     for name, n_args in NEW.items():
-        m = re.search(r"\b%s\s*\(([^)]*)\)\s*;" % name, code)
-        assert m, name
-        assert len(m.group(1).split(",")) == n_args, name
-        assert name in _hip.SIGNATURES and len(_hip.SIGNATURES[name][1]) == n_args, name
-    assert re.search(r"#define\s+XMCA_ABI_VERSION\s+15\b", text) and _hip.ABI_VERSION == 15
+        check_entry(name, n_args)
+    assert header_abi_version() == _hip.ABI_VERSION
+    text = header_text(comments=True)                 # (the stage names stand in a comment)
     for stage in ("gap_center", "gap_eigh", "gap_project", "gap_fill", "gap_finish"):
         assert '"%s"' % stage in text, stage
     for method in ("fill_gaps", "gap_center", "gap_fill_step"):

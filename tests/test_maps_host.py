@@ -1,41 +1,23 @@
 """CPU: xmca_get_maps is declared, exported and bound with the header's argument count under the unchanged ABI number, and the class
 reaches it only with vectors resident on the device and without `_maps_on_host` (a stub device whose `maps` raises)."""
-import os
-import re
-
 import numpy as np
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _header():
-    return open(os.path.join(REPO, "include", "xmca_hip.h")).read()
+from abi_cases import check_entry, header_abi_version, header_define
 
 
 def test_maps_entry_point_is_declared_exported_and_bound():
     from xmca_amd import _hip
-    text = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-    m = re.search(r"\bint\s+xmca_get_maps\s*\(([^)]*)\)\s*;", text)
-    assert m, "xmca_get_maps is not declared in include/xmca_hip.h"
-    args = [a.strip() for a in m.group(1).split(",")]
-    lib = _hip.load_library()
-    assert hasattr(lib, "xmca_get_maps")
-    res, argtypes = _hip.SIGNATURES["xmca_get_maps"]
-    assert len(argtypes) == len(args) == 15, (args, argtypes)
-    assert lib.xmca_get_maps.argtypes == argtypes
+    check_entry("xmca_get_maps", 15)
     assert hasattr(_hip.Handle, "maps")
     for name, value in (("XMCA_MAP_EOF", _hip.MAP_EOF), ("XMCA_MAP_AMPLITUDE", _hip.MAP_AMPLITUDE), ("XMCA_MAP_PHASE", _hip.MAP_PHASE),
                         ("XMCA_SCALE_NONE", _hip.SCALE_NONE), ("XMCA_SCALE_MAX", _hip.SCALE_MAX), ("XMCA_SCALE_STD", _hip.SCALE_STD)):
-        d = re.search(r"#define\s+%s\s+(-?\d+)" % name, text)
-        assert d and int(d.group(1)) == value, name
+        assert header_define(name) == value, name
 
 
 def test_abi_number_is_unchanged_by_the_added_entry_point():
     from xmca_amd import _hip
-    d = re.search(r"#define\s+XMCA_ABI_VERSION\s+(\d+)", _header())
-    assert d and int(d.group(1)) == 15
-    assert _hip.ABI_VERSION == 15 and _hip.load_library().xmca_abi_version() == 15
+    assert header_abi_version() == _hip.ABI_VERSION == _hip.load_library().xmca_abi_version()
 
 
 class _StubDevice:

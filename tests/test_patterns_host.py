@@ -1,34 +1,19 @@
 """CPU: the p-value entry points are declared, exported and bound with the header's argument counts; the host constant of the
 p-value kernel (-ln a - ln B(a, a), xmca_pvalue_log_norm) against mpmath-derived values (tests/golden/pvalue_truth.npz)."""
 import os
-import re
 
 import numpy as np
 import pytest
 
+from abi_cases import check_entry
 from golden_inputs import GOLDEN_DIR
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["xmca_pearson_pvalues", "xmca_pvalue_log_norm", "xmca_correlation_maps"]
-
-
-def _header_arguments(name):
-    text = open(os.path.join(REPO, "include", "xmca_hip.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    m = re.search(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % name, text)
-    assert m, "%s is not declared in include/xmca_hip.h" % name
-    return [a.strip() for a in m.group(1).split(",")]
 
 
 @pytest.mark.parametrize("name", NEW)
 def test_pvalue_entry_points_are_declared_exported_and_bound(name):
-    from xmca_amd import _hip
-    args = _header_arguments(name)
-    lib = _hip.load_library()
-    assert hasattr(lib, name)
-    res, argtypes = _hip.SIGNATURES[name]
-    assert len(argtypes) == len(args), (args, argtypes)
-    assert getattr(lib, name).argtypes == argtypes
+    check_entry(name)
 
 
 def test_abi_number_covers_the_new_entry_points():

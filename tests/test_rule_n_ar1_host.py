@@ -1,42 +1,25 @@
 """CPU: the red-noise (AR(1)) option of rule_n without a device - the ABI entries, the numpy twin against the definition, the
 argument errors of `MCA.rule_n(noise=, phi=)`, the forwarding of `ar1=` and the segment rule of the filter."""
-import ctypes
-import os
-import re
-
 import numpy as np
 import pytest
 
 import ar1_cases as A
+from abi_cases import check_entry, header_abi_version
 from oracle.philox_numpy import surrogate
 from xmca_amd import _hip, dist
 from xmca_amd.array import MCA
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = {"xmca_lag1_autocorrelation": 3, "xmca_rule_n_ar1": 19, "xmca_rule_n_ar1_sharded": 19, "xmca_surrogate_ar1": 9,
        "xmca_ar1_segments": 4}
 
 
-def _header():
-    text = open(os.path.join(REPO, "include", "xmca_hip.h")).read()
-    return re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-
-
 def test_new_entries_are_declared_exported_and_bound_and_the_abi_number_stays():
-    lib = _hip.load_library()
-    header = _header()
     for name, n_args in NEW.items():
-        decl = re.search(r"\b%s\s*\(([^;]*)\)\s*;" % name, header)
-        assert decl, "%s is not declared" % name
-        assert len(decl.group(1).split(",")) == n_args
-        assert hasattr(lib, name), "%s is not exported" % name
-        restype, argtypes = _hip.SIGNATURES[name]
-        assert restype is ctypes.c_int and len(argtypes) == n_args and getattr(lib, name).argtypes == list(argtypes)
+        check_entry(name, n_args)
     # the red entries take the arguments of the white ones and then the phi pair
     for white, red in [("xmca_rule_n", "xmca_rule_n_ar1"), ("xmca_rule_n_sharded", "xmca_rule_n_ar1_sharded")]:
         assert _hip.SIGNATURES[red][1][:-2] == _hip.SIGNATURES[white][1]
-    assert int(re.search(r"#define XMCA_ABI_VERSION (\d+)", header).group(1)) == 15
-    assert _hip.ABI_VERSION == 15 and lib.xmca_abi_version() == 15
+    assert header_abi_version() == _hip.ABI_VERSION == _hip.load_library().xmca_abi_version()
 
 
 def test_twin_phi_zero_is_the_white_surrogate_bit_for_bit():

@@ -1,19 +1,15 @@
 """The Theta fore/back-cast extension without a device: the numpy restatement (tests/theta_cases.py) against closed forms, the
 decomposition X_im = G0 X + B C of `_hip.theta_imag_parts` against the direct route (concatenate, scipy.signal.hilbert, trim,
 remove_mean), the new entry points of the C ABI, and the argument checks of `solve`."""
-import ctypes
-import os
-import re
-
 import numpy as np
 import pytest
 
 import theta_cases as tc
+from abi_cases import check_entry, header_abi_version
 from xmca_amd import _hip
 from xmca_amd.array import MCA
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW_SYMBOLS = ("xmca_complexify_theta", "xmca_theta_fit", "xmca_get_field_imag")
+NEW_SYMBOLS = {"xmca_complexify_theta": 5, "xmca_theta_fit": 4, "xmca_get_field_imag": None}
 
 
 def _one(f, key):
@@ -98,15 +94,9 @@ def test_test_columns_meet_the_condition_on_the_inputs():
 
 
 def test_new_entry_points_are_declared_exported_and_bound():
-    header = open(os.path.join(REPO, "include", "xmca_hip.h")).read()
-    assert re.search(r"#define XMCA_ABI_VERSION 15\b", header)
-    lib = ctypes.CDLL(_hip.library_path())
-    assert lib.xmca_abi_version() == 15
-    for name in NEW_SYMBOLS:
-        assert re.search(r"\bint %s\(" % name, header), name
-        assert name in _hip.SIGNATURES
-        assert hasattr(lib, name)
-    assert len(_hip.SIGNATURES["xmca_complexify_theta"][1]) == 5 and len(_hip.SIGNATURES["xmca_theta_fit"][1]) == 4
+    assert header_abi_version() == _hip.ABI_VERSION == _hip.load_library().xmca_abi_version()
+    for name, n_args in NEW_SYMBOLS.items():
+        check_entry(name, n_args)
 
 
 @pytest.mark.parametrize("period", [0, -3, 2.0, 13, True, None, "12"])
