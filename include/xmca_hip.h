@@ -529,6 +529,29 @@ int xmca_gap_center(xmca_handle* h, const void* X, int64_t T, int64_t N, int dty
 int xmca_gap_fill_step(xmca_handle* h, const void* A, const unsigned char* mask, const double* Z, const double* P, int64_t T, int64_t N,
                        int n_modes, int dtype, void* A_out, double* sum_out);
 int xmca_gap_fill_tile(int* rows_out, int* cols_out);
+
+/* M-SSA gap filling (Kondrashov & Ghil 2006; an extension; entry points added to ABI 15 - no existing signature
+ * changes): the iteration of xmca_fill_gaps on the lag-embedded plane [A_0 | ... | A_{M-1}], A_j = A[j tau : j tau + T', :],
+ * T' = T - (embedding - 1) tau, so that a value is rebuilt from its neighbours in time as well as in space and a time step without
+ * any present value is bridged.  Plane, mask, column means and scale are those of xmca_fill_gaps, formed once; nothing is centred
+ * again.  Iteration: G = A A^T, K = sum_j G[j tau : j tau + T', j tau : j tau + T'] (the lag sum of xmca_lag_gram, not centred),
+ * Z the n_modes leading eigenvectors of K (n_modes x T'), P_j = Z A_j, and at the masked entries only
+ * A[t][n] = (1 / c_t) sum_{j in J(t)} sum_c Z[c][t - j tau] P_j[c][n], J(t) = { j : 0 <= t - j tau < T' }, c_t = |J(t)|: the
+ * diagonally averaged rank-n_modes truncation of the embedded plane, which is never formed.
+ *   xmca_fill_gaps_lagged   the arguments of xmca_fill_gaps and embedding, tau; lam_out: the n_modes leading eigenvalues of K of the
+ *                       last iteration.  embedding == 1 is xmca_fill_gaps to the bit (tau is not looked at).  XMCA_ERR_INVALID,
+ *                       before anything is launched: what xmca_fill_gaps refuses, embedding or tau below 1, and with embedding > 1:
+ *                       T' < 2, tau > T' (time steps in no window), n_modes outside [1, min(T', embedding N) - 1].  Stage timers:
+ *                       those of xmca_fill_gaps and "gap_lag_gram".
+ *   xmca_gap_lag_fill_step  (tests) the lagged fill kernel alone on host inputs: A (T x N in `dtype`), mask bytes (non-zero: fill),
+ *                       Z (n_modes x T') and P (embedding n_modes x N, row j n_modes + c the lag-j pattern of mode c) in float64;
+ *                       A_out is the updated plane, sum_out the sum of the squared changes.  Entries with a zero mask byte come
+ *                       back with their bits.  XMCA_ERR_INVALID: T' < 1, or tau > T' with embedding > 1. */
+int xmca_fill_gaps_lagged(xmca_handle* h, const void* X, int64_t T, int64_t N, int dtype, const int64_t* cv_idx, int64_t n_cv, int n_modes,
+                          int embedding, int tau, int max_iter, double tol, void* out, double* history_out, int* iters_out,
+                          double* cv_rms_out, double* lam_out);
+int xmca_gap_lag_fill_step(xmca_handle* h, const void* A, const unsigned char* mask, const double* Z, const double* P, int64_t T, int64_t N,
+                           int n_modes, int embedding, int tau, int dtype, void* A_out, double* sum_out);
 int xmca_is_complex(xmca_handle* h);
 /* 1 when the singular vectors of `side` from the last xmca_solve are resident in float32: a real float32 field decomposed on
  * its dual side (N > T) keeps `_V` in the input's dtype as the reference does (xmca/array.py:584, the dtype of

@@ -79,6 +79,9 @@ SIGNATURES = {
     "xmca_gap_center": (_c_int, [_vp, _vp, _c_i64, _c_i64, _c_int, _vp, _vp, _vp, _dp]),
     "xmca_gap_fill_step": (_c_int, [_vp, _vp, _vp, _vp, _vp, _c_i64, _c_i64, _c_int, _c_int, _vp, _dp]),
     "xmca_gap_fill_tile": (_c_int, [_ip, _ip]),
+    "xmca_fill_gaps_lagged": (_c_int, [_vp, _vp, _c_i64, _c_i64, _c_int, _vp, _c_i64, _c_int, _c_int, _c_int, _c_int, _c_dbl, _vp, _vp, _ip,
+                                       _dp, _vp]),
+    "xmca_gap_lag_fill_step": (_c_int, [_vp, _vp, _vp, _vp, _vp, _c_i64, _c_i64, _c_int, _c_int, _c_int, _c_int, _vp, _dp]),
     "xmca_correlate": (_c_int, [_vp, _c_int, _vp, _c_i64, _c_i64, _vp]),
     "xmca_pearson_pvalues": (_c_int, [_vp, _vp, _c_i64, _c_i64, _vp]),
     "xmca_pvalue_log_norm": (_c_int, [_c_i64, _dp]),
@@ -1129,11 +1132,12 @@ class Handle:
         self._check(self._lib.xmca_lag_project(self._h, _ptr(W), W.shape[0], M, tau, k, _ptr(out)))
         return out
 
-    def fill_gaps(self, X, n_modes, max_iter, tol, cv_idx=None):
+    def fill_gaps(self, X, n_modes, max_iter, tol, cv_idx=None, embedding=None, tau=1):
         """DINEOF gap filling of the T x N float32 / float64 field `X` with NaN gaps (xmca_fill_gaps): (field, history, cv_rms, lam) -
         X with its gaps filled, in X's dtype and with the present entries untouched; the relative changes d_i of the iterations run;
         the RMS error at the withheld entries `cv_idx` (flat indices of present entries; None without any); the n_modes leading
-        eigenvalues of the last iterate's Gram matrix.  Resident fields and the result of a solve stay as they are."""
+        eigenvalues of the last iterate's Gram matrix.  Resident fields and the result of a solve stay as they are.
+        With `embedding` (see `fill_gaps_lagged`) the call goes through xmca_fill_gaps_lagged."""
         X = _gap_plane("fill_gaps", X)
         T, N = X.shape
         idx = None if cv_idx is None else np.ascontiguousarray(cv_idx, dtype=np.int64).ravel()
@@ -1145,9 +1149,18 @@ class Handle:
         history = np.full(max_iter, np.nan, dtype=np.float64)
         lam = np.empty(max(k, 1), dtype=np.float64)
         iters, cv_rms = _c_int(0), _c_dbl(np.nan)
-        self._check(self._lib.xmca_fill_gaps(self._h, _ptr(X), T, N, _np_dtype_code(X.dtype), _ptr(idx) if n_cv else None, n_cv, k, max_iter,
-                                             float(tol), _ptr(out), _ptr(history), ctypes.byref(iters), ctypes.byref(cv_rms), _ptr(lam)))
+        head = (self._h, _ptr(X), T, N, _np_dtype_code(X.dtype), _ptr(idx) if n_cv else None, n_cv, k)
+        tail = (max_iter, float(tol), _ptr(out), _ptr(history), ctypes.byref(iters), ctypes.byref(cv_rms), _ptr(lam))
+        if embedding is None:
+            self._check(self._lib.xmca_fill_gaps(*head, *tail))
+        else:
+            self._check(self._lib.xmca_fill_gaps_lagged(*head, int(embedding), int(tau), *tail))
         return out, history[:iters.value].copy(), (float(cv_rms.value) if n_cv else None), lam[:k]
+
+    def fill_gaps_lagged(self, X, n_modes, embedding, tau, max_iter, tol, cv_idx=None):
+        """M-SSA gap filling (xmca_fill_gaps_lagged): `fill_gaps` on the plane embedded with `embedding` windows `tau` steps apart;
+        lam are the leading eigenvalues of the lag-summed Gram matrix.  embedding = 1 gives the bits of `fill_gaps`."""
+        return self.fill_gaps(X, n_modes, max_iter, tol, cv_idx=cv_idx, embedding=embedding, tau=tau)
 
     def gap_center(self, X):
         """(tests) The centring and mask kernels of `fill_gaps` on a host field (xmca_gap_center): (mean, mask, A, scale) - the N column
@@ -1178,6 +1191,28 @@ class Handle:
         total = _c_dbl(0.0)
         self._check(self._lib.xmca_gap_fill_step(self._h, _ptr(A), _ptr(mask), _ptr(Z), _ptr(P), T, N, Z.shape[0], _np_dtype_code(A.dtype),
                                                  _ptr(out), ctypes.byref(total)))
+        return out, float(total.value)
+
+    def gap_lag_fill_step(self, A, mask, Z, P, embedding, tau):
+        """(tests) The lagged fill kernel of `fill_gaps(embedding=)` on host inputs (xmca_gap_lag_fill_step): (A_new, sum) - the T x N
+        float32 / float64 plane `A` with the diagonally averaged sum_j Z[:, t - j tau] . P[j k : (j + 1) k, n] written where `mask`
+        (T x N bytes) is non-zero, Z k x T' and P embedding k x N in float64, T' = T - (embedding - 1) tau, and the sum of the squared
+        changes."""
+        A = _gap_plane("gap_lag_fill_step", A)
+        T, N = A.shape
+        M, tau = int(embedding), int(tau)
+        mask = np.ascontiguousarray(mask, dtype=np.uint8)
+        Z = np.ascontiguousarray(Z, dtype=np.float64)
+        P = np.ascontiguousarray(P, dtype=np.float64)
+        if M < 1 or tau < 1:
+            raise ValueError("gap_lag_fill_step: embedding and tau must be at least 1")
+        if mask.shape != (T, N) or Z.ndim != 2 or Z.shape[0] < 1 or Z.shape[1] != T - (M - 1) * tau or P.shape != (M * Z.shape[0], N):
+            raise ValueError("gap_lag_fill_step: need a T x N mask, Z of k x T' and P of embedding k x N, got %s, %s, %s"
+                             % (mask.shape, Z.shape, P.shape))
+        out = np.empty_like(A)
+        total = _c_dbl(0.0)
+        self._check(self._lib.xmca_gap_lag_fill_step(self._h, _ptr(A), _ptr(mask), _ptr(Z), _ptr(P), T, N, Z.shape[0], M, tau,
+                                                     _np_dtype_code(A.dtype), _ptr(out), ctypes.byref(total)))
         return out, float(total.value)
 
     def lag_expand(self, Z, embedding, tau, with_indicators):

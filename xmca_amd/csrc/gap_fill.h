@@ -148,6 +148,97 @@ __global__ __launch_bounds__(GAP_COLS) void gap_fill_kernel(TI* __restrict__ A, 
   if (tid == 0) part[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = change;
 }
 
+// The fill step of the lag-embedded iteration (M-SSA gap filling): Z is k x Tp, Tp = T - (M - 1) tau, P holds M
+// planes of k x N (row j k + c the lag-j pattern of mode c), and the diagonally averaged reconstruction
+//   A[t][n] <- (1 / c_t) sum_{j in J(t)} sum_{c < k} Z[c][t - j tau] P[j k + c][n],   J(t) = { j < M : 0 <= t - j tau < Tp },  c_t = |J(t)|
+// replaces A at the masked entries only; the embedded coefficient plane is never formed.  Layout as gap_fill_kernel: a workgroup
+// owns GAP_ROWS x GAP_COLS, a lane one column.  The lane keeps the accumulators and the mask bits of a piece of R rows in registers
+// (R = GAP_LAG_ROWS; the taller pieces are kept for measurements, see gap_lag_rows) and walks (lag, chunk of modes) outermost, so
+// its GAP_KC values of P are loaded once per (lag, chunk) and piece; per (lag, chunk) the band Z[c0 .. c0 + GAP_KC)[t0 - j tau .. t0 - j tau + R) goes through LDS (rows padded by one double:
+// the staging writes of a wave then spread over the banks) and is read back as broadcasts.  The sum runs j ascending, then c
+// ascending, as one fma chain in float64, then times 1 / c_t, c_t from (t, M, tau, Tp) in closed form: the order depends on the
+// shape alone.  part[tile] as in gap_fill_kernel.
+// Bounds: a Z value is read only for c < k and 0 <= t - j tau < Tp - elsewhere a zero is staged, and a row takes no term from a
+// lag outside J(t) at all; a lag with no row of the piece in its window is skipped whole (uniformly: the barriers stay matched),
+// P with it.  Mask and A as in gap_fill_kernel.  The caller guarantees tau <= Tp when M > 1, so c_t >= 1.
+constexpr int GAP_LAG_ROWS = GAP_SUB;            // rows whose accumulators a lane holds: P is read GAP_ROWS / GAP_LAG_ROWS times per tile
+constexpr int GAP_LAG_PAD = GAP_KC + 1;
+static_assert(GAP_ROWS % GAP_LAG_ROWS == 0 && GAP_LAG_ROWS <= 64, "the mask bits of a piece fit one 64-bit word");
+
+// (the second launch bound is the occupancy the form reaches without scratch: 141 and 166 VGPRs at R = 16 and 32, 256 at R = 64)
+
+template <typename TI, int R>
+__global__ __launch_bounds__(GAP_COLS, R > 32 ? 2 : 3) void gap_lag_fill_kernel(TI* __restrict__ A, const unsigned char* __restrict__ mask,
+                                                                const double* __restrict__ Z, const double* __restrict__ P, int T,
+                                                                int64_t N, int k, int M, int tau, int Tp, double* __restrict__ part) {
+  __shared__ double zs[R][GAP_LAG_PAD];
+  __shared__ double red[4];
+  const int tid = threadIdx.x;
+  const int64_t n = (int64_t)blockIdx.x * GAP_COLS + tid;
+  const bool live = n < N;
+  const int t_begin = (int)blockIdx.y * GAP_ROWS;
+  const int t_end = t_begin + GAP_ROWS < T ? t_begin + GAP_ROWS : T;
+  const int n_chunks = (k + GAP_KC - 1) / GAP_KC;
+  double change = 0.0;
+  for (int t0 = t_begin; t0 < t_end; t0 += R) {
+    const int rows = t_end - t0 < R ? t_end - t0 : R;
+    unsigned long long m = 0;
+    double acc[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      if (live && r < rows && mask[(int64_t)(t0 + r) * N + n]) m |= 1ull << r;
+      acc[r] = 0.0;
+    }
+    for (int j = 0; j < M; ++j) {
+      const int s0 = t0 - j * tau;                 // the window row of the piece's first row at this lag
+      if (s0 + rows <= 0 || s0 >= Tp) continue;    // no row of the piece lies in window j
+      const int r_lo = s0 < 0 ? -s0 : 0, r_hi = Tp - s0 < rows ? Tp - s0 : rows;          // its rows in window j: [r_lo, r_hi)
+      const unsigned long long mj = m & ((~0ull >> (64 - r_hi)) & (~0ull << r_lo));
+      for (int ch = 0; ch < n_chunks; ++ch) {
+        const int c0 = ch * GAP_KC;
+        double p[GAP_KC];
+#pragma unroll
+        for (int c = 0; c < GAP_KC; ++c) p[c] = (live && c0 + c < k) ? P[((int64_t)j * k + c0 + c) * N + n] : 0.0;
+        __syncthreads();          // the readers of the previous band are through
+        for (int e = tid; e < GAP_KC * R; e += GAP_COLS) {
+          const int c = e / R, r = e % R, s = s0 + r;
+          zs[r][c] = (c0 + c < k && r < rows && s >= 0 && s < Tp) ? Z[(int64_t)(c0 + c) * Tp + s] : 0.0;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+          if ((mj >> r) & 1ull) {
+            double a = acc[r];
+#pragma unroll
+            for (int c = 0; c < GAP_KC; ++c) a = fma(zs[r][c], p[c], a);
+            acc[r] = a;
+          }
+        }
+      }
+    }
+    // c_t = j_hi - j_lo + 1: j_hi = min(floor(t / tau), M - 1) is the last lag with t - j tau >= 0, j_lo = floor(u / tau) for
+    // u = t - Tp + tau > 0 (else 0) the first with t - j tau <= Tp - 1.  Two divisions per piece, then quotient and remainder
+    // are stepped row by row (a negative u counts up to 0 with the quotient at 0).
+    int q_hi = t0 / tau, e_hi = t0 % tau;
+    const int u0 = t0 - Tp + tau;
+    int q_lo = u0 > 0 ? u0 / tau : 0, e_lo = u0 > 0 ? u0 % tau : u0;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      if ((m >> r) & 1ull) {
+        const int64_t i = (int64_t)(t0 + r) * N + n;
+        const TI v = (TI)(acc[r] * (1.0 / (double)((q_hi < M - 1 ? q_hi : M - 1) - q_lo + 1)));
+        const double d = (double)v - (double)A[i];
+        change = fma(d, d, change);
+        A[i] = v;
+      }
+      if (++e_hi == tau) { e_hi = 0; ++q_hi; }
+      if (++e_lo == tau) { e_lo = 0; ++q_lo; }
+    }
+  }
+  change = block_sum_256(change, red);
+  if (tid == 0) part[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = change;
+}
+
 // Polish of the k leading rows of an eigenvector basis V (n x n, row j the vector of lam[j], descending).  The block Jacobi sweeps
 // leave couplings below 2e-15 lam[0] unrotated, which tilts the leading subspace by that over the gap lam[k-1] - lam[k]; the fill
 // depends on nothing but this subspace, and the iteration carries the tilt along.  With S[i][j] = v_i G v_j^T the first-order
@@ -240,6 +331,35 @@ static inline void gap_fill_step(hipStream_t st, TI* A, const unsigned char* mas
                                  double* part) {
   const dim3 grid((unsigned)ceil_div(N, GAP_COLS), (unsigned)ceil_div(T, GAP_ROWS));
   hipLaunchKernelGGL((gap_fill_kernel<TI>), grid, dim3(GAP_COLS), 0, st, A, mask, Z, P, T, N, k, part);
+  XMCA_HIP(hipGetLastError());
+}
+
+// XMCA_GAP_LAG_ROWS=32 / 64: the lagged fill with the accumulators of half a tile (P read twice per tile) or of the whole tile
+// (P read once, two waves per SIMD) per lane instead of GAP_LAG_ROWS rows (measurements)
+static inline int gap_lag_rows() {
+  static const int rows = [] {
+    const char* e = std::getenv("XMCA_GAP_LAG_ROWS");
+    const int v = e ? std::atoi(e) : GAP_LAG_ROWS;
+    return v == GAP_ROWS / 2 || v == GAP_ROWS ? v : GAP_LAG_ROWS;
+  }();
+  return rows;
+}
+
+// One fill step of the lag-embedded iteration on the plane A: Z k x Tp, P M k x N, Tp = T - (M - 1) tau >= 1, tau <= Tp when
+// M > 1 (both the caller's to check); part: gap_fill_tiles(T, N) doubles
+template <typename TI>
+static inline void gap_lag_fill_step(hipStream_t st, TI* A, const unsigned char* mask, const double* Z, const double* P, int T, int64_t N,
+                                     int k, int M, int tau, double* part) {
+  const int Tp = T - (M - 1) * tau;
+  XMCA_CHECK(M >= 1 && tau >= 1 && Tp >= 1 && (M == 1 || tau <= Tp), XMCA_ERR_INVALID, "gap_lag_fill: the embedding does not fit the field");
+  const dim3 grid((unsigned)ceil_div(N, GAP_COLS), (unsigned)ceil_div(T, GAP_ROWS));
+  const int rows = gap_lag_rows();
+  if (rows == GAP_ROWS / 2)
+    hipLaunchKernelGGL((gap_lag_fill_kernel<TI, GAP_ROWS / 2>), grid, dim3(GAP_COLS), 0, st, A, mask, Z, P, T, N, k, M, tau, Tp, part);
+  else if (rows == GAP_ROWS)
+    hipLaunchKernelGGL((gap_lag_fill_kernel<TI, GAP_ROWS>), grid, dim3(GAP_COLS), 0, st, A, mask, Z, P, T, N, k, M, tau, Tp, part);
+  else
+    hipLaunchKernelGGL((gap_lag_fill_kernel<TI, GAP_LAG_ROWS>), grid, dim3(GAP_COLS), 0, st, A, mask, Z, P, T, N, k, M, tau, Tp, part);
   XMCA_HIP(hipGetLastError());
 }
 

@@ -1802,18 +1802,22 @@ void gap_check_withheld(const TI* X, int64_t total, const int64_t* cv_idx, int64
   }
 }
 
-// xmca_fill_gaps: the raw plane stays on the device and only its missing entries are written at the end, so present entries come
-// back with their bits.  One iteration is the Gram product of the working plane A, its k leading eigenvectors Z, P = Z A and the
-// fill kernel; the change d_i comes back to the host after every iteration (the eigensolver has synchronised the stream before).
-// Every buffer is this call's own.
+// xmca_fill_gaps, xmca_fill_gaps_lagged: the raw plane stays on the device and only its missing entries are written at the end, so
+// present entries come back with their bits.  One iteration is the Gram product G of the working plane A, the k leading
+// eigenvectors Z of K, P = Z A on the M lagged views of A and the fill kernel; the change d_i comes back to the host after every
+// iteration (the eigensolver has synchronised the stream before).  M = 1 (DINEOF): K is G itself and the fill is
+// gap_fill_kernel.  M > 1 (M-SSA gap filling): K is the lag sum of G (csrc/lag_gram.h, not centred), T' x T' with
+// T' = T - (M - 1) tau, and the fill is the diagonally averaged gap_lag_fill_kernel.  The eigensolver's route, the Z plane and
+// the polish are all taken at T'.  Every buffer is this call's own.
 template <typename TI>
-void fill_gaps_impl(xmca_handle* h, const TI* X, int T, int64_t N, int64_t n_present, const int64_t* cv_idx, int64_t n_cv, int k, int max_iter,
-                    double tol, TI* out, double* history_out, int* iters_out, double* cv_rms_out, double* lam_out) {
+void fill_gaps_impl(xmca_handle* h, const TI* X, int T, int64_t N, int64_t n_present, const int64_t* cv_idx, int64_t n_cv, int k, int M, int tau,
+                    int max_iter, double tol, TI* out, double* history_out, int* iters_out, double* cv_rms_out, double* lam_out) {
   const size_t total = (size_t)T * N;
+  const int Tp = T - (M - 1) * tau;
   const int64_t tiles = gap_fill_tiles(T, N);
   DevBuf<TI> raw, A, saved;
   DevBuf<unsigned char> mask;
-  DevBuf<double> mean, stat, part, P, Z, lam_dev, hist, cv, W, S, Zp;
+  DevBuf<double> mean, stat, part, P, Z, lam_dev, hist, cv, W, S, Zp, K, lag_part, lag_mean;
   DevBuf<int64_t> idx;
   GapCenterScratch scratch;
   CPlanes G;
@@ -1839,48 +1843,57 @@ void fill_gaps_impl(xmca_handle* h, const TI* X, int T, int64_t N, int64_t n_pre
   f.ext_re = A.get();
   Solver<TI> s(h->st, h->gws, h->ews, h->tm);
   std::vector<double> lam;
-  P.ensure((size_t)k * N);
-  // Where the eigensolver takes the block Jacobi sweeps it forms all T vectors whatever is asked for: they are all taken, and the
+  P.ensure((size_t)M * k * N);
+  if (M > 1) K.ensure((size_t)Tp * Tp);
+  // Where the eigensolver takes the block Jacobi sweeps it forms all T' vectors whatever is asked for: they are all taken, and the
   // leading k are polished against the others (csrc/gap_fill.h).  On the tridiagonal route the partial stage gives the leading k
   // alone and nothing is polished.  Not covered: a problem that the partial stage hands back to the sweeps (bit-equal leading
   // eigenvalues, a refused clean-up) comes back as k unpolished Jacobi vectors.
-  const bool polish = !evd_vectors_by_reduction(T, false);
-  Z.ensure((size_t)(polish ? T : k) * T);
-  if (polish) { W.ensure((size_t)k * T); S.ensure((size_t)k * T); Zp.ensure((size_t)k * T); }
-  lam_dev.ensure((size_t)T);
+  const bool polish = !evd_vectors_by_reduction(Tp, false);
+  Z.ensure((size_t)(polish ? Tp : k) * Tp);
+  if (polish) { W.ensure((size_t)k * Tp); S.ensure((size_t)k * Tp); Zp.ensure((size_t)k * Tp); }
+  lam_dev.ensure((size_t)Tp);
   part.ensure((size_t)tiles);
   hist.ensure((size_t)max_iter);
   int iters = 0;
   for (int i = 0; i < max_iter; ++i) {
     s.gram(f, false, G);
+    const double* Km = G.r();
+    if (M > 1) {
+      h->tm.begin("gap_lag_gram");
+      lag_gram(h->st, G.r(), T, T, M, tau, false, K.get(), lag_part, lag_mean);
+      h->tm.end();
+      Km = K.get();
+    }
     EvdInfo info;
     h->tm.begin("gap_eigh");
-    hermitian_evd(h->st, h->ews, G.r(), nullptr, T, T, lam, lam_dev.get(), Z.get(), nullptr, T, &info, false, polish ? -1 : k);
+    hermitian_evd(h->st, h->ews, Km, nullptr, Tp, Tp, lam, lam_dev.get(), Z.get(), nullptr, Tp, &info, false, polish ? -1 : k);
     XMCA_HIP(hipStreamSynchronize(h->st));
     const bool usable = std::isfinite(lam[0]) && lam[0] > 0.0;
     const double* Zk = Z.get();
-    if (polish && usable) {         // (csrc/gap_fill.h gap_polish_coeff_kernel) S = (Z_k G) Z^T, O = Z_k Z^T, coefficients, Z_k += C Z
+    if (polish && usable) {         // (csrc/gap_fill.h gap_polish_coeff_kernel) S = (Z_k K) Z^T, O = Z_k Z^T, coefficients, Z_k += C Z
       GemmOpts o;
-      gemm<double, double>(h->st, h->gws, (const double*)Z.get(), T, (const double*)G.r(), T, W.get(), T, k, T, T, o);
+      gemm<double, double>(h->st, h->gws, (const double*)Z.get(), Tp, Km, Tp, W.get(), Tp, k, Tp, Tp, o);
       o.b_nfast = false;
-      gemm<double, double>(h->st, h->gws, (const double*)W.get(), T, (const double*)Z.get(), T, S.get(), T, k, T, T, o);
-      gemm<double, double>(h->st, h->gws, (const double*)Z.get(), T, (const double*)Z.get(), T, W.get(), T, k, T, T, o);
-      hipLaunchKernelGGL(gap_polish_coeff_kernel, ew_grid((int64_t)k * T), dim3(EW_BLOCK), 0, h->st, S.get(), (const double*)W.get(),
-                         (const double*)lam_dev.get(), k, T);
+      gemm<double, double>(h->st, h->gws, (const double*)W.get(), Tp, (const double*)Z.get(), Tp, S.get(), Tp, k, Tp, Tp, o);
+      gemm<double, double>(h->st, h->gws, (const double*)Z.get(), Tp, (const double*)Z.get(), Tp, W.get(), Tp, k, Tp, Tp, o);
+      hipLaunchKernelGGL(gap_polish_coeff_kernel, ew_grid((int64_t)k * Tp), dim3(EW_BLOCK), 0, h->st, S.get(), (const double*)W.get(),
+                         (const double*)lam_dev.get(), k, Tp);
       XMCA_HIP(hipGetLastError());
-      XMCA_HIP(hipMemcpyAsync(Zp.get(), Z.get(), sizeof(double) * (size_t)k * T, hipMemcpyDeviceToDevice, h->st));
+      XMCA_HIP(hipMemcpyAsync(Zp.get(), Z.get(), sizeof(double) * (size_t)k * Tp, hipMemcpyDeviceToDevice, h->st));
       o.b_nfast = true;
       o.beta = 1.0;
-      gemm<double, double>(h->st, h->gws, (const double*)S.get(), T, (const double*)Z.get(), T, Zp.get(), T, k, T, T, o);
+      gemm<double, double>(h->st, h->gws, (const double*)S.get(), Tp, (const double*)Z.get(), Tp, Zp.get(), Tp, k, Tp, Tp, o);
       Zk = Zp.get();
     }
     h->tm.end();
     XMCA_CHECK(usable, XMCA_ERR_NUMERIC, "fill_gaps: the iterate has no variance");
     h->tm.begin("gap_project");
-    lag_back_project<TI>(h, z, Zk, k, T, 1, 1, (const TI*)A.get(), N, nullptr, P.get());
+    lag_back_project<TI>(h, z, Zk, k, Tp, M, tau, (const TI*)A.get(), N, nullptr, P.get());
     h->tm.end();
     h->tm.begin("gap_fill");
-    gap_fill_step<TI>(h->st, A.get(), mask.get(), Zk, P.get(), T, N, k, part.get());
+    if (M == 1) gap_fill_step<TI>(h->st, A.get(), mask.get(), Zk, P.get(), T, N, k, part.get());
+    else gap_lag_fill_step<TI>(h->st, A.get(), mask.get(), Zk, P.get(), T, N, k, M, tau, part.get());
     hipLaunchKernelGGL(gap_change_kernel, dim3(1), dim3(256), 0, h->st, (const double*)part.get(), tiles, n_masked, (const double*)stat.get(),
                        hist.get() + i, (double*)nullptr);
     XMCA_HIP(hipGetLastError());
@@ -1943,6 +1956,30 @@ void gap_fill_step_impl(xmca_handle* h, const TI* A_in, const unsigned char* mas
   XMCA_HIP(hipMemcpyAsync(P.ensure((size_t)k * N), P_in, sizeof(double) * (size_t)k * N, hipMemcpyHostToDevice, h->st));
   h->tm.begin("gap_fill");
   gap_fill_step<TI>(h->st, A.get(), mask.get(), Z.get(), P.get(), T, N, k, part.ensure((size_t)tiles));
+  hipLaunchKernelGGL(gap_change_kernel, dim3(1), dim3(256), 0, h->st, (const double*)part.get(), tiles, 0.0, (const double*)nullptr,
+                     (double*)nullptr, sum.ensure(1));
+  XMCA_HIP(hipGetLastError());
+  h->tm.end();
+  XMCA_HIP(hipMemcpyAsync(A_out, A.get(), sizeof(TI) * total, hipMemcpyDeviceToHost, h->st));
+  XMCA_HIP(hipMemcpyAsync(sum_out, sum.get(), sizeof(double), hipMemcpyDeviceToHost, h->st));
+  XMCA_HIP(hipStreamSynchronize(h->st));
+}
+
+// (tests) xmca_gap_lag_fill_step: the lagged fill kernel and the finish of its partial sums alone; Z k x T', P M k x N
+template <typename TI>
+void gap_lag_fill_step_impl(xmca_handle* h, const TI* A_in, const unsigned char* mask_in, const double* Z_in, const double* P_in, int T,
+                            int64_t N, int k, int M, int tau, TI* A_out, double* sum_out) {
+  const size_t total = (size_t)T * N, nz = (size_t)k * (size_t)(T - (M - 1) * tau), np = (size_t)M * k * N;
+  const int64_t tiles = gap_fill_tiles(T, N);
+  DevBuf<TI> A;
+  DevBuf<unsigned char> mask;
+  DevBuf<double> Z, P, part, sum;
+  XMCA_HIP(hipMemcpyAsync(A.ensure(total), A_in, sizeof(TI) * total, hipMemcpyHostToDevice, h->st));
+  XMCA_HIP(hipMemcpyAsync(mask.ensure(total), mask_in, total, hipMemcpyHostToDevice, h->st));
+  XMCA_HIP(hipMemcpyAsync(Z.ensure(nz), Z_in, sizeof(double) * nz, hipMemcpyHostToDevice, h->st));
+  XMCA_HIP(hipMemcpyAsync(P.ensure(np), P_in, sizeof(double) * np, hipMemcpyHostToDevice, h->st));
+  h->tm.begin("gap_fill");
+  gap_lag_fill_step<TI>(h->st, A.get(), mask.get(), Z.get(), P.get(), T, N, k, M, tau, part.ensure((size_t)tiles));
   hipLaunchKernelGGL(gap_change_kernel, dim3(1), dim3(256), 0, h->st, (const double*)part.get(), tiles, 0.0, (const double*)nullptr,
                      (double*)nullptr, sum.ensure(1));
   XMCA_HIP(hipGetLastError());
@@ -2703,13 +2740,24 @@ int xmca_gap_fill_tile(int* rows_out, int* cols_out) {
   return XMCA_OK;
 }
 
-int xmca_fill_gaps(xmca_handle* h, const void* X, int64_t T, int64_t N, int dtype, const int64_t* cv_idx, int64_t n_cv, int n_modes,
-                   int max_iter, double tol, void* out, double* history_out, int* iters_out, double* cv_rms_out, double* lam_out) {
-  API_BEGIN(h)
+// The checks and the call shared by xmca_fill_gaps (embedding = tau = 1) and xmca_fill_gaps_lagged
+static void fill_gaps_entry(xmca_handle* h, const void* X, int64_t T, int64_t N, int dtype, const int64_t* cv_idx, int64_t n_cv, int n_modes,
+                            int embedding, int tau, int max_iter, double tol, void* out, double* history_out, int* iters_out,
+                            double* cv_rms_out, double* lam_out) {
   XMCA_CHECK(X && out && history_out && iters_out && cv_rms_out && lam_out && n_cv >= 0 && (cv_idx || n_cv == 0), XMCA_ERR_INVALID,
              "fill_gaps: bad arguments");
   check_gap_plane("fill_gaps", T, N, dtype);
-  XMCA_CHECK(n_modes >= 1 && n_modes <= std::min(T, N) - 1, XMCA_ERR_INVALID, "fill_gaps: n_modes must lie in [1, min(T, N) - 1]");
+  XMCA_CHECK(embedding >= 1 && tau >= 1, XMCA_ERR_INVALID, "fill_gaps: embedding and tau must be at least 1");
+  const int64_t np = T - (int64_t)(embedding - 1) * tau;
+  if (embedding == 1) {
+    XMCA_CHECK(n_modes >= 1 && n_modes <= std::min(T, N) - 1, XMCA_ERR_INVALID, "fill_gaps: n_modes must lie in [1, min(T, N) - 1]");
+  } else {
+    XMCA_CHECK(np >= 2, XMCA_ERR_INVALID, "fill_gaps: T - (embedding - 1) * tau must be at least 2");
+    XMCA_CHECK(tau <= np, XMCA_ERR_INVALID, "fill_gaps: tau above T' leaves time steps outside every window (no reconstruction there)");
+    XMCA_CHECK(n_modes >= 1 && n_modes <= std::min<int64_t>(np, (int64_t)embedding * N) - 1, XMCA_ERR_INVALID,
+               "fill_gaps: n_modes must lie in [1, min(T', embedding * N) - 1]");
+    XMCA_CHECK((int64_t)embedding * n_modes * N < ((int64_t)1 << 34), XMCA_ERR_UNSUPPORTED, "fill_gaps: coefficient matrices too large");
+  }
   XMCA_CHECK(max_iter >= 1, XMCA_ERR_INVALID, "fill_gaps: max_iter must be at least 1");
   XMCA_CHECK(std::isfinite(tol) && tol >= 0.0, XMCA_ERR_INVALID, "fill_gaps: tol must be finite and not negative");
   with_dtype(dtype, [&](auto t) {
@@ -2717,9 +2765,23 @@ int xmca_fill_gaps(xmca_handle* h, const void* X, int64_t T, int64_t N, int dtyp
     const TI* Xt = static_cast<const TI*>(X);
     const int64_t n_present = gap_check_field<TI>("fill_gaps", Xt, T, N);
     gap_check_withheld<TI>(Xt, T * N, cv_idx, n_cv);
-    fill_gaps_impl<TI>(h, Xt, (int)T, N, n_present, cv_idx, n_cv, n_modes, max_iter, tol, static_cast<TI*>(out), history_out, iters_out,
-                       cv_rms_out, lam_out);
+    fill_gaps_impl<TI>(h, Xt, (int)T, N, n_present, cv_idx, n_cv, n_modes, embedding, embedding == 1 ? 1 : tau, max_iter, tol,
+                       static_cast<TI*>(out), history_out, iters_out, cv_rms_out, lam_out);
   });
+}
+
+int xmca_fill_gaps(xmca_handle* h, const void* X, int64_t T, int64_t N, int dtype, const int64_t* cv_idx, int64_t n_cv, int n_modes,
+                   int max_iter, double tol, void* out, double* history_out, int* iters_out, double* cv_rms_out, double* lam_out) {
+  API_BEGIN(h)
+  fill_gaps_entry(h, X, T, N, dtype, cv_idx, n_cv, n_modes, 1, 1, max_iter, tol, out, history_out, iters_out, cv_rms_out, lam_out);
+  API_END(h)
+}
+
+int xmca_fill_gaps_lagged(xmca_handle* h, const void* X, int64_t T, int64_t N, int dtype, const int64_t* cv_idx, int64_t n_cv, int n_modes,
+                          int embedding, int tau, int max_iter, double tol, void* out, double* history_out, int* iters_out,
+                          double* cv_rms_out, double* lam_out) {
+  API_BEGIN(h)
+  fill_gaps_entry(h, X, T, N, dtype, cv_idx, n_cv, n_modes, embedding, tau, max_iter, tol, out, history_out, iters_out, cv_rms_out, lam_out);
   API_END(h)
 }
 
@@ -2745,6 +2807,24 @@ int xmca_gap_fill_step(xmca_handle* h, const void* A, const unsigned char* mask,
   with_dtype(dtype, [&](auto t) {
     using TI = decltype(t);
     gap_fill_step_impl<TI>(h, static_cast<const TI*>(A), mask, Z, P, (int)T, N, n_modes, static_cast<TI*>(A_out), sum_out);
+  });
+  API_END(h)
+}
+
+int xmca_gap_lag_fill_step(xmca_handle* h, const void* A, const unsigned char* mask, const double* Z, const double* P, int64_t T, int64_t N,
+                           int n_modes, int embedding, int tau, int dtype, void* A_out, double* sum_out) {
+  API_BEGIN(h)
+  XMCA_CHECK(A && mask && Z && P && A_out && sum_out && n_modes >= 1, XMCA_ERR_INVALID, "gap_lag_fill_step: bad arguments");
+  check_gap_plane("gap_lag_fill_step", T, N, dtype);
+  XMCA_CHECK(embedding >= 1 && tau >= 1, XMCA_ERR_INVALID, "gap_lag_fill_step: embedding and tau must be at least 1");
+  const int64_t np = T - (int64_t)(embedding - 1) * tau;
+  XMCA_CHECK(np >= 1 && (embedding == 1 || tau <= np), XMCA_ERR_INVALID,
+             "gap_lag_fill_step: T - (embedding - 1) * tau must be at least 1, and at least tau when embedding > 1");
+  XMCA_CHECK((int64_t)embedding * n_modes * std::max(T, N) < ((int64_t)1 << 34), XMCA_ERR_UNSUPPORTED,
+             "gap_lag_fill_step: coefficient matrices too large");
+  with_dtype(dtype, [&](auto t) {
+    using TI = decltype(t);
+    gap_lag_fill_step_impl<TI>(h, static_cast<const TI*>(A), mask, Z, P, (int)T, N, n_modes, embedding, tau, static_cast<TI*>(A_out), sum_out);
   });
   API_END(h)
 }

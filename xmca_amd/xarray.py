@@ -344,13 +344,14 @@ class xMCA(MCA):
             self.apply_coslat()
 
 
-def fill_gaps(da, n_modes, max_iter=300, tol=1e-5, cv_fraction=None, cv_idx=None, seed=None, handle=None):
+def fill_gaps(da, n_modes, max_iter=300, tol=1e-5, cv_fraction=None, cv_idx=None, seed=None, handle=None, embedding=1, tau=1):
     """`xmca_amd.gaps.fill_gaps` of a DataArray whose first dimension is time: the same dict with 'field' as a DataArray over the
     dims, coordinates and attrs of `da`.  `cv_idx` holds flat indices into `da.values.reshape(T, -1)`."""
     xr = _xr()
     if not isinstance(da, xr.DataArray):
         raise TypeError("fill_gaps: the field is not an `xarray.DataArray`")
-    out = _gaps.fill_gaps(da.values, n_modes, max_iter=max_iter, tol=tol, cv_fraction=cv_fraction, cv_idx=cv_idx, seed=seed, handle=handle)
+    out = _gaps.fill_gaps(da.values, n_modes, max_iter=max_iter, tol=tol, cv_fraction=cv_fraction, cv_idx=cv_idx, seed=seed, handle=handle,
+                          embedding=embedding, tau=tau)
     out['field'] = xr.DataArray(out['field'], dims=da.dims, coords=da.coords, attrs=dict(da.attrs), name=da.name)
     return out
 
