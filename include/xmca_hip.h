@@ -552,6 +552,46 @@ int xmca_fill_gaps_lagged(xmca_handle* h, const void* X, int64_t T, int64_t N, i
                           double* cv_rms_out, double* lam_out);
 int xmca_gap_lag_fill_step(xmca_handle* h, const void* A, const unsigned char* mask, const double* Z, const double* P, int64_t T, int64_t N,
                            int n_modes, int embedding, int tau, int dtype, void* A_out, double* sum_out);
+
+/* Column regression: seasonal cycle and trend removed on the device (an extension; entry points added to ABI 15 -
+ * no existing signature changes).  Every column of the T x N field X (NaN = missing) is fitted by least squares on the k columns
+ * of `basis` (T x k float64, row-major, host memory) over its present entries, in float64 whatever `dtype`:
+ * (sum_present b_t b_t^T) c = sum_present b_t x_t, by Cholesky in the order of the basis columns.  A column is FITTED when it has at
+ * least k present entries and every pivot d_j = A[j][j] - sum_{i<j} L[j][i]^2 exceeds 1e-8 A[j][j]; the residual x - B c, one
+ * float64 fma chain c = 0 .. k-1 from x rounded once to `dtype`, replaces its present entries.  Missing entries and the columns
+ * that are not fitted come back NaN.
+ *   X, in_location      XMCA_HOST: contiguous host memory (the strides are not looked at);  XMCA_DEVICE: memory of the handle's GPU,
+ *                       element (t, n) at X[t * stride_t + n * stride_n] (strides in elements, >= 0), copied by the kernels of
+ *                       xmca_set_field_strided into a buffer of this call - the caller's memory is only read
+ *   xmca_column_regress field_out, out_location  T x N in `dtype`, contiguous: host memory, or (XMCA_DEVICE, as xmca_correlation_maps_to)
+ *                       memory of the handle's GPU that the residual kernel writes directly
+ *                       coef_out       k x N float64 (host): the coefficients, NaN where the column is not fitted
+ *                       fitted_out     N bytes (host): 1 fitted, 0 not
+ *                       XMCA_ERR_INVALID, before anything is launched: k outside [1, 16], T < 1, N < 1, a bad dtype or location, a
+ *                       negative stride, a device pointer that is none of the handle's GPU.  Not checked: an Inf in X (the caller's).
+ *                       The call works in buffers of its own: a resident field, the result of a solve, its rotation and a
+ *                       back-projection tail are left as they are.  Stage timers: "reg_mask", "reg_moments", "reg_solve",
+ *                       "reg_residual" (and "ingest_strided" for a device field).  No sum uses a floating-point atomic: a call
+ *                       repeats its bits.
+ *   xmca_column_residual  the residual step alone with given coefficients `coef` (k x N float64, host; a column with a NaN among
+ *                       its k values counts as not fitted): with the basis and coefficients of xmca_column_regress, the bits of
+ *                       its field_out.
+ *   xmca_reg_mask       (tests) the mask / widen pass alone on a host field: the T x N mask bytes (0 present, 1 missing), the plane
+ *                       widened to float64 (0 at the missing entries) and the number of missing entries.
+ *   xmca_reg_solve      (tests) the solve kernel alone on host moments: `normal` holds k (k + 1) / 2 + 1 rows - the packed lower
+ *                       triangle, entry (i, j <= i) at row i (i + 1) / 2 + j, then the number of present entries - of N float64
+ *                       values each, or of one value each when shared_normal != 0 (one matrix for every column); rhs k x N.
+ *   xmca_reg_residual_tile  (no device) rows and columns of a tile of the residual kernel: one workgroup per tile, one lane per
+ *                       column with its k coefficients in registers, the basis rows of the tile through LDS. */
+int xmca_column_regress(xmca_handle* h, const void* X, int in_location, int64_t T, int64_t N, int64_t stride_t, int64_t stride_n, int dtype,
+                        const double* basis, int k, void* field_out, int out_location, double* coef_out, unsigned char* fitted_out);
+int xmca_column_residual(xmca_handle* h, const void* X, int in_location, int64_t T, int64_t N, int64_t stride_t, int64_t stride_n, int dtype,
+                         const double* basis, int k, const double* coef, void* field_out, int out_location);
+int xmca_reg_mask(xmca_handle* h, const void* X, int64_t T, int64_t N, int dtype, unsigned char* mask_out, double* wide_out,
+                  int64_t* missing_out);
+int xmca_reg_solve(xmca_handle* h, const double* normal, int shared_normal, const double* rhs, int64_t N, int k, double* coef_out,
+                   unsigned char* fitted_out);
+int xmca_reg_residual_tile(int* rows_out, int* cols_out);
 int xmca_is_complex(xmca_handle* h);
 /* 1 when the singular vectors of `side` from the last xmca_solve are resident in float32: a real float32 field decomposed on
  * its dual side (N > T) keeps `_V` in the input's dtype as the reference does (xmca/array.py:584, the dtype of

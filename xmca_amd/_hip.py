@@ -82,6 +82,11 @@ SIGNATURES = {
     "xmca_fill_gaps_lagged": (_c_int, [_vp, _vp, _c_i64, _c_i64, _c_int, _vp, _c_i64, _c_int, _c_int, _c_int, _c_int, _c_dbl, _vp, _vp, _ip,
                                        _dp, _vp]),
     "xmca_gap_lag_fill_step": (_c_int, [_vp, _vp, _vp, _vp, _vp, _c_i64, _c_i64, _c_int, _c_int, _c_int, _c_int, _vp, _dp]),
+    "xmca_column_regress": (_c_int, [_vp, _vp, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _vp, _c_int, _vp, _c_int, _vp, _vp]),
+    "xmca_column_residual": (_c_int, [_vp, _vp, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _vp, _c_int, _vp, _vp, _c_int]),
+    "xmca_reg_mask": (_c_int, [_vp, _vp, _c_i64, _c_i64, _c_int, _vp, _vp, ctypes.POINTER(_c_i64)]),
+    "xmca_reg_solve": (_c_int, [_vp, _vp, _c_int, _vp, _c_i64, _c_int, _vp, _vp]),
+    "xmca_reg_residual_tile": (_c_int, [_ip, _ip]),
     "xmca_correlate": (_c_int, [_vp, _c_int, _vp, _c_i64, _c_i64, _vp]),
     "xmca_pearson_pvalues": (_c_int, [_vp, _vp, _c_i64, _c_i64, _vp]),
     "xmca_pvalue_log_norm": (_c_int, [_c_i64, _dp]),
@@ -251,6 +256,13 @@ def gap_fill_tile():
     """(rows, columns) of a tile of the fill kernel of `fill_gaps` (xmca_gap_fill_tile; no device): constants of the build."""
     rows, cols = _c_int(0), _c_int(0)
     load_library().xmca_gap_fill_tile(ctypes.byref(rows), ctypes.byref(cols))
+    return int(rows.value), int(cols.value)
+
+
+def reg_residual_tile():
+    """(rows, columns) of a tile of the residual kernel of `anomalies` (xmca_reg_residual_tile; no device): constants of the build."""
+    rows, cols = _c_int(0), _c_int(0)
+    load_library().xmca_reg_residual_tile(ctypes.byref(rows), ctypes.byref(cols))
     return int(rows.value), int(cols.value)
 
 
@@ -1161,6 +1173,75 @@ class Handle:
         """M-SSA gap filling (xmca_fill_gaps_lagged): `fill_gaps` on the plane embedded with `embedding` windows `tau` steps apart;
         lam are the leading eigenvalues of the lag-summed Gram matrix.  embedding = 1 gives the bits of `fill_gaps`."""
         return self.fill_gaps(X, n_modes, max_iter, tol, cv_idx=cv_idx, embedding=embedding, tau=tau)
+
+    def _regress_field(self, what, X):
+        """The field of the regression entries as their leading arguments: (keep-alive, pointer, location, T, N, stride_t, stride_n,
+        dtype code, numpy dtype) of a contiguous T x N host array or of a `DeviceView`."""
+        if isinstance(X, DeviceView):
+            return X, _vp(X.ptr), DEVICE, X.T, X.N, X.stride_t, X.stride_n, _np_dtype_code(X.dtype), X.dtype
+        X = _gap_plane(what, X)
+        return X, _ptr(X), HOST, X.shape[0], X.shape[1], X.shape[1], 1, _np_dtype_code(X.dtype), X.dtype
+
+    def column_regress(self, X, basis, alloc=None):
+        """Least-squares fit of every column of the T x N float32 / float64 field `X` (a host array or a `DeviceView`; NaN = missing)
+        on the columns of `basis` (T x k float64, k <= 16) over its present entries, and the residual (xmca_column_regress):
+        (field, coefficients, fitted) - T x N in X's dtype with NaN at the missing entries and in the columns that are not fitted,
+        k x N float64 (NaN where not fitted), N bools.  alloc: as in `maps` - the field is written on the device.  Resident fields
+        and the result of a solve stay as they are."""
+        keep, ptr, where_in, T, N, st, sn, code, dt = self._regress_field("column_regress", X)
+        B = np.ascontiguousarray(basis, dtype=np.float64)
+        if B.ndim != 2 or B.shape[0] != T or not 1 <= B.shape[1] <= 16:
+            raise ValueError("column_regress: the basis must be T x k with T = %d and 1 <= k <= 16, got shape %s" % (T, B.shape))
+        k = B.shape[1]
+        field, f_ptr, where_out = _output(alloc, (T, N), dt)
+        coef = np.empty((k, N), dtype=np.float64)
+        fitted = np.empty(N, dtype=np.uint8)
+        self._check(self._lib.xmca_column_regress(self._h, ptr, where_in, T, N, st, sn, code, _ptr(B), k, f_ptr, where_out, _ptr(coef),
+                                                  _ptr(fitted)))
+        return field, coef, fitted.astype(bool)
+
+    def column_residual(self, X, basis, coef, alloc=None):
+        """The residual step of `column_regress` alone with given coefficients (xmca_column_residual): the T x N field minus
+        basis @ coef at its present entries, NaN at the missing ones and in the columns whose coefficients hold a NaN."""
+        keep, ptr, where_in, T, N, st, sn, code, dt = self._regress_field("column_residual", X)
+        B = np.ascontiguousarray(basis, dtype=np.float64)
+        if B.ndim != 2 or B.shape[0] != T or not 1 <= B.shape[1] <= 16:
+            raise ValueError("column_residual: the basis must be T x k with T = %d and 1 <= k <= 16, got shape %s" % (T, B.shape))
+        k = B.shape[1]
+        C = np.ascontiguousarray(coef, dtype=np.float64)
+        if C.shape != (k, N):
+            raise ValueError("column_residual: the coefficients must be k x N = %d x %d, got shape %s" % (k, N, C.shape))
+        field, f_ptr, where_out = _output(alloc, (T, N), dt)
+        self._check(self._lib.xmca_column_residual(self._h, ptr, where_in, T, N, st, sn, code, _ptr(B), k, _ptr(C), f_ptr, where_out))
+        return field
+
+    def reg_mask(self, X):
+        """(tests) The mask / widen pass of `column_regress` on a host field (xmca_reg_mask): (mask, wide, missing) - the T x N mask
+        bytes (0 present, 1 missing), the plane widened to float64 with 0 at the missing entries, and their number."""
+        X = _gap_plane("reg_mask", X)
+        T, N = X.shape
+        mask = np.empty((T, N), dtype=np.uint8)
+        wide = np.empty((T, N), dtype=np.float64)
+        missing = _c_i64(0)
+        self._check(self._lib.xmca_reg_mask(self._h, _ptr(X), T, N, _np_dtype_code(X.dtype), _ptr(mask), _ptr(wide), ctypes.byref(missing)))
+        return mask, wide, int(missing.value)
+
+    def reg_solve(self, normal, rhs):
+        """(tests) The solve kernel of `column_regress` on host moments (xmca_reg_solve): (coefficients k x N, fitted N bools).
+        rhs: k x N; normal: (k (k + 1) / 2 + 1) x N - the packed lower triangles, entry (i, j <= i) in row i (i + 1) / 2 + j, then the
+        numbers of present entries - or 1-D of that length: one matrix shared by all columns."""
+        rhs = np.ascontiguousarray(rhs, dtype=np.float64)
+        normal = np.ascontiguousarray(normal, dtype=np.float64)
+        if rhs.ndim != 2 or not 1 <= rhs.shape[0] <= 16:
+            raise ValueError("reg_solve: rhs must be k x N with 1 <= k <= 16, got shape %s" % (rhs.shape,))
+        k, N = rhs.shape
+        rows = k * (k + 1) // 2 + 1
+        if normal.shape not in ((rows,), (rows, N)):
+            raise ValueError("reg_solve: normal must hold %d rows of 1 or %d values, got shape %s" % (rows, N, normal.shape))
+        coef = np.empty((k, N), dtype=np.float64)
+        fitted = np.empty(N, dtype=np.uint8)
+        self._check(self._lib.xmca_reg_solve(self._h, _ptr(normal), int(normal.ndim == 1), _ptr(rhs), N, k, _ptr(coef), _ptr(fitted)))
+        return coef, fitted.astype(bool)
 
     def gap_center(self, X):
         """(tests) The centring and mask kernels of `fill_gaps` on a host field (xmca_gap_center): (mean, mask, A, scale) - the N column

@@ -18,6 +18,7 @@
 #include "lag_project.h"
 #include "lag_reconstruct.h"
 #include "gap_fill.h"
+#include "regress.h"
 
 using namespace xmca;
 
@@ -1989,6 +1990,129 @@ void gap_lag_fill_step_impl(xmca_handle* h, const TI* A_in, const unsigned char*
   XMCA_HIP(hipStreamSynchronize(h->st));
 }
 
+// xmca_column_regress, xmca_column_residual: the field comes from the host or - through the copy kernels of
+// xmca_set_field_strided - from the caller's device memory into a buffer of this call; the mask / widen pass; with coef_in == nullptr
+// the fit - right-hand sides B^T X0 (k x N) and, where an entry is missing, the packed normal matrices and the counts
+// Q^T P ((k (k + 1) / 2 + 1) x N: the pair products of the basis columns and a row of ones against the presence plane) by the
+// GEMM, one shared normal matrix summed on the host where nothing is missing, then the solve kernel - else the given coefficients
+// (a column with a NaN among them counts as not fitted); the residual pass, into the caller's device memory or a buffer that is
+// copied to the host.  Every buffer is this call's own.
+template <typename TI>
+void column_regress_impl(xmca_handle* h, const void* X, bool in_device, int T, int64_t N, int64_t stride_t, int64_t stride_n, const double* basis,
+                         int k, const double* coef_in, TI* out, bool out_device, double* coef_out, unsigned char* fitted_out) {
+  const size_t total = (size_t)T * N;
+  const int m = reg_packed(k);
+  const bool fit = coef_in == nullptr;
+  DevBuf<TI> raw;
+  DevBuf<unsigned char> mask, fitted;
+  DevBuf<double> wide, pres, Bd, Ad, rhs, nm, coef;
+  RegMaskScratch scratch;
+  if (in_device) {
+    h->tm.begin("ingest_strided");
+    ingest_strided<TI>(h->st, static_cast<const TI*>(X), T, N, stride_t, stride_n, raw.ensure(total));
+    XMCA_HIP(hipGetLastError());
+    h->tm.end();
+  } else {
+    XMCA_HIP(hipMemcpyAsync(raw.ensure(total), X, sizeof(TI) * total, hipMemcpyHostToDevice, h->st));
+  }
+  XMCA_HIP(hipMemcpyAsync(Bd.ensure((size_t)T * k), basis, sizeof(double) * (size_t)T * k, hipMemcpyHostToDevice, h->st));
+  h->tm.begin("reg_mask");
+  reg_mask<TI>(h->st, raw.get(), (int64_t)total, mask.ensure(total), wide.ensure(total), fit ? pres.ensure(total) : nullptr, scratch);
+  h->tm.end();
+  coef.ensure((size_t)k * N);
+  fitted.ensure((size_t)N);
+  std::vector<unsigned char> fitted_host;
+  std::vector<double> a_host, shared;
+  if (fit) {
+    // rows 0 .. k-1: B^T; rows k .. k+m-1: the pair products b_i b_j in packed order; row k+m: ones (the count)
+    a_host.resize((size_t)(k + m + 1) * T);
+    for (int t = 0; t < T; ++t) {
+      const double* b = basis + (size_t)t * k;
+      for (int i = 0; i < k; ++i) {
+        a_host[(size_t)i * T + t] = b[i];
+        for (int j = 0; j <= i; ++j) a_host[(size_t)(k + i * (i + 1) / 2 + j) * T + t] = b[i] * b[j];
+      }
+      a_host[(size_t)(k + m) * T + t] = 1.0;
+    }
+    XMCA_HIP(hipMemcpyAsync(Ad.ensure(a_host.size()), a_host.data(), sizeof(double) * a_host.size(), hipMemcpyHostToDevice, h->st));
+    double missing = 0.0;
+    XMCA_HIP(hipMemcpyAsync(&missing, scratch.count.get(), sizeof(double), hipMemcpyDeviceToHost, h->st));
+    XMCA_HIP(hipStreamSynchronize(h->st));
+    h->tm.begin("reg_moments");
+    GemmOpts o;
+    gemm<double, double>(h->st, h->gws, (const double*)Ad.get(), T, (const double*)wide.get(), N, rhs.ensure((size_t)k * N), N, k, (int)N, T, o);
+    int64_t es = N, ns = 1;
+    if (missing > 0.0) {
+      gemm<double, double>(h->st, h->gws, (const double*)Ad.get() + (size_t)k * T, T, (const double*)pres.get(), N, nm.ensure((size_t)(m + 1) * N),
+                           N, m + 1, (int)N, T, o);
+    } else {          // one normal matrix for every column: the rows of a_host summed over t, ascending
+      shared.assign((size_t)m + 1, 0.0);
+      for (int e = 0; e <= m; ++e) {
+        double s = 0.0;
+        for (int t = 0; t < T; ++t) s += a_host[(size_t)(k + e) * T + t];
+        shared[(size_t)e] = s;
+      }
+      XMCA_HIP(hipMemcpyAsync(nm.ensure((size_t)m + 1), shared.data(), sizeof(double) * ((size_t)m + 1), hipMemcpyHostToDevice, h->st));
+      es = 1;
+      ns = 0;
+    }
+    h->tm.end();
+    h->tm.begin("reg_solve");
+    reg_solve(h->st, k, nm.get(), es, ns, rhs.get(), N, coef.get(), fitted.get());
+    h->tm.end();
+    XMCA_HIP(hipMemcpyAsync(coef_out, coef.get(), sizeof(double) * (size_t)k * N, hipMemcpyDeviceToHost, h->st));
+    XMCA_HIP(hipMemcpyAsync(fitted_out, fitted.get(), (size_t)N, hipMemcpyDeviceToHost, h->st));
+  } else {
+    fitted_host.assign((size_t)N, 1);
+    for (int c = 0; c < k; ++c)
+      for (int64_t n = 0; n < N; ++n)
+        if (!(coef_in[(size_t)c * N + n] == coef_in[(size_t)c * N + n])) fitted_host[(size_t)n] = 0;
+    XMCA_HIP(hipMemcpyAsync(coef.get(), coef_in, sizeof(double) * (size_t)k * N, hipMemcpyHostToDevice, h->st));
+    XMCA_HIP(hipMemcpyAsync(fitted.get(), fitted_host.data(), (size_t)N, hipMemcpyHostToDevice, h->st));
+  }
+  h->tm.begin("reg_residual");
+  TI* dst = out_device ? out : raw.get();          // (the raw plane has been read: the mask pass is ahead on the stream)
+  reg_residual<TI>(h->st, wide.get(), mask.get(), Bd.get(), coef.get(), fitted.get(), T, N, k, dst);
+  h->tm.end();
+  if (!out_device) XMCA_HIP(hipMemcpyAsync(out, raw.get(), sizeof(TI) * total, hipMemcpyDeviceToHost, h->st));
+  XMCA_HIP(hipStreamSynchronize(h->st));
+}
+
+// (tests) xmca_reg_mask: the mask / widen pass alone
+template <typename TI>
+void reg_mask_impl(xmca_handle* h, const TI* X, int64_t total, unsigned char* mask_out, double* wide_out, int64_t* missing_out) {
+  DevBuf<TI> raw;
+  DevBuf<unsigned char> mask;
+  DevBuf<double> wide;
+  RegMaskScratch scratch;
+  XMCA_HIP(hipMemcpyAsync(raw.ensure((size_t)total), X, sizeof(TI) * (size_t)total, hipMemcpyHostToDevice, h->st));
+  h->tm.begin("reg_mask");
+  reg_mask<TI>(h->st, raw.get(), total, mask.ensure((size_t)total), wide.ensure((size_t)total), (double*)nullptr, scratch);
+  h->tm.end();
+  double missing = 0.0;
+  XMCA_HIP(hipMemcpyAsync(mask_out, mask.get(), (size_t)total, hipMemcpyDeviceToHost, h->st));
+  XMCA_HIP(hipMemcpyAsync(wide_out, wide.get(), sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, h->st));
+  XMCA_HIP(hipMemcpyAsync(&missing, scratch.count.get(), sizeof(double), hipMemcpyDeviceToHost, h->st));
+  XMCA_HIP(hipStreamSynchronize(h->st));
+  *missing_out = (int64_t)missing;
+}
+
+// (tests) xmca_reg_solve: the solve kernel alone on host moments
+void reg_solve_impl(xmca_handle* h, const double* normal, bool shared, const double* rhs_in, int64_t N, int k, double* coef_out,
+                    unsigned char* fitted_out) {
+  const size_t n_nm = (size_t)(reg_packed(k) + 1) * (shared ? 1 : (size_t)N);
+  DevBuf<double> nm, rhs, coef;
+  DevBuf<unsigned char> fitted;
+  XMCA_HIP(hipMemcpyAsync(nm.ensure(n_nm), normal, sizeof(double) * n_nm, hipMemcpyHostToDevice, h->st));
+  XMCA_HIP(hipMemcpyAsync(rhs.ensure((size_t)k * N), rhs_in, sizeof(double) * (size_t)k * N, hipMemcpyHostToDevice, h->st));
+  h->tm.begin("reg_solve");
+  reg_solve(h->st, k, nm.get(), shared ? 1 : N, shared ? 0 : 1, rhs.get(), N, coef.ensure((size_t)k * N), fitted.ensure((size_t)N));
+  h->tm.end();
+  XMCA_HIP(hipMemcpyAsync(coef_out, coef.get(), sizeof(double) * (size_t)k * N, hipMemcpyDeviceToHost, h->st));
+  XMCA_HIP(hipMemcpyAsync(fitted_out, fitted.get(), (size_t)N, hipMemcpyDeviceToHost, h->st));
+  XMCA_HIP(hipStreamSynchronize(h->st));
+}
+
 // ---- bootstrapping: working copies on the device -----------------------------------------------------------------
 template <typename TI>
 void bootstrap_begin_impl(xmca_handle* h, int n_fields) {
@@ -2826,6 +2950,73 @@ int xmca_gap_lag_fill_step(xmca_handle* h, const void* A, const unsigned char* m
     using TI = decltype(t);
     gap_lag_fill_step_impl<TI>(h, static_cast<const TI*>(A), mask, Z, P, (int)T, N, n_modes, embedding, tau, static_cast<TI*>(A_out), sum_out);
   });
+  API_END(h)
+}
+
+int xmca_reg_residual_tile(int* rows_out, int* cols_out) {
+  if (!rows_out || !cols_out) return XMCA_ERR_INVALID;
+  *rows_out = REG_ROWS;
+  *cols_out = REG_COLS;
+  return XMCA_OK;
+}
+
+// The checks and the call shared by xmca_column_regress (coef == NULL: the fit) and xmca_column_residual
+static void column_regress_entry(xmca_handle* h, const char* what, const void* X, int in_location, int64_t T, int64_t N, int64_t stride_t,
+                                 int64_t stride_n, int dtype, const double* basis, int k, const double* coef, void* field_out, int out_location,
+                                 double* coef_out, unsigned char* fitted_out) {
+  const std::string w(what);
+  XMCA_CHECK(k >= 1 && k <= REG_K, XMCA_ERR_INVALID, w + ": k must lie in [1, 16]");
+  XMCA_CHECK(T >= 1 && N >= 1, XMCA_ERR_INVALID, w + ": the field must have at least one row and one column");
+  XMCA_CHECK(dtype == XMCA_F32 || dtype == XMCA_F64, XMCA_ERR_INVALID, w + ": dtype must be XMCA_F32 or XMCA_F64");
+  XMCA_CHECK(stride_t >= 0 && stride_n >= 0, XMCA_ERR_INVALID, w + ": strides must not be negative");
+  XMCA_CHECK(X && basis && field_out && (coef || (coef_out && fitted_out)), XMCA_ERR_INVALID, w + ": bad arguments");
+  XMCA_CHECK(in_location == XMCA_HOST || in_location == XMCA_DEVICE, XMCA_ERR_INVALID, w + ": the location must be XMCA_HOST or XMCA_DEVICE");
+  XMCA_CHECK(T <= (int64_t)65535 * REG_ROWS && N < ((int64_t)1 << 31) && T * N < ((int64_t)1 << 40), XMCA_ERR_UNSUPPORTED, w + ": field too large");
+  if (in_location == XMCA_DEVICE) check_device_pointer(h, what, X);
+  check_out_location(h, what, out_location, field_out);
+  with_dtype(dtype, [&](auto t) {
+    using TI = decltype(t);
+    column_regress_impl<TI>(h, X, in_location == XMCA_DEVICE, (int)T, N, stride_t, stride_n, basis, k, coef, static_cast<TI*>(field_out),
+                            out_location == XMCA_DEVICE, coef_out, fitted_out);
+  });
+}
+
+int xmca_column_regress(xmca_handle* h, const void* X, int in_location, int64_t T, int64_t N, int64_t stride_t, int64_t stride_n, int dtype,
+                        const double* basis, int k, void* field_out, int out_location, double* coef_out, unsigned char* fitted_out) {
+  API_BEGIN(h)
+  XMCA_CHECK(coef_out && fitted_out, XMCA_ERR_INVALID, "column_regress: bad arguments");
+  column_regress_entry(h, "column_regress", X, in_location, T, N, stride_t, stride_n, dtype, basis, k, nullptr, field_out, out_location, coef_out,
+                       fitted_out);
+  API_END(h)
+}
+
+int xmca_column_residual(xmca_handle* h, const void* X, int in_location, int64_t T, int64_t N, int64_t stride_t, int64_t stride_n, int dtype,
+                         const double* basis, int k, const double* coef, void* field_out, int out_location) {
+  API_BEGIN(h)
+  XMCA_CHECK(coef, XMCA_ERR_INVALID, "column_residual: bad arguments");
+  column_regress_entry(h, "column_residual", X, in_location, T, N, stride_t, stride_n, dtype, basis, k, coef, field_out, out_location, nullptr,
+                       nullptr);
+  API_END(h)
+}
+
+int xmca_reg_mask(xmca_handle* h, const void* X, int64_t T, int64_t N, int dtype, unsigned char* mask_out, double* wide_out,
+                  int64_t* missing_out) {
+  API_BEGIN(h)
+  XMCA_CHECK(X && mask_out && wide_out && missing_out, XMCA_ERR_INVALID, "reg_mask: bad arguments");
+  check_gap_plane("reg_mask", T, N, dtype);
+  with_dtype(dtype, [&](auto t) {
+    using TI = decltype(t);
+    reg_mask_impl<TI>(h, static_cast<const TI*>(X), T * N, mask_out, wide_out, missing_out);
+  });
+  API_END(h)
+}
+
+int xmca_reg_solve(xmca_handle* h, const double* normal, int shared_normal, const double* rhs, int64_t N, int k, double* coef_out,
+                   unsigned char* fitted_out) {
+  API_BEGIN(h)
+  XMCA_CHECK(k >= 1 && k <= REG_K, XMCA_ERR_INVALID, "reg_solve: k must lie in [1, 16]");
+  XMCA_CHECK(normal && rhs && coef_out && fitted_out && N >= 1 && N < ((int64_t)1 << 31), XMCA_ERR_INVALID, "reg_solve: bad arguments");
+  reg_solve_impl(h, normal, shared_normal != 0, rhs, N, k, coef_out, fitted_out);
   API_END(h)
 }
 

@@ -11,6 +11,7 @@ import os
 import numpy as np
 
 from . import gaps as _gaps
+from . import prepare as _prepare
 from .array import MCA, secure_str
 
 
@@ -353,6 +354,30 @@ def fill_gaps(da, n_modes, max_iter=300, tol=1e-5, cv_fraction=None, cv_idx=None
     out = _gaps.fill_gaps(da.values, n_modes, max_iter=max_iter, tol=tol, cv_fraction=cv_fraction, cv_idx=cv_idx, seed=seed, handle=handle,
                           embedding=embedding, tau=tau)
     out['field'] = xr.DataArray(out['field'], dims=da.dims, coords=da.coords, attrs=dict(da.attrs), name=da.name)
+    return out
+
+
+def anomalies(da, period=None, harmonics=None, trend=False, basis=None, handle=None):
+    """`xmca_amd.prepare.anomalies` of a DataArray whose first dimension is time: the same dict as DataArrays - 'field' over the dims,
+    coordinates and attrs of `da`, 'coefficients' over ('basis',) + the spatial dims, 'fitted' over the spatial dims, 'basis' over
+    (time, 'basis') - each with those coordinates of `da` that lie along its own dims."""
+    xr = _xr()
+    if not isinstance(da, xr.DataArray):
+        raise TypeError("anomalies: the field is not an `xarray.DataArray`")
+    out = _prepare.anomalies(da.values, period=period, harmonics=harmonics, trend=trend, basis=basis, handle=handle)
+    k = out['basis'].shape[1]
+
+    def along(dims):
+        """the coordinates of `da` that lie along `dims`, and the 'basis' index where it is one of them"""
+        coords = {name: c for name, c in dict(da.coords).items() if getattr(c, 'dims', ()) and set(c.dims) <= set(dims)}
+        if 'basis' in dims:
+            coords['basis'] = np.arange(k)
+        return coords
+    time, spatial = tuple(da.dims[:1]), tuple(da.dims[1:])
+    out['field'] = xr.DataArray(out['field'], dims=da.dims, coords=da.coords, attrs=dict(da.attrs), name=da.name)
+    out['coefficients'] = xr.DataArray(out['coefficients'], dims=('basis',) + spatial, coords=along(('basis',) + spatial), name='coefficients')
+    out['fitted'] = xr.DataArray(out['fitted'], dims=spatial, coords=along(spatial), name='fitted')
+    out['basis'] = xr.DataArray(out['basis'], dims=time + ('basis',), coords=along(time + ('basis',)), name='basis')
     return out
 
 
