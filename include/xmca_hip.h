@@ -42,7 +42,7 @@ typedef struct xmca_handle xmca_handle;
 /* library / device management ------------------------------------------------------------------------- */
 const char* xmca_version(void);
 /* Number of this header's ABI (XMCA_ABI_VERSION): the binding refuses a library built from another revision. */
-#define XMCA_ABI_VERSION 15
+#define XMCA_ABI_VERSION 16
 int xmca_abi_version(void);
 int xmca_device_count(void);
 int xmca_create(int device, xmca_handle** out);
@@ -779,6 +779,21 @@ int xmca_lead_rows(xmca_handle* h, const double* A, int64_t lda, const double* B
 int xmca_fft_ex(xmca_handle* h, const double* in_re, const double* in_im, int64_t in_count, int64_t in_bs, int64_t in_es, int n_in,
                 int conj_in, const double* sin, int batch, int n, int sign, double* out_re, double* out_im, int64_t out_count,
                 int64_t out_bs, int64_t out_es, int n_keep, const double* sa, const double* sb, double scale);
+/* The Sturm multisection behind every tridiagonal solve (csrc/tridiag.h trd_bisect_kernel; kernel tests only), host in / host out,
+ * on a chosen symmetric tridiagonal matrix: d (n) its diagonal, e (n - 1; may be NULL for n = 1) its off-diagonal, float64 of any
+ * magnitude.  d and e are multiplied by the power of two f a solve would apply - f * max(|d|, |e|) in [0.5, 1), f = 1 for a zero
+ * matrix, the rule of trd_scale_kernel - and the kernel is launched as trd_eigenvalues launches it.  lam_desc: the n eigenvalues,
+ * descending, in the caller's scale.  A non-finite entry returns XMCA_ERR_NUMERIC as a solve does; n < 1 or a NULL pointer
+ * returns XMCA_ERR_INVALID before anything is launched. */
+int xmca_tridiag_eigenvalues(xmca_handle* h, const double* d, const double* e, int n, double* lam_desc);
+/* The twisted-factorisation vectors behind every tridiagonal solve (csrc/tridiag_vec.h trd_twisted_kernel; kernel tests only),
+ * host in / host out: lam holds nev (1 .. n) eigenvalues of the matrix (d, e) above, ascending, in the scale of d and e - the
+ * caller's, so nothing here depends on the Sturm kernel; the same f is applied to d, e and lam.  The kernel gets planes of n rows
+ * of ldy >= nev elements: Y (n x ldy) goes to the device before the launch and comes back whole, column k the unit vector of
+ * lam[k], the padding columns as they went in.  nev = n is the call of the full route, nev < n with the largest eigenvalues
+ * that of the partial route.  nev < 1, nev > n, ldy < nev, n < 1 or a NULL pointer return XMCA_ERR_INVALID before anything is
+ * launched; a non-finite entry XMCA_ERR_NUMERIC. */
+int xmca_tridiag_vectors(xmca_handle* h, const double* d, const double* e, int n, const double* lam, int nev, double* Y, int64_t ldy);
 /* Time `reps` Gram products G = X X^T of the resident field `side` with hipEvents on the library's stream;
  * avg_ms = mean duration of one product (all launches it needs), kernel_ms = mean duration of the MFMA
  * kernel launches alone, flops = useful flops of one product, T (T+1) N. */

@@ -43,7 +43,7 @@ def test_stale_library_is_refused(monkeypatch):
     """a library built from another revision of include/xmca_hip.h (ABI number) is not bound silently"""
     from xmca_amd import _hip
     _hip.load_library()
-    assert header_abi_version() == _hip.ABI_VERSION == _hip.load_library().xmca_abi_version() == 15
+    assert header_abi_version() == _hip.ABI_VERSION == _hip.load_library().xmca_abi_version() == 16
     monkeypatch.setattr(_hip, "_lib", None)
     monkeypatch.setattr(_hip, "ABI_VERSION", _hip.ABI_VERSION + 1)
     with pytest.raises(ImportError, match="ABI"):

@@ -263,7 +263,7 @@ def test_the_bounds_of_the_gpu_tests_are_those_of_the_profile():
 def test_the_header_declares_the_entries_and_the_binding_has_them():
     for name, n_args in NEW.items():
         check_entry(name, n_args)
-    assert header_abi_version() == _hip.ABI_VERSION == 15
+    assert header_abi_version() == _hip.ABI_VERSION == 16
     text = header_text(comments=True)                 # (the stage names stand in a comment)
     for stage in ("reg_mask", "reg_moments", "reg_solve", "reg_residual"):
         assert '"%s"' % stage in text, stage

@@ -147,6 +147,8 @@ SIGNATURES = {
     "xmca_lead_rows": (_c_int, [_vp, _vp, _c_i64, _vp, _c_i64, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _c_i64, ctypes.POINTER(_c_int)]),
     "xmca_fft_ex": (_c_int, [_vp, _vp, _vp, _c_i64, _c_i64, _c_i64, _c_int, _c_int, _vp, _c_int, _c_int, _c_int, _vp, _vp, _c_i64,
                              _c_i64, _c_i64, _c_int, _vp, _vp, _c_dbl]),
+    "xmca_tridiag_eigenvalues": (_c_int, [_vp, _vp, _vp, _c_int, _vp]),
+    "xmca_tridiag_vectors": (_c_int, [_vp, _vp, _vp, _c_int, _vp, _c_int, _vp, _c_i64]),
     "xmca_bench_gram": (_c_int, [_vp, _c_int, _c_int, _dp, _dp, _dp]),
     "xmca_bench_gemm": (_c_int, [_vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _dp]),
 }
@@ -162,7 +164,7 @@ MAP_EOF, MAP_AMPLITUDE, MAP_PHASE = 0, 1, 2          # `kind` of xmca_get_maps
 SCALE_NONE, SCALE_MAX, SCALE_STD = 0, 1, 2           # ... and its `scaling`
 INGEST_ROWS, INGEST_TRANSPOSE, INGEST_GATHER = 0, 1, 2   # regimes of xmca_set_field_strided (xmca_ingest_regime)
 PVALUE_MAX_OBS = 1000000    # largest n_obs of xmca_pearson_pvalues / xmca_correlation_maps (csrc/kernels.h)
-ABI_VERSION = 15         # bumped whenever a signature of include/xmca_hip.h changes; checked against xmca_abi_version()
+ABI_VERSION = 16        # bumped whenever a signature of include/xmca_hip.h changes; checked against xmca_abi_version()
 
 
 def load_library():
@@ -1542,6 +1544,38 @@ class Handle:
                                           int(batch), int(n), int(sign), _ptr(outr), _ptr(outi), outr.size, out_bs, int(out_es),
                                           n_keep, _ptr(fa), _ptr(fb), float(scale)))
         return outr, outi
+
+    @staticmethod
+    def _tridiagonal(what, d, e):
+        """(d, e, n) of a symmetric tridiagonal matrix as contiguous float64: d has n >= 1 entries, e n - 1 (None: none)."""
+        dd = np.ascontiguousarray(d, dtype=np.float64)
+        ee = np.zeros(0) if e is None else np.ascontiguousarray(e, dtype=np.float64)
+        if dd.ndim != 1 or ee.ndim != 1 or dd.size < 1 or ee.size != dd.size - 1:
+            raise ValueError("%s: d has n >= 1 entries and e n - 1, got shapes %s and %s" % (what, dd.shape, ee.shape))
+        return dd, ee, int(dd.size)
+
+    def tridiag_eigenvalues(self, d, e):
+        """All eigenvalues, descending, of the symmetric tridiagonal matrix with diagonal d (n) and off-diagonal e (n - 1) by the
+        Sturm multisection kernel of the eigensolver alone, scaled and launched as a solve does it (xmca_tridiag_eigenvalues)."""
+        dd, ee, n = Handle._tridiagonal("tridiag_eigenvalues", d, e)
+        lam = np.empty(n)
+        self._check(self._lib.xmca_tridiag_eigenvalues(self._h, _ptr(dd), _ptr(ee) if n > 1 else None, n, _ptr(lam)))
+        return lam
+
+    def tridiag_vectors(self, d, e, lam, out=None):
+        """The unit eigenvectors of the tridiagonal matrix (d, e) for the nev <= n eigenvalues `lam` (ascending, the caller's) by
+        the twisted-factorisation kernel of the eigensolver alone (xmca_tridiag_vectors).  `out`: the (n, ldy >= nev) plane as it
+        is before the call (default: NaN, ldy = nev).  Returns a copy of it with column k the vector of lam[k]."""
+        dd, ee, n = Handle._tridiagonal("tridiag_vectors", d, e)
+        ll = np.ascontiguousarray(lam, dtype=np.float64)
+        if ll.ndim != 1 or not 1 <= ll.size <= n:
+            raise ValueError("tridiag_vectors: lam holds between 1 and n eigenvalues, got shape %s" % (ll.shape,))
+        Y = np.full((n, ll.size), np.nan) if out is None else np.array(out, dtype=np.float64, order="C", copy=True)
+        if Y.ndim != 2 or Y.shape[0] != n or Y.shape[1] < ll.size:
+            raise ValueError("tridiag_vectors: out is (n, ldy >= nev), got shape %s" % (Y.shape,))
+        self._check(self._lib.xmca_tridiag_vectors(self._h, _ptr(dd), _ptr(ee) if n > 1 else None, n, _ptr(ll), int(ll.size), _ptr(Y),
+                                                   Y.shape[1]))
+        return Y
 
     def bench_gemm(self, M, N, K, dtype, a_kfast=True, b_nfast=True, upper_only=False, splits=0, reps=5):
         """ms per product C = op(A) op(B) on device-resident random operands."""

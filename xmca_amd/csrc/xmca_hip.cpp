@@ -3770,6 +3770,81 @@ int xmca_fft_ex(xmca_handle* h, const double* in_re, const double* in_im, int64_
   API_END(h)
 }
 
+// xmca_tridiag_eigenvalues and xmca_tridiag_vectors: (d, e) (and `extra`, n_extra values in the same scale) times the power of two
+// a solve would apply - trd_scale_kernel itself decides it, from max(|d|, |e|) as the bit pattern trd_maxabs_kernel leaves behind -
+// into dd / de / dx.  ws.scal and ws.flag are left as trd_reduce leaves them.  Returns false (nothing scaled: f = 1, scal[1] = 1)
+// when an entry is not finite.  Synchronises the stream.
+static bool tridiag_stage_upload(xmca_handle* h, TrdWorkspace& ws, const double* d, const double* e, int n, const double* extra, int n_extra,
+                                 DevBuf<double>& dd, DevBuf<double>& de, DevBuf<double>& dx) {
+  double m = 0.0;
+  bool bad = false;
+  auto see = [&](double v) {
+    const double a = std::fabs(v);
+    if (!(a <= 1.7e308)) bad = true;
+    else if (a > m) m = a;
+  };
+  for (int i = 0; i < n; ++i) see(d[i]);
+  for (int i = 0; i + 1 < n; ++i) see(e[i]);
+  for (int i = 0; i < n_extra; ++i)
+    if (!(std::fabs(extra[i]) <= 1.7e308)) bad = true;
+  unsigned long long acc[2] = {0ull, bad ? 1ull : 0ull};
+  if (!bad) std::memcpy(&acc[0], &m, sizeof(double));
+  ws.scal.ensure(4);
+  ws.flag.ensure(4);
+  XMCA_HIP(hipMemsetAsync(ws.flag.get(), 0, sizeof(int) * 4, h->st));
+  unsigned long long* dacc = reinterpret_cast<unsigned long long*>(ws.scal.get() + 2);
+  XMCA_HIP(hipMemcpyAsync(dacc, acc, sizeof(acc), hipMemcpyHostToDevice, h->st));
+  hipLaunchKernelGGL(trd_scale_kernel, dim3(1), dim3(1), 0, h->st, dacc, ws.scal.get());
+  XMCA_HIP(hipGetLastError());
+  double scal[2] = {1.0, 0.0};
+  XMCA_HIP(hipMemcpyAsync(scal, ws.scal.get(), sizeof(scal), hipMemcpyDeviceToHost, h->st));
+  XMCA_HIP(hipStreamSynchronize(h->st));
+  const double f = scal[0];                      // (a power of two: the products below are the ones trd_copy_kernel forms)
+  std::vector<double> hd((size_t)n), he((size_t)std::max(n - 1, 1), 0.0), hx((size_t)std::max(n_extra, 1), 0.0);
+  for (int i = 0; i < n; ++i) hd[i] = f * d[i];
+  for (int i = 0; i + 1 < n; ++i) he[i] = f * e[i];
+  for (int i = 0; i < n_extra; ++i) hx[i] = f * extra[i];
+  XMCA_HIP(hipMemcpyAsync(dd.ensure(hd.size()), hd.data(), sizeof(double) * hd.size(), hipMemcpyHostToDevice, h->st));
+  XMCA_HIP(hipMemcpyAsync(de.ensure(he.size()), he.data(), sizeof(double) * he.size(), hipMemcpyHostToDevice, h->st));
+  XMCA_HIP(hipMemcpyAsync(dx.ensure(hx.size()), hx.data(), sizeof(double) * hx.size(), hipMemcpyHostToDevice, h->st));
+  XMCA_HIP(hipStreamSynchronize(h->st));         // (the host copies go out of scope)
+  return !bad;
+}
+
+int xmca_tridiag_eigenvalues(xmca_handle* h, const double* d, const double* e, int n, double* lam_desc) {
+  if (!d || !lam_desc || n < 1 || (!e && n > 1)) return XMCA_ERR_INVALID;
+  API_BEGIN(h)
+  XMCA_CHECK((size_t)n * 16 <= (size_t)150 * 1024, XMCA_ERR_UNSUPPORTED, "tridiag_eigenvalues: the matrix does not fit the LDS of a workgroup");
+  TrdWorkspace ws;
+  DevBuf<double> dd, de, dx, lam_tmp;
+  tridiag_stage_upload(h, ws, d, e, n, nullptr, 0, dd, de, dx);
+  TrdParams P{};
+  P.n = n;
+  P.d = dd.get();
+  P.e = de.get();
+  std::vector<double> lam;
+  trd_eigenvalues(h->st, ws, P, lam, nullptr, lam_tmp);       // (a non-finite entry: the numeric error of a solve)
+  std::memcpy(lam_desc, lam.data(), sizeof(double) * (size_t)n);
+  API_END(h)
+}
+
+int xmca_tridiag_vectors(xmca_handle* h, const double* d, const double* e, int n, const double* lam, int nev, double* Y, int64_t ldy) {
+  if (!d || !lam || !Y || n < 1 || (!e && n > 1) || nev < 1 || nev > n || ldy < nev) return XMCA_ERR_INVALID;
+  API_BEGIN(h)
+  TrdWorkspace ws;
+  DevBuf<double> dd, de, dl, W, Yd;
+  const bool finite = tridiag_stage_upload(h, ws, d, e, n, lam, nev, dd, de, dl);
+  XMCA_CHECK(finite, XMCA_ERR_NUMERIC, "tridiag_vectors: d, e and lam must be finite");
+  const size_t plane = (size_t)n * (size_t)ldy;
+  W.ensure(plane);
+  XMCA_HIP(hipMemcpyAsync(Yd.ensure(plane), Y, sizeof(double) * plane, hipMemcpyHostToDevice, h->st));
+  hipLaunchKernelGGL(trd_twisted_kernel, dim3(ceil_div(nev, 64)), dim3(128), 0, h->st, dd.get(), de.get(), n, nev, dl.get(), W.get(), Yd.get(), ldy);
+  XMCA_HIP(hipGetLastError());
+  XMCA_HIP(hipMemcpyAsync(Y, Yd.get(), sizeof(double) * plane, hipMemcpyDeviceToHost, h->st));
+  XMCA_HIP(hipStreamSynchronize(h->st));
+  API_END(h)
+}
+
 // xmca_eigh and xmca_eigh_lead: upload, hermitian_evd, packed rows back.  n_lead < 0: the n x n planes of xmca_eigh.  Otherwise the
 // planes handed to hermitian_evd have n_lead + 1 rows of ldz = (n rounded up to 16) + 16 elements, the padding columns and the
 // extra row filled with a sentinel beforehand; *guard_clean says whether every sentinel word is still there afterwards.
