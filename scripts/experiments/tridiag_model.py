@@ -79,6 +79,34 @@ def sturm_count(d, e2, lam, pivmin):
     return cnt
 
 
+def sturm_count_two_ended(d, e2, lam, floor=2.0 ** -200):
+    """number of eigenvalues < lam, counted from both ends as trd_bisect_kernel does (csrc/tridiag.h): sign changes of the
+    leading minors p_0 .. p_m (m = n // 2) and of the trailing minors q_n .. q_{m+1} by their three-term recurrences (no
+    division), plus [gamma_m < 0] with sign(gamma_m) = sign(det) sign(p_m) sign(q_{m+1}), det = p_{m+1} q_{m+1} - e_m^2 p_m q_{m+2}.
+    e2 is floored so that a zero minor is followed by a non-zero one; a sign is the sign bit.  (Without the kernel's power-of-two
+    rescales: small orders only.  The restatement with them: tests/tridiag_two_ended.py.)"""
+    n = len(d)
+    m = n // 2
+    c2 = np.maximum(np.asarray(e2, dtype=float), floor)
+
+    def chain(dd, cc, rows):                     # cc[j]: squared coupling of rows j - 1 and j
+        pm, pc, cnt = 0.0, 1.0, 0
+        for j in range(rows):
+            pn = (dd[j] - lam) * pc - (cc[j] * pm if j else 0.0)
+            cnt += bool(np.signbit(pn)) != bool(np.signbit(pc))
+            pm, pc = pc, pn
+        return pc, pm, cnt
+
+    cf = np.concatenate(([floor], c2))
+    cb = np.concatenate(([floor], c2[::-1]))
+    p_c, p_m, cnt_f = chain(d, cf, m)
+    q_c, q_m, cnt_b = chain(d[::-1], cb, n - 1 - m)
+    ext = (d[m] - lam) * p_c - cf[m] * p_m
+    det = ext * q_c - ((c2[m] if m < n - 1 else floor) * p_c) * q_m
+    neg = bool(np.signbit(det)) ^ bool(np.signbit(p_c)) ^ bool(np.signbit(q_c))
+    return cnt_f + cnt_b + int(neg)
+
+
 def bisect_all(d, e):
     n = len(d)
     e2 = e * e
@@ -147,6 +175,12 @@ def main():
         print("cplx", cplx, "n", n, "tridiagonal eigenvalues vs eigvalsh(G): %.2e (rel. to lam_max)" % (np.max(np.abs(lam_t - ref)) / ref[-1]))
         lam_b = bisect_all(d, e) if n <= 200 else lam_t
         print("   bisection vs eigvalsh(T): %.2e" % (np.max(np.abs(lam_b - lam_t)) / ref[-1]))
+        # the two-ended count on a scaled leading block (24 rows: the minors stay in range without the kernel's rescales)
+        sc = 1.0 / max(np.max(np.abs(d)), np.max(np.abs(e)))
+        ds, e2s = sc * d[:24], (sc * e[:23]) ** 2
+        pts = np.linspace(-2.0, 2.0, 81)
+        same = sum(sturm_count_two_ended(ds, e2s, x) == sturm_count(ds, e2s, x, np.finfo(float).tiny) for x in pts)
+        print("   two-ended Sturm count = one-ended count at %d of %d points" % (same, len(pts)))
         Y = np.stack([twisted_vector(d, e, l) for l in lam_b], axis=1)
         print("   twisted vectors: orthogonality %.2e, residual %.2e" % (np.max(np.abs(Y.T @ Y - np.eye(n))), np.max(np.linalg.norm(T @ Y - Y * lam_b, axis=0)) / ref[-1]))
         Z = back_transform(Vs, taus, Y)

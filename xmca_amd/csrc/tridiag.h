@@ -13,8 +13,9 @@
 //      so the trailing matrix is read and written once per column and the only synchronisation is the launch boundary
 //      (1.5-1.9 us on MI355X against 4-5 us for a grid barrier inside a persistent kernel).  Everything is summed in a
 //      fixed order: bit-reproducible, independent of lanes / ranks.
-//   2. all eigenvalues of the tridiagonal by Sturm-sequence multisection (trd_bisect_kernel): 16 lanes per eigenvalue
-//      evaluate the count at 16 interior points of the current bracket, 14 passes from the Gershgorin interval.
+//   2. all eigenvalues of the tridiagonal by Sturm-sequence multisection (trd_bisect_kernel): 32 lanes per eigenvalue
+//      evaluate the count at 16 interior points of the current bracket, each from both ends of the matrix at once, 14 passes
+//      from the Gershgorin interval.
 //   3. (eigenvectors, trd_vectors_*) twisted factorisations of T - lambda_k I, one lane per eigenvalue, back-transformation
 //      by blocked reflectors (compact WY, GEMMs), Newton-Schulz re-orthonormalisation; clusters the twisted vectors
 //      cannot resolve are detected from the Gram matrix of the result and handed to the Jacobi solver.
@@ -1143,28 +1144,45 @@ __global__ void trd_copy_kernel(const double* __restrict__ Ar, const double* __r
 }
 
 // ---- all eigenvalues of the symmetric tridiagonal (d, e) by Sturm multisection ------------------------------------
-// 16 lanes per eigenvalue: count(x) = number of eigenvalues below x at 16 interior points of the bracket per pass (sign
-// changes of the leading principal minors by their three-term recurrence: one dependent FMA per row, no division, no
-// compare in the chain).  14 passes shrink the Gershgorin interval by 17^14 = 1.7e17.
+// count(x) = number of eigenvalues below x at 16 interior points of the bracket per pass; 14 passes shrink the Gershgorin
+// interval by 17^14 = 1.7e17.  The count is taken FROM BOTH ENDS (the inertia of the twisted factorisation at row m = n / 2):
+//   forward minors   p_0 = 1,  p_{i+1} = (d_i - x) p_i - e_{i-1}^2 p_{i-1}               up to p_m      (m rows),
+//   backward minors  q_n = 1,  q_{n+1} = 0,  q_i = (d_i - x) q_{i+1} - e_i^2 q_{i+2}      down to q_{m+1} (n - 1 - m rows),
+//   count = changes(p_0 .. p_m) + changes(q_n .. q_{m+1}) + [gamma_m < 0],
+//   sign(gamma_m) = sign(det) sign(p_m) sign(q_{m+1}),  det = p_{m+1} q_{m+1} - e_m^2 p_m q_{m+2}  (p_{m+1}: one more forward step)
+// - two independent recurrences of half the length, one dependent FMA per row each, no division, no compare in a chain.
+// 32 lanes per eigenvalue: 16 points x 2 directions, one chain per lane; the two lanes of a point exchange their last pairs.
+// A sign is the sign BIT.  An exactly zero p_m at the junction gives p_{m+1} = -e_{m-1}^2 p_{m-1} (e^2 has a floor: not zero) and
+// det = p_{m+1} q_{m+1}, so [gamma_m < 0] = [the zero's bit equals sign(p_{m-1})] while changes(.. p_m) counts [it differs]: one
+// sign change over the two steps whichever bit the zero carries, as inside a chain (below); the same holds, mirrored, for a zero
+// q_{m+1}.  n = 1: m = 0, no backward part (q_1 = 1, q_2 = 0): count = [d_0 - x < 0].
 // lam_desc[n-1-k] = eigenvalue k (ascending) / scale factor.  flag[0] != 0: non-finite input.
+// LDS: one 16-byte record per row, read with one ds_read_b128: {d_i, e_{i-1}^2} for the forward rows i <= m (the record of
+// row m serves the step to p_{m+1}), then {d_i, e_i^2} for i = n-1 down to m+1 - the backward chain is the forward chain of
+// the reversed matrix.
 constexpr int TRD_BIS_THREADS = 256;
+constexpr int TRD_BIS_LANES = 32;                  // per eigenvalue
+constexpr double TRD_E2_FLOOR = 0x1p-200;
 __global__ __launch_bounds__(TRD_BIS_THREADS) void trd_bisect_kernel(const double* __restrict__ d, const double* __restrict__ e, int n,
                                                                    const double* __restrict__ scal, double* lam_desc, double* lam_asc_scaled, int* flag) {
   extern __shared__ __attribute__((aligned(16))) double bis_lds[];
   __shared__ double red[2][TRD_BIS_THREADS / 64];
-  double* sd = bis_lds;
-  double* se2 = bis_lds + n;
+  __shared__ double e2m_sh;
   const int tid = threadIdx.x;
+  const int m = n >> 1, nb = n - 1 - m;                          // rows of the forward and of the backward chain (nb <= m <= nb + 1)
+  double2* recs = reinterpret_cast<double2*>(bis_lds);
   double gl = 1.7e308, gu = -1.7e308;
   bool bad = false;
   for (int i = tid; i < n; i += TRD_BIS_THREADS) {
     const double di = d[i];
     const double el = i > 0 ? e[i - 1] : 0.0, er = i < n - 1 ? e[i] : 0.0;
     if (!(fabs(di) <= 1.7e308) || !(fabs(er) <= 1.7e308)) bad = true;
-    sd[i] = di;
-    // se2[i] couples i and i+1.  Floor 2^-200 (the matrix is scaled to norm <= 1: a perturbation of 8e-31 of an entry) so
-    // that an exactly split matrix (e = 0) cannot leave two consecutive zero minors behind - see the count below
-    se2[i] = fmax(er * er, 0x1p-200);
+    // Floor 2^-200 on e^2 (the matrix is scaled to norm <= 1: a perturbation of 8e-31 of an entry) so that an exactly split
+    // matrix (e = 0) cannot leave two consecutive zero minors behind - see the count below
+    const double e2l = fmax(el * el, TRD_E2_FLOOR), e2r = fmax(er * er, TRD_E2_FLOOR);
+    if (i <= m) recs[i] = make_double2(di, e2l);
+    else recs[m + 1 + (n - 1 - i)] = make_double2(di, e2r);
+    if (i == m) e2m_sh = e2r;                                    // couples the junction row m with the backward part
     const double r = fabs(el) + fabs(er);
     gl = fmin(gl, di - r);
     gu = fmax(gu, di + r);
@@ -1180,72 +1198,97 @@ __global__ __launch_bounds__(TRD_BIS_THREADS) void trd_bisect_kernel(const doubl
   const double bnorm = fmax(fabs(gl), fabs(gu));
   gl -= 2.2e-16 * bnorm * n + 1e-300;
   gu += 2.2e-16 * bnorm * n + 1e-300;
-  const int grp = tid >> 4, l = tid & 15;
-  const int k = blockIdx.x * (TRD_BIS_THREADS / 16) + grp;       // eigenvalue index, ascending
+  const int grp = tid / TRD_BIS_LANES, l = tid & 15;
+  const bool back = (tid >> 4) & 1;                              // the second sixteen lanes of a group run the backward chain
+  const int k = blockIdx.x * (TRD_BIS_THREADS / TRD_BIS_LANES) + grp;       // eigenvalue index, ascending
   const bool live = k < n;
   double lo = gl, hi = gu;
-  const int gshift = ((tid & 63) >> 4) * 16;
+  const int gshift = ((tid & 63) / TRD_BIS_LANES) * TRD_BIS_LANES;
+  // the lane's chain: its records and its rows (no backward row, n <= 2: that chain stays at q_n = 1, q_{n+1} = 0)
+  const double2* rec = recs + (back && nb > 0 ? m + 1 : 0);
+  const int len = back ? nb : m;
+  const double2 rj = recs[m];                                    // {d_m, e_{m-1}^2}
+  const double e2m = e2m_sh;
   for (int pass = 0; pass < 14; ++pass) {
     const double x = lo + (hi - lo) * ((double)(l + 1) * (1.0 / 17.0));
-    // Sturm count by the three-term recurrence of the leading principal minors, p_{i+1} = (d_i - x) p_i - e_{i-1}^2 p_{i-1}:
-    // count = sign changes along p_0 = 1, p_1, ..., p_n.  One dependent FMA per row instead of a division; the pair
-    // (p_i, p_{i-1}) is rescaled by a power of two every eight rows (growth per row is bounded by ~5 for the scaled matrix, so
-    // neither overflows within eight rows, and the larger of the two is kept near 1).
+    // A chain: count = sign changes along 1, c_1, ..., c_len by the three-term recurrence, one dependent FMA per row instead
+    // of a division; the pair (c_i, c_{i-1}) is rescaled by a power of two every eight rows (growth per row is bounded by ~5 for
+    // the scaled matrix, so neither overflows within eight rows - nor within the up to eight rows of a chain's tail and the
+    // junction's products behind them - and the larger of the two is kept near 1).  Both chains are cut into their eight-row
+    // blocks by the SHORTER one's length nb, so that the lanes of a wave stay together; the longer one has one more row in its tail.
     // An exact zero needs no fix-up in the chain (round 4: the compare + selects were a third of the row's instructions and
-    // sat on its dependent path): e^2 has a floor (below), so a zero p_i is followed by p_{i+1} = -e_i^2 p_{i-1} != 0 of the
-    // sign opposite to p_{i-1} - exactly one sign change over the two steps whichever sign the zero is given, the same count
-    // as dstebz's "a zero takes the sign opposite to its predecessor".  Signs are compared on the high words.
-    double pm = 1.0, pc = sd[0] - x;
-    unsigned int sc = (unsigned int)__double2hiint(pc);
-    int cnt = (int)(sc >> 31);
+    // sat on its dependent path): e^2 has a floor, so a zero c_i is followed by c_{i+1} = -e^2 c_{i-1} != 0 of the sign
+    // opposite to c_{i-1} - exactly one sign change over the two steps whichever sign the zero is given, the same count as
+    // dstebz's "a zero takes the sign opposite to its predecessor".
+    double pm = len > 0 ? 1.0 : 0.0, pc = len > 0 ? rec[0].x - x : 1.0;
+    // the signs so far, newest in bit 0: one v_alignbit per row, the changes counted by a popcount once per block
+    unsigned int sg = (unsigned int)__double2hiint(pc) >> 31;
+    int cnt = (int)sg;
+    auto row = [&](double2 r) __attribute__((always_inline)) {
+      const double pn = fma(r.x - x, pc, -(r.y * pm));
+      sg = __builtin_amdgcn_alignbit(sg, (unsigned int)__double2hiint(pn), 31);
+      pm = pc;
+      pc = pn;
+    };
     int i = 1;
-    // (the operands of the NEXT eight rows are requested before the current eight are used: the LDS latency stays off the chain)
-    double dv[8], ev[8];
-    if (i + 8 <= n) {
+    // The records of the NEXT eight rows are requested before the current eight are used - the LDS latency stays off the
+    // chain - into the other of two buffers: no register copies between the blocks.
+    double2 va[8], vb[8];
+    auto load8 = [&](double2 (&v)[8], int i0) __attribute__((always_inline)) {
 #pragma unroll
-      for (int u = 0; u < 8; ++u) { dv[u] = sd[i + u]; ev[u] = se2[i + u - 1]; }
-    }
-    for (; i + 8 <= n; i += 8) {
-      double dn[8], en[8];
-      const int inext = i + 16 <= n ? i + 8 : i;           // (the last block reads its own rows again)
+      for (int u = 0; u < 8; ++u) v[u] = rec[i0 + u];
+    };
+    auto block8 = [&](const double2 (&v)[8]) __attribute__((always_inline)) {
 #pragma unroll
-      for (int u = 0; u < 8; ++u) { dn[u] = sd[inext + u]; en[u] = se2[inext + u - 1]; }
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const double pn = fma(dv[u] - x, pc, -(ev[u] * pm));
-        const unsigned int sn = (unsigned int)__double2hiint(pn);
-        cnt += (int)((sn ^ sc) >> 31);
-        sc = sn;
-        pm = pc;
-        pc = pn;
-      }
+      for (int u = 0; u < 8; ++u) row(v[u]);
+      cnt += __popc((sg ^ (sg >> 1)) & 0xFFu);
       const double mx = fmax(fabs(pc), fabs(pm));
-      if (mx == 0.0) pc = (sc >> 31) ? -1.0 : 1.0;            // (both underflowed: start again with the sign kept - not reachable with the floor on e^2)
+      if (mx == 0.0) pc = (sg & 1u) ? -1.0 : 1.0;          // (both underflowed: start again with the sign kept - not reachable with the floor on e^2)
       const int ex = __builtin_amdgcn_frexp_exp(mx);
       pc = ldexp(pc, -ex);
       pm = ldexp(pm, -ex);
-#pragma unroll
-      for (int u = 0; u < 8; ++u) { dv[u] = dn[u]; ev[u] = en[u]; }
+    };
+    if (i + 8 <= nb) load8(va, i);
+    while (i + 8 <= nb) {
+      const bool more = i + 16 <= nb;                      // (the last block reads its own rows again)
+      load8(vb, more ? i + 8 : i);
+      __builtin_amdgcn_sched_barrier(0);
+      block8(va);
+      i += 8;
+      if (!more) break;
+      load8(va, i + 16 <= nb ? i + 8 : i);
+      __builtin_amdgcn_sched_barrier(0);
+      block8(vb);
+      i += 8;
     }
-    for (; i < n; ++i) {
-      const double pn = fma(sd[i] - x, pc, -(se2[i - 1] * pm));
-      const unsigned int sn = (unsigned int)__double2hiint(pn);
-      cnt += (int)((sn ^ sc) >> 31);
-      sc = sn;
-      pm = pc;
-      pc = pn;
+    for (; i < len; ++i) {
+      row(rec[i]);
+      cnt += (int)((sg ^ (sg >> 1)) & 1u);
     }
-    const unsigned long long mask = __ballot(cnt <= k);
+    // junction: p_{m+1} (forward lanes), the partner's pair, det and the sign of gamma_m
+    const double ext = fma(rj.x - x, pc, -(rj.y * pm));
+    const double o_pc = __shfl_xor(pc, 16), o_pm = __shfl_xor(pm, 16), o_ext = __shfl_xor(ext, 16);
+    const double f_pc = back ? o_pc : pc, f_ext = back ? o_ext : ext;
+    const double q_c = back ? pc : o_pc, q_m = back ? pm : o_pm;
+    const double det = fma(f_ext, q_c, -((e2m * f_pc) * q_m));
+    const int total = cnt + __shfl_xor(cnt, 16) + (int)(((unsigned int)(__double2hiint(det) ^ __double2hiint(f_pc) ^ __double2hiint(q_c))) >> 31);
+    const unsigned long long mask = __ballot(total <= k);
     const int s = __popcll((mask >> gshift) & 0xFFFFull);       // points at or below eigenvalue k (counts are monotone in x)
     const double x_lo = __shfl(x, s > 0 ? s - 1 : 0, 16);
     const double x_hi = __shfl(x, s < 16 ? s : 15, 16);
     if (s > 0) lo = x_lo;
     if (s < 16) hi = x_hi;
   }
-  if (live && l == 0) {
+  if (live && (tid & (TRD_BIS_LANES - 1)) == 0) {
     lam_desc[n - 1 - k] = 0.5 * (lo + hi) / scal[0];
     if (lam_asc_scaled) lam_asc_scaled[k] = 0.5 * (lo + hi);
   }
+}
+inline void trd_bisect_launch(hipStream_t st, const double* d, const double* e, int n, const double* scal, double* lam_desc, double* lam_asc_scaled,
+                              int* flag) {
+  XMCA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(trd_bisect_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+  hipLaunchKernelGGL(trd_bisect_kernel, dim3(ceil_div(n, TRD_BIS_THREADS / TRD_BIS_LANES)), dim3(TRD_BIS_THREADS), sizeof(double) * 2 * (size_t)n, st,
+                     d, e, n, scal, lam_desc, lam_asc_scaled, flag);
 }
 
 struct TrdWorkspace {
@@ -1654,9 +1697,7 @@ inline void trd_eigenvalues(hipStream_t st, TrdWorkspace& ws, const TrdParams& P
                             DevBuf<double>& lam_tmp, double* lam_asc_scaled = nullptr) {
   const int n = P.n;
   double* out = lam_dev ? lam_dev : lam_tmp.ensure((size_t)n);
-  XMCA_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(trd_bisect_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-  hipLaunchKernelGGL(trd_bisect_kernel, dim3(ceil_div(n, TRD_BIS_THREADS / 16)), dim3(TRD_BIS_THREADS), sizeof(double) * 2 * (size_t)n, st, P.d,
-                     P.e, n, ws.scal.get(), out, lam_asc_scaled, ws.flag.get());
+  trd_bisect_launch(st, P.d, P.e, n, ws.scal.get(), out, lam_asc_scaled, ws.flag.get());
   XMCA_HIP(hipGetLastError());
   lam_host.resize((size_t)n);
   int flag = 0;
