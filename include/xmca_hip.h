@@ -786,7 +786,7 @@ int xmca_fft_ex(xmca_handle* h, const double* in_re, const double* in_im, int64_
  * descending, in the caller's scale.  A non-finite entry returns XMCA_ERR_NUMERIC as a solve does; n < 1 or a NULL pointer
  * returns XMCA_ERR_INVALID before anything is launched. */
 int xmca_tridiag_eigenvalues(xmca_handle* h, const double* d, const double* e, int n, double* lam_desc);
-/* The twisted-factorisation vectors behind every tridiagonal solve (csrc/tridiag_vec.h trd_twisted_kernel; kernel tests only),
+/* The twisted-factorisation vectors behind every tridiagonal solve (csrc/tridiag_vec.h trd_twisted_vectors; kernel tests only),
  * host in / host out: lam holds nev (1 .. n) eigenvalues of the matrix (d, e) above, ascending, in the scale of d and e - the
  * caller's, so nothing here depends on the Sturm kernel; the same f is applied to d, e and lam.  The kernel gets planes of n rows
  * of ldy >= nev elements: Y (n x ldy) goes to the device before the launch and comes back whole, column k the unit vector of

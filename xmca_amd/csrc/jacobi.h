@@ -427,9 +427,14 @@ inline void hermitian_evd(hipStream_t st, EvdWorkspace& ws, const double* Ar, co
   if (Zr && !nearly_diagonal && evd_vectors_by_reduction(n, Ai != nullptr)) {
     ws.trdv.count_call();
     TrdParams P = trd_reduce(st, ws.trd, Ar, Ai, n, lda, true);
-    trd_wy_prepare(st, ws.trdv, ws.gws, P, Ai != nullptr);  // (from the second call on: on a second stream, under the two kernels below)
+    // The Sturm kernel is queued FIRST, so that it starts when the reduction ends and not behind the host's queueing of the
+    // compact-WY launches; those wait for the reduction alone (the fork is recorded in front of the Sturm kernel) and run on
+    // a second stream from the second call on, under the Sturm and twisted kernels - otherwise on `st` behind the Sturm kernel.
+    trd_wy_fork(st, ws.trdv, P);
     std::vector<double> lam_t;
-    trd_eigenvalues(st, ws.trd, P, lam_t, lam_dev, ws.lam_tmp, ws.trdv.lam_asc.ensure((size_t)n));
+    trd_eigenvalues_launch(st, ws.trd, P, lam_dev, ws.lam_tmp, ws.trdv.lam_asc.ensure((size_t)n));
+    trd_wy_prepare(st, ws.trdv, ws.gws, P, Ai != nullptr);
+    trd_eigenvalues_collect(st, ws.trd, P, lam_t, ws.lam_tmp);
     if (part) {
       // The leading n_lead vectors only: k' of them are formed (the guard above).  Whatever keeps the partial stage from
       // finishing - no gap within the cap, more than n / 4 vectors, bit-equal leading values, a refused clean-up - goes on

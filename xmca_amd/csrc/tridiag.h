@@ -1692,22 +1692,49 @@ inline void trd_trace_checksums(hipStream_t st, const TrdParams& P, const double
   }
 }
 
-// all eigenvalues, descending, into lam_dev (device, n doubles; may be nullptr) and lam_host.  Synchronises `st`.
+// What the host reads behind the Sturm kernel, in one buffer for one copy: pack[0 .. n) = lam (when it lies elsewhere),
+// pack[n] = flag[0] != 0, pack[n + 1], pack[n + 2] = scal[0], scal[1].  (flag is complete only when trd_bisect_kernel has ended.)
+__global__ __launch_bounds__(256) void trd_eig_pack_kernel(const double* lam, int n, const int* __restrict__ flag,
+                                                           const double* __restrict__ scal, double* pack) {
+  if (lam != pack)
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) pack[i] = lam[i];
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    pack[n] = flag[0] != 0 ? 1.0 : 0.0;
+    pack[n + 1] = scal[0];
+    pack[n + 2] = scal[1];
+  }
+}
+
+// All eigenvalues, descending, into lam_dev (device, n doubles; may be nullptr) and lam_host, in two halves so that the caller
+// can queue other work between them: _launch queues the Sturm kernel on `st` and gathers what the host wants in lam_tmp (n + 3
+// doubles: the eigenvalues, the flag, the two scale words); _collect fetches them with ONE copy, synchronises `st` and raises
+// the numeric error of a non-finite input.
+inline void trd_eigenvalues_launch(hipStream_t st, TrdWorkspace& ws, const TrdParams& P, double* lam_dev, DevBuf<double>& lam_tmp,
+                                   double* lam_asc_scaled = nullptr) {
+  const int n = P.n;
+  double* pack = lam_tmp.ensure((size_t)n + 3);
+  double* out = lam_dev ? lam_dev : pack;
+  trd_bisect_launch(st, P.d, P.e, n, ws.scal.get(), out, lam_asc_scaled, ws.flag.get());
+  hipLaunchKernelGGL(trd_eig_pack_kernel, dim3(lam_dev ? std::min(ceil_div(n, 256), 64) : 1), dim3(256), 0, st, out, n, ws.flag.get(), ws.scal.get(), pack);
+  XMCA_HIP(hipGetLastError());
+}
+// (the copy is issued HERE: into pageable memory it holds the host until the Sturm kernel has ended - measured: issued in
+// _launch, everything the caller queued behind it started 790 us after the reduction instead of beside the Sturm kernel)
+inline void trd_eigenvalues_collect(hipStream_t st, TrdWorkspace& ws, const TrdParams& P, std::vector<double>& lam_host, DevBuf<double>& lam_tmp) {
+  const size_t n = (size_t)P.n;
+  lam_host.resize(n + 3);
+  XMCA_HIP(hipMemcpyAsync(lam_host.data(), lam_tmp.get(), sizeof(double) * (n + 3), hipMemcpyDeviceToHost, st));
+  XMCA_HIP(hipStreamSynchronize(st));
+  const bool bad = lam_host[n] != 0.0 || lam_host[n + 2] != 0.0;
+  lam_host.resize(n);
+  ws.ev_collect();
+  XMCA_CHECK(!bad, XMCA_ERR_NUMERIC, "SVD failed. NaN entries may be the problem.");
+}
+// both halves.  Synchronises `st`.
 inline void trd_eigenvalues(hipStream_t st, TrdWorkspace& ws, const TrdParams& P, std::vector<double>& lam_host, double* lam_dev,
                             DevBuf<double>& lam_tmp, double* lam_asc_scaled = nullptr) {
-  const int n = P.n;
-  double* out = lam_dev ? lam_dev : lam_tmp.ensure((size_t)n);
-  trd_bisect_launch(st, P.d, P.e, n, ws.scal.get(), out, lam_asc_scaled, ws.flag.get());
-  XMCA_HIP(hipGetLastError());
-  lam_host.resize((size_t)n);
-  int flag = 0;
-  double scal[2] = {1.0, 0.0};
-  XMCA_HIP(hipMemcpyAsync(lam_host.data(), out, sizeof(double) * n, hipMemcpyDeviceToHost, st));
-  XMCA_HIP(hipMemcpyAsync(&flag, ws.flag.get(), sizeof(int), hipMemcpyDeviceToHost, st));
-  XMCA_HIP(hipMemcpyAsync(scal, ws.scal.get(), sizeof(double) * 2, hipMemcpyDeviceToHost, st));
-  XMCA_HIP(hipStreamSynchronize(st));
-  ws.ev_collect();
-  XMCA_CHECK(flag == 0 && scal[1] == 0.0, XMCA_ERR_NUMERIC, "SVD failed. NaN entries may be the problem.");
+  trd_eigenvalues_launch(st, ws, P, lam_dev, lam_tmp, lam_asc_scaled);
+  trd_eigenvalues_collect(st, ws, P, lam_host, lam_tmp);
 }
 
 }  // namespace xmca

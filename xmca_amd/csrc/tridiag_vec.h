@@ -1,8 +1,10 @@
 // Eigenvectors for the tridiagonal route (tridiag.h):  A = Q T Q^H,  T y_k = lambda_k y_k,  u_k = Q y_k.
 //
-//   1. trd_twisted_kernel - one lane pair per eigenvalue: the two stationary factorisations of T - lambda_k I (forward L D+ L^T,
-//      backward U D- U^T), the twist index r = argmin |gamma_r| and the vector z(r) = 1, z(i) = -(e_i / D+_i) z(i+1) upwards,
-//      z(i+1) = -(e_i / D-_{i+1}) z(i) downwards (Parlett & Dhillon; LAPACK dlar1v without the RRR shifts).  With an
+//   1. trd_twisted_vectors - four kernels, a lane per eigenvalue in each: the two stationary factorisations of T - lambda_k I
+//      (forward L D+ L^T, backward U D- U^T; trd_twisted_kernel, one wave per direction), the twist index r = argmin |gamma_r|
+//      (trd_twist_index_kernel, chip-wide over row segments), the vector z(r) = 1, z(i) = -(e_i / D+_i) z(i+1) upwards,
+//      z(i+1) = -(e_i / D-_{i+1}) z(i) downwards (trd_twist_vector_kernel, one wave per direction) and its scaling to unit
+//      length (trd_twist_scale_kernel, chip-wide) (Parlett & Dhillon; LAPACK dlar1v without the RRR shifts).  With an
 //      eigenvalue accurate to eps ||T|| the residual is eps ||T||; vectors of close eigenvalues are orthogonal only to
 //      eps ||T|| / gap - the clean-up below restores that;
 //   2. back-transformation with super-blocks of 512 reflectors in compact WY form, Z -= V (T (V^H Z)): two MFMA GEMMs per
@@ -34,21 +36,30 @@ __device__ __forceinline__ double trd_lane_value(double v, int u) {
 // Yt[i * ldy + k] = component i of the eigenvector of eigenvalue lam[k], k < nev;  W: work plane of the same shape (n x ldy).
 // n is the order of the tridiagonal matrix, nev the number of eigenvalues handed in: all n of them (ascending) on the full
 // route, the k' leading ones on the partial route (trd_eigenvectors_partial), whose planes are n x k' only.
-// 128 threads per 64 eigenvalues: the forward (D+) and the backward (D-) factorisation are independent recurrences and run
-// in the two waves side by side; so do the two halves of the vector (upwards / downwards from the twist index) and of the
-// final scaling.  Every loop requests its operands one chunk (64 rows of d / e, 32 rows of the planes) ahead of the recurrence.
+// Four kernels (trd_twisted_vectors), cut where the work changes its nature: the two recurrences can use one wave per 64
+// eigenvalues and direction - 92 waves at n = 2920 - and nothing more; the twist-index scan and the final scaling are streams
+// over the planes without a recurrence and are spread over the whole chip.
+//   trd_twisted_kernel       the pivots: D+ into Yt, D- into W.  128 threads per 64 eigenvalues: the forward and the backward
+//                            factorisation are independent recurrences and run in the two waves side by side, each requesting
+//                            its next 64 rows of d / e ahead of the recurrence;
+//   trd_twist_index_kernel   per 64 eigenvalues and segment of TRD_TW_SEG rows (one wave): the first smallest |gamma| of the
+//                            segment and its row;
+//   trd_twist_vector_kernel  the segments' minima combined (ascending, strict <: the first occurrence of the minimum, as a single
+//                            scan would find it), then the two halves of the vector upwards / downwards from the twist index in
+//                            the two waves, unnormalised, and the scale 1 / ||z|| of every eigenvalue;
+//   trd_twist_scale_kernel   Yt[i][k] *= scale[k], segments as in the index kernel.
+// Per lane the operations and their order are those of the single kernel these four were: the same bits.
+// At n = 2920 in the step of the bench: 221 + 36 + 303 + 26 us (the single kernel: 727 us).
+constexpr int TRD_TW_SEG = 64;               // rows per wave of the two streaming kernels
 __global__ __launch_bounds__(128) void trd_twisted_kernel(const double* __restrict__ d, const double* __restrict__ e, int n, int nev,
                                                          const double* __restrict__ lam, double* __restrict__ W, double* __restrict__ Yt,
                                                          int64_t ldy) {
-  __shared__ double nrm_sh[2][64];
-  __shared__ int idx_sh[2][64];
   const int lane = threadIdx.x & 63, half = threadIdx.x >> 6;
   const int k = blockIdx.x * 64 + lane;
   const bool live = k < nev;
   const int kk = live ? k : nev - 1;                         // (idle lanes shadow the last eigenvalue and store nothing)
   const double l = lam[kk];
-  if (n == 1) { if (live && half == 0) Yt[k] = 1.0; return; }
-  constexpr int B = 32;
+  if (n == 1) { if (live && half == 0) Yt[k] = 1.0; return; }       // (the vector itself: the other three kernels do not run)
   double emax = 0.0;
   for (int i = lane; i < n - 1; i += 64) emax = fmax(emax, fabs(e[i]));
   for (int o = 32; o > 0; o >>= 1) emax = fmax(emax, __shfl_xor(emax, o));
@@ -104,45 +115,93 @@ __global__ __launch_bounds__(128) void trd_twisted_kernel(const double* __restri
       ev = ev_n; dv = dv_n;
     }
   }
-  __threadfence_block();
-  __syncthreads();
-  // twist index: gamma_i = D+_i + D-_i - (d_i - lambda), smallest |gamma| (no recurrence, pure streaming: each wave scans one
-  // half of the rows, the lower half wins ties - the first occurrence of the minimum, as a single scan would find it; rows
-  // past a half's end repeat its last row, which cannot displace that)
+}
+
+// gamma_i = D+_i + D-_i - (d_i - lambda) over the rows of one segment, per eigenvalue: gpart / rpart[seg * nev + k] = the
+// smallest |gamma| below 1.7e308 and its first row (1.7e308 and the segment's first row when there is none: not finite, or
+// not below).  No recurrence, pure streaming: 64 eigenvalues across the lanes, every access one coalesced row; rows past the
+// segment's end repeat its last row, which cannot displace that.  Grid: (nev / 64, segments / 4), four segments per workgroup.
+__global__ __launch_bounds__(256) void trd_twist_index_kernel(const double* __restrict__ d, int n, int nev, const double* __restrict__ lam,
+                                                             const double* __restrict__ W, const double* __restrict__ Yt, int64_t ldy,
+                                                             double* __restrict__ gpart, int* __restrict__ rpart) {
+  const int lane = threadIdx.x & 63;
+  const int seg = blockIdx.y * 4 + (threadIdx.x >> 6);
+  const int h0s = seg * TRD_TW_SEG;
+  if (h0s >= n) return;                                      // (uniform per wave; no barrier below)
+  const int h1s = h0s + TRD_TW_SEG < n ? h0s + TRD_TW_SEG : n;
+  const int k = blockIdx.x * 64 + lane;
+  const bool live = k < nev;
+  const int kk = live ? k : nev - 1;
+  const double l = lam[kk];
+  constexpr int B = 32;
+  double gbest = 1.7e308;
+  int r = h0s;
+  for (int i0 = h0s; i0 < h1s; i0 += B) {
+    double yp[B], wm[B];
+    const double dv = d[i0 + lane < h1s ? i0 + lane : h1s - 1];
+#pragma unroll
+    for (int u = 0; u < B; ++u) {
+      const int i = i0 + u < h1s ? i0 + u : h1s - 1;
+      yp[u] = Yt[(int64_t)i * ldy + kk];
+      wm[u] = W[(int64_t)i * ldy + kk];
+    }
+#pragma unroll
+    for (int u = 0; u < B; ++u) {
+      const int i = i0 + u < h1s ? i0 + u : h1s - 1;
+      const double g = fabs(yp[u] + wm[u] - (trd_lane_value(dv, u) - l));
+      if (g < gbest) { gbest = g; r = i; }
+    }
+  }
+  if (live) {
+    gpart[(int64_t)seg * nev + k] = gbest;
+    rpart[(int64_t)seg * nev + k] = r;
+  }
+}
+
+// The vector of every eigenvalue, unnormalised, over the pivots in Yt (D+) and W (D-): z(r) = 1 at the twist index r, and
+// scale[k] = 1 / sqrt(sum of the squares upwards + sum downwards).  r: the segments of trd_twist_index_kernel combined in
+// ascending order with a strict <, from 1.7e308 and row 0 - the first occurrence of the smallest |gamma| over all rows.
+__global__ __launch_bounds__(128) void trd_twist_vector_kernel(const double* __restrict__ e, int n, int nev, const double* __restrict__ W,
+                                                              double* __restrict__ Yt, int64_t ldy, const double* __restrict__ gpart,
+                                                              const int* __restrict__ rpart, int nseg, double* __restrict__ scale) {
+  __shared__ double nrm_sh[2][64];
+  const int lane = threadIdx.x & 63, half = threadIdx.x >> 6;
+  const int k = blockIdx.x * 64 + lane;
+  const bool live = k < nev;
+  const int kk = live ? k : nev - 1;                         // (idle lanes shadow the last eigenvalue and store nothing)
   int r = 0;
   {
-    const int h0s = half == 0 ? 0 : n / 2, h1s = half == 0 ? n / 2 : n;     // (n >= 2: neither half is empty)
+    constexpr int BS = 16;                                   // (segments past the last repeat it: a strict < never takes them)
     double gbest = 1.7e308;
-    r = h0s;
-    for (int i0 = h0s; i0 < h1s; i0 += B) {
-      double yp[B], wm[B];
-      const double dv = d[i0 + lane < h1s ? i0 + lane : h1s - 1];
+    for (int s0 = 0; s0 < nseg; s0 += BS) {
+      double gs[BS];
+      int rs[BS];
 #pragma unroll
-      for (int u = 0; u < B; ++u) {
-        const int i = i0 + u < h1s ? i0 + u : h1s - 1;
-        yp[u] = Yt[(int64_t)i * ldy + kk];
-        wm[u] = W[(int64_t)i * ldy + kk];
+      for (int u = 0; u < BS; ++u) {
+        const int s = s0 + u < nseg ? s0 + u : nseg - 1;
+        gs[u] = gpart[(int64_t)s * nev + kk];
+        rs[u] = rpart[(int64_t)s * nev + kk];
       }
 #pragma unroll
-      for (int u = 0; u < B; ++u) {
-        const int i = i0 + u < h1s ? i0 + u : h1s - 1;
-        const double g = fabs(yp[u] + wm[u] - (trd_lane_value(dv, u) - l));
-        if (g < gbest) { gbest = g; r = i; }
-      }
+      for (int u = 0; u < BS; ++u)
+        if (gs[u] < gbest) { gbest = gs[u]; r = rs[u]; }
     }
-    nrm_sh[half][lane] = gbest;
-    idx_sh[half][lane] = r;
-    __syncthreads();
-    if (nrm_sh[0][lane] <= nrm_sh[1][lane]) r = idx_sh[0][lane];
-    else r = idx_sh[1][lane];
   }
-  __syncthreads();                                           // (both waves have read D+ before the upper half overwrites it)
   double nrm = 0.0;
   // The twist index differs from lane to lane, the ROW index of the two vector recurrences must not: with per-lane rows every
   // load and store of a wave touched 64 different cache lines (round 3-4: 500 of the kernel's 970 us, 16 x the bytes).  Both
   // loops therefore walk the rows of the whole wave - from the largest twist index down, from the smallest one up - and a lane
   // joins when the walk reaches its own twist: coalesced rows, e[i] by lane broadcast, the same arithmetic per lane as before.
-  constexpr int B3 = 64;
+  // The rows of the NEXT batch (and its 32 values of e) are requested before the current batch is worked on, into the other
+  // of two buffers: a batch's stores then lie BEHIND the loads the next batch waits for - loads and stores leave the same
+  // in-order counter, and with the request behind the stores every batch waited for its predecessor's rows to be written
+  // (363 -> 335 us at n = 2920).  A batch past the end requests row 0 / n - 1 again and is not used.
+  // The walk's row is held in scalar registers (readfirstlane) and every access is row pointer + lane offset: with the row in
+  // a vector register each load and store cost a 64-bit multiply-add per lane, and the kernel is bound by the instructions it
+  // issues - one wave per SIMD, nothing to hide them behind (335 -> 303 us).  An idle lane never joins (its twist lies
+  // outside the walk).
+  constexpr int B3 = 32;
+  const unsigned ko = (unsigned)kk;                          // (= k in every lane that stores)
   if (half == 0) {
     // upwards from the twist: z(i) = -(e_i / D+_i) z(i+1)
     double z = 1.0;
@@ -150,61 +209,132 @@ __global__ __launch_bounds__(128) void trd_twisted_kernel(const double* __restri
     if (live) Yt[(int64_t)r * ldy + k] = 1.0;
     int rmax = r;
     for (int o = 32; o > 0; o >>= 1) rmax = max(rmax, __shfl_xor(rmax, o));
-    for (int i0 = rmax - 1; i0 >= 0; i0 -= B3) {
-      double yp[B3];
-      const double ev = e[i0 - lane >= 0 ? i0 - lane : 0];
+    rmax = __builtin_amdgcn_readfirstlane(rmax);
+    const int rj = live ? r : 0;
+    double ya[B3], yb[B3], eva, evb;
+    auto request = [&](double (&yp)[B3], double& ev, int i0) __attribute__((always_inline)) {
+      ev = e[i0 - lane >= 0 ? i0 - lane : 0];
 #pragma unroll
-      for (int u = 0; u < B3; ++u) yp[u] = Yt[(int64_t)(i0 - u >= 0 ? i0 - u : 0) * ldy + kk];
+      for (int u = 0; u < B3; ++u) yp[u] = (Yt + (int64_t)(i0 - u >= 0 ? i0 - u : 0) * ldy)[ko];
+    };
+    auto batch = [&](const double (&yp)[B3], double ev, int i0) __attribute__((always_inline)) {
 #pragma unroll
       for (int u = 0; u < B3; ++u) {
         const int i = i0 - u;
         if (i >= 0) {                                        // (uniform)
           const double zn = -(trd_lane_value(ev, u) * trd_rcp(yp[u])) * z;
-          if (i < r) {
+          if (i < rj) {
             z = zn;
-            if (live) Yt[(int64_t)i * ldy + k] = z;
+            (Yt + (int64_t)i * ldy)[ko] = z;
             nrm += z * z;
           }
         }
       }
+    };
+    int i0 = rmax - 1;
+    if (i0 >= 0) request(ya, eva, i0);
+    while (i0 >= 0) {
+      request(yb, evb, i0 - B3);
+      __builtin_amdgcn_sched_barrier(0);
+      batch(ya, eva, i0);
+      i0 -= B3;
+      if (i0 < 0) break;
+      request(ya, eva, i0 - B3);
+      __builtin_amdgcn_sched_barrier(0);
+      batch(yb, evb, i0);
+      i0 -= B3;
     }
   } else {
     // downwards: z(i+1) = -(e_i / D-_{i+1}) z(i)
     double z = 1.0;
     int rmin = r;
     for (int o = 32; o > 0; o >>= 1) rmin = min(rmin, __shfl_xor(rmin, o));
-    for (int i0 = rmin; i0 < n - 1; i0 += B3) {
-      double wm[B3];
-      const double ev = e[i0 + lane < n - 1 ? i0 + lane : n - 2];
+    rmin = __builtin_amdgcn_readfirstlane(rmin);
+    const int rj = live ? r : n;
+    double wa[B3], wb[B3], eva, evb;
+    auto request = [&](double (&wm)[B3], double& ev, int i0) __attribute__((always_inline)) {
+      ev = e[i0 + lane < n - 1 ? i0 + lane : n - 2];
 #pragma unroll
-      for (int u = 0; u < B3; ++u) wm[u] = W[(int64_t)((i0 + u < n - 1 ? i0 + u : n - 2) + 1) * ldy + kk];
+      for (int u = 0; u < B3; ++u) wm[u] = (W + (int64_t)((i0 + u < n - 1 ? i0 + u : n - 2) + 1) * ldy)[ko];
+    };
+    auto batch = [&](const double (&wm)[B3], double ev, int i0) __attribute__((always_inline)) {
 #pragma unroll
       for (int u = 0; u < B3; ++u) {
         const int i = i0 + u;
         if (i < n - 1) {                                     // (uniform)
           const double zn = -(trd_lane_value(ev, u) * trd_rcp(wm[u])) * z;
-          if (i >= r) {
+          if (i >= rj) {
             z = zn;
-            if (live) Yt[(int64_t)(i + 1) * ldy + k] = z;
+            (Yt + (int64_t)(i + 1) * ldy)[ko] = z;
             nrm += z * z;
           }
         }
       }
+    };
+    int i0 = rmin;
+    if (i0 < n - 1) request(wa, eva, i0);
+    while (i0 < n - 1) {
+      request(wb, evb, i0 + B3);
+      __builtin_amdgcn_sched_barrier(0);
+      batch(wa, eva, i0);
+      i0 += B3;
+      if (i0 >= n - 1) break;
+      request(wa, eva, i0 + B3);
+      __builtin_amdgcn_sched_barrier(0);
+      batch(wb, evb, i0);
+      i0 += B3;
     }
   }
   nrm_sh[half][lane] = nrm;
-  __threadfence_block();
   __syncthreads();
-  const double s = 1.0 / sqrt(nrm_sh[0][lane] + nrm_sh[1][lane]);
-  const int h0 = half == 0 ? 0 : n / 2, h1 = half == 0 ? n / 2 : n;
-  for (int i0 = h0; i0 < h1; i0 += B3) {
-    double y[B3];
+  if (half == 0 && live) scale[k] = 1.0 / sqrt(nrm_sh[0][lane] + nrm_sh[1][lane]);
+}
+
+// Yt[i][k] *= scale[k]: one segment of TRD_TW_SEG rows per wave, 64 eigenvalues across the lanes (grid as trd_twist_index_kernel)
+__global__ __launch_bounds__(256) void trd_twist_scale_kernel(int n, int nev, const double* __restrict__ scale, double* __restrict__ Yt,
+                                                             int64_t ldy) {
+  const int lane = threadIdx.x & 63;
+  const int h0 = (blockIdx.y * 4 + (threadIdx.x >> 6)) * TRD_TW_SEG;
+  if (h0 >= n) return;
+  const int h1 = h0 + TRD_TW_SEG < n ? h0 + TRD_TW_SEG : n;
+  const int k = blockIdx.x * 64 + lane;
+  const bool live = k < nev;
+  const int kk = live ? k : nev - 1;
+  const double s = scale[kk];
+  constexpr int B = 32;
+  for (int i0 = h0; i0 < h1; i0 += B) {
+    double y[B];
 #pragma unroll
-    for (int u = 0; u < B3; ++u) y[u] = Yt[(int64_t)(i0 + u < h1 ? i0 + u : h1 - 1) * ldy + kk];
+    for (int u = 0; u < B; ++u) y[u] = Yt[(int64_t)(i0 + u < h1 ? i0 + u : h1 - 1) * ldy + kk];
 #pragma unroll
-    for (int u = 0; u < B3; ++u)
+    for (int u = 0; u < B; ++u)
       if (live && i0 + u < h1) Yt[(int64_t)(i0 + u) * ldy + k] = y[u] * s;
   }
+}
+
+// partial minima of trd_twist_index_kernel (segments x nev) and the scales of trd_twist_vector_kernel (nev)
+struct TrdTwistScratch {
+  DevBuf<double> g, scale;
+  DevBuf<int> r;
+};
+
+// Yt[i * ldy + k] = component i of the unit eigenvector of eigenvalue lam[k], k < nev: the four kernels above on `st`.
+// W: work plane of the shape of Yt.  Columns nev .. ldy-1 of both planes are neither read nor written.
+inline void trd_twisted_vectors(hipStream_t st, const double* d, const double* e, int n, int nev, const double* lam, double* W, double* Yt,
+                                int64_t ldy, TrdTwistScratch& sc) {
+  const int nb = ceil_div(nev, 64);
+  hipLaunchKernelGGL(trd_twisted_kernel, dim3(nb), dim3(128), 0, st, d, e, n, nev, lam, W, Yt, ldy);
+  if (n > 1) {
+    const int nseg = ceil_div(n, TRD_TW_SEG);
+    double* g = sc.g.ensure((size_t)nseg * nev);
+    int* r = sc.r.ensure((size_t)nseg * nev);
+    double* scale = sc.scale.ensure((size_t)nev);
+    const dim3 stream_grid(nb, ceil_div(nseg, 4));
+    hipLaunchKernelGGL(trd_twist_index_kernel, stream_grid, dim3(256), 0, st, d, n, nev, lam, W, Yt, ldy, g, r);
+    hipLaunchKernelGGL(trd_twist_vector_kernel, dim3(nb), dim3(128), 0, st, e, n, nev, W, Yt, ldy, g, r, nseg, scale);
+    hipLaunchKernelGGL(trd_twist_scale_kernel, stream_grid, dim3(256), 0, st, n, nev, scale, Yt, ldy);
+  }
+  XMCA_HIP(hipGetLastError());
 }
 
 // Row R of the back substitution x_R = (w_R - sum_{l > R} M[R][l] x_l) tau_R and, recursively, the rows below it in the order
@@ -379,6 +509,7 @@ struct TrdBackPlan {
 struct TrdVecWorkspace {
   DevBuf<double> Y[2];        // Yt / Z (n x ld planes)
   DevBuf<double> Wk[2];       // work planes (twisted factorisation; Newton-Schulz)
+  TrdTwistScratch twist;      // segment minima and scales of the twisted-vector kernels
   DevBuf<double> S[2];        // Gram matrix of the vectors
   DevBuf<double> small;       // X of one super-block (512 x ld planes)
   DevBuf<double> band[2];     // S, T, P of the compact-WY precomputation (band layout), re / im
@@ -390,6 +521,7 @@ struct TrdVecWorkspace {
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   GemmWorkspace side_gws;
   bool prepared = false, joined = true;
+  bool forked = false;        // trd_wy_fork has run and trd_wy_prepare has not yet
   int calls = 0;
   // Called once per eigen-decomposition with vectors, BEFORE the reduction is queued.  The second stream is made on the second
   // call - and with every CU of the device claimed at the gate of the persistent kernels: creating a stream (a hardware queue)
@@ -425,17 +557,28 @@ struct TrdVecWorkspace {
   int ns_steps = 0;
 };
 
+// The point of `st` that trd_wy_prepare's work waits for: right behind the reduction.  Whatever the caller queues on `st`
+// between this call and trd_wy_prepare (the Sturm kernel) does not hold the second stream back.
+inline void trd_wy_fork(hipStream_t st, TrdVecWorkspace& vw, const TrdParams& P) {
+  if (vw.prepared && vw.side) XMCA_HIP(hipStreamSynchronize(vw.side));    // (an earlier call left without joining: an exception in between)
+  vw.prepared = false;
+  vw.forked = true;
+  if (P.n - 1 <= 0) return;
+  if (vw.plan.n != P.n) vw.plan.build(st, P.n);
+  if (vw.side != nullptr && !in_surrogate_lanes()) XMCA_HIP(hipEventRecord(vw.ev_fork, st));
+}
+
 // T of every super-block and T V^H from the reflectors of trd_reduce(..., keep_reflectors = true), queued on the workspace's
-// second stream behind everything `st` holds so far; trd_eigenvectors joins it in front of the back-transformation.
+// second stream behind everything `st` held at trd_wy_fork (without one: on `st`); trd_eigenvectors joins it in front of the
+// back-transformation.
 inline void trd_wy_prepare(hipStream_t st, TrdVecWorkspace& vw, GemmWorkspace& gws_main, const TrdParams& P, bool cplx) {
   const int n = P.n;
   const int64_t ldv = P.ld;                                   // reflectors: row j = v_j, zero outside its support j+1 .. n-1
   constexpr int SBK = TRD_SBK;
   const int nref = n - 1;
-  if (vw.prepared && vw.side) XMCA_HIP(hipStreamSynchronize(vw.side));    // (an earlier call left without joining: an exception in between)
-  vw.prepared = false;
+  if (!vw.forked) trd_wy_fork(st, vw, P);
+  vw.forked = false;
   if (nref <= 0) return;
-  if (vw.plan.n != n) vw.plan.build(st, n);
   // Creating a stream costs ~10 ms (measured: hipStreamCreateWithFlags inside the first solve of a process) - thirty solves'
   // worth of what the overlap saves.  The first call of a workspace therefore stays on `st`; from the second call on the
   // workspace belongs to somebody who solves repeatedly, and the second stream exists (count_call).
@@ -445,10 +588,7 @@ inline void trd_wy_prepare(hipStream_t st, TrdVecWorkspace& vw, GemmWorkspace& g
   // of this function would otherwise go back to the pool - and to a kernel on `st` - while the first GEMM still writes it).
   // hipFree synchronises the device; the sizes settle after the first call of a given order.
   PoolScope scope(use_side ? nullptr : current_pool());
-  if (use_side) {
-    XMCA_HIP(hipEventRecord(vw.ev_fork, st));
-    XMCA_HIP(hipStreamWaitEvent(vw.side, vw.ev_fork, 0));
-  }
+  if (use_side) XMCA_HIP(hipStreamWaitEvent(vw.side, vw.ev_fork, 0));
   {
     hipStream_t st_main = st;
     hipStream_t st = use_side ? vw.side : st_main;            // (everything below runs on the second stream when there is one)
@@ -535,8 +675,7 @@ inline bool trd_eigenvectors(hipStream_t st, TrdWorkspace& ws, TrdVecWorkspace& 
   double* Yi = cplx ? vw.Y[1].ensure(plane) : nullptr;
   double* Wr = vw.Wk[0].ensure(plane);
   double* Wi = cplx ? vw.Wk[1].ensure(plane) : nullptr;
-  hipLaunchKernelGGL(trd_twisted_kernel, dim3(ceil_div(n, 64)), dim3(128), 0, st, P.d, P.e, n, n, vw.lam_asc.get(), Wr, Yr, ld);
-  XMCA_HIP(hipGetLastError());
+  trd_twisted_vectors(st, P.d, P.e, n, n, vw.lam_asc.get(), Wr, Yr, ld, vw.twist);
   if (cplx) XMCA_HIP(hipMemsetAsync(Yi, 0, sizeof(double) * plane, st));
   const int nref = n - 1;
   if (nref > 0) {
@@ -643,8 +782,7 @@ inline bool trd_eigenvectors_partial(hipStream_t st, TrdVecWorkspace& vw, GemmWo
   if (cplx) XMCA_HIP(hipMemsetAsync(Yi, 0, sizeof(double) * plane, st));
   if (cplx) XMCA_HIP(hipMemsetAsync(Wi, 0, sizeof(double) * plane, st));
   // column c = eigenvalue n - kp + c of the ascending list
-  hipLaunchKernelGGL(trd_twisted_kernel, dim3(ceil_div(kp, 64)), dim3(128), 0, st, P.d, P.e, n, kp, vw.lam_asc.get() + (n - kp), Wr, Yr, ld);
-  XMCA_HIP(hipGetLastError());
+  trd_twisted_vectors(st, P.d, P.e, n, kp, vw.lam_asc.get() + (n - kp), Wr, Yr, ld, vw.twist);
   const int nref = n - 1;
   if (nref > 0) {
     XMCA_CHECK(vw.prepared, XMCA_ERR_STATE, "trd_eigenvectors_partial: trd_wy_prepare has not run");

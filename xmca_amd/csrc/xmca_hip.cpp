@@ -3833,13 +3833,13 @@ int xmca_tridiag_vectors(xmca_handle* h, const double* d, const double* e, int n
   API_BEGIN(h)
   TrdWorkspace ws;
   DevBuf<double> dd, de, dl, W, Yd;
+  TrdTwistScratch twist;
   const bool finite = tridiag_stage_upload(h, ws, d, e, n, lam, nev, dd, de, dl);
   XMCA_CHECK(finite, XMCA_ERR_NUMERIC, "tridiag_vectors: d, e and lam must be finite");
   const size_t plane = (size_t)n * (size_t)ldy;
   W.ensure(plane);
   XMCA_HIP(hipMemcpyAsync(Yd.ensure(plane), Y, sizeof(double) * plane, hipMemcpyHostToDevice, h->st));
-  hipLaunchKernelGGL(trd_twisted_kernel, dim3(ceil_div(nev, 64)), dim3(128), 0, h->st, dd.get(), de.get(), n, nev, dl.get(), W.get(), Yd.get(), ldy);
-  XMCA_HIP(hipGetLastError());
+  trd_twisted_vectors(h->st, dd.get(), de.get(), n, nev, dl.get(), W.get(), Yd.get(), ldy, twist);
   XMCA_HIP(hipMemcpyAsync(Y, Yd.get(), sizeof(double) * plane, hipMemcpyDeviceToHost, h->st));
   XMCA_HIP(hipStreamSynchronize(h->st));
   API_END(h)
