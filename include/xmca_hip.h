@@ -592,6 +592,39 @@ int xmca_reg_mask(xmca_handle* h, const void* X, int64_t T, int64_t N, int dtype
 int xmca_reg_solve(xmca_handle* h, const double* normal, int shared_normal, const double* rhs, int64_t N, int k, double* coef_out,
                    unsigned char* fitted_out);
 int xmca_reg_residual_tile(int* rows_out, int* cols_out);
+
+/* Time filter: a gap-aware FIR filter along time on the device (an extension; entry points added to ABI 16 - no
+ * existing signature changes).  With L = n_weights = 2 h + 1 weights w (float64, host memory; any finite values, symmetric or not)
+ * the smoother of the T x N field X (NaN = missing) is the correlation S[t][n] = sum_{k < L} w[k] X[t + k - h][n] - w[0] meets the
+ * earliest step - accumulated in float64 whatever `dtype` as one fma chain in ascending k that starts from +0.0.  The output is S,
+ * or X - S with complement != 0, rounded once to `dtype`.
+ *   renormalise == 0    strict: an output entry is NaN exactly when one of the L entries of its window is missing or lies outside
+ *                       the record (so the first and last h rows are NaN).  trim != 0 returns only the T - 2 h rows h .. T - h - 1,
+ *                       with the bits they have without trim; it needs T >= L.  den_min is not looked at.
+ *   renormalise != 0    S = num / den, the same ascending chains of w[k] x and of w[k] over the PRESENT entries of the window, steps
+ *                       outside the record counting as missing.  An output entry is NaN exactly when X[t][n] itself is missing or
+ *                       den < den_min.  The caller forms den_min = min_weight * sum(w) once in float64; it needs sum(w) > 0 (summed
+ *                       in ascending k), 0 < den_min <= sum(w) and trim == 0.
+ *   X, in_location      XMCA_HOST: contiguous host memory (the strides are not looked at);  XMCA_DEVICE: memory of the handle's GPU,
+ *                       element (t, n) at X[t * stride_t + n * stride_n] (strides in elements, >= 0), copied by the kernels of
+ *                       xmca_set_field_strided into a buffer of this call - the caller's memory is only read
+ *   field_out, out_location  (trim ? T - 2 h : T) x N in `dtype`, contiguous: host memory, or (XMCA_DEVICE, as xmca_column_regress)
+ *                       memory of the handle's GPU that the filter kernel writes directly
+ *   XMCA_ERR_INVALID, before anything is launched: n_weights even or outside [1, 1025], a weight that is not finite, T < 1, N < 1,
+ *                       a bad dtype or location, a negative stride, trim with T < L or with renormalise, renormalise with
+ *                       sum(w) <= 0 or den_min outside (0, sum(w)], a device pointer that is none of the handle's GPU.  Not
+ *                       checked: an Inf in X (the caller's).  XMCA_ERR_UNSUPPORTED: the size limits of xmca_column_regress.
+ *                       The call works in buffers of its own: a resident field, the result of a solve, its rotation and a
+ *                       back-projection tail are left as they are.  Stage timers: "time_filter" (and "ingest_strided" for a device
+ *                       field).  One kernel reads X in its own type and writes the result - no mask plane, no widened plane, no
+ *                       floating-point atomic, no scratch memory: a call repeats its bits.
+ *   xmca_time_filter_tile  (no device) output rows and columns of a workgroup's tile of the filter kernel - one lane per column with
+ *                       the accumulators of its rows in registers, the weights in LDS, the rows of the tile and its 2 h halo rows
+ *                       streamed once - and the most weights a call takes. */
+int xmca_time_filter(xmca_handle* h, const void* X, int in_location, int64_t T, int64_t N, int64_t stride_t, int64_t stride_n, int dtype,
+                     const double* weights, int n_weights, int complement, int renormalise, double den_min, int trim, void* field_out,
+                     int out_location);
+int xmca_time_filter_tile(int* rows_out, int* cols_out, int* max_weights_out);
 int xmca_is_complex(xmca_handle* h);
 /* 1 when the singular vectors of `side` from the last xmca_solve are resident in float32: a real float32 field decomposed on
  * its dual side (N > T) keeps `_V` in the input's dtype as the reference does (xmca/array.py:584, the dtype of

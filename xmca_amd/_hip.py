@@ -87,6 +87,9 @@ SIGNATURES = {
     "xmca_reg_mask": (_c_int, [_vp, _vp, _c_i64, _c_i64, _c_int, _vp, _vp, ctypes.POINTER(_c_i64)]),
     "xmca_reg_solve": (_c_int, [_vp, _vp, _c_int, _vp, _c_i64, _c_int, _vp, _vp]),
     "xmca_reg_residual_tile": (_c_int, [_ip, _ip]),
+    "xmca_time_filter": (_c_int, [_vp, _vp, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _vp, _c_int, _c_int, _c_int, _c_dbl, _c_int, _vp,
+                                  _c_int]),
+    "xmca_time_filter_tile": (_c_int, [_ip, _ip, _ip]),
     "xmca_correlate": (_c_int, [_vp, _c_int, _vp, _c_i64, _c_i64, _vp]),
     "xmca_pearson_pvalues": (_c_int, [_vp, _vp, _c_i64, _c_i64, _vp]),
     "xmca_pvalue_log_norm": (_c_int, [_c_i64, _dp]),
@@ -266,6 +269,14 @@ def reg_residual_tile():
     rows, cols = _c_int(0), _c_int(0)
     load_library().xmca_reg_residual_tile(ctypes.byref(rows), ctypes.byref(cols))
     return int(rows.value), int(cols.value)
+
+
+def time_filter_tile():
+    """(rows, columns, most weights): the output rows and columns of a workgroup's tile of the filter kernel of `time_filter` and the
+    longest filter it takes (xmca_time_filter_tile; no device): constants of the build."""
+    rows, cols, most = _c_int(0), _c_int(0), _c_int(0)
+    load_library().xmca_time_filter_tile(ctypes.byref(rows), ctypes.byref(cols), ctypes.byref(most))
+    return int(rows.value), int(cols.value), int(most.value)
 
 
 def _gap_plane(what, X):
@@ -1215,6 +1226,25 @@ class Handle:
             raise ValueError("column_residual: the coefficients must be k x N = %d x %d, got shape %s" % (k, N, C.shape))
         field, f_ptr, where_out = _output(alloc, (T, N), dt)
         self._check(self._lib.xmca_column_residual(self._h, ptr, where_in, T, N, st, sn, code, _ptr(B), k, _ptr(C), f_ptr, where_out))
+        return field
+
+    def time_filter(self, X, weights, complement=False, renormalise=False, den_min=0.0, trim=False, alloc=None):
+        """The FIR filter along time of the T x N float32 / float64 field `X` (a host array or a `DeviceView`; NaN = missing) with the
+        odd number L = 2 h + 1 <= 1025 of float64 `weights` (xmca_time_filter): S[t] = sum_k w[k] x[t + k - h] as one float64 fma
+        chain in ascending k, or x - S with `complement`, in X's dtype.  Strict (NaN where the window holds a missing entry or
+        leaves the record; `trim` returns rows h .. T - h - 1 only), or `renormalise`: S = num / den over the present entries, NaN
+        where x itself is missing or den < den_min.  alloc: as in `maps` - the field is written on the device.  Resident fields and
+        the result of a solve stay as they are."""
+        keep, ptr, where_in, T, N, st, sn, code, dt = self._regress_field("time_filter", X)
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        if w.ndim != 1 or w.size % 2 != 1 or w.size > 1025:
+            raise ValueError("time_filter: the weights must be a vector of odd length, at most 1025, got shape %s" % (w.shape,))
+        L = w.size
+        if trim and T < L:
+            raise ValueError("time_filter: trimmed edges need at least as many time steps (%d) as weights (%d)" % (T, L))
+        field, f_ptr, where_out = _output(alloc, (T - (L - 1) if trim else T, N), dt)
+        self._check(self._lib.xmca_time_filter(self._h, ptr, where_in, T, N, st, sn, code, _ptr(w), L, int(bool(complement)),
+                                               int(bool(renormalise)), float(den_min), int(bool(trim)), f_ptr, where_out))
         return field
 
     def reg_mask(self, X):

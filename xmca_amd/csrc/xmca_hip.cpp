@@ -19,6 +19,7 @@
 #include "lag_reconstruct.h"
 #include "gap_fill.h"
 #include "regress.h"
+#include "time_filter.h"
 
 using namespace xmca;
 
@@ -2078,6 +2079,33 @@ void column_regress_impl(xmca_handle* h, const void* X, bool in_device, int T, i
   XMCA_HIP(hipStreamSynchronize(h->st));
 }
 
+// xmca_time_filter: the field comes from the host or - through the copy kernels of xmca_set_field_strided - from
+// the caller's device memory into a buffer of this call; the one filter kernel writes the caller's device memory, or a buffer
+// that is copied to the host.  Every buffer is this call's own.
+template <typename TI>
+void time_filter_impl(xmca_handle* h, const void* X, bool in_device, int T, int64_t N, int64_t stride_t, int64_t stride_n, const double* weights,
+                      int L, bool complement, bool renormalise, double den_min, bool trim, TI* out, bool out_device) {
+  const size_t total = (size_t)T * N;
+  const size_t total_out = (size_t)(trim ? T - (L - 1) : T) * N;
+  DevBuf<TI> raw, res;
+  DevBuf<double> wd;
+  if (in_device) {
+    h->tm.begin("ingest_strided");
+    ingest_strided<TI>(h->st, static_cast<const TI*>(X), T, N, stride_t, stride_n, raw.ensure(total));
+    XMCA_HIP(hipGetLastError());
+    h->tm.end();
+  } else {
+    XMCA_HIP(hipMemcpyAsync(raw.ensure(total), X, sizeof(TI) * total, hipMemcpyHostToDevice, h->st));
+  }
+  XMCA_HIP(hipMemcpyAsync(wd.ensure((size_t)L), weights, sizeof(double) * (size_t)L, hipMemcpyHostToDevice, h->st));
+  TI* dst = out_device ? out : res.ensure(total_out);
+  h->tm.begin("time_filter");
+  time_filter<TI>(h->st, raw.get(), T, N, wd.get(), L, complement, renormalise, den_min, trim, dst);
+  h->tm.end();
+  if (!out_device) XMCA_HIP(hipMemcpyAsync(out, res.get(), sizeof(TI) * total_out, hipMemcpyDeviceToHost, h->st));
+  XMCA_HIP(hipStreamSynchronize(h->st));
+}
+
 // (tests) xmca_reg_mask: the mask / widen pass alone
 template <typename TI>
 void reg_mask_impl(xmca_handle* h, const TI* X, int64_t total, unsigned char* mask_out, double* wide_out, int64_t* missing_out) {
@@ -2996,6 +3024,47 @@ int xmca_column_residual(xmca_handle* h, const void* X, int in_location, int64_t
   XMCA_CHECK(coef, XMCA_ERR_INVALID, "column_residual: bad arguments");
   column_regress_entry(h, "column_residual", X, in_location, T, N, stride_t, stride_n, dtype, basis, k, coef, field_out, out_location, nullptr,
                        nullptr);
+  API_END(h)
+}
+
+int xmca_time_filter_tile(int* rows_out, int* cols_out, int* max_weights_out) {
+  if (!rows_out || !cols_out || !max_weights_out) return XMCA_ERR_INVALID;
+  *rows_out = TF_ROWS;
+  *cols_out = TF_COLS;
+  *max_weights_out = TF_MAX_WEIGHTS;
+  return XMCA_OK;
+}
+
+int xmca_time_filter(xmca_handle* h, const void* X, int in_location, int64_t T, int64_t N, int64_t stride_t, int64_t stride_n, int dtype,
+                     const double* weights, int n_weights, int complement, int renormalise, double den_min, int trim, void* field_out,
+                     int out_location) {
+  API_BEGIN(h)
+  const char* what = "time_filter";
+  const std::string w(what);
+  XMCA_CHECK(n_weights >= 1 && n_weights <= TF_MAX_WEIGHTS && n_weights % 2 == 1, XMCA_ERR_INVALID,
+             w + ": the number of weights must be odd and lie in [1, 1025]");
+  XMCA_CHECK(T >= 1 && N >= 1, XMCA_ERR_INVALID, w + ": the field must have at least one row and one column");
+  XMCA_CHECK(dtype == XMCA_F32 || dtype == XMCA_F64, XMCA_ERR_INVALID, w + ": dtype must be XMCA_F32 or XMCA_F64");
+  XMCA_CHECK(stride_t >= 0 && stride_n >= 0, XMCA_ERR_INVALID, w + ": strides must not be negative");
+  XMCA_CHECK(X && weights && field_out, XMCA_ERR_INVALID, w + ": bad arguments");
+  XMCA_CHECK(in_location == XMCA_HOST || in_location == XMCA_DEVICE, XMCA_ERR_INVALID, w + ": the location must be XMCA_HOST or XMCA_DEVICE");
+  double sum = 0.0;          // (ascending, as the chain of the denominators: with every entry present den == sum to the bit)
+  for (int k = 0; k < n_weights; ++k) {
+    XMCA_CHECK(std::isfinite(weights[k]), XMCA_ERR_INVALID, w + ": the weights hold a NaN or an Inf");
+    sum += weights[k];
+  }
+  XMCA_CHECK(!trim || T >= n_weights, XMCA_ERR_INVALID, w + ": trimmed edges need at least as many time steps as weights");
+  XMCA_CHECK(!renormalise || !trim, XMCA_ERR_INVALID, w + ": renormalised weights keep the edges, they cannot be trimmed");
+  XMCA_CHECK(!renormalise || (sum > 0.0 && den_min > 0.0 && den_min <= sum), XMCA_ERR_INVALID,
+             w + ": renormalised weights need a positive sum and 0 < den_min <= that sum");
+  XMCA_CHECK(T <= (int64_t)65535 * TF_ROWS && N < ((int64_t)1 << 31) && T * N < ((int64_t)1 << 40), XMCA_ERR_UNSUPPORTED, w + ": field too large");
+  if (in_location == XMCA_DEVICE) check_device_pointer(h, what, X);
+  check_out_location(h, what, out_location, field_out);
+  with_dtype(dtype, [&](auto t) {
+    using TI = decltype(t);
+    time_filter_impl<TI>(h, X, in_location == XMCA_DEVICE, (int)T, N, stride_t, stride_n, weights, n_weights, complement != 0, renormalise != 0,
+                         den_min, trim != 0, static_cast<TI*>(field_out), out_location == XMCA_DEVICE);
+  });
   API_END(h)
 }
 

@@ -1,4 +1,5 @@
-"""`xmca_amd.prepare` - anomalies of a field on the device: seasonal cycle and trend removed.
+"""`xmca_amd.prepare` - a field prepared on the device: seasonal cycle and trend removed (`anomalies`), then
+band-limited along time (`time_filter`).  The workflow: anomalies -> time_filter -> fill_gaps -> MCA.
 
 Every analysis of this package starts from anomalies: the field minus its seasonal cycle, and often minus a linear trend.  The model
 classes remove one mean per grid point and nothing else; `anomalies` regresses every grid point on a small basis of time functions
@@ -6,10 +7,11 @@ classes remove one mean per grid point and nothing else; `anomalies` regresses e
 values of a grid point, so a record with gaps (NaN) can be prepared before `fill_gaps` completes it; the whole step runs on the
 device (xmca_column_regress) and takes a GPU tensor where it lies.
 
-    from xmca_amd.prepare import anomalies, remove, time_basis
+    from xmca_amd.prepare import anomalies, lanczos_weights, remove, time_basis, time_filter
     from xmca_amd.gaps import fill_gaps
     prep = anomalies(sst, period=12, trend=True)              # monthly means and a trend, fitted over the present values
-    full = fill_gaps(prep['field'], n_modes=6)
+    low = time_filter(prep['field'], lanczos_weights(121, 1 / 60), missing='renormalise')     # gaps stay gaps
+    full = fill_gaps(low, n_modes=6)
     model = MCA(full['field']); model.solve()
     later = remove(sst_new, time_basis(len(sst_new), period=12, trend=True, start=len(sst), span=len(sst)), prep['coefficients'])
 
@@ -22,6 +24,7 @@ from .gaps import _is_tensor
 
 MAX_COLUMNS = 16          # most basis columns (csrc/regress.h REG_K)
 PIVOT_MIN = 1e-8          # the definiteness criterion (csrc/regress.h REG_PIVOT_MIN)
+MAX_WEIGHTS = 1025        # most weights of a time filter (csrc/time_filter.h TF_MAX_WEIGHTS)
 
 
 def _int(what, name, v, least):
@@ -212,3 +215,125 @@ def remove(X, basis, coefficients, handle=None):
     C = np.ascontiguousarray(C.reshape(B.shape[1], -1), dtype=np.float64)
     res = h.column_residual(field, B, C, alloc=_tensor_alloc(h.device) if tensor else None)
     return res.reshape(shape)
+
+
+def _lowpass(L, fc):
+    h = (L - 1) // 2
+    j = np.arange(-h, h + 1, dtype=np.float64)
+    w = np.empty(L, dtype=np.float64)
+    nz = j != 0.0
+    a = np.pi * j[nz] / (h + 1)
+    w[nz] = np.sin(2.0 * np.pi * fc * j[nz]) / (np.pi * j[nz]) * (np.sin(a) / a)
+    w[h] = 2.0 * fc
+    w = 0.5 * (w + w[::-1])          # (the formula is even in j: keep the array so to the bit)
+    return w / w.sum()
+
+
+def lanczos_weights(n_weights, cutoff):
+    """The float64 (n_weights,) weights of a Lanczos filter (Duchon 1979) for `time_filter`.
+
+    n_weights    odd, L = 2 h + 1, 1 <= L <= 1025
+    cutoff       a scalar f_c in cycles per time step, 0 < f_c < 0.5: the low-pass weights - with j = k - h,
+                 w_j ~ sin(2 pi f_c j) / (pi j) * sin(pi j / (h + 1)) / (pi j / (h + 1)), w_0 ~ 2 f_c - normalised to sum to 1
+                 (L = 1: [1.0]);  a pair (f_lo, f_hi), 0 < f_lo < f_hi < 0.5: the band-pass weights low(f_hi) - low(f_lo), their
+                 sum brought to 0 at rounding level
+
+    `time_filter(X, w, complement=True)` is the high-pass of low-pass weights w.  Anything else is a ValueError."""
+    what = "lanczos_weights"
+    L = _int(what, "n_weights", n_weights, 1)
+    if L % 2 != 1 or L > MAX_WEIGHTS:
+        raise ValueError("%s: n_weights must be odd and at most %d, got %d" % (what, MAX_WEIGHTS, L))
+
+    def freq(v):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0.0 < float(v) < 0.5:
+            raise ValueError("%s: a cutoff must be a number in (0, 0.5) cycles per time step, got %r" % (what, v))
+        return float(v)
+    if isinstance(cutoff, (tuple, list, np.ndarray)):
+        if len(np.shape(cutoff)) != 1 or len(cutoff) != 2:
+            raise ValueError("%s: cutoff must be a frequency or a pair (f_lo, f_hi), got %r" % (what, cutoff))
+        lo, hi = freq(cutoff[0]), freq(cutoff[1])
+        if not lo < hi:
+            raise ValueError("%s: a band needs f_lo < f_hi, got %r" % (what, cutoff))
+        w = _lowpass(L, hi) - _lowpass(L, lo)
+        return w - w.sum() / L if L > 1 else w          # (the difference of two unit sums, brought to zero at rounding level)
+    return _lowpass(L, freq(cutoff))
+
+
+def _weight_sum(w):
+    """sum(w) in ascending order, in float64: the chain the device runs for the denominator of a full window"""
+    s = np.float64(0.0)
+    for v in w:
+        s = s + v
+    return float(s)
+
+
+def _check_weights(what, weights):
+    w = np.asarray(weights)
+    if w.dtype.kind not in 'fiu' or w.ndim != 1:
+        raise ValueError("%s: the weights must be a real vector, got %s of shape %s" % (what, w.dtype, w.shape))
+    if w.size % 2 != 1 or w.size > MAX_WEIGHTS:
+        raise ValueError("%s: the number of weights must be odd and at most %d, got %d" % (what, MAX_WEIGHTS, w.size))
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    if not np.isfinite(w).all():
+        raise ValueError("%s: the weights hold a NaN or an Inf" % what)
+    return w
+
+
+def time_filter(X, weights, complement=False, missing='nan', min_weight=0.5, edges='nan', handle=None):
+    """`X` filtered along time by the FIR weights `weights`, grid point by grid point, on the device.
+
+    X            as in `anomalies`: time first and any spatial shape, real float32 or float64, NaN marking a missing value (an Inf
+                 is refused): a numpy array, or a `torch.Tensor` on the handle's GPU in any layout
+    weights      a real finite vector of odd length L = 2 h + 1 <= 1025, symmetric or not, e.g. `lanczos_weights(121, 1 / 60)`
+    complement   False: the smoother S;  True: X - S, the high-pass of low-pass weights
+    missing      'nan' (strict): an output entry is NaN exactly when one of the L entries of its window is missing or lies outside
+                 the record;  'renormalise': S = num / den, the sums of w_k x and of w_k over the present entries of the window
+                 only (steps outside the record count as missing) - an output entry is NaN exactly when X[t, n] itself is missing
+                 or den < min_weight * sum(w).  It needs sum(w) > 0 (so no band-pass weights), 0 < min_weight <= 1 and edges='nan'
+    edges        'nan': the shape of X, the first and last h steps NaN under missing='nan';  'trim' (missing='nan' only, T >= L):
+                 the T - 2 h steps h .. T - h - 1 whose window lies inside the record, with the bits they have under 'nan' - `MCA`
+                 drops every grid point with a NaN
+    handle       a `_hip.Handle` (default: the one of the device); its resident fields and results are left as they are
+
+    The smoother is a correlation, S[t, n] = sum_k weights[k] X[t + k - h, n]: weights[0] multiplies the earliest step.  It is one
+    float64 fma chain in ascending k that starts from +0.0, whatever the dtype of X, and the output is rounded once to that dtype.
+    The threshold min_weight * sum(w) is formed once on the host in float64 (sum(w) in ascending order).
+
+    Returns the field alone: dtype and kind of X (a GPU tensor, written there by the device, when X was one).  Every argument error
+    is a ValueError raised before the library's device code is reached."""
+    what = "time_filter"
+    w = _check_weights(what, weights)
+    if not isinstance(complement, (bool, np.bool_)):
+        raise ValueError("%s: complement must be True or False, got %r" % (what, complement))
+    if not isinstance(missing, str) or missing not in ('nan', 'renormalise'):
+        raise ValueError("%s: missing must be 'nan' or 'renormalise', got %r" % (what, missing))
+    if not isinstance(edges, str) or edges not in ('nan', 'trim'):
+        raise ValueError("%s: edges must be 'nan' or 'trim', got %r" % (what, edges))
+    renorm, trim = missing == 'renormalise', edges == 'trim'
+    den_min = 0.0
+    if renorm:
+        if trim:
+            raise ValueError("%s: missing='renormalise' keeps the edges; it needs edges='nan'" % what)
+        if isinstance(min_weight, (bool, np.bool_)) or not isinstance(min_weight, (int, float, np.integer, np.floating)) \
+                or not 0.0 < float(min_weight) <= 1.0:
+            raise ValueError("%s: min_weight must lie in (0, 1], got %r" % (what, min_weight))
+        total = _weight_sum(w)
+        if not total > 0.0:
+            raise ValueError("%s: missing='renormalise' divides by the sum of the present weights; it needs sum(weights) > 0, got %g "
+                             "(band-pass weights sum to 0)" % (what, total))
+        den_min = float(np.float64(min_weight) * np.float64(total))
+        if not den_min > 0.0:
+            raise ValueError("%s: min_weight * sum(weights) underflows to zero" % what)
+    if _is_tensor(X):
+        T = int(X.shape[0]) if X.dim() >= 1 else 0
+    else:
+        T = int(np.shape(X)[0]) if np.ndim(X) >= 1 else 0
+    if T < 1:
+        raise ValueError("%s: the field needs time first and at least one spatial dimension" % what)
+    if trim and T < w.size:
+        raise ValueError("%s: edges='trim' needs at least as many time steps as weights, got %d steps and %d weights" % (what, T, w.size))
+    field, shape, tensor = _check_field(what, X, handle)
+    h = handle if handle is not None else _hip.default_handle()
+    res = h.time_filter(field, w, complement=bool(complement), renormalise=renorm, den_min=den_min, trim=trim,
+                        alloc=_tensor_alloc(h.device) if tensor else None)
+    return res.reshape((shape[0] - (w.size - 1) if trim else shape[0],) + tuple(shape[1:]))

@@ -381,6 +381,24 @@ def anomalies(da, period=None, harmonics=None, trend=False, basis=None, handle=N
     return out
 
 
+def time_filter(da, weights, complement=False, missing='nan', min_weight=0.5, edges='nan', handle=None):
+    """`xmca_amd.prepare.time_filter` of a DataArray whose first dimension is time: a DataArray over the dims, coordinates and attrs
+    of `da`; with edges='trim' everything along time is sliced [h : T - h], h = (len(weights) - 1) // 2."""
+    xr = _xr()
+    if not isinstance(da, xr.DataArray):
+        raise TypeError("time_filter: the field is not an `xarray.DataArray`")
+    out = _prepare.time_filter(da.values, weights, complement=complement, missing=missing, min_weight=min_weight, edges=edges, handle=handle)
+    coords = dict(da.coords)
+    if edges == 'trim':
+        time, h = da.dims[0], (len(weights) - 1) // 2
+        for name, c in coords.items():
+            dims = tuple(getattr(c, 'dims', ()))
+            if time in dims:
+                cut = tuple(slice(h, da.shape[0] - h) if d == time else slice(None) for d in dims)
+                coords[name] = xr.DataArray(np.asarray(c.values)[cut], dims=dims, name=name, attrs=dict(getattr(c, 'attrs', {})))
+    return xr.DataArray(out, dims=da.dims, coords=coords, attrs=dict(da.attrs), name=da.name)
+
+
 class _NumpyView:
     """Delegates attribute access to an xMCA but resolves the public getters to the numpy base-class versions."""
 
