@@ -625,6 +625,46 @@ int xmca_time_filter(xmca_handle* h, const void* X, int in_location, int64_t T, 
                      const double* weights, int n_weights, int complement, int renormalise, double den_min, int trim, void* field_out,
                      int out_location);
 int xmca_time_filter_tile(int* rows_out, int* cols_out, int* max_weights_out);
+
+/* Lead-lag maps: regression and correlation of every column of a field with gaps on index series at a list of lags, on the device
+ * (an extension; entry points added to ABI 16 - no existing signature changes).  X is the T x N field (NaN =
+ * missing), Y the T x q plane of the CENTRED index series (float64, host memory, row-major, finite; 1 <= q <= 8), lags n_lags
+ * distinct integers with |lag| <= T - 1 and n_lags * q <= 1024.  For lag l the pairs of column n are (y[s], x[s + l][n]) over the
+ * steps s in [max(0, -l), min(T, T - l)) at which x[s + l][n] is present: a positive lag means the index leads the field.  With c_n
+ * the mean of the present values of column n (one ascending float64 chain; 0 for an empty column) and x' = x - c_n, the sums
+ * n, Sx, Sxx per (lag, column) and Sy, Syy, Sxy per (lag, column, series) are float64 chains in ascending s that start from +0.0,
+ * whatever `dtype`; Cxx = Sxx - Sx^2 / n, Cyy = Syy - Sy^2 / n, Cxy = Sxy - Sx Sy / n.  An entry is live exactly when
+ * n >= min_pairs, Cxx > 2^-40 Sxx and Cyy > 2^-40 Syy; r = Cxy / sqrt(Cxx Cyy) clamped to [-1, 1] and slope = Cxy / Cyy are rounded
+ * once to `dtype`; a dead entry has r, slope and p NaN and dof 0.
+ *   dof_mode            XMCA_DOF_N: dof = n;  XMCA_DOF_BRETHERTON: dof = min(n, floor(n f)), f = 1 where rho <= 0 else
+ *                       (1 - rho) / (1 + rho), rho = rho_x[n] rho_y[j]; rho_x[n] = [sum_P x'_t x'_{t+1} / |P|] / [sum_present x'^2 /
+ *                       n0] over the steps P with x[t] and x[t + 1] present (0 where |P| = 0 or the denominator is not positive;
+ *                       clamped to [-1, 1]) is formed on the device, rho_y (q values in [-1, 1], host) is the caller's
+ *   p                   pearson_two_sided_p(the rounded r, dof / 2 - 1, log_norm[dof]) with a table of xmca_pvalue_log_norm at
+ *                       3 .. T built on the host once per call; NaN where dof < 3
+ *   X, in_location, strides   as xmca_time_filter
+ *   r_out, slope_out    n_lags x N x q in `dtype`;  p_out n_lags x N x q float64;  dof_out n_lags x N x q int;  pairs_out
+ *                       n_lags x N int (every column);  lag1_out N float64, rho_x - required with XMCA_DOF_BRETHERTON, else
+ *                       NULL.  All in host memory, or (out_location == XMCA_DEVICE) all in memory of the handle's GPU that the
+ *                       kernels write directly.
+ *   XMCA_ERR_INVALID, before anything is launched: q outside [1, 8], n_lags < 1, n_lags * q > 1024, a duplicate lag, |lag| >= T,
+ *                       min_pairs < 3, a NaN or an Inf in Y, an unknown dof_mode, XMCA_DOF_BRETHERTON without rho_y or lag1_out
+ *                       or with a rho_y outside [-1, 1], T < 1, N < 1, a bad dtype or location, a negative stride, a missing
+ *                       pointer, a device pointer that is none of the handle's GPU.  Not checked: an Inf in X (the caller's).
+ *                       XMCA_ERR_UNSUPPORTED: T above 1 000 000 (the p-value's range), the size limits of xmca_column_regress.
+ *                       The call works in buffers of its own: a resident field, the result of a solve, its rotation and a
+ *                       back-projection tail are left as they are.  Stage timers: "lead_lag_center", "lead_lag_lag1"
+ *                       (XMCA_DOF_BRETHERTON), "lead_lag_moments", "lead_lag_finish" (and "ingest_strided" for a device field).
+ *                       No mask plane, no widened plane, no floating-point atomic, no scratch memory: a call repeats its bits,
+ *                       and the results of a lag do not depend on the other lags of the call or on their order.
+ *   xmca_lead_lag_tile  (no device) the columns of a workgroup of the moment kernel, the rows of a piece a lane loads together, and
+ *                       lag_group_out[q - 1], q = 1 .. 8: the lags of a workgroup's group with q index series. */
+#define XMCA_DOF_N 0
+#define XMCA_DOF_BRETHERTON 1
+int xmca_lead_lag_maps(xmca_handle* h, const void* X, int in_location, int64_t T, int64_t N, int64_t stride_t, int64_t stride_n, int dtype,
+                       const double* Y, int q, const int* lags, int n_lags, int min_pairs, int dof_mode, const double* rho_y, void* r_out,
+                       void* slope_out, double* p_out, int* dof_out, int* pairs_out, double* lag1_out, int out_location);
+int xmca_lead_lag_tile(int* cols_out, int* rows_out, int* lag_group_out);
 int xmca_is_complex(xmca_handle* h);
 /* 1 when the singular vectors of `side` from the last xmca_solve are resident in float32: a real float32 field decomposed on
  * its dual side (N > T) keeps `_V` in the input's dtype as the reference does (xmca/array.py:584, the dtype of

@@ -90,6 +90,9 @@ SIGNATURES = {
     "xmca_time_filter": (_c_int, [_vp, _vp, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _vp, _c_int, _c_int, _c_int, _c_dbl, _c_int, _vp,
                                   _c_int]),
     "xmca_time_filter_tile": (_c_int, [_ip, _ip, _ip]),
+    "xmca_lead_lag_maps": (_c_int, [_vp, _vp, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _vp, _c_int, _vp, _c_int, _c_int, _c_int, _vp, _vp,
+                                    _vp, _vp, _vp, _vp, _vp, _c_int]),
+    "xmca_lead_lag_tile": (_c_int, [_ip, _ip, _ip]),
     "xmca_correlate": (_c_int, [_vp, _c_int, _vp, _c_i64, _c_i64, _vp]),
     "xmca_pearson_pvalues": (_c_int, [_vp, _vp, _c_i64, _c_i64, _vp]),
     "xmca_pvalue_log_norm": (_c_int, [_c_i64, _dp]),
@@ -166,6 +169,7 @@ def library_path():
 MAP_EOF, MAP_AMPLITUDE, MAP_PHASE = 0, 1, 2          # `kind` of xmca_get_maps
 SCALE_NONE, SCALE_MAX, SCALE_STD = 0, 1, 2           # ... and its `scaling`
 INGEST_ROWS, INGEST_TRANSPOSE, INGEST_GATHER = 0, 1, 2   # regimes of xmca_set_field_strided (xmca_ingest_regime)
+DOF_N, DOF_BRETHERTON = 0, 1                         # `dof_mode` of xmca_lead_lag_maps
 PVALUE_MAX_OBS = 1000000    # largest n_obs of xmca_pearson_pvalues / xmca_correlation_maps (csrc/kernels.h)
 ABI_VERSION = 16        # bumped whenever a signature of include/xmca_hip.h changes; checked against xmca_abi_version()
 
@@ -277,6 +281,15 @@ def time_filter_tile():
     rows, cols, most = _c_int(0), _c_int(0), _c_int(0)
     load_library().xmca_time_filter_tile(ctypes.byref(rows), ctypes.byref(cols), ctypes.byref(most))
     return int(rows.value), int(cols.value), int(most.value)
+
+
+def lead_lag_tile():
+    """(columns, rows, groups): the columns of a workgroup of the moment kernel of `lead_lag_maps`, the rows of a piece a lane loads
+    together, and groups[q - 1], q = 1 .. 8, the lags of a workgroup's group with q index series (xmca_lead_lag_tile; no device)."""
+    cols, rows = _c_int(0), _c_int(0)
+    groups = (_c_int * 8)()
+    load_library().xmca_lead_lag_tile(ctypes.byref(cols), ctypes.byref(rows), groups)
+    return int(cols.value), int(rows.value), tuple(int(g) for g in groups)
 
 
 def _gap_plane(what, X):
@@ -1246,6 +1259,38 @@ class Handle:
         self._check(self._lib.xmca_time_filter(self._h, ptr, where_in, T, N, st, sn, code, _ptr(w), L, int(bool(complement)),
                                                int(bool(renormalise)), float(den_min), int(bool(trim)), f_ptr, where_out))
         return field
+
+    def lead_lag_maps(self, X, Yc, lags, min_pairs, rho_y=None, alloc=None):
+        """The lagged regression maps of the T x N float32 / float64 field `X` (a host array or a `DeviceView`; NaN = missing) on the
+        q <= 8 columns of the CENTRED, finite index plane `Yc` (T x q) at the distinct `lags` (xmca_lead_lag_maps):
+        (r, slope, p, dof, pairs, lag1) - r, slope (L, N, q) in X's dtype, p (L, N, q) float64, dof (L, N, q) int32, pairs (L, N)
+        int32, and lag1 (N,) float64 or None.  rho_y: None - dof = pairs; the q lag-1 autocorrelations of the index - the
+        effective sample size of Bretherton et al. (1999).  alloc: as in `maps` - every output is written on the device.
+        Resident fields and the result of a solve stay as they are."""
+        keep, ptr, where_in, T, N, st, sn, code, dt = self._regress_field("lead_lag_maps", X)
+        Y = np.ascontiguousarray(Yc, dtype=np.float64)
+        if Y.ndim != 2 or Y.shape[0] != T or not 1 <= Y.shape[1] <= 8:
+            raise ValueError("lead_lag_maps: the index must be T x q with T = %d and 1 <= q <= 8, got shape %s" % (T, Y.shape))
+        q = Y.shape[1]
+        lg = np.ascontiguousarray(lags, dtype=np.int32)
+        if lg.ndim != 1 or lg.size < 1 or lg.size * q > 1024:
+            raise ValueError("lead_lag_maps: it needs a lag, and at most 1024 lags x index series, got %d x %d" % (lg.size, q))
+        L = lg.size
+        ry = None if rho_y is None else np.ascontiguousarray(rho_y, dtype=np.float64)
+        if ry is not None and ry.shape != (q,):
+            raise ValueError("lead_lag_maps: rho_y must hold one value per index series (%d), got shape %s" % (q, ry.shape))
+        r, r_ptr, where_out = _output(alloc, (L, N, q), dt)
+        slope, s_ptr, _ = _output(alloc, (L, N, q), dt)
+        p, p_ptr, _ = _output(alloc, (L, N, q), np.float64)
+        dof, d_ptr, _ = _output(alloc, (L, N, q), np.int32)
+        pairs, n_ptr, _ = _output(alloc, (L, N), np.int32)
+        lag1, l_ptr = None, None
+        if ry is not None:
+            lag1, l_ptr, _ = _output(alloc, (N,), np.float64)
+        self._check(self._lib.xmca_lead_lag_maps(self._h, ptr, where_in, T, N, st, sn, code, _ptr(Y), q, _ptr(lg), L, int(min_pairs),
+                                                 DOF_N if ry is None else DOF_BRETHERTON, _ptr(ry), r_ptr, s_ptr, p_ptr, d_ptr, n_ptr,
+                                                 l_ptr, where_out))
+        return r, slope, p, dof, pairs, lag1
 
     def reg_mask(self, X):
         """(tests) The mask / widen pass of `column_regress` on a host field (xmca_reg_mask): (mask, wide, missing) - the T x N mask

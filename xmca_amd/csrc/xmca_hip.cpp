@@ -20,6 +20,7 @@
 #include "gap_fill.h"
 #include "regress.h"
 #include "time_filter.h"
+#include "lead_lag.h"
 
 using namespace xmca;
 
@@ -2106,6 +2107,69 @@ void time_filter_impl(xmca_handle* h, const void* X, bool in_device, int T, int6
   XMCA_HIP(hipStreamSynchronize(h->st));
 }
 
+// xmca_lead_lag_maps: the field comes from the host or - through the copy kernels of xmca_set_field_strided - from
+// the caller's device memory into a buffer of this call; the centring pass, the lag-1 pass (Bretherton), the moment kernel into a
+// moments plane of this call, the finish into the caller's device memory or into buffers that are copied to the host.  Every
+// buffer is this call's own.
+template <typename TI>
+void lead_lag_impl(xmca_handle* h, const void* X, bool in_device, int T, int64_t N, int64_t stride_t, int64_t stride_n, const double* Y, int q,
+                   const int* lags, int n_lags, int min_pairs, bool bretherton, const double* rho_y, TI* r_out, TI* slope_out, double* p_out,
+                   int* dof_out, int* pairs_out, double* lag1_out, bool out_device) {
+  const size_t total = (size_t)T * N;
+  const size_t planes = (size_t)n_lags * N, entries = planes * q;
+  DevBuf<TI> raw, rd, sd;
+  DevBuf<double> cn, Yd, rx, ry, mom, ln, pd;
+  DevBuf<int> n0, lg, dd, prs;
+  if (in_device) {
+    h->tm.begin("ingest_strided");
+    ingest_strided<TI>(h->st, static_cast<const TI*>(X), T, N, stride_t, stride_n, raw.ensure(total));
+    XMCA_HIP(hipGetLastError());
+    h->tm.end();
+  } else {
+    XMCA_HIP(hipMemcpyAsync(raw.ensure(total), X, sizeof(TI) * total, hipMemcpyHostToDevice, h->st));
+  }
+  std::vector<double> table((size_t)T + 1, 0.0);          // log_norm[k] at 3 <= k <= T: a dof never exceeds a pair count, and that not T
+  for (int k = 3; k <= T; ++k) table[(size_t)k] = pvalue_log_norm(k);
+  XMCA_HIP(hipMemcpyAsync(Yd.ensure((size_t)T * q), Y, sizeof(double) * (size_t)T * q, hipMemcpyHostToDevice, h->st));
+  XMCA_HIP(hipMemcpyAsync(lg.ensure((size_t)n_lags), lags, sizeof(int) * (size_t)n_lags, hipMemcpyHostToDevice, h->st));
+  XMCA_HIP(hipMemcpyAsync(ln.ensure(table.size()), table.data(), sizeof(double) * table.size(), hipMemcpyHostToDevice, h->st));
+  if (bretherton) XMCA_HIP(hipMemcpyAsync(ry.ensure((size_t)q), rho_y, sizeof(double) * (size_t)q, hipMemcpyHostToDevice, h->st));
+  const dim3 cols((unsigned)ceil_div(N, LL_COLS)), block(LL_COLS);
+  h->tm.begin("lead_lag_center");
+  hipLaunchKernelGGL((lead_lag_center_kernel<TI>), cols, block, 0, h->st, (const TI*)raw.get(), T, N, cn.ensure((size_t)N), n0.ensure((size_t)N));
+  XMCA_HIP(hipGetLastError());
+  h->tm.end();
+  double* rho_x = nullptr;
+  if (bretherton) {
+    rho_x = out_device ? lag1_out : rx.ensure((size_t)N);
+    h->tm.begin("lead_lag_lag1");
+    hipLaunchKernelGGL((lag1_gappy_kernel<TI>), cols, block, 0, h->st, (const TI*)raw.get(), T, N, (const double*)cn.get(), (const int*)n0.get(),
+                       rho_x);
+    XMCA_HIP(hipGetLastError());
+    h->tm.end();
+  }
+  int* pairs = out_device ? pairs_out : prs.ensure(planes);
+  h->tm.begin("lead_lag_moments");
+  lead_lag_moments<TI>(h->st, raw.get(), T, N, cn.get(), Yd.get(), q, lg.get(), n_lags, pairs, mom.ensure(planes * (size_t)ll_moments(q)));
+  h->tm.end();
+  h->tm.begin("lead_lag_finish");
+  hipLaunchKernelGGL((lead_lag_finish_kernel<TI>), ew_grid((int64_t)entries), dim3(EW_BLOCK), 0, h->st, (const int*)pairs, (const double*)mom.get(),
+                     N, q, n_lags, min_pairs, (const double*)rho_x, (const double*)(bretherton ? ry.get() : nullptr), (const double*)ln.get(),
+                     out_device ? r_out : rd.ensure(entries), out_device ? slope_out : sd.ensure(entries),
+                     out_device ? p_out : pd.ensure(entries), out_device ? dof_out : dd.ensure(entries));
+  XMCA_HIP(hipGetLastError());
+  h->tm.end();
+  if (!out_device) {
+    XMCA_HIP(hipMemcpyAsync(r_out, rd.get(), sizeof(TI) * entries, hipMemcpyDeviceToHost, h->st));
+    XMCA_HIP(hipMemcpyAsync(slope_out, sd.get(), sizeof(TI) * entries, hipMemcpyDeviceToHost, h->st));
+    XMCA_HIP(hipMemcpyAsync(p_out, pd.get(), sizeof(double) * entries, hipMemcpyDeviceToHost, h->st));
+    XMCA_HIP(hipMemcpyAsync(dof_out, dd.get(), sizeof(int) * entries, hipMemcpyDeviceToHost, h->st));
+    XMCA_HIP(hipMemcpyAsync(pairs_out, prs.get(), sizeof(int) * planes, hipMemcpyDeviceToHost, h->st));
+    if (bretherton) XMCA_HIP(hipMemcpyAsync(lag1_out, rx.get(), sizeof(double) * (size_t)N, hipMemcpyDeviceToHost, h->st));
+  }
+  XMCA_HIP(hipStreamSynchronize(h->st));
+}
+
 // (tests) xmca_reg_mask: the mask / widen pass alone
 template <typename TI>
 void reg_mask_impl(xmca_handle* h, const TI* X, int64_t total, unsigned char* mask_out, double* wide_out, int64_t* missing_out) {
@@ -3064,6 +3128,59 @@ int xmca_time_filter(xmca_handle* h, const void* X, int in_location, int64_t T, 
     using TI = decltype(t);
     time_filter_impl<TI>(h, X, in_location == XMCA_DEVICE, (int)T, N, stride_t, stride_n, weights, n_weights, complement != 0, renormalise != 0,
                          den_min, trim != 0, static_cast<TI*>(field_out), out_location == XMCA_DEVICE);
+  });
+  API_END(h)
+}
+
+int xmca_lead_lag_tile(int* cols_out, int* rows_out, int* lag_group_out) {
+  if (!cols_out || !rows_out || !lag_group_out) return XMCA_ERR_INVALID;
+  *cols_out = LL_COLS;
+  *rows_out = LL_ROWS;
+  for (int q = 1; q <= LL_MAX_Q; ++q) lag_group_out[q - 1] = ll_group(q);
+  return XMCA_OK;
+}
+
+int xmca_lead_lag_maps(xmca_handle* h, const void* X, int in_location, int64_t T, int64_t N, int64_t stride_t, int64_t stride_n, int dtype,
+                       const double* Y, int q, const int* lags, int n_lags, int min_pairs, int dof_mode, const double* rho_y, void* r_out,
+                       void* slope_out, double* p_out, int* dof_out, int* pairs_out, double* lag1_out, int out_location) {
+  API_BEGIN(h)
+  const char* what = "lead_lag_maps";
+  const std::string w(what);
+  XMCA_CHECK(q >= 1 && q <= LL_MAX_Q, XMCA_ERR_INVALID, w + ": between 1 and 8 index series are supported");
+  XMCA_CHECK(n_lags >= 1 && (int64_t)n_lags * q <= LL_MAX_ENTRIES, XMCA_ERR_INVALID, w + ": it needs a lag, and at most 1024 lags x index series");
+  XMCA_CHECK(T >= 1 && N >= 1, XMCA_ERR_INVALID, w + ": the field must have at least one row and one column");
+  XMCA_CHECK(dtype == XMCA_F32 || dtype == XMCA_F64, XMCA_ERR_INVALID, w + ": dtype must be XMCA_F32 or XMCA_F64");
+  XMCA_CHECK(stride_t >= 0 && stride_n >= 0, XMCA_ERR_INVALID, w + ": strides must not be negative");
+  XMCA_CHECK(min_pairs >= 3, XMCA_ERR_INVALID, w + ": min_pairs must be at least 3");
+  XMCA_CHECK(dof_mode == XMCA_DOF_N || dof_mode == XMCA_DOF_BRETHERTON, XMCA_ERR_INVALID, w + ": dof_mode must be XMCA_DOF_N or XMCA_DOF_BRETHERTON");
+  XMCA_CHECK(X && Y && lags && r_out && slope_out && p_out && dof_out && pairs_out, XMCA_ERR_INVALID, w + ": bad arguments");
+  XMCA_CHECK(in_location == XMCA_HOST || in_location == XMCA_DEVICE, XMCA_ERR_INVALID, w + ": the location must be XMCA_HOST or XMCA_DEVICE");
+  XMCA_CHECK(T <= PVALUE_MAX_OBS, XMCA_ERR_UNSUPPORTED, w + ": T above " + std::to_string(PVALUE_MAX_OBS));
+  for (int g = 0; g < n_lags; ++g) {
+    XMCA_CHECK((int64_t)lags[g] > -T && (int64_t)lags[g] < T, XMCA_ERR_INVALID, w + ": a lag must lie in [-(T - 1), T - 1]");
+    for (int e = 0; e < g; ++e) XMCA_CHECK(lags[e] != lags[g], XMCA_ERR_INVALID, w + ": the lags must be distinct");
+  }
+  for (int64_t i = 0; i < T * q; ++i) XMCA_CHECK(std::isfinite(Y[i]), XMCA_ERR_INVALID, w + ": the index holds a NaN or an Inf");
+  const bool bretherton = dof_mode == XMCA_DOF_BRETHERTON;
+  if (bretherton) {
+    XMCA_CHECK(rho_y && lag1_out, XMCA_ERR_INVALID, w + ": XMCA_DOF_BRETHERTON needs rho_y and lag1_out");
+    for (int j = 0; j < q; ++j) XMCA_CHECK(rho_y[j] >= -1.0 && rho_y[j] <= 1.0, XMCA_ERR_INVALID, w + ": rho_y must lie in [-1, 1]");
+  }
+  XMCA_CHECK(N < ((int64_t)1 << 31) && T * N < ((int64_t)1 << 40) && (int64_t)n_lags * N * ll_moments(q) < ((int64_t)1 << 40), XMCA_ERR_UNSUPPORTED,
+             w + ": field too large");
+  if (in_location == XMCA_DEVICE) check_device_pointer(h, what, X);
+  check_out_location(h, what, out_location, r_out);
+  if (out_location == XMCA_DEVICE) {
+    check_device_pointer(h, what, slope_out);
+    check_device_pointer(h, what, p_out);
+    check_device_pointer(h, what, dof_out);
+    check_device_pointer(h, what, pairs_out);
+    if (bretherton) check_device_pointer(h, what, lag1_out);
+  }
+  with_dtype(dtype, [&](auto t) {
+    using TI = decltype(t);
+    lead_lag_impl<TI>(h, X, in_location == XMCA_DEVICE, (int)T, N, stride_t, stride_n, Y, q, lags, n_lags, min_pairs, bretherton, rho_y,
+                      static_cast<TI*>(r_out), static_cast<TI*>(slope_out), p_out, dof_out, pairs_out, lag1_out, out_location == XMCA_DEVICE);
   });
   API_END(h)
 }

@@ -11,6 +11,7 @@ import os
 import numpy as np
 
 from . import gaps as _gaps
+from . import lagged as _lagged
 from . import prepare as _prepare
 from .array import MCA, secure_str
 
@@ -397,6 +398,37 @@ def time_filter(da, weights, complement=False, missing='nan', min_weight=0.5, ed
                 cut = tuple(slice(h, da.shape[0] - h) if d == time else slice(None) for d in dims)
                 coords[name] = xr.DataArray(np.asarray(c.values)[cut], dims=dims, name=name, attrs=dict(getattr(c, 'attrs', {})))
     return xr.DataArray(out, dims=da.dims, coords=coords, attrs=dict(da.attrs), name=da.name)
+
+
+def lead_lag_maps(da, index, lags, min_pairs=8, dof='n', handle=None):
+    """`xmca_amd.lagged.lead_lag_maps` of a DataArray whose first dimension is time: the same dict as DataArrays - 'r', 'slope', 'p'
+    and 'dof' over ('lag',) + the spatial dims + ('index',), 'pairs' over ('lag',) + the spatial dims, 'lag1' over the spatial dims,
+    'lags' over ('lag',) - with `lags` as the 'lag' coordinate and those coordinates of `da` that lie along the spatial dims.
+    `index` may be a DataArray over the time dim (and one more dim for several series)."""
+    xr = _xr()
+    if not isinstance(da, xr.DataArray):
+        raise TypeError("lead_lag_maps: the field is not an `xarray.DataArray`")
+    if isinstance(index, xr.DataArray):
+        index = index.values
+    out = _lagged.lead_lag_maps(da.values, index, lags, min_pairs=min_pairs, dof=dof, handle=handle)
+    spatial = tuple(da.dims[1:])
+    q = out['r'].shape[-1]
+
+    def along(dims):
+        coords = {name: c for name, c in dict(da.coords).items() if getattr(c, 'dims', ()) and set(c.dims) <= set(spatial)}
+        if 'lag' in dims:
+            coords['lag'] = out['lags'].copy()
+        if 'index' in dims:
+            coords['index'] = np.arange(q)
+        return coords
+    full = ('lag',) + spatial + ('index',)
+    for key in ('r', 'slope', 'p', 'dof'):
+        out[key] = xr.DataArray(out[key], dims=full, coords=along(full), name=key)
+    out['pairs'] = xr.DataArray(out['pairs'], dims=('lag',) + spatial, coords=along(('lag',) + spatial), name='pairs')
+    if 'lag1' in out:
+        out['lag1'] = xr.DataArray(out['lag1'], dims=spatial, coords=along(spatial), name='lag1')
+    out['lags'] = xr.DataArray(out['lags'], dims=('lag',), coords={'lag': out['lags'].copy()}, name='lags')
+    return out
 
 
 class _NumpyView:
