@@ -665,6 +665,54 @@ int xmca_lead_lag_maps(xmca_handle* h, const void* X, int in_location, int64_t T
                        const double* Y, int q, const int* lags, int n_lags, int min_pairs, int dof_mode, const double* rho_y, void* r_out,
                        void* slope_out, double* p_out, int* dof_out, int* pairs_out, double* lag1_out, int out_location);
 int xmca_lead_lag_tile(int* cols_out, int* rows_out, int* lag_group_out);
+
+/* Spectral maps: Welch power spectra of every column of a field with gaps, and its cross-spectrum, coherence, phase and gain against
+ * index series, on the device (an extension; entry points added to ABI 16 - no existing signature changes).  X is the
+ * T x N field (NaN = missing), Y the T x q plane of the CENTRED index series (float64, host memory, row-major, finite; 0 <= q <= 4;
+ * NULL with q = 0), L = nperseg in [8, 4096], L <= T, step in [ceil(L / 4), L], weights L finite float64 values with a positive sum of
+ * squares, bins n_bins distinct integers in [0, L / 2].  Segment m covers the rows m step .. m step + L - 1, m < K = (T - L) / step + 1;
+ * it is present for column n exactly when its L entries are, and K_n counts the present ones.  With c_n the mean of the present
+ * values of column n (one ascending float64 chain; 0 for an empty column and with XMCA_DETREND_NONE) and x' = x - c_n, the segment
+ * DFT A_k = sum_j (w_j x'_j) (cos t - i sin t), t = 2 pi ((k j) mod L) / L, is one float64 fma chain per part in ascending j from
+ * +0.0, whatever `dtype`, with (cos t, -sin t) from a table of L entries built on the host in extended precision and indexed by
+ * exact integer arithmetic; Z_k = A_k - mu W_k, mu = (sum_j x'_j) / L and W the DFT of the weights (XMCA_DETREND_MEAN; mu = 0 with
+ * XMCA_DETREND_NONE); the energy of the segment e = sum_j (w_j x'_j)^2 - mu (2 sum_j w_j^2 x'_j - mu sum w^2).  The index goes
+ * through the same code and gives Y and e_y per segment.  Over the present segments of the column in ascending m:
+ * Sxx_k = sum |Z|^2, R = sum e, and per series Syy_k = sum |Y|^2, C_k = sum conj(Y) Z, Ry = sum e_y.  With side_k = 1 at k = 0 and at
+ * k = L / 2 of an even L, else 2, and scale_k = side_k / (fs sum w^2 K_n):
+ *   power_out           n_bins x N in `dtype`: scale Sxx;  segments_out N int: K_n, every column
+ *   index_power_out, cospectrum_out, quadrature_out   n_bins x N x q in `dtype`: scale Syy, scale Re C, scale Im C
+ *   coherence_out, phase_out, gain_out                n_bins x N x q in `dtype`: |C|^2 / (Sxx Syy) clamped to [0, 1], atan2(Im C, Re C)
+ *                       (the sign of scipy.signal.csd(index, x): negative where the index leads), |C| / Syy
+ *   p_out               n_bins x N x q float64: (1 - coherence)^(Ke - 1) = exp((Ke[K_n] - 1) log1p(-coherence)) from the rounded
+ *                       coherence, 0 where that is 1; Ke[K] = K / (1 + 2 sum_{j >= 1, j step < L, j < K} (1 - j / K) rho_j^2),
+ *                       rho_j = sum_i w_i w_{i + j step} / sum w^2 (Welch 1967), a host table at 0 .. K built once per call; the
+ *                       present segments of a gappy column count as contiguous
+ *                       A column with K_n < min_segments is NaN in every map.  Coherence, phase, gain and p are NaN as well where
+ *                       K_n < 2 or the bin carries no power: unless Sxx > 2^-40 R and Syy > 2^-40 Ry (a definition).
+ *                       The q-maps are NULL with q = 0.  All in host memory, or (out_location == XMCA_DEVICE) all in memory of
+ *                       the handle's GPU that the kernels write directly.
+ *   X, in_location, strides   as xmca_time_filter
+ *   XMCA_ERR_INVALID, before anything is launched: q outside [0, 4], nperseg outside [8, 4096] or above T, step outside
+ *                       [ceil(L / 4), L], an unknown detrend, n_bins outside [1, L / 2 + 1], a bin outside [0, L / 2], a duplicate
+ *                       bin, a NaN or an Inf in the weights or a sum of squares that is not positive, fs not positive and finite,
+ *                       min_segments < 1, a NaN or an Inf in Y, T < 1, N < 1, a bad dtype or location, a negative stride, a missing
+ *                       pointer, a device pointer that is none of the handle's GPU.  Not checked: an Inf in X (the caller's).
+ *                       XMCA_ERR_UNSUPPORTED: the size limits of xmca_column_regress.
+ *                       The call works in buffers of its own: a resident field, the result of a solve, its rotation and a
+ *                       back-projection tail are left as they are.  Stage timers: "spectral_center" (XMCA_DETREND_MEAN),
+ *                       "spectral_index" (q > 0), "spectral_segments", "spectral_finish" (and "ingest_strided" for a device field).
+ *                       No mask plane, no widened plane, no atomic, no scratch memory: a call repeats its bits, and the maps of
+ *                       a bin do not depend on the other bins of the call or on their order.
+ *   xmca_spectral_tile  (no device) the columns of a workgroup of the segment kernel, the rows of a piece a lane loads together, and
+ *                       bin_group_out[q], q = 0 .. 4: the bins of a workgroup's group with q index series. */
+#define XMCA_DETREND_NONE 0
+#define XMCA_DETREND_MEAN 1
+int xmca_spectral_maps(xmca_handle* h, const void* X, int in_location, int64_t T, int64_t N, int64_t stride_t, int64_t stride_n, int dtype,
+                       const double* Y, int q, int nperseg, int step, const double* weights, int detrend, const int* bins, int n_bins, double fs,
+                       int min_segments, void* power_out, void* index_power_out, void* cospectrum_out, void* quadrature_out, void* coherence_out,
+                       void* phase_out, void* gain_out, double* p_out, int* segments_out, int out_location);
+int xmca_spectral_tile(int* cols_out, int* rows_out, int* bin_group_out);
 int xmca_is_complex(xmca_handle* h);
 /* 1 when the singular vectors of `side` from the last xmca_solve are resident in float32: a real float32 field decomposed on
  * its dual side (N > T) keeps `_V` in the input's dtype as the reference does (xmca/array.py:584, the dtype of

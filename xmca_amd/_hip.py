@@ -93,6 +93,9 @@ SIGNATURES = {
     "xmca_lead_lag_maps": (_c_int, [_vp, _vp, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _vp, _c_int, _vp, _c_int, _c_int, _c_int, _vp, _vp,
                                     _vp, _vp, _vp, _vp, _vp, _c_int]),
     "xmca_lead_lag_tile": (_c_int, [_ip, _ip, _ip]),
+    "xmca_spectral_maps": (_c_int, [_vp, _vp, _c_int, _c_i64, _c_i64, _c_i64, _c_i64, _c_int, _vp, _c_int, _c_int, _c_int, _vp, _c_int, _vp, _c_int,
+                                    _c_dbl, _c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_int]),
+    "xmca_spectral_tile": (_c_int, [_ip, _ip, _ip]),
     "xmca_correlate": (_c_int, [_vp, _c_int, _vp, _c_i64, _c_i64, _vp]),
     "xmca_pearson_pvalues": (_c_int, [_vp, _vp, _c_i64, _c_i64, _vp]),
     "xmca_pvalue_log_norm": (_c_int, [_c_i64, _dp]),
@@ -170,6 +173,7 @@ MAP_EOF, MAP_AMPLITUDE, MAP_PHASE = 0, 1, 2          # `kind` of xmca_get_maps
 SCALE_NONE, SCALE_MAX, SCALE_STD = 0, 1, 2           # ... and its `scaling`
 INGEST_ROWS, INGEST_TRANSPOSE, INGEST_GATHER = 0, 1, 2   # regimes of xmca_set_field_strided (xmca_ingest_regime)
 DOF_N, DOF_BRETHERTON = 0, 1                         # `dof_mode` of xmca_lead_lag_maps
+DETREND_NONE, DETREND_MEAN = 0, 1                    # `detrend` of xmca_spectral_maps
 PVALUE_MAX_OBS = 1000000    # largest n_obs of xmca_pearson_pvalues / xmca_correlation_maps (csrc/kernels.h)
 ABI_VERSION = 16        # bumped whenever a signature of include/xmca_hip.h changes; checked against xmca_abi_version()
 
@@ -289,6 +293,15 @@ def lead_lag_tile():
     cols, rows = _c_int(0), _c_int(0)
     groups = (_c_int * 8)()
     load_library().xmca_lead_lag_tile(ctypes.byref(cols), ctypes.byref(rows), groups)
+    return int(cols.value), int(rows.value), tuple(int(g) for g in groups)
+
+
+def spectral_tile():
+    """(columns, rows, groups): the columns of a workgroup of the segment kernel of `spectral_maps`, the rows of a piece a lane loads
+    together, and groups[q], q = 0 .. 4, the bins of a workgroup's group with q index series (xmca_spectral_tile; no device)."""
+    cols, rows = _c_int(0), _c_int(0)
+    groups = (_c_int * 5)()
+    load_library().xmca_spectral_tile(ctypes.byref(cols), ctypes.byref(rows), groups)
     return int(cols.value), int(rows.value), tuple(int(g) for g in groups)
 
 
@@ -1291,6 +1304,39 @@ class Handle:
                                                  DOF_N if ry is None else DOF_BRETHERTON, _ptr(ry), r_ptr, s_ptr, p_ptr, d_ptr, n_ptr,
                                                  l_ptr, where_out))
         return r, slope, p, dof, pairs, lag1
+
+    def spectral_maps(self, X, Yc, nperseg, step, weights, detrend_mean, bins, fs, min_segments, alloc=None):
+        """The Welch spectra of the T x N float32 / float64 field `X` (a host array or a `DeviceView`; NaN = missing) over segments of
+        `nperseg` rows every `step` rows with the float64 `weights`, at the distinct `bins`, and its cross-spectra with the q <= 4
+        columns of the CENTRED, finite index plane `Yc` (T x q, or None) (xmca_spectral_maps): a dict with 'power' (F, N) in X's dtype
+        and 'segments' (N,) int32, and with an index 'index_power', 'cospectrum', 'quadrature', 'coherence', 'phase', 'gain' (F, N, q)
+        in X's dtype and 'p' (F, N, q) float64.  alloc: as in `maps` - every output is written on the device.  Resident fields and
+        the result of a solve stay as they are."""
+        keep, ptr, where_in, T, N, st, sn, code, dt = self._regress_field("spectral_maps", X)
+        Y, q = None, 0
+        if Yc is not None:
+            Y = np.ascontiguousarray(Yc, dtype=np.float64)
+            if Y.ndim != 2 or Y.shape[0] != T or not 1 <= Y.shape[1] <= 4:
+                raise ValueError("spectral_maps: the index must be T x q with T = %d and 1 <= q <= 4, got shape %s" % (T, Y.shape))
+            q = Y.shape[1]
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        if w.shape != (int(nperseg),):
+            raise ValueError("spectral_maps: it needs nperseg = %d weights, got shape %s" % (nperseg, w.shape))
+        b = np.ascontiguousarray(bins, dtype=np.int32)
+        if b.ndim != 1 or b.size < 1:
+            raise ValueError("spectral_maps: it needs a bin, got shape %s" % (b.shape,))
+        F = b.size
+        out = {}
+        out['power'], pw_ptr, where_out = _output(alloc, (F, N), dt)
+        out['segments'], sg_ptr, _ = _output(alloc, (N,), np.int32)
+        ptrs = [None] * 7
+        if q:
+            for i, key in enumerate(('index_power', 'cospectrum', 'quadrature', 'coherence', 'phase', 'gain', 'p')):
+                out[key], ptrs[i], _ = _output(alloc, (F, N, q), np.float64 if key == 'p' else dt)
+        self._check(self._lib.xmca_spectral_maps(self._h, ptr, where_in, T, N, st, sn, code, _ptr(Y), q, int(nperseg), int(step), _ptr(w),
+                                                 DETREND_MEAN if detrend_mean else DETREND_NONE, _ptr(b), F, float(fs), int(min_segments),
+                                                 pw_ptr, ptrs[0], ptrs[1], ptrs[2], ptrs[3], ptrs[4], ptrs[5], ptrs[6], sg_ptr, where_out))
+        return out
 
     def reg_mask(self, X):
         """(tests) The mask / widen pass of `column_regress` on a host field (xmca_reg_mask): (mask, wide, missing) - the T x N mask

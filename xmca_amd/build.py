@@ -13,7 +13,7 @@ CSRC = os.path.join(HERE, "csrc")
 REPO = os.path.dirname(HERE)
 LIB = os.path.join(HERE, "libxmca_hip.so")
 SOURCES = ["xmca_hip.cpp"]
-HEADERS = ["boot_patterns.h", "chol64.h","cholesky.h", "column_pass.h", "comm.h", "common.h", "fft.h", "gap_fill.h", "gemm.h", "jacobi.h", "jacobi_kernels.h", "kernels.h", "lag_gram.h", "lag_project.h", "lag_reconstruct.h", "lead_lag.h", "regress.h", "rotate.h", "solver.h", "theta.h", "time_filter.h", "tridiag.h", "tridiag_vec.h"]
+HEADERS = ["boot_patterns.h", "chol64.h","cholesky.h", "column_pass.h", "comm.h", "common.h", "fft.h", "gap_fill.h", "gemm.h", "jacobi.h", "jacobi_kernels.h", "kernels.h", "lag_gram.h", "lag_project.h", "lag_reconstruct.h", "lead_lag.h", "regress.h", "rotate.h", "solver.h", "spectral.h", "theta.h", "time_filter.h", "tridiag.h", "tridiag_vec.h"]
 ARCH = "gfx950"
 
 

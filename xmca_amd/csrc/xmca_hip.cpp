@@ -21,6 +21,7 @@
 #include "regress.h"
 #include "time_filter.h"
 #include "lead_lag.h"
+#include "spectral.h"
 
 using namespace xmca;
 
@@ -2170,6 +2171,89 @@ void lead_lag_impl(xmca_handle* h, const void* X, bool in_device, int T, int64_t
   XMCA_HIP(hipStreamSynchronize(h->st));
 }
 
+// xmca_spectral_maps: the field comes from the host or - through the copy kernels of xmca_set_field_strided - from
+// the caller's device memory into a buffer of this call; the host tables (twiddles, DFT of the weights, effective segments); the
+// centring pass (detrend = mean), the index spectra, the segment kernel into a sums plane of this call, the finish into the
+// caller's device memory or into buffers that are copied to the host.  Every buffer is this call's own.
+template <typename TI>
+void spectral_impl(xmca_handle* h, const void* X, bool in_device, int T, int64_t N, int64_t stride_t, int64_t stride_n, const double* Y, int q, int L,
+                   int step, const double* weights, bool demean, const int* bins, int F, double fs, int min_segments, TI* power_out,
+                   TI* ipower_out, TI* co_out, TI* quad_out, TI* coh_out, TI* phase_out, TI* gain_out, double* p_out, int* seg_out,
+                   bool out_device) {
+  const size_t total = (size_t)T * N;
+  const int K = (T - L) / step + 1;
+  const size_t planes = (size_t)F * N, entries = planes * (size_t)q;
+  std::vector<double> tw, W, Ke;
+  double w2 = 0.0;
+  sp_tables(weights, L, step, bins, F, K, tw, W, &w2, Ke);
+  DevBuf<TI> raw, o_pw, o_ip, o_co, o_qu, o_ch, o_ph, o_ga;
+  DevBuf<double> cn, Yd, twd, wd, Wd, Ked, Ys, ey, sums, rr, pd;
+  DevBuf<int> n0, bd, sg;
+  if (in_device) {
+    h->tm.begin("ingest_strided");
+    ingest_strided<TI>(h->st, static_cast<const TI*>(X), T, N, stride_t, stride_n, raw.ensure(total));
+    XMCA_HIP(hipGetLastError());
+    h->tm.end();
+  } else {
+    XMCA_HIP(hipMemcpyAsync(raw.ensure(total), X, sizeof(TI) * total, hipMemcpyHostToDevice, h->st));
+  }
+  XMCA_HIP(hipMemcpyAsync(twd.ensure(tw.size()), tw.data(), sizeof(double) * tw.size(), hipMemcpyHostToDevice, h->st));
+  XMCA_HIP(hipMemcpyAsync(wd.ensure((size_t)L), weights, sizeof(double) * (size_t)L, hipMemcpyHostToDevice, h->st));
+  XMCA_HIP(hipMemcpyAsync(Wd.ensure(W.size()), W.data(), sizeof(double) * W.size(), hipMemcpyHostToDevice, h->st));
+  XMCA_HIP(hipMemcpyAsync(Ked.ensure(Ke.size()), Ke.data(), sizeof(double) * Ke.size(), hipMemcpyHostToDevice, h->st));
+  XMCA_HIP(hipMemcpyAsync(bd.ensure((size_t)F), bins, sizeof(int) * (size_t)F, hipMemcpyHostToDevice, h->st));
+  const double2* tw_d = reinterpret_cast<const double2*>(twd.get());
+  const double2* W_d = reinterpret_cast<const double2*>(Wd.get());
+  cn.ensure((size_t)N);
+  if (demean) {
+    h->tm.begin("spectral_center");
+    hipLaunchKernelGGL((lead_lag_center_kernel<TI>), dim3((unsigned)ceil_div(N, LL_COLS)), dim3(LL_COLS), 0, h->st, (const TI*)raw.get(), T, N, cn.get(),
+                       n0.ensure((size_t)N));
+    XMCA_HIP(hipGetLastError());
+    h->tm.end();
+  } else {
+    XMCA_HIP(hipMemsetAsync(cn.get(), 0, sizeof(double) * (size_t)N, h->st));
+  }
+  const double2* Y_d = nullptr;
+  if (q > 0) {
+    XMCA_HIP(hipMemcpyAsync(Yd.ensure((size_t)T * q), Y, sizeof(double) * (size_t)T * q, hipMemcpyHostToDevice, h->st));
+    h->tm.begin("spectral_index");
+    spectral_index(h->st, Yd.get(), q, L, step, K, demean ? 1 : 0, tw_d, wd.get(), w2, bd.get(), W_d, F,
+                   reinterpret_cast<double2*>(Ys.ensure(2 * (size_t)K * F * q)), ey.ensure((size_t)K * q));
+    h->tm.end();
+    Y_d = reinterpret_cast<const double2*>(Ys.get());
+  }
+  int* seg = out_device ? seg_out : sg.ensure((size_t)N);
+  h->tm.begin("spectral_segments");
+  spectral_segments<TI>(h->st, raw.get(), N, cn.get(), q, L, step, K, demean ? 1 : 0, tw_d, wd.get(), w2, bd.get(), W_d, F, Y_d,
+                        q > 0 ? ey.get() : nullptr, sums.ensure(planes * (size_t)sp_sums(q)), seg, rr.ensure((size_t)N * (1 + q)));
+  h->tm.end();
+  h->tm.begin("spectral_finish");
+  hipLaunchKernelGGL((spectral_finish_kernel<TI>), ew_grid((int64_t)(planes * (size_t)(q > 0 ? q : 1))), dim3(EW_BLOCK), 0, h->st,
+                     (const double*)sums.get(), (const int*)seg, (const double*)rr.get(), (const double*)Ked.get(), (const int*)bd.get(), N, q, F, L, fs,
+                     w2, min_segments, out_device ? power_out : o_pw.ensure(planes),
+                     q == 0 ? nullptr : (out_device ? ipower_out : o_ip.ensure(entries)), q == 0 ? nullptr : (out_device ? co_out : o_co.ensure(entries)),
+                     q == 0 ? nullptr : (out_device ? quad_out : o_qu.ensure(entries)), q == 0 ? nullptr : (out_device ? coh_out : o_ch.ensure(entries)),
+                     q == 0 ? nullptr : (out_device ? phase_out : o_ph.ensure(entries)), q == 0 ? nullptr : (out_device ? gain_out : o_ga.ensure(entries)),
+                     q == 0 ? nullptr : (out_device ? p_out : pd.ensure(entries)));
+  XMCA_HIP(hipGetLastError());
+  h->tm.end();
+  if (!out_device) {
+    XMCA_HIP(hipMemcpyAsync(power_out, o_pw.get(), sizeof(TI) * planes, hipMemcpyDeviceToHost, h->st));
+    XMCA_HIP(hipMemcpyAsync(seg_out, sg.get(), sizeof(int) * (size_t)N, hipMemcpyDeviceToHost, h->st));
+    if (q > 0) {
+      XMCA_HIP(hipMemcpyAsync(ipower_out, o_ip.get(), sizeof(TI) * entries, hipMemcpyDeviceToHost, h->st));
+      XMCA_HIP(hipMemcpyAsync(co_out, o_co.get(), sizeof(TI) * entries, hipMemcpyDeviceToHost, h->st));
+      XMCA_HIP(hipMemcpyAsync(quad_out, o_qu.get(), sizeof(TI) * entries, hipMemcpyDeviceToHost, h->st));
+      XMCA_HIP(hipMemcpyAsync(coh_out, o_ch.get(), sizeof(TI) * entries, hipMemcpyDeviceToHost, h->st));
+      XMCA_HIP(hipMemcpyAsync(phase_out, o_ph.get(), sizeof(TI) * entries, hipMemcpyDeviceToHost, h->st));
+      XMCA_HIP(hipMemcpyAsync(gain_out, o_ga.get(), sizeof(TI) * entries, hipMemcpyDeviceToHost, h->st));
+      XMCA_HIP(hipMemcpyAsync(p_out, pd.get(), sizeof(double) * entries, hipMemcpyDeviceToHost, h->st));
+    }
+  }
+  XMCA_HIP(hipStreamSynchronize(h->st));
+}
+
 // (tests) xmca_reg_mask: the mask / widen pass alone
 template <typename TI>
 void reg_mask_impl(xmca_handle* h, const TI* X, int64_t total, unsigned char* mask_out, double* wide_out, int64_t* missing_out) {
@@ -3181,6 +3265,73 @@ int xmca_lead_lag_maps(xmca_handle* h, const void* X, int in_location, int64_t T
     using TI = decltype(t);
     lead_lag_impl<TI>(h, X, in_location == XMCA_DEVICE, (int)T, N, stride_t, stride_n, Y, q, lags, n_lags, min_pairs, bretherton, rho_y,
                       static_cast<TI*>(r_out), static_cast<TI*>(slope_out), p_out, dof_out, pairs_out, lag1_out, out_location == XMCA_DEVICE);
+  });
+  API_END(h)
+}
+
+int xmca_spectral_tile(int* cols_out, int* rows_out, int* bin_group_out) {
+  if (!cols_out || !rows_out || !bin_group_out) return XMCA_ERR_INVALID;
+  *cols_out = SP_COLS;
+  *rows_out = SP_ROWS;
+  for (int q = 0; q <= SP_MAX_Q; ++q) bin_group_out[q] = sp_group(q);
+  return XMCA_OK;
+}
+
+int xmca_spectral_maps(xmca_handle* h, const void* X, int in_location, int64_t T, int64_t N, int64_t stride_t, int64_t stride_n, int dtype,
+                       const double* Y, int q, int nperseg, int step, const double* weights, int detrend, const int* bins, int n_bins, double fs,
+                       int min_segments, void* power_out, void* index_power_out, void* cospectrum_out, void* quadrature_out, void* coherence_out,
+                       void* phase_out, void* gain_out, double* p_out, int* segments_out, int out_location) {
+  API_BEGIN(h)
+  const char* what = "spectral_maps";
+  const std::string w(what);
+  const int L = nperseg;
+  XMCA_CHECK(q >= 0 && q <= SP_MAX_Q, XMCA_ERR_INVALID, w + ": between 0 and 4 index series are supported");
+  XMCA_CHECK(T >= 1 && N >= 1, XMCA_ERR_INVALID, w + ": the field must have at least one row and one column");
+  XMCA_CHECK(L >= SP_MIN_L && L <= SP_MAX_L && L <= T, XMCA_ERR_INVALID, w + ": nperseg must lie in [8, 4096] and not exceed T");
+  XMCA_CHECK(step >= (L + 3) / 4 && step <= L, XMCA_ERR_INVALID, w + ": step must lie in [ceil(nperseg / 4), nperseg]");
+  XMCA_CHECK(detrend == XMCA_DETREND_NONE || detrend == XMCA_DETREND_MEAN, XMCA_ERR_INVALID, w + ": detrend must be XMCA_DETREND_NONE or XMCA_DETREND_MEAN");
+  XMCA_CHECK(n_bins >= 1 && n_bins <= L / 2 + 1, XMCA_ERR_INVALID, w + ": between 1 and nperseg / 2 + 1 bins");
+  XMCA_CHECK(std::isfinite(fs) && fs > 0.0, XMCA_ERR_INVALID, w + ": fs must be positive and finite");
+  XMCA_CHECK(min_segments >= 1, XMCA_ERR_INVALID, w + ": min_segments must be at least 1");
+  XMCA_CHECK(dtype == XMCA_F32 || dtype == XMCA_F64, XMCA_ERR_INVALID, w + ": dtype must be XMCA_F32 or XMCA_F64");
+  XMCA_CHECK(stride_t >= 0 && stride_n >= 0, XMCA_ERR_INVALID, w + ": strides must not be negative");
+  XMCA_CHECK(X && weights && bins && power_out && segments_out, XMCA_ERR_INVALID, w + ": bad arguments");
+  XMCA_CHECK(q == 0 || (Y && index_power_out && cospectrum_out && quadrature_out && coherence_out && phase_out && gain_out && p_out), XMCA_ERR_INVALID,
+             w + ": an index needs its series and every one of its maps");
+  XMCA_CHECK(in_location == XMCA_HOST || in_location == XMCA_DEVICE, XMCA_ERR_INVALID, w + ": the location must be XMCA_HOST or XMCA_DEVICE");
+  {
+    std::vector<char> seen((size_t)L / 2 + 1, 0);
+    for (int f = 0; f < n_bins; ++f) {
+      XMCA_CHECK(bins[f] >= 0 && bins[f] <= L / 2, XMCA_ERR_INVALID, w + ": a bin must lie in [0, nperseg / 2]");
+      XMCA_CHECK(!seen[(size_t)bins[f]], XMCA_ERR_INVALID, w + ": the bins must be distinct");
+      seen[(size_t)bins[f]] = 1;
+    }
+  }
+  double w2 = 0.0;
+  for (int i = 0; i < L; ++i) {
+    XMCA_CHECK(std::isfinite(weights[i]), XMCA_ERR_INVALID, w + ": the weights hold a NaN or an Inf");
+    w2 += weights[i] * weights[i];
+  }
+  XMCA_CHECK(w2 > 0.0 && std::isfinite(w2), XMCA_ERR_INVALID, w + ": the sum of the squared weights must be positive and finite");
+  for (int64_t i = 0; i < T * q; ++i) XMCA_CHECK(std::isfinite(Y[i]), XMCA_ERR_INVALID, w + ": the index holds a NaN or an Inf");
+  XMCA_CHECK(N < ((int64_t)1 << 31) && T < ((int64_t)1 << 31) && T * N < ((int64_t)1 << 40) && (int64_t)n_bins * N * sp_sums(q) < ((int64_t)1 << 40),
+             XMCA_ERR_UNSUPPORTED, w + ": field too large");
+  if (in_location == XMCA_DEVICE) check_device_pointer(h, what, X);
+  check_out_location(h, what, out_location, power_out);
+  if (out_location == XMCA_DEVICE) {
+    check_device_pointer(h, what, segments_out);
+    if (q > 0) {
+      for (const void* ptr : {(const void*)index_power_out, (const void*)cospectrum_out, (const void*)quadrature_out, (const void*)coherence_out,
+                              (const void*)phase_out, (const void*)gain_out, (const void*)p_out})
+        check_device_pointer(h, what, ptr);
+    }
+  }
+  with_dtype(dtype, [&](auto t) {
+    using TI = decltype(t);
+    spectral_impl<TI>(h, X, in_location == XMCA_DEVICE, (int)T, N, stride_t, stride_n, Y, q, L, step, weights, detrend == XMCA_DETREND_MEAN, bins,
+                      n_bins, fs, min_segments, static_cast<TI*>(power_out), static_cast<TI*>(index_power_out), static_cast<TI*>(cospectrum_out),
+                      static_cast<TI*>(quadrature_out), static_cast<TI*>(coherence_out), static_cast<TI*>(phase_out), static_cast<TI*>(gain_out), p_out,
+                      segments_out, out_location == XMCA_DEVICE);
   });
   API_END(h)
 }

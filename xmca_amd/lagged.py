@@ -28,8 +28,8 @@ def _ascending_sum(v):
     return s
 
 
-def _check_index(what, index, T):
-    """The index as a (T, q) float64 plane, checked."""
+def _check_index(what, index, T, most=MAX_INDICES):
+    """The index as a (T, q) float64 plane with 1 <= q <= `most`, checked."""
     if _is_tensor(index):
         index = index.detach().cpu().numpy()
     y = np.asarray(index)
@@ -39,8 +39,8 @@ def _check_index(what, index, T):
         y = y[:, None]
     if y.ndim != 2 or y.shape[0] != T:
         raise ValueError("%s: the index must have shape (T,) or (T, q) with T = %d time steps, got %s" % (what, T, np.shape(index)))
-    if not 1 <= y.shape[1] <= MAX_INDICES:
-        raise ValueError("%s: between 1 and %d index series are supported, got %d" % (what, MAX_INDICES, y.shape[1]))
+    if not 1 <= y.shape[1] <= most:
+        raise ValueError("%s: between 1 and %d index series are supported, got %d" % (what, most, y.shape[1]))
     y = np.ascontiguousarray(y, dtype=np.float64)
     if not np.isfinite(y).all():
         raise ValueError("%s: the index holds a NaN or an Inf (an index with gaps is not supported)" % what)

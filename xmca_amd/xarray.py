@@ -13,6 +13,7 @@ import numpy as np
 from . import gaps as _gaps
 from . import lagged as _lagged
 from . import prepare as _prepare
+from . import spectral as _spectral
 from .array import MCA, secure_str
 
 
@@ -428,6 +429,40 @@ def lead_lag_maps(da, index, lags, min_pairs=8, dof='n', handle=None):
     if 'lag1' in out:
         out['lag1'] = xr.DataArray(out['lag1'], dims=spatial, coords=along(spatial), name='lag1')
     out['lags'] = xr.DataArray(out['lags'], dims=('lag',), coords={'lag': out['lags'].copy()}, name='lags')
+    return out
+
+
+def spectral_maps(da, index=None, nperseg=256, step=None, window='hann', detrend='mean', bins=None, fs=1.0, min_segments=2, handle=None):
+    """`xmca_amd.spectral.spectral_maps` of a DataArray whose first dimension is time: the same dict as DataArrays - 'power' over
+    ('frequency',) + the spatial dims, 'index_power', 'cospectrum', 'quadrature', 'coherence', 'phase', 'gain' and 'p' over
+    ('frequency',) + the spatial dims + ('index',), 'segments' over the spatial dims, 'freqs' and 'bins' over ('frequency',) - with
+    'freqs' as the 'frequency' coordinate and those coordinates of `da` that lie along the spatial dims.  `index` may be a DataArray
+    over the time dim (and one more dim for several series)."""
+    xr = _xr()
+    if not isinstance(da, xr.DataArray):
+        raise TypeError("spectral_maps: the field is not an `xarray.DataArray`")
+    if isinstance(index, xr.DataArray):
+        index = index.values
+    out = _spectral.spectral_maps(da.values, index, nperseg=nperseg, step=step, window=window, detrend=detrend, bins=bins, fs=fs,
+                                  min_segments=min_segments, handle=handle)
+    spatial = tuple(da.dims[1:])
+    freqs = out['freqs']
+
+    def along(dims):
+        coords = {name: c for name, c in dict(da.coords).items() if getattr(c, 'dims', ()) and set(c.dims) <= set(spatial)}
+        if 'frequency' in dims:
+            coords['frequency'] = freqs.copy()
+        if 'index' in dims:
+            coords['index'] = np.arange(out['coherence'].shape[-1])
+        return coords
+    full = ('frequency',) + spatial + ('index',)
+    for key in ('index_power', 'cospectrum', 'quadrature', 'coherence', 'phase', 'gain', 'p'):
+        if key in out:
+            out[key] = xr.DataArray(out[key], dims=full, coords=along(full), name=key)
+    out['power'] = xr.DataArray(out['power'], dims=('frequency',) + spatial, coords=along(('frequency',) + spatial), name='power')
+    out['segments'] = xr.DataArray(out['segments'], dims=spatial, coords=along(spatial), name='segments')
+    for key in ('freqs', 'bins'):
+        out[key] = xr.DataArray(out[key], dims=('frequency',), coords={'frequency': freqs.copy()}, name=key)
     return out
 
 
